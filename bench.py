@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Headline benchmark: EI candidates scored per second at N = 2048 observations, d = 32 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--candidates M_PER_GPU] [--workload metric|cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--candidates M_PER_GPU] [--workload metric|cfg2|cfg3|cfg4|cfg5|default]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -23,6 +24,14 @@ first of 2^20 ties.  Starting the pool at point 2 keeps every other property of 
 interior of the grid that the CPU leg re-derives.  Rank r owns candidate rows [r*M, (r+1)*M): it generates the contiguous pool range that holds them and
 deletes the observation rows inside it (b7_grid_remove_rows).  Y = the reference's objective restated on the host
 (harness/benchmarks.py); hypers lenscale_sq = d/8, amp = var(Y), mean = mean(Y), noise = 1e-4*amp.
+
+A plain run sets up, warms up, times --steps steps (HIP events around every kernel phase, as the phases and rooflines of the line
+are read from them) and prints one JSON line; `value` and `ms_per_step` come from those steps.  --full adds what takes runs of its
+own: the same steps without the phase events, the S = 10 leg, GP-fit timings by N, the CPU baseline and the oracle's check of
+the winner, and for the metric workload the other BASELINE configurations and the default regime.  --dump-outputs DIR writes
+what the last timed step computed: the winner (best_value, best_index1) and the scores score:div left over the candidates
+(scores; when they do not fit in 64 MB a fixed, seeded sample, with scores_index1), or for --workload default the last
+experiment's nominees, observations, responses and hyper draws.
 """
 import argparse
 import gc
@@ -54,6 +63,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md
 SOBOL_SKIP = 2                 # config.skip of the pool: see "Inputs" above
 PMC_SUMMARIES = ("r04_pmc_summary.json", "r03_pmc_summary.json", "r02_pmc_summary.json", "r01z_pmc_summary.json")  # newest first
 KSX_PMC_BY_CLASS = "r04_ksx_pmc_by_class.json"   # instruction counts of ksx_kernel per width class (tools/ksx_pmc.sh; covar.hip unchanged since round 3)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: all files of all processes together (each process gets its share)
+NPY_HEADER_BYTES = 128            # what np.save puts in front of the data of a 1-D or 2-D float64 array
 
 
 def parse():
@@ -80,6 +91,13 @@ def parse():
     ap.add_argument("--virtual-ranks", action="store_true",
                     help="group layout on fewer than N devices: members share device 0 (rehearsal on a one-GPU box; RCCL refuses "
                          "that, the exchange is merged on the host unless the diagnostic build + test double force the grouped call)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the second timed pass without phase events, the S = 10 leg, the GP-fit "
+                         "timings, the CPU baseline and the oracle's check of the winner, the other BASELINE configurations and the "
+                         "default regime (--workload default: its per-kernel figures and the oracle-driven loop).  Off: set up, "
+                         "warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, 64 MB at most)")
     return ap.parse_args()
 
 
@@ -177,13 +195,55 @@ def pmc_traffic(rows_per_launch, N):
     return None, None
 
 
+def dump_bytes(arrays):
+    """Bytes the .npy files of `arrays` take (data + header)."""
+    return sum(np.asarray(a).size * 8 + NPY_HEADER_BYTES for a in arrays.values())
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: one float64 .npy per array under out_dir, `limit` bytes at most in all (this process's share of
+    DUMP_LIMIT_BYTES when several processes write into the same directory)."""
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = dump_bytes(arrays)
+    if total > limit:
+        raise ValueError("--dump-outputs: %d bytes exceed the limit of %d" % (total, limit))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def nomination_outputs(ctx, best, suffix="", limit=DUMP_LIMIT_BYTES):
+    """What a nomination step computed: the winner it hands back (value, 1-based global index) and the scores that score:div left
+    on the device over this process's candidates (bots/bayesopt.lua's score tensor).  Dividing them by 1.0 again reads them back
+    unchanged.  All of them when they fit in `limit` bytes beside the winner; otherwise a fixed, seeded sample of the rows, as
+    many as fit together with their 1-based local indices (scores_index1: 16 bytes a row)."""
+    out = {"best_value" + suffix: [best[0]], "best_index1" + suffix: [best[1]]}
+    room = limit - dump_bytes(out)
+    M = ctx.grid_shape()[0]
+    if M > 0:
+        _, _, scores = ctx.score_finish(1.0, download=True)
+        if M * 8 + NPY_HEADER_BYTES > room:
+            rows = np.sort(np.random.default_rng(0).choice(M, (room - 2 * NPY_HEADER_BYTES) // 16, replace=False))
+            out["scores_index1" + suffix] = rows + 1
+            scores = scores[rows]
+        out["scores" + suffix] = scores
+    return out
+
+
+def experiment_outputs(g):
+    """What one experiment of --workload default hands back: the nominee of every trial, the observations and responses, the
+    hyper draws of every model-based trial, the best response."""
+    return {"nominees": g["nominees"], "X": g["X"], "Y": g["Y"], "hyper_draws": np.concatenate(g["draws"], axis=0),
+            "best_y": [g["best"]["y"]]}
+
+
 def run_default(args, ctx=None, emit=True, cpu_seconds=None):
     """bench.py --workload default: the reference's own default experiment as a whole trial loop (harness/default_regime.py):
     hartmann6, d = 6, 2e4 Sobol candidates, budget 100 (N <= 100), nInitial 2, nSamples 10 slice-sampled hyper vectors per
     nomination, EI.  One step = one experiment; `value` = trials/s over the whole experiments (objective evaluations, a closed
     form, included).  cpu_baseline = the oracle driving the SAME loop (same host code, seeds and random streams) on the host
     cores: its nominee sequence is the parity check of the GPU run.  One GPU only (the regime is latency-bound; sharding
-    2e4 candidates is exercised by the tests, not timed here)."""
+    2e4 candidates is exercised by the tests, not timed here).  The per-kernel figures and the cpu_baseline leg run with --full."""
     import bot7_amd
     from harness import default_regime as dr
     d, N, M, obj_name, score = WORKLOADS["default"]
@@ -209,66 +269,13 @@ def run_default(args, ctx=None, emit=True, cpu_seconds=None):
     for r in runs[1:]:
         assert r["nominees"] == runs[0]["nominees"], "two identical experiments nominated different candidates"
     g = runs[-1]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, experiment_outputs(g))
     per_trial = [dict(r) for r in g["per_trial"]]
     for k in ("sampler_ms", "nominate_ms", "commit_ms", "trial_ms"):   # the mean over the timed experiments, trial by trial
         for i, r in enumerate(per_trial):
             r[k] = float(np.mean([run["per_trial"][i][k] for run in runs]))
     split = dr.summarise(per_trial)
-
-    # ---- kernel durations of the regime, HIP events on the context's stream (the phase timers of the library): the likelihood
-    # kernel (one launch per density evaluation: what a trial is made of) and the nomination's kernels at the last trial's N
-    Xo, Yo = g["X"], g["Y"]
-    hyp = {"lenscale_sq": np.full(d, d / 8.0), "amp": float(np.var(Yo)), "noise": 1e-4 * float(np.var(Yo)), "mean": float(np.mean(Yo))}
-    ctx.grid_sobol(M, d, 1, download=False)
-    kern = {}
-    for n_obs in sorted({min(25, len(Xo)), min(64, len(Xo)), len(Xo)}):
-        ctx.gp_set_data(Xo[:n_obs], Yo[:n_obs])
-        for _ in range(5):
-            ctx.gp_nll_batch(hyp["lenscale_sq"], hyp["amp"], hyp["noise"], hyp["mean"])
-        t0 = time.perf_counter()
-        reps = 200
-        for _ in range(reps):
-            ctx.gp_nll_batch(hyp["lenscale_sq"], hyp["amp"], hyp["noise"], hyp["mean"])
-        call_us = (time.perf_counter() - t0) / reps * 1e6
-        ctx.profile_enable(True)
-        ctx.profile_reset()
-        for _ in range(50):
-            ctx.gp_nll_batch(hyp["lenscale_sq"], hyp["amp"], hyp["noise"], hyp["mean"])
-        nll_ms, nll_n = ctx.profile_get("potrf")
-        ctx.profile_reset()
-        hyps = [dict(hyp, lenscale_sq=hyp["lenscale_sq"] * (1.0 + 0.05 * s_i)) for s_i in range(10)]
-        spec = {"score": "ei", "fmin": [float(Yo[:n_obs].min())], "tradeoff": 0.0}
-        for _ in range(20):
-            ctx.eval_nominate(hyps, **spec)
-        ph = {}
-        for name in ("prep", "kxx", "potrf", "alpha", "ksx", "post", "kpost", "score", "argmax"):
-            ms, cnt = ctx.profile_get(name)
-            if cnt:
-                ph[name] = round(ms / 20 * 1e3, 2)     # us per nomination
-        ctx.profile_enable(False)
-        ctx.profile_reset()
-        for _ in range(5):
-            ctx.eval_nominate(hyps, **spec)
-        t0 = time.perf_counter()
-        for _ in range(100):
-            ctx.eval_nominate(hyps, **spec)
-        nom_us = (time.perf_counter() - t0) / 100 * 1e6
-        kern[str(n_obs)] = {"nll_call_us": round(call_us, 2), "nll_kernel_us": round(nll_ms / max(1, nll_n) * 1e3, 2),
-                            "nominate_call_us": round(nom_us, 1), "nominate_phase_us": ph}
-    n_last = str(len(Xo))
-    # roofline of the kernel a trial spends most of its time in -- the one-workgroup likelihood (K + Cholesky + solve of one
-    # hyper vector): algorithmic flops N^3/3 (factor) + N^2 (2 d + 1) (K, solve) against the fp64-MFMA peak.  It is a dependent
-    # chain on ONE CU: the fraction says how far a latency-bound kernel is from a throughput roofline, nothing more.
-    nn = float(len(Xo))
-    nll_flops = nn ** 3 / 3.0 + nn * nn * (2.0 * d + 1.0)
-    nll_t = kern[n_last]["nll_kernel_us"] * 1e-6
-    post_us = kern[n_last]["nominate_phase_us"].get("kpost") or kern[n_last]["nominate_phase_us"].get("post")
-    post_flops = 10.0 * M * nn * nn
-    nt = -(-len(Xo) // 16)
-    chain_us = nt * 3925 / GPU_CLOCK_HZ * 1e6
-    dpad = 4 if d <= 4 else 8 if d <= 8 else 16 if d <= 16 else 32
-    strip_cycles = 64.0 * (nt * max(1, dpad // 4) + 2 * nt * (nt + 1)) + 64 * nt * 4.8
-    pipe_us = 10 * -(-M // 16) * strip_cycles / (1024 * GPU_CLOCK_HZ) * 1e6
     line = {
         "metric": "BO trials/sec at the reference's default regime (hartmann6 d=6, 2e4 Sobol candidates, nSamples=10, budget %d)" % budget,
         "value": args.steps * budget / elapsed, "unit": "trials/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -282,31 +289,11 @@ def run_default(args, ctx=None, emit=True, cpu_seconds=None):
                    "d": d, "budget": budget, "candidates": M, "nSamples": 10, "score": "ei",
                    "parallelism": "one GPU, one context (the regime is latency-bound)", "device": info["name"]},
         "ms_per_trial": split,
-        "kernels_by_N": kern,
-        "roofline": {"bound": "dependent chain",
-                     "kernel": "gp_small_kernel<0> (one density evaluation of the slice sampler: K + Cholesky + solve in one "
-                               "workgroup; ~%d launches per trial)" % round(split.get("nll_calls", 0) / max(1, split.get("model_based_trials", 1))),
-                     "floor_us": chain_us, "frac_of_floor": chain_us * 1e-6 / nll_t if nll_t > 0 else None,
-                     "achieved": nll_flops / nll_t / 1e12 if nll_t > 0 else None, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": nll_flops / nll_t / 1e12 / FP64_MFMA_PEAK_TFLOPS if nll_t > 0 else None, "traffic": None,
-                     "flops_per_launch": nll_flops, "avg_launch_ms": nll_t * 1e3,
-                     "note": "one workgroup on one CU; floor_us = the ceil(N/16) pivot chains of the two 64-column factor routines alone "
-                             "(3 925 cycles per 16 columns: sixteen dependent {rsqrt, scale, rank-1} steps on one wave; stamps in "
-                             "profiles/r04_gp_small_stamps.txt); frac against the MFMA peak is tiny by construction and kept only "
-                             "because the contract asks for it"},
-        "roofline_nominate": {"bound": "fp64 pipe (MFMA+VALU)",
-                              "kernel": "kpost_small_kernel (K*, mean and variance of the S = 10 fits over the grid at N = %s, K* never stored)" % n_last,
-                              "achieved": post_flops / (post_us * 1e-6) / 1e12 if post_us else None, "peak": FP64_MFMA_PEAK_TFLOPS,
-                              "unit": "TFLOP/s", "frac": post_flops / (post_us * 1e-6) / 1e12 / FP64_MFMA_PEAK_TFLOPS if post_us else None,
-                              "pipe_us": pipe_us, "frac_of_pipe": pipe_us / post_us if post_us else None,
-                              "traffic": None, "flops_per_launch": post_flops, "avg_launch_ms": post_us * 1e-3 if post_us else None,
-                              "note": "pipe_us = what the one fp64 pipe per SIMD needs for the kernel's instructions: per 16-candidate "
-                                      "strip NT dpad/4 + 2 NT (NT + 1) MFMAs of 64 cycles (NT = ceil(N/16): distances, then the lower "
-                                      "triangle of L^-1 against the K* tile) and 64 NT exponential instructions of 4.8 cycles, over "
-                                      "1 024 SIMDs at 2.4 GHz; avg_launch_ms is the library's phase timer (events around the launch)"},
         "best": g["best"], "nominees_first_10": g["nominees"][:10],
     }
-    if not args.no_cpu_baseline:
+    if args.full:
+        line.update(default_kernel_figures(ctx, g, split))
+    if args.full and not args.no_cpu_baseline:
         from oracle.hostctx import OracleContext
         cores = usable_cores()
         try:
@@ -370,11 +357,95 @@ def run_default(args, ctx=None, emit=True, cpu_seconds=None):
     return line
 
 
+def default_kernel_figures(ctx, g, split):
+    """bench.py --workload default --full: kernel durations of the regime, HIP events on the context's stream (the phase timers of the
+    library): the likelihood kernel (one launch per density evaluation: what a trial is made of) and the nomination's kernels at
+    the last trial's N, each against its roofline.  Runs of their own after the timed experiments."""
+    d, M = WORKLOADS["default"][0], WORKLOADS["default"][2]
+    Xo, Yo = g["X"], g["Y"]
+    hyp = {"lenscale_sq": np.full(d, d / 8.0), "amp": float(np.var(Yo)), "noise": 1e-4 * float(np.var(Yo)), "mean": float(np.mean(Yo))}
+    ctx.grid_sobol(M, d, 1, download=False)
+    kern = {}
+    for n_obs in sorted({min(25, len(Xo)), min(64, len(Xo)), len(Xo)}):
+        ctx.gp_set_data(Xo[:n_obs], Yo[:n_obs])
+        for _ in range(5):
+            ctx.gp_nll_batch(hyp["lenscale_sq"], hyp["amp"], hyp["noise"], hyp["mean"])
+        t0 = time.perf_counter()
+        reps = 200
+        for _ in range(reps):
+            ctx.gp_nll_batch(hyp["lenscale_sq"], hyp["amp"], hyp["noise"], hyp["mean"])
+        call_us = (time.perf_counter() - t0) / reps * 1e6
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        for _ in range(50):
+            ctx.gp_nll_batch(hyp["lenscale_sq"], hyp["amp"], hyp["noise"], hyp["mean"])
+        nll_ms, nll_n = ctx.profile_get("potrf")
+        ctx.profile_reset()
+        hyps = [dict(hyp, lenscale_sq=hyp["lenscale_sq"] * (1.0 + 0.05 * s_i)) for s_i in range(10)]
+        spec = {"score": "ei", "fmin": [float(Yo[:n_obs].min())], "tradeoff": 0.0}
+        for _ in range(20):
+            ctx.eval_nominate(hyps, **spec)
+        ph = {}
+        for name in ("prep", "kxx", "potrf", "alpha", "ksx", "post", "kpost", "score", "argmax"):
+            ms, cnt = ctx.profile_get(name)
+            if cnt:
+                ph[name] = round(ms / 20 * 1e3, 2)     # us per nomination
+        ctx.profile_enable(False)
+        ctx.profile_reset()
+        for _ in range(5):
+            ctx.eval_nominate(hyps, **spec)
+        t0 = time.perf_counter()
+        for _ in range(100):
+            ctx.eval_nominate(hyps, **spec)
+        nom_us = (time.perf_counter() - t0) / 100 * 1e6
+        kern[str(n_obs)] = {"nll_call_us": round(call_us, 2), "nll_kernel_us": round(nll_ms / max(1, nll_n) * 1e3, 2),
+                            "nominate_call_us": round(nom_us, 1), "nominate_phase_us": ph}
+    n_last = str(len(Xo))
+    # roofline of the kernel a trial spends most of its time in -- the one-workgroup likelihood (K + Cholesky + solve of one
+    # hyper vector): algorithmic flops N^3/3 (factor) + N^2 (2 d + 1) (K, solve) against the fp64-MFMA peak.  It is a dependent
+    # chain on ONE CU: the fraction says how far a latency-bound kernel is from a throughput roofline, nothing more.
+    nn = float(len(Xo))
+    nll_flops = nn ** 3 / 3.0 + nn * nn * (2.0 * d + 1.0)
+    nll_t = kern[n_last]["nll_kernel_us"] * 1e-6
+    post_us = kern[n_last]["nominate_phase_us"].get("kpost") or kern[n_last]["nominate_phase_us"].get("post")
+    post_flops = 10.0 * M * nn * nn
+    nt = -(-len(Xo) // 16)
+    chain_us = nt * 3925 / GPU_CLOCK_HZ * 1e6
+    dpad = 4 if d <= 4 else 8 if d <= 8 else 16 if d <= 16 else 32
+    strip_cycles = 64.0 * (nt * max(1, dpad // 4) + 2 * nt * (nt + 1)) + 64 * nt * 4.8
+    pipe_us = 10 * -(-M // 16) * strip_cycles / (1024 * GPU_CLOCK_HZ) * 1e6
+    return {
+        "kernels_by_N": kern,
+        "roofline": {"bound": "dependent chain",
+                     "kernel": "gp_small_kernel<0> (one density evaluation of the slice sampler: K + Cholesky + solve in one "
+                               "workgroup; ~%d launches per trial)" % round(split.get("nll_calls", 0) / max(1, split.get("model_based_trials", 1))),
+                     "floor_us": chain_us, "frac_of_floor": chain_us * 1e-6 / nll_t if nll_t > 0 else None,
+                     "achieved": nll_flops / nll_t / 1e12 if nll_t > 0 else None, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": nll_flops / nll_t / 1e12 / FP64_MFMA_PEAK_TFLOPS if nll_t > 0 else None, "traffic": None,
+                     "flops_per_launch": nll_flops, "avg_launch_ms": nll_t * 1e3,
+                     "note": "one workgroup on one CU; floor_us = the ceil(N/16) pivot chains of the two 64-column factor routines alone "
+                             "(3 925 cycles per 16 columns: sixteen dependent {rsqrt, scale, rank-1} steps on one wave; stamps in "
+                             "profiles/r04_gp_small_stamps.txt); frac against the MFMA peak is tiny by construction and kept only "
+                             "because the contract asks for it"},
+        "roofline_nominate": {"bound": "fp64 pipe (MFMA+VALU)",
+                              "kernel": "kpost_small_kernel (K*, mean and variance of the S = 10 fits over the grid at N = %s, K* never stored)" % n_last,
+                              "achieved": post_flops / (post_us * 1e-6) / 1e12 if post_us else None, "peak": FP64_MFMA_PEAK_TFLOPS,
+                              "unit": "TFLOP/s", "frac": post_flops / (post_us * 1e-6) / 1e12 / FP64_MFMA_PEAK_TFLOPS if post_us else None,
+                              "pipe_us": pipe_us, "frac_of_pipe": pipe_us / post_us if post_us else None,
+                              "traffic": None, "flops_per_launch": post_flops, "avg_launch_ms": post_us * 1e-3 if post_us else None,
+                              "note": "pipe_us = what the one fp64 pipe per SIMD needs for the kernel's instructions: per 16-candidate "
+                                      "strip NT dpad/4 + 2 NT (NT + 1) MFMAs of 64 cycles (NT = ceil(N/16): distances, then the lower "
+                                      "triangle of L^-1 against the K* tile) and 64 NT exponential instructions of 4.8 cycles, over "
+                                      "1 024 SIMDs at 2.4 GHz; avg_launch_ms is the library's phase timer (events around the launch)"},
+    }
+
+
 def run_group(args):
     """python bench.py --gpus N with no launcher: ONE process drives N GPUs (b7_group_*), the layout the reference itself has
     (one LuaJIT process, bots/abstract.lua:155-169).  Candidates are sharded over the members by contiguous row ranges, the fit
     is replicated, every member's work is enqueued without a host wait in between, and the winners are combined by ONE grouped
-    ncclAllReduce (ncclCommInitAll) when the devices are distinct.  Weak scaling: --candidates rows per GPU."""
+    ncclAllReduce (ncclCommInitAll) when the devices are distinct.  Weak scaling: --candidates rows per GPU.  The K steps are timed
+    twice with or without --full (member 0's phase events on, then off): with virtual ranks `value` comes from the second pass."""
     import bot7_amd
     from harness import benchmarks
     d, N, M_default, obj_name, score = WORKLOADS[args.workload]
@@ -444,6 +515,8 @@ def run_group(args):
     m0.profile_reset()
     elapsed, best = timed(args.steps)
     m0.profile_enable(False)
+    if args.dump_outputs:   # what b7_group_eval_nominate hands back: the winner
+        dump_outputs(args.dump_outputs, {"best_value": [best[0]], "best_index1": [best[1]]})
     elapsed_plain, best_plain = timed(args.steps)
     assert best_plain == best
     shared = len(set(devices)) < G
@@ -649,10 +722,15 @@ def main():
         ctx.profile_reset()
         elapsed, best = timed(args.steps, args.samples)
         ctx.profile_enable(False)
-        # the same K steps once more without the per-phase HIP events: at the small configurations the event records
-        # themselves (two per phase, ~16 per step) are a third of the step; at the headline size they are 0.1 %
-        elapsed_plain, best_plain = timed(args.steps, args.samples)
-        assert best_plain == best, "the nomination changed between two identical passes"
+        if args.dump_outputs:
+            share = DUMP_LIMIT_BYTES // world      # every rank writes its own files into the same directory
+            dump_outputs(args.dump_outputs, nomination_outputs(ctx, best, "" if world == 1 else "_rank%d" % rank, share), share)
+        elapsed_plain = None
+        if args.full:
+            # the same K steps once more without the per-phase HIP events: at the small configurations the event records
+            # themselves (two per phase, ~16 per step) are a third of the step; at the headline size they are 0.1 %
+            elapsed_plain, best_plain = timed(args.steps, args.samples)
+            assert best_plain == best, "the nomination changed between two identical passes"
 
         phases = {}
         for ph in ("prep", "kxx", "potrf", "trtri", "alpha", "basis", "mean", "ksx", "post", "kpost", "score", "argmax", "exchange"):
@@ -746,7 +824,6 @@ def main():
             "unit": "candidates/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_without_phase_events": elapsed_plain / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": "%s: %s d=%d, N=%d obs (strided pick from the pool, SURVEY 8d), %d %s candidates per "
@@ -783,8 +860,11 @@ def main():
                         ("b7_eval_nominate (one call, one host synchronisation per step)" if ctx.comm_info()[1] == world
                          else "b7_gp_predict_hyp + b7_score_* per sample, gloo exchange"),
         }
+        if elapsed_plain is not None:
+            line["ms_per_step_without_phase_events"] = elapsed_plain / args.steps * 1e3
 
-        extras = not args.no_extras and obj_name != "dngo"
+        extras = args.full and not args.no_extras and obj_name != "dngo"
+        cpu_leg = args.full and not args.no_cpu_baseline
         # ---- the reference-faithful S = 10 marginalisation loop (bots/abstract.lua:67), beside the S = 1 headline
         if extras and args.samples == 1:
             S = 10
@@ -827,7 +907,7 @@ def main():
         # ---- CPU baseline on a bounded sample, and the arg-max check against it.  The sample is the window of rows around the
         # GPU's GLOBAL winner, so the headline arg-max itself is what the oracle re-derives (the first rows of the
         # grid hold one dominant candidate and say nothing about the winner).
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and obj_name != "dngo":
+        if rank == 0 and world == 1 and cpu_leg and obj_name != "dngo":
             sample = min(args.cpu_sample, M)
 
             def window_of(idx1, rows):
@@ -876,7 +956,7 @@ def main():
                 print(json.dumps(line))
                 sys.exit("the oracle does not confirm the GPU's arg-max: S=1 window %r, S=10 %r"
                          % (line["best_in_cpu_sample"], line.get("marginalised", {}).get("cpu_check")))
-        elif rank == 0 and world == 1 and not args.no_cpu_baseline and obj_name == "dngo":
+        elif rank == 0 and world == 1 and cpu_leg and obj_name == "dngo":
             # config 5: the head and the acquisition re-derived by the oracle (oracle/blr.py: parity unpinned) on the window of rows
             # around the GPU's winner
             from oracle import blr, cport
@@ -901,14 +981,15 @@ def main():
         return line
 
     line = measure(args)
-    # ---- the other BASELINE configurations, compactly, behind the headline (one GPU, the default run only): the same
+    # ---- the other BASELINE configurations, compactly, behind the headline (one GPU, the metric workload with --full): the same
     # measurement at few steps, a bounded oracle window around each winner
-    if rank == 0 and world == 1 and args.workload == "metric" and not args.no_extras and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.workload == "metric" and args.full and not args.no_extras and not args.no_cpu_baseline:
         import copy
         line["configs"] = {}
         for name in ("cfg2", "cfg3", "cfg4", "cfg5"):
             a2 = copy.copy(args)
             a2.workload, a2.candidates, a2.steps, a2.warmup, a2.samples, a2.no_extras, a2.cpu_sample = name, 0, 5, 1, 1, True, 8192
+            a2.dump_outputs = None
             if name in ("cfg2", "cfg5"):
                 a2.steps, a2.warmup = 20, 3        # a quarter of a millisecond per step
             l2 = measure(a2)
@@ -929,7 +1010,7 @@ def main():
         # ---- and the reference's OWN default experiment (--workload default), compactly: one timed experiment of 100 trials, the
         # oracle behind the same driver for a few seconds (its first ~40 trials: the nominee sequence is the parity check)
         a3 = copy.copy(args)
-        a3.steps, a3.warmup, a3.no_cpu_baseline = 1, 1, False
+        a3.steps, a3.warmup, a3.no_cpu_baseline, a3.dump_outputs = 1, 1, False, None
         with quiet_stdout():
             l3 = run_default(a3, ctx=ctx, emit=False, cpu_seconds=4.0)
         last = sorted(l3["kernels_by_N"], key=int)[-1]

@@ -321,3 +321,64 @@ def test_density_memo_follows_the_data_and_the_point():
     m.hyp = m.parse_hypers(v1)
     m.sample_hypers(X2, Y2, None, None, True)                                     # starts from log(exp(.)) of v1 again: fine, just not the memo
     assert np.all(np.isfinite(m._chain_state[0])) and kept.shape == m._chain_state[0].shape
+
+
+def test_bench_dump_outputs_on_the_host(tmp_path):
+    """bench.py --dump-outputs: float64 arrays; the scores whole when they fit, else a fixed, seeded sample with its 1-based rows,
+    sized so that the files of the whole dump stay within DUMP_LIMIT_BYTES -- at the default limit, and for every rank's share
+    when several ranks write; nothing is written over the limit; the default workload's experiment record."""
+    import bench
+
+    class Ctx(object):
+        def __init__(self, scores):
+            self.scores = scores
+
+        def grid_shape(self):
+            return self.scores.shape[0], 3
+
+        def score_finish(self, divisor=1.0, download=False):
+            return None, None, self.scores / divisor
+
+    def files_bytes(d):
+        return sum(os.path.getsize(os.path.join(str(d), f)) for f in os.listdir(str(d)))
+
+    rng = np.random.default_rng(1)
+    small = rng.random(1000)
+    whole = bench.nomination_outputs(Ctx(small), (0.5, 7))
+    assert np.array_equal(whole["scores"], small) and "scores_index1" not in whole and whole["best_index1"] == [7]
+    # more rows than the default limit holds (one more than fit whole): the sampled branch must produce a dump that is accepted
+    fit_whole = (bench.DUMP_LIMIT_BYTES - 3 * bench.NPY_HEADER_BYTES - 16) // 8
+    for M, world in ((fit_whole, 1), (fit_whole + 1, 1), (1 << 20, 8), (5 << 20, 2)):
+        scores = rng.random(M)
+        share = bench.DUMP_LIMIT_BYTES // world
+        a = bench.nomination_outputs(Ctx(scores), (0.5, 7), "_rank0" if world > 1 else "", share)
+        b = bench.nomination_outputs(Ctx(scores), (0.5, 7), "_rank0" if world > 1 else "", share)
+        sfx = "_rank0" if world > 1 else ""
+        sampled = "scores_index1" + sfx in a
+        assert sampled == (M > fit_whole or world > 1), (M, world)
+        if sampled:
+            idx = a["scores_index1" + sfx]
+            assert np.array_equal(idx, b["scores_index1" + sfx]) and np.all(np.diff(idx) > 0) and idx[0] >= 1 and idx[-1] <= M
+            assert np.array_equal(a["scores" + sfx], scores[idx - 1])
+            assert len(idx) > (share - 1024) // 16, "the sample leaves room unused"
+        else:
+            assert np.array_equal(a["scores"], scores)
+        out = tmp_path / ("m%d_w%d" % (M, world))
+        bench.dump_outputs(str(out), a, share)
+        assert files_bytes(out) <= share and files_bytes(out) == bench.dump_bytes(a), (M, world)
+        for name, want in a.items():
+            got = np.load(str(out / (name + ".npy")))
+            assert got.dtype == np.float64 and np.array_equal(got, np.asarray(want, dtype=np.float64)), name
+        assert world * share <= bench.DUMP_LIMIT_BYTES
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "over"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8)})
+    assert not (tmp_path / "over").exists()
+    # --workload default: one experiment's record as harness/default_regime.run returns it
+    g = {"nominees": [5, 17, 3], "X": rng.random((3, 6)), "Y": rng.random((3, 1)), "best": {"t": 2, "y": -1.5},
+         "draws": [np.zeros((0, 9)), rng.random((10, 9)), rng.random((10, 9))]}
+    e = bench.experiment_outputs(g)
+    bench.dump_outputs(str(tmp_path / "default"), e)
+    got = {n: np.load(str(tmp_path / "default" / (n + ".npy"))) for n in e}
+    assert got["nominees"].tolist() == [5.0, 17.0, 3.0] and got["X"].shape == (3, 6) and got["Y"].shape == (3, 1)
+    assert got["hyper_draws"].shape == (20, 9) and np.array_equal(got["hyper_draws"][10:], g["draws"][2])
+    assert got["best_y"].tolist() == [-1.5] and all(v.dtype == np.float64 for v in got.values())

@@ -7,15 +7,15 @@ TAG=${1:-r02}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 20 --warmup 5 > $OUT/bench_metric.json 2> $OUT/bench_metric.err || exit 1
+python3 $R/bench.py --steps 20 --warmup 5 --full > $OUT/bench_metric.json 2> $OUT/bench_metric.err || exit 1
 echo "metric done"
 : > $OUT/bench_other_configs.jsonl
 for w in cfg2 cfg3 cfg4 cfg5; do
   sleep 3   # the previous process freed tens of GB: let the driver finish before a sub-millisecond workload is timed
-  python3 $R/bench.py --workload $w --steps 20 --warmup 5 >> $OUT/bench_other_configs.jsonl 2> $OUT/bench_$w.err || echo "$w failed"
+  python3 $R/bench.py --workload $w --steps 20 --warmup 5 --full >> $OUT/bench_other_configs.jsonl 2> $OUT/bench_$w.err || echo "$w failed"
 done
 echo "configs done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-extras \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-extras --full \
   > $OUT/bench_under_rocprof.json 2> $OUT/trace.err || echo "trace failed"
 for ctrs in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES"; do
   n=$(echo $ctrs | tr ' ' '_')

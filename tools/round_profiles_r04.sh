@@ -8,9 +8,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/r04p
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --workload default --steps 3 --warmup 1 > $OUT/default_regime.json 2> $OUT/default_regime.err || echo "default failed"
+python3 $R/bench.py --workload default --steps 3 --warmup 1 --full > $OUT/default_regime.json 2> $OUT/default_regime.err || echo "default failed"
 echo "default regime done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/default_trace --output-format csv -- python3 $R/bench.py --workload default --steps 1 --warmup 0 --no-cpu-baseline \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/default_trace --output-format csv -- python3 $R/bench.py --workload default --steps 1 --warmup 0 --no-cpu-baseline --full \
   > $OUT/default_under_rocprof.json 2> $OUT/default_trace.err || echo "default trace failed"
 cp $OUT/default_trace/*/*kernel_stats.csv $OUT/default_kernel_stats.csv 2>/dev/null
 head -8 $OUT/default_kernel_stats.csv
@@ -37,5 +37,5 @@ timeout -k 10 200 python3 $R/tools/fit_by_n.py > $OUT/fit_by_N.txt 2>&1
 cat $OUT/fit_by_N.txt
 python3 $R/bench.py --gpus 2 --virtual-ranks --steps 3 > $OUT/group2_virtual.json 2> $OUT/group2.err || echo "group failed"
 python3 $R/bench.py --gpus 8 --virtual-ranks --steps 3 --candidates 131072 > $OUT/group8_virtual.json 2> $OUT/group8.err || echo "group8 failed"
-python3 $R/bench.py --workload cfg5 --steps 20 --samples 10 --no-cpu-baseline > $OUT/cfg5_s10.json 2>/dev/null
+python3 $R/bench.py --workload cfg5 --steps 20 --samples 10 --no-cpu-baseline --full > $OUT/cfg5_s10.json 2>/dev/null
 echo "r04 extras done"
