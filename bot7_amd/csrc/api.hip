@@ -100,9 +100,8 @@ PhaseScope::~PhaseScope() {
 static double *cur_grid(b7_ctx *c) { return (double *)c->grid[c->grid_cur].p; }
 
 static void invalidate_predictions(b7_ctx *c) {
-  c->pend.on = false;  // a batched score nobody collected belongs to the grid that just changed
   c->predicted = false;
-  c->acc_valid = false;
+  acc_forget(c);
   c->Mfeat = 0;  // DNGO features belong to the grid they were computed from
   c->win_valid = false;  // so does the winner's row of the last exchange
 }
@@ -995,11 +994,21 @@ static int fit_front(b7_ctx *c, const b7_hyp *hyp, const double *ls_dev) {
 
 int npad_of(const b7_ctx *c, int64_t n) { return (c->npad_small && n <= 64) ? 64 : (int)round_up(n, B7_NPAD); }
 
-int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec) {
-  if (S < 1 || !hyps || !spec) return b7_fail(c, B7_ERR_INVALID, "eval_nominate: S >= 1, hyps and spec required");
+// The score spec and the global row offset of an eval + nominate entry point (`who` in the messages).  Only a shard of a
+// larger candidate set -- a rank of a communicator, a member of a group -- may be empty: the exchange covers the others.
+static int nominate_args(b7_ctx *c, const char *who, const b7_score_spec *spec, int64_t offset) {
   if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB)
-    return b7_fail(c, B7_ERR_INVALID, "eval_nominate: unknown score kind %d", spec->kind);
-  if (spec->kind == B7_SCORE_EI && !spec->fmin) return b7_fail(c, B7_ERR_INVALID, "eval_nominate: EI needs fmin");
+    return b7_fail(c, B7_ERR_INVALID, "%s: unknown score kind %d", who, spec->kind);
+  if (spec->kind == B7_SCORE_EI && !spec->fmin) return b7_fail(c, B7_ERR_INVALID, "%s: EI needs fmin", who);
+  if (offset < 0) return b7_fail(c, B7_ERR_INVALID, "%s: negative row offset", who);
+  if (c->M == 0 && !(c->comm && c->comm_world > 1) && !c->group)
+    return b7_fail(c, B7_ERR_STATE, "%s: no candidate grid on this context", who);
+  return B7_OK;
+}
+
+int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t offset) {
+  if (S < 1 || !hyps || !spec) return b7_fail(c, B7_ERR_INVALID, "eval_nominate: S >= 1, hyps and spec required");
+  B7_TRY(nominate_args(c, "eval_nominate", spec, offset));
   if (!c->have_data) return b7_fail(c, B7_ERR_STATE, "eval_nominate: call b7_gp_set_data first");
   if (c->M > 0 && c->d != c->dfit)
     return b7_fail(c, B7_ERR_INVALID, "eval_nominate: grid dims %d != data dims %d", c->d, c->dfit);
@@ -1007,9 +1016,31 @@ int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spe
   return B7_OK;
 }
 
+// c->pin_eval, the pinned, device-mapped block of a nomination's pivot reports and staging: at least `bytes` (twice that when
+// it has to grow)
+static int pin_eval_ensure(b7_ctx *c, size_t bytes) {
+  if (c->pin_eval_bytes >= bytes) return B7_OK;
+  B7_HIP(c, hipStreamSynchronize(c->stream));  // nothing in flight writes reports into the block about to go
+  if (c->pin_eval) (void)hipHostFree(c->pin_eval);
+  c->pin_eval = nullptr;
+  c->pin_eval_bytes = 0;
+  B7_HIP(c, hipHostMalloc(&c->pin_eval, 2 * bytes, hipHostMallocMapped));
+  B7_HIP(c, hipHostGetDevicePointer(&c->pin_eval_dev, c->pin_eval, 0));
+  c->pin_eval_bytes = 2 * bytes;
+  return B7_OK;
+}
+
+// score:add x S of the batch in c->bmu / c->bvar, owed to the exchange step (exch_local), which runs it fused with score:div,
+// the arg-max and the record
+static PendingScore pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd) {
+  return PendingScore{true, spec->kind, S, spec->upper, (const double *)c->bmu.p, (const double *)c->bvar.p, fd, c->M,
+                      spec->tradeoff, spec->sign};
+}
+
 // bots/bayesopt.lua:69-78 as stream work: zero the accumulator, then fit + posterior + score:add per hyper sample, each
-// fit's pivot report copied to its pinned slot in stream order.  Returns without waiting for any of it.
-int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec) {
+// fit's pivot report copied to its pinned slot in stream order.  Returns without waiting for any of it; the small regime's
+// score:add is left to the caller's exchange step in *pend.
+int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, PendingScore *pend) {
   const int d = c->dfit;
   B7_HIP(c, hipSetDevice(c->device));
   B7_TRY(b7_ensure(c, c->mu, sizeof(double) * (size_t)c->M * c->ycols));
@@ -1024,15 +1055,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
   }
   // pinned staging: [S][4] pivot reports | hypers of all S samples ([S][d] lengthscales, then S amp, S noise, S mean)
   const size_t hyp_doubles = (size_t)S * (d + 3), ls_bytes = sizeof(double) * hyp_doubles, rep_bytes = 16 * (size_t)S;
-  if (c->pin_eval_bytes < ls_bytes + rep_bytes) {
-    B7_HIP(c, hipStreamSynchronize(c->stream));  // nothing in flight writes reports into the block about to go
-    if (c->pin_eval) (void)hipHostFree(c->pin_eval);
-    c->pin_eval = nullptr;
-    c->pin_eval_bytes = 0;
-    B7_HIP(c, hipHostMalloc(&c->pin_eval, 2 * (ls_bytes + rep_bytes), hipHostMallocMapped));
-    B7_HIP(c, hipHostGetDevicePointer(&c->pin_eval_dev, c->pin_eval, 0));
-    c->pin_eval_bytes = 2 * (ls_bytes + rep_bytes);
-  }
+  B7_TRY(pin_eval_ensure(c, ls_bytes + rep_bytes));
   B7_TRY(b7_ensure(c, c->bhyp, ls_bytes));
   int *reports = static_cast<int *>(c->pin_eval);                                        // [S][4]
   double *ls_host = reinterpret_cast<double *>(static_cast<char *>(c->pin_eval) + rep_bytes);  // [S][d] | amp | noise | mean
@@ -1072,9 +1095,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
   double *fd = nullptr;
   if (spec->kind == B7_SCORE_EI) B7_TRY(stage_fmin(c, spec->fmin, &fd));
 
-  c->pend.on = false;
-  c->acc_fresh = true;  // torch.zeros(X_hid:size(1)), bots/bayesopt.lua:69: declared, not launched -- the first score:add starts from 0.0
-  c->acc_valid = true;
+  acc_declare_zeros(c);
   if (batch) {
     const double *hyp_dev = (const double *)c->bhyp.p, *amp_dev = hyp_dev + (size_t)S * d, *noise_dev = amp_dev + S,
                  *mean_dev = noise_dev + S;
@@ -1115,11 +1136,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
       B7_TRY(launch_kpost_small(c, S, (const double *)c->grid[c->grid_cur].p, c->M, (const double *)c->bw.p, (const double *)c->bzsc.p,
                                 (const double *)c->bzss.p, (const double *)c->bLinv.p, (const double *)c->balpha.p, hyp_dev, 0.0, 0.0, 0.0,
                                 (double *)c->bmu.p, (double *)c->bvar.p, c->M));
-      // score:add of the S samples is left to the exchange step, which runs it fused with score:div, the arg-max and the record
-      c->pend.on = true;
-      c->pend.kind = spec->kind, c->pend.S = S, c->pend.upper = spec->upper;
-      c->pend.mu = (const double *)c->bmu.p, c->pend.var = (const double *)c->bvar.p, c->pend.fd = fd;
-      c->pend.stride = c->M, c->pend.tradeoff = spec->tradeoff, c->pend.sign = spec->sign;
+      *pend = pending_score(c, S, spec, fd);
       c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
       c->predicted = false;
     } else if ((size_t)Mpad * S * row_bytes <= c->ks_bytes) {
@@ -1187,24 +1204,22 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
   return B7_OK;
 }
 
-// after the stream has drained: did every fit of the last eval_enqueue factor at the first attempt, without a hand-off
-// time-out?
-bool eval_reports_clean(b7_ctx *c, int S) {
-  const int *reports = static_cast<const int *>(c->pin_eval);
+// after the stream has drained: did each of S fits ([S][4] report words) factor at the first attempt, without a hand-off
+// time-out?  persist: the fits may have run the persistent schedule, which a time-out switches off (persist_gave_up)
+bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist) {
   bool clean = true, aborted = false;
   for (int s = 0; s < S; ++s) {
     clean = clean && reports[4 * s] == 0 && reports[4 * s + 1] == 0;
     aborted = aborted || reports[4 * s + 1] != 0;
   }
-  if (aborted) persist_gave_up(c);
+  if (aborted && persist) persist_gave_up(c);
   return clean;
 }
 
 // the same nomination through the per-sample path, jitter schedule (utils/math.lua:159-218) included; synchronous
 int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out) {
   B7_HIP(c, hipSetDevice(c->device));
-  B7_TRY(launch_fill(c, (double *)c->acc.p, c->M, 0.0));
-  c->acc_fresh = false;
+  B7_TRY(acc_write_zeros(c));
   double *fd = nullptr;
   for (int s = 0; s < S; ++s) {
     B7_TRY(fit_hyp_core(c, &hyps[s], nullptr, jitter_out ? jitter_out + s : nullptr, info_out ? info_out + s : nullptr, true));
@@ -1216,28 +1231,24 @@ int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, d
   return B7_OK;
 }
 
-extern "C" {
-
-int b7_eval_nominate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset,
-                     double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out) {
-  if (!c) return B7_ERR_INVALID;
-  if (c->group) return b7_fail(c, B7_ERR_STATE, "eval_nominate: this context belongs to a group (b7_group_eval_nominate)");
-  const bool exchange = c->comm && c->comm_world > 1;
+// The protocol of the three eval + nominate entry points, once.  rc: their argument checks.  enqueue(&pend): the local
+// bayesopt:eval as stream work, its batched score possibly left pending; clean(): after the stream has drained, did every fit
+// factor at the first attempt; redo(): the same nomination again, synchronously, through the jitter schedule.  The redo starts
+// from nothing pending: what the failed fits left is dropped with them.
+template <class Enqueue, class Clean, class Redo>
+static int nominate_run(b7_ctx *c, const char *who, int rc, int64_t offset, double divisor, Enqueue enqueue, Clean clean,
+                        Redo redo, double *best_val, int64_t *best_idx1) {
   const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
-  if (jitter_out && S > 0) std::fill(jitter_out, jitter_out + S, 0.0);
-  if (info_out && S > 0) std::fill(info_out, info_out + S, 0);
-  int rc = eval_validate(c, S, hyps, spec);
-  if (rc == B7_OK && global_row_offset < 0) rc = b7_fail(c, B7_ERR_INVALID, "eval_nominate: negative row offset");
-  if (rc == B7_OK && c->M == 0 && !exchange) rc = b7_fail(c, B7_ERR_STATE, "eval_nominate: no candidate grid on this context");
-  if (!exchange) {
+  PendingScore pend;
+  if (!(c->comm && c->comm_world > 1)) {
     // the arg-max and the copy of its record are enqueued before the host has seen any report: one synchronisation
     B7_TRY(rc);
-    B7_TRY(eval_enqueue(c, S, hyps, spec));
-    B7_TRY(exch_local(c, (double)S, global_row_offset, rank, world, true, true));  // record mirrored into mapped host memory
+    B7_TRY(enqueue(&pend));
+    B7_TRY(exch_local(c, divisor, offset, rank, world, true, true, &pend));  // record mirrored into mapped host memory
     B7_TRY(exch_wait_mirror(c));
-    if (!eval_reports_clean(c, S)) {
-      B7_TRY(eval_redo(c, S, hyps, spec, jitter_out, info_out));
-      B7_TRY(exch_local(c, (double)S, global_row_offset, rank, world, true, true));
+    if (!clean()) {
+      B7_TRY(redo());
+      B7_TRY(exch_local(c, divisor, offset, rank, world, true, true));
       B7_TRY(exch_wait_mirror(c));
     }
     return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
@@ -1245,22 +1256,30 @@ int b7_eval_nominate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *
   // with a communicator the collective comes after the report check (a rank that redoes its nomination must not
   // issue one collective too many), and a rank that fails locally still reaches it, with a failure record
   if (rc == B7_OK && c->M > 0) {
-    rc = eval_enqueue(c, S, hyps, spec);
-    if (rc == B7_OK) rc = hipStreamSynchronize(c->stream) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "eval_nominate: stream failed");
-    if (rc == B7_OK && !eval_reports_clean(c, S)) rc = eval_redo(c, S, hyps, spec, jitter_out, info_out);
+    rc = enqueue(&pend);
+    if (rc == B7_OK) rc = hipStreamSynchronize(c->stream) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "%s: stream failed", who);
+    if (rc == B7_OK && !clean()) {
+      pend = PendingScore();
+      rc = redo();
+    }
   }
-  if (rc == B7_OK) rc = exch_local(c, (double)S, global_row_offset, rank, world, true);
-  const std::string own = c->err;
-  if (rc != B7_OK) B7_TRY(exch_fail_record(c, rank, world, rc));
-  B7_TRY(exch_allreduce(c));
-  B7_TRY(exch_fetch(c, 0, world));
-  B7_HIP(c, hipStreamSynchronize(c->stream));
-  if (rc != B7_OK) {
-    exch_forget(c);
-    c->err = own;
-    return rc;
-  }
-  return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
+  if (rc == B7_OK) rc = exch_local(c, divisor, offset, rank, world, true, false, &pend);
+  return exch_collective(c, rc, rank, world, best_val, best_idx1);
+}
+
+extern "C" {
+
+int b7_eval_nominate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset,
+                     double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out) {
+  if (!c) return B7_ERR_INVALID;
+  if (c->group) return b7_fail(c, B7_ERR_STATE, "eval_nominate: this context belongs to a group (b7_group_eval_nominate)");
+  if (jitter_out && S > 0) std::fill(jitter_out, jitter_out + S, 0.0);
+  if (info_out && S > 0) std::fill(info_out, info_out + S, 0);
+  return nominate_run(
+      c, "eval_nominate", eval_validate(c, S, hyps, spec, global_row_offset), global_row_offset, (double)S,
+      [&](PendingScore *pend) { return eval_enqueue(c, S, hyps, spec, pend); },
+      [&]() { return reports_clean(c, static_cast<const int *>(c->pin_eval), S, true); },
+      [&]() { return eval_redo(c, S, hyps, spec, jitter_out, info_out); }, best_val, best_idx1);
 }
 
 int b7_gp_fit(b7_ctx *c, const double *X, const double *Y, int N, int d, int ycols, const b7_hyp *hyp,
@@ -1647,7 +1666,7 @@ int b7_blr_features(b7_ctx *c, const double *Z1, int64_t M, int z) {
   if (c->M != M) {  // features stand in for a grid: the score calls size themselves by M
     c->M = M;
     c->d = 0;
-    c->acc_valid = false;
+    acc_forget(c);
   }
   return B7_OK;
 }
@@ -1871,7 +1890,8 @@ static int blr_enqueue_score(b7_ctx *c, const b7_mlp *net, int z, const b7_score
   B7_TRY(launch_post(c, (const double *)c->feat.p, 0, round_up(c->M, B7_MROWS), c->M, (double *)c->var.p));
   c->predicted = true;
   c->Mpred = c->M;
-  // bots/bayesopt.lua:65-66: the score of the one model, no accumulation over samples -> written, not added
+  // bots/bayesopt.lua:65-66: the score of the one model, no accumulation over samples -> written, not added (which makes the
+  // accumulator valid: score.hip, acc_mode)
   double *fd = nullptr;
   if (spec->kind == B7_SCORE_EI) {
     B7_TRY(stage_fmin(c, spec->fmin, &fd));
@@ -1880,7 +1900,6 @@ static int blr_enqueue_score(b7_ctx *c, const b7_mlp *net, int z, const b7_score
     B7_TRY(launch_cb(c, (const double *)c->mu.p, (const double *)c->var.p, spec->tradeoff, spec->upper, spec->sign, c->M, 1,
                      (double *)c->acc.p, false));
   }
-  c->acc_valid = true;
   return B7_OK;
 }
 
@@ -1889,64 +1908,30 @@ int b7_blr_eval_nominate(b7_ctx *c, const b7_mlp *net, const double *X0, const d
                          int64_t *best_idx1, double *jitter_used) {
   if (!c) return B7_ERR_INVALID;
   if (c->group) return b7_fail(c, B7_ERR_STATE, "blr_eval_nominate: this context belongs to a group");
-  const bool exchange = c->comm && c->comm_world > 1;
-  const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
   if (jitter_used) *jitter_used = 0.0;
   int rc = B7_OK, z = 0;
   if (!X0 || !Y0 || N < 1 || !spec) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: bad arguments");
   else if (!(alpha_prec > 0.0) || !(beta > 0.0)) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: precisions must be > 0");
-  else if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: unknown score kind %d", spec->kind);
-  else if (spec->kind == B7_SCORE_EI && !spec->fmin) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: EI needs fmin");
-  else if (global_row_offset < 0) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: negative row offset");
-  else if (c->M == 0 && !exchange) rc = b7_fail(c, B7_ERR_STATE, "blr_eval_nominate: no candidate grid on this context");
+  else rc = nominate_args(c, "blr_eval_nominate", spec, global_row_offset);
   if (rc == B7_OK) rc = hipSetDevice(c->device) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "hipSetDevice failed");
   if (rc == B7_OK) rc = upload_net(c, net, &z);
   if (rc == B7_OK && z > 256) rc = b7_fail(c, B7_ERR_UNSUPPORTED, "blr: basis width %d > 256", z);
   if (rc == B7_OK && c->M > 0 && net->dims[0] != c->d)
     rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: network input width %d != grid dims %d", net->dims[0], c->d);
-  std::vector<double> rb;  // beta (Y - mean): the source of an asynchronous copy, alive until the synchronisation below
-  auto local = [&]() -> int {
-    if (c->M == 0) return B7_OK;   // an empty shard: nothing to score, but the exchange is collective
-    B7_TRY(blr_enqueue_fit(c, net, X0, Y0, N, z, alpha_prec, beta, mean, rb));
-    return blr_enqueue_score(c, net, z, spec);
-  };
-  auto redo = [&]() -> int {        // the jitter schedule of utils/math.lua:159-218, through the synchronous fit
-    B7_TRY(b7_blr_fit_x(c, net, X0, Y0, N, alpha_prec, beta, mean, nullptr));
-    if (jitter_used) *jitter_used = -2.0;  // "a jitter was needed" (its size is the fit's business; see b7_blr_fit_x)
-    return blr_enqueue_score(c, net, z, spec);
-  };
-  const int *report = static_cast<const int *>(c->pinned);
-  if (!exchange) {
-    B7_TRY(rc);
-    B7_TRY(local());
-    B7_TRY(exch_local(c, 1.0, global_row_offset, rank, world, true, true));
-    B7_TRY(exch_wait_mirror(c));
-    if (report[0] != 0 || report[1] != 0) {
-      if (report[1] != 0) persist_gave_up(c);
-      B7_TRY(redo());
-      B7_TRY(exch_local(c, 1.0, global_row_offset, rank, world, true, true));
-      B7_TRY(exch_wait_mirror(c));
-    }
-    return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
-  }
-  if (rc == B7_OK) rc = local();
-  if (rc == B7_OK) rc = hipStreamSynchronize(c->stream) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "blr_eval_nominate: stream failed");
-  if (rc == B7_OK && c->M > 0 && (report[0] != 0 || report[1] != 0)) {
-    if (report[1] != 0) persist_gave_up(c);
-    rc = redo();
-  }
-  if (rc == B7_OK) rc = exch_local(c, 1.0, global_row_offset, rank, world, true);
-  const std::string own = c->err;
-  if (rc != B7_OK) B7_TRY(exch_fail_record(c, rank, world, rc));
-  B7_TRY(exch_allreduce(c));
-  B7_TRY(exch_fetch(c, 0, world));
-  B7_HIP(c, hipStreamSynchronize(c->stream));
-  if (rc != B7_OK) {
-    exch_forget(c);
-    c->err = own;
-    return rc;
-  }
-  return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
+  std::vector<double> rb;  // beta (Y - mean): the source of an asynchronous copy, alive until the synchronisation
+  return nominate_run(
+      c, "blr_eval_nominate", rc, global_row_offset, 1.0,
+      [&](PendingScore *) {
+        B7_TRY(blr_enqueue_fit(c, net, X0, Y0, N, z, alpha_prec, beta, mean, rb));
+        return blr_enqueue_score(c, net, z, spec);
+      },
+      [&]() { return reports_clean(c, static_cast<const int *>(c->pinned), 1, true); },  // the head's report (blr_enqueue_fit)
+      [&]() {  // the jitter schedule of utils/math.lua:159-218, through the synchronous fit
+        B7_TRY(b7_blr_fit_x(c, net, X0, Y0, N, alpha_prec, beta, mean, nullptr));
+        if (jitter_used) *jitter_used = -2.0;  // "a jitter was needed" (its size is the fit's business; see b7_blr_fit_x)
+        return blr_enqueue_score(c, net, z, spec);
+      },
+      best_val, best_idx1);
 }
 
 // ---- the same with the head's hypers marginalised (models/dngo.lua:109,174) -------------------------------------------------
@@ -1957,11 +1942,8 @@ int b7_blr_eval_nominate(b7_ctx *c, const b7_mlp *net, const double *X0, const d
 static int blr_marg_slow(b7_ctx *c, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *ap,
                          const double *bt, const double *mn, int z, const b7_score_spec *spec, double *nll_out) {
   const int zpad = npad_of(c, z);
-  c->pend.on = false;
   B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
-  B7_TRY(launch_fill(c, (double *)c->acc.p, c->M, 0.0));
-  c->acc_fresh = false;
-  c->acc_valid = true;
+  B7_TRY(acc_write_zeros(c));
   for (int s = 0; s < S; ++s) {
     B7_TRY(b7_blr_fit_x(c, net, X0, Y0, N, ap[s], bt[s], mn[s], nll_out ? nll_out + s : nullptr));   // synchronous, jitter schedule included
     if (s == 0) {
@@ -1990,7 +1972,7 @@ static int blr_marg_slow(b7_ctx *c, const b7_mlp *net, const double *X0, const d
 }
 
 static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *ap,
-                         const double *bt, const double *mn, int z, const b7_score_spec *spec, bool want_terms) {
+                         const double *bt, const double *mn, int z, const b7_score_spec *spec, bool want_terms, PendingScore *pend) {
   const int d = net->dims[0];
   const size_t up_doubles = (size_t)N * d + (size_t)N + 5 * (size_t)S;   // [X0 | y | S alpha | S beta | S mean | S zeros | S 1/beta]
   B7_TRY(b7_ensure(c, c->tmpmu, sizeof(double) * (up_doubles + (size_t)N * z)));
@@ -2006,15 +1988,7 @@ static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const d
   B7_TRY(b7_ensure(c, c->info, B7_INFO_BYTES));
   // pinned, device-mapped block for the reports and the evidence's terms: [S][4] ints | [S][3] doubles
   const size_t rep_bytes = 16 * (size_t)S, term_bytes = sizeof(double) * 3 * (size_t)S;
-  if (c->pin_eval_bytes < rep_bytes + term_bytes) {
-    B7_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->pin_eval) (void)hipHostFree(c->pin_eval);
-    c->pin_eval = nullptr;
-    c->pin_eval_bytes = 0;
-    B7_HIP(c, hipHostMalloc(&c->pin_eval, 2 * (rep_bytes + term_bytes), hipHostMallocMapped));
-    B7_HIP(c, hipHostGetDevicePointer(&c->pin_eval_dev, c->pin_eval, 0));
-    c->pin_eval_bytes = 2 * (rep_bytes + term_bytes);
-  }
+  B7_TRY(pin_eval_ensure(c, rep_bytes + term_bytes));
   if (c->pin_blr_bytes < sizeof(double) * up_doubles) {
     B7_HIP(c, hipStreamSynchronize(c->stream));
     if (c->pin_blr) (void)hipHostFree(c->pin_blr);
@@ -2048,12 +2022,8 @@ static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const d
                            (double *)c->bvar.p, c->M, hdev + 3 * (size_t)S, hdev + 4 * (size_t)S));
   double *fd = nullptr;
   if (spec->kind == B7_SCORE_EI) B7_TRY(stage_fmin(c, spec->fmin, &fd));
-  c->acc_fresh = true;
-  c->acc_valid = true;
-  c->pend.on = true;
-  c->pend.kind = spec->kind, c->pend.S = S, c->pend.upper = spec->upper;
-  c->pend.mu = (const double *)c->bmu.p, c->pend.var = (const double *)c->bvar.p, c->pend.fd = fd;
-  c->pend.stride = c->M, c->pend.tradeoff = spec->tradeoff, c->pend.sign = spec->sign;
+  acc_declare_zeros(c);
+  *pend = pending_score(c, S, spec, fd);
   return B7_OK;
 }
 
@@ -2062,15 +2032,10 @@ int b7_blr_eval_nominate_marg(b7_ctx *c, const b7_mlp *net, const double *X0, co
                               double *best_val, int64_t *best_idx1, double *nll_out, double *jitter_used) {
   if (!c) return B7_ERR_INVALID;
   if (c->group) return b7_fail(c, B7_ERR_STATE, "blr_eval_nominate_marg: this context belongs to a group");
-  const bool exchange = c->comm && c->comm_world > 1;
-  const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
   if (jitter_used) *jitter_used = 0.0;
   int rc = B7_OK, z = 0;
   if (!X0 || !Y0 || N < 1 || S < 1 || !ap || !bt || !mn || !spec) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: bad arguments");
-  else if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: unknown score kind %d", spec->kind);
-  else if (spec->kind == B7_SCORE_EI && !spec->fmin) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: EI needs fmin");
-  else if (global_row_offset < 0) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: negative row offset");
-  else if (c->M == 0 && !exchange) rc = b7_fail(c, B7_ERR_STATE, "blr_eval_nominate_marg: no candidate grid on this context");
+  else rc = nominate_args(c, "blr_eval_nominate_marg", spec, global_row_offset);
   for (int s = 0; rc == B7_OK && s < S; ++s)
     if (!(ap[s] > 0.0) || !(bt[s] > 0.0)) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: precisions must be > 0 (sample %d)", s);
   if (rc == B7_OK) rc = hipSetDevice(c->device) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "hipSetDevice failed");
@@ -2079,66 +2044,30 @@ int b7_blr_eval_nominate_marg(b7_ctx *c, const b7_mlp *net, const double *X0, co
   if (rc == B7_OK && c->M > 0 && net->dims[0] != c->d)
     rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: network input width %d != grid dims %d", net->dims[0], c->d);
   const bool fast = rc == B7_OK && z <= 64 && c->blr_small && c->npad_small;
-  auto finish_terms = [&]() {   // the evidence of every head from the kernel's three sums (Bishop 3.82 / 3.86, as blr_fit_core)
-    if (!nll_out) return;
-    const double *t = reinterpret_cast<const double *>(static_cast<const char *>(c->pin_eval) + 16 * (size_t)S);
-    for (int s = 0; s < S; ++s) {
-      const double Em = 0.5 * bt[s] * t[3 * s + 2] - 0.5 * t[3 * s + 1];
-      nll_out[s] = -(0.5 * z * log(ap[s]) + 0.5 * N * log(bt[s]) - Em - t[3 * s] - 0.5 * N * log(2.0 * M_PI));
-    }
-  };
-  auto reports_clean = [&]() {
-    const int *rep = static_cast<const int *>(c->pin_eval);
-    for (int s = 0; s < S; ++s)
-      if (rep[4 * s] != 0 || rep[4 * s + 1] != 0) return false;
-    return true;
-  };
-  if (!exchange) {
-    B7_TRY(rc);
-    if (fast) {
-      B7_TRY(blr_marg_fast(c, net, X0, Y0, N, S, ap, bt, mn, z, spec, nll_out != nullptr));
-      B7_TRY(exch_local(c, (double)S, global_row_offset, rank, world, true, true));
-      B7_TRY(exch_wait_mirror(c));
-      if (reports_clean()) {
-        finish_terms();
-        c->fitted = false;   // the context's own fit slot holds none of the S heads
-        return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
-      }
-      if (jitter_used) *jitter_used = -2.0;
-    }
-    B7_TRY(blr_marg_slow(c, net, X0, Y0, N, S, ap, bt, mn, z, spec, nll_out));
-    B7_TRY(exch_local(c, (double)S, global_row_offset, rank, world, true, true));
-    B7_TRY(exch_wait_mirror(c));
-    return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
-  }
-  // with a communicator: the local part first (a rank that fails still reaches the collective with a failure record)
-  if (rc == B7_OK && c->M > 0) {
-    bool done = false;
-    if (fast) {
-      rc = blr_marg_fast(c, net, X0, Y0, N, S, ap, bt, mn, z, spec, nll_out != nullptr);
-      if (rc == B7_OK) rc = score_flush_pending(c);
-      if (rc == B7_OK) rc = hipStreamSynchronize(c->stream) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "blr_eval_nominate_marg: stream failed");
-      if (rc == B7_OK && reports_clean()) {
-        finish_terms();
-        done = true;
-      } else if (rc == B7_OK && jitter_used) {
-        *jitter_used = -2.0;
-      }
-    }
-    if (rc == B7_OK && !done) rc = blr_marg_slow(c, net, X0, Y0, N, S, ap, bt, mn, z, spec, nll_out);
-  }
-  if (rc == B7_OK) rc = exch_local(c, (double)S, global_row_offset, rank, world, true);
-  const std::string own = c->err;
-  if (rc != B7_OK) B7_TRY(exch_fail_record(c, rank, world, rc));
-  B7_TRY(exch_allreduce(c));
-  B7_TRY(exch_fetch(c, 0, world));
-  B7_HIP(c, hipStreamSynchronize(c->stream));
-  if (rc != B7_OK) {
-    exch_forget(c);
-    c->err = own;
-    return rc;
-  }
-  return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
+  return nominate_run(
+      c, "blr_eval_nominate_marg", rc, global_row_offset, (double)S,
+      [&](PendingScore *pend) {
+        return fast ? blr_marg_fast(c, net, X0, Y0, N, S, ap, bt, mn, z, spec, nll_out != nullptr, pend)
+                    : blr_marg_slow(c, net, X0, Y0, N, S, ap, bt, mn, z, spec, nll_out);
+      },
+      [&]() {  // the slow path needs no check: its fits went through the jitter schedule one by one
+        if (!fast) return true;
+        if (!reports_clean(c, static_cast<const int *>(c->pin_eval), S, false)) return false;
+        if (nll_out) {  // the evidence of every head from the kernel's three sums (Bishop 3.82 / 3.86, as blr_fit_core)
+          const double *t = reinterpret_cast<const double *>(static_cast<const char *>(c->pin_eval) + 16 * (size_t)S);
+          for (int s = 0; s < S; ++s) {
+            const double Em = 0.5 * bt[s] * t[3 * s + 2] - 0.5 * t[3 * s + 1];
+            nll_out[s] = -(0.5 * z * log(ap[s]) + 0.5 * N * log(bt[s]) - Em - t[3 * s] - 0.5 * N * log(2.0 * M_PI));
+          }
+        }
+        c->fitted = false;  // the context's own fit slot holds none of the S heads
+        return true;
+      },
+      [&]() {
+        if (jitter_used) *jitter_used = -2.0;
+        return blr_marg_slow(c, net, X0, Y0, N, S, ap, bt, mn, z, spec, nll_out);
+      },
+      best_val, best_idx1);
 }
 
 // ---- scores --------------------------------------------------------------------------------------------
@@ -2147,10 +2076,7 @@ int b7_score_reset(b7_ctx *c) {
   if (c->M <= 0) return b7_fail(c, B7_ERR_STATE, "score_reset: no candidate grid");
   B7_HIP(c, hipSetDevice(c->device));
   B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
-  B7_TRY(launch_fill(c, (double *)c->acc.p, c->M, 0.0));  // torch.zeros(X_hid:size(1)), bots/bayesopt.lua:69
-  c->acc_fresh = false;
-  c->acc_valid = true;
-  return B7_OK;
+  return acc_write_zeros(c);  // torch.zeros(X_hid:size(1)), bots/bayesopt.lua:69
 }
 
 static int score_ready(b7_ctx *c, const char *who) {

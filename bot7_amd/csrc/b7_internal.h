@@ -49,6 +49,17 @@ struct PhaseStat {
   int64_t launches = 0;
 };
 
+// A nomination's batched score (all S samples' mean / variance on the device), not launched yet: the exchange step runs it fused
+// with score:div, the arg-max and the record (score.hip: score_finish_slot_kernel).  A value of the call that made it, never
+// of the context: no later call can meet a pending score.
+struct PendingScore {
+  bool on = false;
+  int kind = 0, S = 0, upper = 0;
+  const double *mu = nullptr, *var = nullptr, *fd = nullptr;
+  int64_t stride = 0;
+  double tradeoff = 0.0, sign = 0.0;
+};
+
 struct b7_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -98,16 +109,7 @@ struct b7_ctx {
   bool blr_small = true;     // b7_blr_eval_nominate: the head for z <= 64 features in one workgroup of one launch (blr_small.hip)
   double fmin_scalar = 0.0;  // f_min of a single response column: a kernel argument of the EI kernels (launched with fmin_dev == nullptr), no staging copy
   bool acc_fresh = false;  // the accumulator stands for zeros that were never written: the next score launch onto it starts from 0.0
-  // b7_eval_nominate's batched score (all S samples' mean / variance on the device), not launched yet: the exchange step runs it
-  // fused with score:div, the arg-max and the record (score.hip: score_finish_slot_kernel); anybody else who needs the
-  // accumulator first flushes it through the plain batch kernel (score_flush_pending)
-  struct PendingScore {
-    bool on = false;
-    int kind = 0, S = 0, upper = 0;
-    const double *mu = nullptr, *var = nullptr, *fd = nullptr;
-    int64_t stride = 0;
-    double tradeoff = 0.0, sign = 0.0;
-  } pend;
+                           // (acc_valid and acc_fresh change only through score.hip's acc_* helpers)
   DevBuf ks;     // K(X*,X) chunk workspace
   size_t ks_bytes = (size_t)4 << 30;
   int diag_variant = 1;  // 64x64 diagonal-block kernel: 0 = rsqrt pivot chain, 1 = square-root-free chain with the DPP-fused
@@ -371,31 +373,41 @@ int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64
                        int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
                        unsigned *host_done = nullptr);
 
-int launch_score_finish_slot(b7_ctx *c, const b7_ctx::PendingScore &ps, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
+int launch_score_finish_slot(b7_ctx *c, const PendingScore &ps, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
                              int rank, int world, int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
                              unsigned *host_done = nullptr);
-int score_flush_pending(b7_ctx *c);
+// the accumulator's state: zeros declared (bots/bayesopt.lua:69 without a launch of its own: the first score launch onto it
+// starts from 0.0), zeros written now, no accumulator (the grid changed), declared zeros written before anybody reads them
+void acc_declare_zeros(b7_ctx *c);
+int acc_write_zeros(b7_ctx *c);
+void acc_forget(b7_ctx *c);
+int acc_materialize(b7_ctx *c);
 int launch_keep_record(b7_ctx *c, uint64_t *tab_dev, int rank, int world);
 int launch_row_slot(b7_ctx *c, uint64_t *tab_dev, int rank, int world, int64_t idx1_global, int64_t local0, const double *grid,
                     int d);
 
-// comm.hip: the pieces of a sharded nomination that b7_eval_nominate, b7_score_finish_global and the single-process
-// group (group.hip) are assembled from
+// comm.hip: the pieces of a sharded nomination that the eval + nominate entry points (api.hip: nominate_run),
+// b7_score_finish_global and the single-process group (group.hip) are assembled from
 int exch_table_ensure(b7_ctx *c, int world);
-int acc_materialize(b7_ctx *c);  // acc_fresh -> real zeros (before anything reads the accumulator)
-int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, bool all_slots, bool mirror = false);
-int exch_wait_mirror(b7_ctx *c);  // after exch_local(..., mirror = true): spin on the completion word, then (or instead, when it takes long) the stream  // enqueue: score:div, local arg-max, this rank's record
+// enqueue: score:div, local arg-max, this rank's record; pend (nullable): the nomination's batched score, run fused with them
+int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, bool all_slots, bool mirror = false,
+               const PendingScore *pend = nullptr);
+int exch_wait_mirror(b7_ctx *c);  // after exch_local(..., mirror = true): spin on the completion word, then (or instead, when it takes long) the stream
 int exch_fail_record(b7_ctx *c, int rank, int world, int code);  // enqueue: this rank's record says "could not score"
 int exch_allreduce(b7_ctx *c);                                   // enqueue: the collective (no-op without a communicator)
+// a communicator's end of a nomination after exch_local: failure record if rc says so, all-reduce, fetch, wait, conclude (or
+// return rc with this rank's own message)
+int exch_collective(b7_ctx *c, int rc, int rank, int world, double *best_val, int64_t *best_idx1);
 int exch_rewrite_record(b7_ctx *c, int rank, int world);         // enqueue: zero every record but this rank's (before a repeated all-reduce)
 int exch_fetch(b7_ctx *c, int first_rank, int nranks);           // enqueue: records [first, first + n) -> pinned host copy
 bool exch_pick(const uint64_t *tab, int world, int stride, double *val, int64_t *idx1, int *rank);
 int exch_conclude(b7_ctx *c, const uint64_t *tab, int world, double *best_val, int64_t *best_idx1);  // statuses, winner, cache
 void exch_forget(b7_ctx *c);
 
-// api.hip: bayesopt:eval as stream work without a host wait, its report check and the per-sample redo
-int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec);
-int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec);
-bool eval_reports_clean(b7_ctx *c, int S);
+// api.hip: bayesopt:eval as stream work without a host wait (its batched score left in *pend), the pivot reports' check and
+// the per-sample redo
+int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t offset);
+int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, PendingScore *pend);
+bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist);
 int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out);
 int grid_drop_row(b7_ctx *c, int64_t local_idx1, double *row_out_sync);  // stable deletion, enqueued; row_out != NULL synchronises

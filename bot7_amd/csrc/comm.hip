@@ -59,7 +59,7 @@ Rccl &rccl() {
   return r;
 }
 
-// ---- the exchange, in pieces (b7_eval_nominate, b7_score_finish_global and group.hip assemble them) --------------------
+// ---- the exchange, in pieces (api.hip's nominate_run, b7_score_finish_global and group.hip assemble them) ---------------
 
 int exch_table_ensure(b7_ctx *c, int world) {
   if (world < 1 || world > B7_MAX_WORLD) return b7_fail(c, B7_ERR_UNSUPPORTED, "exchange: world %d not in [1, %d]", world, B7_MAX_WORLD);
@@ -81,7 +81,8 @@ void exch_forget(b7_ctx *c) { c->win_valid = false; }
 // and the grid row it names beside it (an empty shard contributes a zero record)
 // mirror: the kernel also writes this rank's record into the mapped host table and raises the completion word behind it
 // (a context that nominates by itself: no copy launch and no stream wait between the arg-max and the answer; exch_wait_mirror)
-int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, bool all_slots, bool mirror) {
+// pend (nullable): the nomination's batched score, still owed -- score:add x S, div, arg-max and record then go in ONE launch
+int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, bool all_slots, bool mirror, const PendingScore *pend) {
   B7_TRY(exch_table_ensure(c, world));
   uint64_t *host_rec = nullptr;
   unsigned *host_done = nullptr;
@@ -90,12 +91,9 @@ int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, b
     host_rec = c->tab_host_dev + (size_t)rank * B7_TAB_W;
     host_done = reinterpret_cast<unsigned *>(c->tab_host_dev + (size_t)(B7_MAX_WORLD + 1) * B7_TAB_W);
   }
-  if (c->M > 0 && c->pend.on) {  // the nomination's batched score is still owed: score:add x S, div, arg-max, record in ONE launch
-    const b7_ctx::PendingScore ps = c->pend;
-    c->pend.on = false;
-    return launch_score_finish_slot(c, ps, (double *)c->acc.p, c->M, divisor, (uint64_t *)c->slots.p, rank, world, offset,
+  if (c->M > 0 && pend && pend->on)
+    return launch_score_finish_slot(c, *pend, (double *)c->acc.p, c->M, divisor, (uint64_t *)c->slots.p, rank, world, offset,
                                     (const double *)c->grid[c->grid_cur].p, c->d, all_slots, host_rec, host_done);
-  }
   if (c->M > 0) B7_TRY(acc_materialize(c));
   return launch_finish_slot(c, c->M > 0 ? (double *)c->acc.p : nullptr, c->M, divisor, (uint64_t *)c->slots.p, rank, world,
                             offset, c->M > 0 ? (const double *)c->grid[c->grid_cur].p : nullptr, c->d, all_slots, host_rec,
@@ -129,6 +127,22 @@ int exch_fail_record(b7_ctx *c, int rank, int world, int code) {
   B7_HIP(c, hipMemcpyAsync((uint64_t *)c->slots.p + (size_t)rank * B7_TAB_W, stage, sizeof(uint64_t) * B7_TAB_W,
                            hipMemcpyHostToDevice, c->stream));
   return B7_OK;
+}
+
+// A rank whose local part failed (rc) publishes a failure record instead of its own; every rank takes part in the one
+// all-reduce, and a failed rank returns its own error with its own message.
+int exch_collective(b7_ctx *c, int rc, int rank, int world, double *best_val, int64_t *best_idx1) {
+  const std::string own = c->err;
+  if (rc != B7_OK) B7_TRY(exch_fail_record(c, rank, world, rc));
+  B7_TRY(exch_allreduce(c));
+  B7_TRY(exch_fetch(c, 0, world));
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  if (rc != B7_OK) {
+    exch_forget(c);
+    c->err = own;
+    return rc;
+  }
+  return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
 }
 
 int exch_allreduce(b7_ctx *c) {
@@ -304,24 +318,12 @@ int b7_score_finish_global(b7_ctx *c, double divisor, int64_t global_row_offset,
   else if (c->M > 0 && !c->acc_valid) rc = b7_fail(c, B7_ERR_STATE, "score_finish_global: call b7_score_reset first");
   if (rc == B7_OK) rc = hipSetDevice(c->device) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "hipSetDevice failed");
   if (rc == B7_OK) rc = exch_local(c, divisor, global_row_offset, rank, world, true, !c->comm);
-  if (rc != B7_OK) {
-    if (world == 1) return rc;
-    const std::string own = c->err;
-    B7_TRY(exch_fail_record(c, rank, world, rc));  // reach the collective all the same
-    B7_TRY(exch_allreduce(c));
-    B7_HIP(c, hipStreamSynchronize(c->stream));
-    exch_forget(c);
-    c->err = own;
-    return rc;
-  }
+  if (rc != B7_OK && world == 1) return rc;
   if (!c->comm) {  // no communicator, nobody to exchange with: the record went straight to the mapped host table
     B7_TRY(exch_wait_mirror(c));
     return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
   }
-  B7_TRY(exch_allreduce(c));
-  B7_TRY(exch_fetch(c, 0, world));
-  B7_HIP(c, hipStreamSynchronize(c->stream));
-  return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
+  return exch_collective(c, rc, rank, world, best_val, best_idx1);  // a failed rank reaches the collective all the same
 }
 
 int b7_exchange_info(b7_ctx *c, int *world_out, int64_t *rows_per_rank, int64_t *winner_idx1, int *winner_rank,

@@ -369,14 +369,15 @@ int b7_group_eval_nominate(b7_group *g, int S, const b7_hyp *hyps, const b7_scor
   if (jitter_out && S > 0) std::fill(jitter_out, jitter_out + S, 0.0);
   if (info_out && S > 0) std::fill(info_out, info_out + S, 0);
   g->win_valid = false;
-  for (int i = 0; i < n; ++i) G_TRY(g, i, eval_validate(g->ctx[i], S, hyps, spec));
+  for (int i = 0; i < n; ++i) G_TRY(g, i, eval_validate(g->ctx[i], S, hyps, spec, 0));
   if (offset_of(g, n) == 0) return gfail(g, B7_ERR_STATE, "group_eval_nominate: no candidate grid on this group");
   // everything a member has to do, enqueued on its stream; the host moves on to the next member without waiting
   for (int i = 0; i < n; ++i) {
     b7_ctx *c = g->ctx[i];
-    if (c->M > 0) G_TRY(g, i, eval_enqueue(c, S, hyps, spec));
+    PendingScore pend;  // this member's batched score, run by its exchange step
+    if (c->M > 0) G_TRY(g, i, eval_enqueue(c, S, hyps, spec, &pend));
     if (hipSetDevice(c->device) != hipSuccess) return gfail(g, B7_ERR_HIP, "hipSetDevice(%d) failed", c->device);
-    G_TRY(g, i, exch_local(c, (double)S, offset_of(g, i), i, n, g->use_rccl));
+    G_TRY(g, i, exch_local(c, (double)S, offset_of(g, i), i, n, g->use_rccl, false, &pend));
   }
   int rc = exchange(g);
   if (rc != B7_OK) return rc;
@@ -388,7 +389,7 @@ int b7_group_eval_nominate(b7_group *g, int S, const b7_hyp *hyps, const b7_scor
   std::vector<char> member_redone(n, 0);
   for (int i = 0; i < n; ++i) {
     b7_ctx *c = g->ctx[i];
-    if (c->M == 0 || eval_reports_clean(c, S)) continue;
+    if (c->M == 0 || reports_clean(c, static_cast<const int *>(c->pin_eval), S, true)) continue;
     if (hipSetDevice(c->device) != hipSuccess) return gfail(g, B7_ERR_HIP, "hipSetDevice(%d) failed", c->device);
     G_TRY(g, i, eval_redo(c, S, hyps, spec, redone ? nullptr : jitter_out, redone ? nullptr : info_out));
     G_TRY(g, i, exch_local(c, (double)S, offset_of(g, i), i, n, g->use_rccl));

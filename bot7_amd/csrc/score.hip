@@ -306,11 +306,13 @@ int nblocks(b7_ctx *c, int64_t n) {
 }  // namespace
 
 // 0: out = score; 1: out += score; 2: out = 0.0 + score -- the context's accumulator was declared torch.zeros without being
-// filled (b7_eval_nominate: bots/bayesopt.lua:69 costs no launch of its own) and this is the first score:add onto it
+// filled (b7_eval_nominate: bots/bayesopt.lua:69 costs no launch of its own) and this is the first score:add onto it.  A score
+// written (not added) onto the accumulator is the accumulator from then on (bots/bayesopt.lua:65-66: the DNGO branch)
 static int acc_mode(b7_ctx *c, const double *out, bool accumulate) {
   if (out != (const double *)c->acc.p) return accumulate ? 1 : 0;
   const bool fresh = c->acc_fresh;
   c->acc_fresh = false;
+  if (!accumulate) c->acc_valid = true;
   return accumulate ? (fresh ? 2 : 1) : 0;
 }
 
@@ -362,22 +364,29 @@ int launch_fill(b7_ctx *c, double *p, int64_t n, double v) {
   return B7_OK;
 }
 
-// zeros that were only declared (acc_fresh) and never met a score launch: write them before anybody reads the accumulator
-// a batched score that b7_eval_nominate left for the fused finish (launch_score_finish_slot) and somebody else wants first
-int score_flush_pending(b7_ctx *c) {
-  if (!c->pend.on) return B7_OK;
-  const b7_ctx::PendingScore ps = c->pend;
-  c->pend.on = false;
-  if (ps.kind == B7_SCORE_EI) return launch_ei_batch(c, ps.S, ps.mu, ps.var, ps.stride, ps.fd, ps.tradeoff, c->M, (double *)c->acc.p);
-  return launch_cb_batch(c, ps.S, ps.mu, ps.var, ps.stride, ps.tradeoff, ps.upper, ps.sign, c->M, (double *)c->acc.p);
+// ---- the accumulator's state: set here and nowhere else ----
+// torch.zeros(X_hid:size(1)), bots/bayesopt.lua:69, declared without a launch: the first score launch onto it starts from 0.0
+void acc_declare_zeros(b7_ctx *c) {
+  c->acc_valid = true;
+  c->acc_fresh = true;
 }
 
-int acc_materialize(b7_ctx *c) {
-  B7_TRY(score_flush_pending(c));
-  if (!c->acc_fresh) return B7_OK;
+// the same zeros written now (the caller has sized c->acc for c->M)
+int acc_write_zeros(b7_ctx *c) {
+  B7_TRY(launch_fill(c, (double *)c->acc.p, c->M, 0.0));
+  c->acc_valid = true;
   c->acc_fresh = false;
-  return launch_fill(c, (double *)c->acc.p, c->M, 0.0);
+  return B7_OK;
 }
+
+// the grid changed: there is no accumulator until the next reset or nomination
+void acc_forget(b7_ctx *c) {
+  c->acc_valid = false;
+  c->acc_fresh = false;
+}
+
+// zeros that were only declared and never met a score launch: written before anybody reads the accumulator
+int acc_materialize(b7_ctx *c) { return c->acc_fresh ? acc_write_zeros(c) : B7_OK; }
 
 int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *best_val, int64_t *best_idx1) {
   PhaseScope ps(c, "argmax");
@@ -416,7 +425,7 @@ int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64
 }
 
 // The fused form: the S-sample score, score:div, the local arg-max and the record in one launch.
-int launch_score_finish_slot(b7_ctx *c, const b7_ctx::PendingScore &ps, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
+int launch_score_finish_slot(b7_ctx *c, const PendingScore &ps, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
                              int rank, int world, int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec,
                              unsigned *host_done) {
   PhaseScope scope(c, "score");

@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 rank, world, idhex, trials, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], int(sys.argv[4]), sys.argv[5]
 import bot7_amd  # noqa: E402
 from harness import dist  # noqa: E402
-from test_sharded_loop import _cfg1_grid, _run_bot  # noqa: E402
+from test_sharded_loop import _cfg1_grid, _nominations_after_the_loop, _run_bot  # noqa: E402
 
 ctx = bot7_amd.Context(0)
 ident = bytes.fromhex(idhex).ljust(128, b"\0")
@@ -29,6 +29,7 @@ res = {"rank": rank}
 xs, ys, best = _run_bot(shard, ctx, trials, nSamples=3, sample=(os.environ.get("B7_TEST_SAMPLE") == "1"))
 res.update(nominees=xs.tolist(), responses=ys.tolist(), best=[best[0], best[1].tolist(), best[2]], lo=shard.lo,
            rows=ctx.grid_download().tolist(), info_world=None)
+res["after"] = _nominations_after_the_loop(ctx, shard.lo)
 # a failure on ONE rank must come back as an error on EVERY rank, not as a hang: rank 1 asks for EI without fmin ... no:
 # arguments are checked before anything is enqueued, so break the state instead -- rank (world - 1) drops its data
 ctx.gp_set_data(np.asarray(xs), np.asarray(ys))

@@ -83,6 +83,30 @@ def _run_bot(cand, model_ctx, trials, nSamples=2, sample=False):
     return np.stack(xs), bot.responses.copy(), (bot.best["t"], np.array(bot.best["x"]).ravel(), float(np.ravel(bot.best["y"])[0]))
 
 
+def _nominations_after_the_loop(ctx, offset):
+    """What every rank of the communicator test runs after its trial loop, and the parent on one context: (a) a small-regime
+    b7_eval_nominate (N <= 128, d <= 32: the fused score) whose zero-noise sample meets duplicated rows, so that its plain
+    factorisation fails and the nomination is redone through the jitter schedule (the data of _group_worker.py's redo case);
+    (b) b7_blr_eval_nominate_marg at S = 3 (the fast path: its batched score left to the exchange step).
+    -> {case: [value bits, index, report]}."""
+    from harness import benchmarks
+    from oracle import cport
+    X = cport.sobol(40, 2, 2)
+    Y = benchmarks.braninhoo(X)
+    amp, m, fmin = float(np.var(Y)), float(np.mean(Y)), [float(Y.min())]
+    hyps = [dict(lenscale_sq=np.full(2, 0.25), amp=amp, noise=1e-4 * amp, mean=m), dict(lenscale_sq=np.full(2, 0.325), amp=amp, noise=0.0, mean=m)]
+    ctx.gp_set_data(np.concatenate([X, X[:7]]), np.concatenate([Y, Y[:7]]))
+    v, i, rep = ctx.eval_nominate(hyps, score="ei", fmin=fmin, global_row_offset=offset, want_report=True)
+    res = {"redo": [float(v).hex(), i, [float(j).hex() for j in rep["jitter"]], rep["info"].tolist()]}
+    rng = np.random.default_rng(7)
+    W = [rng.normal(scale=0.7, size=(16, 2)), rng.normal(scale=0.25, size=(16, 16))]
+    b = [rng.normal(scale=0.1, size=16) for _ in W]
+    v, i, jit = ctx.blr_eval_nominate_marg(W, b, "Tanh", X, Y, [0.5, 1.0, 2.0], [0.05, 0.1, 0.2], [m - 1.0, m, m + 1.0],
+                                           score="ei", fmin=fmin, global_row_offset=offset)
+    res["marg"] = [float(v).hex(), i, float(jit).hex()]
+    return res
+
+
 def _loop_worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -414,7 +438,9 @@ def test_processes_sharing_the_gpu_run_the_trial_loop_through_the_communicator_p
     broadcast all-reduce for the random initial ones, offset shift).  RCCL refuses two ranks on one device, so its eight entry
     points are served by a shared-memory test double loaded through B7_RCCL_LIB; every line of libbot7hip is the product's.
     Every rank must reproduce the single-context run, the shards must concatenate to its candidate set, and a rank that fails
-    locally must make EVERY rank return B7_ERR_COMM (nobody hangs in the collective)."""
+    locally must make EVERY rank return B7_ERR_COMM (nobody hangs in the collective).  After the loop every rank nominates once
+    through a jitter redo in the small regime and once through the marginalised DNGO head (_nominations_after_the_loop): value,
+    index and report equal the single context's bit for bit."""
     import json
     import subprocess
     from harness import dist
@@ -423,6 +449,8 @@ def test_processes_sharing_the_gpu_run_the_trial_loop_through_the_communicator_p
     one = dist.ShardedScorer(ctx, grid.shape[0], 0, 1)
     xs1, ys1, best1 = _run_bot(one, ctx, trials, nSamples=3, sample=sample)
     left1 = ctx.grid_download()
+    after1 = _nominations_after_the_loop(ctx, 0)
+    assert float.fromhex(after1["redo"][2][1]) > 0, after1   # the redo did happen
     env = dict(os.environ, B7_RCCL_LIB=_stub_lib(), BOT7HIP_LIB=_diag_lib(), PYTHONPATH=ROOT, B7_TEST_SAMPLE="1" if sample else "0")
     ident = ("b7stub_%d_%d" % (os.getpid(), world)).encode().hex()
     outs = [str(tmp_path / ("rank%d.json" % r)) for r in range(world)]
@@ -445,6 +473,7 @@ def test_processes_sharing_the_gpu_run_the_trial_loop_through_the_communicator_p
         assert np.array_equal(np.array(d["responses"]), ys1)
         assert d["best"][0] == best1[0] and np.array_equal(np.array(d["best"][1]), best1[1]) and d["best"][2] == best1[2]
         assert d["lo"] == sum(len(x["rows"]) for x in res[:r]), "rank %d: offset after %d commits" % (r, trials)
+        assert d["after"] == after1, "rank %d: %r != %r" % (r, d["after"], after1)
         rows += d["rows"]
         code = d["failure"][0] if isinstance(d["failure"], list) else None
         assert code == (-1 if r == world - 1 else -7), "rank %d: %r" % (r, d["failure"])   # its own error / B7_ERR_COMM
