@@ -114,7 +114,7 @@ constexpr int MLP_IN = 32;
 __device__ __forceinline__ double mlp_act(double v, int kind) {
   switch (kind) {
     case 1: return tanh(v);
-    case 2: return v > 0.0 ? v : 0.0;
+    case 2: return v <= 0.0 ? 0.0 : v;   // max(v, 0) with NaN passing (the oracle's np.maximum)
     case 3: return 1.0 / (1.0 + exp(-v));
     default: return v;
   }
@@ -444,7 +444,7 @@ __global__ void __launch_bounds__(512)
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-              post[r] = ACT == 2 ? (pre[r] > 0.0 ? pre[r] : 0.0) : ACT == 3 ? 1.0 / (1.0 + exp(-pre[r])) : pre[r];
+              post[r] = ACT == 2 ? (pre[r] <= 0.0 ? 0.0 : pre[r]) : ACT == 3 ? 1.0 / (1.0 + exp(-pre[r])) : pre[r];
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) act[(lq + 4 * r) * as + col] = (col < nout) ? post[r] : 0.0;

@@ -17,8 +17,9 @@
 //   q  = r * (1 + r/2 + r^2/6 + r^3/24 + r^4/120)        e^r - 1, truncation r^6/720 <= 5.5e-19
 //   q  = fma(arg, 0.0, q)                      NaN (or inf) in arg -> NaN; otherwise adds a signed zero
 //   amp * exp(a) = 2^(n >> 7) * T[n & 127] * (1 + q),  T[j] = amp * 2^(j/128) in LDS, v_ldexp for the power of two
-// (gradual underflow; a = -1000 gives exactly 0).  Measured against long-double exp over 2e7 arguments in [-40, 0]:
-// relative error <= 1.85 * 2^-53 with amp = 1 (tools/gen_exp_table.py writes the table and the constants).
+// (gradual underflow; a = -1000 gives exactly 0).  Measured on the device against mpmath over the whole domain [-1000, 0]
+// (tests/test_gpu_numerics.py, amp = 2^-40 .. 2^40): <= 2 ulp where amp * exp(arg) is normal, <= 2^-1074 absolute where it is
+// subnormal (tools/gen_exp_table.py writes the table and the constants).
 // Padding observations carry zs/2 = 1e300 (not +inf: inf * 0 would make the NaN carrier fire): arg = -1e300 -> exactly 0.
 // Four arguments at a time, stage by stage: one such chain is 14 dependent fp64 instructions (8.6 cycles each when the next
 // one waits for it, 4.8 when it does not), and the compiler, left to itself, ran the four chains of a 16x16 tile nearly one
