@@ -21,11 +21,11 @@ SYMBOLS = [
     "b7_abi_version", "b7_create", "b7_destroy", "b7_last_error", "b7_device_info", "b7_sync", "b7_set_workspace",
     "b7_sobol_direction_numbers", "b7_grid_sobol", "b7_grid_random", "b7_grid_upload", "b7_grid_download", "b7_grid_shape", "b7_grid_remove", "b7_grid_remove_rows",
     "b7_grid_colrange", "b7_grid_apply_onesided", "b7_grid_random_torch", "b7_torch_rand",
-    "b7_gp_default_opts", "b7_gp_set_opts", "b7_gp_fit", "b7_gp_set_data", "b7_gp_fit_hyp", "b7_gp_predict_hyp", "b7_gp_nll_batch", "b7_chol", "b7_gp_predict", "b7_gp_predict_at", "b7_gp_fantasize", "b7_gp_append", "b7_gp_download",
+    "b7_gp_default_opts", "b7_gp_set_opts", "b7_gp_set_kernel", "b7_gp_fit", "b7_gp_set_data", "b7_gp_fit_hyp", "b7_gp_predict_hyp", "b7_gp_nll_batch", "b7_chol", "b7_gp_predict", "b7_gp_predict_at", "b7_gp_fantasize", "b7_gp_append", "b7_gp_download",
     "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_cb", "b7_score_finish",
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
-    "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts",
+    "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
     "b7_group_grid_sobol", "b7_group_grid_random", "b7_group_grid_onesided", "b7_group_grid_upload", "b7_group_grid_shape", "b7_group_grid_download",
     "b7_group_grid_remove_rows", "b7_group_gp_set_data", "b7_group_eval_nominate", "b7_group_nominate_commit",
     "b7_ei_compute", "b7_cb_compute", "b7_argmax",
@@ -50,6 +50,20 @@ class ScoreSpec(C.Structure):
 
 
 SCORE_EI, SCORE_CB = 1, 2
+
+# covariance kernels (b7_gp_set_kernel): config.model.kernel names (bots/bayesopt.lua:41) -> B7_KERNEL_*
+KERNELS = {"ardse": 0, "ardmatern52": 1}
+
+
+def kernel_code(kernel):
+    """'ardse' / 'ardmatern52' (or the B7_KERNEL_* code itself) -> the code; anything else raises Bot7HipError."""
+    if isinstance(kernel, str):
+        if kernel not in KERNELS:
+            raise Bot7HipError(-1, "unknown covariance kernel %r (built: %s)" % (kernel, ", ".join(sorted(KERNELS))))
+        return KERNELS[kernel]
+    if int(kernel) not in KERNELS.values():
+        raise Bot7HipError(-1, "unknown covariance kernel code %r" % (kernel,))
+    return int(kernel)
 
 
 class Mlp(C.Structure):
@@ -110,6 +124,7 @@ def load(which=None):
         "b7_grid_remove_rows": (i32, [vp, vp, i64, vp]),
         "b7_gp_default_opts": (i32, [C.POINTER(GpOpts)]),
         "b7_gp_set_opts": (i32, [vp, C.POINTER(GpOpts)]),
+        "b7_gp_set_kernel": (i32, [vp, i32]),
         "b7_gp_fit": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(Hyp), vp, C.POINTER(dbl), C.POINTER(i32)]),
         "b7_gp_set_data": (i32, [vp, vp, vp, i32, i32, i32]),
         "b7_gp_fit_hyp": (i32, [vp, C.POINTER(Hyp), vp, C.POINTER(dbl), C.POINTER(i32)]),
@@ -157,6 +172,7 @@ def load(which=None):
         "b7_group_ctx": (vp, [vp, i32]),
         "b7_group_set_workspace": (i32, [vp, i64]),
         "b7_group_gp_set_opts": (i32, [vp, C.POINTER(GpOpts)]),
+        "b7_group_gp_set_kernel": (i32, [vp, i32]),
         "b7_group_grid_sobol": (i32, [vp, i64, i32, i64, vp, vp]),
         "b7_group_grid_random": (i32, [vp, i64, i32, C.c_uint64, vp, vp]),
         "b7_group_grid_onesided": (i32, [vp, vp, vp]),
@@ -214,6 +230,7 @@ class Context(object):
         self.device_id = int(device_id)
         self.grid_version = 0  # bumped whenever the resident grid changes (DeviceGrid views compare against it)
         self.fit_token = 0     # bumped by every call that replaces the fit (models check it before gp_append)
+        self.kernel = KERNELS["ardse"]  # the context's covariance kernel (b7_gp_set_kernel; a new context starts on ARD-SE)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -338,6 +355,16 @@ class Context(object):
                 raise Bot7HipError(-1, "unknown gp option %r" % k)
             setattr(o, k, v)
         self._ck(self._L.b7_gp_set_opts(self._h, C.byref(o)))
+
+    def gp_set_kernel(self, kernel):
+        """The covariance kernel of every later fit, posterior and likelihood: 'ardse' or 'ardmatern52' (or its B7_KERNEL_*
+        code).  The library is called only on a change, which drops the fit (fit_token moves: whoever cached "the fit is
+        current" refits)."""
+        code = kernel_code(kernel)
+        if code != self.kernel:
+            self._ck(self._L.b7_gp_set_kernel(self._h, code))
+            self.kernel = code
+            self.fit_token += 1
 
     def gp_fit(self, X_obs, Y_obs, lenscale_sq, amp, noise, mean, want_nll=False):
         X = _f64(X_obs)
@@ -801,6 +828,16 @@ class Group(object):
 
     def set_workspace(self, nbytes):
         self._ck(self._L.b7_group_set_workspace(self._h, int(nbytes)))
+
+    def gp_set_kernel(self, kernel):
+        """b7_gp_set_kernel on every member (Context.gp_set_kernel)."""
+        code = kernel_code(kernel)
+        if any(m.kernel != code for m in self.members):
+            self._ck(self._L.b7_group_gp_set_kernel(self._h, code))
+            for m in self.members:
+                if m.kernel != code:
+                    m.kernel = code
+                    m.fit_token += 1
 
     def grid_sobol(self, size, dims, skip=1, mins=None, maxes=None):
         mn, mx = Context._minmax(mins, maxes, dims)

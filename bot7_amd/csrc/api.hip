@@ -564,6 +564,19 @@ int b7_gp_set_opts(b7_ctx *c, const b7_gp_opts *o) {
   return B7_OK;
 }
 
+int b7_gp_set_kernel(b7_ctx *c, int kernel) {
+  if (!c) return B7_ERR_INVALID;
+  if (kernel != B7_KERNEL_ARDSE && kernel != B7_KERNEL_MATERN52)
+    return b7_fail(c, B7_ERR_INVALID, "gp_set_kernel: unknown kernel %d", kernel);
+  if (kernel == c->kernel) return B7_OK;
+  // what a fit under the old kernel left behind goes; the resident data and grid stay (no nomination leaves a score pending
+  // in the context: PendingScore belongs to the call that made it)
+  c->kernel = kernel;
+  c->fitted = false;
+  c->predicted = false;
+  return B7_OK;
+}
+
 // One factorisation attempt of K + extra*I; returns dpotrf-style info through *info.
 static int try_factor(b7_ctx *c, double extra, int *info, bool with_inverse, FactorNote *note = nullptr);
 void persist_gave_up(b7_ctx *c);

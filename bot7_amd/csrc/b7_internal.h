@@ -81,6 +81,7 @@ struct b7_ctx {
   int yld = 1;   // leading dimension of alpha: 1 for one column, else ycols rounded up to 64 (zero padded)
   double amp = 0, noise = 0, mean = 0;
   b7_gp_opts opts;
+  int kernel = B7_KERNEL_ARDSE;  // covariance kernel of every K this context forms (b7_gp_set_kernel): the launchers pick the instance
   DevBuf xobs;   // N x d raw observations
   DevBuf w;      // dpad inverse squared lengthscales (0 in the padding)
   DevBuf zsc;    // Npad x dpad: observations scaled by w (0 in the padding)

@@ -3,7 +3,8 @@
 // Reference arithmetic replaced (the kernel object itself, gp.kernels.ardse, is in the absent `gp` package;
 // the in-repo statement of its distance is utils.math.pdist):
 //   utils/math.lua:65-111   D = X^2 w (+) (Z^2 w)' - 2 X (Z' .* w),  w = 1/lenscale,  clamp(0, huge) (:106)
-//   K = amp * exp(-D/2)     (+ noise on the diagonal of K(X,X))
+//   K = amp * exp(-D/2)     (+ noise on the diagonal of K(X,X)); under b7_gp_set_kernel's ARD Matern-5/2
+//   K = amp (1 + s + s^2/3) exp(-s), s = sqrt(5 D): the kernel's KERN instance (ksx_exp.h cov_nonpos4)
 //   mean part of model:predict (scores/expected_improvement.lua:63): mu = m + K(X*,X) alpha
 //
 // Layout: the inner product X (Z' .* w) runs on v_mfma_f64_16x16x4_f64 with the query rows as the A operand
@@ -115,7 +116,8 @@ __host__ __device__ constexpr int ksx_slab(int dpad) { return dpad >= 48 ? 32 : 
 // the MFMA chain over DPAD/4 k-steps unrolls and the query fragments stay in registers for the whole block.
 // blockIdx.z = fit index of a batch over the same observations (b7_gp_nll_batch); all zero / null for a single fit
 using KBatch = KBatchDesc;
-template <int DPAD>
+// KERN: the covariance kernel (B7_KERNEL_*, ksx_exp.h cov_nonpos4)
+template <int DPAD, int KERN>
 __global__ void __launch_bounds__(256)
     ksx_kernel(const double *__restrict__ xq, int64_t row0, int64_t Mtotal, int d, int dpad_rt, const double *w,
                const double *zsc, const double *zsh, const double *__restrict__ alpha, double amp, double meanc, int Npad,
@@ -251,7 +253,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
       for (int r = 0; r < 4; ++r) kv[r] = arg[r];
 #else
-      amp_exp_nonpos4(arg, stab, kv);  // :106 clamp(0, huge) on the distance (NaN passes), amp * exp(-D/2)
+      cov_nonpos4<KERN>(arg, stab, kv);  // :106 clamp(0, huge) on the distance (NaN passes), amp * exp(-D/2) (ARD-SE)
 #endif
 #pragma unroll
       for (int r = 0; r < 4; ++r) macc[r] = __builtin_fma(kv[r], al, macc[r]);
@@ -336,11 +338,11 @@ int ensure_exp_table(b7_ctx *c) {
   return B7_OK;
 }
 
-template <int DPAD>
+template <int DPAD, int KERN>
 int ksx_launch(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
                const double *alpha, double meanc, double *out, double *mu) {
   const size_t lds = ksx_lds_bytes(DPAD);
-  auto kern = ksx_kernel<DPAD>;
+  auto kern = ksx_kernel<DPAD, KERN>;
   B7_TRY(ensure_exp_table(c));
   // dynamic LDS above the 64 KiB default needs an explicit opt-in (gfx950 has 160 KiB per workgroup)
   B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -351,18 +353,25 @@ int ksx_launch(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mto
   return B7_OK;
 }
 
-int ksx_dispatch(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
-                 const double *alpha, double meanc, double *out, double *mu) {
+template <int KERN>
+int ksx_dispatch_k(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
+                   const double *alpha, double meanc, double *out, double *mu) {
   switch (c->dpad) {
-    case 4: return ksx_launch<4>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 8: return ksx_launch<8>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 16: return ksx_launch<16>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 32: return ksx_launch<32>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 48: return ksx_launch<48>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 64: return ksx_launch<64>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 96: return ksx_launch<96>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+    case 4: return ksx_launch<4, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+    case 8: return ksx_launch<8, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+    case 16: return ksx_launch<16, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+    case 32: return ksx_launch<32, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+    case 48: return ksx_launch<48, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+    case 64: return ksx_launch<64, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+    case 96: return ksx_launch<96, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
     default: return b7_fail(c, B7_ERR_UNSUPPORTED, "covariance kernel: dpad %d is not a built class", c->dpad);
   }
+}
+
+int ksx_dispatch(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
+                 const double *alpha, double meanc, double *out, double *mu) {
+  if (c->kernel == B7_KERNEL_MATERN52) return ksx_dispatch_k<B7_KERNEL_MATERN52>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+  return ksx_dispatch_k<B7_KERNEL_ARDSE>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
 }
 
 }  // namespace

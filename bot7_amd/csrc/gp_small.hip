@@ -96,7 +96,8 @@ __device__ __forceinline__ void zero_block(double *X) {
 // x (z .* w)' on MFMA exactly as ksx_kernel forms it: A fragments are the raw rows, B fragments the raw columns' rows times w
 // (the product rounded once, as prep_obs_kernel rounds z .* w), a chain of v_mfma_f64_16x16x4 over the k-steps = the ascending
 // fma chain over the (zero padded) dimensions; ks = dpad / 4 steps hold anything.  A sub-tile wholly in the padding is not
-// computed.
+// computed.  KERN: the covariance kernel (B7_KERNEL_*, ksx_exp.h cov_nonpos4).
+template <int KERN>
 __device__ __forceinline__ void k_tile_vals(const double *__restrict__ obs, const double (&wq)[8], const double *__restrict__ hn,
                                             const double *__restrict__ tab, int I0, int J0, int N, double noise, int it, int jt,
                                             int ks, double (&v)[4]) {
@@ -128,7 +129,7 @@ __device__ __forceinline__ void k_tile_vals(const double *__restrict__ obs, cons
   double arg[4], kv[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) arg[r] = (c[r] - hn[I0 + 16 * it + lq + 4 * r]) - hj;
-  amp_exp_nonpos4(arg, tab, kv);
+  cov_nonpos4<KERN>(arg, tab, kv);
   // all four exponentials exist HERE, side by side: without this the optimiser sinks each of them into its own lane-divergent
   // "not padding" branch below and the four 14-deep chains run one after the other (a sub-tile took 2000 cycles, not 900)
   asm volatile("" : "+v"(kv[0]), "+v"(kv[1]), "+v"(kv[2]), "+v"(kv[3]));
@@ -213,7 +214,7 @@ __device__ __forceinline__ void store_zero_block(double *__restrict__ dst, int64
 // TWO: N > 64 (two 64-blocks).  A template parameter, not a run-time test: the kernel runs every instruction once, out of a cold
 // instruction cache, and each block of code it has to jump over is a fetch from memory (a one-block evaluation that carried
 // the two-block phases as untaken branches was 0.9 us slower).
-template <int MODE, bool TWO>
+template <int MODE, bool TWO, int KERN>
 __global__ void __launch_bounds__(GS_THREADS) gp_small_kernel(GsArgs a, GsInline hin) {
   extern __shared__ __align__(16) double sm[];
   __shared__ int inf[4];
@@ -317,7 +318,7 @@ __global__ void __launch_bounds__(GS_THREADS) gp_small_kernel(GsArgs a, GsInline
   {
     constexpr int R1_I[8] = {0, 1, 2, 3, 1, 2, 3, 2}, R1_J[8] = {0, 0, 0, 0, 1, 1, 1, 2};
     double kv[4];
-    k_tile_vals(obs, wq, hn, tab, 0, 0, N, noise, R1_I[wave], R1_J[wave], ks, kv);
+    k_tile_vals<KERN>(obs, wq, hn, tab, 0, 0, N, noise, R1_I[wave], R1_J[wave], ks, kv);
     tile_put(B1, R1_I[wave], R1_J[wave], kv);
   }
   GS_STAMP(3);
@@ -326,7 +327,7 @@ __global__ void __launch_bounds__(GS_THREADS) gp_small_kernel(GsArgs a, GsInline
     constexpr int R1_I[8] = {0, 1, 2, 3, 1, 2, 3, 2}, R1_J[8] = {0, 0, 0, 0, 1, 1, 1, 2};
     double kv2[4];
     GS_STAMP(14);
-    k_tile_vals(obs, wq, hn, tab, 0, 0, N, noise, R1_I[wave], R1_J[wave], ks, kv2);
+    k_tile_vals<KERN>(obs, wq, hn, tab, 0, 0, N, noise, R1_I[wave], R1_J[wave], ks, kv2);
     tile_put(B1, R1_I[wave], R1_J[wave], kv2);
     GS_STAMP(15);
     if (blockIdx.x == 0 && lane == 0) b7_gs_stamps[16 + wave] = __builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);  // HW_ID.SIMD_ID
@@ -358,7 +359,7 @@ __global__ void __launch_bounds__(GS_THREADS) gp_small_kernel(GsArgs a, GsInline
       lower_tile(job - 16, it, jt);
     }
     double kv[4];
-    k_tile_vals(obs, wq, hn, tab, I0, J0, N, noise, it, jt, ks, kv);
+    k_tile_vals<KERN>(obs, wq, hn, tab, I0, J0, N, noise, it, jt, ks, kv);
     if (job >= 16 && job < 22) {
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) ks22[(job - 16) * 256 + rr * 64 + lane] = kv[rr];
@@ -449,7 +450,7 @@ __global__ void __launch_bounds__(GS_THREADS) gp_small_kernel(GsArgs a, GsInline
 #pragma unroll
       for (int k4 = 0; k4 < 16; ++k4) av[k4] = ar[4 * k4], bv[k4] = br[4 * k4];
       if (q >= K22_STASH) {
-        k_tile_vals(obs, wq, hn, tab, 64, 64, N, noise, it, jt, ks, kv);  // row strip 3 (N > 112): formed here
+        k_tile_vals<KERN>(obs, wq, hn, tab, 64, 64, N, noise, it, jt, ks, kv);  // row strip 3 (N > 112): formed here
       } else {
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) kv[rr] = ks22[q * 256 + rr * 64 + lane];
@@ -689,27 +690,32 @@ int ensure_gs_table(b7_ctx *c) {
   return B7_OK;
 }
 
-template <int MODE, bool TWO>
+template <int MODE, bool TWO, int KERN>
 int gs_launch2(b7_ctx *c, const GsArgs &a, const double *hyp_host) {
   B7_TRY(ensure_gs_table(c));
   const size_t lds = sizeof(double) * GS_LDS_DOUBLES;
   // the opt-in to > 64 KiB of dynamic LDS is per device: once per process AND device (a process may hold contexts on several)
   static bool attr_done[64] = {false};
   if (c->device >= 64 || !attr_done[c->device]) {
-    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(gp_small_kernel<MODE, TWO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(gp_small_kernel<MODE, TWO, KERN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (c->device < 64) attr_done[c->device] = true;
   }
   GsInline hin = {};
   GsArgs k = a;
   k.use_inline = (a.B == 1 && hyp_host != nullptr) ? 1 : 0;
   for (int i = 0; k.use_inline && i < a.d + 3; ++i) hin.v[i] = hyp_host[i];
-  hipLaunchKernelGGL((gp_small_kernel<MODE, TWO>), dim3(a.B), dim3(GS_THREADS), lds, c->stream, k, hin);
+  hipLaunchKernelGGL((gp_small_kernel<MODE, TWO, KERN>), dim3(a.B), dim3(GS_THREADS), lds, c->stream, k, hin);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
+template <int MODE, int KERN>
+int gs_launch_k(b7_ctx *c, const GsArgs &a, const double *hyp_host) {
+  return a.N > NB ? gs_launch2<MODE, true, KERN>(c, a, hyp_host) : gs_launch2<MODE, false, KERN>(c, a, hyp_host);
+}
 template <int MODE>
 int gs_launch(b7_ctx *c, const GsArgs &a, const double *hyp_host) {
-  return a.N > NB ? gs_launch2<MODE, true>(c, a, hyp_host) : gs_launch2<MODE, false>(c, a, hyp_host);
+  return c->kernel == B7_KERNEL_MATERN52 ? gs_launch_k<MODE, B7_KERNEL_MATERN52>(c, a, hyp_host)
+                                         : gs_launch_k<MODE, B7_KERNEL_ARDSE>(c, a, hyp_host);
 }
 
 }  // namespace

@@ -217,6 +217,12 @@ int b7_group_gp_set_opts(b7_group *g, const b7_gp_opts *opts) {
   return B7_OK;
 }
 
+int b7_group_gp_set_kernel(b7_group *g, int kernel) {
+  if (!g) return B7_ERR_INVALID;
+  for (size_t i = 0; i < g->ctx.size(); ++i) G_TRY(g, (int)i, b7_gp_set_kernel(g->ctx[i], kernel));
+  return B7_OK;
+}
+
 // ---- the sharded candidate grid -------------------------------------------------------------------------------------
 int b7_group_grid_sobol(b7_group *g, int64_t size, int dims, int64_t skip, const double *mins, const double *maxes) {
   if (!g) return B7_ERR_INVALID;

@@ -54,10 +54,16 @@ __host__ __device__ constexpr int kp_lds_doubles(int nt) {
 // two workgroups per CU (four waves per SIMD: <= 128 registers) for the narrow classes up to seven row strips -- where two LDS
 // copies of a fit fit as well --: twice the waves to hide the exponential's dependent chain behind, and 16-candidate strips
 // dealt in units half the size
-__host__ __device__ constexpr int kp_waves_per_simd(int dpad, int nt) { return (dpad <= 8 && nt <= 7) ? 4 : 2; }
+// (the Matern-5/2 epilogue holds more registers across its chain: at six and seven row strips it spilled under the 128-register
+// bound, so those two instances take the 256 of two waves per SIMD -- the launcher reads the register count and goes to one
+// workgroup per CU)
+__host__ __device__ constexpr int kp_waves_per_simd(int dpad, int nt, int kern) {
+  return (dpad <= 8 && nt <= (kern == B7_KERNEL_ARDSE ? 7 : 5)) ? 4 : 2;
+}
 
-template <int DPAD, int NT>
-__global__ void __launch_bounds__(KP_THREADS) __attribute__((amdgpu_waves_per_eu(kp_waves_per_simd(DPAD, NT), 4)))
+// KERN: the covariance kernel (B7_KERNEL_*, ksx_exp.h cov_nonpos4)
+template <int DPAD, int NT, int KERN>
+__global__ void __launch_bounds__(KP_THREADS) __attribute__((amdgpu_waves_per_eu(kp_waves_per_simd(DPAD, NT, KERN), 4)))
 kpost_small_kernel(KpArgs a) {
   constexpr int KS = DPAD / 4;
   extern __shared__ __align__(16) double sm[];
@@ -134,7 +140,7 @@ kpost_small_kernel(KpArgs a) {
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) arg[r] = (c[r] - hq) - hk[r];  // = -1/2 (((-2 c) + xs) + zs), utils/math.lua:82
-      amp_exp_nonpos4(arg, tab, kv);
+      cov_nonpos4<KERN>(arg, tab, kv);
       // all four exponentials exist HERE: left alone, the optimiser sinks each one in front of the k-step that consumes it
       // and the four 14-deep chains run one after the other between the MFMAs
       asm volatile("" : "+v"(kv[0]), "+v"(kv[1]), "+v"(kv[2]), "+v"(kv[3]));
@@ -193,14 +199,14 @@ int ensure_kp_table(b7_ctx *c) {
   return B7_OK;
 }
 
-template <int DPAD, int NT>
+template <int DPAD, int NT, int KERN>
 int kp_launch(b7_ctx *c, const KpArgs &a) {
   B7_TRY(ensure_kp_table(c));
   const size_t lds = sizeof(double) * (size_t)kp_lds_doubles<DPAD>(NT);
   // the opt-in to > 64 KiB of dynamic LDS is per device: once per instantiation AND device (a process may hold contexts on several)
   static bool attr_done[64] = {false};
   if (c->device >= 64 || !attr_done[c->device]) {
-    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kpost_small_kernel<DPAD, NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kpost_small_kernel<DPAD, NT, KERN>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds));
     if (c->device < 64) attr_done[c->device] = true;
   }
@@ -209,7 +215,7 @@ int kp_launch(b7_ctx *c, const KpArgs &a) {
   static int per_cu_cache = 0;  // per instantiation
   if (per_cu_cache == 0) {
     hipFuncAttributes fa;
-    B7_HIP(c, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kpost_small_kernel<DPAD, NT>)));
+    B7_HIP(c, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kpost_small_kernel<DPAD, NT, KERN>)));
     per_cu_cache = (fa.numRegs <= 128 && 2 * (lds + 512) <= (size_t)160 * 1024) ? 2 : 1;
   }
   const int64_t nstrips = (a.M + 15) / 16;
@@ -217,30 +223,34 @@ int kp_launch(b7_ctx *c, const KpArgs &a) {
   const int64_t need = (nstrips + (KP_THREADS / 64) - 1) / (KP_THREADS / 64);
   if (gx > need) gx = need;
   if (gx < 1) gx = 1;
-  hipLaunchKernelGGL((kpost_small_kernel<DPAD, NT>), dim3((unsigned)gx, (unsigned)a.S), dim3(KP_THREADS), lds, c->stream, a);
+  hipLaunchKernelGGL((kpost_small_kernel<DPAD, NT, KERN>), dim3((unsigned)gx, (unsigned)a.S), dim3(KP_THREADS), lds, c->stream, a);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
 
 // the instance for ceil(N / 16) row strips: all eight for the narrow classes (d <= 8: the regime the kernel is for), rounded up
 // to 4 / 8 for the wide ones (their padding strips multiply zeros: same bits, a bounded waste, a quarter of the binary)
-template <int DPAD>
-int kp_dispatch(b7_ctx *c, const KpArgs &a) {
+template <int DPAD, int KERN>
+int kp_dispatch_k(b7_ctx *c, const KpArgs &a) {
   const int nt = (a.N + 15) / 16;
   if constexpr (DPAD <= 8) {
     switch (nt) {
-      case 1: return kp_launch<DPAD, 1>(c, a);
-      case 2: return kp_launch<DPAD, 2>(c, a);
-      case 3: return kp_launch<DPAD, 3>(c, a);
-      case 4: return kp_launch<DPAD, 4>(c, a);
-      case 5: return kp_launch<DPAD, 5>(c, a);
-      case 6: return kp_launch<DPAD, 6>(c, a);
-      case 7: return kp_launch<DPAD, 7>(c, a);
-      default: return kp_launch<DPAD, 8>(c, a);
+      case 1: return kp_launch<DPAD, 1, KERN>(c, a);
+      case 2: return kp_launch<DPAD, 2, KERN>(c, a);
+      case 3: return kp_launch<DPAD, 3, KERN>(c, a);
+      case 4: return kp_launch<DPAD, 4, KERN>(c, a);
+      case 5: return kp_launch<DPAD, 5, KERN>(c, a);
+      case 6: return kp_launch<DPAD, 6, KERN>(c, a);
+      case 7: return kp_launch<DPAD, 7, KERN>(c, a);
+      default: return kp_launch<DPAD, 8, KERN>(c, a);
     }
   } else {
-    return nt <= 4 ? kp_launch<DPAD, 4>(c, a) : kp_launch<DPAD, 8>(c, a);
+    return nt <= 4 ? kp_launch<DPAD, 4, KERN>(c, a) : kp_launch<DPAD, 8, KERN>(c, a);
   }
+}
+template <int DPAD>
+int kp_dispatch(b7_ctx *c, const KpArgs &a) {
+  return c->kernel == B7_KERNEL_MATERN52 ? kp_dispatch_k<DPAD, B7_KERNEL_MATERN52>(c, a) : kp_dispatch_k<DPAD, B7_KERNEL_ARDSE>(c, a);
 }
 
 }  // namespace

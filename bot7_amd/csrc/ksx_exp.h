@@ -1,8 +1,9 @@
-// The exponential of the ARD-SE covariance, shared by covar.hip (K(X*,X), K(X,X)) and nll_small.hip (the fused small-N
-// likelihood): identical code, so identical bits.
+// The ARD-SE and ARD Matern-5/2 covariances, shared by covar.hip (K(X*,X), K(X,X)), gp_small.hip, kpost_small.hip and
+// nll_small.hip (the fused small-N kernels): identical code, so identical bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "bot7hip.h"
 #include "exp_table.h"
 #ifndef B7_KSX_ABLATE
 #define B7_KSX_ABLATE 0
@@ -75,5 +76,87 @@ B7_STAGE();
   B7_STAGE();
 #pragma unroll
   for (int i = 0; i < 4; ++i) out[i] = __builtin_ldexp(__builtin_fma(t[i], q[i], t[i]), n[i] >> 7);
+}
+
+// ARD Matern-5/2 on the same argument arg = -D/2 (D = sum_k (x_k - z_k)^2 / lenscale_sq_k, clamped at 0 as above):
+//   s = sqrt(5 D) = sqrt(-10 a),  k = amp (1 + s + s^2/3) exp(-s)
+// with exp(-s) by the table exponential above and these differences:
+//   s   = min(sqrt(-10 a), 1000)               IEEE sqrt (correctly rounded).  The clamp keeps padding's s ~ 3e150 (zs/2 = 1e300)
+//                                              out of the polynomial, where it would overflow: amp m exp(-1000) is exactly 0
+//   m   = 1 + s (1 + s/3)                      the polynomial, Horner
+//   out = 2^(n >> 7) * (m * T[n & 127] (1 + q))            m goes on BEFORE the power of two, so a normal result for s in
+//                                              ~700..760 is not built from a subnormal amp exp(-s): one rounding, in v_ldexp
+// NaN and inf in arg come through the same carrier on q.  Error: the exponential's and m's few ulp, plus the inherent 0.75 s ulp
+// of exp(-s) that comes from rounding s itself (-10 a and the sqrt: 1/4 + 1/2 ulp of s).  k(x, x) = amp as for the SE, so the
+// posterior-variance kernels need no form of their own.  Same four-at-a-time staging as amp_exp_nonpos4.  Measured on the
+// device against mpmath (tests/test_gpu_matern.py, s in [0, 2000], amp = 2^-40 .. 2^40, both paths): <= s + 2.14 ulp where the
+// result is normal, <= 2^-1073 absolute beyond the same relative s term where it is subnormal.
+__device__ __forceinline__ void amp_matern52_nonpos4(const double (&arg)[4], const double *__restrict__ tab, double (&out)[4]) {
+  double a[4], s[4], nb[4], nf[4], r[4], p[4], q[4], t[4], m[4];
+  int n[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] = __builtin_fmin(arg[i], 0.0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) s[i] = __builtin_sqrt(-10.0 * a[i]);
+  B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) s[i] = __builtin_fmin(s[i], 1000.0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) nb[i] = __builtin_fma(s[i], -B7_EXP_INV, B7_EXP_MAGIC);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    n[i] = __double2loint(nb[i]);
+    t[i] = tab[n[i] & 127];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) nf[i] = nb[i] - B7_EXP_MAGIC;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = __builtin_fma(nf[i], -B7_EXP_HEAD, -s[i]);
+B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = __builtin_fma(nf[i], -B7_EXP_TAIL, r[i]);
+  B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) p[i] = __builtin_fma(r[i], 1.0 / 120.0, 1.0 / 24.0);
+B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) p[i] = __builtin_fma(p[i], r[i], 1.0 / 6.0);
+  B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) p[i] = __builtin_fma(p[i], r[i], 0.5);
+B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) p[i] = __builtin_fma(p[i], r[i], 1.0);
+  B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) q[i] = r[i] * p[i];
+B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m[i] = __builtin_fma(s[i], 1.0 / 3.0, 1.0);
+  B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m[i] = __builtin_fma(s[i], m[i], 1.0);
+B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) q[i] = __builtin_fma(arg[i], 0.0, q[i]);
+  B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) t[i] = __builtin_fma(t[i], q[i], t[i]);
+B7_STAGE();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) out[i] = __builtin_ldexp(m[i] * t[i], n[i] >> 7);
+}
+
+// The covariance of the context's kernel (b7_gp_set_kernel), four entries at a time.  KERN is a template parameter of every
+// kernel that forms covariance entries (ksx_kernel, gp_small_kernel, kpost_small_kernel, nll_small_kernel) and of their
+// launchers, never a run-time branch: the ARD-SE instances are the code they were before the Matern branch existed.  The small
+// kernels and the general path share this one function, so they give the same bits under either kernel.
+template <int KERN>
+__device__ __forceinline__ void cov_nonpos4(const double (&arg)[4], const double *__restrict__ tab, double (&out)[4]) {
+  static_assert(KERN == B7_KERNEL_ARDSE || KERN == B7_KERNEL_MATERN52, "covariance kernel");
+  if constexpr (KERN == B7_KERNEL_ARDSE)
+    amp_exp_nonpos4(arg, tab, out);
+  else
+    amp_matern52_nonpos4(arg, tab, out);
 }
 

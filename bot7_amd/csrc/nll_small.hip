@@ -45,7 +45,8 @@ __device__ __forceinline__ void identity_corner(double *A) {
 // over the eight k-steps is the ascending fma chain over the 32 (zero padded) dimensions.
 // The sub-tiles are dealt round-robin to the four waves.  A diagonal block (I0 == J0) gets its ten sub-tiles on and below
 // the diagonal only (diag_core reads nothing above: potrf_diag.h:87); sub-tiles that lie wholly in the padding are written,
-// not computed -- early in a run (N of a few dozen) that is most of them.
+// not computed -- early in a run (N of a few dozen) that is most of them.  KERN: the covariance kernel (ksx_exp.h cov_nonpos4).
+template <int KERN>
 __device__ __forceinline__ void k_block(const double *__restrict__ obs, const double *__restrict__ w, const double *__restrict__ hn,
                                         const double *__restrict__ tab, int I0, int J0, int N, double noise,
                                         double *__restrict__ T) {
@@ -81,7 +82,7 @@ __device__ __forceinline__ void k_block(const double *__restrict__ obs, const do
     double arg[4], kv[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) arg[r] = (c[r] - hn[I0 + 16 * it + lq + 4 * r]) - hj;
-    amp_exp_nonpos4(arg, tab, kv);
+    cov_nonpos4<KERN>(arg, tab, kv);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = 16 * it + lq + 4 * r, gi = I0 + i;
@@ -114,6 +115,7 @@ struct NllSmallInline {  // the hypers of a single evaluation, passed in the ker
   double v[35];
 };
 
+template <int KERN>
 __global__ void __launch_bounds__(256)
     nll_small_kernel(const double *__restrict__ xobs, const double *__restrict__ y, int N, int d, const double *__restrict__ hyp_mem,
                      int B, double *__restrict__ terms, int *__restrict__ info, unsigned *__restrict__ done, NllSmallInline hin,
@@ -190,10 +192,10 @@ __global__ void __launch_bounds__(256)
   }
   __syncthreads();
   STAMP();  // 3
-  k_block(obs, w, hn, tab, 0, 0, N, noise, A11);
+  k_block<KERN>(obs, w, hn, tab, 0, 0, N, noise, A11);
   if (npad == 128) {
-    k_block(obs, w, hn, tab, 64, 0, N, noise, A21);
-    k_block(obs, w, hn, tab, 64, 64, N, noise, A22);
+    k_block<KERN>(obs, w, hn, tab, 64, 0, N, noise, A21);
+    k_block<KERN>(obs, w, hn, tab, 64, 64, N, noise, A22);
   }
   __syncthreads();  // the observation image is dead: its place becomes X
   STAMP();  // 4
@@ -327,6 +329,26 @@ int ensure_small_table(b7_ctx *c) {
   return B7_OK;
 }
 
+template <int KERN>
+int nll_small_launch(b7_ctx *c, int B, const double *hyp_dev, const double *hyp_host, double *terms_dev, int *info_dev,
+                     unsigned *done_dev) {
+  B7_TRY(ensure_small_table(c));
+  const size_t lds = sizeof(double) * NLL_SMALL_LDS_DOUBLES;
+  // the opt-in to > 64 KiB of dynamic LDS is per device: once per process AND device (a process may hold contexts on several)
+  static bool attr_done[64] = {false};
+  if (c->device >= 64 || !attr_done[c->device]) {
+    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(nll_small_kernel<KERN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (c->device < 64) attr_done[c->device] = true;
+  }
+  NllSmallInline hin = {};
+  const int use_inline = (B == 1 && hyp_host != nullptr) ? 1 : 0;
+  for (int k = 0; use_inline && k < c->dfit + 3; ++k) hin.v[k] = hyp_host[k];
+  hipLaunchKernelGGL(nll_small_kernel<KERN>, dim3(B), dim3(256), lds, c->stream, (const double *)c->xobs.p, (const double *)c->ybuf.p, c->N,
+                     c->dfit, hyp_dev, B, terms_dev, info_dev, B == 1 ? done_dev : nullptr, hin, use_inline);
+  B7_HIP(c, hipGetLastError());
+  return B7_OK;
+}
+
 }  // namespace
 
 bool nll_small_applies(const b7_ctx *c) { return c->Npad <= 128 && c->dfit <= 32 && c->ycols == 1; }
@@ -337,19 +359,7 @@ bool nll_small_applies(const b7_ctx *c) { return c->Npad <= 128 && c->dfit <= 32
 int launch_nll_small(b7_ctx *c, int B, const double *hyp_dev, const double *hyp_host, double *terms_dev, int *info_dev,
                      unsigned *done_dev) {
   PhaseScope ps(c, "potrf");
-  B7_TRY(ensure_small_table(c));
-  const size_t lds = sizeof(double) * NLL_SMALL_LDS_DOUBLES;
-  // the opt-in to > 64 KiB of dynamic LDS is per device: once per process AND device (a process may hold contexts on several)
-  static bool attr_done[64] = {false};
-  if (c->device >= 64 || !attr_done[c->device]) {
-    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(nll_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (c->device < 64) attr_done[c->device] = true;
-  }
-  NllSmallInline hin = {};
-  const int use_inline = (B == 1 && hyp_host != nullptr) ? 1 : 0;
-  for (int k = 0; use_inline && k < c->dfit + 3; ++k) hin.v[k] = hyp_host[k];
-  hipLaunchKernelGGL(nll_small_kernel, dim3(B), dim3(256), lds, c->stream, (const double *)c->xobs.p, (const double *)c->ybuf.p, c->N,
-                     c->dfit, hyp_dev, B, terms_dev, info_dev, B == 1 ? done_dev : nullptr, hin, use_inline);
-  B7_HIP(c, hipGetLastError());
-  return B7_OK;
+  return c->kernel == B7_KERNEL_MATERN52
+             ? nll_small_launch<B7_KERNEL_MATERN52>(c, B, hyp_dev, hyp_host, terms_dev, info_dev, done_dev)
+             : nll_small_launch<B7_KERNEL_ARDSE>(c, B, hyp_dev, hyp_host, terms_dev, info_dev, done_dev);
 }

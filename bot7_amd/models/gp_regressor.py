@@ -1,5 +1,12 @@
-"""HIP-backed stand-in for gp.models.gp_regressor with the ardse kernel, GaussianNoise_iso noise model and
+"""HIP-backed stand-in for gp.models.gp_regressor with the ardse kernel (or ardmatern52), GaussianNoise_iso noise model and
 constant mean -- the defaults bots/bayesopt.lua:39-45 selects.
+
+config.kernel (bots/bayesopt.lua:41, default 'ardse'):
+    'ardse'         K = amp exp(-D/2)
+    'ardmatern52'   K = amp (1 + s + s^2/3) exp(-s),  s = sqrt(5 D)   (ARD Matern-5/2, Snoek et al. 2012)
+with D = sum_k (x_k - z_k)^2 / lenscale_sq_k under the same hyper vector.  The kernel is context state (b7_gp_set_kernel): the
+model sets it before every library call that fits, predicts, evaluates a likelihood, fantasizes or appends, so one context
+can serve an SE model and a Matern model in turn.
 
 The reference's class lives in the un-vendored `gp` package (models/init.lua:15); what is mirrored here is the
 protocol its callers use:
@@ -23,7 +30,7 @@ is what the fixed-hyper parity tests and the benchmark use."""
 import numpy as np
 
 from .abstract import abstract
-from .._lib import default_context
+from .._lib import KERNELS, default_context
 from ..grids.abstract import DeviceGrid
 
 
@@ -35,8 +42,8 @@ class gp_regressor(abstract):
         self.kernel = self.config.get("kernel", "ardse")              # bots/bayesopt.lua:41
         self.nzModel = self.config.get("nzModel", "GaussianNoise_iso")  # :42
         self.mean = self.config.get("mean", "constant")               # :43
-        if (self.kernel, self.nzModel, self.mean) != ("ardse", "GaussianNoise_iso", "constant"):
-            raise NotImplementedError("only ardse + GaussianNoise_iso + constant mean are built")
+        if (self.kernel not in KERNELS or (self.nzModel, self.mean) != ("GaussianNoise_iso", "constant")):
+            raise NotImplementedError("only ardse | ardmatern52 + GaussianNoise_iso + constant mean are built")
         self._ctx = context
         self.hyp = None
         self.last_fit = None
@@ -46,6 +53,17 @@ class gp_regressor(abstract):
         if self._ctx is None:
             self._ctx = default_context()
         return self._ctx
+
+    def _use_kernel(self):
+        """The context's covariance kernel := this model's (a no-op when it is that already).  A context without kernels (a host
+        stand-in) serves ARD-SE only."""
+        ctx = self.ctx
+        setk = getattr(ctx, "gp_set_kernel", None)
+        if setk is not None:
+            setk(self.kernel)
+        elif self.kernel != "ardse":
+            raise NotImplementedError("%s has no covariance kernel but ardse" % type(ctx).__name__)
+        return ctx
 
     # ---- hyper-parameters -------------------------------------------------------------------------
     def init(self, X_obs, Y_obs):
@@ -104,6 +122,7 @@ class gp_regressor(abstract):
     def _make_resident(self, X, Y):
         """The observations on the device (b7_gp_set_data), once per data set: a cheap look first (addresses, shapes, the last
         entries, the context's fit token), the content hash only when that differs."""
+        self._use_kernel()
         fast = (X.__array_interface__["data"][0], X.shape, Y.__array_interface__["data"][0], float(X[-1, -1]), float(Y[-1, 0]),
                 self.ctx.fit_token)
         if getattr(self, "_resident_fast", None) != fast:
@@ -126,7 +145,7 @@ class gp_regressor(abstract):
         ctx = self.ctx
         one = getattr(ctx, "gp_nll1", None)
 
-        data_key = self._resident_key
+        data_key = self._resident_key   # (_make_resident set this model's kernel: nothing else calls the context during an update)
 
         def f(t, _args):
             t = np.asarray(t, dtype=np.float64).ravel()
@@ -237,6 +256,7 @@ class gp_regressor(abstract):
         C, d = len(self._chain_thetas), X.shape[1]
         lo, hi = self._bounds(X, Y)
         key = self._data_key(X, Y)
+        self._use_kernel()
         if getattr(self, "_resident_key", None) != (key, self.ctx.fit_token):
             self.ctx.gp_set_data(X, Y)
             self._resident_key = (key, self.ctx.fit_token)
@@ -316,6 +336,7 @@ class gp_regressor(abstract):
             nll, jit, info = self.ctx.gp_nll_batch(hyp["lenscale_sq"], hyp["amp"], hyp["noise"], hyp["mean"], want_info=True)
             self.last_fit = {"nll": nll, "jitter": float(jit[0]), "info": int(info[0])}
             return nll
+        self._use_kernel()
         out = self.ctx.gp_fit(X, Y, hyp["lenscale_sq"], hyp["amp"], hyp["noise"], hyp["mean"], want_nll=True)
         self.last_fit = out
         return out["nll"]
@@ -330,6 +351,7 @@ class gp_regressor(abstract):
             hyp = self.init(X_obs, Y_obs)
         X = np.atleast_2d(np.asarray(X_obs, dtype=np.float64))
         Y = np.asarray(Y_obs, dtype=np.float64).reshape(X.shape[0], -1)
+        self._use_kernel()   # (a change of kernel moves the fit token: the append below is then not taken)
         key = (tuple(np.asarray(hyp["lenscale_sq"], dtype=np.float64).ravel()), hyp["amp"], hyp["noise"], hyp["mean"])
         prev = getattr(self, "_prev", None)
         # only a clean factor is extended: after a jittered fit (or the chol(I) fallback) the reference refactors
@@ -372,6 +394,7 @@ class gp_regressor(abstract):
         X = np.atleast_2d(np.asarray(X_obs, dtype=np.float64))
         Y = np.asarray(Y_obs, dtype=np.float64).reshape(X.shape[0], -1)
         key = self._data_key(X, Y)
+        self._use_kernel()
         if getattr(self, "_resident_key", None) != (key, self.ctx.fit_token):
             self.ctx.gp_set_data(X, Y)
             self._resident_key = (key, self.ctx.fit_token)

@@ -58,6 +58,7 @@ class bayesopt(abstract):
             # a candidate set sharded over GPUs: every shard scores its rows, ONE exchange names the winner in the union
             # (b7_eval_nominate with a communicator / b7_group_eval_nominate); ranks run this loop in lock step
             hyps = [model.parse_hypers(model.sample_hypers(X_obs, Y_obs, None, None, True)) for _ in range(nSamples)]
+            X_hid.set_kernel(getattr(model, "kernel", "ardse"))   # config.model.kernel on every context the nomination uses
             X_hid.stage_data(X_obs, Y_obs)
             sp = spec(Y_obs)
             val, idx = X_hid.eval_nominate(hyps, sp)

@@ -39,8 +39,10 @@ def run(ctx, trials=None, on_trial=None, out=None, **over):
     config = {"bot": {"verbose": 0, "budget": budget, "nInitial": int(cfg["nInitial"]), "nSamples": int(cfg["nSamples"]),
                       "seed": int(cfg["bot_seed"])},
               "grid": {"type": "sobol", "size": int(cfg["grid_size"]), "dims": d}, "score": {"type": cfg["score"]}}
-    model = bot7_amd.models.gp_regressor({"sample": True, "nBurnin": int(cfg["nBurnin"]), "seed": int(cfg["model_seed"])},
-                                         context=ctx)
+    mcfg = {"sample": True, "nBurnin": int(cfg["nBurnin"]), "seed": int(cfg["model_seed"])}
+    if "kernel" in cfg:   # optional: the model's covariance kernel (config.model.kernel, bots/bayesopt.lua:41; default ardse)
+        mcfg["kernel"] = cfg["kernel"]
+    model = bot7_amd.models.gp_regressor(mcfg, context=ctx)
     # the candidate grid on the context (grids/sobol.lua:58-90 defaults: skip 1, no affine map), handed to the bot as a
     # sharded set with a world of one: nominations are global indices, the steal is b7_nominate_commit
     ctx.grid_sobol(int(cfg["grid_size"]), d, 1, download=False)

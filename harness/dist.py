@@ -85,6 +85,14 @@ class ShardedScorer(object):
     def stage_data(self, X_obs, Y_obs):
         self.ctx.gp_set_data(X_obs, Y_obs)
 
+    def set_kernel(self, kernel):
+        """The covariance kernel of this rank's fits (Context.gp_set_kernel); a context without kernels serves 'ardse' only."""
+        setk = getattr(self.ctx, "gp_set_kernel", None)
+        if setk is not None:
+            setk(kernel)
+        elif kernel != "ardse":
+            raise NotImplementedError("%s has no covariance kernel but ardse" % type(self.ctx).__name__)
+
     def commit(self, idx1_global, device=None, group=None):
         """bots/abstract.lua:118 steal(pending, candidates, idx) on the sharded set: the nominee's coordinates on every
         rank, its stable deletion on the owner, the offset shift behind it.  Product path: ONE C-ABI call,
@@ -165,6 +173,9 @@ class GroupCandidates(object):
 
     def stage_data(self, X_obs, Y_obs):
         self.group.gp_set_data(X_obs, Y_obs)
+
+    def set_kernel(self, kernel):
+        self.group.gp_set_kernel(kernel)     # every member (b7_group_gp_set_kernel)
 
     def eval_nominate(self, hyps, spec, device=None, group=None):
         return self.group.eval_nominate(hyps, **spec)

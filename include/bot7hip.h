@@ -106,7 +106,7 @@ int b7_grid_remove(b7_ctx *ctx, int64_t idx1, double *row_out);
  * in the order given. */
 int b7_grid_remove_rows(b7_ctx *ctx, const int64_t *idx1, int64_t n, double *rows_out);
 
-/* ---- model: gp_regressor + ardse + GaussianNoise_iso + constant mean (bots/bayesopt.lua:40-43) - */
+/* ---- model: gp_regressor + ardse | ardmatern52 + GaussianNoise_iso + constant mean (bots/bayesopt.lua:40-43) - */
 
 /* Replaces the table model:parse_hypers returns (bots/bayesopt.lua:75).  lenscale_sq[k] is what
  * utils.math.pdist receives as `lenscale` (it divides squared differences, utils/math.lua:72). */
@@ -128,9 +128,22 @@ typedef struct {
 int b7_gp_default_opts(b7_gp_opts *out);
 int b7_gp_set_opts(b7_ctx *ctx, const b7_gp_opts *opts);
 
+/* The covariance kernel (bots/bayesopt.lua:41 config.model.kernel; the kernels themselves live in the absent `gp` package).
+ * With D = sum_k (x_k - z_k)^2 / lenscale_sq_k, the same distance for both, and the same b7_hyp layout:
+ *   B7_KERNEL_ARDSE      K = amp * exp(-D/2)                                 (the default)
+ *   B7_KERNEL_MATERN52   K = amp * (1 + s + s^2/3) * exp(-s),  s = sqrt(5 D)  (ARD Matern-5/2, Snoek et al. 2012)
+ * Every entry point below that forms a covariance uses the context's kernel; k(x, x) = amp under both.  Context state, not a
+ * field of the hyper or option structs above (hosts allocate those): a context that never calls this stays on ARD-SE.  Setting a DIFFERENT
+ * kernel drops the fit and the predictions made from it (predict, fantasize, append and download answer B7_ERR_STATE until the
+ * next fit); the resident data and grid stay.  Setting the current one again does nothing.  Unknown values: B7_ERR_INVALID.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_KERNEL_ARDSE 0
+#define B7_KERNEL_MATERN52 1
+int b7_gp_set_kernel(b7_ctx *ctx, int kernel);
+
 /* The arithmetic of model:predict's first half (call sites scores/expected_improvement.lua:63,
  * scores/confidence_bound.lua:63): K = amp*exp(-pdist(X,X,lenscale_sq)/2) + noise*I with the distance of
- * utils/math.lua:65-111; L = chol(K) with the jitter schedule of utils/math.lua:159-218 (eps <- eps*growth
+ * utils/math.lua:65-111 (the ARD-SE form: K is the context's kernel, b7_gp_set_kernel above); L = chol(K) with the jitter schedule of utils/math.lua:159-218 (eps <- eps*growth
  * added to the ORIGINAL diagonal until success, or chol(I) once eps > ||K||_F); alpha = K^-1 (Y - mean).
  * X_obs N x d (d <= 96), Y_obs N x ycols (ycols <= 256: fantasy columns share K, L and differ only in alpha).
  * Outputs (all nullable): nll_out[ycols] negative log marginal likelihood,
@@ -385,6 +398,8 @@ int b7_group_info(b7_group *g, int *n, int *uses_rccl);
 b7_ctx *b7_group_ctx(b7_group *g, int rank);
 int b7_group_set_workspace(b7_group *g, int64_t bytes);
 int b7_group_gp_set_opts(b7_group *g, const b7_gp_opts *opts);
+/* b7_gp_set_kernel on every member. */
+int b7_group_gp_set_kernel(b7_group *g, int kernel);
 /* b7_grid_sobol / _random / _upload for the whole grid: every member generates (receives) its shard; one-sided maps use
  * the column extremes of the union. */
 int b7_group_grid_sobol(b7_group *g, int64_t size, int dims, int64_t skip, const double *mins, const double *maxes);

@@ -35,6 +35,7 @@ typedef struct { const double *lenscale_sq; double amp; double noise; double mea
 typedef struct { double jitter_eps; double jitter_growth; int var_with_noise; int var_clamp; double var_min; } b7_gp_opts;
 int b7_gp_default_opts(b7_gp_opts *out);
 int b7_gp_set_opts(b7_ctx *ctx, const b7_gp_opts *opts);
+int b7_gp_set_kernel(b7_ctx *ctx, int kernel);
 int b7_gp_fit(b7_ctx *ctx, const double *X_obs, const double *Y_obs, int N, int d, int ycols, const b7_hyp *hyp, double *nll_out, double *jitter_used, int *info);
 int b7_gp_set_data(b7_ctx *ctx, const double *X_obs, const double *Y_obs, int N, int d, int ycols);
 int b7_gp_fit_hyp(b7_ctx *ctx, const b7_hyp *hyp, double *nll_out, double *jitter_used, int *info);
@@ -78,6 +79,7 @@ int b7_group_info(b7_group *g, int *n, int *uses_rccl);
 b7_ctx *b7_group_ctx(b7_group *g, int rank);
 int b7_group_set_workspace(b7_group *g, int64_t bytes);
 int b7_group_gp_set_opts(b7_group *g, const b7_gp_opts *opts);
+int b7_group_gp_set_kernel(b7_group *g, int kernel);
 int b7_group_grid_sobol(b7_group *g, int64_t size, int dims, int64_t skip, const double *mins, const double *maxes);
 int b7_group_grid_random(b7_group *g, int64_t size, int dims, uint64_t seed, const double *mins, const double *maxes);
 int b7_group_grid_onesided(b7_group *g, const double *mins, const double *maxes);
@@ -115,6 +117,8 @@ M.ERR_STATE = -4
 M.ERR_UNSUPPORTED = -5
 M.ERR_RANGE = -6
 M.ERR_COMM = -7
+M.KERNEL_ARDSE = 0
+M.KERNEL_MATERN52 = 1
 M.COMM_ID_BYTES = 128
 M.COMM_SUM = 0
 M.COMM_MAX = 1
@@ -157,11 +161,31 @@ function M.use_group(device_ids)
   M.solo  = M.ctx                       -- keep the stand-alone context alive (its finaliser would run otherwise)
   M.ctx   = C.b7_group_ctx(M.group, 0)  -- owned by the group: no finaliser
   M.forget_resident()
+  local k = M.kernel                    -- the members start on ARD-SE: the kernel chosen so far goes to all of them
+  M.kernel = M.KERNEL_ARDSE
+  M.set_kernel(k)
   return n
 end
 function M.gcheck(rc)
   if rc ~= 0 then error('bot7hip(' .. rc .. '): ' .. ffi.string(C.b7_group_last_error(M.group)), 2) end
   return rc
+end
+
+-- ---- the covariance kernel (config.model.kernel, bots/bayesopt.lua:41) ------------------------------------------------
+-- Context state (b7_gp_set_kernel; under use_group every member's, b7_group_gp_set_kernel).  The model shim sets its kernel
+-- before each call that fits, predicts or evaluates a likelihood; the library is called only on a change (which drops the fit).
+M.KERNELS = {ardse = M.KERNEL_ARDSE, ardmatern52 = M.KERNEL_MATERN52}
+M.kernel  = M.KERNEL_ARDSE
+function M.kernel_code(name)                 -- config.kernel -> B7_KERNEL_*; error() on a kernel that is not built
+  local code = M.KERNELS[name or 'ardse']
+  if code == nil then error('bot7hip: unknown covariance kernel ' .. tostring(name) .. ' (built: ardse, ardmatern52)', 2) end
+  return code
+end
+function M.set_kernel(code)
+  if code == M.kernel then return end
+  if M.group then M.gcheck(C.b7_group_gp_set_kernel(M.group, code))
+  else M.check(C.b7_gp_set_kernel(M.ctx, code)) end
+  M.kernel = code
 end
 
 -- DoubleTensor -> contiguous DoubleTensor whose storage the C call may read.  The CALLER keeps the returned tensor

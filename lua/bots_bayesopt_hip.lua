@@ -73,6 +73,7 @@ function bot:nominate(candidates)
   else
     model:stage_data(X_obs, Y_obs)   -- this rank's shard has run empty: it still refits and takes part in the exchange
   end
+  hip.set_kernel(model.kernel_code)   -- config.model.kernel on the context, or on every member of the group
   local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
   local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
   if hip.group then   -- one process, several GPUs: i indexes self.candidates, the host tensor of all candidates

@@ -1,6 +1,7 @@
 --[[
 Drop-in for gp.models.gp_regressor (ardse + GaussianNoise_iso + constant mean, bots/bayesopt.lua:39-45)
-backed by b7_gp_set_data / b7_gp_fit_hyp / b7_gp_predict.
+backed by b7_gp_set_data / b7_gp_fit_hyp / b7_gp_predict.  config.kernel = 'ardmatern52' selects the ARD Matern-5/2
+covariance instead of the default 'ardse' (same hyper vector; b7_gp_set_kernel).
 Register:  bot7.models.gp_hip = require('bot7hip.models_gp_hip')
 and select it with config.model.type = 'gp_hip' (bots/bayesopt.lua:31), or pass it as cache.model.
 Mirrors bot7_amd/models/gp_regressor.py method for method (that file is what the tests drive).
@@ -24,6 +25,8 @@ local model, parent = torch.class(title, parent)
 function model:__init(config)
   parent.__init(self)
   self.config = config or {}
+  self.kernel = self.config.kernel or 'ardse'          -- bots/bayesopt.lua:41; 'ardse' or 'ardmatern52', anything else: error()
+  self.kernel_code = hip.kernel_code(self.kernel)
   self.hyp    = nil
   self.nEvals = 0
 end
@@ -73,7 +76,10 @@ local function same_data(self, X, Y)
 end
 
 -- (X_obs, Y_obs) resident on the device; uploads only when they are not the pair already there.  Returns Y as N x c.
+-- Every fit, likelihood and posterior goes through here first: the context's covariance kernel becomes this model's
+-- (b7_gp_set_kernel through hip.set_kernel; a no-op when it is that already), so SE and Matern models can share the context.
 function model:stage_data(X_obs, Y_obs)
+  hip.set_kernel(self.kernel_code)
   local X = hip.pin(X_obs)
   local Y = hip.pin(Y_obs:dim() == 1 and Y_obs:view(-1, 1) or Y_obs)
   if not same_data(self, X, Y) then
