@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libbot7hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <map>
@@ -43,6 +44,56 @@ struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
 };
+
+// A pinned host buffer that grows on demand (b7_pin_ensure); dev: its device address when it is mapped, else null.
+struct PinBuf {
+  void *host = nullptr, *dev = nullptr;
+  size_t bytes = 0;
+};
+
+// ---- the two fixed staging blocks of a context ------------------------------------------------------------
+// What a fit reports to the host: the pivot report (first failing pivot, 1-based, 0 if none | hand-off time-out code) and the
+// likelihood terms (sum log L_ii, then r_k' alpha_k per response column).
+struct FitBlock { int info[4]; double terms[257]; };
+// An arg-max as the kernels write it: layout of score.hip's Best, whose name is part of its kernels' symbols and stays there.
+struct BestPair { double v; int64_t i; };
+// Direction numbers of the Sobol sequence (sobol.hip), uploaded into the scratch block.
+constexpr int SOBOL_DIMS = 40;  // table rows (the reference admits dims < 40, grids/sobol.lua:36)
+constexpr int SOBOL_BITS = 30;  // log_max, grids/sobol.lua:32
+struct SobolTable {
+  uint32_t v[SOBOL_DIMS][SOBOL_BITS];
+};
+
+// c->pinned: 16 KiB of pinned, device-mapped host memory.  Kernels write into it through c->pinned_dev, or a copy lands in it
+// without pageable staging; the host reads after a stream synchronisation.
+constexpr size_t B7_PINNED_BYTES = 16384;
+struct PinnedBlock {
+  FitBlock fit;                       // a fit's report (gp_api.hip: fit_hyp_core); the Bayesian linear head's, its first 16 bytes
+  alignas(256) BestPair best;            // launch_finish's arg-max, written by the kernel through the mapped address
+  alignas(4096) double fmin[256];     // f_min of several response columns on their way to the device (stage_fmin)
+  alignas(4096) double vec[B7_MAX_D + 3];  // a small vector on its way to the device: a fit's lengthscales (the one-launch fit reads
+                                           // amp, noise and mean behind them), a grid map's per-column shift / scale
+};
+static_assert(offsetof(PinnedBlock, fit) == 0 && offsetof(PinnedBlock, best) == 2304 && offsetof(PinnedBlock, fmin) == 4096 &&
+                  offsetof(PinnedBlock, vec) == 8192 && sizeof(PinnedBlock) <= B7_PINNED_BYTES,
+              "pinned block: kernels and copies address these slots");
+
+// c->scratch: 64 KiB of device memory, never regrown.
+constexpr size_t B7_SCRATCH_BYTES = 64 * 1024;
+struct ScratchBlock {
+  // THE LENGTHSCALES OF THE CURRENT FIT LIVE HERE UNTIL THE NEXT FIT: fit_hyp_core uploads them (or launch_fit_small leaves them,
+  // through its hyp_out), and b7_gp_append / b7_gp_fantasize scale new points with them.  A nomination's batched fits keep theirs
+  // in c->bhyp and declare the context's fit slot empty instead.
+  double lenscale[256];
+  double fmin[256];                   // f_min of several response columns (stage_fmin, b7_ei_compute)
+  SobolTable sobol;                   // launch_sobol
+  double minmax[2 * B7_MAX_D];        // a generated grid's mins | maxes (sobol.hip: upload_minmax)
+  alignas(4096) double colvec[2 * B7_MAX_D];  // column minima | maxima out (b7_grid_colrange), a grid map's per-column vector in
+};
+static_assert(offsetof(ScratchBlock, lenscale) == 0 && offsetof(ScratchBlock, fmin) == 2048 && offsetof(ScratchBlock, sobol) == 4096 &&
+                  offsetof(ScratchBlock, minmax) == 4096 + sizeof(SobolTable) && offsetof(ScratchBlock, colvec) == 12288 &&
+                  sizeof(ScratchBlock) <= B7_SCRATCH_BYTES,
+              "scratch block: the layout every earlier build used");
 
 struct PhaseStat {
   double ms = 0.0;
@@ -117,20 +168,11 @@ struct b7_ctx {
                          // multiply-add, 2 = the same with mov_dpp + fma (the bit-for-bit reference of 1) (B7_DIAG_VARIANT)
   int inverse_inline = 1;  // build inv(L) inside the factorisation launches: 0 never (separate trtri passes), 1 for
                            // Npad <= 8192, 2 always (B7_INVERSE_INLINE)
-  // 8 KiB of pinned, device-mapped host memory for the small blocks: [0, 2304) fit report, [2304, 2320) arg-max
-  // result, [4096, 6144) fmin staging, [6144, 8192) host copy of the exchange table, [8192, 8960) lengthscale
-  // staging: kernels write
-  // them directly or a copy lands without pageable staging; read after a stream synchronisation
-  void *pinned = nullptr;
+  PinnedBlock *pinned = nullptr, *pinned_dev = nullptr;  // the fixed pinned block as the host / the device addresses it
   std::vector<double> net_host;  // the basis network last uploaded to netbuf (packed W, b per layer)
-  void *pin_blr = nullptr;  // b7_blr_eval_nominate: pinned staging of the observations and beta (y - mean)
-  size_t pin_blr_bytes = 0;
-  void *pin_eval_dev = nullptr;  // device address of pin_eval (mapped)
-  void *pin_eval = nullptr;  // b7_eval_nominate: [S][4] pivot reports + [S][d] lengthscale staging (pinned)
-  size_t pin_eval_bytes = 0;
-  void *pinned_dev = nullptr;
-  void *pin_nll = nullptr, *pin_nll_dev = nullptr;  // b7_gp_nll_batch's small path: hypers in, results out (pinned, device-mapped)
-  size_t pin_nll_bytes = 0;
+  PinBuf pin_blr;   // b7_blr_eval_nominate: staging of the observations and beta (y - mean) (not mapped)
+  PinBuf pin_eval;  // b7_eval_nominate: [S][4] pivot reports + the packed hypers of all S samples (mapped)
+  PinBuf pin_nll;   // b7_gp_nll_batch: hypers in, results out (mapped)
   bool fmin_staged = false;  // the fmin staging slot of the pinned block holds a caller's values
   bool potrf_attrs_set = false;  // dynamic-LDS limits of the Cholesky kernels raised (once per context)
   bool linv_done = false;  // launch_potrf produced Linv for the current factor
@@ -161,7 +203,7 @@ struct b7_ctx {
   int potrf_sched_saved = 0; // the schedule to return to after such a redo
   DevBuf part;   // argmax partials (value, index)
   DevBuf ticket; // score_finish_slot_kernel's arrival counter (zero between launches)
-  DevBuf scratch; // misc (fmin upload, results)
+  DevBuf scratch; // a ScratchBlock (b7_scratch)
   DevBuf tmpgrid; // predict_at temporary grid
   DevBuf tmpmu, tmpvar;
   DevBuf fant;   // fantasize workspace (pending-point covariance pieces)
@@ -221,6 +263,9 @@ int b7_fail(b7_ctx *c, int code, const char *fmt, ...);
 
 int b7_ensure(b7_ctx *c, DevBuf &b, size_t bytes);
 void b7_release(DevBuf &b);
+// at least `bytes` of pinned host memory in b; growing waits for the stream (nothing in flight may use the old block) and allocates twice the need
+int b7_pin_ensure(b7_ctx *c, PinBuf &b, size_t bytes, bool mapped);
+static inline ScratchBlock *b7_scratch(const b7_ctx *c) { return static_cast<ScratchBlock *>(c->scratch.p); }
 
 // Phase timing (no-ops unless profiling is on).
 struct PhaseScope {
@@ -296,12 +341,11 @@ int launch_potrf(b7_ctx *c, double extra, bool with_inverse, int *report_hint = 
 int launch_trtri(b7_ctx *c);           // L, dinv -> Linv (no-op when launch_potrf already built it)
 int launch_potrf_persist(b7_ctx *c, double extra, bool with_inverse);  // the same in one persistent launch (Npad <= 4096)
 int launch_nll_batch(b7_ctx *c, int B, const double *K, double *L, double *dinv, unsigned *flags, int *info,
-                     const double *resid, double *terms, const double *unused);
+                     const double *resid, double *terms);
 int launch_nll_one(b7_ctx *c, const double *K, double *L, double *dinv, unsigned *flags, int *info, const double *resid,
                    double *terms, double extra);
 size_t persist_flag_words_host(int nb);
-// nll_small.hip
-bool nll_small_applies(const b7_ctx *c);
+// blr_small.hip, nll_small.hip
 int launch_potrf_small(b7_ctx *c, int B, const double *K, double *L, double *Linv, double *dinv, const double *resid, double *alpha,
                        double extra, int *info, int *report_dev, int64_t sK, int64_t sL, int64_t sdinv, int64_t svec, int sinfo);
 int launch_blr_head_small(b7_ctx *c, const double *Z, int N, int z, int ldz, const double *yv, double alpha_prec, double beta,
@@ -321,6 +365,10 @@ int launch_kpost_small(b7_ctx *c, int S, const double *xq, int64_t M, const doub
                        double *mu, double *var, int64_t sout);
 // gp_small.hip
 bool gp_small_applies(const b7_ctx *c);
+// ... and the whole fit of a hyper vector runs as one workgroup of one launch (launch_fit_small)
+static inline bool fit_small_applies(const b7_ctx *c) {
+  return c->fit_small && c->potrf_sched == 3 && c->inverse_inline && gp_small_applies(c);
+}
 int launch_nll_small8(b7_ctx *c, int B, const double *hyp_dev, const double *hyp_host, double *terms_dev, int *info_dev,
                       unsigned *done_dev);
 int launch_fit_small(b7_ctx *c, int B, const double *hyp_dev, const double *hyp_host, double *hyp_out, double *w, double *zsc,
@@ -387,7 +435,7 @@ int launch_keep_record(b7_ctx *c, uint64_t *tab_dev, int rank, int world);
 int launch_row_slot(b7_ctx *c, uint64_t *tab_dev, int rank, int world, int64_t idx1_global, int64_t local0, const double *grid,
                     int d);
 
-// comm.hip: the pieces of a sharded nomination that the eval + nominate entry points (api.hip: nominate_run),
+// comm.hip: the pieces of a sharded nomination that the eval + nominate entry points (nominate_run below),
 // b7_score_finish_global and the single-process group (group.hip) are assembled from
 int exch_table_ensure(b7_ctx *c, int world);
 // enqueue: score:div, local arg-max, this rank's record; pend (nullable): the nomination's batched score, run fused with them
@@ -405,10 +453,73 @@ bool exch_pick(const uint64_t *tab, int world, int stride, double *val, int64_t 
 int exch_conclude(b7_ctx *c, const uint64_t *tab, int world, double *best_val, int64_t *best_idx1);  // statuses, winner, cache
 void exch_forget(b7_ctx *c);
 
-// api.hip: bayesopt:eval as stream work without a host wait (its batched score left in *pend), the pivot reports' check and
+// gp_api.hip: the pieces of a fit that the nomination and the Bayesian linear head share with the GP entry points
+void persist_gave_up(b7_ctx *c);  // a persistent factorisation timed out on a hand-off: the launch schedule from here on
+// utils/math.lua:159-218 on c->K: plain attempt, then the growing-jitter retries; leaves L and dinv (+ Linv) on the device
+int chol_with_jitter(b7_ctx *c, double *jitter_out, int *info_first_out, bool with_inverse, FactorNote *note = nullptr);
+int check_hyp(b7_ctx *c, const b7_hyp *hyp, int d);
+void launch_resid_batch(b7_ctx *c, int B, const double *mean_dev);  // c->bresid[b] = Y - mean[b] (padding rows zero), B fits
+int fit_front(b7_ctx *c, const b7_hyp *hyp, const double *ls_dev);  // residual, observation scaling and K(X,X) of one hyper sample
+int fit_hyp_core(b7_ctx *c, const b7_hyp *hyp, double *nll_out, double *jitter_used, int *info_out, bool then_predict);
+int64_t predict_chunk(const b7_ctx *c, int64_t M);  // candidate rows per pass of predict_into: what c->ks has to hold
+int predict_into(b7_ctx *c, const double *xq, int64_t M, double *mu, double *var);
+// mean (M x cols) / variance (M) to the caller (either may be null), then one synchronisation if either was asked for, or `wait`
+int copy_out_mu_var(b7_ctx *c, const void *mu, const void *var, int64_t M, int cols, double *mean_host, double *var_host,
+                    bool wait = false);
+
+// The packed hyper block of B fits over d dimensions: [B x d lengthscales | B amp | B noise | B mean]
+struct HypPack { double *ls, *amp, *noise, *mean; };
+static inline HypPack hyp_pack(void *base, int B, int d) {
+  double *amp = static_cast<double *>(base) + (size_t)B * d;
+  return {static_cast<double *>(base), amp, amp + B, amp + 2 * (size_t)B};
+}
+
+// nominate.hip: bayesopt:eval as stream work without a host wait (its batched score left in *pend), the pivot reports' check and
 // the per-sample redo
+int nominate_args(b7_ctx *c, const char *who, const b7_score_spec *spec, int64_t offset);
+int stage_fmin(b7_ctx *c, const double *fmin, double **fd_out);
+// the acquisition of c->mu / c->var over the resident candidates into c->acc: added (score:add) or, for a single model, written
+int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumulate = true);
+PendingScore pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd);
 int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t offset);
 int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, PendingScore *pend);
 bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist);
 int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out);
+// grid_api.hip
 int grid_drop_row(b7_ctx *c, int64_t local_idx1, double *row_out_sync);  // stable deletion, enqueued; row_out != NULL synchronises
+
+// The protocol of the three eval + nominate entry points, once.  rc: their argument checks.  enqueue(&pend): the local
+// bayesopt:eval as stream work, its batched score possibly left pending; clean(): after the stream has drained, did every fit
+// factor at the first attempt; redo(): the same nomination again, synchronously, through the jitter schedule.  The redo starts
+// from nothing pending: what the failed fits left is dropped with them.
+template <class Enqueue, class Clean, class Redo>
+static inline int nominate_run(b7_ctx *c, const char *who, int rc, int64_t offset, double divisor, Enqueue enqueue, Clean clean,
+                        Redo redo, double *best_val, int64_t *best_idx1) {
+  const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
+  PendingScore pend;
+  if (!(c->comm && c->comm_world > 1)) {
+    // the arg-max and the copy of its record are enqueued before the host has seen any report: one synchronisation
+    B7_TRY(rc);
+    B7_TRY(enqueue(&pend));
+    B7_TRY(exch_local(c, divisor, offset, rank, world, true, true, &pend));  // record mirrored into mapped host memory
+    B7_TRY(exch_wait_mirror(c));
+    if (!clean()) {
+      B7_TRY(redo());
+      B7_TRY(exch_local(c, divisor, offset, rank, world, true, true));
+      B7_TRY(exch_wait_mirror(c));
+    }
+    return exch_conclude(c, c->tab_host, world, best_val, best_idx1);
+  }
+  // with a communicator the collective comes after the report check (a rank that redoes its nomination must not
+  // issue one collective too many), and a rank that fails locally still reaches it, with a failure record
+  if (rc == B7_OK && c->M > 0) {
+    rc = enqueue(&pend);
+    if (rc == B7_OK) rc = hipStreamSynchronize(c->stream) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "%s: stream failed", who);
+    if (rc == B7_OK && !clean()) {
+      pend = PendingScore();
+      rc = redo();
+    }
+  }
+  if (rc == B7_OK) rc = exch_local(c, divisor, offset, rank, world, true, false, &pend);
+  return exch_collective(c, rc, rank, world, best_val, best_idx1);
+}

@@ -59,7 +59,7 @@ Rccl &rccl() {
   return r;
 }
 
-// ---- the exchange, in pieces (api.hip's nominate_run, b7_score_finish_global and group.hip assemble them) ---------------
+// ---- the exchange, in pieces (b7_internal.h's nominate_run, b7_score_finish_global and group.hip assemble them) ---------------
 
 int exch_table_ensure(b7_ctx *c, int world) {
   if (world < 1 || world > B7_MAX_WORLD) return b7_fail(c, B7_ERR_UNSUPPORTED, "exchange: world %d not in [1, %d]", world, B7_MAX_WORLD);

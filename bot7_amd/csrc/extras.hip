@@ -105,7 +105,7 @@ __global__ void fantasy_sample_kernel(const double *__restrict__ Lp, const doubl
 // ---- DNGO: basis network forward and the pieces of the Bayesian-linear head -------------------------------------------
 // Reference: models/dngo.lua:155-171 pushes X through `network` in minibatches and keeps `self.basis.output`
 // (the activations of the last hidden layer: nn.Linear / activation stacks from nnTools/builder.lua:118-151);
-// :174 hands those features to gp.models.bayes_linear (absent `gp` package), restated in api.hip.
+// :174 hands those features to gp.models.bayes_linear (absent `gp` package), restated in blr_api.hip.
 // One block = 32 inputs; activations ping-pong between two LDS buffers (dynamic, 2 x 32 x (maxw+1) doubles);
 // thread t computes units (t / 32 + 8 i) of input (t % 32).  Weights (row-major out x in, nn.Linear's layout, each
 // followed by its bias) stream from L2.

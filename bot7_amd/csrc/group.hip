@@ -395,7 +395,7 @@ int b7_group_eval_nominate(b7_group *g, int S, const b7_hyp *hyps, const b7_scor
   std::vector<char> member_redone(n, 0);
   for (int i = 0; i < n; ++i) {
     b7_ctx *c = g->ctx[i];
-    if (c->M == 0 || reports_clean(c, static_cast<const int *>(c->pin_eval), S, true)) continue;
+    if (c->M == 0 || reports_clean(c, static_cast<const int *>(c->pin_eval.host), S, true)) continue;
     if (hipSetDevice(c->device) != hipSuccess) return gfail(g, B7_ERR_HIP, "hipSetDevice(%d) failed", c->device);
     G_TRY(g, i, eval_redo(c, S, hyps, spec, redone ? nullptr : jitter_out, redone ? nullptr : info_out));
     G_TRY(g, i, exch_local(c, (double)S, offset_of(g, i), i, n, g->use_rccl));

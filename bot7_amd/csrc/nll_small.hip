@@ -351,7 +351,6 @@ int nll_small_launch(b7_ctx *c, int B, const double *hyp_dev, const double *hyp_
 
 }  // namespace
 
-bool nll_small_applies(const b7_ctx *c) { return c->Npad <= 128 && c->dfit <= 32 && c->ycols == 1; }
 
 // hyp_dev: [B x d lengthscales | B amp | B noise | B mean] (b7_gp_nll_batch's pack); terms_dev[2 B], info_dev[4 B]
 // done_dev (nullable): a word the kernel sets to 1 after its results are visible to the host (B == 1 only).

@@ -1,0 +1,376 @@
+// bayesopt:eval + nominate as one call, and the separate score / arg-max entry points it replaces.
+#include <string.h>
+
+#include <algorithm>
+
+#include "b7_internal.h"
+
+// ---- bayesopt:eval + nominate as one call ------------------------------------------------------------------
+// bots/bayesopt.lua:56-99: score = (1/S) sum_s acq(model, hyp_s, X_obs, Y_obs, X_hid), then score:max(1).  The
+// separate entry points (b7_gp_predict_hyp, b7_score_*, b7_score_finish*) cost one host round trip per hyper sample
+// (the pivot report) plus one for the arg-max; at small N and M (cfg2: 0.2 ms of GPU work per sample) the round trips
+// are a third of the wall time.  Here every sample's fit, posterior and score:add are enqueued back to back, each
+// fit's 16-byte pivot report is copied into its own pinned slot in stream order, the arg-max follows, and the host
+// synchronises ONCE.  Knowing all S samples up front also lets the S fits run SIDE BY SIDE: one persistent launch with
+// grid.y = sample (launch_fit_batch), K assembly, residuals and alpha batched the same way; a fit is a dependent chain
+// that leaves most of the chip idle, so ten cost little more than one (cfg2, S = 10: 1.55 -> 0.75 ms per nomination).  A report that says "pivot failed" or "hand-off timed out" (rare) throws the accumulated score
+// away and redoes the whole nomination through the per-sample path, jitter schedule included, so the result is the
+// one the separate calls give.
+int stage_fmin(b7_ctx *c, const double *fmin, double **fd_out) {
+  if (c->ycols == 1) {  // one response column (every path but the fantasy scores): f_min travels as a kernel argument
+    c->fmin_scalar = fmin[0];
+    *fd_out = nullptr;
+    return B7_OK;
+  }
+  double *fh = c->pinned->fmin, *fd = b7_scratch(c)->fmin;
+  if (!c->fmin_staged || memcmp(fh, fmin, sizeof(double) * c->ycols) != 0) {
+    B7_HIP(c, hipStreamSynchronize(c->stream));
+    memcpy(fh, fmin, sizeof(double) * c->ycols);
+    c->fmin_staged = true;
+  }
+  B7_HIP(c, hipMemcpyAsync(fd, fh, sizeof(double) * c->ycols, hipMemcpyHostToDevice, c->stream));
+  *fd_out = fd;
+  return B7_OK;
+}
+
+int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumulate) {
+  if (sp->kind == B7_SCORE_EI)
+    return launch_ei(c, (const double *)c->mu.p, (const double *)c->var.p, fd, sp->tradeoff, c->M, c->ycols,
+                     (double *)c->acc.p, accumulate);
+  return launch_cb(c, (const double *)c->mu.p, (const double *)c->var.p, sp->tradeoff, sp->upper, sp->sign, c->M,
+                   c->ycols, (double *)c->acc.p, accumulate);
+}
+
+// The score spec and the global row offset of an eval + nominate entry point (`who` in the messages).  Only a shard of a
+// larger candidate set -- a rank of a communicator, a member of a group -- may be empty: the exchange covers the others.
+int nominate_args(b7_ctx *c, const char *who, const b7_score_spec *spec, int64_t offset) {
+  if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB)
+    return b7_fail(c, B7_ERR_INVALID, "%s: unknown score kind %d", who, spec->kind);
+  if (spec->kind == B7_SCORE_EI && !spec->fmin) return b7_fail(c, B7_ERR_INVALID, "%s: EI needs fmin", who);
+  if (offset < 0) return b7_fail(c, B7_ERR_INVALID, "%s: negative row offset", who);
+  if (c->M == 0 && !(c->comm && c->comm_world > 1) && !c->group)
+    return b7_fail(c, B7_ERR_STATE, "%s: no candidate grid on this context", who);
+  return B7_OK;
+}
+
+int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t offset) {
+  if (S < 1 || !hyps || !spec) return b7_fail(c, B7_ERR_INVALID, "eval_nominate: S >= 1, hyps and spec required");
+  B7_TRY(nominate_args(c, "eval_nominate", spec, offset));
+  if (!c->have_data) return b7_fail(c, B7_ERR_STATE, "eval_nominate: call b7_gp_set_data first");
+  if (c->M > 0 && c->d != c->dfit)
+    return b7_fail(c, B7_ERR_INVALID, "eval_nominate: grid dims %d != data dims %d", c->d, c->dfit);
+  for (int s = 0; s < S; ++s) B7_TRY(check_hyp(c, &hyps[s], c->dfit));
+  return B7_OK;
+}
+
+// score:add x S of the batch in c->bmu / c->bvar, owed to the exchange step (exch_local), which runs it fused with score:div,
+// the arg-max and the record
+PendingScore pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd) {
+  return PendingScore{true, spec->kind, S, spec->upper, (const double *)c->bmu.p, (const double *)c->bvar.p, fd, c->M,
+                      spec->tradeoff, spec->sign};
+}
+
+// bots/bayesopt.lua:69-78 as stream work: zero the accumulator, then fit + posterior + score:add per hyper sample, each
+// fit's pivot report copied to its pinned slot in stream order.  Returns without waiting for any of it; the small regime's
+// score:add is left to the caller's exchange step in *pend.
+int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, PendingScore *pend) {
+  const int d = c->dfit;
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(b7_ensure(c, c->mu, sizeof(double) * (size_t)c->M * c->ycols));
+  B7_TRY(b7_ensure(c, c->var, sizeof(double) * (size_t)c->M));
+  B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
+  // predict_into's workspace, sized now: a reallocation inside the loop would synchronise
+  B7_TRY(b7_ensure(c, c->ks, sizeof(double) * (size_t)predict_chunk(c, c->M) * c->Npad));
+  // pinned staging: [S][4] pivot reports | hypers of all S samples ([S][d] lengthscales, then S amp, S noise, S mean)
+  const size_t hyp_doubles = (size_t)S * (d + 3), ls_bytes = sizeof(double) * hyp_doubles, rep_bytes = 16 * (size_t)S;
+  B7_TRY(b7_pin_ensure(c, c->pin_eval, ls_bytes + rep_bytes, true));
+  B7_TRY(b7_ensure(c, c->bhyp, ls_bytes));
+  int *reports = static_cast<int *>(c->pin_eval.host);                                        // [S][4]
+  double *ls_host = reinterpret_cast<double *>(static_cast<char *>(c->pin_eval.host) + rep_bytes);  // the packed hypers
+  const HypPack hp = hyp_pack(ls_host, S, d);
+  for (int s = 0; s < S; ++s) {
+    memcpy(hp.ls + (size_t)s * d, hyps[s].lenscale_sq, sizeof(double) * d);
+    hp.amp[s] = hyps[s].amp;
+    hp.noise[s] = hyps[s].noise;
+    hp.mean[s] = hyps[s].mean;
+  }
+  memset(reports, 0xff, rep_bytes);
+  // the fits of all samples side by side in one persistent launch (one critical workgroup each) when that schedule serves
+  // this size and the responses are a single column; otherwise one after the other
+  // N <= 128, d <= 32 (the reference's own regime): the whole fit of every hyper sample is one workgroup of ONE launch
+  // (gp_small.hip), for any S -- observation scaling, K(X,X), factorisation, inverse, alpha, the pivot reports into the mapped
+  // block; the kernel reads the hypers straight from that block and leaves the device copy the kernels downstream read
+  const bool small = fit_small_applies(c);
+  const bool batch = small || (S > 1 && c->ycols == 1 && c->potrf_sched == 3 && c->Npad <= B7_PERSIST_NMAX && c->inverse_inline);
+  const int n = c->Npad;
+  const size_t nn = (size_t)n * n;
+  if (batch) {
+    const size_t fw = persist_flag_words_host(n / B7_PANEL);
+    B7_TRY(b7_ensure(c, c->bw, sizeof(double) * (size_t)S * c->dpad));
+    B7_TRY(b7_ensure(c, c->bzsc, sizeof(double) * (size_t)S * n * c->dpad));
+    B7_TRY(b7_ensure(c, c->bzss, sizeof(double) * (size_t)S * n));
+    B7_TRY(b7_ensure(c, c->bLinv, sizeof(double) * S * nn));
+    B7_TRY(b7_ensure(c, c->binfo, sizeof(int) * 4 * (size_t)S));
+    B7_TRY(b7_ensure(c, c->balpha, sizeof(double) * (size_t)S * n));
+    if (!small) {
+      B7_TRY(b7_ensure(c, c->bK, sizeof(double) * S * nn));
+      B7_TRY(b7_ensure(c, c->bL, sizeof(double) * S * nn));
+      B7_TRY(b7_ensure(c, c->bdinv, sizeof(double) * (size_t)S * n * B7_PANEL));
+      B7_TRY(b7_ensure(c, c->bflags, sizeof(unsigned) * S * fw));
+      B7_TRY(b7_ensure(c, c->bresid, sizeof(double) * (size_t)S * n));
+    }
+  }
+  if (!small) B7_HIP(c, hipMemcpyAsync(c->bhyp.p, ls_host, ls_bytes, hipMemcpyHostToDevice, c->stream));
+  double *fd = nullptr;
+  if (spec->kind == B7_SCORE_EI) B7_TRY(stage_fmin(c, spec->fmin, &fd));
+
+  acc_declare_zeros(c);
+  if (batch) {
+    const HypPack hd = hyp_pack(c->bhyp.p, S, d);
+    const double *hyp_dev = hd.ls, *amp_dev = hd.amp, *noise_dev = hd.noise, *mean_dev = hd.mean;
+    int *reports_dev = static_cast<int *>(c->pin_eval.dev);
+    if (small) {
+      const double *hyp_map = reinterpret_cast<const double *>(static_cast<const char *>(c->pin_eval.dev) + rep_bytes);
+      B7_TRY(launch_fit_small(c, S, hyp_map, ls_host, (double *)c->bhyp.p, (double *)c->bw.p, (double *)c->bzsc.p, (double *)c->bzss.p,
+                              nullptr, (double *)c->bLinv.p, nullptr, (double *)c->balpha.p, nullptr, (int *)c->binfo.p, reports_dev));
+    } else {
+      launch_resid_batch(c, S, mean_dev);
+      B7_TRY(launch_kxx_batch(c, S, hyp_dev, amp_dev, noise_dev, (double *)c->bw.p, (double *)c->bzsc.p, (double *)c->bzss.p,
+                              (double *)c->bK.p));
+      if (n == 64 && c->potrf_small) {
+        // one 64-block per fit: factorisation, inverse, alpha and the pivot report (mirrored into the mapped block) of all S
+        // fits in ONE launch of S workgroups
+        B7_TRY(launch_potrf_small(c, S, (const double *)c->bK.p, (double *)c->bL.p, (double *)c->bLinv.p, (double *)c->bdinv.p,
+                                  (const double *)c->bresid.p, (double *)c->balpha.p, 0.0, (int *)c->binfo.p, reports_dev, (int64_t)nn,
+                                  (int64_t)nn, (int64_t)n * B7_PANEL, (int64_t)n, 4));
+      } else {
+        B7_TRY(launch_fit_batch(c, S, (const double *)c->bK.p, (double *)c->bL.p, (double *)c->bLinv.p, (double *)c->bdinv.p,
+                                (unsigned *)c->bflags.p, (int *)c->binfo.p));
+        if (4 * S <= 256) {  // the reports ride on the last kernel of the fits into the mapped block: no copy launch
+          B7_TRY(launch_alpha_batch(c, S, (const double *)c->bLinv.p, (const double *)c->bresid.p, (double *)c->balpha.p,
+                                    (const int *)c->binfo.p, reports_dev, 4 * S));
+        } else {
+          B7_TRY(launch_alpha_batch(c, S, (const double *)c->bLinv.p, (const double *)c->bresid.p, (double *)c->balpha.p));
+          B7_HIP(c, hipMemcpyAsync(reports, c->binfo.p, rep_bytes, hipMemcpyDeviceToHost, c->stream));
+        }
+      }
+    }
+    const size_t row_bytes = sizeof(double) * (size_t)n;
+    const int64_t Mpad = round_up(c->M, B7_MROWS);
+    if (c->kpost_small && kpost_small_applies(c)) {
+      // N <= 128, d <= 32: K(X*,X), mean and variance of all S samples in ONE kernel that never stores K* (kpost_small.hip)
+      B7_TRY(b7_ensure(c, c->bmu, sizeof(double) * (size_t)S * c->M));
+      B7_TRY(b7_ensure(c, c->bvar, sizeof(double) * (size_t)S * c->M));
+      B7_TRY(launch_kpost_small(c, S, (const double *)c->grid[c->grid_cur].p, c->M, (const double *)c->bw.p, (const double *)c->bzsc.p,
+                                (const double *)c->bzss.p, (const double *)c->bLinv.p, (const double *)c->balpha.p, hyp_dev, 0.0, 0.0, 0.0,
+                                (double *)c->bmu.p, (double *)c->bvar.p, c->M));
+      *pend = pending_score(c, S, spec, fd);
+      c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
+      c->predicted = false;
+    } else if ((size_t)Mpad * S * row_bytes <= c->ks_bytes) {
+      // K* of all S samples fits the workspace at once (the reference's default sizes: 2e4 candidates, tens to hundreds
+      // of observations, 10 samples): K*, posterior and score:add of all samples in ONE launch each (grid.z / grid.y =
+      // sample), the score summed over the samples in order inside the kernel
+      B7_TRY(b7_ensure(c, c->ks, (size_t)Mpad * S * row_bytes));
+      B7_TRY(b7_ensure(c, c->bmu, sizeof(double) * (size_t)S * c->M));
+      B7_TRY(b7_ensure(c, c->bvar, sizeof(double) * (size_t)S * c->M));
+      B7_TRY(launch_ksx_batch(c, S, (const double *)c->grid[c->grid_cur].p, Mpad, c->M, (const double *)c->bw.p,
+                              (const double *)c->bzsc.p, (const double *)c->bzss.p, amp_dev, mean_dev,
+                              (const double *)c->balpha.p, (double *)c->ks.p, (int64_t)Mpad * n, (double *)c->bmu.p, c->M));
+      B7_TRY(launch_post_batch(c, S, (const double *)c->bLinv.p, (const double *)c->ks.p, (int64_t)Mpad * n, Mpad, c->M,
+                               (double *)c->bvar.p, c->M, amp_dev, noise_dev));
+      if (spec->kind == B7_SCORE_EI)
+        B7_TRY(launch_ei_batch(c, S, (const double *)c->bmu.p, (const double *)c->bvar.p, c->M, fd, spec->tradeoff, c->M,
+                               (double *)c->acc.p));
+      else
+        B7_TRY(launch_cb_batch(c, S, (const double *)c->bmu.p, (const double *)c->bvar.p, c->M, spec->tradeoff, spec->upper,
+                               spec->sign, c->M, (double *)c->acc.p));
+      c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
+      c->predicted = false;
+    } else {
+      // the posterior kernels read the fit through the context: point it at one sample's slot after the other
+      void *const zsc0 = c->zsc.p, *const zss0 = c->zss.p, *const w0 = c->w.p, *const alpha0 = c->alpha.p, *const linv0 = c->Linv.p;
+      int rc = B7_OK;
+      for (int s = 0; s < S && rc == B7_OK; ++s) {
+        c->zsc.p = (double *)c->bzsc.p + (size_t)s * n * c->dpad;
+        c->zss.p = (double *)c->bzss.p + (size_t)s * n;
+        c->w.p = (double *)c->bw.p + (size_t)s * c->dpad;
+        c->alpha.p = (double *)c->balpha.p + (size_t)s * n;
+        c->Linv.p = (double *)c->bLinv.p + s * nn;
+        c->amp = hyps[s].amp;
+        c->noise = hyps[s].noise;
+        c->mean = hyps[s].mean;
+        c->model_kind = 0;
+        c->fitted = true;
+        rc = predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p);
+        if (rc == B7_OK) rc = score_add(c, spec, fd);
+      }
+      c->zsc.p = zsc0, c->zss.p = zss0, c->w.p = w0, c->alpha.p = alpha0, c->Linv.p = linv0;
+      c->fitted = false;  // the context's own fit slot does not hold any of these fits
+      c->predicted = true;
+      c->Mpred = c->M;
+      B7_TRY(rc);
+    }
+  } else {
+    for (int s = 0; s < S; ++s) {
+      B7_TRY(fit_front(c, &hyps[s], (const double *)c->bhyp.p + (size_t)s * d));
+      int *report = static_cast<int *>(c->pin_eval.dev) + 4 * s;  // a one-block factorisation mirrors its report itself
+      FactorNote note;
+      B7_TRY(launch_potrf(c, 0.0, true, report, &note));
+      if (!c->linv_done) B7_TRY(launch_trtri(c));  // on a failed factor this inverts rubbish; the report discards it
+      B7_TRY(launch_alpha(c, report, 4, note));  // + this fit's pivot report, no copy launch
+      c->fitted = true;
+      B7_TRY(predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
+      c->predicted = true;
+      c->Mpred = c->M;
+      B7_TRY(score_add(c, spec, fd));
+    }
+    // this fit's lengthscales sit in the batch staging block, not in ScratchBlock::lenscale: the fit slot is declared empty
+    c->fitted = false;
+  }
+  return B7_OK;
+}
+
+// after the stream has drained: did each of S fits ([S][4] report words) factor at the first attempt, without a hand-off
+// time-out?  persist: the fits may have run the persistent schedule, which a time-out switches off (persist_gave_up)
+bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist) {
+  bool clean = true, aborted = false;
+  for (int s = 0; s < S; ++s) {
+    clean = clean && reports[4 * s] == 0 && reports[4 * s + 1] == 0;
+    aborted = aborted || reports[4 * s + 1] != 0;
+  }
+  if (aborted && persist) persist_gave_up(c);
+  return clean;
+}
+
+// the same nomination through the per-sample path, jitter schedule (utils/math.lua:159-218) included; synchronous
+int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out) {
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(acc_write_zeros(c));
+  double *fd = nullptr;
+  for (int s = 0; s < S; ++s) {
+    B7_TRY(fit_hyp_core(c, &hyps[s], nullptr, jitter_out ? jitter_out + s : nullptr, info_out ? info_out + s : nullptr, true));
+    c->predicted = true;
+    c->Mpred = c->M;
+    if (spec->kind == B7_SCORE_EI) B7_TRY(stage_fmin(c, spec->fmin, &fd));
+    B7_TRY(score_add(c, spec, fd));
+  }
+  return B7_OK;
+}
+
+static int score_ready(b7_ctx *c, const char *who) {
+  if (!c->predicted || c->Mpred != c->M) return b7_fail(c, B7_ERR_STATE, "%s: call b7_gp_predict first", who);
+  if (!c->acc_valid) return b7_fail(c, B7_ERR_STATE, "%s: call b7_score_reset first", who);
+  return B7_OK;
+}
+
+static int upload_mv(b7_ctx *c, const double *mean, const double *var, int64_t M, int cc) {
+  B7_TRY(b7_ensure(c, c->tmpmu, sizeof(double) * (size_t)M * cc));
+  B7_TRY(b7_ensure(c, c->tmpvar, sizeof(double) * (size_t)M));
+  B7_TRY(b7_ensure(c, c->tmpgrid, sizeof(double) * (size_t)M));
+  B7_HIP(c, hipMemcpyAsync(c->tmpmu.p, mean, sizeof(double) * (size_t)M * cc, hipMemcpyHostToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync(c->tmpvar.p, var, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+  return B7_OK;
+}
+
+extern "C" {
+
+int b7_eval_nominate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset,
+                     double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out) {
+  if (!c) return B7_ERR_INVALID;
+  if (c->group) return b7_fail(c, B7_ERR_STATE, "eval_nominate: this context belongs to a group (b7_group_eval_nominate)");
+  if (jitter_out && S > 0) std::fill(jitter_out, jitter_out + S, 0.0);
+  if (info_out && S > 0) std::fill(info_out, info_out + S, 0);
+  return nominate_run(
+      c, "eval_nominate", eval_validate(c, S, hyps, spec, global_row_offset), global_row_offset, (double)S,
+      [&](PendingScore *pend) { return eval_enqueue(c, S, hyps, spec, pend); },
+      [&]() { return reports_clean(c, static_cast<const int *>(c->pin_eval.host), S, true); },
+      [&]() { return eval_redo(c, S, hyps, spec, jitter_out, info_out); }, best_val, best_idx1);
+}
+
+// ---- scores --------------------------------------------------------------------------------------------
+int b7_score_reset(b7_ctx *c) {
+  if (!c) return B7_ERR_INVALID;
+  if (c->M <= 0) return b7_fail(c, B7_ERR_STATE, "score_reset: no candidate grid");
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
+  return acc_write_zeros(c);  // torch.zeros(X_hid:size(1)), bots/bayesopt.lua:69
+}
+
+int b7_score_ei(b7_ctx *c, const double *fmin, double tradeoff) {
+  if (!c) return B7_ERR_INVALID;
+  if (!fmin) return b7_fail(c, B7_ERR_INVALID, "score_ei: fmin is NULL");
+  B7_TRY(score_ready(c, "score_ei"));
+  B7_HIP(c, hipSetDevice(c->device));
+  // fmin goes pageable -> pinned staging (PinnedBlock::fmin) -> device: the caller's array need not
+  // outlive this call and the copy is a true asynchronous one.  The staging slot may still be the source of an
+  // earlier copy in flight, hence the wait when the values change (once per nomination: fmin is the same for every
+  // hyper sample of a marginalisation loop).
+  double *fd = nullptr;
+  B7_TRY(stage_fmin(c, fmin, &fd));
+  return launch_ei(c, (const double *)c->mu.p, (const double *)c->var.p, fd, tradeoff, c->M, c->ycols,
+                   (double *)c->acc.p, true);
+}
+
+int b7_score_cb(b7_ctx *c, double tradeoff, int upper, double sign) {
+  if (!c) return B7_ERR_INVALID;
+  B7_TRY(score_ready(c, "score_cb"));
+  B7_HIP(c, hipSetDevice(c->device));
+  return launch_cb(c, (const double *)c->mu.p, (const double *)c->var.p, tradeoff, upper, sign, c->M, c->ycols,
+                   (double *)c->acc.p, true);
+}
+
+int b7_score_finish(b7_ctx *c, double divisor, double *best_val, int64_t *best_idx1, double *scores_host) {
+  if (!c) return B7_ERR_INVALID;
+  if (!c->acc_valid) return b7_fail(c, B7_ERR_STATE, "score_finish: call b7_score_reset first");
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(acc_materialize(c));
+  B7_TRY(launch_finish(c, (double *)c->acc.p, c->M, divisor, best_val, best_idx1));
+  if (scores_host) {
+    B7_HIP(c, hipMemcpyAsync(scores_host, c->acc.p, sizeof(double) * (size_t)c->M, hipMemcpyDeviceToHost, c->stream));
+    B7_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return B7_OK;
+}
+
+int b7_ei_compute(b7_ctx *c, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M,
+                  int cc, double *out) {
+  if (!c) return B7_ERR_INVALID;
+  if (M < 0 || cc < 1 || cc > 256 || (M > 0 && (!mean || !var || !fmin || !out)))
+    return b7_fail(c, B7_ERR_INVALID, "ei_compute: bad arguments");
+  if (M == 0) return B7_OK;
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(upload_mv(c, mean, var, M, cc));
+  double *fd = b7_scratch(c)->fmin;
+  B7_HIP(c, hipMemcpyAsync(fd, fmin, sizeof(double) * cc, hipMemcpyHostToDevice, c->stream));
+  B7_TRY(launch_ei(c, (const double *)c->tmpmu.p, (const double *)c->tmpvar.p, fd, tradeoff, M, cc,
+                   (double *)c->tmpgrid.p, false));
+  B7_HIP(c, hipMemcpyAsync(out, c->tmpgrid.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  return B7_OK;
+}
+
+int b7_cb_compute(b7_ctx *c, const double *mean, const double *var, double tradeoff, int upper, double sign, int64_t M,
+                  int cc, double *out) {
+  if (!c) return B7_ERR_INVALID;
+  if (M < 0 || cc < 1 || (M > 0 && (!mean || !var || !out))) return b7_fail(c, B7_ERR_INVALID, "cb_compute: bad arguments");
+  if (M == 0) return B7_OK;
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(upload_mv(c, mean, var, M, cc));
+  B7_TRY(launch_cb(c, (const double *)c->tmpmu.p, (const double *)c->tmpvar.p, tradeoff, upper, sign, M, cc,
+                   (double *)c->tmpgrid.p, false));
+  B7_HIP(c, hipMemcpyAsync(out, c->tmpgrid.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  return B7_OK;
+}
+
+int b7_argmax(b7_ctx *c, const double *scores, int64_t M, double *best_val, int64_t *best_idx1) {
+  if (!c) return B7_ERR_INVALID;
+  if (M < 1 || !scores) return b7_fail(c, B7_ERR_INVALID, "argmax: empty input");
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(b7_ensure(c, c->tmpgrid, sizeof(double) * (size_t)M));
+  B7_HIP(c, hipMemcpyAsync(c->tmpgrid.p, scores, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+  return launch_finish(c, (double *)c->tmpgrid.p, M, 1.0, best_val, best_idx1);
+}
+
+}  // extern "C"

@@ -4,7 +4,7 @@
 //   utils/math.lua:165      torch.potrf(res, src, 'L')  (LAPACK dpotrf): K = L L'
 //   utils/math.lua:168-202  the pcall/jitter loop around it needs to know THAT a pivot failed: the first
 //                           non-positive pivot is reported (1-based) like dpotrf's info; the retry schedule
-//                           itself runs on the host (api.hip) with the same eps arithmetic
+//                           itself runs on the host (gp_api.hip) with the same eps arithmetic
 //   alpha = L^-T L^-1 (Y - mean)  -- first half of gp_regressor:predict (call site
 //                           scores/expected_improvement.lua:63); the op order inside the absent `gp`
 //                           package is unknown, tolerance-checked against oracle/gp.py

@@ -1036,8 +1036,7 @@ static int fits_per_launch(const b7_ctx *c, int nb, bool with_inverse) {
 }
 
 int launch_nll_batch(b7_ctx *c, int B, const double *K, double *L, double *dinv, unsigned *flags, int *info,
-                     const double *resid, double *terms, const double *extra_per_fit_unused) {
-  (void)extra_per_fit_unused;
+                     const double *resid, double *terms) {
   PhaseScope ps(c, "potrf");
   const int n = c->Npad, nb = n / NB;
   const int4 *jobs = nullptr;

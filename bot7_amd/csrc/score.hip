@@ -121,6 +121,7 @@ struct Best {
   double v;
   int64_t i;
 };
+static_assert(sizeof(Best) == sizeof(BestPair) && offsetof(Best, i) == offsetof(BestPair, i), "PinnedBlock::best holds a Best");
 __device__ __forceinline__ bool better(const Best &a, const Best &b) {  // is a strictly preferred to b
   if (b.i < 0) return a.i >= 0;
   if (a.i < 0) return false;
@@ -396,8 +397,8 @@ int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *bes
   Best *part = (Best *)c->part.p;
   hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, M, divisor, part);
   // the final (value, index) goes straight into pinned, device-mapped host memory: no copy, just the synchronisation
-  Best *res_dev = reinterpret_cast<Best *>(static_cast<char *>(c->pinned_dev) + 2304);
-  const Best &h = *reinterpret_cast<const Best *>(static_cast<const char *>(c->pinned) + 2304);
+  Best *res_dev = reinterpret_cast<Best *>(&c->pinned_dev->best);
+  const BestPair &h = c->pinned->best;
   hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, c->stream, (const Best *)part, nb, res_dev);
   B7_HIP(c, hipGetLastError());
   B7_HIP(c, hipStreamSynchronize(c->stream));

@@ -18,13 +18,6 @@
 
 namespace {
 
-constexpr int SOBOL_DIMS = 40;  // table rows (the reference admits dims < 40, grids/sobol.lua:36)
-constexpr int SOBOL_BITS = 30;  // log_max, grids/sobol.lua:32
-
-struct SobolTable {
-  uint32_t v[SOBOL_DIMS][SOBOL_BITS];
-};
-
 // Direction numbers V[i][b] = m_{b+1} * 2^(29-b), Bratley & Fox section 2, from the reference's tables.
 SobolTable make_table() {
   static const unsigned short poly[SOBOL_DIMS] = {1,   3,   7,   11,  13,  19,  25,  37,  59,  47,
@@ -260,7 +253,7 @@ int grid_blocks(b7_ctx *c, int64_t total) {
 int upload_minmax(b7_ctx *c, const double *mins, const double *maxes, int dims, const double **dev) {
   *dev = nullptr;
   if (!mins || !maxes) return B7_OK;
-  double *p = (double *)((char *)c->scratch.p + 4096 + sizeof(SobolTable));
+  double *p = b7_scratch(c)->minmax;
   B7_HIP(c, hipMemcpyAsync(p, mins, sizeof(double) * dims, hipMemcpyHostToDevice, c->stream));
   B7_HIP(c, hipMemcpyAsync(p + dims, maxes, sizeof(double) * dims, hipMemcpyHostToDevice, c->stream));
   *dev = p;
@@ -280,7 +273,7 @@ extern "C" int b7_sobol_direction_numbers(int dims, uint32_t *out) {
 int launch_sobol(b7_ctx *c, double *out, int64_t size, int dims, int64_t skip, const double *mins,
                  const double *maxes) {
   PhaseScope ps(c, "sobol");
-  uint32_t *vt = (uint32_t *)((char *)c->scratch.p + 4096);
+  uint32_t *vt = &b7_scratch(c)->sobol.v[0][0];
   B7_HIP(c, hipMemcpyAsync(vt, &table(), sizeof(SobolTable), hipMemcpyHostToDevice, c->stream));
   const double *mm = nullptr;
   B7_TRY(upload_minmax(c, mins, maxes, dims, &mm));
