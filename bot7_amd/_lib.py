@@ -22,13 +22,13 @@ SYMBOLS = [
     "b7_sobol_direction_numbers", "b7_grid_sobol", "b7_grid_random", "b7_grid_upload", "b7_grid_download", "b7_grid_shape", "b7_grid_remove", "b7_grid_remove_rows",
     "b7_grid_colrange", "b7_grid_apply_onesided", "b7_grid_random_torch", "b7_torch_rand",
     "b7_gp_default_opts", "b7_gp_set_opts", "b7_gp_set_kernel", "b7_gp_fit", "b7_gp_set_data", "b7_gp_fit_hyp", "b7_gp_predict_hyp", "b7_gp_nll_batch", "b7_chol", "b7_gp_predict", "b7_gp_predict_at", "b7_gp_fantasize", "b7_gp_append", "b7_gp_download",
-    "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_cb", "b7_score_finish",
+    "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_cb", "b7_score_finish",
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
     "b7_group_grid_sobol", "b7_group_grid_random", "b7_group_grid_onesided", "b7_group_grid_upload", "b7_group_grid_shape", "b7_group_grid_download",
     "b7_group_grid_remove_rows", "b7_group_gp_set_data", "b7_group_eval_nominate", "b7_group_nominate_commit",
-    "b7_ei_compute", "b7_cb_compute", "b7_argmax",
+    "b7_ei_compute", "b7_cb_compute", "b7_logei_compute", "b7_argmax",
     "b7_timer_start", "b7_timer_stop", "b7_timer_ms", "b7_profile_enable", "b7_profile_reset", "b7_profile_get", "b7_persist_fallbacks",
 ]
 
@@ -49,7 +49,7 @@ class ScoreSpec(C.Structure):
                 ("fmin", C.POINTER(C.c_double))]
 
 
-SCORE_EI, SCORE_CB = 1, 2
+SCORE_EI, SCORE_CB, SCORE_LOGEI = 1, 2, 3
 
 # covariance kernels (b7_gp_set_kernel): config.model.kernel names (bots/bayesopt.lua:41) -> B7_KERNEL_*
 KERNELS = {"ardse": 0, "ardmatern52": 1}
@@ -143,6 +143,7 @@ def load(which=None):
         "b7_blr_predict": (i32, [vp, vp, vp]),
         "b7_score_reset": (i32, [vp]),
         "b7_score_ei": (i32, [vp, vp, dbl]),
+        "b7_score_logei": (i32, [vp, vp, dbl]),
         "b7_score_cb": (i32, [vp, dbl, i32, dbl]),
         "b7_score_finish": (i32, [vp, dbl, C.POINTER(dbl), C.POINTER(i64), vp]),
         "b7_comm_pick_winner": (i32, [vp, i32, C.POINTER(dbl), C.POINTER(i64)]),
@@ -185,6 +186,7 @@ def load(which=None):
         "b7_group_nominate_commit": (i32, [vp, i64, vp]),
         "b7_ei_compute": (i32, [vp, vp, vp, vp, dbl, i64, i32, vp]),
         "b7_cb_compute": (i32, [vp, vp, vp, dbl, i32, dbl, i64, i32, vp]),
+        "b7_logei_compute": (i32, [vp, vp, vp, vp, dbl, i64, i32, vp]),
         "b7_argmax": (i32, [vp, vp, i64, C.POINTER(dbl), C.POINTER(i64)]),
         "b7_timer_start": (i32, [vp, i32]),
         "b7_timer_stop": (i32, [vp, i32]),
@@ -638,6 +640,11 @@ class Context(object):
         f = _f64(fmin).ravel()
         self._ck(self._L.b7_score_ei(self._h, _ptr(f), float(tradeoff)))
 
+    def score_logei(self, fmin, tradeoff=0.0):
+        """Log-space EI of the last predict, folded into the accumulator as a running log-sum-exp (b7_score_logei)."""
+        f = _f64(fmin).ravel()
+        self._ck(self._L.b7_score_logei(self._h, _ptr(f), float(tradeoff)))
+
     def score_cb(self, tradeoff=1.0, upper=False, sign=-1.0):
         self._ck(self._L.b7_score_cb(self._h, float(tradeoff), int(bool(upper)), float(sign)))
 
@@ -711,16 +718,16 @@ class Context(object):
 
     @staticmethod
     def _pack_spec(score, fmin, tradeoff, upper, sign):
-        if score == "ei":
+        if score in ("ei", "logei"):
             if fmin is None:
                 raise Bot7HipError(-1, "EI needs fmin")
             fm = _f64(fmin).ravel()
-            return ScoreSpec(SCORE_EI, 0.0 if tradeoff is None else float(tradeoff), 0, 0.0,
+            return ScoreSpec(SCORE_EI if score == "ei" else SCORE_LOGEI, 0.0 if tradeoff is None else float(tradeoff), 0, 0.0,
                              fm.ctypes.data_as(C.POINTER(C.c_double))), fm
         if score == "cb":
             return ScoreSpec(SCORE_CB, 1.0 if tradeoff is None else float(tradeoff), int(bool(upper)), float(sign),
                              None), None
-        raise Bot7HipError(-1, "score must be 'ei' or 'cb'")
+        raise Bot7HipError(-1, "score must be 'ei', 'logei' or 'cb'")
 
     def eval_nominate(self, hyps, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0,
                       global_row_offset=0, want_report=False):
@@ -746,6 +753,16 @@ class Context(object):
         var, fmin = _f64(var).ravel(), _f64(fmin).ravel()
         out = np.empty(M, dtype=np.float64)
         self._ck(self._L.b7_ei_compute(self._h, _ptr(mean), _ptr(var), _ptr(fmin), float(tradeoff), M, c, _ptr(out)))
+        return out
+
+    def logei_compute(self, mean, var, fmin, tradeoff=0.0):
+        """log EI on caller-provided mean (M or M x c) / var (M); c > 1: the log of the row mean of EI (b7_logei_compute)."""
+        mean = _f64(mean)
+        M = mean.shape[0]
+        c = 1 if mean.ndim == 1 else mean.shape[1]
+        var, fmin = _f64(var).ravel(), _f64(fmin).ravel()
+        out = np.empty(M, dtype=np.float64)
+        self._ck(self._L.b7_logei_compute(self._h, _ptr(mean), _ptr(var), _ptr(fmin), float(tradeoff), M, c, _ptr(out)))
         return out
 
     def cb_compute(self, mean, var, tradeoff=1.0, upper=False, sign=-1.0):

@@ -95,6 +95,8 @@ static_assert(offsetof(ScratchBlock, lenscale) == 0 && offsetof(ScratchBlock, fm
                   sizeof(ScratchBlock) <= B7_SCRATCH_BYTES,
               "scratch block: the layout every earlier build used");
 
+constexpr int B7_ACC_NONE = 0, B7_ACC_LINEAR = 1, B7_ACC_LOG = 2;  // b7_ctx::acc_kind
+
 struct PhaseStat {
   double ms = 0.0;
   int64_t launches = 0;
@@ -161,7 +163,9 @@ struct b7_ctx {
   bool blr_small = true;     // b7_blr_eval_nominate: the head for z <= 64 features in one workgroup of one launch (blr_small.hip)
   double fmin_scalar = 0.0;  // f_min of a single response column: a kernel argument of the EI kernels (launched with fmin_dev == nullptr), no staging copy
   bool acc_fresh = false;  // the accumulator stands for zeros that were never written: the next score launch onto it starts from 0.0
-                           // (acc_valid and acc_fresh change only through score.hip's acc_* helpers)
+                           // (acc_valid, acc_fresh and acc_kind change only through score.hip's acc_* helpers)
+  int acc_kind = 0;        // what the live accumulator holds (B7_ACC_*): nothing added since the reset, a linear sum (EI, CB), or a
+                           // running log-sum-exp (LogEI), whose empty value is -inf and whose score:div is a subtraction of log(divisor)
   DevBuf ks;     // K(X*,X) chunk workspace
   size_t ks_bytes = (size_t)4 << 30;
   int diag_variant = 1;  // 64x64 diagonal-block kernel: 0 = rsqrt pivot chain, 1 = square-root-free chain with the DPP-fused
@@ -322,6 +326,8 @@ int launch_ei_batch(b7_ctx *c, int S, const double *mu, const double *var, int64
                     double tradeoff, int64_t M, double *acc);
 int launch_cb_batch(b7_ctx *c, int S, const double *mu, const double *var, int64_t stride, double tradeoff, int upper,
                     double sign, int64_t M, double *acc);
+int launch_logei_batch(b7_ctx *c, int S, const double *mu, const double *var, int64_t stride, const double *fmin_dev,
+                       double tradeoff, int64_t M, double *acc);
 int launch_kxx_batch(b7_ctx *c, int B, const double *ls_dev, const double *amp_dev, const double *noise_dev, double *w,
                      double *zsc, double *zss, double *K);
 int launch_ksx(b7_ctx *c, const double *xq, int64_t row0, int64_t rows, int64_t Mtotal, int d, double *ks,
@@ -416,18 +422,21 @@ int launch_ei(b7_ctx *c, const double *mu, const double *var, const double *fmin
               int64_t M, int ycols, double *out, bool accumulate);
 int launch_cb(b7_ctx *c, const double *mu, const double *var, double tradeoff, int upper, double sign, int64_t M,
               int ycols, double *out, bool accumulate);
-int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *best_val, int64_t *best_idx1);
+int launch_logei(b7_ctx *c, const double *mu, const double *var, const double *fmin_dev, double tradeoff,
+                 int64_t M, int ycols, double *out, bool accumulate);
+// logacc: acc is a log accumulator -- score:div is acc - log(divisor)
+int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *best_val, int64_t *best_idx1, bool logacc = false);
 int launch_fill(b7_ctx *c, double *p, int64_t n, double v);
 int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64_t *tab_dev, int rank, int world,
                        int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
-                       unsigned *host_done = nullptr);
+                       unsigned *host_done = nullptr, bool logacc = false);
 
 int launch_score_finish_slot(b7_ctx *c, const PendingScore &ps, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
                              int rank, int world, int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
                              unsigned *host_done = nullptr);
 // the accumulator's state: zeros declared (bots/bayesopt.lua:69 without a launch of its own: the first score launch onto it
 // starts from 0.0), zeros written now, no accumulator (the grid changed), declared zeros written before anybody reads them
-void acc_declare_zeros(b7_ctx *c);
+void acc_declare_zeros(b7_ctx *c, bool log = false);
 int acc_write_zeros(b7_ctx *c);
 void acc_forget(b7_ctx *c);
 int acc_materialize(b7_ctx *c);
@@ -478,6 +487,7 @@ static inline HypPack hyp_pack(void *base, int B, int d) {
 // the per-sample redo
 int nominate_args(b7_ctx *c, const char *who, const b7_score_spec *spec, int64_t offset);
 int stage_fmin(b7_ctx *c, const double *fmin, double **fd_out);
+static inline bool score_needs_fmin(int kind) { return kind == B7_SCORE_EI || kind == B7_SCORE_LOGEI; }
 // the acquisition of c->mu / c->var over the resident candidates into c->acc: added (score:add) or, for a single model, written
 int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumulate = true);
 PendingScore pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd);

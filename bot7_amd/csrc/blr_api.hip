@@ -187,7 +187,7 @@ static int blr_enqueue_score(b7_ctx *c, const b7_mlp *net, int z, const b7_score
   // bots/bayesopt.lua:65-66: the score of the one model, no accumulation over samples -> written, not added (which makes the
   // accumulator valid: score.hip, acc_mode)
   double *fd = nullptr;
-  if (spec->kind == B7_SCORE_EI) B7_TRY(stage_fmin(c, spec->fmin, &fd));
+  if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
   return score_add(c, spec, fd, false);
 }
 
@@ -211,7 +211,7 @@ static int blr_marg_slow(b7_ctx *c, const b7_mlp *net, const double *X0, const d
     c->Mfeat = c->M;
     B7_TRY(blr_predict_enqueue(c, c->M));
     double *fd = nullptr;
-    if (spec->kind == B7_SCORE_EI) B7_TRY(stage_fmin(c, spec->fmin, &fd));
+    if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
     B7_TRY(score_add(c, spec, fd));
   }
   return B7_OK;
@@ -258,8 +258,8 @@ static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const d
   B7_TRY(launch_post_heads(c, S, (const double *)c->bLinv.p, (const double *)c->feat.p, round_up(c->M, B7_MROWS), c->M,
                            (double *)c->bvar.p, c->M, hdev + 3 * (size_t)S, hdev + 4 * (size_t)S));
   double *fd = nullptr;
-  if (spec->kind == B7_SCORE_EI) B7_TRY(stage_fmin(c, spec->fmin, &fd));
-  acc_declare_zeros(c);
+  if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
+  acc_declare_zeros(c, spec->kind == B7_SCORE_LOGEI);
   *pend = pending_score(c, S, spec, fd);
   return B7_OK;
 }

@@ -97,7 +97,7 @@ int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, b
   if (c->M > 0) B7_TRY(acc_materialize(c));
   return launch_finish_slot(c, c->M > 0 ? (double *)c->acc.p : nullptr, c->M, divisor, (uint64_t *)c->slots.p, rank, world,
                             offset, c->M > 0 ? (const double *)c->grid[c->grid_cur].p : nullptr, c->d, all_slots, host_rec,
-                            host_done);
+                            host_done, c->acc_kind == B7_ACC_LOG);
 }
 
 // Everything enqueued before the mirrored arg-max has completed once its word is up (one stream).  Short nominations are

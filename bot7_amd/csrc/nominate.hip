@@ -37,6 +37,9 @@ int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumul
   if (sp->kind == B7_SCORE_EI)
     return launch_ei(c, (const double *)c->mu.p, (const double *)c->var.p, fd, sp->tradeoff, c->M, c->ycols,
                      (double *)c->acc.p, accumulate);
+  if (sp->kind == B7_SCORE_LOGEI)
+    return launch_logei(c, (const double *)c->mu.p, (const double *)c->var.p, fd, sp->tradeoff, c->M, c->ycols,
+                        (double *)c->acc.p, accumulate);
   return launch_cb(c, (const double *)c->mu.p, (const double *)c->var.p, sp->tradeoff, sp->upper, sp->sign, c->M,
                    c->ycols, (double *)c->acc.p, accumulate);
 }
@@ -44,9 +47,9 @@ int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumul
 // The score spec and the global row offset of an eval + nominate entry point (`who` in the messages).  Only a shard of a
 // larger candidate set -- a rank of a communicator, a member of a group -- may be empty: the exchange covers the others.
 int nominate_args(b7_ctx *c, const char *who, const b7_score_spec *spec, int64_t offset) {
-  if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB)
+  if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB && spec->kind != B7_SCORE_LOGEI)
     return b7_fail(c, B7_ERR_INVALID, "%s: unknown score kind %d", who, spec->kind);
-  if (spec->kind == B7_SCORE_EI && !spec->fmin) return b7_fail(c, B7_ERR_INVALID, "%s: EI needs fmin", who);
+  if (score_needs_fmin(spec->kind) && !spec->fmin) return b7_fail(c, B7_ERR_INVALID, "%s: EI needs fmin", who);
   if (offset < 0) return b7_fail(c, B7_ERR_INVALID, "%s: negative row offset", who);
   if (c->M == 0 && !(c->comm && c->comm_world > 1) && !c->group)
     return b7_fail(c, B7_ERR_STATE, "%s: no candidate grid on this context", who);
@@ -122,9 +125,9 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
   }
   if (!small) B7_HIP(c, hipMemcpyAsync(c->bhyp.p, ls_host, ls_bytes, hipMemcpyHostToDevice, c->stream));
   double *fd = nullptr;
-  if (spec->kind == B7_SCORE_EI) B7_TRY(stage_fmin(c, spec->fmin, &fd));
+  if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
 
-  acc_declare_zeros(c);
+  acc_declare_zeros(c, spec->kind == B7_SCORE_LOGEI);
   if (batch) {
     const HypPack hd = hyp_pack(c->bhyp.p, S, d);
     const double *hyp_dev = hd.ls, *amp_dev = hd.amp, *noise_dev = hd.noise, *mean_dev = hd.mean;
@@ -182,6 +185,9 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
       if (spec->kind == B7_SCORE_EI)
         B7_TRY(launch_ei_batch(c, S, (const double *)c->bmu.p, (const double *)c->bvar.p, c->M, fd, spec->tradeoff, c->M,
                                (double *)c->acc.p));
+      else if (spec->kind == B7_SCORE_LOGEI)
+        B7_TRY(launch_logei_batch(c, S, (const double *)c->bmu.p, (const double *)c->bvar.p, c->M, fd, spec->tradeoff, c->M,
+                                  (double *)c->acc.p));
       else
         B7_TRY(launch_cb_batch(c, S, (const double *)c->bmu.p, (const double *)c->bvar.p, c->M, spec->tradeoff, spec->upper,
                                spec->sign, c->M, (double *)c->acc.p));
@@ -252,7 +258,7 @@ int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, d
     B7_TRY(fit_hyp_core(c, &hyps[s], nullptr, jitter_out ? jitter_out + s : nullptr, info_out ? info_out + s : nullptr, true));
     c->predicted = true;
     c->Mpred = c->M;
-    if (spec->kind == B7_SCORE_EI) B7_TRY(stage_fmin(c, spec->fmin, &fd));
+    if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
     B7_TRY(score_add(c, spec, fd));
   }
   return B7_OK;
@@ -312,6 +318,18 @@ int b7_score_ei(b7_ctx *c, const double *fmin, double tradeoff) {
                    (double *)c->acc.p, true);
 }
 
+// log-space EI of the last predict, folded into the accumulator as a running log-sum-exp (score.hip's header)
+int b7_score_logei(b7_ctx *c, const double *fmin, double tradeoff) {
+  if (!c) return B7_ERR_INVALID;
+  if (!fmin) return b7_fail(c, B7_ERR_INVALID, "score_logei: fmin is NULL");
+  B7_TRY(score_ready(c, "score_logei"));
+  B7_HIP(c, hipSetDevice(c->device));
+  double *fd = nullptr;
+  B7_TRY(stage_fmin(c, fmin, &fd));
+  return launch_logei(c, (const double *)c->mu.p, (const double *)c->var.p, fd, tradeoff, c->M, c->ycols,
+                      (double *)c->acc.p, true);
+}
+
 int b7_score_cb(b7_ctx *c, double tradeoff, int upper, double sign) {
   if (!c) return B7_ERR_INVALID;
   B7_TRY(score_ready(c, "score_cb"));
@@ -325,7 +343,7 @@ int b7_score_finish(b7_ctx *c, double divisor, double *best_val, int64_t *best_i
   if (!c->acc_valid) return b7_fail(c, B7_ERR_STATE, "score_finish: call b7_score_reset first");
   B7_HIP(c, hipSetDevice(c->device));
   B7_TRY(acc_materialize(c));
-  B7_TRY(launch_finish(c, (double *)c->acc.p, c->M, divisor, best_val, best_idx1));
+  B7_TRY(launch_finish(c, (double *)c->acc.p, c->M, divisor, best_val, best_idx1, c->acc_kind == B7_ACC_LOG));
   if (scores_host) {
     B7_HIP(c, hipMemcpyAsync(scores_host, c->acc.p, sizeof(double) * (size_t)c->M, hipMemcpyDeviceToHost, c->stream));
     B7_HIP(c, hipStreamSynchronize(c->stream));
@@ -345,6 +363,23 @@ int b7_ei_compute(b7_ctx *c, const double *mean, const double *var, const double
   B7_HIP(c, hipMemcpyAsync(fd, fmin, sizeof(double) * cc, hipMemcpyHostToDevice, c->stream));
   B7_TRY(launch_ei(c, (const double *)c->tmpmu.p, (const double *)c->tmpvar.p, fd, tradeoff, M, cc,
                    (double *)c->tmpgrid.p, false));
+  B7_HIP(c, hipMemcpyAsync(out, c->tmpgrid.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  return B7_OK;
+}
+
+int b7_logei_compute(b7_ctx *c, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M,
+                     int cc, double *out) {
+  if (!c) return B7_ERR_INVALID;
+  if (M < 0 || cc < 1 || cc > 256 || (M > 0 && (!mean || !var || !fmin || !out)))
+    return b7_fail(c, B7_ERR_INVALID, "logei_compute: bad arguments");
+  if (M == 0) return B7_OK;
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(upload_mv(c, mean, var, M, cc));
+  double *fd = b7_scratch(c)->fmin;
+  B7_HIP(c, hipMemcpyAsync(fd, fmin, sizeof(double) * cc, hipMemcpyHostToDevice, c->stream));
+  B7_TRY(launch_logei(c, (const double *)c->tmpmu.p, (const double *)c->tmpvar.p, fd, tradeoff, M, cc,
+                      (double *)c->tmpgrid.p, false));
   B7_HIP(c, hipMemcpyAsync(out, c->tmpgrid.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
   B7_HIP(c, hipStreamSynchronize(c->stream));
   return B7_OK;

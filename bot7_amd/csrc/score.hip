@@ -9,6 +9,30 @@
 //   bots/bayesopt.lua:69-79                score:add(...) per hyper sample, score:div(nSamples)
 //   bots/bayesopt.lua:96                   score:max(1): first maximum, first NaN wins (TH max)
 // exp/sqrt/division are the correctly-rounded-or-1-ulp ocml double routines; everything else is exact IEEE.
+//
+// Log-space expected improvement (B7_SCORE_LOGEI) has NO counterpart in the reference's scores/: it is EI evaluated so that it
+// never underflows (Ament et al., "Unexpected Improvements to Expected Improvement", NeurIPS 2023).  With the same first three
+// operations as EI -- sigma = sqrt(var); imprv = (fmin - mu) - xi; z = imprv/sigma -- and h(z) = phi(z) + z Phi(z):
+//   logEI = log(sigma) + log h(z)
+//   z >  -1:  log h = log(phi(z) + z * erfc(-z/sqrt2)/2)
+//   z <= -1:  log h = -z^2/2 - log(2 pi)/2 + log1p(-t sqrt(pi/2) erfcx(t/sqrt2)),  t = -z
+//   t >= 1e5: log h = -z^2/2 - log(2 pi)/2 + (-2 log t + log1p(-3/t^2))
+// through ocml's fp64 erfc, erfcx, log1p, log and exp: no tables.  The last line is the far tail of the one above it:
+// r = t sqrt(pi/2) erfcx(t/sqrt2) = 1 - 1/t^2 + 3/t^4 - 15/t^6 + ..., so log(1 - r) = -2 log t + log1p(-3/t^2 + 15/t^4 - ...); at
+// t >= 1e5 the dropped 15/t^4 is below 1.5e-19, far under an ulp of 2 log t.  It is there because r is within half an ulp of 1 from
+// t ~ 3e7 and the roundings of its three multiplications then put it ABOVE 1 about as often as at it: log1p(-r) would be NaN for a
+// finite input, and TH's max lets the first NaN win.  Below 1e5, 1 - r >= 1e-10 and r < 1 by a wide margin.  With the tail, log EI
+// is finite and ordered down to t ~ 1.3e154, where z^2/2 overflows and the score is -inf.  Edge cases, beside EI's
+// (EI: var NaN or < 0 -> NaN; var == 0 -> z = +-inf or NaN and the sum follows IEEE):
+//   var NaN or var < 0        NaN (sigma is NaN)            mu NaN                NaN
+//   var == 0, imprv > 0       log(imprv)                    var == 0, imprv <= 0  -inf
+//   z = +inf (sigma > 0)      log(imprv)                    z = -inf              -inf
+// A finite (mu, var, fmin, xi) with var >= 0 never scores NaN.
+// Marginalisation is log((1/S) sum_s EI_s), not the mean of the logs: the accumulator of LogEI is a running log-sum-exp, empty at
+// -inf, folded by a <- logaddexp(a, v) = max + log1p(exp(min - max)) in sample order (NaN if either is NaN, -inf / +inf when both are);
+// c > 1 response columns are the same fold over the columns of a row, then - log(c); score:div becomes a - log(divisor), the
+// log taken here.  b7_logei_fold is that one operation order for the per-sample kernel, the S-batch kernel and the fused
+// nomination kernel, which is what makes the one-call nomination equal the per-sample loop bit for bit.
 #pragma clang fp contract(off)
 #include "b7_internal.h"
 
@@ -38,6 +62,42 @@ __device__ __forceinline__ double b7_norm_cdf(double z) {
 }
 __device__ __forceinline__ double b7_norm_pdf(double z) {
   return exp((z * z) * -0.5) * 0.3989422804014327;  // 1/math.sqrt(2*math.pi), utils/math.lua:15
+}
+
+// ---- log-space EI (see the header): shared by logei_kernel, logei_batch_kernel and score_finish_slot_logei_kernel ----
+__device__ __forceinline__ double b7_logei(double mu, double var, double fmin, double xi) {
+  const double sigma = sqrt(var);
+  const double imprv = (fmin + (-mu)) + (-xi);
+  const double z = imprv / sigma;
+  if (sigma == 0.0 || z == INFINITY) return (imprv > 0.0) ? log(imprv) : ((imprv != imprv) ? imprv : -INFINITY);
+  if (z == -INFINITY) return -INFINITY;
+  double lh;
+  if (z > -1.0) {
+    const double pdf = exp((z * z) * -0.5) * 0.39894228040143267794;  // 1/sqrt(2 pi)
+    const double cdf = erfc(z * -0.70710678118654752440) * 0.5;       // Phi(z) = erfc(-z/sqrt2)/2
+    lh = log(pdf + (z * cdf));
+  } else {  // NaN comes this way too, and stays NaN
+    const double t = -z;
+    double l1r;  // log(1 - r), r = t sqrt(pi/2) erfcx(t/sqrt2) = -z Phi(z)/phi(z)
+    if (t >= 1e5) {
+      l1r = (log(t) * -2.0) + log1p(-3.0 / (t * t));  // 1 - r = (1 - 3/t^2 + ..)/t^2: r itself rounds to 1 or past it out here
+    } else {
+      const double r = (t * 1.2533141373155002512) * erfcx(t * 0.70710678118654752440);
+      l1r = log1p(-r);
+    }
+    lh = (((z * z) * -0.5) + -0.91893853320467274178) + l1r;  // log phi(z) + log(1 - r)
+  }
+  return log(sigma) + lh;
+}
+__device__ __forceinline__ double b7_logaddexp(double a, double v) {
+  if (a != a || v != v) return a + v;
+  const double m = (a > v) ? a : v, n = (a > v) ? v : a;
+  if (m == -INFINITY || n == INFINITY) return m;  // both -inf, both +inf: n - m would be NaN
+  return m + log1p(exp(n + (-m)));
+}
+// a <- logaddexp(a, logEI): THE operation order of every LogEI path
+__device__ __forceinline__ double b7_logei_fold(double a, double mu, double var, double fmin, double xi) {
+  return b7_logaddexp(a, b7_logei(mu, var, fmin, xi));
 }
 
 __global__ void __launch_bounds__(256)
@@ -111,6 +171,38 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// LogEI of one hyper sample: accumulate 0 writes log EI (c > 1: log of the row mean of EI), 1 folds it into out, 2 folds it into
+// an empty (-inf) accumulator that is not read
+__global__ void __launch_bounds__(256)
+    logei_kernel(const double *__restrict__ mu, const double *__restrict__ var, const double *__restrict__ fmin, double xi,
+                 int64_t M, int c, double *__restrict__ out, int accumulate, double fmin0) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
+    const double vr = var[j];
+    if (c == 1) {
+      const double f = fmin ? fmin[0] : fmin0, m = mu[j];
+      out[j] = accumulate == 1 ? b7_logei_fold(out[j], m, vr, f, xi)
+                               : (accumulate == 2 ? b7_logei_fold(-INFINITY, m, vr, f, xi) : b7_logei(m, vr, f, xi));
+      continue;
+    }
+    double row = -INFINITY;
+    for (int k = 0; k < c; ++k) row = b7_logei_fold(row, mu[j * c + k], vr, fmin[k], xi);
+    row = row + (-log((double)c));
+    out[j] = accumulate == 1 ? b7_logaddexp(out[j], row) : (accumulate == 2 ? b7_logaddexp(-INFINITY, row) : row);
+  }
+}
+// S hyper samples at once (one response column): the same folds in sample order
+__global__ void __launch_bounds__(256)
+    logei_batch_kernel(const double *__restrict__ mu, const double *__restrict__ var, int S, int64_t sstride,
+                       const double *__restrict__ fmin, double xi, int64_t M, double *__restrict__ out, int fresh, double fmin0) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
+    double a = fresh ? -INFINITY : out[j];
+    for (int s = 0; s < S; ++s) a = b7_logei_fold(a, mu[s * sstride + j], var[s * sstride + j], fmin ? fmin[0] : fmin0, xi);
+    out[j] = a;
+  }
+}
+
 __global__ void __launch_bounds__(256) fill_kernel(double *__restrict__ p, int64_t n, double v) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) p[j] = v;
@@ -152,14 +244,14 @@ __device__ __forceinline__ Best block_best(Best x, Best *sh) {
   return sh[0];
 }
 
-// acc[j] /= divisor (score:div), then per-block best.
+// acc[j] /= divisor (score:div; a log accumulator: acc[j] -= log(divisor)), then per-block best.
 __global__ void __launch_bounds__(256)
-    finish_kernel(double *__restrict__ acc, int64_t M, double divisor, Best *__restrict__ part) {
+    finish_kernel(double *__restrict__ acc, int64_t M, double divisor, Best *__restrict__ part, int logacc) {
   __shared__ Best sh[4];
   Best b{0.0, -1};
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    double v = acc[j] / divisor;
+    double v = logacc ? acc[j] + (-log(divisor)) : acc[j] / divisor;
     acc[j] = v;
     Best cnd{v, j};
     if (better(cnd, b)) b = cnd;
@@ -233,7 +325,7 @@ __global__ void __launch_bounds__(256) argmax_slot_kernel(const Best *__restrict
 // the record.  Three dependent launches at the ~4.5 us dispatch floor each become one.
 struct ScoreArgs {
   const double *mu, *var;
-  int S, kind;  // kind: B7_SCORE_EI / B7_SCORE_CB
+  int S, kind;  // kind: B7_SCORE_EI / B7_SCORE_CB / B7_SCORE_LOGEI
   long long sstride;
   const double *fmin;
   double fmin0, tradeoff, sign;
@@ -294,6 +386,59 @@ __global__ void __launch_bounds__(256)
   write_record(f, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
 }
 
+// The same launch for B7_SCORE_LOGEI, a kernel of its own: ocml's erfcx / log1p / log take three times the registers of the EI / CB
+// arms, and the kernel above keeps the instructions it had before LogEI existed.  acc = logaddexp(..logaddexp(-inf, s_0).., s_S-1),
+// acc - log(divisor); then the same per-block best, ticket and last block's pass, here as a function (the kernel above keeps its own
+// inlined text so that its instructions stay what they were: a change to one of the two belongs in the other).
+// Every thread of the block calls; sh: 4 Best, last: one word, both in LDS.
+__device__ __forceinline__ void block_best_ticket_record(Best b, Best *sh, unsigned *last, Best *__restrict__ part,
+                                                         unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank,
+                                                         int world, long long offset, long long M, const double *__restrict__ grid, int d,
+                                                         int all_slots, unsigned long long *__restrict__ host_rec,
+                                                         unsigned *__restrict__ host_done) {
+  b = block_best(b, sh);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = b;
+    __threadfence();  // the partial is visible device-wide before the ticket is taken
+    const unsigned t = atomicAdd(ticket, 1u);
+    *last = (t == gridDim.x - 1) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!*last) return;
+  __threadfence();  // the other blocks' partials, published before their tickets
+  Best f{0.0, -1};
+  for (int j = threadIdx.x; j < (int)gridDim.x; j += blockDim.x) {
+    Best pj;  // agent-scope loads: the partials of other CUs, not a stale line of this CU's cache
+    pj.v = __hip_atomic_load(&part[j].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    pj.i = __hip_atomic_load(&part[j].i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (better(pj, f)) f = pj;
+  }
+  __syncthreads();
+  f = block_best(f, sh);
+  if (threadIdx.x == 0) *ticket = 0u;  // ready for the next launch (stream order: nobody else touches it meanwhile)
+  write_record(f, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
+}
+__global__ void __launch_bounds__(256)
+    score_finish_slot_logei_kernel(ScoreArgs sa, double *__restrict__ acc, long long M, double divisor, Best *__restrict__ part,
+                                   unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank, int world,
+                                   long long offset, const double *__restrict__ grid, int d, int all_slots,
+                                   unsigned long long *__restrict__ host_rec, unsigned *__restrict__ host_done) {
+  __shared__ Best sh[4];
+  __shared__ unsigned last;
+  Best b{0.0, -1};
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
+    double a = sa.fresh ? -INFINITY : acc[j];  // fresh: an empty log-sum-exp, not read
+    for (int s = 0; s < sa.S; ++s)
+      a = b7_logei_fold(a, sa.mu[s * sa.sstride + j], sa.var[s * sa.sstride + j], sa.fmin ? sa.fmin[0] : sa.fmin0, sa.tradeoff);
+    const double v = a + (-log(divisor));
+    acc[j] = v;
+    Best cnd{v, j};
+    if (better(cnd, b)) b = cnd;
+  }
+  block_best_ticket_record(b, sh, &last, part, ticket, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
+}
+
 __global__ void __launch_bounds__(256) keep_record_kernel(unsigned long long *__restrict__ tab, int rank, int world) {
   for (int e = threadIdx.x; e < world * B7_TAB_W; e += blockDim.x)
     if (e / B7_TAB_W != rank) tab[e] = 0ull;
@@ -309,12 +454,25 @@ int nblocks(b7_ctx *c, int64_t n) {
 // 0: out = score; 1: out += score; 2: out = 0.0 + score -- the context's accumulator was declared torch.zeros without being
 // filled (b7_eval_nominate: bots/bayesopt.lua:69 costs no launch of its own) and this is the first score:add onto it.  A score
 // written (not added) onto the accumulator is the accumulator from then on (bots/bayesopt.lua:65-66: the DNGO branch)
-static int acc_mode(b7_ctx *c, const double *out, bool accumulate) {
+// kind: what this launch adds, a linear sum (EI, CB) or a log-sum-exp (LogEI).  The first add after a reset decides what the
+// accumulator holds -- a log one then starts from -inf whatever the reset wrote --; adding the other kind onto it is -1 (the
+// launchers answer B7_ERR_STATE through acc_mode_or_fail)
+static int acc_mode(b7_ctx *c, const double *out, bool accumulate, int kind = B7_ACC_LINEAR) {
   if (out != (const double *)c->acc.p) return accumulate ? 1 : 0;
-  const bool fresh = c->acc_fresh;
+  if (accumulate && c->acc_kind != B7_ACC_NONE && c->acc_kind != kind) return -1;
+  const bool fresh = c->acc_fresh || (accumulate && kind == B7_ACC_LOG && c->acc_kind == B7_ACC_NONE);
   c->acc_fresh = false;
+  c->acc_kind = kind;
   if (!accumulate) c->acc_valid = true;
   return accumulate ? (fresh ? 2 : 1) : 0;
+}
+static int acc_mode_or_fail(b7_ctx *c, const double *out, bool accumulate, int kind, int *mode) {
+  *mode = acc_mode(c, out, accumulate, kind);
+  if (*mode < 0)
+    return b7_fail(c, B7_ERR_STATE, "score: the accumulator holds a %s; a %s cannot be added onto it (b7_score_reset first)",
+                   c->acc_kind == B7_ACC_LOG ? "log-sum-exp (LogEI)" : "linear sum (EI / CB)",
+                   kind == B7_ACC_LOG ? "log score" : "linear score");
+  return B7_OK;
 }
 
 int launch_ei(b7_ctx *c, const double *mu, const double *var, const double *fmin_dev, double tradeoff, int64_t M,
@@ -322,8 +480,23 @@ int launch_ei(b7_ctx *c, const double *mu, const double *var, const double *fmin
   PhaseScope ps(c, "score");
   if (M <= 0) return B7_OK;
   if (!fmin_dev && ycols != 1) return b7_fail(c, B7_ERR_INVALID, "ei: f_min of %d columns must be staged on the device", ycols);
+  int mode;
+  B7_TRY(acc_mode_or_fail(c, out, accumulate, B7_ACC_LINEAR, &mode));
   hipLaunchKernelGGL(ei_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, fmin_dev, tradeoff, M, ycols,
-                     out, acc_mode(c, out, accumulate), c->fmin_scalar);
+                     out, mode, c->fmin_scalar);
+  B7_HIP(c, hipGetLastError());
+  return B7_OK;
+}
+
+int launch_logei(b7_ctx *c, const double *mu, const double *var, const double *fmin_dev, double tradeoff, int64_t M,
+                 int ycols, double *out, bool accumulate) {
+  PhaseScope ps(c, "score");
+  if (M <= 0) return B7_OK;
+  if (!fmin_dev && ycols != 1) return b7_fail(c, B7_ERR_INVALID, "logei: f_min of %d columns must be staged on the device", ycols);
+  int mode;
+  B7_TRY(acc_mode_or_fail(c, out, accumulate, B7_ACC_LOG, &mode));
+  hipLaunchKernelGGL(logei_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, fmin_dev, tradeoff, M, ycols,
+                     out, mode, c->fmin_scalar);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
@@ -332,8 +505,10 @@ int launch_cb(b7_ctx *c, const double *mu, const double *var, double tradeoff, i
               int ycols, double *out, bool accumulate) {
   PhaseScope ps(c, "score");
   if (M <= 0) return B7_OK;
+  int mode;
+  B7_TRY(acc_mode_or_fail(c, out, accumulate, B7_ACC_LINEAR, &mode));
   hipLaunchKernelGGL(cb_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, tradeoff, upper, sign, M,
-                     ycols, out, acc_mode(c, out, accumulate));
+                     ycols, out, mode);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
@@ -342,8 +517,22 @@ int launch_ei_batch(b7_ctx *c, int S, const double *mu, const double *var, int64
                     double tradeoff, int64_t M, double *acc) {
   PhaseScope ps(c, "score");
   if (M <= 0) return B7_OK;
+  int mode;
+  B7_TRY(acc_mode_or_fail(c, acc, true, B7_ACC_LINEAR, &mode));
   hipLaunchKernelGGL(ei_batch_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, S, stride, fmin_dev, tradeoff, M,
-                     acc, acc_mode(c, acc, true) == 2 ? 1 : 0, c->fmin_scalar);
+                     acc, mode == 2 ? 1 : 0, c->fmin_scalar);
+  B7_HIP(c, hipGetLastError());
+  return B7_OK;
+}
+
+int launch_logei_batch(b7_ctx *c, int S, const double *mu, const double *var, int64_t stride, const double *fmin_dev,
+                       double tradeoff, int64_t M, double *acc) {
+  PhaseScope ps(c, "score");
+  if (M <= 0) return B7_OK;
+  int mode;
+  B7_TRY(acc_mode_or_fail(c, acc, true, B7_ACC_LOG, &mode));
+  hipLaunchKernelGGL(logei_batch_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, S, stride, fmin_dev, tradeoff, M,
+                     acc, mode == 2 ? 1 : 0, c->fmin_scalar);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
@@ -352,8 +541,10 @@ int launch_cb_batch(b7_ctx *c, int S, const double *mu, const double *var, int64
                     double sign, int64_t M, double *acc) {
   PhaseScope ps(c, "score");
   if (M <= 0) return B7_OK;
+  int mode;
+  B7_TRY(acc_mode_or_fail(c, acc, true, B7_ACC_LINEAR, &mode));
   hipLaunchKernelGGL(cb_batch_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, S, stride, tradeoff, upper, sign,
-                     M, acc, acc_mode(c, acc, true) == 2 ? 1 : 0);
+                     M, acc, mode == 2 ? 1 : 0);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
@@ -367,9 +558,11 @@ int launch_fill(b7_ctx *c, double *p, int64_t n, double v) {
 
 // ---- the accumulator's state: set here and nowhere else ----
 // torch.zeros(X_hid:size(1)), bots/bayesopt.lua:69, declared without a launch: the first score launch onto it starts from 0.0
-void acc_declare_zeros(b7_ctx *c) {
+// (log: the nomination will fold LogEI into it -- an empty log-sum-exp, -inf, declared the same way)
+void acc_declare_zeros(b7_ctx *c, bool log) {
   c->acc_valid = true;
   c->acc_fresh = true;
+  c->acc_kind = log ? B7_ACC_LOG : B7_ACC_NONE;
 }
 
 // the same zeros written now (the caller has sized c->acc for c->M)
@@ -377,6 +570,7 @@ int acc_write_zeros(b7_ctx *c) {
   B7_TRY(launch_fill(c, (double *)c->acc.p, c->M, 0.0));
   c->acc_valid = true;
   c->acc_fresh = false;
+  c->acc_kind = B7_ACC_NONE;  // the first add decides (acc_mode)
   return B7_OK;
 }
 
@@ -384,18 +578,26 @@ int acc_write_zeros(b7_ctx *c) {
 void acc_forget(b7_ctx *c) {
   c->acc_valid = false;
   c->acc_fresh = false;
+  c->acc_kind = B7_ACC_NONE;
 }
 
-// zeros that were only declared and never met a score launch: written before anybody reads the accumulator
-int acc_materialize(b7_ctx *c) { return c->acc_fresh ? acc_write_zeros(c) : B7_OK; }
+// zeros that were only declared and never met a score launch: written before anybody reads the accumulator (a declared log
+// accumulator: -inf, the empty log-sum-exp)
+int acc_materialize(b7_ctx *c) {
+  if (!c->acc_fresh) return B7_OK;
+  if (c->acc_kind != B7_ACC_LOG) return acc_write_zeros(c);
+  B7_TRY(launch_fill(c, (double *)c->acc.p, c->M, -INFINITY));
+  c->acc_fresh = false;
+  return B7_OK;
+}
 
-int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *best_val, int64_t *best_idx1) {
+int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *best_val, int64_t *best_idx1, bool logacc) {
   PhaseScope ps(c, "argmax");
   if (M <= 0) return b7_fail(c, B7_ERR_INVALID, "finish: empty score vector");
   const int nb = nblocks(c, M);
   B7_TRY(b7_ensure(c, c->part, sizeof(Best) * (size_t)(nb + 1)));
   Best *part = (Best *)c->part.p;
-  hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, M, divisor, part);
+  hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, M, divisor, part, logacc ? 1 : 0);
   // the final (value, index) goes straight into pinned, device-mapped host memory: no copy, just the synchronisation
   Best *res_dev = reinterpret_cast<Best *>(&c->pinned_dev->best);
   const BestPair &h = c->pinned->best;
@@ -412,12 +614,13 @@ int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *bes
 // host_rec / host_done (nullable): device addresses of a mapped host copy of this rank's record and of the word the kernel
 // sets once that copy is complete (comm.hip: exch_local with a mirror).
 int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64_t *tab_dev, int rank, int world,
-                       int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec, unsigned *host_done) {
+                       int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec, unsigned *host_done,
+                       bool logacc) {
   PhaseScope ps(c, "argmax");
   const int nb = M > 0 ? nblocks(c, M) : 0;
   B7_TRY(b7_ensure(c, c->part, sizeof(Best) * (size_t)(nb + 1)));
   Best *part = (Best *)c->part.p;
-  if (nb > 0) hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, M, divisor, part);
+  if (nb > 0) hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, M, divisor, part, logacc ? 1 : 0);
   hipLaunchKernelGGL(argmax_slot_kernel, dim3(1), dim3(256), 0, c->stream, (const Best *)part, nb,
                      (unsigned long long *)tab_dev, rank, world, (long long)offset, (long long)M, grid, d, all_slots ? 1 : 0,
                      -1ll, (unsigned long long *)host_rec, host_done);
@@ -443,11 +646,18 @@ int launch_score_finish_slot(b7_ctx *c, const PendingScore &ps, double *acc, int
     B7_HIP(c, hipMemsetAsync(c->ticket.p, 0, 64, c->stream));
   }
   unsigned *ticket = (unsigned *)c->ticket.p;
+  int mode;
+  B7_TRY(acc_mode_or_fail(c, acc, true, ps.kind == B7_SCORE_LOGEI ? B7_ACC_LOG : B7_ACC_LINEAR, &mode));
   ScoreArgs sa{ps.mu, ps.var, ps.S, ps.kind, (long long)ps.stride, ps.fd, c->fmin_scalar, ps.tradeoff, ps.sign, ps.upper,
-               acc_mode(c, acc, true) == 2 ? 1 : 0};
-  hipLaunchKernelGGL(score_finish_slot_kernel, dim3(nb), dim3(threads), 0, c->stream, sa, acc, (long long)M, divisor, part, ticket,
-                     (unsigned long long *)tab_dev, rank, world, (long long)offset, grid, d, all_slots ? 1 : 0,
-                     (unsigned long long *)host_rec, host_done);
+               mode == 2 ? 1 : 0};
+  if (ps.kind == B7_SCORE_LOGEI)
+    hipLaunchKernelGGL(score_finish_slot_logei_kernel, dim3(nb), dim3(threads), 0, c->stream, sa, acc, (long long)M, divisor, part,
+                       ticket, (unsigned long long *)tab_dev, rank, world, (long long)offset, grid, d, all_slots ? 1 : 0,
+                       (unsigned long long *)host_rec, host_done);
+  else
+    hipLaunchKernelGGL(score_finish_slot_kernel, dim3(nb), dim3(threads), 0, c->stream, sa, acc, (long long)M, divisor, part, ticket,
+                       (unsigned long long *)tab_dev, rank, world, (long long)offset, grid, d, all_slots ? 1 : 0,
+                       (unsigned long long *)host_rec, host_done);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }

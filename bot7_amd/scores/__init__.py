@@ -2,5 +2,7 @@
 from .abstract import abstract  # noqa: F401
 from .expected_improvement import expected_improvement  # noqa: F401
 from .confidence_bound import confidence_bound  # noqa: F401
+from .log_expected_improvement import log_expected_improvement  # noqa: F401
 
-registry = {"expected_improvement": expected_improvement, "confidence_bound": confidence_bound}
+registry = {"expected_improvement": expected_improvement, "confidence_bound": confidence_bound,
+            "log_expected_improvement": log_expected_improvement}

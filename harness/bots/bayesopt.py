@@ -5,7 +5,12 @@ score:add(acq); score:div(nSamples) -- but the accumulator lives on the GPU (b7_
 _finish) so no M-vector crosses PCIe per sample; nominate (:85-99) takes the arg-max from the same finish call
 (score:max(1): first maximum, 1-based).  When only the winner is wanted (nominate) and the score has a device
 spec, the whole of eval + max is ONE library call, b7_eval_nominate: same hyper samples, same arithmetic, one host
-synchronisation instead of one per sample (config.bot.fused, default True)."""
+synchronisation instead of one per sample (config.bot.fused, default True).
+
+config.score.type picks the score from bot7_amd.scores.registry and every path below takes whatever it names: the registry's
+'log_expected_improvement' (log-space EI, not in the reference) travels as score="logei" in the device spec -- fused, sharded and
+group nominations alike -- and as b7_score_logei in the per-sample loop, where score_finish's division is the log accumulator's
+subtraction of log(nSamples)."""
 import numpy as np
 
 from .abstract import abstract

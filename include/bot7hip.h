@@ -260,9 +260,20 @@ int b7_score_ei(b7_ctx *ctx, const double *fmin, double tradeoff);
 /* scores/confidence_bound.lua:70-106; upper != 0 selects UCB (:96-100) else LCB (:102-106); the result is
  * val if sign > 0 else -val (:89-93); added into the accumulator. */
 int b7_score_cb(b7_ctx *ctx, double tradeoff, int upper, double sign);
+/* Log-space expected improvement of the last predict -- NO counterpart in scores/ of the reference (Ament et al.,
+ * "Unexpected Improvements to Expected Improvement", NeurIPS 2023): with sigma, imprv and z as b7_score_ei forms them and
+ * h(z) = phi(z) + z Phi(z),  log EI = log(sigma) + log h(z),  log h = log(phi(z) + z erfc(-z/sqrt2)/2) for z > -1 and
+ * -z^2/2 - log(2 pi)/2 + log1p(-t sqrt(pi/2) erfcx(t/sqrt2)), t = -z, below (from t = 1e5 on the log1p term is its own
+ * expansion, -2 log t + log1p(-3/t^2): the product rounds to 1 or past it out there): finite and ordered where EI has long
+ * underflowed to 0, down to z ~ -1.3e154, and never NaN for finite inputs with var >= 0.  var == 0: log(imprv) for imprv > 0, else -inf; var < 0, NaN: NaN.  The accumulator becomes a running
+ * log-sum-exp (empty at -inf): each call folds a <- logaddexp(a, log EI) -- the marginal is log((1/S) sum_s EI_s), not the
+ * mean of the logs; ycols > 1 (fantasies): the log of the row mean of EI.  The first add after b7_score_reset decides
+ * whether the accumulator is linear (b7_score_ei / _cb) or logarithmic; adding the other kind onto it is B7_ERR_STATE. */
+int b7_score_logei(b7_ctx *ctx, const double *fmin, double tradeoff);
 /* bots/bayesopt.lua:79 score:div(nSamples) then :96 score:max(1): best_val and the 1-based index of the
  * first maximum (first NaN wins, as TH's max).  divisor = 1 skips nothing: x/1 is exact.
- * scores_host nullable (M). */
+ * scores_host nullable (M).  On a log accumulator (b7_score_logei) score:div is a - log(divisor), and best_val /
+ * scores_host are log EI; the same holds for b7_score_finish_global. */
 int b7_score_finish(b7_ctx *ctx, double divisor, double *best_val, int64_t *best_idx1, double *scores_host);
 
 /* ---- multi-GPU: the one exchange of a candidate-sharded nomination (RCCL over xGMI) ------------ *
@@ -343,6 +354,12 @@ int b7_exchange_info(b7_ctx *ctx, int *world, int64_t *rows_per_rank, int64_t *w
  * the S samples (fit again before b7_gp_predict / b7_score_*). */
 #define B7_SCORE_EI 1 /* scores/expected_improvement.lua: needs fmin[ycols]; tradeoff = xi */
 #define B7_SCORE_CB 2 /* scores/confidence_bound.lua: tradeoff = kappa, upper, sign as b7_score_cb */
+/* Log-space EI, as b7_score_logei: no counterpart in scores/ of the reference (Ament et al., NeurIPS 2023).
+ * log EI = log(sigma) + log(phi(z) + z Phi(z)); fmin and tradeoff as for B7_SCORE_EI, upper and sign ignored; the
+ * marginal over the S samples is log((1/S) sum_s EI_s), best_val and the accumulator are log EI.  Accepted by every
+ * eval + nominate entry point (b7_eval_nominate, b7_group_eval_nominate, b7_blr_eval_nominate, b7_blr_eval_nominate_marg).
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_SCORE_LOGEI 3
 typedef struct {
   int kind;
   double tradeoff;
@@ -426,6 +443,11 @@ int b7_ei_compute(b7_ctx *ctx, const double *mean, const double *var, const doub
                   int64_t M, int c, double *out);
 int b7_cb_compute(b7_ctx *ctx, const double *mean, const double *var, double tradeoff, int upper, double sign,
                   int64_t M, int c, double *out);
+/* b7_ei_compute's sibling in log space -- no counterpart in scores/ of the reference (Ament et al., NeurIPS 2023):
+ * out[j] = log(sigma_j) + log(phi(z) + z Phi(z)), z = ((fmin - mean_j) - tradeoff) / sigma_j, evaluated as b7_score_logei
+ * describes; c > 1 columns: out[j] = log((1/c) sum_k EI_jk) by log-sum-exp over the columns. */
+int b7_logei_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff,
+                     int64_t M, int c, double *out);
 int b7_argmax(b7_ctx *ctx, const double *scores, int64_t M, double *best_val, int64_t *best_idx1);
 
 /* ---- measurement ------------------------------------------------------------------------------ */

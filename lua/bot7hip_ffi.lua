@@ -56,6 +56,7 @@ int b7_blr_predict(b7_ctx *ctx, double *mean_host, double *var_host);
 int b7_score_reset(b7_ctx *ctx);
 int b7_score_ei(b7_ctx *ctx, const double *fmin, double tradeoff);
 int b7_score_cb(b7_ctx *ctx, double tradeoff, int upper, double sign);
+int b7_score_logei(b7_ctx *ctx, const double *fmin, double tradeoff);
 int b7_score_finish(b7_ctx *ctx, double divisor, double *best_val, int64_t *best_idx1, double *scores_host);
 int b7_comm_unique_id(void *id_out);
 int b7_comm_init(b7_ctx *ctx, int rank, int world, const void *id);
@@ -92,6 +93,7 @@ int b7_group_eval_nominate(b7_group *g, int S, const b7_hyp *hyps, const b7_scor
 int b7_group_nominate_commit(b7_group *g, int64_t idx1_global, double *row_out);
 int b7_ei_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M, int c, double *out);
 int b7_cb_compute(b7_ctx *ctx, const double *mean, const double *var, double tradeoff, int upper, double sign, int64_t M, int c, double *out);
+int b7_logei_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M, int c, double *out);
 int b7_argmax(b7_ctx *ctx, const double *scores, int64_t M, double *best_val, int64_t *best_idx1);
 int b7_timer_start(b7_ctx *ctx, int slot);
 int b7_timer_stop(b7_ctx *ctx, int slot);
@@ -125,6 +127,7 @@ M.COMM_MAX = 1
 M.COMM_MIN = 2
 M.SCORE_EI = 1
 M.SCORE_CB = 2
+M.SCORE_LOGEI = 3
 M.MAX_TIMERS = 16
 -- END generated constants
 

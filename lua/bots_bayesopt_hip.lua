@@ -35,10 +35,11 @@ end
 -- b7_score_spec of a *_hip score object, or nil when the score has no device form
 local function score_spec(score, Y_obs, keep)
   local cfg, kind = score.config or {}, torch.type(score)
-  if kind == 'bot7.scores.expected_improvement_hip' then
+  if kind == 'bot7.scores.expected_improvement_hip' or kind == 'bot7.scores.log_expected_improvement_hip' then
     local fmins = hip.pin(Y_obs:min(1):view(-1))            -- scores/expected_improvement.lua:64
     keep[#keep + 1] = fmins
-    return ffi.new('b7_score_spec', {hip.SCORE_EI, cfg.tradeoff or 0.0, 0, 0.0, hip.data(fmins)})
+    local code = (kind == 'bot7.scores.expected_improvement_hip') and hip.SCORE_EI or hip.SCORE_LOGEI   -- log-space EI: no original
+    return ffi.new('b7_score_spec', {code, cfg.tradeoff or 0.0, 0, 0.0, hip.data(fmins)})
   elseif kind == 'bot7.scores.confidence_bound_hip' then
     local upper = (string.lower(cfg.bound or 'lower') == 'upper') and 1 or 0   -- scores/confidence_bound.lua:72
     return ffi.new('b7_score_spec', {hip.SCORE_CB, cfg.tradeoff or 1.0, upper, cfg.sign or -1.0, nil})

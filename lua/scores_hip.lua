@@ -2,6 +2,8 @@
 Drop-ins for bot7.scores.expected_improvement / confidence_bound (scores/*.lua) backed by b7_score_*.
 Register:  local S = require('bot7hip.scores_hip')
            bot7.scores.expected_improvement = S.expected_improvement ; bot7.scores.confidence_bound = S.confidence_bound
+S.log_expected_improvement has no original to replace: log-space EI (b7_score_logei; Ament et al., NeurIPS 2023), which still
+ranks the candidates where EI has underflowed to 0.  Register it as a new score: bot7.scores.log_expected_improvement = ...
 They return the M-element score tensor like the originals (bots/bayesopt.lua:76 adds it); with a gp_hip model the
 posterior never leaves the GPU between predict and score.  Mirrors bot7_amd/scores/*.py.
 --]]
@@ -43,6 +45,45 @@ do
     return finish(X_hid:size(1))
   end
   S.expected_improvement = EI
+end
+
+do
+  -- log EI = log(sigma) + log(phi(z) + z Phi(z)); config and the pending-points branch are EI's own.  The tensor it returns
+  -- holds LOGARITHMS: a host-side marginalisation (bots/bayesopt.lua:76-79 score:add / score:div) would average logs, so
+  -- this score is meant for the fused nomination (bots_bayesopt_hip), which marginalises by log-sum-exp on the device and
+  -- never calls this method.  A call from anywhere else says so once, on stderr
+  local warned = false
+  local LEI, parent = torch.class('bot7.scores.log_expected_improvement_hip', 'bot7.scores.abstract')
+  function LEI:__init(config)
+    parent.__init(self)
+    local config = config or {}
+    config['tradeoff']   = config.tradeoff or 0.0
+    config['nFantasies'] = config.nFantasies or 100
+    self.config = config
+  end
+  function LEI:__call__(model, hyp, X_obs, Y_obs, X_hid, X_pend, config)
+    if not warned then
+      warned = true
+      io.stderr:write('bot7.scores.log_expected_improvement_hip: returning LOG scores; averaging them over hyper samples on the ',
+                      'host (bot7.bots.bayesopt) is not the marginal EI: use bot7.bots.bayesopt_hip, or nSamples = 1\n')
+    end
+    local hyp, config = hyp or model.hyp, config or self.config
+    local X_obs, Y_obs = X_obs, Y_obs
+    if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
+    if torch.isTensor(X_pend) and X_pend:dim() > 0 and X_pend:size(1) > 0 then
+      if X_pend:dim() == 1 then X_pend = X_pend:view(1, -1) end
+      local Y_fant = model:fantasize(config.nFantasies, X_obs, Y_obs, X_pend, hyp)
+      Y_obs = Y_obs:narrow(2, 1, 1):repeatTensor(1, config.nFantasies)
+      Y_obs = Y_obs:cat(Y_fant, 1)
+      X_obs = X_obs:cat(X_pend, 1)
+    end
+    model:predict_device(X_obs, Y_obs, X_hid, hyp)
+    local fmins = hip.pin(Y_obs:min(1):view(-1))
+    hip.check(hip.C.b7_score_reset(hip.ctx))
+    hip.check(hip.C.b7_score_logei(hip.ctx, hip.data(fmins), config.tradeoff or 0.0))   -- the log of the row mean when > 1 column
+    return finish(X_hid:size(1))
+  end
+  S.log_expected_improvement = LEI
 end
 
 do
