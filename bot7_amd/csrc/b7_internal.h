@@ -102,15 +102,16 @@ struct PhaseStat {
   int64_t launches = 0;
 };
 
-// A nomination's batched score (all S samples' mean / variance on the device), not launched yet: the exchange step runs it fused
-// with score:div, the arg-max and the record (score.hip: score_finish_slot_kernel).  A value of the call that made it, never
-// of the context: no later call can meet a pending score.
-struct PendingScore {
-  bool on = false;
-  int kind = 0, S = 0, upper = 0;
-  const double *mu = nullptr, *var = nullptr, *fd = nullptr;
-  int64_t stride = 0;
-  double tradeoff = 0.0, sign = 0.0;
+// A score's parameters as the kernels take them (score.hip), built by score_params (nominate.hip) and nowhere else: S hyper
+// samples' mean / variance on the device, sample s at mu + s * stride.  fmin == nullptr: one response column, its f_min in fmin0.
+// S == 0: no score.  With S > 0 it is also a nomination's batched score, not launched yet: the exchange step runs it fused with
+// score:div, the arg-max and the record (score.hip: score_finish_slot_kernel).  A value of the call that made it, never of the
+// context: no later call can meet a pending score.
+struct ScoreParams {
+  int kind = 0, S = 0, upper = 0;  // kind: B7_SCORE_*
+  const double *mu = nullptr, *var = nullptr, *fmin = nullptr;
+  long long stride = 0;
+  double fmin0 = 0.0, tradeoff = 0.0, sign = 0.0;
 };
 
 struct b7_ctx {
@@ -322,12 +323,6 @@ int launch_kxx(b7_ctx *c, double diag_add);
 int launch_ksx_batch(b7_ctx *c, int S, const double *xq, int64_t rows, int64_t Mtotal, const double *w, const double *zsc,
                      const double *zss, const double *amp_dev, const double *mean_dev, const double *alpha, double *ks,
                      int64_t s_out, double *mu, int64_t s_mu);
-int launch_ei_batch(b7_ctx *c, int S, const double *mu, const double *var, int64_t stride, const double *fmin_dev,
-                    double tradeoff, int64_t M, double *acc);
-int launch_cb_batch(b7_ctx *c, int S, const double *mu, const double *var, int64_t stride, double tradeoff, int upper,
-                    double sign, int64_t M, double *acc);
-int launch_logei_batch(b7_ctx *c, int S, const double *mu, const double *var, int64_t stride, const double *fmin_dev,
-                       double tradeoff, int64_t M, double *acc);
 int launch_kxx_batch(b7_ctx *c, int B, const double *ls_dev, const double *amp_dev, const double *noise_dev, double *w,
                      double *zsc, double *zss, double *K);
 int launch_ksx(b7_ctx *c, const double *xq, int64_t row0, int64_t rows, int64_t Mtotal, int d, double *ks,
@@ -418,12 +413,9 @@ int launch_transpose_pad(b7_ctx *c, const double *Z, int n, int ldz, int z, doub
 int launch_blr_assemble(b7_ctx *c, const double *G, double *K, int z, int zpad, double alpha_prec, double beta);
 
 // score.hip
-int launch_ei(b7_ctx *c, const double *mu, const double *var, const double *fmin_dev, double tradeoff,
-              int64_t M, int ycols, double *out, bool accumulate);
-int launch_cb(b7_ctx *c, const double *mu, const double *var, double tradeoff, int upper, double sign, int64_t M,
-              int ycols, double *out, bool accumulate);
-int launch_logei(b7_ctx *c, const double *mu, const double *var, const double *fmin_dev, double tradeoff,
-                 int64_t M, int ycols, double *out, bool accumulate);
+// one hyper sample's score of mu (M x ycols) / var (M) written to out or added onto it; p's S samples added onto acc in order
+int launch_score(b7_ctx *c, ScoreParams p, const double *mu, const double *var, int64_t M, int ycols, double *out, bool accumulate);
+int launch_score_batch(b7_ctx *c, const ScoreParams &p, double *acc, int64_t M);
 // logacc: acc is a log accumulator -- score:div is acc - log(divisor)
 int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *best_val, int64_t *best_idx1, bool logacc = false);
 int launch_fill(b7_ctx *c, double *p, int64_t n, double v);
@@ -431,12 +423,13 @@ int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64
                        int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
                        unsigned *host_done = nullptr, bool logacc = false);
 
-int launch_score_finish_slot(b7_ctx *c, const PendingScore &ps, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
+int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
                              int rank, int world, int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
                              unsigned *host_done = nullptr);
 // the accumulator's state: zeros declared (bots/bayesopt.lua:69 without a launch of its own: the first score launch onto it
-// starts from 0.0), zeros written now, no accumulator (the grid changed), declared zeros written before anybody reads them
-void acc_declare_zeros(b7_ctx *c, bool log = false);
+// starts from 0.0; score_kind: the B7_SCORE_* it will add), zeros written now, no accumulator (the grid changed), declared zeros
+// written before anybody reads them
+void acc_declare_zeros(b7_ctx *c, int score_kind);
 int acc_write_zeros(b7_ctx *c);
 void acc_forget(b7_ctx *c);
 int acc_materialize(b7_ctx *c);
@@ -449,7 +442,7 @@ int launch_row_slot(b7_ctx *c, uint64_t *tab_dev, int rank, int world, int64_t i
 int exch_table_ensure(b7_ctx *c, int world);
 // enqueue: score:div, local arg-max, this rank's record; pend (nullable): the nomination's batched score, run fused with them
 int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, bool all_slots, bool mirror = false,
-               const PendingScore *pend = nullptr);
+               const ScoreParams *pend = nullptr);
 int exch_wait_mirror(b7_ctx *c);  // after exch_local(..., mirror = true): spin on the completion word, then (or instead, when it takes long) the stream
 int exch_fail_record(b7_ctx *c, int rank, int world, int code);  // enqueue: this rank's record says "could not score"
 int exch_allreduce(b7_ctx *c);                                   // enqueue: the collective (no-op without a communicator)
@@ -488,11 +481,15 @@ static inline HypPack hyp_pack(void *base, int B, int d) {
 int nominate_args(b7_ctx *c, const char *who, const b7_score_spec *spec, int64_t offset);
 int stage_fmin(b7_ctx *c, const double *fmin, double **fd_out);
 static inline bool score_needs_fmin(int kind) { return kind == B7_SCORE_EI || kind == B7_SCORE_LOGEI; }
+// what a score of this kind leaves in an accumulator: a linear sum (EI, CB) or a log-sum-exp (LogEI)
+constexpr int score_acc_kind(int kind) { return kind == B7_SCORE_LOGEI ? B7_ACC_LOG : B7_ACC_LINEAR; }
+// a score's parameters from its spec; fd: f_min staged on the device (stage_fmin), or null with the one column's f_min in c->fmin_scalar
+ScoreParams score_params(const b7_ctx *c, const b7_score_spec *spec, const double *fd);
 // the acquisition of c->mu / c->var over the resident candidates into c->acc: added (score:add) or, for a single model, written
 int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumulate = true);
-PendingScore pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd);
+ScoreParams pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd);
 int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t offset);
-int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, PendingScore *pend);
+int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend);
 bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist);
 int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out);
 // grid_api.hip
@@ -506,7 +503,7 @@ template <class Enqueue, class Clean, class Redo>
 static inline int nominate_run(b7_ctx *c, const char *who, int rc, int64_t offset, double divisor, Enqueue enqueue, Clean clean,
                         Redo redo, double *best_val, int64_t *best_idx1) {
   const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
-  PendingScore pend;
+  ScoreParams pend;
   if (!(c->comm && c->comm_world > 1)) {
     // the arg-max and the copy of its record are enqueued before the host has seen any report: one synchronisation
     B7_TRY(rc);
@@ -526,7 +523,7 @@ static inline int nominate_run(b7_ctx *c, const char *who, int rc, int64_t offse
     rc = enqueue(&pend);
     if (rc == B7_OK) rc = hipStreamSynchronize(c->stream) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "%s: stream failed", who);
     if (rc == B7_OK && !clean()) {
-      pend = PendingScore();
+      pend = ScoreParams();
       rc = redo();
     }
   }

@@ -218,7 +218,7 @@ static int blr_marg_slow(b7_ctx *c, const b7_mlp *net, const double *X0, const d
 }
 
 static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *ap,
-                         const double *bt, const double *mn, int z, const b7_score_spec *spec, bool want_terms, PendingScore *pend) {
+                         const double *bt, const double *mn, int z, const b7_score_spec *spec, bool want_terms, ScoreParams *pend) {
   const int d = net->dims[0];
   const size_t up_doubles = (size_t)N * d + (size_t)N + 5 * (size_t)S;   // [X0 | y | S alpha | S beta | S mean | S zeros | S 1/beta]
   B7_TRY(b7_ensure(c, c->tmpmu, sizeof(double) * (up_doubles + (size_t)N * z)));
@@ -259,7 +259,7 @@ static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const d
                            (double *)c->bvar.p, c->M, hdev + 3 * (size_t)S, hdev + 4 * (size_t)S));
   double *fd = nullptr;
   if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
-  acc_declare_zeros(c, spec->kind == B7_SCORE_LOGEI);
+  acc_declare_zeros(c, spec->kind);
   *pend = pending_score(c, S, spec, fd);
   return B7_OK;
 }
@@ -385,7 +385,7 @@ int b7_blr_eval_nominate(b7_ctx *c, const b7_mlp *net, const double *X0, const d
     rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: network input width %d != grid dims %d", net->dims[0], c->d);
   return nominate_run(
       c, "blr_eval_nominate", rc, global_row_offset, 1.0,
-      [&](PendingScore *) {
+      [&](ScoreParams *) {
         B7_TRY(blr_enqueue_fit(c, net, X0, Y0, N, z, alpha_prec, beta, mean));
         return blr_enqueue_score(c, net, z, spec);
       },
@@ -417,7 +417,7 @@ int b7_blr_eval_nominate_marg(b7_ctx *c, const b7_mlp *net, const double *X0, co
   const bool fast = rc == B7_OK && z <= 64 && c->blr_small && c->npad_small;
   return nominate_run(
       c, "blr_eval_nominate_marg", rc, global_row_offset, (double)S,
-      [&](PendingScore *pend) {
+      [&](ScoreParams *pend) {
         return fast ? blr_marg_fast(c, net, X0, Y0, N, S, ap, bt, mn, z, spec, nll_out != nullptr, pend)
                     : blr_marg_slow(c, net, X0, Y0, N, S, ap, bt, mn, z, spec, nll_out);
       },

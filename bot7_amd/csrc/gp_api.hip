@@ -287,7 +287,7 @@ int b7_gp_set_kernel(b7_ctx *c, int kernel) {
     return b7_fail(c, B7_ERR_INVALID, "gp_set_kernel: unknown kernel %d", kernel);
   if (kernel == c->kernel) return B7_OK;
   // what a fit under the old kernel left behind goes; the resident data and grid stay (no nomination leaves a score pending
-  // in the context: PendingScore belongs to the call that made it)
+  // in the context: ScoreParams belongs to the call that made it)
   c->kernel = kernel;
   c->fitted = false;
   c->predicted = false;

@@ -380,7 +380,7 @@ int b7_group_eval_nominate(b7_group *g, int S, const b7_hyp *hyps, const b7_scor
   // everything a member has to do, enqueued on its stream; the host moves on to the next member without waiting
   for (int i = 0; i < n; ++i) {
     b7_ctx *c = g->ctx[i];
-    PendingScore pend;  // this member's batched score, run by its exchange step
+    ScoreParams pend;  // this member's batched score, run by its exchange step
     if (c->M > 0) G_TRY(g, i, eval_enqueue(c, S, hyps, spec, &pend));
     if (hipSetDevice(c->device) != hipSuccess) return gfail(g, B7_ERR_HIP, "hipSetDevice(%d) failed", c->device);
     G_TRY(g, i, exch_local(c, (double)S, offset_of(g, i), i, n, g->use_rccl, false, &pend));

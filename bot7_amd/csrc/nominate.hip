@@ -33,15 +33,17 @@ int stage_fmin(b7_ctx *c, const double *fmin, double **fd_out) {
   return B7_OK;
 }
 
+ScoreParams score_params(const b7_ctx *c, const b7_score_spec *spec, const double *fd) {
+  ScoreParams p;
+  p.kind = spec->kind, p.upper = spec->upper;
+  p.fmin = fd, p.fmin0 = c->fmin_scalar;
+  p.tradeoff = spec->tradeoff, p.sign = spec->sign;
+  return p;
+}
+
 int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumulate) {
-  if (sp->kind == B7_SCORE_EI)
-    return launch_ei(c, (const double *)c->mu.p, (const double *)c->var.p, fd, sp->tradeoff, c->M, c->ycols,
-                     (double *)c->acc.p, accumulate);
-  if (sp->kind == B7_SCORE_LOGEI)
-    return launch_logei(c, (const double *)c->mu.p, (const double *)c->var.p, fd, sp->tradeoff, c->M, c->ycols,
-                        (double *)c->acc.p, accumulate);
-  return launch_cb(c, (const double *)c->mu.p, (const double *)c->var.p, sp->tradeoff, sp->upper, sp->sign, c->M,
-                   c->ycols, (double *)c->acc.p, accumulate);
+  return launch_score(c, score_params(c, sp, fd), (const double *)c->mu.p, (const double *)c->var.p, c->M, c->ycols,
+                      (double *)c->acc.p, accumulate);
 }
 
 // The score spec and the global row offset of an eval + nominate entry point (`who` in the messages).  Only a shard of a
@@ -68,15 +70,16 @@ int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spe
 
 // score:add x S of the batch in c->bmu / c->bvar, owed to the exchange step (exch_local), which runs it fused with score:div,
 // the arg-max and the record
-PendingScore pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd) {
-  return PendingScore{true, spec->kind, S, spec->upper, (const double *)c->bmu.p, (const double *)c->bvar.p, fd, c->M,
-                      spec->tradeoff, spec->sign};
+ScoreParams pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd) {
+  ScoreParams p = score_params(c, spec, fd);
+  p.S = S, p.mu = (const double *)c->bmu.p, p.var = (const double *)c->bvar.p, p.stride = c->M;
+  return p;
 }
 
 // bots/bayesopt.lua:69-78 as stream work: zero the accumulator, then fit + posterior + score:add per hyper sample, each
 // fit's pivot report copied to its pinned slot in stream order.  Returns without waiting for any of it; the small regime's
 // score:add is left to the caller's exchange step in *pend.
-int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, PendingScore *pend) {
+int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend) {
   const int d = c->dfit;
   B7_HIP(c, hipSetDevice(c->device));
   B7_TRY(b7_ensure(c, c->mu, sizeof(double) * (size_t)c->M * c->ycols));
@@ -127,7 +130,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
   double *fd = nullptr;
   if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
 
-  acc_declare_zeros(c, spec->kind == B7_SCORE_LOGEI);
+  acc_declare_zeros(c, spec->kind);
   if (batch) {
     const HypPack hd = hyp_pack(c->bhyp.p, S, d);
     const double *hyp_dev = hd.ls, *amp_dev = hd.amp, *noise_dev = hd.noise, *mean_dev = hd.mean;
@@ -182,15 +185,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
                               (const double *)c->balpha.p, (double *)c->ks.p, (int64_t)Mpad * n, (double *)c->bmu.p, c->M));
       B7_TRY(launch_post_batch(c, S, (const double *)c->bLinv.p, (const double *)c->ks.p, (int64_t)Mpad * n, Mpad, c->M,
                                (double *)c->bvar.p, c->M, amp_dev, noise_dev));
-      if (spec->kind == B7_SCORE_EI)
-        B7_TRY(launch_ei_batch(c, S, (const double *)c->bmu.p, (const double *)c->bvar.p, c->M, fd, spec->tradeoff, c->M,
-                               (double *)c->acc.p));
-      else if (spec->kind == B7_SCORE_LOGEI)
-        B7_TRY(launch_logei_batch(c, S, (const double *)c->bmu.p, (const double *)c->bvar.p, c->M, fd, spec->tradeoff, c->M,
-                                  (double *)c->acc.p));
-      else
-        B7_TRY(launch_cb_batch(c, S, (const double *)c->bmu.p, (const double *)c->bvar.p, c->M, spec->tradeoff, spec->upper,
-                               spec->sign, c->M, (double *)c->acc.p));
+      B7_TRY(launch_score_batch(c, pending_score(c, S, spec, fd), (double *)c->acc.p, c->M));
       c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
       c->predicted = false;
     } else {
@@ -279,6 +274,24 @@ static int upload_mv(b7_ctx *c, const double *mean, const double *var, int64_t M
   return B7_OK;
 }
 
+// EI.compute / conf_bound.compute on the caller's host vectors (arguments checked by the entry point): upload, the cc values of
+// spec.fmin (if the score takes one) to the device, the score, download, wait
+static int score_compute(b7_ctx *c, const b7_score_spec &spec, const double *mean, const double *var, int64_t M, int cc, double *out) {
+  if (M == 0) return B7_OK;
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(upload_mv(c, mean, var, M, cc));
+  double *fd = nullptr;
+  if (score_needs_fmin(spec.kind)) {
+    fd = b7_scratch(c)->fmin;
+    B7_HIP(c, hipMemcpyAsync(fd, spec.fmin, sizeof(double) * cc, hipMemcpyHostToDevice, c->stream));
+  }
+  B7_TRY(launch_score(c, score_params(c, &spec, fd), (const double *)c->tmpmu.p, (const double *)c->tmpvar.p, M, cc,
+                      (double *)c->tmpgrid.p, false));
+  B7_HIP(c, hipMemcpyAsync(out, c->tmpgrid.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  return B7_OK;
+}
+
 extern "C" {
 
 int b7_eval_nominate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset,
@@ -289,7 +302,7 @@ int b7_eval_nominate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *
   if (info_out && S > 0) std::fill(info_out, info_out + S, 0);
   return nominate_run(
       c, "eval_nominate", eval_validate(c, S, hyps, spec, global_row_offset), global_row_offset, (double)S,
-      [&](PendingScore *pend) { return eval_enqueue(c, S, hyps, spec, pend); },
+      [&](ScoreParams *pend) { return eval_enqueue(c, S, hyps, spec, pend); },
       [&]() { return reports_clean(c, static_cast<const int *>(c->pin_eval.host), S, true); },
       [&]() { return eval_redo(c, S, hyps, spec, jitter_out, info_out); }, best_val, best_idx1);
 }
@@ -303,39 +316,32 @@ int b7_score_reset(b7_ctx *c) {
   return acc_write_zeros(c);  // torch.zeros(X_hid:size(1)), bots/bayesopt.lua:69
 }
 
-int b7_score_ei(b7_ctx *c, const double *fmin, double tradeoff) {
+// one score of the last predict added onto the accumulator; who: the entry point in the messages
+static int score_entry(b7_ctx *c, const char *who, const b7_score_spec &spec) {
   if (!c) return B7_ERR_INVALID;
-  if (!fmin) return b7_fail(c, B7_ERR_INVALID, "score_ei: fmin is NULL");
-  B7_TRY(score_ready(c, "score_ei"));
+  if (score_needs_fmin(spec.kind) && !spec.fmin) return b7_fail(c, B7_ERR_INVALID, "%s: fmin is NULL", who);
+  B7_TRY(score_ready(c, who));
   B7_HIP(c, hipSetDevice(c->device));
   // fmin goes pageable -> pinned staging (PinnedBlock::fmin) -> device: the caller's array need not
   // outlive this call and the copy is a true asynchronous one.  The staging slot may still be the source of an
   // earlier copy in flight, hence the wait when the values change (once per nomination: fmin is the same for every
   // hyper sample of a marginalisation loop).
   double *fd = nullptr;
-  B7_TRY(stage_fmin(c, fmin, &fd));
-  return launch_ei(c, (const double *)c->mu.p, (const double *)c->var.p, fd, tradeoff, c->M, c->ycols,
-                   (double *)c->acc.p, true);
+  if (score_needs_fmin(spec.kind)) B7_TRY(stage_fmin(c, spec.fmin, &fd));
+  return score_add(c, &spec, fd);
+}
+
+int b7_score_ei(b7_ctx *c, const double *fmin, double tradeoff) {
+  return score_entry(c, "score_ei", b7_score_spec{B7_SCORE_EI, tradeoff, 0, 0.0, fmin});
 }
 
 // log-space EI of the last predict, folded into the accumulator as a running log-sum-exp (score.hip's header)
 int b7_score_logei(b7_ctx *c, const double *fmin, double tradeoff) {
-  if (!c) return B7_ERR_INVALID;
-  if (!fmin) return b7_fail(c, B7_ERR_INVALID, "score_logei: fmin is NULL");
-  B7_TRY(score_ready(c, "score_logei"));
-  B7_HIP(c, hipSetDevice(c->device));
-  double *fd = nullptr;
-  B7_TRY(stage_fmin(c, fmin, &fd));
-  return launch_logei(c, (const double *)c->mu.p, (const double *)c->var.p, fd, tradeoff, c->M, c->ycols,
-                      (double *)c->acc.p, true);
+  return score_entry(c, "score_logei", b7_score_spec{B7_SCORE_LOGEI, tradeoff, 0, 0.0, fmin});
 }
 
 int b7_score_cb(b7_ctx *c, double tradeoff, int upper, double sign) {
-  if (!c) return B7_ERR_INVALID;
-  B7_TRY(score_ready(c, "score_cb"));
-  B7_HIP(c, hipSetDevice(c->device));
-  return launch_cb(c, (const double *)c->mu.p, (const double *)c->var.p, tradeoff, upper, sign, c->M, c->ycols,
-                   (double *)c->acc.p, true);
+  return score_entry(c, "score_cb", b7_score_spec{B7_SCORE_CB, tradeoff, upper, sign, nullptr});
 }
 
 int b7_score_finish(b7_ctx *c, double divisor, double *best_val, int64_t *best_idx1, double *scores_host) {
@@ -356,16 +362,7 @@ int b7_ei_compute(b7_ctx *c, const double *mean, const double *var, const double
   if (!c) return B7_ERR_INVALID;
   if (M < 0 || cc < 1 || cc > 256 || (M > 0 && (!mean || !var || !fmin || !out)))
     return b7_fail(c, B7_ERR_INVALID, "ei_compute: bad arguments");
-  if (M == 0) return B7_OK;
-  B7_HIP(c, hipSetDevice(c->device));
-  B7_TRY(upload_mv(c, mean, var, M, cc));
-  double *fd = b7_scratch(c)->fmin;
-  B7_HIP(c, hipMemcpyAsync(fd, fmin, sizeof(double) * cc, hipMemcpyHostToDevice, c->stream));
-  B7_TRY(launch_ei(c, (const double *)c->tmpmu.p, (const double *)c->tmpvar.p, fd, tradeoff, M, cc,
-                   (double *)c->tmpgrid.p, false));
-  B7_HIP(c, hipMemcpyAsync(out, c->tmpgrid.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
-  B7_HIP(c, hipStreamSynchronize(c->stream));
-  return B7_OK;
+  return score_compute(c, b7_score_spec{B7_SCORE_EI, tradeoff, 0, 0.0, fmin}, mean, var, M, cc, out);
 }
 
 int b7_logei_compute(b7_ctx *c, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M,
@@ -373,30 +370,14 @@ int b7_logei_compute(b7_ctx *c, const double *mean, const double *var, const dou
   if (!c) return B7_ERR_INVALID;
   if (M < 0 || cc < 1 || cc > 256 || (M > 0 && (!mean || !var || !fmin || !out)))
     return b7_fail(c, B7_ERR_INVALID, "logei_compute: bad arguments");
-  if (M == 0) return B7_OK;
-  B7_HIP(c, hipSetDevice(c->device));
-  B7_TRY(upload_mv(c, mean, var, M, cc));
-  double *fd = b7_scratch(c)->fmin;
-  B7_HIP(c, hipMemcpyAsync(fd, fmin, sizeof(double) * cc, hipMemcpyHostToDevice, c->stream));
-  B7_TRY(launch_logei(c, (const double *)c->tmpmu.p, (const double *)c->tmpvar.p, fd, tradeoff, M, cc,
-                      (double *)c->tmpgrid.p, false));
-  B7_HIP(c, hipMemcpyAsync(out, c->tmpgrid.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
-  B7_HIP(c, hipStreamSynchronize(c->stream));
-  return B7_OK;
+  return score_compute(c, b7_score_spec{B7_SCORE_LOGEI, tradeoff, 0, 0.0, fmin}, mean, var, M, cc, out);
 }
 
 int b7_cb_compute(b7_ctx *c, const double *mean, const double *var, double tradeoff, int upper, double sign, int64_t M,
                   int cc, double *out) {
   if (!c) return B7_ERR_INVALID;
   if (M < 0 || cc < 1 || (M > 0 && (!mean || !var || !out))) return b7_fail(c, B7_ERR_INVALID, "cb_compute: bad arguments");
-  if (M == 0) return B7_OK;
-  B7_HIP(c, hipSetDevice(c->device));
-  B7_TRY(upload_mv(c, mean, var, M, cc));
-  B7_TRY(launch_cb(c, (const double *)c->tmpmu.p, (const double *)c->tmpvar.p, tradeoff, upper, sign, M, cc,
-                   (double *)c->tmpgrid.p, false));
-  B7_HIP(c, hipMemcpyAsync(out, c->tmpgrid.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
-  B7_HIP(c, hipStreamSynchronize(c->stream));
-  return B7_OK;
+  return score_compute(c, b7_score_spec{B7_SCORE_CB, tradeoff, upper, sign, nullptr}, mean, var, M, cc, out);
 }
 
 int b7_argmax(b7_ctx *c, const double *scores, int64_t M, double *best_val, int64_t *best_idx1) {

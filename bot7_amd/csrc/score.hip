@@ -31,9 +31,14 @@
 // Marginalisation is log((1/S) sum_s EI_s), not the mean of the logs: the accumulator of LogEI is a running log-sum-exp, empty at
 // -inf, folded by a <- logaddexp(a, v) = max + log1p(exp(min - max)) in sample order (NaN if either is NaN, -inf / +inf when both are);
 // c > 1 response columns are the same fold over the columns of a row, then - log(c); score:div becomes a - log(divisor), the
-// log taken here.  b7_logei_fold is that one operation order for the per-sample kernel, the S-batch kernel and the fused
-// nomination kernel, which is what makes the one-call nomination equal the per-sample loop bit for bit.
+// log taken here.
+//
+// Every score kind is written ONCE, as the per-kind pieces below (hoist / value / row_sign over the accumulator algebra empty / fold /
+// div); the per-sample kernel, the S-batch kernel and the fused nomination kernel are templates over the kind that only arrange
+// those pieces, which is what makes the one-call nomination equal the per-sample loop bit for bit.
 #pragma clang fp contract(off)
+#include <type_traits>
+
 #include "b7_internal.h"
 
 namespace {
@@ -64,7 +69,7 @@ __device__ __forceinline__ double b7_norm_pdf(double z) {
   return exp((z * z) * -0.5) * 0.3989422804014327;  // 1/math.sqrt(2*math.pi), utils/math.lua:15
 }
 
-// ---- log-space EI (see the header): shared by logei_kernel, logei_batch_kernel and score_finish_slot_logei_kernel ----
+// ---- log-space EI (see the header) ----
 __device__ __forceinline__ double b7_logei(double mu, double var, double fmin, double xi) {
   const double sigma = sqrt(var);
   const double imprv = (fmin + (-mu)) + (-xi);
@@ -95,112 +100,89 @@ __device__ __forceinline__ double b7_logaddexp(double a, double v) {
   if (m == -INFINITY || n == INFINITY) return m;  // both -inf, both +inf: n - m would be NaN
   return m + log1p(exp(n + (-m)));
 }
-// a <- logaddexp(a, logEI): THE operation order of every LogEI path
-__device__ __forceinline__ double b7_logei_fold(double a, double mu, double var, double fmin, double xi) {
-  return b7_logaddexp(a, b7_logei(mu, var, fmin, xi));
+// ---- a score kind K (B7_SCORE_*), once.  The accumulator algebra follows score_acc_kind(K): a linear sum or a log-sum-exp ----
+template <int K>
+__device__ __forceinline__ double empty() {  // torch.zeros (bots/bayesopt.lua:69); log: the empty log-sum-exp
+  if constexpr (score_acc_kind(K) == B7_ACC_LOG) return -INFINITY;
+  else return 0.0;
 }
-
-__global__ void __launch_bounds__(256)
-    ei_kernel(const double *__restrict__ mu, const double *__restrict__ var, const double *__restrict__ fmin,
-              double xi, int64_t M, int c, double *__restrict__ out, int accumulate, double fmin0) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    double sigma = sqrt(var[j]);
-    double acc = 0.0;
-    for (int k = 0; k < c; ++k) {
-      double imprv = ((fmin ? fmin[k] : fmin0) + (-mu[j * c + k])) + (-xi);  // fmin == nullptr: one column, its f_min a kernel argument
-      double z = imprv / sigma;
-      double ei = (imprv * b7_norm_cdf(z)) + (sigma * b7_norm_pdf(z));
-      ei = (ei < 0.0) ? 0.0 : ei;
-      acc = (c == 1) ? ei : acc + ei;
-    }
-    double v = (c == 1) ? acc : acc / (double)c;
-    out[j] = accumulate == 1 ? out[j] + v : (accumulate == 2 ? 0.0 + v : v);  // 2: the first score:add onto torch.zeros
+template <int K>
+__device__ __forceinline__ double fold(double a, double v) {  // score:add, and the sum over the columns of a row
+  if constexpr (score_acc_kind(K) == B7_ACC_LOG) return b7_logaddexp(a, v);
+  else return a + v;
+}
+template <int K>
+__device__ __forceinline__ double div(double a, double divisor) {  // score:div, and the row mean
+  if constexpr (score_acc_kind(K) == B7_ACC_LOG) return a + (-log(divisor));
+  else return a / divisor;
+}
+// what a candidate's variance contributes to every response column: sigma (EI), sqrt(var) * kappa (CB), the variance itself (LogEI)
+template <int K>
+__device__ __forceinline__ double hoist(double var, const ScoreParams &p) {
+  if constexpr (K == B7_SCORE_EI) return sqrt(var);
+  else if constexpr (K == B7_SCORE_CB) return sqrt(var) * p.tradeoff;
+  else return var;
+}
+// one candidate, one response column; h = hoist<K>(var)
+template <int K>
+__device__ __forceinline__ double value(double mu, double h, double fmin, const ScoreParams &p) {
+  if constexpr (K == B7_SCORE_EI) {
+    double imprv = (fmin + (-mu)) + (-p.tradeoff);
+    double z = imprv / h;
+    double ei = (imprv * b7_norm_cdf(z)) + (h * b7_norm_pdf(z));
+    return (ei < 0.0) ? 0.0 : ei;
+  } else if constexpr (K == B7_SCORE_CB) {
+    return p.upper ? (mu + h) : (mu + (-h));
+  } else {
+    return b7_logei(mu, h, fmin, p.tradeoff);
   }
 }
-
-__global__ void __launch_bounds__(256)
-    cb_kernel(const double *__restrict__ mu, const double *__restrict__ var, double kappa, int upper, double sign,
-              int64_t M, int c, double *__restrict__ out, int accumulate) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    double s = sqrt(var[j]) * kappa;
-    double acc = 0.0;
-    for (int k = 0; k < c; ++k) {
-      double v = upper ? (mu[j * c + k] + s) : (mu[j * c + k] + (-s));
-      acc = (c == 1) ? v : acc + v;
-    }
-    double val = (c == 1) ? acc : acc / (double)c;
-    val = (sign > 0.0) ? val : -val;
-    out[j] = accumulate == 1 ? out[j] + val : (accumulate == 2 ? 0.0 + val : val);
-  }
+// the sign flip of the confidence bound (scores/confidence_bound.lua:89-93), applied to a row's score: after the row mean
+template <int K>
+__device__ __forceinline__ double row_sign(double v, const ScoreParams &p) {
+  if constexpr (K == B7_SCORE_CB) return (p.sign > 0.0) ? v : -v;
+  else return v;
+}
+__device__ __forceinline__ double fmin_of(const ScoreParams &p, int k) {  // fmin == nullptr: one column, its f_min a kernel argument
+  return p.fmin ? p.fmin[k] : p.fmin0;
 }
 
-// S hyper samples at once (one response column): acc[j] = ((acc[j] + score_0) + score_1) + ... in sample order, exactly
-// what S score:add calls leave (bots/bayesopt.lua:76)
-__global__ void __launch_bounds__(256)
-    ei_batch_kernel(const double *__restrict__ mu, const double *__restrict__ var, int S, int64_t sstride,
-                    const double *__restrict__ fmin, double xi, int64_t M, double *__restrict__ out, int fresh, double fmin0) {
+// The score of ONE hyper sample (p.S == 1) over c response columns, the row mean if c > 1.  accumulate 0 writes it, 1 folds it
+// onto out, 2 folds it onto an empty accumulator that is not read: the first score:add onto torch.zeros (0.0 + v, not v)
+template <int K>
+__global__ void __launch_bounds__(256) score_kernel(ScoreParams p, int64_t M, int c, double *__restrict__ out, int accumulate) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    double a = fresh ? 0.0 : out[j];  // fresh: the accumulator is torch.zeros (bots/bayesopt.lua:69), not read
-    for (int s = 0; s < S; ++s) {
-      double sigma = sqrt(var[s * sstride + j]);
-      double imprv = ((fmin ? fmin[0] : fmin0) + (-mu[s * sstride + j])) + (-xi);
-      double z = imprv / sigma;
-      double ei = (imprv * b7_norm_cdf(z)) + (sigma * b7_norm_pdf(z));
-      ei = (ei < 0.0) ? 0.0 : ei;
-      a = a + ei;
-    }
-    out[j] = a;
-  }
-}
-__global__ void __launch_bounds__(256)
-    cb_batch_kernel(const double *__restrict__ mu, const double *__restrict__ var, int S, int64_t sstride, double kappa,
-                    int upper, double sign, int64_t M, double *__restrict__ out, int fresh) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    double a = fresh ? 0.0 : out[j];
-    for (int s = 0; s < S; ++s) {
-      double sd = sqrt(var[s * sstride + j]) * kappa;
-      double v = upper ? (mu[s * sstride + j] + sd) : (mu[s * sstride + j] + (-sd));
-      v = (sign > 0.0) ? v : -v;
-      a = a + v;
-    }
-    out[j] = a;
-  }
-}
-
-// LogEI of one hyper sample: accumulate 0 writes log EI (c > 1: log of the row mean of EI), 1 folds it into out, 2 folds it into
-// an empty (-inf) accumulator that is not read
-__global__ void __launch_bounds__(256)
-    logei_kernel(const double *__restrict__ mu, const double *__restrict__ var, const double *__restrict__ fmin, double xi,
-                 int64_t M, int c, double *__restrict__ out, int accumulate, double fmin0) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    const double vr = var[j];
+    const double h = hoist<K>(p.var[j], p);
+    double row;
     if (c == 1) {
-      const double f = fmin ? fmin[0] : fmin0, m = mu[j];
-      out[j] = accumulate == 1 ? b7_logei_fold(out[j], m, vr, f, xi)
-                               : (accumulate == 2 ? b7_logei_fold(-INFINITY, m, vr, f, xi) : b7_logei(m, vr, f, xi));
-      continue;
+      row = value<K>(p.mu[j], h, fmin_of(p, 0), p);
+    } else {
+      row = empty<K>();
+      for (int k = 0; k < c; ++k) row = fold<K>(row, value<K>(p.mu[j * c + k], h, fmin_of(p, k), p));
+      row = div<K>(row, (double)c);
     }
-    double row = -INFINITY;
-    for (int k = 0; k < c; ++k) row = b7_logei_fold(row, mu[j * c + k], vr, fmin[k], xi);
-    row = row + (-log((double)c));
-    out[j] = accumulate == 1 ? b7_logaddexp(out[j], row) : (accumulate == 2 ? b7_logaddexp(-INFINITY, row) : row);
+    row = row_sign<K>(row, p);
+    out[j] = accumulate == 1 ? fold<K>(out[j], row) : (accumulate == 2 ? fold<K>(empty<K>(), row) : row);
   }
 }
-// S hyper samples at once (one response column): the same folds in sample order
-__global__ void __launch_bounds__(256)
-    logei_batch_kernel(const double *__restrict__ mu, const double *__restrict__ var, int S, int64_t sstride,
-                       const double *__restrict__ fmin, double xi, int64_t M, double *__restrict__ out, int fresh, double fmin0) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    double a = fresh ? -INFINITY : out[j];
-    for (int s = 0; s < S; ++s) a = b7_logei_fold(a, mu[s * sstride + j], var[s * sstride + j], fmin ? fmin[0] : fmin0, xi);
-    out[j] = a;
+
+// S hyper samples of candidate j (one response column) folded onto a in sample order: a = fold(..fold(fold(a, s_0), s_1).., s_S-1),
+// exactly what S score:add calls leave (bots/bayesopt.lua:76)
+template <int K>
+__device__ __forceinline__ double fold_samples(const ScoreParams &p, int64_t j, double a) {
+  for (int s = 0; s < p.S; ++s) {
+    const double m = p.mu[s * p.stride + j], h = hoist<K>(p.var[s * p.stride + j], p);
+    a = fold<K>(a, row_sign<K>(value<K>(m, h, fmin_of(p, 0), p), p));
   }
+  return a;
+}
+// fresh: the accumulator is torch.zeros (bots/bayesopt.lua:69; log: an empty log-sum-exp), not read
+template <int K>
+__global__ void __launch_bounds__(256) score_batch_kernel(ScoreParams p, int64_t M, double *__restrict__ out, int fresh) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride)
+    out[j] = fold_samples<K>(p, j, fresh ? empty<K>() : out[j]);
 }
 
 __global__ void __launch_bounds__(256) fill_kernel(double *__restrict__ p, int64_t n, double v) {
@@ -318,78 +300,8 @@ __global__ void __launch_bounds__(256) argmax_slot_kernel(const Best *__restrict
   write_record(b, tab, rank, world, offset, rows, grid, d, all_slots, host_rec, host_done);
 }
 
-// score:add over the S hyper samples of a nomination, score:div, score:max(1) and this rank's exchange record in ONE launch
-// (bots/bayesopt.lua:76-79, :96): ei_batch_kernel / cb_batch_kernel + finish_kernel + argmax_slot_kernel, the same operations in
-// the same order per candidate -- acc = ((0 + s_0) + s_1) + ..., acc / divisor -- then the per-block best, and the LAST block to
-// arrive (a ticket from one atomic counter; every block's partial is fenced before its ticket) reduces the partials and writes
-// the record.  Three dependent launches at the ~4.5 us dispatch floor each become one.
-struct ScoreArgs {
-  const double *mu, *var;
-  int S, kind;  // kind: B7_SCORE_EI / B7_SCORE_CB / B7_SCORE_LOGEI
-  long long sstride;
-  const double *fmin;
-  double fmin0, tradeoff, sign;
-  int upper, fresh;
-};
-__global__ void __launch_bounds__(256)
-    score_finish_slot_kernel(ScoreArgs sa, double *__restrict__ acc, long long M, double divisor, Best *__restrict__ part,
-                             unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank, int world, long long offset,
-                             const double *__restrict__ grid, int d, int all_slots, unsigned long long *__restrict__ host_rec,
-                             unsigned *__restrict__ host_done) {
-  __shared__ Best sh[4];
-  __shared__ unsigned last;
-  Best b{0.0, -1};
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    double a = sa.fresh ? 0.0 : acc[j];  // fresh: the accumulator is torch.zeros (bots/bayesopt.lua:69), not read
-    for (int s = 0; s < sa.S; ++s) {
-      const double m = sa.mu[s * sa.sstride + j], vr = sa.var[s * sa.sstride + j];
-      double sc;
-      if (sa.kind == B7_SCORE_EI) {
-        double sigma = sqrt(vr);
-        double imprv = ((sa.fmin ? sa.fmin[0] : sa.fmin0) + (-m)) + (-sa.tradeoff);
-        double z = imprv / sigma;
-        sc = (imprv * b7_norm_cdf(z)) + (sigma * b7_norm_pdf(z));
-        sc = (sc < 0.0) ? 0.0 : sc;
-      } else {
-        double sd = sqrt(vr) * sa.tradeoff;
-        sc = sa.upper ? (m + sd) : (m + (-sd));
-        sc = (sa.sign > 0.0) ? sc : -sc;
-      }
-      a = a + sc;
-    }
-    const double v = a / divisor;
-    acc[j] = v;
-    Best cnd{v, j};
-    if (better(cnd, b)) b = cnd;
-  }
-  b = block_best(b, sh);
-  if (threadIdx.x == 0) {
-    part[blockIdx.x] = b;
-    __threadfence();  // the partial is visible device-wide before the ticket is taken
-    const unsigned t = atomicAdd(ticket, 1u);
-    last = (t == gridDim.x - 1) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();  // the other blocks' partials, published before their tickets
-  Best f{0.0, -1};
-  for (int j = threadIdx.x; j < (int)gridDim.x; j += blockDim.x) {
-    Best pj;  // agent-scope loads: the partials of other CUs, not a stale line of this CU's cache
-    pj.v = __hip_atomic_load(&part[j].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    pj.i = __hip_atomic_load(&part[j].i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (better(pj, f)) f = pj;
-  }
-  __syncthreads();
-  f = block_best(f, sh);
-  if (threadIdx.x == 0) *ticket = 0u;  // ready for the next launch (stream order: nobody else touches it meanwhile)
-  write_record(f, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
-}
-
-// The same launch for B7_SCORE_LOGEI, a kernel of its own: ocml's erfcx / log1p / log take three times the registers of the EI / CB
-// arms, and the kernel above keeps the instructions it had before LogEI existed.  acc = logaddexp(..logaddexp(-inf, s_0).., s_S-1),
-// acc - log(divisor); then the same per-block best, ticket and last block's pass, here as a function (the kernel above keeps its own
-// inlined text so that its instructions stay what they were: a change to one of the two belongs in the other).
+// The tail of the fused nomination kernel: per-block best, and the LAST block to arrive (a ticket from one atomic counter; every
+// block's partial is fenced before its ticket) reduces the partials and writes the record.
 // Every thread of the block calls; sh: 4 Best, last: one word, both in LDS.
 __device__ __forceinline__ void block_best_ticket_record(Best b, Best *sh, unsigned *last, Best *__restrict__ part,
                                                          unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank,
@@ -418,20 +330,24 @@ __device__ __forceinline__ void block_best_ticket_record(Best b, Best *sh, unsig
   if (threadIdx.x == 0) *ticket = 0u;  // ready for the next launch (stream order: nobody else touches it meanwhile)
   write_record(f, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
 }
+
+// score:add over the S hyper samples of a nomination, score:div, score:max(1) and this rank's exchange record in ONE launch
+// (bots/bayesopt.lua:76-79, :96): score_batch_kernel + finish_kernel + argmax_slot_kernel, the same operations in the same order
+// per candidate -- fold_samples onto the accumulator, div by the divisor -- then the tail above.  Three dependent launches at the
+// ~4.5 us dispatch floor each become one.  (One kernel per kind: ocml's erfcx / log1p / log give the LogEI instance three times the
+// registers of the EI and CB ones.)
+template <int K>
 __global__ void __launch_bounds__(256)
-    score_finish_slot_logei_kernel(ScoreArgs sa, double *__restrict__ acc, long long M, double divisor, Best *__restrict__ part,
-                                   unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank, int world,
-                                   long long offset, const double *__restrict__ grid, int d, int all_slots,
-                                   unsigned long long *__restrict__ host_rec, unsigned *__restrict__ host_done) {
+    score_finish_slot_kernel(ScoreParams p, int fresh, double *__restrict__ acc, long long M, double divisor, Best *__restrict__ part,
+                             unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank, int world, long long offset,
+                             const double *__restrict__ grid, int d, int all_slots, unsigned long long *__restrict__ host_rec,
+                             unsigned *__restrict__ host_done) {
   __shared__ Best sh[4];
   __shared__ unsigned last;
   Best b{0.0, -1};
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    double a = sa.fresh ? -INFINITY : acc[j];  // fresh: an empty log-sum-exp, not read
-    for (int s = 0; s < sa.S; ++s)
-      a = b7_logei_fold(a, sa.mu[s * sa.sstride + j], sa.var[s * sa.sstride + j], sa.fmin ? sa.fmin[0] : sa.fmin0, sa.tradeoff);
-    const double v = a + (-log(divisor));
+    const double v = div<K>(fold_samples<K>(p, j, fresh ? empty<K>() : acc[j]), divisor);
     acc[j] = v;
     Best cnd{v, j};
     if (better(cnd, b)) b = cnd;
@@ -475,76 +391,41 @@ static int acc_mode_or_fail(b7_ctx *c, const double *out, bool accumulate, int k
   return B7_OK;
 }
 
-int launch_ei(b7_ctx *c, const double *mu, const double *var, const double *fmin_dev, double tradeoff, int64_t M,
-              int ycols, double *out, bool accumulate) {
+// THE step from a run-time score kind to its template instance: f(std::integral_constant<int, B7_SCORE_*>)
+template <class F>
+static void with_score_kind(int kind, F f) {
+  switch (kind) {
+    case B7_SCORE_EI: return f(std::integral_constant<int, B7_SCORE_EI>());
+    case B7_SCORE_LOGEI: return f(std::integral_constant<int, B7_SCORE_LOGEI>());
+    default: return f(std::integral_constant<int, B7_SCORE_CB>());
+  }
+}
+
+// one hyper sample: the score of mu (M x ycols) / var (M), written to out or added onto it
+int launch_score(b7_ctx *c, ScoreParams p, const double *mu, const double *var, int64_t M, int ycols, double *out, bool accumulate) {
   PhaseScope ps(c, "score");
   if (M <= 0) return B7_OK;
-  if (!fmin_dev && ycols != 1) return b7_fail(c, B7_ERR_INVALID, "ei: f_min of %d columns must be staged on the device", ycols);
+  if (score_needs_fmin(p.kind) && !p.fmin && ycols != 1)
+    return b7_fail(c, B7_ERR_INVALID, "%s: f_min of %d columns must be staged on the device", p.kind == B7_SCORE_EI ? "ei" : "logei", ycols);
   int mode;
-  B7_TRY(acc_mode_or_fail(c, out, accumulate, B7_ACC_LINEAR, &mode));
-  hipLaunchKernelGGL(ei_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, fmin_dev, tradeoff, M, ycols,
-                     out, mode, c->fmin_scalar);
+  B7_TRY(acc_mode_or_fail(c, out, accumulate, score_acc_kind(p.kind), &mode));
+  p.mu = mu, p.var = var, p.S = 1, p.stride = 0;
+  with_score_kind(p.kind, [&](auto k) {
+    hipLaunchKernelGGL(score_kernel<decltype(k)::value>, dim3(nblocks(c, M)), dim3(256), 0, c->stream, p, M, ycols, out, mode);
+  });
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
 
-int launch_logei(b7_ctx *c, const double *mu, const double *var, const double *fmin_dev, double tradeoff, int64_t M,
-                 int ycols, double *out, bool accumulate) {
-  PhaseScope ps(c, "score");
-  if (M <= 0) return B7_OK;
-  if (!fmin_dev && ycols != 1) return b7_fail(c, B7_ERR_INVALID, "logei: f_min of %d columns must be staged on the device", ycols);
-  int mode;
-  B7_TRY(acc_mode_or_fail(c, out, accumulate, B7_ACC_LOG, &mode));
-  hipLaunchKernelGGL(logei_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, fmin_dev, tradeoff, M, ycols,
-                     out, mode, c->fmin_scalar);
-  B7_HIP(c, hipGetLastError());
-  return B7_OK;
-}
-
-int launch_cb(b7_ctx *c, const double *mu, const double *var, double tradeoff, int upper, double sign, int64_t M,
-              int ycols, double *out, bool accumulate) {
+// the S hyper samples of p (one response column) added onto acc in sample order
+int launch_score_batch(b7_ctx *c, const ScoreParams &p, double *acc, int64_t M) {
   PhaseScope ps(c, "score");
   if (M <= 0) return B7_OK;
   int mode;
-  B7_TRY(acc_mode_or_fail(c, out, accumulate, B7_ACC_LINEAR, &mode));
-  hipLaunchKernelGGL(cb_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, tradeoff, upper, sign, M,
-                     ycols, out, mode);
-  B7_HIP(c, hipGetLastError());
-  return B7_OK;
-}
-
-int launch_ei_batch(b7_ctx *c, int S, const double *mu, const double *var, int64_t stride, const double *fmin_dev,
-                    double tradeoff, int64_t M, double *acc) {
-  PhaseScope ps(c, "score");
-  if (M <= 0) return B7_OK;
-  int mode;
-  B7_TRY(acc_mode_or_fail(c, acc, true, B7_ACC_LINEAR, &mode));
-  hipLaunchKernelGGL(ei_batch_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, S, stride, fmin_dev, tradeoff, M,
-                     acc, mode == 2 ? 1 : 0, c->fmin_scalar);
-  B7_HIP(c, hipGetLastError());
-  return B7_OK;
-}
-
-int launch_logei_batch(b7_ctx *c, int S, const double *mu, const double *var, int64_t stride, const double *fmin_dev,
-                       double tradeoff, int64_t M, double *acc) {
-  PhaseScope ps(c, "score");
-  if (M <= 0) return B7_OK;
-  int mode;
-  B7_TRY(acc_mode_or_fail(c, acc, true, B7_ACC_LOG, &mode));
-  hipLaunchKernelGGL(logei_batch_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, S, stride, fmin_dev, tradeoff, M,
-                     acc, mode == 2 ? 1 : 0, c->fmin_scalar);
-  B7_HIP(c, hipGetLastError());
-  return B7_OK;
-}
-
-int launch_cb_batch(b7_ctx *c, int S, const double *mu, const double *var, int64_t stride, double tradeoff, int upper,
-                    double sign, int64_t M, double *acc) {
-  PhaseScope ps(c, "score");
-  if (M <= 0) return B7_OK;
-  int mode;
-  B7_TRY(acc_mode_or_fail(c, acc, true, B7_ACC_LINEAR, &mode));
-  hipLaunchKernelGGL(cb_batch_kernel, dim3(nblocks(c, M)), dim3(256), 0, c->stream, mu, var, S, stride, tradeoff, upper, sign,
-                     M, acc, mode == 2 ? 1 : 0);
+  B7_TRY(acc_mode_or_fail(c, acc, true, score_acc_kind(p.kind), &mode));
+  with_score_kind(p.kind, [&](auto k) {
+    hipLaunchKernelGGL(score_batch_kernel<decltype(k)::value>, dim3(nblocks(c, M)), dim3(256), 0, c->stream, p, M, acc, mode == 2 ? 1 : 0);
+  });
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
@@ -558,11 +439,11 @@ int launch_fill(b7_ctx *c, double *p, int64_t n, double v) {
 
 // ---- the accumulator's state: set here and nowhere else ----
 // torch.zeros(X_hid:size(1)), bots/bayesopt.lua:69, declared without a launch: the first score launch onto it starts from 0.0
-// (log: the nomination will fold LogEI into it -- an empty log-sum-exp, -inf, declared the same way)
-void acc_declare_zeros(b7_ctx *c, bool log) {
+// (score_kind: what the nomination will add.  LogEI: an empty log-sum-exp, -inf, declared the same way)
+void acc_declare_zeros(b7_ctx *c, int score_kind) {
   c->acc_valid = true;
   c->acc_fresh = true;
-  c->acc_kind = log ? B7_ACC_LOG : B7_ACC_NONE;
+  c->acc_kind = score_acc_kind(score_kind) == B7_ACC_LOG ? B7_ACC_LOG : B7_ACC_NONE;  // a linear one: the first add decides
 }
 
 // the same zeros written now (the caller has sized c->acc for c->M)
@@ -629,7 +510,7 @@ int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64
 }
 
 // The fused form: the S-sample score, score:div, the local arg-max and the record in one launch.
-int launch_score_finish_slot(b7_ctx *c, const PendingScore &ps, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
+int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
                              int rank, int world, int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec,
                              unsigned *host_done) {
   PhaseScope scope(c, "score");
@@ -647,17 +528,12 @@ int launch_score_finish_slot(b7_ctx *c, const PendingScore &ps, double *acc, int
   }
   unsigned *ticket = (unsigned *)c->ticket.p;
   int mode;
-  B7_TRY(acc_mode_or_fail(c, acc, true, ps.kind == B7_SCORE_LOGEI ? B7_ACC_LOG : B7_ACC_LINEAR, &mode));
-  ScoreArgs sa{ps.mu, ps.var, ps.S, ps.kind, (long long)ps.stride, ps.fd, c->fmin_scalar, ps.tradeoff, ps.sign, ps.upper,
-               mode == 2 ? 1 : 0};
-  if (ps.kind == B7_SCORE_LOGEI)
-    hipLaunchKernelGGL(score_finish_slot_logei_kernel, dim3(nb), dim3(threads), 0, c->stream, sa, acc, (long long)M, divisor, part,
-                       ticket, (unsigned long long *)tab_dev, rank, world, (long long)offset, grid, d, all_slots ? 1 : 0,
-                       (unsigned long long *)host_rec, host_done);
-  else
-    hipLaunchKernelGGL(score_finish_slot_kernel, dim3(nb), dim3(threads), 0, c->stream, sa, acc, (long long)M, divisor, part, ticket,
-                       (unsigned long long *)tab_dev, rank, world, (long long)offset, grid, d, all_slots ? 1 : 0,
-                       (unsigned long long *)host_rec, host_done);
+  B7_TRY(acc_mode_or_fail(c, acc, true, score_acc_kind(p.kind), &mode));
+  with_score_kind(p.kind, [&](auto k) {
+    hipLaunchKernelGGL(score_finish_slot_kernel<decltype(k)::value>, dim3(nb), dim3(threads), 0, c->stream, p, mode == 2 ? 1 : 0, acc,
+                       (long long)M, divisor, part, ticket, (unsigned long long *)tab_dev, rank, world, (long long)offset, grid, d,
+                       all_slots ? 1 : 0, (unsigned long long *)host_rec, host_done);
+  });
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }

@@ -173,7 +173,7 @@ def _objective(X):
 @pytest.mark.parametrize("N,d,M,S", [(24, 3, 2048, 1), (24, 3, 2048, 3), (150, 5, 2048, 3)])
 def test_eval_nominate_is_the_per_sample_loop_bit_for_bit(ctx, orc, N, d, M, S):
     """b7_eval_nominate(B7_SCORE_LOGEI) against the separate calls: equal winner, equal best_val bits, equal accumulator bits (the
-    first two shapes: small-problem kernels + the fused LogEI kernel; the third: general schedule + logei_batch_kernel; the phase
+    first two shapes: small-problem kernels + the fused kernel's LogEI instance; the third: general schedule + score_batch_kernel; the phase
     counters say which ran), and the
     scores equal logsumexp_s(logEI_s) - log S in 50 digits from the downloaded mean / variance, within the bar."""
     X_obs, Y, X_hid, hyp = make_problem(ctx, orc, d, N, M, _objective)
@@ -189,7 +189,7 @@ def test_eval_nominate_is_the_per_sample_loop_bit_for_bit(ctx, orc, N, d, M, S):
     finally:
         ctx.profile_enable(False)
     # which kernels ran: the fused launch is one "score" phase and no "argmax" phase (score, division, arg-max and record in
-    # score_finish_slot_logei_kernel); the batch route is one "score" phase (logei_batch_kernel, all S samples) and one "argmax"
+    # score_finish_slot_kernel<B7_SCORE_LOGEI>); the batch route is one "score" phase (score_batch_kernel, all S samples) and one "argmax"
     # phase (finish_kernel); the per-sample fall-back would show S "score" phases
     assert (n_score, n_argmax) == ((1, 0) if N <= 128 else (1, 1)), (n_score, n_argmax)
     _, _, sc1 = ctx.score_finish(1.0, download=True)      # a log accumulator: a - log(1) = a

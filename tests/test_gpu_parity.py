@@ -2216,7 +2216,7 @@ def _diag_context(monkeypatch, **env):
 def test_small_problem_kernels_equal_the_general_schedule_bit_for_bit(ctx, orc, monkeypatch, N, d):
     """gp_small_kernel (the whole fit, or the likelihood, of a hyper vector in one eight-wave workgroup), kpost_small_kernel
     (K(X*,X) + mean + variance, K* never stored) and score_finish_slot_kernel (score:add x S + div + arg-max + record) against the
-    general schedule -- observation scaling, ksx_kernel, persistent Cholesky, trmv launches, post_kernel, ei_batch / finish /
+    general schedule -- observation scaling, ksx_kernel, persistent Cholesky, trmv launches, post_kernel, score_batch / finish /
     argmax_slot -- selected in the diagnostic build by B7_FIT_SMALL=0 B7_KPOST_SMALL=0 B7_NLL_SMALL=2 (round 3's four-wave
     likelihood kernel): L, L^-1, alpha, the likelihoods, posterior mean and variance, the marginalised scores and the nominations
     must agree BIT FOR BIT, across one / two 64-blocks, partly and wholly padded 16-strips, every width class."""
@@ -2386,3 +2386,62 @@ def test_dngo_head_marginalised_over_hyper_samples(ctx, orc, S):
             if S == 1:
                 v1, i1 = ctx.blr_eval_nominate(W, b, "Tanh", X_obs, Y, al[0], be[0], mn[0], score=kind, fmin=[float(Y.min())])
                 assert (i1, v1) == (i, pytest.approx(v, rel=1e-12))
+
+
+# ---- every score kind, every route: one definition of the arithmetic, three arrangements of it -----------------------------------
+_SCORE_KINDS = {"ei": dict(score="ei"), "cb-lower": dict(score="cb", upper=False, sign=1.0),
+                "cb-upper-negated": dict(score="cb", upper=True, sign=-1.0), "logei": dict(score="logei")}
+
+
+@pytest.mark.parametrize("N,d", [(24, 3), (150, 5)])
+@pytest.mark.parametrize("kind", list(_SCORE_KINDS))
+def test_score_routes_leave_the_same_bits(ctx, orc, monkeypatch, kind, N, d):
+    """score_kernel (once per hyper sample), score_batch_kernel (all S at once) and score_finish_slot_kernel (the fused launch) are
+    instances over the score kind of the same per-kind pieces (score.hip).  M = 300 candidates (two blocks, the second ragged), S = 3:
+      the per-sample loop   {b7_gp_predict_hyp; b7_score_*} x S + b7_score_finish_global(S)
+      b7_eval_nominate      N = 24: small-problem kernels + the fused launch; N = 150: general schedule + the S-batch kernel
+      b7_eval_nominate with B7_FIT_SMALL=0 B7_KPOST_SMALL=0 (diagnostic build): the general schedule at either N
+    must name the same winner with the same value bits and leave bitwise-equal accumulators (b7_score_finish(1.0)).  The profile
+    says which route b7_eval_nominate took: the fused launch is one "score" phase and no "argmax" phase, the batch route one of each."""
+    M, S = 300, 3
+    X_obs, Y, X_hid, hyp = make_problem(ctx, orc, d, N, M, lambda X: np.sin(3.0 * X).sum(axis=1, keepdims=True))
+    hyps = [dict(hyp, lenscale_sq=hyp["lenscale_sq"] * (1.0 + 0.25 * s), amp=hyp["amp"] * (1.0 + 0.1 * s)) for s in range(S)]
+    spec = dict(_SCORE_KINDS[kind])
+    fmin = [float(Y.min())]
+    if spec["score"] != "cb":
+        spec["fmin"] = fmin
+    ctx.grid_upload(X_hid)
+    ctx.gp_set_data(X_obs, Y)
+    for s, h in enumerate(hyps):
+        ctx.gp_predict_hyp(h["lenscale_sq"], h["amp"], h["noise"], h["mean"])
+        if s == 0:
+            ctx.score_reset()
+        if spec["score"] == "cb":
+            ctx.score_cb(1.0, spec["upper"], spec["sign"])
+        else:
+            (ctx.score_ei if spec["score"] == "ei" else ctx.score_logei)(fmin, 0.0)
+    results = [ctx.score_finish_global(float(S), 0) + (ctx.score_finish(1.0, download=True)[2],)]
+    ref = _diag_context(monkeypatch, B7_FIT_SMALL="0", B7_KPOST_SMALL="0")
+    try:
+        counts = []
+        for c in (ctx, ref):
+            c.grid_upload(X_hid)
+            c.gp_set_data(X_obs, Y)
+            c.profile_enable(True)
+            try:
+                c.profile_reset()
+                val, idx, rep = c.eval_nominate(hyps, want_report=True, **spec)
+                counts.append((c.profile_get("score")[1], c.profile_get("argmax")[1]))
+            finally:
+                c.profile_enable(False)
+            assert not rep["jitter"].any() and not rep["info"].any()
+            results.append((val, idx, c.score_finish(1.0, download=True)[2]))
+    finally:
+        ref.close()
+    print("%s N %d: (score, argmax) launches %r, with the small-problem kernels off %r" % (kind, N, counts[0], counts[1]))
+    assert counts[0] == ((1, 0) if N <= 128 else (1, 1)), counts
+    val0, idx0, acc0 = results[0]
+    assert np.isfinite(acc0).all() and acc0.size == M
+    for route, (val, idx, acc) in zip(("b7_eval_nominate", "b7_eval_nominate, general schedule"), results[1:]):
+        assert idx == idx0 and np.float64(val).tobytes() == np.float64(val0).tobytes(), "%s: %s names another winner" % (kind, route)
+        assert acc.tobytes() == acc0.tobytes(), "%s: %s leaves other accumulator bits than the per-sample loop" % (kind, route)
