@@ -23,7 +23,7 @@ SYMBOLS = [
     "b7_grid_colrange", "b7_grid_apply_onesided", "b7_grid_random_torch", "b7_torch_rand",
     "b7_gp_default_opts", "b7_gp_set_opts", "b7_gp_set_kernel", "b7_gp_fit", "b7_gp_set_data", "b7_gp_fit_hyp", "b7_gp_predict_hyp", "b7_gp_nll_batch", "b7_chol", "b7_gp_predict", "b7_gp_predict_at", "b7_gp_fantasize", "b7_gp_append", "b7_gp_download",
     "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_cb", "b7_score_finish",
-    "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
+    "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_eval_nominate_batch", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
     "b7_group_grid_sobol", "b7_group_grid_random", "b7_group_grid_onesided", "b7_group_grid_upload", "b7_group_grid_shape", "b7_group_grid_download",
@@ -155,6 +155,7 @@ def load(which=None):
         "b7_score_finish_global": (i32, [vp, dbl, i64, C.POINTER(dbl), C.POINTER(i64)]),
         "b7_eval_nominate": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), i64, C.POINTER(dbl), C.POINTER(i64),
                                    vp, vp]),
+        "b7_eval_nominate_batch": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), i32, vp, vp, vp, vp]),
         "b7_blr_eval_nominate": (i32, [vp, C.POINTER(Mlp), vp, vp, i32, dbl, dbl, dbl, C.POINTER(ScoreSpec), i64, C.POINTER(dbl),
                                        C.POINTER(i64), C.POINTER(dbl)]),
         "b7_blr_eval_nominate_marg": (i32, [vp, C.POINTER(Mlp), vp, vp, i32, i32, vp, vp, vp, C.POINTER(ScoreSpec), i64, C.POINTER(dbl),
@@ -745,6 +746,23 @@ class Context(object):
         if want_report:
             return v.value, i.value, {"jitter": jit, "info": info}
         return v.value, i.value
+
+    def eval_nominate_batch(self, hyps, q, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0, want_report=False):
+        """A greedy batch of q nominees (b7_eval_nominate_batch): eval_nominate's pick, then q - 1 more by kriging-believer
+        variance downdates, the rows already picked left out.  hyps, score, fmin, tradeoff, upper, sign as eval_nominate.
+        Returns (values[q], 1-based indices[q][, report]); the grid is not modified (commit with grid_remove_rows)."""
+        S = len(hyps)
+        arr, keep = self._pack_hyps(hyps, getattr(self, "_data_d", -1))
+        spec, fm = self._pack_spec(score, fmin, tradeoff, upper, sign)
+        jit = np.zeros(S, dtype=np.float64) if want_report else None
+        info = np.zeros(S, dtype=np.int32) if want_report else None
+        n = max(int(q), 1)
+        vals, idx = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int64)
+        self._ck(self._L.b7_eval_nominate_batch(self._h, S, arr, C.byref(spec), int(q), _ptr(vals), _ptr(idx), _ptr(jit), _ptr(info)))
+        self.fit_token += 1
+        if want_report:
+            return vals, idx, {"jitter": jit, "info": info}
+        return vals, idx
 
     def ei_compute(self, mean, var, fmin, tradeoff=0.0):
         mean = _f64(mean)

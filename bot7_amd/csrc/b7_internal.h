@@ -212,6 +212,11 @@ struct b7_ctx {
   DevBuf tmpgrid; // predict_at temporary grid
   DevBuf tmpmu, tmpvar;
   DevBuf fant;   // fantasize workspace (pending-point covariance pieces)
+  // ---- b7_eval_nominate_batch (batch.hip): per hyper sample the posterior mean, the variance being downdated and the
+  // believer columns u_1 .. u_q-1 over the grid ([S][M] each), and the small vectors of a pick
+  DevBuf bel;     // mu [S][M] | var [S][M] | u [q-1][S][M]
+  DevBuf belvec;  // per sample: k(X, x_j) [Npad] | w_j = inv(K) k(X, x_j) [Npad] | amp, noise + jitter | t_j, u_i(x_j) (i < j)
+  PinBuf pin_bel; // amp, noise + jitter of the S samples on their way to belvec (not mapped)
   DevBuf feat;   // DNGO basis features of the resident grid: Mfeat x Npad (zero-padded columns)
   size_t feat_zeroed_bytes = 0;  // how much of `feat` was zeroed when it was laid out for feat_z columns
   int feat_z = -1;
@@ -423,9 +428,14 @@ int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64
                        int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
                        unsigned *host_done = nullptr, bool logacc = false);
 
+// excl (nullable): rows that take no part in the arg-max (their score is still written to acc)
+struct ExclRows {
+  int n = 0;
+  long long row[B7_BATCH_MAX];  // 0-based
+};
 int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
                              int rank, int world, int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
-                             unsigned *host_done = nullptr);
+                             unsigned *host_done = nullptr, const ExclRows *excl = nullptr);
 // the accumulator's state: zeros declared (bots/bayesopt.lua:69 without a launch of its own: the first score launch onto it
 // starts from 0.0; score_kind: the B7_SCORE_* it will add), zeros written now, no accumulator (the grid changed), declared zeros
 // written before anybody reads them
@@ -441,8 +451,9 @@ int launch_row_slot(b7_ctx *c, uint64_t *tab_dev, int rank, int world, int64_t i
 // b7_score_finish_global and the single-process group (group.hip) are assembled from
 int exch_table_ensure(b7_ctx *c, int world);
 // enqueue: score:div, local arg-max, this rank's record; pend (nullable): the nomination's batched score, run fused with them
+// excl (nullable, with pend): rows kept out of the arg-max (b7_eval_nominate_batch: the rows already picked)
 int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, bool all_slots, bool mirror = false,
-               const ScoreParams *pend = nullptr);
+               const ScoreParams *pend = nullptr, const ExclRows *excl = nullptr);
 int exch_wait_mirror(b7_ctx *c);  // after exch_local(..., mirror = true): spin on the completion word, then (or instead, when it takes long) the stream
 int exch_fail_record(b7_ctx *c, int rank, int world, int code);  // enqueue: this rank's record says "could not score"
 int exch_allreduce(b7_ctx *c);                                   // enqueue: the collective (no-op without a communicator)
@@ -489,9 +500,31 @@ ScoreParams score_params(const b7_ctx *c, const b7_score_spec *spec, const doubl
 int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumulate = true);
 ScoreParams pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd);
 int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t offset);
-int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend);
+// keep (nullable; b7_eval_nominate_batch): where every sample's posterior mean and variance over the grid, and its fit, are left
+// for the picks that follow the first.  The enqueued work is the same with and without it, copies aside.
+struct BelKeep {
+  double *mu = nullptr, *var = nullptr;  // [S][M]
+  // the S fits afterwards, sample s at base + s * (dpad | Npad dpad | Npad | Npad^2): the batch slots, or (S == 1) the context's own
+  const double *w = nullptr, *zsc = nullptr, *zss = nullptr, *Linv = nullptr;
+};
+int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend, BelKeep *keep = nullptr);
 bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist);
-int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out);
+int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out,
+              BelKeep *keep = nullptr);
+// batch.hip: the believer pass of sample s = blockIdx.z over rows x of xq (rows of them).  column: out kcol[s][Npad] = k(X, x_j)
+// (xq = the raw observations) and the believed row's scalars; else the downdate of var[s] and the store of u_j[s] (see batch.hip)
+struct BelPass {
+  const double *xq; int64_t rows;      // candidate rows (or the N observations)
+  const double *xj;                    // the believed point: one raw row of d entries
+  const double *w, *zsc, *zss;         // the S fits (strides dpad, Npad dpad, Npad)
+  const double *wj;                    // [S][Npad] inv(K_s) k_s(X, x_j); unused by the column pass
+  const double *par;                   // [S][2] amp, noise + jitter
+  double *scal;                        // [S][1 + B7_BATCH_MAX] t_j, u_i(x_j)
+  double *kcol;                        // column pass: [S][Npad] out
+  double *var, *u; int64_t sgrid;      // downdate: var[s][M] in/out, u[i][s][M] (i < j read, i = j written); sgrid = M
+  int64_t idx; int j;                  // the believed row (0-based), the number of earlier believer columns
+};
+int launch_believer(b7_ctx *c, int S, const BelPass &p, bool column);
 // grid_api.hip
 int grid_drop_row(b7_ctx *c, int64_t local_idx1, double *row_out_sync);  // stable deletion, enqueued; row_out != NULL synchronises
 

@@ -79,7 +79,46 @@ ScoreParams pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, con
 // bots/bayesopt.lua:69-78 as stream work: zero the accumulator, then fit + posterior + score:add per hyper sample, each
 // fit's pivot report copied to its pinned slot in stream order.  Returns without waiting for any of it; the small regime's
 // score:add is left to the caller's exchange step in *pend.
-int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend) {
+// b7_eval_nominate_batch's hook (keep, nullable): sample s of S has just been fitted into the context's own slots and predicted
+// into c->mu / c->var; its mean and variance go to keep's arrays, its fit to batch slot s (S == 1: it stays where it is)
+static int keep_slots_ensure(b7_ctx *c, int S) {
+  const size_t n = (size_t)c->Npad;
+  B7_TRY(b7_ensure(c, c->bw, sizeof(double) * (size_t)S * c->dpad));
+  B7_TRY(b7_ensure(c, c->bzsc, sizeof(double) * (size_t)S * n * c->dpad));
+  B7_TRY(b7_ensure(c, c->bzss, sizeof(double) * (size_t)S * n));
+  return b7_ensure(c, c->bLinv, sizeof(double) * (size_t)S * n * n);
+}
+static int keep_sample(b7_ctx *c, BelKeep *keep, int S, int s) {
+  if (!keep) return B7_OK;
+  const size_t n = (size_t)c->Npad, mb = sizeof(double) * (size_t)c->M;
+  B7_HIP(c, hipMemcpyAsync(keep->mu + (size_t)s * c->M, c->mu.p, mb, hipMemcpyDeviceToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync(keep->var + (size_t)s * c->M, c->var.p, mb, hipMemcpyDeviceToDevice, c->stream));
+  if (S == 1) {
+    keep->w = (const double *)c->w.p, keep->zsc = (const double *)c->zsc.p, keep->zss = (const double *)c->zss.p;
+    keep->Linv = (const double *)c->Linv.p;
+    return B7_OK;
+  }
+  keep->w = (const double *)c->bw.p, keep->zsc = (const double *)c->bzsc.p, keep->zss = (const double *)c->bzss.p;
+  keep->Linv = (const double *)c->bLinv.p;
+  if (c->w.p == (double *)c->bw.p + (size_t)s * c->dpad) return B7_OK;  // the fit already lives in its batch slot
+  B7_HIP(c, hipMemcpyAsync((double *)c->bw.p + (size_t)s * c->dpad, c->w.p, sizeof(double) * c->dpad, hipMemcpyDeviceToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync((double *)c->bzsc.p + s * n * c->dpad, c->zsc.p, sizeof(double) * n * c->dpad, hipMemcpyDeviceToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync((double *)c->bzss.p + s * n, c->zss.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync((double *)c->bLinv.p + s * n * n, c->Linv.p, sizeof(double) * n * n, hipMemcpyDeviceToDevice, c->stream));
+  return B7_OK;
+}
+// ... or all S at once, from the batched posterior's arrays
+static int keep_batch(b7_ctx *c, BelKeep *keep, int S) {
+  if (!keep) return B7_OK;
+  const size_t bytes = sizeof(double) * (size_t)S * c->M;
+  B7_HIP(c, hipMemcpyAsync(keep->mu, c->bmu.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync(keep->var, c->bvar.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+  keep->w = (const double *)c->bw.p, keep->zsc = (const double *)c->bzsc.p, keep->zss = (const double *)c->bzss.p;
+  keep->Linv = (const double *)c->bLinv.p;
+  return B7_OK;
+}
+
+int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend, BelKeep *keep) {
   const int d = c->dfit;
   B7_HIP(c, hipSetDevice(c->device));
   B7_TRY(b7_ensure(c, c->mu, sizeof(double) * (size_t)c->M * c->ycols));
@@ -170,6 +209,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
       B7_TRY(launch_kpost_small(c, S, (const double *)c->grid[c->grid_cur].p, c->M, (const double *)c->bw.p, (const double *)c->bzsc.p,
                                 (const double *)c->bzss.p, (const double *)c->bLinv.p, (const double *)c->balpha.p, hyp_dev, 0.0, 0.0, 0.0,
                                 (double *)c->bmu.p, (double *)c->bvar.p, c->M));
+      B7_TRY(keep_batch(c, keep, S));
       *pend = pending_score(c, S, spec, fd);
       c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
       c->predicted = false;
@@ -185,6 +225,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
                               (const double *)c->balpha.p, (double *)c->ks.p, (int64_t)Mpad * n, (double *)c->bmu.p, c->M));
       B7_TRY(launch_post_batch(c, S, (const double *)c->bLinv.p, (const double *)c->ks.p, (int64_t)Mpad * n, Mpad, c->M,
                                (double *)c->bvar.p, c->M, amp_dev, noise_dev));
+      B7_TRY(keep_batch(c, keep, S));
       B7_TRY(launch_score_batch(c, pending_score(c, S, spec, fd), (double *)c->acc.p, c->M));
       c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
       c->predicted = false;
@@ -205,6 +246,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
         c->fitted = true;
         rc = predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p);
         if (rc == B7_OK) rc = score_add(c, spec, fd);
+        if (rc == B7_OK) rc = keep_sample(c, keep, S, s);
       }
       c->zsc.p = zsc0, c->zss.p = zss0, c->w.p = w0, c->alpha.p = alpha0, c->Linv.p = linv0;
       c->fitted = false;  // the context's own fit slot does not hold any of these fits
@@ -213,6 +255,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
       B7_TRY(rc);
     }
   } else {
+    if (keep && S > 1) B7_TRY(keep_slots_ensure(c, S));
     for (int s = 0; s < S; ++s) {
       B7_TRY(fit_front(c, &hyps[s], (const double *)c->bhyp.p + (size_t)s * d));
       int *report = static_cast<int *>(c->pin_eval.dev) + 4 * s;  // a one-block factorisation mirrors its report itself
@@ -225,6 +268,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
       c->predicted = true;
       c->Mpred = c->M;
       B7_TRY(score_add(c, spec, fd));
+      B7_TRY(keep_sample(c, keep, S, s));
     }
     // this fit's lengthscales sit in the batch staging block, not in ScratchBlock::lenscale: the fit slot is declared empty
     c->fitted = false;
@@ -245,8 +289,9 @@ bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist) {
 }
 
 // the same nomination through the per-sample path, jitter schedule (utils/math.lua:159-218) included; synchronous
-int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out) {
+int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out, BelKeep *keep) {
   B7_HIP(c, hipSetDevice(c->device));
+  if (keep && S > 1) B7_TRY(keep_slots_ensure(c, S));
   B7_TRY(acc_write_zeros(c));
   double *fd = nullptr;
   for (int s = 0; s < S; ++s) {
@@ -255,6 +300,7 @@ int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, d
     c->Mpred = c->M;
     if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
     B7_TRY(score_add(c, spec, fd));
+    B7_TRY(keep_sample(c, keep, S, s));
   }
   return B7_OK;
 }

@@ -355,6 +355,29 @@ __global__ void __launch_bounds__(256)
   block_best_ticket_record(b, sh, &last, part, ticket, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
 }
 
+// The same with rows left out of the arg-max (b7_eval_nominate_batch: the rows already picked).  Their score is computed and
+// written like any other; only the candidate for the block reduction is withheld, so a NaN there does not win.
+template <int K>
+__global__ void __launch_bounds__(256)
+    score_finish_slot_excl_kernel(ScoreParams p, int fresh, double *__restrict__ acc, long long M, double divisor, Best *__restrict__ part,
+                                  unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank, int world,
+                                  long long offset, const double *__restrict__ grid, int d, int all_slots,
+                                  unsigned long long *__restrict__ host_rec, unsigned *__restrict__ host_done, ExclRows excl) {
+  __shared__ Best sh[4];
+  __shared__ unsigned last;
+  Best b{0.0, -1};
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
+    const double v = div<K>(fold_samples<K>(p, j, fresh ? empty<K>() : acc[j]), divisor);
+    acc[j] = v;
+    bool out = false;
+    for (int e = 0; e < excl.n; ++e) out = out || excl.row[e] == j;
+    Best cnd{v, j};
+    if (!out && better(cnd, b)) b = cnd;
+  }
+  block_best_ticket_record(b, sh, &last, part, ticket, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
+}
+
 __global__ void __launch_bounds__(256) keep_record_kernel(unsigned long long *__restrict__ tab, int rank, int world) {
   for (int e = threadIdx.x; e < world * B7_TAB_W; e += blockDim.x)
     if (e / B7_TAB_W != rank) tab[e] = 0ull;
@@ -512,7 +535,7 @@ int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64
 // The fused form: the S-sample score, score:div, the local arg-max and the record in one launch.
 int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
                              int rank, int world, int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec,
-                             unsigned *host_done) {
+                             unsigned *host_done, const ExclRows *excl) {
   PhaseScope scope(c, "score");
   // (one-wave blocks for small grids -- 313 instead of 79 workgroups for 2e4 candidates -- measured SLOWER: 145 vs 139 us per
   // nomination at N = 100, S = 10; the last block's pass over four times as many partials costs more than the spread saves.
@@ -530,9 +553,14 @@ int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64
   int mode;
   B7_TRY(acc_mode_or_fail(c, acc, true, score_acc_kind(p.kind), &mode));
   with_score_kind(p.kind, [&](auto k) {
-    hipLaunchKernelGGL(score_finish_slot_kernel<decltype(k)::value>, dim3(nb), dim3(threads), 0, c->stream, p, mode == 2 ? 1 : 0, acc,
-                       (long long)M, divisor, part, ticket, (unsigned long long *)tab_dev, rank, world, (long long)offset, grid, d,
-                       all_slots ? 1 : 0, (unsigned long long *)host_rec, host_done);
+    if (excl && excl->n > 0)
+      hipLaunchKernelGGL(score_finish_slot_excl_kernel<decltype(k)::value>, dim3(nb), dim3(threads), 0, c->stream, p, mode == 2 ? 1 : 0,
+                         acc, (long long)M, divisor, part, ticket, (unsigned long long *)tab_dev, rank, world, (long long)offset, grid,
+                         d, all_slots ? 1 : 0, (unsigned long long *)host_rec, host_done, *excl);
+    else
+      hipLaunchKernelGGL(score_finish_slot_kernel<decltype(k)::value>, dim3(nb), dim3(threads), 0, c->stream, p, mode == 2 ? 1 : 0, acc,
+                         (long long)M, divisor, part, ticket, (unsigned long long *)tab_dev, rank, world, (long long)offset, grid, d,
+                         all_slots ? 1 : 0, (unsigned long long *)host_rec, host_done);
   });
   B7_HIP(c, hipGetLastError());
   return B7_OK;

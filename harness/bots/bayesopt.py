@@ -14,6 +14,8 @@ subtraction of log(nSamples)."""
 import numpy as np
 
 from .abstract import abstract
+from .. import tensor as T
+from bot7_amd.grids.abstract import DeviceGrid
 from bot7_amd import models as Models
 from bot7_amd import scores as Scores
 
@@ -42,6 +44,7 @@ class bayesopt(abstract):
         score = dict(config.get("score") or {})
         score.setdefault("type", "expected_improvement")  # :49
         config["score"] = score
+        config["bot"].setdefault("batch", 1)            # ours: nominees per trial (nominate_batch); 1 is the reference's loop
         return config
 
     def eval(self, candidates=None, want_scores=True):
@@ -96,3 +99,49 @@ class bayesopt(abstract):
             return int(np.floor(self._rng.random() * cand.shape[0])) + 1
         _, _, idx = self.eval(cand, want_scores=False)            # :95-96
         return idx
+
+    def nominate_batch(self, q=None, candidates=None):
+        """q nominees from ONE library call (b7_eval_nominate_batch; no counterpart in the reference): nominate's pick, then
+        q - 1 more by kriging-believer variance downdates.  Returns q 1-based indices into the candidates as they stand; the
+        caller commits them.  Sampling as eval's fused branch (bots/bayesopt.lua:68, :73-75); q = 1 is nominate."""
+        cand = self.candidates if candidates is None else candidates
+        q = int(self.config["bot"]["batch"] if q is None else q)
+        if q == 1:
+            return [int(self.nominate(cand))]
+        if self.nTrials <= self.config["bot"]["nInitial"]:        # :90-91, q distinct rows
+            return [int(i) + 1 for i in self._rng.choice(cand.shape[0], size=q, replace=False)]
+        X_obs, Y_obs, model = self.observed, self.responses, self.model
+        spec = getattr(self.score, "device_spec", None)
+        assert spec is not None and hasattr(model, "stage") and not hasattr(cand, "commit"), \
+            "nominate_batch: a GP model with a device score on one GPU (sharded batches are not built)"
+        model.sample_hypers(X_obs, Y_obs)                         # :68 (burn-in call)
+        hyps = [model.parse_hypers(model.sample_hypers(X_obs, Y_obs, None, None, True))
+                for _ in range(self.config["bot"]["nSamples"])]   # :73-75
+        model.stage(X_obs, Y_obs, cand)
+        _, idx = model.ctx.eval_nominate_batch(hyps, q, **spec(Y_obs))
+        self.last_scores = None
+        return [int(i) for i in idx]
+
+    def run_trial(self):
+        """bots/abstract.lua:112-152 with config.bot.batch nominees per trial: all of them are stolen from the candidates in one
+        stable pass (:118), evaluated and observed (:124-144).  batch = 1 is the parent's loop, untouched."""
+        q = int(self.config["bot"]["batch"])
+        if q == 1:
+            return super().run_trial()
+        self.nTrials += 1
+        idx = self.nominate_batch(q)                               # :117
+        cand = self.candidates
+        rows = np.array(np.asarray(cand)[np.asarray(idx) - 1], dtype=np.float64)
+        host = T.remove(np.asarray(cand), idx)                     # :118, an index list (utils/tensor.lua:158-193)
+        if isinstance(cand, DeviceGrid) and cand.ctx is not None and cand.version == cand.ctx.grid_version:
+            assert np.array_equal(cand.ctx.grid_remove_rows(idx), rows)   # the same stable deletion on the resident copy
+            self.candidates = None if host is None else DeviceGrid(host, cand.ctx, cand.ctx.grid_version)
+        else:
+            self.candidates = host
+        ys = np.concatenate([np.asarray(self.objective(r), dtype=np.float64).reshape(1, -1) for r in rows], 0)   # :124
+        self.responses = ys if self.responses is None else np.concatenate([self.responses, ys], 0)
+        self.observed = rows if self.observed is None else np.concatenate([self.observed, rows], 0)            # :143-144
+        if self.model is not None and self.nTrials == self.config["bot"]["nInitial"]:
+            self.model.init(self.observed, self.responses)         # :147-149
+        best = int(ys[:, 0].argmin())
+        return rows[best], ys[best:best + 1]

@@ -370,6 +370,31 @@ typedef struct {
 int b7_eval_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset,
                      double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out);
 
+/* A greedy BATCH of q nominees from one call: b7_eval_nominate's pick, then q - 1 more by KRIGING-BELIEVER variance downdates.
+ * No counterpart in the reference, whose bots nominate one point per trial (bots/abstract.lua:118).  The believer pretends that
+ * the row just picked, x_j, was observed at its own posterior mean under each hyper sample s (y_j := mu_s(x_j)).  Under that
+ * lie the posterior mean of every candidate is unchanged, and the latent variance takes a rank-one downdate:
+ *   c_s,j(x)   = k_s(x, x_j) - K*_s(x, X) w_s,j,        w_s,j = inv(K_s) k_s(X, x_j) = inv(L)' (inv(L) k_s(X, x_j))
+ *   u_s,j(x)   = (c_s,j(x) - sum_{i<j} u_s,i(x) u_s,i(x_j)) / sqrt(t_s,j),     t_s,j = var_s,j-1(x_j) + noise_s
+ *   var_s,j(x) = var_s,j-1(x) - u_s,j(x)^2
+ * (noise_s includes the jitter that sample's factorisation needed, if any).  No refit, no factorisation, no variance product:
+ * an extra pick is one pass that forms the rows of K* without storing them, two triangular mat-vecs per sample and a rescoring.
+ *   pick 1     best_val[0], best_idx1[0], jitter_out and info_out are b7_eval_nominate's with global_row_offset = 0, bit for
+ *              bit, for every score kind and covariance kernel, the jitter redo included;
+ *   pick 2..q  the whole grid re-scored from the unchanged per-sample means, the downdated variances and the caller's spec (fmin
+ *              stays the caller's: the lie never enters it), marginalised over the S samples as b7_eval_nominate does, then
+ *              score:max(1) with the rows already picked in this call left out (a NaN there does not win).
+ * q in 1..B7_BATCH_MAX and q <= the grid's rows, else B7_ERR_INVALID.  B7_ERR_UNSUPPORTED: b7_gp_opts.var_with_noise or
+ * var_clamp set (the downdate works on the latent variance), more than one response column, a communicator of more than one
+ * rank; a member of a group answers B7_ERR_STATE as b7_eval_nominate does (sharded batches are not built).  The grid is not
+ * modified: the caller commits the q rows itself (b7_grid_remove_rows).  Deterministic: the same call twice gives the same
+ * bits.  Afterwards the accumulator holds the LAST pick's score / S, and the context's own fit slot holds none of the samples.
+ * Device memory: S (q + 1) M doubles beside b7_eval_nominate's, allocated on demand (B7_ERR_NOMEM) and freed with the context.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_BATCH_MAX 16
+int b7_eval_nominate_batch(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int q, double *best_val /*q*/,
+                           int64_t *best_idx1 /*q*/, double *jitter_out, int *info_out);
+
 /* bayesopt:eval's DNGO branch + nominate as ONE call (bots/bayesopt.lua:65-66, :96 over models/dngo.lua:155-175):
  * b7_blr_fit_x(net, X0, Y0, ...) + b7_blr_basis(net, resident grid) + b7_blr_predict + the acquisition of `spec` (written,
  * not accumulated: ONE point (alpha_prec, beta, mean); b7_blr_eval_nominate_marg below marginalises over S of them) +

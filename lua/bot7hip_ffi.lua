@@ -70,6 +70,7 @@ int b7_shard_commit_rule(int64_t idx1_global, int64_t offset, int64_t M_local, i
 int b7_exchange_info(b7_ctx *ctx, int *world, int64_t *rows_per_rank, int64_t *winner_idx1, int *winner_rank, double *winner_row);
 typedef struct { int kind; double tradeoff; int upper; double sign; const double *fmin; } b7_score_spec;
 int b7_eval_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out);
+int b7_eval_nominate_batch(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int q, double *best_val , int64_t *best_idx1 , double *jitter_out, int *info_out);
 int b7_blr_eval_nominate(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, double alpha_prec, double beta, double mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *jitter_used);
 int b7_blr_eval_nominate_marg(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *alpha_prec, const double *beta, const double *mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *nll_out, double *jitter_used);
 typedef struct b7_group b7_group;
@@ -128,6 +129,7 @@ M.COMM_MIN = 2
 M.SCORE_EI = 1
 M.SCORE_CB = 2
 M.SCORE_LOGEI = 3
+M.BATCH_MAX = 16
 M.MAX_TIMERS = 16
 -- END generated constants
 

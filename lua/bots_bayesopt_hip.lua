@@ -91,6 +91,44 @@ function bot:nominate(candidates)
   return torch.LongTensor{tonumber(i[0])}
 end
 
+-- q nominees from ONE library call (b7_eval_nominate_batch; no counterpart in the reference, whose bots nominate one point per
+-- trial): nominate's pick, then q - 1 more by kriging-believer variance downdates, the rows already picked left out.  Returns a
+-- LongTensor of q indices into `candidates` as it stands (the caller commits them: utils.tensor.steal takes an index list).
+-- One rank, no group: sharded batches are not built.  config.bot.batch (default 1) is the q a driver passes; nominate_batch(1)
+-- is nominate.
+function bot:nominate_batch(q, candidates)
+  local candidates = candidates or self.candidates
+  q = q or self.config.bot.batch or 1
+  if q == 1 then return self:nominate(candidates) end
+  assert(D.world == 1 and not hip.group, 'nominate_batch: one rank, no group (sharded batches are not built)')
+  if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91, q distinct rows
+    return torch.randperm(candidates:size(1)):narrow(1, 1, q):long()
+  end
+  local model, keep = self.model, {}
+  local Y_obs = self.responses
+  if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
+  local spec = (torch.type(model) == 'bot7.models.gp_hip') and score_spec(self.score, Y_obs, keep) or nil
+  assert(spec ~= nil, 'nominate_batch: needs the gp_hip model and a *_hip score')
+  local X_obs, S = self.observed, self.config.bot.nSamples
+  model:sample_hypers(X_obs, Y_obs)                                          -- :68
+  local hyps = ffi.new('b7_hyp[?]', S)
+  for s = 1, S do                                                            -- :73-75
+    local hyp = model:parse_hypers(model:sample_hypers(X_obs, Y_obs, nil, nil, true))
+    local ls  = hip.pin(hyp.lenscale_sq)
+    keep[#keep + 1] = ls
+    hyps[s-1].lenscale_sq, hyps[s-1].amp, hyps[s-1].noise, hyps[s-1].mean = hip.data(ls), hyp.amp, hyp.noise, hyp.mean
+  end
+  model:stage(X_obs, Y_obs, candidates)
+  hip.set_kernel(model.kernel_code)
+  local v, i = ffi.new('double[?]', q), ffi.new('int64_t[?]', q)
+  local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+  hip.check(hip.C.b7_eval_nominate_batch(hip.ctx, S, hyps, spec, q, v, i, jit, info))
+  local out = torch.LongTensor(q)
+  for k = 0, q - 1 do out[k + 1] = tonumber(i[k]) end
+  self.best_score = v[0]
+  return out
+end
+
 -- bots/abstract.lua:112-152 for candidates sharded one process per GPU.  Only line 118 differs: `idx` is 1-based in the
 -- union of the shards, so it must not index this rank's shard; dist_hip.commit returns the nominee on every rank and
 -- deletes the row where it lives.  With one rank (or a group) the parent's code is right as it stands.
