@@ -1,7 +1,9 @@
 """Float64 numpy references for kriging-believer batch nomination (tests/test_believer_host.py, tests/test_gpu_believer.py):
 the rank-one variance downdate as include/bot7hip.h states it, the refit it must equal (the believed point appended to the data
 at its own posterior mean), the three acquisition scores as bot7_amd/csrc/score.hip evaluates them, and the greedy pick sequence
-with its top-2 gaps.  No GPU needed here."""
+with its top-2 gaps; and the same refit in 50-digit arithmetic (believer_truth), the truth both the float64 restatements and the
+device are measured against.  No GPU needed here."""
+import mpmath
 import numpy as np
 from scipy import special
 from scipy.linalg import cholesky, solve_triangular
@@ -64,6 +66,65 @@ def refit(X, y, Xc, hyp, kernel, rows0):
         X, y = np.vstack([X, np.asarray(Xc)[r]]), np.append(y, p.mu[r])
         p = Posterior(X, y, Xc, hyp, kernel)
     return p.mu, p.var
+
+
+# ---- the refit at 50 digits --------------------------------------------------------------------------------------------------
+def believer_truth(X, y, Xc, hyp, kernel, rows0, probes, after=None, jitter=0.0, dps=50):
+    """The GP the believer stands for, in dps-digit arithmetic: the rows rows0 of Xc appended to the data one after the other, each
+    observed at the posterior mean of the model just before it; K + (noise + jitter) I on the diagonal, believed rows included.
+    Returns {j: (mu, var)} for every j in `after` (default: len(rows0) only): the posterior mean and LATENT variance at the rows
+    `probes` of Xc once the first j of rows0 are believed, as lists of mpf.  ARD-SE amp exp(-D/2); ARD Matern-5/2
+    amp (1 + s + s^2/3) exp(-s), s = sqrt(5 D) (tests/_matern_ref.py), D = sum_k (x_k - z_k)^2 / lenscale_sq_k from the float64
+    inputs.  One factorisation serves every j: the factor of the first N + j points is the leading block of the factor of all of
+    them, and so are inv(L) k and inv(L) (y - mean)."""
+    X, Xc = np.asarray(X, dtype=np.float64), np.asarray(Xc, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64).ravel()
+    rows0 = [int(r) for r in rows0]
+    after = [len(rows0)] if after is None else sorted(int(j) for j in after)
+    N, d, q = X.shape[0], X.shape[1], len(rows0)
+    with mpmath.workdps(dps):
+        mpf = mpmath.mpf
+        ls = [mpf(float(v)) for v in np.asarray(hyp["lenscale_sq"], dtype=np.float64).ravel()]
+        A, m = mpf(float(hyp["amp"])), mpf(float(hyp["mean"]))
+        diag = mpf(float(hyp["noise"])) + mpf(float(jitter))
+        pts = [[mpf(float(v)) for v in r] for r in np.vstack([X, Xc[rows0].reshape(q, d)])]
+
+        def k(a, b):
+            D = mpmath.fsum((a[i] - b[i]) ** 2 / ls[i] for i in range(d))
+            if kernel == "ardse":
+                return A * mpmath.exp(-D / 2)
+            s = mpmath.sqrt(5 * D)
+            return A * (1 + s + s * s / 3) * mpmath.exp(-s)
+
+        # row-by-row Cholesky of the (N + q)-point K; t = inv(L) (y - mean), the believed values made on the way
+        n = N + q
+        L = [[mpf(0)] * n for _ in range(n)]
+        t = []
+        for i in range(n):
+            for j in range(i + 1):
+                kij = k(pts[i], pts[j]) + (diag if i == j else 0)
+                acc = kij - mpmath.fsum(L[i][c] * L[j][c] for c in range(j))
+                L[i][j] = mpmath.sqrt(acc) if i == j else acc / L[j][j]
+            # the response of point i less the mean: the data's, or the posterior mean of the first i points at a believed row,
+            # k' inv(K) r = (inv(L) k) . (inv(L) r), whose inv(L) k is row i of L itself
+            r = (mpf(float(y[i])) - m) if i < N else mpmath.fsum(L[i][c] * t[c] for c in range(i))
+            t.append((r - mpmath.fsum(L[i][c] * t[c] for c in range(i))) / L[i][i])
+        out = {j: ([], []) for j in after}
+        for p in probes:
+            z = [mpf(float(v)) for v in Xc[int(p)]]
+            v = []
+            for i in range(n):
+                v.append((k(z, pts[i]) - mpmath.fsum(L[i][c] * v[c] for c in range(i))) / L[i][i])
+            for j in after:
+                out[j][0].append(m + mpmath.fsum(v[c] * t[c] for c in range(N + j)))
+                out[j][1].append(A - mpmath.fsum(v[c] ** 2 for c in range(N + j)))
+        return out
+
+
+def err_vs_truth(got, truth):
+    """max |got - truth| over a float64 vector and a list of mpf, evaluated at the truth's precision."""
+    with mpmath.workdps(50):
+        return float(max(abs(mpmath.mpf(float(g)) - tv) for g, tv in zip(np.asarray(got, dtype=np.float64).ravel(), truth)))
 
 
 # ---- the scores, as score.hip evaluates them ---------------------------------------------------------------------------------
