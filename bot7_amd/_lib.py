@@ -22,7 +22,7 @@ SYMBOLS = [
     "b7_sobol_direction_numbers", "b7_grid_sobol", "b7_grid_random", "b7_grid_upload", "b7_grid_download", "b7_grid_shape", "b7_grid_remove", "b7_grid_remove_rows",
     "b7_grid_colrange", "b7_grid_apply_onesided", "b7_grid_random_torch", "b7_torch_rand",
     "b7_gp_default_opts", "b7_gp_set_opts", "b7_gp_set_kernel", "b7_gp_fit", "b7_gp_set_data", "b7_gp_fit_hyp", "b7_gp_predict_hyp", "b7_gp_nll_batch", "b7_chol", "b7_gp_predict", "b7_gp_predict_at", "b7_gp_fantasize", "b7_gp_append", "b7_gp_download",
-    "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_cb", "b7_score_finish",
+    "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_mes", "b7_mes_set_levels", "b7_mes_last_ystar", "b7_mes_ystar", "b7_mes_compute", "b7_score_cb", "b7_score_finish",
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_eval_nominate_batch", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
@@ -49,7 +49,8 @@ class ScoreSpec(C.Structure):
                 ("fmin", C.POINTER(C.c_double))]
 
 
-SCORE_EI, SCORE_CB, SCORE_LOGEI = 1, 2, 3
+SCORE_EI, SCORE_CB, SCORE_LOGEI, SCORE_MES = 1, 2, 3, 4
+MES_KMAX = 64
 
 # covariance kernels (b7_gp_set_kernel): config.model.kernel names (bots/bayesopt.lua:41) -> B7_KERNEL_*
 KERNELS = {"ardse": 0, "ardmatern52": 1}
@@ -144,6 +145,11 @@ def load(which=None):
         "b7_score_reset": (i32, [vp]),
         "b7_score_ei": (i32, [vp, vp, dbl]),
         "b7_score_logei": (i32, [vp, vp, dbl]),
+        "b7_score_mes": (i32, [vp]),
+        "b7_mes_set_levels": (i32, [vp, i32]),
+        "b7_mes_last_ystar": (i32, [vp, C.POINTER(i32), C.POINTER(i32), vp, vp]),
+        "b7_mes_ystar": (i32, [vp, vp, vp, i64, i32, vp, vp]),
+        "b7_mes_compute": (i32, [vp, vp, vp, vp, i32, i64, vp]),
         "b7_score_cb": (i32, [vp, dbl, i32, dbl]),
         "b7_score_finish": (i32, [vp, dbl, C.POINTER(dbl), C.POINTER(i64), vp]),
         "b7_comm_pick_winner": (i32, [vp, i32, C.POINTER(dbl), C.POINTER(i64)]),
@@ -646,6 +652,36 @@ class Context(object):
         f = _f64(fmin).ravel()
         self._ck(self._L.b7_score_logei(self._h, _ptr(f), float(tradeoff)))
 
+    def score_mes(self):
+        """Max-value entropy search of the last predict: the y* search on the device, then score:add (b7_score_mes)."""
+        self._ck(self._L.b7_score_mes(self._h))
+
+    def mes_set_levels(self, K):
+        """K quantiles of the grid minimum per hyper sample for the searches that follow (b7_mes_set_levels; default 8)."""
+        self._ck(self._L.b7_mes_set_levels(self._h, int(K)))
+
+    def mes_last_ystar(self):
+        """(ystar S x K, bracket S x 2 = lo0, hi0) of the last y* search on this context (b7_mes_last_ystar)."""
+        S, K = C.c_int(0), C.c_int(0)
+        self._ck(self._L.b7_mes_last_ystar(self._h, C.byref(S), C.byref(K), None, None))
+        ystar, bracket = np.empty((S.value, K.value), dtype=np.float64), np.empty((S.value, 2), dtype=np.float64)
+        self._ck(self._L.b7_mes_last_ystar(self._h, None, None, _ptr(ystar), _ptr(bracket)))
+        return ystar, bracket
+
+    def mes_ystar(self, mean, var, K=8):
+        """The y* search alone on caller-provided mean / var (M each): (ystar K, bracket 2 = lo0, hi0) (b7_mes_ystar)."""
+        mean, var = _f64(mean).ravel(), _f64(var).ravel()
+        ystar, bracket = np.empty(int(K) if 1 <= int(K) <= MES_KMAX else 1, dtype=np.float64), np.empty(2, dtype=np.float64)
+        self._ck(self._L.b7_mes_ystar(self._h, _ptr(mean), _ptr(var), mean.shape[0], int(K), _ptr(ystar), _ptr(bracket)))
+        return ystar, bracket
+
+    def mes_compute(self, mean, var, ystar):
+        """The MES score on caller-provided mean / var (M each) with the caller's y* (K values) (b7_mes_compute)."""
+        mean, var, ystar = _f64(mean).ravel(), _f64(var).ravel(), _f64(ystar).ravel()
+        out = np.empty(mean.shape[0], dtype=np.float64)
+        self._ck(self._L.b7_mes_compute(self._h, _ptr(mean), _ptr(var), _ptr(ystar), ystar.shape[0], mean.shape[0], _ptr(out)))
+        return out
+
     def score_cb(self, tradeoff=1.0, upper=False, sign=-1.0):
         self._ck(self._L.b7_score_cb(self._h, float(tradeoff), int(bool(upper)), float(sign)))
 
@@ -725,15 +761,20 @@ class Context(object):
             fm = _f64(fmin).ravel()
             return ScoreSpec(SCORE_EI if score == "ei" else SCORE_LOGEI, 0.0 if tradeoff is None else float(tradeoff), 0, 0.0,
                              fm.ctypes.data_as(C.POINTER(C.c_double))), fm
+        if score == "mes":  # fmin, tradeoff, upper and sign are ignored
+            return ScoreSpec(SCORE_MES, 0.0, 0, 0.0, None), None
         if score == "cb":
             return ScoreSpec(SCORE_CB, 1.0 if tradeoff is None else float(tradeoff), int(bool(upper)), float(sign),
                              None), None
-        raise Bot7HipError(-1, "score must be 'ei', 'logei' or 'cb'")
+        raise Bot7HipError(-1, "score must be 'ei', 'logei', 'mes' or 'cb'")
 
     def eval_nominate(self, hyps, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0,
-                      global_row_offset=0, want_report=False):
+                      global_row_offset=0, want_report=False, levels=None):
         """bayesopt:eval + nominate in one call: hyps is a sequence of (lenscale_sq, amp, noise, mean) or dicts
-        with those keys; score "ei" (needs fmin) or "cb".  Returns (value, 1-based global index[, report])."""
+        with those keys; score "ei" / "logei" (need fmin), "cb" or "mes" (levels: mes_set_levels first).  Returns (value, 1-based
+        global index[, report])."""
+        if levels is not None:
+            self.mes_set_levels(levels)
         S = len(hyps)
         arr, keep = self._pack_hyps(hyps, getattr(self, "_data_d", -1))
         spec, fm = self._pack_spec(score, fmin, tradeoff, upper, sign)
@@ -747,10 +788,13 @@ class Context(object):
             return v.value, i.value, {"jitter": jit, "info": info}
         return v.value, i.value
 
-    def eval_nominate_batch(self, hyps, q, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0, want_report=False):
+    def eval_nominate_batch(self, hyps, q, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0, want_report=False, levels=None):
         """A greedy batch of q nominees (b7_eval_nominate_batch): eval_nominate's pick, then q - 1 more by kriging-believer
-        variance downdates, the rows already picked left out.  hyps, score, fmin, tradeoff, upper, sign as eval_nominate.
+        variance downdates, the rows already picked left out.  hyps, score, fmin, tradeoff, upper, sign, levels as eval_nominate
+        (score "mes" reaches the library, which answers "unsupported" for batches).
         Returns (values[q], 1-based indices[q][, report]); the grid is not modified (commit with grid_remove_rows)."""
+        if levels is not None:
+            self.mes_set_levels(levels)
         S = len(hyps)
         arr, keep = self._pack_hyps(hyps, getattr(self, "_data_d", -1))
         spec, fm = self._pack_spec(score, fmin, tradeoff, upper, sign)
@@ -921,7 +965,10 @@ class Group(object):
             m.ycols = Y.shape[1]
             m.fit_token += 1
 
-    def eval_nominate(self, hyps, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0, want_report=False):
+    def eval_nominate(self, hyps, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0, want_report=False, levels=None):
+        if levels is not None:   # as Context.eval_nominate: the members' level count (the group call itself refuses score "mes")
+            for m in self.members:
+                m.mes_set_levels(levels)
         S = len(hyps)
         arr, keep = Context._pack_hyps(hyps, self._data_d)
         spec, fm = Context._pack_spec(score, fmin, tradeoff, upper, sign)

@@ -107,9 +107,15 @@ struct PhaseStat {
 // S == 0: no score.  With S > 0 it is also a nomination's batched score, not launched yet: the exchange step runs it fused with
 // score:div, the arg-max and the record (score.hip: score_finish_slot_kernel).  A value of the call that made it, never of the
 // context: no later call can meet a pending score.
+// A kind reads ONE of fmin (EI, LogEI) and ystar (MES: y*[S][nlev] on the device, sample s at ystar + s * nlev; mes.hip); they share
+// a slot, and nlev sits in what was padding, so the argument layout of the EI / CB / LogEI kernels is what it was.
 struct ScoreParams {
-  int kind = 0, S = 0, upper = 0;  // kind: B7_SCORE_*
-  const double *mu = nullptr, *var = nullptr, *fmin = nullptr;
+  int kind = 0, S = 0, upper = 0, nlev = 0;  // kind: B7_SCORE_*
+  const double *mu = nullptr, *var = nullptr;
+  union {
+    const double *fmin = nullptr;
+    const double *ystar;
+  };
   long long stride = 0;
   double fmin0 = 0.0, tradeoff = 0.0, sign = 0.0;
 };
@@ -207,6 +213,14 @@ struct b7_ctx {
   int persist_fault = -1;    // tests only (B7_PERSIST_FAULT): panel whose flag workgroup 0 withholds, to exercise the time-out
   int potrf_sched_saved = 0; // the schedule to return to after such a redo
   DevBuf part;   // argmax partials (value, index)
+  // ---- max-value entropy search (mes.hip): y* of the last search, its brackets and the rounds' partial sums, laid out by mes_begin
+  DevBuf ystar, mes_ticket;
+  DevBuf mes_user;          // b7_mes_compute: the caller's y* (up to B7_MES_KMAX doubles), apart from the last search's
+  int mes_levels = 8;       // K of the searches a score starts (b7_mes_set_levels)
+  int mes_S = 0, mes_K = 0, mes_nb = 0;  // the layout of c->ystar: samples, levels, row blocks
+  int64_t mes_M = 0;        // rows per sample of that layout
+  int mes_slot = 0;         // the sample slot the next score_add of kind MES searches into (the nomination's per-sample loops set it)
+  bool mes_valid = false;   // a search has filled the buffer since it was laid out (b7_mes_last_ystar)
   DevBuf ticket; // score_finish_slot_kernel's arrival counter (zero between launches)
   DevBuf scratch; // a ScratchBlock (b7_scratch)
   DevBuf tmpgrid; // predict_at temporary grid
@@ -494,11 +508,20 @@ int stage_fmin(b7_ctx *c, const double *fmin, double **fd_out);
 static inline bool score_needs_fmin(int kind) { return kind == B7_SCORE_EI || kind == B7_SCORE_LOGEI; }
 // what a score of this kind leaves in an accumulator: a linear sum (EI, CB) or a log-sum-exp (LogEI)
 constexpr int score_acc_kind(int kind) { return kind == B7_SCORE_LOGEI ? B7_ACC_LOG : B7_ACC_LINEAR; }
+// mes.hip: c->ystar laid out for S samples of M rows at K levels; y* of nS samples (sample s at mu / var + s * stride) searched into
+// slots [slot0, slot0 + nS) of that layout, R + 1 launches; the device address of a slot's K values
+int mes_begin(b7_ctx *c, int S, int64_t M, int K);
+int launch_mes_search(b7_ctx *c, const double *mu, const double *var, int64_t stride, int nS, int slot0);
+const double *mes_ystar_dev(const b7_ctx *c, int slot);
+// what MES does not do yet, each answered B7_ERR_UNSUPPORTED with the case named: a sharded grid (y* over shards needs R more
+// all-reduces) and fantasies (more than one response column)
+int mes_refuse(b7_ctx *c, const char *who, const b7_score_spec *spec);
 // a score's parameters from its spec; fd: f_min staged on the device (stage_fmin), or null with the one column's f_min in c->fmin_scalar
 ScoreParams score_params(const b7_ctx *c, const b7_score_spec *spec, const double *fd);
 // the acquisition of c->mu / c->var over the resident candidates into c->acc: added (score:add) or, for a single model, written
 int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumulate = true);
-ScoreParams pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd);
+// (kind MES: the y* search of the S samples is enqueued here, ahead of the score that reads it)
+int pending_score(b7_ctx *c, int S, const b7_score_spec *spec, const double *fd, ScoreParams *out);
 int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t offset);
 // keep (nullable; b7_eval_nominate_batch): where every sample's posterior mean and variance over the grid, and its fit, are left
 // for the picks that follow the first.  The enqueued work is the same with and without it, copies aside.

@@ -291,6 +291,8 @@ int b7_eval_nominate_batch(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_
   if (c->comm && c->comm_world > 1)
     return b7_fail(c, B7_ERR_UNSUPPORTED, "eval_nominate_batch: a communicator of %d ranks (sharded batches are not built)", c->comm_world);
   B7_TRY(eval_validate(c, S, hyps, spec, 0));
+  if (spec->kind == B7_SCORE_MES)
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "eval_nominate_batch: max-value entropy search is not built for batches (y* would have to follow the believer downdates)");
   if (c->ycols != 1) return b7_fail(c, B7_ERR_UNSUPPORTED, "eval_nominate_batch: %d response columns (one is built)", c->ycols);
   if (c->opts.var_with_noise || c->opts.var_clamp)
     return b7_fail(c, B7_ERR_UNSUPPORTED, "eval_nominate_batch: the downdate works on the latent variance (var_with_noise / var_clamp are set)");

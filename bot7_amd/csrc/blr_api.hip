@@ -260,7 +260,7 @@ static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const d
   double *fd = nullptr;
   if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
   acc_declare_zeros(c, spec->kind);
-  *pend = pending_score(c, S, spec, fd);
+  B7_TRY(pending_score(c, S, spec, fd, pend));
   return B7_OK;
 }
 
@@ -378,6 +378,8 @@ int b7_blr_eval_nominate(b7_ctx *c, const b7_mlp *net, const double *X0, const d
   if (!X0 || !Y0 || N < 1 || !spec) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: bad arguments");
   else if (!(alpha_prec > 0.0) || !(beta > 0.0)) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: precisions must be > 0");
   else rc = nominate_args(c, "blr_eval_nominate", spec, global_row_offset);
+  if (rc == B7_OK && spec->kind == B7_SCORE_MES)
+    rc = b7_fail(c, B7_ERR_UNSUPPORTED, "blr_eval_nominate: max-value entropy search is not built on this route (b7_blr_predict + b7_score_mes is)");
   if (rc == B7_OK) rc = hipSetDevice(c->device) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "hipSetDevice failed");
   if (rc == B7_OK) rc = upload_net(c, net, &z);
   if (rc == B7_OK && z > 256) rc = b7_fail(c, B7_ERR_UNSUPPORTED, "blr: basis width %d > 256", z);
@@ -407,6 +409,8 @@ int b7_blr_eval_nominate_marg(b7_ctx *c, const b7_mlp *net, const double *X0, co
   int rc = B7_OK, z = 0;
   if (!X0 || !Y0 || N < 1 || S < 1 || !ap || !bt || !mn || !spec) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: bad arguments");
   else rc = nominate_args(c, "blr_eval_nominate_marg", spec, global_row_offset);
+  if (rc == B7_OK && spec->kind == B7_SCORE_MES)
+    rc = b7_fail(c, B7_ERR_UNSUPPORTED, "blr_eval_nominate_marg: max-value entropy search is not built on this route (b7_blr_predict + b7_score_mes is)");
   for (int s = 0; rc == B7_OK && s < S; ++s)
     if (!(ap[s] > 0.0) || !(bt[s] > 0.0)) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: precisions must be > 0 (sample %d)", s);
   if (rc == B7_OK) rc = hipSetDevice(c->device) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "hipSetDevice failed");

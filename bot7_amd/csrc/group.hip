@@ -375,6 +375,8 @@ int b7_group_eval_nominate(b7_group *g, int S, const b7_hyp *hyps, const b7_scor
   if (jitter_out && S > 0) std::fill(jitter_out, jitter_out + S, 0.0);
   if (info_out && S > 0) std::fill(info_out, info_out + S, 0);
   g->win_valid = false;
+  if (spec && spec->kind == B7_SCORE_MES)
+    return gfail(g, B7_ERR_UNSUPPORTED, "group_eval_nominate: max-value entropy search over a sharded grid is not built (y* needs an all-reduce per round)");
   for (int i = 0; i < n; ++i) G_TRY(g, i, eval_validate(g->ctx[i], S, hyps, spec, 0));
   if (offset_of(g, n) == 0) return gfail(g, B7_ERR_STATE, "group_eval_nominate: no candidate grid on this group");
   // everything a member has to do, enqueued on its stream; the host moves on to the next member without waiting

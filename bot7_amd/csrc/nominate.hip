@@ -41,15 +41,34 @@ ScoreParams score_params(const b7_ctx *c, const b7_score_spec *spec, const doubl
   return p;
 }
 
+// max-value entropy search: the y* search of nS samples into slots [slot0, slot0 + nS) of the layout the caller's mes_begin made,
+// enqueued ahead of the score p that reads it
+static int mes_search_for(b7_ctx *c, ScoreParams *p, const double *mu, const double *var, int64_t stride, int nS, int slot0) {
+  B7_TRY(launch_mes_search(c, mu, var, stride, nS, slot0));
+  p->ystar = mes_ystar_dev(c, slot0), p->nlev = c->mes_K;
+  return B7_OK;
+}
+
+int mes_refuse(b7_ctx *c, const char *who, const b7_score_spec *spec) {
+  if (spec->kind != B7_SCORE_MES) return B7_OK;
+  if (c->comm && c->comm_world > 1)
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: max-value entropy search over a communicator of %d ranks is not built (y* over a sharded grid needs an all-reduce per round)", who, c->comm_world);
+  if (c->ycols != 1)
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: max-value entropy search over %d response columns (fantasies) is not built", who, c->ycols);
+  return B7_OK;
+}
+
 int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumulate) {
-  return launch_score(c, score_params(c, sp, fd), (const double *)c->mu.p, (const double *)c->var.p, c->M, c->ycols,
-                      (double *)c->acc.p, accumulate);
+  ScoreParams p = score_params(c, sp, fd);
+  if (sp->kind == B7_SCORE_MES)  // y* of this sample first, into the slot the caller named (c->mes_slot)
+    B7_TRY(mes_search_for(c, &p, (const double *)c->mu.p, (const double *)c->var.p, 0, 1, c->mes_slot));
+  return launch_score(c, p, (const double *)c->mu.p, (const double *)c->var.p, c->M, c->ycols, (double *)c->acc.p, accumulate);
 }
 
 // The score spec and the global row offset of an eval + nominate entry point (`who` in the messages).  Only a shard of a
 // larger candidate set -- a rank of a communicator, a member of a group -- may be empty: the exchange covers the others.
 int nominate_args(b7_ctx *c, const char *who, const b7_score_spec *spec, int64_t offset) {
-  if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB && spec->kind != B7_SCORE_LOGEI)
+  if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB && spec->kind != B7_SCORE_LOGEI && spec->kind != B7_SCORE_MES)
     return b7_fail(c, B7_ERR_INVALID, "%s: unknown score kind %d", who, spec->kind);
   if (score_needs_fmin(spec->kind) && !spec->fmin) return b7_fail(c, B7_ERR_INVALID, "%s: EI needs fmin", who);
   if (offset < 0) return b7_fail(c, B7_ERR_INVALID, "%s: negative row offset", who);
@@ -65,15 +84,17 @@ int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spe
   if (c->M > 0 && c->d != c->dfit)
     return b7_fail(c, B7_ERR_INVALID, "eval_nominate: grid dims %d != data dims %d", c->d, c->dfit);
   for (int s = 0; s < S; ++s) B7_TRY(check_hyp(c, &hyps[s], c->dfit));
-  return B7_OK;
+  return mes_refuse(c, "eval_nominate", spec);
 }
 
 // score:add x S of the batch in c->bmu / c->bvar, owed to the exchange step (exch_local), which runs it fused with score:div,
 // the arg-max and the record
-ScoreParams pending_score(const b7_ctx *c, int S, const b7_score_spec *spec, const double *fd) {
+int pending_score(b7_ctx *c, int S, const b7_score_spec *spec, const double *fd, ScoreParams *out) {
   ScoreParams p = score_params(c, spec, fd);
   p.S = S, p.mu = (const double *)c->bmu.p, p.var = (const double *)c->bvar.p, p.stride = c->M;
-  return p;
+  if (spec->kind == B7_SCORE_MES) B7_TRY(mes_search_for(c, &p, p.mu, p.var, p.stride, S, 0));  // all S samples: grid.y = sample
+  *out = p;
+  return B7_OK;
 }
 
 // bots/bayesopt.lua:69-78 as stream work: zero the accumulator, then fit + posterior + score:add per hyper sample, each
@@ -126,6 +147,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
   B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
   // predict_into's workspace, sized now: a reallocation inside the loop would synchronise
   B7_TRY(b7_ensure(c, c->ks, sizeof(double) * (size_t)predict_chunk(c, c->M) * c->Npad));
+  if (spec->kind == B7_SCORE_MES) B7_TRY(mes_begin(c, S, c->M, c->mes_levels));  // y*[S][K], brackets and partials, sized before anything is in flight
   // pinned staging: [S][4] pivot reports | hypers of all S samples ([S][d] lengthscales, then S amp, S noise, S mean)
   const size_t hyp_doubles = (size_t)S * (d + 3), ls_bytes = sizeof(double) * hyp_doubles, rep_bytes = 16 * (size_t)S;
   B7_TRY(b7_pin_ensure(c, c->pin_eval, ls_bytes + rep_bytes, true));
@@ -210,7 +232,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
                                 (const double *)c->bzss.p, (const double *)c->bLinv.p, (const double *)c->balpha.p, hyp_dev, 0.0, 0.0, 0.0,
                                 (double *)c->bmu.p, (double *)c->bvar.p, c->M));
       B7_TRY(keep_batch(c, keep, S));
-      *pend = pending_score(c, S, spec, fd);
+      B7_TRY(pending_score(c, S, spec, fd, pend));
       c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
       c->predicted = false;
     } else if ((size_t)Mpad * S * row_bytes <= c->ks_bytes) {
@@ -226,7 +248,9 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
       B7_TRY(launch_post_batch(c, S, (const double *)c->bLinv.p, (const double *)c->ks.p, (int64_t)Mpad * n, Mpad, c->M,
                                (double *)c->bvar.p, c->M, amp_dev, noise_dev));
       B7_TRY(keep_batch(c, keep, S));
-      B7_TRY(launch_score_batch(c, pending_score(c, S, spec, fd), (double *)c->acc.p, c->M));
+      ScoreParams all;
+      B7_TRY(pending_score(c, S, spec, fd, &all));
+      B7_TRY(launch_score_batch(c, all, (double *)c->acc.p, c->M));
       c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
       c->predicted = false;
     } else {
@@ -245,6 +269,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
         c->model_kind = 0;
         c->fitted = true;
         rc = predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p);
+        c->mes_slot = s;
         if (rc == B7_OK) rc = score_add(c, spec, fd);
         if (rc == B7_OK) rc = keep_sample(c, keep, S, s);
       }
@@ -267,6 +292,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
       B7_TRY(predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
       c->predicted = true;
       c->Mpred = c->M;
+      c->mes_slot = s;
       B7_TRY(score_add(c, spec, fd));
       B7_TRY(keep_sample(c, keep, S, s));
     }
@@ -293,12 +319,14 @@ int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, d
   B7_HIP(c, hipSetDevice(c->device));
   if (keep && S > 1) B7_TRY(keep_slots_ensure(c, S));
   B7_TRY(acc_write_zeros(c));
+  if (spec->kind == B7_SCORE_MES) B7_TRY(mes_begin(c, S, c->M, c->mes_levels));
   double *fd = nullptr;
   for (int s = 0; s < S; ++s) {
     B7_TRY(fit_hyp_core(c, &hyps[s], nullptr, jitter_out ? jitter_out + s : nullptr, info_out ? info_out + s : nullptr, true));
     c->predicted = true;
     c->Mpred = c->M;
     if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
+    c->mes_slot = s;
     B7_TRY(score_add(c, spec, fd));
     B7_TRY(keep_sample(c, keep, S, s));
   }
@@ -346,6 +374,9 @@ int b7_eval_nominate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *
   if (c->group) return b7_fail(c, B7_ERR_STATE, "eval_nominate: this context belongs to a group (b7_group_eval_nominate)");
   if (jitter_out && S > 0) std::fill(jitter_out, jitter_out + S, 0.0);
   if (info_out && S > 0) std::fill(info_out, info_out + S, 0);
+  // a property of the spec and the communicator, the same on every rank: refused before anything is enqueued and WITHOUT a
+  // collective (every rank returns here, nobody is left inside one)
+  if (spec && spec->kind == B7_SCORE_MES && c->comm && c->comm_world > 1) return mes_refuse(c, "eval_nominate", spec);
   return nominate_run(
       c, "eval_nominate", eval_validate(c, S, hyps, spec, global_row_offset), global_row_offset, (double)S,
       [&](ScoreParams *pend) { return eval_enqueue(c, S, hyps, spec, pend); },
@@ -384,6 +415,18 @@ int b7_score_ei(b7_ctx *c, const double *fmin, double tradeoff) {
 // log-space EI of the last predict, folded into the accumulator as a running log-sum-exp (score.hip's header)
 int b7_score_logei(b7_ctx *c, const double *fmin, double tradeoff) {
   return score_entry(c, "score_logei", b7_score_spec{B7_SCORE_LOGEI, tradeoff, 0, 0.0, fmin});
+}
+
+// max-value entropy search of the last predict: the y* search (K = b7_mes_set_levels' value), then score:add (score.hip's header)
+int b7_score_mes(b7_ctx *c) {
+  if (!c) return B7_ERR_INVALID;
+  const b7_score_spec spec{B7_SCORE_MES, 0.0, 0, 0.0, nullptr};
+  B7_TRY(score_ready(c, "score_mes"));
+  B7_TRY(mes_refuse(c, "score_mes", &spec));
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(mes_begin(c, 1, c->M, c->mes_levels));
+  c->mes_slot = 0;
+  return score_add(c, &spec, nullptr);
 }
 
 int b7_score_cb(b7_ctx *c, double tradeoff, int upper, double sign) {

@@ -33,6 +33,16 @@
 // c > 1 response columns are the same fold over the columns of a row, then - log(c); score:div becomes a - log(divisor), the
 // log taken here.
 //
+// Max-value entropy search (B7_SCORE_MES) has NO counterpart in the reference's scores/ either (Wang & Jegelka, "Max-value Entropy
+// Search for Efficient Bayesian Optimization", ICML 2017).  The library minimises, so the paper's maximum is the MINIMUM y*: with
+// K quantiles y*_k of the grid minimum's distribution under a hyper sample (mes.hip finds them; they arrive as ScoreParams::ystar),
+//   g_k = (mu - y*_k)/sigma,   h(g) = g phi(g)/(2 Phi(g)) - log Phi(g),   score = (1/K) sum_k h(g_k)        (mes_math.h)
+// fmin, tradeoff, upper and sign are ignored; the accumulator is linear, as EI's, each sample with its own K values.  Row classes:
+//   bad    mu or var NaN, or var < 0     NaN (the first NaN wins the arg-max, as everywhere)
+//   exact  var == 0                      exactly 0.0 (nothing is left to learn there)
+// A y* found by the search keeps g >= -Phi^-1(1 - 1/(2K)) >= -2.5; with a caller's y* (b7_mes_compute) the accuracy bar holds for
+// g >= -8 and the value stays finite below.
+//
 // Every score kind is written ONCE, as the per-kind pieces below (hoist / value / row_sign over the accumulator algebra empty / fold /
 // div); the per-sample kernel, the S-batch kernel and the fused nomination kernel are templates over the kind that only arrange
 // those pieces, which is what makes the one-call nomination equal the per-sample loop bit for bit.
@@ -40,6 +50,7 @@
 #include <type_traits>
 
 #include "b7_internal.h"
+#include "mes_math.h"
 
 namespace {
 
@@ -100,6 +111,15 @@ __device__ __forceinline__ double b7_logaddexp(double a, double v) {
   if (m == -INFINITY || n == INFINITY) return m;  // both -inf, both +inf: n - m would be NaN
   return m + log1p(exp(n + (-m)));
 }
+// ---- max-value entropy search (see the header): y = the sample's nlev quantiles of the grid minimum ----
+__device__ __forceinline__ double b7_mes(double mu, double var, const double *__restrict__ y, int nlev) {
+  if (!(var >= 0.0) || mu != mu) return NAN;
+  if (var == 0.0) return 0.0;
+  const double sigma = sqrt(var);
+  double a = 0.0;
+  for (int k = 0; k < nlev; ++k) a = a + b7_mes_h((mu + (-y[k])) / sigma);
+  return a / (double)nlev;
+}
 // ---- a score kind K (B7_SCORE_*), once.  The accumulator algebra follows score_acc_kind(K): a linear sum or a log-sum-exp ----
 template <int K>
 __device__ __forceinline__ double empty() {  // torch.zeros (bots/bayesopt.lua:69); log: the empty log-sum-exp
@@ -116,16 +136,16 @@ __device__ __forceinline__ double div(double a, double divisor) {  // score:div,
   if constexpr (score_acc_kind(K) == B7_ACC_LOG) return a + (-log(divisor));
   else return a / divisor;
 }
-// what a candidate's variance contributes to every response column: sigma (EI), sqrt(var) * kappa (CB), the variance itself (LogEI)
+// what a candidate's variance contributes to every response column: sigma (EI), sqrt(var) * kappa (CB), the variance itself (LogEI, MES)
 template <int K>
 __device__ __forceinline__ double hoist(double var, const ScoreParams &p) {
   if constexpr (K == B7_SCORE_EI) return sqrt(var);
   else if constexpr (K == B7_SCORE_CB) return sqrt(var) * p.tradeoff;
   else return var;
 }
-// one candidate, one response column; h = hoist<K>(var)
+// one candidate, one response column of hyper sample s; h = hoist<K>(var)
 template <int K>
-__device__ __forceinline__ double value(double mu, double h, double fmin, const ScoreParams &p) {
+__device__ __forceinline__ double value(double mu, double h, double fmin, const ScoreParams &p, int s) {
   if constexpr (K == B7_SCORE_EI) {
     double imprv = (fmin + (-mu)) + (-p.tradeoff);
     double z = imprv / h;
@@ -133,6 +153,8 @@ __device__ __forceinline__ double value(double mu, double h, double fmin, const 
     return (ei < 0.0) ? 0.0 : ei;
   } else if constexpr (K == B7_SCORE_CB) {
     return p.upper ? (mu + h) : (mu + (-h));
+  } else if constexpr (K == B7_SCORE_MES) {
+    return b7_mes(mu, h, p.ystar + (long long)s * p.nlev, p.nlev);
   } else {
     return b7_logei(mu, h, fmin, p.tradeoff);
   }
@@ -156,10 +178,10 @@ __global__ void __launch_bounds__(256) score_kernel(ScoreParams p, int64_t M, in
     const double h = hoist<K>(p.var[j], p);
     double row;
     if (c == 1) {
-      row = value<K>(p.mu[j], h, fmin_of(p, 0), p);
+      row = value<K>(p.mu[j], h, fmin_of(p, 0), p, 0);
     } else {
       row = empty<K>();
-      for (int k = 0; k < c; ++k) row = fold<K>(row, value<K>(p.mu[j * c + k], h, fmin_of(p, k), p));
+      for (int k = 0; k < c; ++k) row = fold<K>(row, value<K>(p.mu[j * c + k], h, fmin_of(p, k), p, 0));
       row = div<K>(row, (double)c);
     }
     row = row_sign<K>(row, p);
@@ -173,7 +195,7 @@ template <int K>
 __device__ __forceinline__ double fold_samples(const ScoreParams &p, int64_t j, double a) {
   for (int s = 0; s < p.S; ++s) {
     const double m = p.mu[s * p.stride + j], h = hoist<K>(p.var[s * p.stride + j], p);
-    a = fold<K>(a, row_sign<K>(value<K>(m, h, fmin_of(p, 0), p), p));
+    a = fold<K>(a, row_sign<K>(value<K>(m, h, fmin_of(p, 0), p, s), p));
   }
   return a;
 }
@@ -420,6 +442,7 @@ static void with_score_kind(int kind, F f) {
   switch (kind) {
     case B7_SCORE_EI: return f(std::integral_constant<int, B7_SCORE_EI>());
     case B7_SCORE_LOGEI: return f(std::integral_constant<int, B7_SCORE_LOGEI>());
+    case B7_SCORE_MES: return f(std::integral_constant<int, B7_SCORE_MES>());
     default: return f(std::integral_constant<int, B7_SCORE_CB>());
   }
 }

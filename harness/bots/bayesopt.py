@@ -10,7 +10,9 @@ synchronisation instead of one per sample (config.bot.fused, default True).
 config.score.type picks the score from bot7_amd.scores.registry and every path below takes whatever it names: the registry's
 'log_expected_improvement' (log-space EI, not in the reference) travels as score="logei" in the device spec -- fused, sharded and
 group nominations alike -- and as b7_score_logei in the per-sample loop, where score_finish's division is the log accumulator's
-subtraction of log(nSamples)."""
+subtraction of log(nSamples).  'max_value_entropy_search' (not in the reference either) travels as score="mes" with its
+level count (config.score.nLevels) and as b7_score_mes in the per-sample loop, each hyper sample with its own y* search on the
+device; on one GPU only -- a sharded candidate set or a batch (config.bot.batch > 1) answers "unsupported"."""
 import numpy as np
 
 from .abstract import abstract

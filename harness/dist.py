@@ -134,6 +134,8 @@ class ShardedScorer(object):
         rehearsal runs the separate entry points and exchanges through torch.distributed."""
         if self.ctx.comm_info()[1] == self.world:
             return self.ctx.eval_nominate(hyps, global_row_offset=self.lo, **spec)
+        if spec["score"] == "mes":   # y* is the minimum over the WHOLE grid: per-shard values would not be the score
+            raise NotImplementedError("max_value_entropy_search over a sharded candidate set is not built")
         if self.hi > self.lo:
             for s, h in enumerate(hyps):
                 self.ctx.gp_predict_hyp(h["lenscale_sq"], h["amp"], h["noise"], h["mean"])

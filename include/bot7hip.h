@@ -270,6 +270,39 @@ int b7_score_cb(b7_ctx *ctx, double tradeoff, int upper, double sign);
  * mean of the logs; ycols > 1 (fantasies): the log of the row mean of EI.  The first add after b7_score_reset decides
  * whether the accumulator is linear (b7_score_ei / _cb) or logarithmic; adding the other kind onto it is B7_ERR_STATE. */
 int b7_score_logei(b7_ctx *ctx, const double *fmin, double tradeoff);
+/* Max-value entropy search of the last predict -- NO counterpart in scores/ of the reference (Wang & Jegelka, "Max-value
+ * Entropy Search for Efficient Bayesian Optimization", ICML 2017): the expected reduction of the entropy of the optimum's VALUE.
+ * The library minimises, so the paper's maximum is the minimum y*, and its distribution is that of the minimum over the
+ * resident candidates themselves (independent candidates, as in the paper): no sampler, no joint posterior, no random numbers,
+ * and no clamp to the incumbent.  Rows of the last predict (mu_j, var_j):
+ *   bad    mu or var NaN, or var < 0    score NaN (the first NaN wins the arg-max, as everywhere)
+ *   exact  var == 0                     score exactly 0.0
+ *   live   the rest, sigma_j = sqrt(var_j); only these take part in the search
+ * Search: L(y) = sum_live log Phi((mu_j - y)/sigma_j); y*_k (k = 1..K) is the root of L(y) = log1p(-(k - 1/2)/K), bracketed by
+ * lo0 = min_j(mu_j - 10 sigma_j), hi0 = min_j(mu_j + 10 sigma_j) -- s = sqrt(var); t = s * 10; mu - t; mu + t, one rounded operation
+ * each, then the minimum, so lo0 / hi0 do not depend on the decomposition -- and narrowed by 10 rounds of 15 interior probes
+ * y_p = lo + (hi - lo) p/16 to 16^-10 of the bracket; y*_k is the last bracket's midpoint.  11 launches, no host round trip,
+ * bit-reproducible.  No live row: every y*_k is NaN.
+ * Score: with g_k = (mu_j - y*_k)/sigma_j and h(g) = g phi(g)/(2 Phi(g)) - log Phi(g),  score_j = (1/K) sum_k h(g_k), added into
+ * the (linear) accumulator like b7_score_ei; the marginal over hyper samples is the mean, each sample with its own y*.
+ * One response column only (fantasies: B7_ERR_UNSUPPORTED), and no communicator of more than one rank (y* over a sharded grid
+ * needs an all-reduce per round: B7_ERR_UNSUPPORTED).  After b7_blr_predict it scores the DNGO head's posterior.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_MES_KMAX 64
+int b7_score_mes(b7_ctx *ctx);
+/* K of the searches that b7_score_mes and a B7_SCORE_MES nomination start: default 8; outside 1..B7_MES_KMAX: B7_ERR_INVALID. */
+int b7_mes_set_levels(b7_ctx *ctx, int K);
+/* y* of the last search on this context (b7_score_mes: S = 1; a B7_SCORE_MES nomination: its S samples in order):
+ * ystar S x K (nullable), bracket S x 2 = lo0, hi0 per sample (nullable).  B7_ERR_STATE when no search has run. */
+int b7_mes_last_ystar(b7_ctx *ctx, int *S, int *K, double *ystar, double *bracket);
+/* The search alone on caller-provided host vectors (M mean, M var): ystar[K], bracket[2] = lo0, hi0 (nullable).  It IS a search
+ * on this context: afterwards b7_mes_last_ystar reports this one (S = 1, this K), not an earlier nomination's. */
+int b7_mes_ystar(b7_ctx *ctx, const double *mean, const double *var, int64_t M, int K, double *ystar, double *bracket);
+/* The score alone, with the caller's y*[K]: out[j] = (1/K) sum_k h((mean_j - ystar_k)/sigma_j), row classes as above.  Domain:
+ * within 1e-13 max(1, |h|) of exact arithmetic for g >= -8 (a searched y* keeps g >= -2.5); below that the same form -- phi/Phi
+ * through erfcx -- stays finite but is not held to that bar.  The caller's y* is kept apart from the context's own: the
+ * last search's values (b7_mes_last_ystar) are untouched. */
+int b7_mes_compute(b7_ctx *ctx, const double *mean, const double *var, const double *ystar, int K, int64_t M, double *out);
 /* bots/bayesopt.lua:79 score:div(nSamples) then :96 score:max(1): best_val and the 1-based index of the
  * first maximum (first NaN wins, as TH's max).  divisor = 1 skips nothing: x/1 is exact.
  * scores_host nullable (M).  On a log accumulator (b7_score_logei) score:div is a - log(divisor), and best_val /
@@ -360,6 +393,15 @@ int b7_exchange_info(b7_ctx *ctx, int *world, int64_t *rows_per_rank, int64_t *w
  * eval + nominate entry point (b7_eval_nominate, b7_group_eval_nominate, b7_blr_eval_nominate, b7_blr_eval_nominate_marg).
  * Added without a change of B7_ABI_VERSION: the change is additive. */
 #define B7_SCORE_LOGEI 3
+/* Max-value entropy search, as b7_score_mes: no counterpart in scores/ of the reference (Wang & Jegelka, ICML 2017).  fmin,
+ * tradeoff, upper and sign are ignored.  Accepted by b7_eval_nominate on one rank and one response column: every sample's y*
+ * search runs on the device ahead of its score, on every route of the call, the jitter redo included, and equals the loop
+ * { b7_gp_predict_hyp; b7_score_mes } x S + b7_score_finish(S) bit for bit (b7_mes_last_ystar gives the S x K values of y*).
+ * B7_ERR_UNSUPPORTED, each with a message naming the case: a communicator of more than one rank and b7_group_eval_nominate
+ * (y* over a sharded grid), b7_blr_eval_nominate and b7_blr_eval_nominate_marg (b7_blr_predict + b7_score_mes works),
+ * b7_eval_nominate_batch, more than one response column.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_SCORE_MES 4
 typedef struct {
   int kind;
   double tradeoff;

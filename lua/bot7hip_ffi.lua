@@ -57,6 +57,11 @@ int b7_score_reset(b7_ctx *ctx);
 int b7_score_ei(b7_ctx *ctx, const double *fmin, double tradeoff);
 int b7_score_cb(b7_ctx *ctx, double tradeoff, int upper, double sign);
 int b7_score_logei(b7_ctx *ctx, const double *fmin, double tradeoff);
+int b7_score_mes(b7_ctx *ctx);
+int b7_mes_set_levels(b7_ctx *ctx, int K);
+int b7_mes_last_ystar(b7_ctx *ctx, int *S, int *K, double *ystar, double *bracket);
+int b7_mes_ystar(b7_ctx *ctx, const double *mean, const double *var, int64_t M, int K, double *ystar, double *bracket);
+int b7_mes_compute(b7_ctx *ctx, const double *mean, const double *var, const double *ystar, int K, int64_t M, double *out);
 int b7_score_finish(b7_ctx *ctx, double divisor, double *best_val, int64_t *best_idx1, double *scores_host);
 int b7_comm_unique_id(void *id_out);
 int b7_comm_init(b7_ctx *ctx, int rank, int world, const void *id);
@@ -122,6 +127,7 @@ M.ERR_RANGE = -6
 M.ERR_COMM = -7
 M.KERNEL_ARDSE = 0
 M.KERNEL_MATERN52 = 1
+M.MES_KMAX = 64
 M.COMM_ID_BYTES = 128
 M.COMM_SUM = 0
 M.COMM_MAX = 1
@@ -129,6 +135,7 @@ M.COMM_MIN = 2
 M.SCORE_EI = 1
 M.SCORE_CB = 2
 M.SCORE_LOGEI = 3
+M.SCORE_MES = 4
 M.BATCH_MAX = 16
 M.MAX_TIMERS = 16
 -- END generated constants

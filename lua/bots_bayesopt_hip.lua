@@ -40,6 +40,9 @@ local function score_spec(score, Y_obs, keep)
     keep[#keep + 1] = fmins
     local code = (kind == 'bot7.scores.expected_improvement_hip') and hip.SCORE_EI or hip.SCORE_LOGEI   -- log-space EI: no original
     return ffi.new('b7_score_spec', {code, cfg.tradeoff or 0.0, 0, 0.0, hip.data(fmins)})
+  elseif kind == 'bot7.scores.max_value_entropy_search_hip' then   -- no original; one GPU only (a sharded grid answers "unsupported")
+    hip.check(hip.C.b7_mes_set_levels(hip.ctx, cfg.nLevels or 8))
+    return ffi.new('b7_score_spec', {hip.SCORE_MES, 0.0, 0, 0.0, nil})
   elseif kind == 'bot7.scores.confidence_bound_hip' then
     local upper = (string.lower(cfg.bound or 'lower') == 'upper') and 1 or 0   -- scores/confidence_bound.lua:72
     return ffi.new('b7_score_spec', {hip.SCORE_CB, cfg.tradeoff or 1.0, upper, cfg.sign or -1.0, nil})

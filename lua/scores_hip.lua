@@ -2,6 +2,7 @@
 Drop-ins for bot7.scores.expected_improvement / confidence_bound (scores/*.lua) backed by b7_score_*.
 Register:  local S = require('bot7hip.scores_hip')
            bot7.scores.expected_improvement = S.expected_improvement ; bot7.scores.confidence_bound = S.confidence_bound
+S.max_value_entropy_search has no original either (b7_score_mes; Wang & Jegelka, ICML 2017): register it as a new score.
 S.log_expected_improvement has no original to replace: log-space EI (b7_score_logei; Ament et al., NeurIPS 2023), which still
 ranks the candidates where EI has underflowed to 0.  Register it as a new score: bot7.scores.log_expected_improvement = ...
 They return the M-element score tensor like the originals (bots/bayesopt.lua:76 adds it); with a gp_hip model the
@@ -84,6 +85,31 @@ do
     return finish(X_hid:size(1))
   end
   S.log_expected_improvement = LEI
+end
+
+do
+  -- max-value entropy search (Wang & Jegelka, ICML 2017; b7_score_mes): K = config.nLevels quantiles of the grid MINIMUM's
+  -- distribution under this hyper sample are found on the device, then score = mean_k h((mu - y*_k)/sigma).  A linear score:
+  -- the host-side marginalisation (bots/bayesopt.lua:76-79) averages it as it averages EI.  No pending points: one response column
+  local MES, parent = torch.class('bot7.scores.max_value_entropy_search_hip', 'bot7.scores.abstract')
+  function MES:__init(config)
+    parent.__init(self)
+    local config = config or {}
+    config['nLevels'] = config.nLevels or 8
+    self.config = config
+  end
+  function MES:__call__(model, hyp, X_obs, Y_obs, X_hid, X_pend, config)
+    local hyp, config = hyp or model.hyp, config or self.config
+    if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
+    assert(not (torch.isTensor(X_pend) and X_pend:dim() > 0 and X_pend:size(1) > 0),
+           'max_value_entropy_search_hip: pending points (fantasies) are not supported')
+    model:predict_device(X_obs, Y_obs, X_hid, hyp)
+    hip.check(hip.C.b7_mes_set_levels(hip.ctx, config.nLevels or 8))
+    hip.check(hip.C.b7_score_reset(hip.ctx))
+    hip.check(hip.C.b7_score_mes(hip.ctx))
+    return finish(X_hid:size(1))
+  end
+  S.max_value_entropy_search = MES
 end
 
 do
