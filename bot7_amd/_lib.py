@@ -24,6 +24,7 @@ SYMBOLS = [
     "b7_gp_default_opts", "b7_gp_set_opts", "b7_gp_set_kernel", "b7_gp_fit", "b7_gp_set_data", "b7_gp_fit_hyp", "b7_gp_predict_hyp", "b7_gp_nll_batch", "b7_chol", "b7_gp_predict", "b7_gp_predict_at", "b7_gp_fantasize", "b7_gp_append", "b7_gp_download",
     "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_mes", "b7_mes_set_levels", "b7_mes_last_ystar", "b7_mes_ystar", "b7_mes_compute", "b7_score_cb", "b7_score_finish",
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_eval_nominate_batch", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
+    "b7_ts_nominate", "b7_ts_last_paths", "b7_ts_last_draws", "b7_rff_compute",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
     "b7_group_grid_sobol", "b7_group_grid_random", "b7_group_grid_onesided", "b7_group_grid_upload", "b7_group_grid_shape", "b7_group_grid_download",
@@ -162,6 +163,10 @@ def load(which=None):
         "b7_eval_nominate": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), i64, C.POINTER(dbl), C.POINTER(i64),
                                    vp, vp]),
         "b7_eval_nominate_batch": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), i32, vp, vp, vp, vp]),
+        "b7_ts_nominate": (i32, [vp, i32, C.POINTER(Hyp), i32, i32, C.c_uint64, vp, vp, vp, vp]),
+        "b7_ts_last_paths": (i32, [vp, vp]),
+        "b7_ts_last_draws": (i32, [vp, i32, vp, vp, vp, vp]),
+        "b7_rff_compute": (i32, [vp, vp, i64, i32, vp, vp, vp, i32, i32, vp]),
         "b7_blr_eval_nominate": (i32, [vp, C.POINTER(Mlp), vp, vp, i32, dbl, dbl, dbl, C.POINTER(ScoreSpec), i64, C.POINTER(dbl),
                                        C.POINTER(i64), C.POINTER(dbl)]),
         "b7_blr_eval_nominate_marg": (i32, [vp, C.POINTER(Mlp), vp, vp, i32, i32, vp, vp, vp, C.POINTER(ScoreSpec), i64, C.POINTER(dbl),
@@ -391,6 +396,7 @@ class Context(object):
                                    C.byref(jit), C.byref(info)))
         self.ycols = Y.shape[1]
         self._data_d = d
+        self._data_n = N
         self.fit_token += 1
         return {"nll": nll, "jitter": jit.value, "info": info.value}
 
@@ -404,6 +410,7 @@ class Context(object):
         self._ck(self._L.b7_gp_set_data(self._h, _ptr(X), _ptr(Y), N, d, Y.shape[1]))
         self.ycols = Y.shape[1]
         self._data_d = d
+        self._data_n = N
         self.fit_token += 1
 
     def gp_fit_hyp(self, lenscale_sq, amp, noise, mean, want_nll=False):
@@ -520,6 +527,8 @@ class Context(object):
         x = _f64(x_new).ravel()
         y = _f64(y_new).ravel()
         self._ck(self._L.b7_gp_append(self._h, _ptr(x), _ptr(y)))
+        if hasattr(self, "_data_n"):
+            self._data_n += 1
 
     def gp_download(self, N, ycols=1):
         Lh = np.empty((N, N), dtype=np.float64)
@@ -807,6 +816,51 @@ class Context(object):
         if want_report:
             return vals, idx, {"jitter": jit, "info": info}
         return vals, idx
+
+    def ts_nominate(self, hyps, q, n_features=1024, seed=0, want_report=False):
+        """Thompson sampling (b7_ts_nominate): q pathwise posterior samples over the resident data and grid, path j under hyper
+        sample j mod len(hyps), each path's first minimum among the rows no earlier path of the call took.
+        Returns (path minima[q], 1-based indices[q][, report]); the grid is not modified (commit with grid_remove_rows)."""
+        S = len(hyps)
+        arr, keep = self._pack_hyps(hyps, getattr(self, "_data_d", -1))
+        jit = np.zeros(max(S, 1), dtype=np.float64) if want_report else None
+        info = np.zeros(max(S, 1), dtype=np.int32) if want_report else None
+        n = max(int(q), 1)
+        vals, idx = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int64)
+        self._ck(self._L.b7_ts_nominate(self._h, S, arr, int(q), int(n_features), int(seed) & (2 ** 64 - 1), _ptr(vals), _ptr(idx),
+                                        _ptr(jit), _ptr(info)))
+        self.fit_token += 1
+        self._ts_shape = (self.grid_shape()[0], n, int(n_features), self._data_d, getattr(self, "_data_n", 0))   # what the inspection entries return
+        if want_report:
+            return vals, idx, {"jitter": jit[:S], "info": info[:S]}
+        return vals, idx
+
+    def ts_last_paths(self):
+        """The last ts_nominate's sample paths over the grid as it stood, M x q (b7_ts_last_paths)."""
+        M, q = getattr(self, "_ts_shape", (1, 1, 0, 0, 0))[:2]
+        out = np.empty((M, q), dtype=np.float64)
+        self._ck(self._L.b7_ts_last_paths(self._h, _ptr(out)))
+        return out
+
+    def ts_last_draws(self, path):
+        """Path `path`'s draws of the last ts_nominate: dict(omega F x d, phase F, weight F, eps N) (b7_ts_last_draws)."""
+        _, _, F, d, N = getattr(self, "_ts_shape", (1, 1, 1, 1, 1))
+        out = {"omega": np.empty((F, d), dtype=np.float64), "phase": np.empty(F, dtype=np.float64),
+               "weight": np.empty(F, dtype=np.float64), "eps": np.empty(N, dtype=np.float64)}
+        self._ck(self._L.b7_ts_last_draws(self._h, int(path), _ptr(out["omega"]), _ptr(out["phase"]), _ptr(out["weight"]), _ptr(out["eps"])))
+        return out
+
+    def rff_compute(self, X, omega, phase, W):
+        """cos(X omega' + phase) W on host arrays (b7_rff_compute): X M1 x d, omega F x d, phase F, W F x q -> M1 x q."""
+        X, omega, phase, W = _f64(X), _f64(omega), _f64(phase).ravel(), _f64(W)
+        if W.ndim == 1:
+            W = W.reshape(-1, 1)
+        if X.ndim != 2 or omega.ndim != 2 or omega.shape[1] != X.shape[1] or phase.size != omega.shape[0] or W.shape[0] != omega.shape[0]:
+            raise Bot7HipError(-1, "rff_compute: X M1 x d, omega F x d, phase F, W F x q")
+        out = np.empty((X.shape[0], W.shape[1]), dtype=np.float64)
+        self._ck(self._L.b7_rff_compute(self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(omega), _ptr(phase), _ptr(W), omega.shape[0],
+                                        W.shape[1], _ptr(out)))
+        return out
 
     def ei_compute(self, mean, var, fmin, tradeoff=0.0):
         mean = _f64(mean)

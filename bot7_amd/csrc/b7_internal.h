@@ -231,6 +231,14 @@ struct b7_ctx {
   DevBuf bel;     // mu [S][M] | var [S][M] | u [q-1][S][M]
   DevBuf belvec;  // per sample: k(X, x_j) [Npad] | w_j = inv(K) k(X, x_j) [Npad] | amp, noise + jitter | t_j, u_i(x_j) (i < j)
   PinBuf pin_bel; // amp, noise + jitter of the S samples on their way to belvec (not mapped)
+  // ---- b7_ts_nominate (rff.hip): the last call's sample paths and draws (b7_ts_last_paths / _draws), one hyper sample's operands,
+  // and b7_rff_compute's staging, apart from them
+  DevBuf ts_paths;  // [M][q]
+  DevBuf ts_draw;   // omega [min(S, q)][F][d] | phase [F] | weight [q][F] | eps [q][N]
+  DevBuf ts_work, ts_user;
+  bool ts_valid = false;  // a b7_ts_nominate has succeeded; the shapes of what it left:
+  int64_t ts_M = 0;
+  int ts_q = 0, ts_S = 0, ts_F = 0, ts_N = 0, ts_d = 0;
   DevBuf feat;   // DNGO basis features of the resident grid: Mfeat x Npad (zero-padded columns)
   size_t feat_zeroed_bytes = 0;  // how much of `feat` was zeroed when it was laid out for feat_z columns
   int feat_z = -1;

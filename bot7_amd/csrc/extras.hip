@@ -11,6 +11,7 @@
 #include "b7_internal.h"
 #include <stdlib.h>
 
+#include "counter_rng.h"
 #include "gemm_f64.h"
 #include "exp_table.h"
 #ifndef B7_MLP_ABLATE
@@ -75,20 +76,6 @@ __global__ void fantasy_cov_kernel(const double *__restrict__ kpp, const double 
 __global__ void add_diag_kernel(double *__restrict__ S, int ld, int n, double v) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) S[(int64_t)i * ld + i] += v;
-}
-
-__device__ inline uint64_t splitmix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-// z(k, s) ~ N(0,1): Box-Muller on two counter-based uniforms; u1 in (0, 1]
-__device__ inline double counter_normal(uint64_t seed, uint64_t ctr) {
-  const uint64_t a = splitmix64(seed + 0x9E3779B97F4A7C15ull * (2 * ctr + 1));
-  const uint64_t b = splitmix64(seed + 0x9E3779B97F4A7C15ull * (2 * ctr + 2));
-  const double u1 = (double)((a >> 11) + 1) * 1.1102230246251565404e-16;
-  const double u2 = (double)(b >> 11) * 1.1102230246251565404e-16;
-  return sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925 * u2);
 }
 
 // out[i][s] = mu[i] + sum_{k <= i} Lp[i][k] z(k, s)

@@ -12,7 +12,9 @@ config.score.type picks the score from bot7_amd.scores.registry and every path b
 group nominations alike -- and as b7_score_logei in the per-sample loop, where score_finish's division is the log accumulator's
 subtraction of log(nSamples).  'max_value_entropy_search' (not in the reference either) travels as score="mes" with its
 level count (config.score.nLevels) and as b7_score_mes in the per-sample loop, each hyper sample with its own y* search on the
-device; on one GPU only -- a sharded candidate set or a batch (config.bot.batch > 1) answers "unsupported"."""
+device; on one GPU only -- a sharded candidate set or a batch (config.bot.batch > 1) answers "unsupported".
+'thompson_sampling' (not in the reference) is not a per-point score: nominate and nominate_batch, q = 1 included, go through
+b7_ts_nominate with a seed from the bot's own generator, and eval(want_scores=True) raises -- there is no score vector."""
 import numpy as np
 
 from .abstract import abstract
@@ -54,6 +56,11 @@ class bayesopt(abstract):
         X_obs, Y_obs = self.observed, self.responses
         X_hid = self.candidates if candidates is None else candidates
         model, ctx = self.model, self.model.ctx
+        if self._thompson():
+            if want_scores:
+                raise NotImplementedError("thompson_sampling has no score vector (eval with want_scores=False, or nominate)")
+            idx = self._ts_nominate(1, X_hid)[0]
+            return None, None, idx
         if model.class_() == "bot7.models.dngo":                  # :65-66: one score call, no marginalisation loop
             model.predict_device(X_obs, Y_obs, X_hid, None)
             ctx.score_reset()
@@ -94,6 +101,24 @@ class bayesopt(abstract):
         self.last_scores = scores
         return scores, val, idx
 
+    def _thompson(self):
+        return self.config["score"]["type"] == "thompson_sampling"
+
+    def _ts_nominate(self, q, cand):
+        """q nominees by Thompson sampling (b7_ts_nominate): the hyper samples as eval's fused branch draws them
+        (bots/bayesopt.lua:68, :73-75), the call's seed from the bot's own generator."""
+        X_obs, Y_obs, model = self.observed, self.responses, self.model
+        assert hasattr(model, "stage") and model.class_() != "bot7.models.dngo" and not hasattr(cand, "commit"), \
+            "thompson_sampling: a GP model on one GPU (sharded Thompson sampling is not built)"
+        model.sample_hypers(X_obs, Y_obs)                         # :68 (burn-in call)
+        hyps = [model.parse_hypers(model.sample_hypers(X_obs, Y_obs, None, None, True))
+                for _ in range(self.config["bot"]["nSamples"])]   # :73-75
+        model.stage(X_obs, Y_obs, cand)
+        seed = int(self._rng.integers(0, 2 ** 63))
+        idx = self.score.nominate(model.ctx, hyps, q, seed)
+        self.last_scores = None
+        return [int(i) for i in idx]
+
     def nominate(self, candidates=None):
         """bots/bayesopt.lua:85-99."""
         cand = self.candidates if candidates is None else candidates
@@ -112,6 +137,8 @@ class bayesopt(abstract):
             return [int(self.nominate(cand))]
         if self.nTrials <= self.config["bot"]["nInitial"]:        # :90-91, q distinct rows
             return [int(i) + 1 for i in self._rng.choice(cand.shape[0], size=q, replace=False)]
+        if self._thompson():
+            return self._ts_nominate(q, cand)
         X_obs, Y_obs, model = self.observed, self.responses, self.model
         spec = getattr(self.score, "device_spec", None)
         assert spec is not None and hasattr(model, "stage") and not hasattr(cand, "commit"), \

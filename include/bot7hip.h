@@ -437,6 +437,48 @@ int b7_eval_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec
 int b7_eval_nominate_batch(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int q, double *best_val /*q*/,
                            int64_t *best_idx1 /*q*/, double *jitter_out, int *info_out);
 
+/* THOMPSON SAMPLING: q nominees from q pathwise (decoupled) posterior samples.  No counterpart in the reference; Wilson,
+ * Borovitskiy, Terenin, Mostowsky, Deisenroth (ICML 2020).  A sample path of the posterior is
+ *   f_j(x) = m + phi(x)' w_j + K(x, X) v_j,        v_j = inv(K) (y - m - Phi(X) w_j - eps_j)
+ * phi: F random Fourier features of the prior, phi(x)[f] = sqrt(2 amp / F) cos(Omega[f] . x + phase[f]); w_j ~ N(0, I);
+ * eps_j ~ N(0, noise I) with the hyper sample's own noise (not the jitter its factorisation may add).  No M x M covariance is
+ * formed: the update term is the posterior mean of a fit whose response columns are the pseudo-responses, the prior term one
+ * kernel over the grid that never stores Phi.  Runs over the resident data (b7_gp_set_data, one response column) and grid.
+ *   hyper samples  path j is drawn under hyper sample j mod S (Thompson sampling over hypers and function at once): min(S, q)
+ *                  factorisations; hyper samples beyond the q-th are unused and report jitter 0, info 0.
+ *   draws          from the library's counter generator (splitmix64 -> Box-Muller, as b7_gp_fantasize).  The basis (the normals
+ *                  behind Omega, Matern's chi-square, the phases) is one per seed and shared by the call's paths; weight and eps are
+ *                  path j's own.  Everything depends on (seed, j) alone: the paths of a q = 3 call are the first three of a q = 5
+ *                  call.  ARD-SE: Omega[f][k] = z / sqrt(lenscale_sq[k]); ARD Matern-5/2: z sqrt(5 / u_f) / sqrt(lenscale_sq[k]),
+ *                  u_f a sum of five squared normals (the spectral density is a multivariate t with 5 degrees of freedom).
+ *   arg-mins       paths in order j = 0 .. q-1; path j takes its first minimum over the rows NOT TAKEN BY AN EARLIER PATH of this
+ *                  call (two paths often share their minimiser); a NaN does not win; path_min[j] is the path's value at the row it
+ *                  took, best_idx1[j] that row, 1-based.
+ * jitter_out / info_out: nullable, S entries, as b7_eval_nominate's; a failed pivot goes through utils.math.chol's jitter schedule.
+ * Deterministic: the same call twice gives the same bits.  The grid is not modified (commit with b7_grid_remove_rows); the
+ * context's fit slot holds none of the samples afterwards; the score accumulator is untouched.
+ * B7_ERR_INVALID: q outside 1..B7_BATCH_MAX or q > the grid's rows; F outside 16..B7_TS_MAX_FEATURES or not a multiple of 16;
+ * S < 1; NULL arguments.  B7_ERR_UNSUPPORTED, the case named: more than one response column, a communicator of more than one
+ * rank.  B7_ERR_STATE: a member of a group (as b7_eval_nominate_batch answers), no resident data or grid.
+ * Device memory beside the posterior's own buffers: M q doubles for the paths (plus the draws, min(S, q) F d + (q + 1) F + q N, and
+ * one hyper sample's operands), allocated on demand (B7_ERR_NOMEM) and freed with the context.
+ * Not built: sharded grids and groups, the Bayesian-linear head, more than one response column, a one-launch variant for N <= 128.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_TS_MAX_FEATURES 4096
+int b7_ts_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *path_min /*q*/,
+                   int64_t *best_idx1 /*q*/, double *jitter_out /*S*/, int *info_out /*S*/);
+/* Inspection (tests): the last successful b7_ts_nominate's paths over the grid, M x q row-major, and path `path`'s draws -- omega
+ * (F x d, under its hyper sample's lengthscales), phase (F), weight (F, before the sqrt(2 amp / F) scale), eps (N); each nullable.
+ * B7_ERR_STATE before a successful b7_ts_nominate. */
+int b7_ts_last_paths(b7_ctx *ctx, double *paths_host /* M x q */);
+int b7_ts_last_draws(b7_ctx *ctx, int path, double *omega /*F x d*/, double *phase /*F*/, double *weight /*F*/, double *eps /*N*/);
+/* The feature kernel alone on host arrays (the b7_ei_compute of Thompson sampling): out = cos(X omega' + phase) W, M1 x q.
+ * d in 1..96, q in 1..B7_BATCH_MAX, F a multiple of 16 in 16..B7_TS_MAX_FEATURES.  Its cosine reduces the argument in two
+ * fused steps: accurate to ~1e-16 absolute for |argument| up to ~1e6, which unit-cube inputs over any admissible lengthscale stay
+ * far inside. */
+int b7_rff_compute(b7_ctx *ctx, const double *X /*M1 x d*/, int64_t M1, int d, const double *omega /*F x d*/,
+                   const double *phase /*F*/, const double *W /*F x q*/, int F, int q, double *out /*M1 x q*/);
+
 /* bayesopt:eval's DNGO branch + nominate as ONE call (bots/bayesopt.lua:65-66, :96 over models/dngo.lua:155-175):
  * b7_blr_fit_x(net, X0, Y0, ...) + b7_blr_basis(net, resident grid) + b7_blr_predict + the acquisition of `spec` (written,
  * not accumulated: ONE point (alpha_prec, beta, mean); b7_blr_eval_nominate_marg below marginalises over S of them) +

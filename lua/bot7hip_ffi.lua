@@ -76,6 +76,10 @@ int b7_exchange_info(b7_ctx *ctx, int *world, int64_t *rows_per_rank, int64_t *w
 typedef struct { int kind; double tradeoff; int upper; double sign; const double *fmin; } b7_score_spec;
 int b7_eval_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out);
 int b7_eval_nominate_batch(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int q, double *best_val , int64_t *best_idx1 , double *jitter_out, int *info_out);
+int b7_ts_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *path_min , int64_t *best_idx1 , double *jitter_out , int *info_out );
+int b7_ts_last_paths(b7_ctx *ctx, double *paths_host );
+int b7_ts_last_draws(b7_ctx *ctx, int path, double *omega , double *phase , double *weight , double *eps );
+int b7_rff_compute(b7_ctx *ctx, const double *X , int64_t M1, int d, const double *omega , const double *phase , const double *W , int F, int q, double *out );
 int b7_blr_eval_nominate(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, double alpha_prec, double beta, double mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *jitter_used);
 int b7_blr_eval_nominate_marg(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *alpha_prec, const double *beta, const double *mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *nll_out, double *jitter_used);
 typedef struct b7_group b7_group;
@@ -137,6 +141,7 @@ M.SCORE_CB = 2
 M.SCORE_LOGEI = 3
 M.SCORE_MES = 4
 M.BATCH_MAX = 16
+M.TS_MAX_FEATURES = 4096
 M.MAX_TIMERS = 16
 -- END generated constants
 

@@ -50,6 +50,36 @@ local function score_spec(score, Y_obs, keep)
   return nil
 end
 
+-- Thompson sampling (b7_ts_nominate; no original): q pathwise posterior samples, path j under hyper sample j mod S, each path's
+-- first minimum among the rows no earlier path took.  The seed comes from torch's generator, once per call.  One rank, no group.
+-- Returns a LongTensor of q indices into `candidates` as it stands.
+local function ts_nominate(self, q, candidates)
+  assert(D.world == 1 and not hip.group, 'thompson_sampling: one rank, no group (sharded Thompson sampling is not built)')
+  local model, keep = self.model, {}
+  assert(torch.type(model) == 'bot7.models.gp_hip', 'thompson_sampling: needs the gp_hip model')
+  local Y_obs = self.responses
+  if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
+  local X_obs, S = self.observed, self.config.bot.nSamples
+  model:sample_hypers(X_obs, Y_obs)                                          -- :68
+  local hyps = ffi.new('b7_hyp[?]', S)
+  for s = 1, S do                                                            -- :73-75
+    local hyp = model:parse_hypers(model:sample_hypers(X_obs, Y_obs, nil, nil, true))
+    local ls  = hip.pin(hyp.lenscale_sq)
+    keep[#keep + 1] = ls
+    hyps[s-1].lenscale_sq, hyps[s-1].amp, hyps[s-1].noise, hyps[s-1].mean = hip.data(ls), hyp.amp, hyp.noise, hyp.mean
+  end
+  model:stage(X_obs, Y_obs, candidates)
+  hip.set_kernel(model.kernel_code)
+  local seed = ffi.new('uint64_t', torch.random())
+  local v, i = ffi.new('double[?]', q), ffi.new('int64_t[?]', q)
+  local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+  hip.check(hip.C.b7_ts_nominate(hip.ctx, S, hyps, q, (self.score.config or {}).nFeatures or 1024, seed, v, i, jit, info))
+  local out = torch.LongTensor(q)
+  for k = 0, q - 1 do out[k + 1] = tonumber(i[k]) end
+  self.best_score = v[0]
+  return out
+end
+
 function bot:nominate(candidates)
   local candidates = candidates or self.candidates
   if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91
@@ -57,6 +87,7 @@ function bot:nominate(candidates)
     local rows = (D.world > 1) and assert(D.M_global, 'dist_hip.shard_range first') or candidates:size(1)
     return torch.rand(1):mul(rows):long():add(1)
   end
+  if torch.type(self.score) == 'bot7.scores.thompson_sampling_hip' then return ts_nominate(self, 1, candidates) end
   local model, keep = self.model, {}
   local Y_obs = self.responses
   if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
@@ -107,6 +138,7 @@ function bot:nominate_batch(q, candidates)
   if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91, q distinct rows
     return torch.randperm(candidates:size(1)):narrow(1, 1, q):long()
   end
+  if torch.type(self.score) == 'bot7.scores.thompson_sampling_hip' then return ts_nominate(self, q, candidates) end
   local model, keep = self.model, {}
   local Y_obs = self.responses
   if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end

@@ -113,6 +113,23 @@ do
 end
 
 do
+  -- Thompson sampling (b7_ts_nominate; no original): not a per-point score.  The class only carries config.nFeatures to
+  -- bots_bayesopt_hip.lua, whose nominate / nominate_batch call the library in place of eval + arg-max.  Checked by the static
+  -- checker only (no LuaJIT / Torch7 in the pipeline).
+  local TS, parent = torch.class('bot7.scores.thompson_sampling_hip', 'bot7.scores.abstract')
+  function TS:__init(config)
+    parent.__init(self)
+    local config = config or {}
+    config['nFeatures'] = config.nFeatures or 1024
+    self.config = config
+  end
+  function TS:__call__(model, hyp, X_obs, Y_obs, X_hid, X_pend, config)
+    error('thompson_sampling_hip is not a per-point score: nominate through bot7.bots.bayesopt_hip (b7_ts_nominate)')
+  end
+  S.thompson_sampling = TS
+end
+
+do
   local CB, parent = torch.class('bot7.scores.confidence_bound_hip', 'bot7.scores.abstract')
   function CB:__init(config)
     parent.__init(self)
