@@ -21,7 +21,7 @@ SYMBOLS = [
     "b7_abi_version", "b7_create", "b7_destroy", "b7_last_error", "b7_device_info", "b7_sync", "b7_set_workspace",
     "b7_sobol_direction_numbers", "b7_grid_sobol", "b7_grid_random", "b7_grid_upload", "b7_grid_download", "b7_grid_shape", "b7_grid_remove", "b7_grid_remove_rows",
     "b7_grid_colrange", "b7_grid_apply_onesided", "b7_grid_random_torch", "b7_torch_rand",
-    "b7_gp_default_opts", "b7_gp_set_opts", "b7_gp_set_kernel", "b7_gp_fit", "b7_gp_set_data", "b7_gp_fit_hyp", "b7_gp_predict_hyp", "b7_gp_nll_batch", "b7_chol", "b7_gp_predict", "b7_gp_predict_at", "b7_gp_fantasize", "b7_gp_append", "b7_gp_download",
+    "b7_gp_default_opts", "b7_gp_set_opts", "b7_gp_set_kernel", "b7_gp_fit", "b7_gp_set_data", "b7_gp_fit_hyp", "b7_gp_predict_hyp", "b7_gp_nll_batch", "b7_gp_slice_sample", "b7_gp_slice_trace_enable", "b7_gp_slice_trace", "b7_chol", "b7_gp_predict", "b7_gp_predict_at", "b7_gp_fantasize", "b7_gp_append", "b7_gp_download",
     "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_mes", "b7_mes_set_levels", "b7_mes_last_ystar", "b7_mes_ystar", "b7_mes_compute", "b7_score_cb", "b7_score_finish",
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_eval_nominate_batch", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
     "b7_ts_nominate", "b7_ts_last_paths", "b7_ts_last_draws", "b7_rff_compute",
@@ -51,6 +51,9 @@ class ScoreSpec(C.Structure):
 
 
 SCORE_EI, SCORE_CB, SCORE_LOGEI, SCORE_MES = 1, 2, 3, 4
+# b7_gp_slice_sample: the trace's record width and the status bits of an update
+SLICE_TRACE_WIDTH = 136
+SLICE_NAN, SLICE_ZERO, SLICE_CAP, SLICE_PIVOT, SLICE_NOT_RUN = 1, 2, 4, 8, 16
 MES_KMAX = 64
 
 # covariance kernels (b7_gp_set_kernel): config.model.kernel names (bots/bayesopt.lua:41) -> B7_KERNEL_*
@@ -132,6 +135,9 @@ def load(which=None):
         "b7_gp_fit_hyp": (i32, [vp, C.POINTER(Hyp), vp, C.POINTER(dbl), C.POINTER(i32)]),
         "b7_gp_predict_hyp": (i32, [vp, C.POINTER(Hyp), vp, vp, vp, C.POINTER(dbl), C.POINTER(i32)]),
         "b7_gp_nll_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "b7_gp_slice_sample": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, C.c_uint64, C.c_uint64, vp, vp, vp, vp]),
+        "b7_gp_slice_trace_enable": (i32, [vp, i32]),
+        "b7_gp_slice_trace": (i32, [vp, i32, vp, C.POINTER(i32)]),
         "b7_chol": (i32, [vp, vp, i32, vp, C.POINTER(dbl), C.POINTER(i32)]),
         "b7_gp_predict": (i32, [vp, vp, vp]),
         "b7_gp_predict_at": (i32, [vp, vp, i64, vp, vp]),
@@ -479,6 +485,61 @@ class Context(object):
         if self._L.b7_persist_fallbacks(self._h) != before:
             self.fit_token += 1
         return float(buf[4][0]), float(buf[5][0]), int(buf[6][0])
+
+    def gp_slice_sample(self, theta0, lo, hi, widths, U, seed, update0=0, max_step=1000, max_evals=512, gibbs=False,
+                        logspace=True):
+        """C slice-sampling chains of U updates over the resident data in ONE launch (b7_gp_slice_sample): theta0 is C x (d + 3)
+        (or one start point), theta = [log lenscale_sq, log amp, log noise, mean]; lo, hi, widths have d + 3 entries.  Returns
+        {'theta': C x U x (d + 3), 'value': C x U, 'status': C x U bit masks (SLICE_*), 'nevals': C}.  The kernel runs the
+        sampler's default mode only: Gibbs updates and linear space are refused by name."""
+        if gibbs:
+            raise Bot7HipError(-5, "gp_slice_sample: Gibbs updates are not built on the device (random direction only)")
+        if not logspace:
+            raise Bot7HipError(-5, "gp_slice_sample: linear space is not built on the device (log space only)")
+        D = getattr(self, "_data_d", -4) + 3
+        t0 = _f64(theta0)
+        t0 = t0.reshape(1, -1) if t0.ndim == 1 else t0
+        lo, hi, wd = _f64(lo).ravel(), _f64(hi).ravel(), _f64(widths).ravel()
+        if D >= 4 and (t0.shape[1] != D or lo.size != D or hi.size != D or wd.size != D):
+            raise Bot7HipError(-1, "gp_slice_sample: theta0 must be C x (d + 3), lo / hi / widths d + 3 long")
+        Cn, U = t0.shape[0], int(U)
+        D = t0.shape[1]
+        n = max(Cn, 0) * max(U, 0)
+        theta = np.empty((Cn, max(U, 0), D), dtype=np.float64)
+        value = np.empty((Cn, max(U, 0)), dtype=np.float64)
+        status = np.empty((Cn, max(U, 0)), dtype=np.int32)
+        nev = np.empty(max(Cn, 1), dtype=np.int32)
+        keep = [np.empty(max(n, 1))]  # (a zero-sized array has no address worth passing)
+        self._ck(self._L.b7_gp_slice_sample(self._h, Cn, U, _ptr(t0), _ptr(lo), _ptr(hi), _ptr(wd), int(max_step), int(max_evals),
+                                            int(seed) & (2 ** 64 - 1), int(update0) & (2 ** 64 - 1),
+                                            _ptr(theta if n else keep[0]), _ptr(value if n else keep[0]),
+                                            _ptr(status if n else keep[0]), _ptr(nev)))
+        self._slice_shape = (Cn, D)
+        return {"theta": theta, "value": value, "status": status, "nevals": nev[:Cn]}
+
+    def gp_slice_trace_enable(self, records_per_chain):
+        """Keep the first `records_per_chain` trace records of every chain of the following gp_slice_sample calls (0: off)."""
+        self._ck(self._L.b7_gp_slice_trace_enable(self._h, int(records_per_chain)))
+        self._slice_rpc = int(records_per_chain)
+
+    def gp_slice_trace(self, chain):
+        """Chain `chain`'s records of the last traced gp_slice_sample, in order, as a list of dicts: an update's draws
+        {'type': 'update', 'g', 'u_Y', 'log_u_Y', 'z', 'u_right'} or a density request {'type': 'request', 'kind' (0 start,
+        1 step-out right, 2 step-out left, 3 shrink), 'u', 'in_bounds', 'reused', 'value', 'ticks' (100 MHz), 'theta', 'hyp'}."""
+        rpc = getattr(self, "_slice_rpc", 0)
+        D = getattr(self, "_slice_shape", (0, 0))[1]
+        buf = np.zeros((max(rpc, 1), SLICE_TRACE_WIDTH), dtype=np.float64)
+        n = C.c_int()
+        self._ck(self._L.b7_gp_slice_trace(self._h, int(chain), _ptr(buf), C.byref(n)))
+        out = []
+        for r in buf[:n.value]:
+            if r[0] == 0.0:
+                out.append({"type": "update", "g": int(r[1]), "u_Y": r[2], "log_u_Y": r[3], "z": r[8:8 + D].copy(),
+                            "u_right": r[72:72 + D].copy()})
+            else:
+                out.append({"type": "request", "kind": int(r[1]), "u": r[2], "in_bounds": bool(r[3]), "reused": bool(r[4]),
+                            "value": r[5], "ticks": r[6], "theta": r[8:8 + D].copy(), "hyp": r[72:72 + D].copy()})
+        return out
 
     def chol(self, src):
         """utils.math.chol(src, 'L') with the jitter schedule; returns (L, jitter_used, info_first)."""

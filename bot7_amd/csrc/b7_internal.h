@@ -184,6 +184,11 @@ struct b7_ctx {
   PinBuf pin_blr;   // b7_blr_eval_nominate: staging of the observations and beta (y - mean) (not mapped)
   PinBuf pin_eval;  // b7_eval_nominate: [S][4] pivot reports + the packed hypers of all S samples (mapped)
   PinBuf pin_nll;   // b7_gp_nll_batch: hypers in, results out (mapped)
+  PinBuf pin_slice; // b7_gp_slice_sample: start points, bounds and widths in, samples, values, statuses and the completion counter out (mapped)
+  DevBuf slice_state;          // b7_gp_slice_sample: the chains' state blocks (slice_chain_kernel)
+  DevBuf slice_trace;          // b7_gp_slice_trace_enable: the last call's trace records, [C][rpc][B7_SLICE_TRACE_WIDTH] doubles | [C] counts
+  int slice_trace_rpc = 0;     // records per chain to keep (0: no trace)
+  int slice_trace_C = 0, slice_trace_D = 0;  // shape of what the last traced call left (0: nothing)
   bool fmin_staged = false;  // the fmin staging slot of the pinned block holds a caller's values
   bool potrf_attrs_set = false;  // dynamic-LDS limits of the Cholesky kernels raised (once per context)
   bool linv_done = false;  // launch_potrf produced Linv for the current factor

@@ -10,6 +10,13 @@
 //                      128 f + 101                phase[f] = 2 pi counter_uniform
 //       a = 1 + j    PATH j:   f (f < 4096)  weight[f] ~ N(0,1);   4096 + i  eps[i] / sqrt(noise) ~ N(0,1), observation i
 //     Nothing depends on q, S, F, d or N: feature f, path j and observation i have the same draws in every call with that seed.
+//   b7_gp_slice_sample (gp_small.hip: slice_chain_kernel)   chain c of a call draws from the stream key(seed, c); update number
+//       g = update0 + u owns the counters 4096 g .. 4096 g + 4095 (D = d + 3 <= 64 components, at most 3840 shrink steps):
+//                      4096 g + k        (k < D)     z_k ~ N(0,1), the direction before it is normalised (counter_normal)
+//                      4096 g + 64                   u_Y: the slice level is f(x0) + log(u_Y)               (counter_uniform)
+//                      4096 g + 128 + k  (k < D)     the uniform of right_k
+//                      4096 g + 256 + i  (i < 3840)  the uniform of shrink step i
+//     Nothing depends on C, U or how a run is split into calls: a draw is a function of (seed, chain, g).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

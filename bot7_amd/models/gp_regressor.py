@@ -24,7 +24,8 @@ Hyper-parameter vector layout (ours; the reference's parse_hypers layout is unkn
 Hyper sampling (config.sampler = 'slice', bots/bayesopt.lua:44): bot7.samplers.slice walks the log posterior
     log p(theta | X, Y) = -NLL(theta) + log prior(theta),   theta = [log lenscale_sq, log amp, log noise, mean]
 with a flat prior inside explicit bounds (config.bounds; the gp package's priors are unknown).  Every evaluation
-is one device fit (K + Cholesky + log-det + quadratic form, the `GP-fit ms` unit of work).  With
+is one device fit (K + Cholesky + log-det + quadratic form, the `GP-fit ms` unit of work).  config.sampler =
+'slice_device' runs the same sampler inside the library, a whole chain of updates per launch (_sample_hypers_device).  With
 ``config.nBurnin = 0`` and ``config.sample = False`` (default) sample_hypers returns the point estimate, which
 is what the fixed-hyper parity tests and the benchmark use."""
 import numpy as np
@@ -188,6 +189,8 @@ class gp_regressor(abstract):
         Y = np.asarray(Y_obs, dtype=np.float64).reshape(X.shape[0], -1)
         if self.hyp is None:
             self.init(X, Y)
+        if self.config.get("sample") and self.config.get("sampler", "slice") == "slice_device":
+            return self._sample_hypers_device(X, Y, state)
         if self.config.get("sample") and int(self.config.get("chains", 1)) > 1:
             return self._sample_hypers_chains(X, Y, state)
         if self.config.get("sample"):
@@ -211,6 +214,100 @@ class gp_regressor(abstract):
             self._chain_state = (theta, self.hyp)
         h = self.hyp
         return np.concatenate([h["lenscale_sq"], [h["amp"], h["noise"], h["mean"]]])
+
+    # ---- the chain on the device: one b7_gp_slice_sample per burn-in and per pool of samples ----------------------------------
+    def _sample_hypers_device(self, X, Y, state):
+        """config.sampler = 'slice_device': the sampler of bot7.samplers.slice in its default mode (random direction, log space,
+        step-out, max_step), decision for decision, run by the library in ONE launch per call (b7_gp_slice_sample) instead of
+        one launch per density evaluation.  Same theta, bounds and width default (0.5) as the host path.
+
+        config.chains (default 1): C independent chains, chain 0 from the point estimate, the others a little off it.
+        config.prefetch (default 1): updates per chain drawn per launch.  The call without `state` runs config.nBurnin updates
+        of every chain in one launch; the calls with it are served from a pool of `prefetch` updates of every chain (update by
+        update, chain after chain) which one launch refills when it is empty or the data have changed.  Update numbers only
+        ever grow (update0), so no draw is used twice across calls or trials.  The draws are the library's counter generator's,
+        not a numpy Generator's: a different stream from config.sampler = 'slice', the same distribution.
+
+        Fallback: the kernel never runs the jitter schedule.  A chain that reports a failed pivot (status bit 8) stops on its
+        last good theta; its remaining updates of that call are run from there by the registered host 'slice' sampler, whose
+        density evaluations (b7_gp_nll_batch) carry the schedule -- self.last_fit then shows the jitter."""
+        if Y.shape[1] != 1 or X.shape[0] > 128 or X.shape[1] > 32:
+            raise NotImplementedError("sampler 'slice_device' runs N <= 128 observations, d <= 32 and one response column "
+                                      "(got N = %d, d = %d, %d columns): use sampler = 'slice'" % (X.shape[0], X.shape[1], Y.shape[1]))
+        C = max(1, int(self.config.get("chains", 1)))
+        lo, hi = self._bounds(X, Y)
+        sopt = dict(self.config.get("sampler_opt") or {})
+        dev = getattr(self, "_dev", None)
+        if dev is None:
+            if self.config.get("noiseless") and self.hyp["noise"] <= 0.0:
+                self.hyp["noise"] = np.exp(lo[-2])
+            t0 = self._to_theta(self.hyp)
+            seed = int(self.config.get("seed", 0))
+            rngs = [np.random.default_rng([seed, c]) for c in range(C)]
+            thetas = np.stack([np.clip(t0 + (0.1 * rngs[c].standard_normal(t0.size) if c else 0.0), lo, hi) for c in range(C)])
+            dev = self._dev = {"thetas": thetas, "update0": 0, "pool": [], "pool_key": None, "seed": seed, "hyp": self.hyp}
+        elif C == 1 and dev["hyp"] is not self.hyp:
+            dev["thetas"] = self._to_theta(self.hyp).reshape(1, -1)   # somebody replaced the point estimate: the chain restarts there
+            dev["pool"] = []
+        key = self._data_key(X, Y)
+        if not state:
+            n = int(self.config.get("nBurnin", 0))
+            if n > 0:
+                self._device_updates(X, Y, key, n, sopt)
+                self.hyp = dev["hyp"] = self._from_theta(dev["thetas"][0])   # (as the host path: the estimate follows the chain)
+            dev["pool"] = []
+        else:
+            if not dev["pool"] or dev["pool_key"] != key:
+                P = max(1, int(self.config.get("prefetch", 1)))
+                drawn = self._device_updates(X, Y, key, P, sopt)            # C x P x D
+                dev["pool"] = [drawn[c, u].copy() for u in range(P) for c in range(C)]
+                dev["pool_key"] = key
+            self.hyp = self._from_theta(dev["pool"].pop(0))
+            dev["hyp"] = self.hyp
+        h = self.hyp
+        return np.concatenate([h["lenscale_sq"], [h["amp"], h["noise"], h["mean"]]])
+
+    def _device_updates(self, X, Y, key, U, sopt):
+        """U updates of every chain in one library call; returns the C x U x (d + 3) samples and leaves the chains on the last."""
+        dev = self._dev
+        lo, hi = self._bounds(X, Y)
+        self._use_kernel()
+        if getattr(self, "_resident_key", None) != (key, self.ctx.fit_token):
+            self.ctx.gp_set_data(X, Y)
+            self._resident_key = (key, self.ctx.fit_token)
+        D = lo.size
+        widths = sopt.get("widths")
+        widths = np.full(D, sopt.get("width") or 0.5) if widths is None else np.asarray(widths, dtype=np.float64).ravel()
+        out = self.ctx.gp_slice_sample(dev["thetas"], lo, hi, widths, U, dev["seed"], update0=dev["update0"],
+                                       max_step=int(sopt.get("max_step", 1000)), max_evals=int(sopt.get("max_evals", 512)),
+                                       gibbs=bool(sopt.get("gibbs")), logspace=sopt.get("logspace") is not False)
+        dev["update0"] += U
+        self.nDeviceCalls = getattr(self, "nDeviceCalls", 0) + 1
+        self.nEvals = getattr(self, "nEvals", 0) + int(np.sum(out["nevals"]))
+        theta = out["theta"]
+        for c in range(theta.shape[0]):
+            stopped = np.nonzero(out["status"][c] & 8)[0]
+            if stopped.size:                       # failed pivot: the rest of this chain's updates on the host (jitter schedule)
+                u0 = int(stopped[0])
+                theta[c, u0:] = self._host_updates(X, Y, theta[c, u0], U - u0, sopt, widths)
+        dev["thetas"] = theta[:, -1, :].copy()
+        return theta
+
+    def _host_updates(self, X, Y, theta, n, sopt, widths):
+        """n updates of the registered host 'slice' sampler from theta (the device chain's fallback)."""
+        from .abstract import sampler_registry
+        if "slice" not in sampler_registry:
+            raise KeyError("sampler 'slice_device' finishes a chain stopped by a failed pivot through the host sampler: register "
+                           "'slice' in bot7_amd.models.abstract.sampler_registry")
+        sampler = sampler_registry["slice"]()
+        self._dev["host_calls"] = self._dev.get("host_calls", 0) + 1
+        opt = sampler.configure(dict(sopt, widths=widths, seed=[self._dev["seed"], 1 << 20, self._dev["update0"]]))
+        f = self._density(X, Y)
+        out = np.empty((n, theta.size))
+        for i in range(n):
+            theta = np.asarray(sampler.sample(f, theta.reshape(1, -1), dict(opt, nSamples=1), None)[0], dtype=np.float64)
+            out[i] = theta
+        return out
 
     # ---- several chains in lock step: one b7_gp_nll_batch per round of density evaluations -------------------------------
     def _sample_hypers_chains(self, X, Y, state):

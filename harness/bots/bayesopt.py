@@ -44,6 +44,8 @@ class bayesopt(abstract):
         model.setdefault("nzModel", "GaussianNoise_iso")  # :42
         model.setdefault("mean", "constant")            # :43
         model.setdefault("sampler", "slice")            # :44
+        if model["sampler"] == "slice_device":          # ours: the chain on the device draws a trial's samples in one launch
+            model["prefetch"] = config["bot"]["nSamples"]
         config["model"] = model
         score = dict(config.get("score") or {})
         score.setdefault("type", "expected_improvement")  # :49

@@ -42,6 +42,11 @@ def run(ctx, trials=None, on_trial=None, out=None, **over):
     mcfg = {"sample": True, "nBurnin": int(cfg["nBurnin"]), "seed": int(cfg["model_seed"])}
     if "kernel" in cfg:   # optional: the model's covariance kernel (config.model.kernel, bots/bayesopt.lua:41; default ardse)
         mcfg["kernel"] = cfg["kernel"]
+    for k in ("sampler", "chains"):   # optional: config.model.sampler ('slice_device': the chain on the device) and its chain count
+        if k in cfg:
+            mcfg[k] = cfg[k]
+    if mcfg.get("sampler") == "slice_device":   # (the model is handed over ready-made: what the bot's configure step would set)
+        mcfg["prefetch"] = int(cfg["nSamples"])
     model = bot7_amd.models.gp_regressor(mcfg, context=ctx)
     # the candidate grid on the context (grids/sobol.lua:58-90 defaults: skip 1, no affine map), handed to the bot as a
     # sharded set with a world of one: nominations are global indices, the steal is b7_nominate_commit

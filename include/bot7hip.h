@@ -184,6 +184,59 @@ int b7_gp_predict_hyp(b7_ctx *ctx, const b7_hyp *hyp, double *mean_host, double 
 int b7_gp_nll_batch(b7_ctx *ctx, int B, const double *lenscale_sq, const double *amp, const double *noise,
                     const double *mean, double *nll_out, double *jitter_out, int *info_out);
 
+/* THE SLICE SAMPLER'S HYPER CHAIN ON THE DEVICE: C chains of U updates each in ONE launch, one workgroup per chain -- the
+ * control flow of samplers/slice.lua:51-168 and the likelihood evaluation loop inside the kernel, so a trial's 46-74 sequential
+ * density evaluations cost one launch and one host wait instead of one each.  No counterpart in the reference's call
+ * structure; the same decisions: the default mode -- random direction (:78-86), log space, step-out, per-dimension widths,
+ * max_step -- over the density  -NLL(exp(theta_1..d+2), theta_d+3)  with a flat prior inside [lo, hi]:
+ *   theta = [log lenscale_sq_1..d, log amp, log noise, mean], d + 3 components; theta0 is C x (d + 3), the chains' start points.
+ *   A theta with a component outside [lo, hi] or not finite has density -inf and is not evaluated.  An update after the first
+ *   of a call starts from the value of the point the last one ended on without evaluating it again.
+ *   Every evaluation is b7_gp_nll_batch's, bit for bit: the value is -(0.5 t0 + t1 + c0) of the same two terms.
+ * Runs over the resident data (b7_gp_set_data) under the context's covariance kernel (b7_gp_set_kernel), N <= 128, d <= 32, one
+ * response column.  The context's current fit, its predictions, the grid and the score accumulator are untouched.
+ * Draws: the library's counter generator.  Chain c of a call draws from the stream key(seed, c); update number g = update0 + u
+ * owns the counters 4096 g .. 4096 g + 4095:  4096 g + k (k < d + 3) the direction's normal z_k;  4096 g + 64 the uniform u_Y of
+ * the slice level Y = f(x0) + log(u_Y);  4096 g + 128 + k the uniforms of `right`;  4096 g + 256 + i the uniform of shrink step i.
+ * A draw depends on (seed, chain, g) alone: U updates in one call are U calls of one update chained through theta_out and
+ * update0, and chain c's samples do not depend on C.
+ * Every loop is bounded: step-outs by max_step, the density requests of one update (the start point's included, evaluated or
+ * not) by max_evals.  status_out, per (chain, update), is a bit mask:
+ *   1   a NaN density was met: as the reference does (:138-141), the update stops shrinking and takes the point
+ *   2   the slice shrank to zero (:146-149): the reference's behaviour, the point is taken
+ *   4   max_evals was reached: the update returns the point it started from
+ *   8   a likelihood's plain factorisation reported a failed pivot: the chain stops -- this update and all later ones return
+ *       the chain's last good theta.  The kernel never runs the jitter schedule; the call still returns B7_OK and the caller
+ *       decides (the models finish such a chain through the host sampler, whose evaluations carry the schedule)
+ *   16  the update was not run (it follows one with bit 8)
+ * theta_out C x U x (d + 3), value_out C x U (the density at theta_out; NaN where none is known), nevals_out[C] the likelihood
+ * evaluations the chain ran.
+ * B7_ERR_STATE: no resident data.  B7_ERR_UNSUPPORTED, the case named: N > 128, d > 32, more than one response column (Gibbs
+ * updates and linear space are not built: the bindings answer those by name).  B7_ERR_INVALID: NULL arguments, C outside
+ * 1..B7_SLICE_MAX_CHAINS, U < 1, max_evals outside 1..B7_SLICE_MAX_EVALS, U * max_evals > B7_SLICE_MAX_WORK, max_step < 0,
+ * d + 3 > 64, a width <= 0, lo > hi.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_SLICE_MAX_CHAINS 256
+#define B7_SLICE_MAX_EVALS 3840
+#define B7_SLICE_MAX_WORK 65536
+int b7_gp_slice_sample(b7_ctx *ctx, int C, int U, const double *theta0 /*C x (d+3)*/, const double *lo, const double *hi,
+                       const double *widths /*d+3 each*/, int max_step, int max_evals, uint64_t seed, uint64_t update0,
+                       double *theta_out /*C x U x (d+3)*/, double *value_out /*C x U*/, int *status_out /*C x U*/,
+                       int *nevals_out /*C*/);
+/* Inspection (tests, cost tools): with records_per_chain > 0 every later b7_gp_slice_sample keeps, per chain, its first
+ * records_per_chain records of B7_SLICE_TRACE_WIDTH doubles each, in the order the kernel made them; 0 (default) turns it off.
+ * A full buffer stops recording and leaves the chain unaffected.  rec[0] is the record's type:
+ *   0  an update:   rec[1] g, rec[2] u_Y, rec[3] log u_Y, rec[8 + k] z_k, rec[72 + k] the uniform of right_k      (k < d + 3)
+ *   1  a density request:  rec[1] kind (0 start, 1 step-out right, 2 step-out left, 3 shrink), rec[2] the shrink uniform (else
+ *      0), rec[3] 1 inside the bounds, rec[4] 1 reused (the known value of the start point), rec[5] the value, rec[6] the
+ *      evaluation's length in ticks of the 100 MHz wall clock (0 when nothing was evaluated), rec[7] reserved, rec[8 + k]
+ *      theta_k, rec[72 + k] the hyper pack the likelihood body was given (lenscale_sq_1..d, amp, noise, mean; 0 when not evaluated)
+ * b7_gp_slice_trace copies chain `chain`'s records of the last traced call (records: room for records_per_chain records,
+ * nullable) and their number.  B7_ERR_STATE without one. */
+#define B7_SLICE_TRACE_WIDTH 136
+int b7_gp_slice_trace_enable(b7_ctx *ctx, int records_per_chain);
+int b7_gp_slice_trace(b7_ctx *ctx, int chain, double *records, int *n_records);
+
 /* utils.math.chol(src, 'L') (utils/math.lua:159-218) on a caller-provided symmetric n x n matrix: lower factor
  * with the same jitter schedule as b7_gp_fit.  res_host n x n (upper triangle zero).  Replaces the current fit
  * on this context.  jitter_used / info as in b7_gp_fit (nullable). */

@@ -41,6 +41,9 @@ int b7_gp_set_data(b7_ctx *ctx, const double *X_obs, const double *Y_obs, int N,
 int b7_gp_fit_hyp(b7_ctx *ctx, const b7_hyp *hyp, double *nll_out, double *jitter_used, int *info);
 int b7_gp_predict_hyp(b7_ctx *ctx, const b7_hyp *hyp, double *mean_host, double *var_host, double *nll_out, double *jitter_used, int *info);
 int b7_gp_nll_batch(b7_ctx *ctx, int B, const double *lenscale_sq, const double *amp, const double *noise, const double *mean, double *nll_out, double *jitter_out, int *info_out);
+int b7_gp_slice_sample(b7_ctx *ctx, int C, int U, const double *theta0 , const double *lo, const double *hi, const double *widths , int max_step, int max_evals, uint64_t seed, uint64_t update0, double *theta_out , double *value_out , int *status_out , int *nevals_out );
+int b7_gp_slice_trace_enable(b7_ctx *ctx, int records_per_chain);
+int b7_gp_slice_trace(b7_ctx *ctx, int chain, double *records, int *n_records);
 int b7_chol(b7_ctx *ctx, const double *src_host, int n, double *res_host, double *jitter_used, int *info);
 int b7_gp_predict(b7_ctx *ctx, double *mean_host, double *var_host);
 int b7_gp_predict_at(b7_ctx *ctx, const double *X1, int64_t M1, double *mean_host, double *var_host);
@@ -131,6 +134,10 @@ M.ERR_RANGE = -6
 M.ERR_COMM = -7
 M.KERNEL_ARDSE = 0
 M.KERNEL_MATERN52 = 1
+M.SLICE_MAX_CHAINS = 256
+M.SLICE_MAX_EVALS = 3840
+M.SLICE_MAX_WORK = 65536
+M.SLICE_TRACE_WIDTH = 136
 M.MES_KMAX = 64
 M.COMM_ID_BYTES = 128
 M.COMM_SUM = 0

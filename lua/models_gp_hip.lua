@@ -220,8 +220,96 @@ function model:sample_hypers_chains(X_obs, Y_obs, state)
   return torch.cat(h.lenscale_sq, torch.DoubleTensor{h.amp, h.noise, h.mean})
 end
 
+-- config.sampler = 'slice_device': the same sampler (samplers/slice.lua:51-168, its default mode) run by the library, a whole
+-- chain of updates per launch (b7_gp_slice_sample) instead of one launch per density evaluation.  config.chains (default 1)
+-- chains, config.prefetch (default 1) updates of every chain per launch: the call without `state` runs config.nBurnin updates
+-- in one launch, the calls with it are served from a pool of `prefetch` updates per chain that one launch refills when it is
+-- empty or the data have changed.  update0 only grows: no draw is used twice.  A chain stopped by a failed pivot (status bit 8)
+-- finishes its updates through bot7.samplers.slice from its last good theta (log_posterior carries the jitter schedule).
+-- Mirrors gp_regressor._sample_hypers_device of the Python harness.
+function model:device_updates(X_obs, Y_obs, U)
+  local dev, sopt = self.dev, self.config.sampler_opt or {}
+  if sopt.gibbs then error('bot7hip: slice_device: Gibbs updates are not built on the device (B7_ERR_UNSUPPORTED)') end
+  if sopt.logspace == false then error('bot7hip: slice_device: linear space is not built on the device (B7_ERR_UNSUPPORTED)') end
+  self:stage_data(X_obs, Y_obs)
+  local lo, hi = self:bounds(X_obs, Y_obs)
+  local C, D = dev.thetas:size(1), dev.thetas:size(2)
+  local start = dev.thetas:contiguous()   -- (kept in a local: no pointer from a temporary)
+  local widths = sopt.widths and sopt.widths:clone():view(-1) or torch.DoubleTensor(D):fill(sopt.width or 0.5)
+  local theta, value = torch.DoubleTensor(C, U, D), torch.DoubleTensor(C, U)
+  local status, nevals = ffi.new('int[?]', C * U), ffi.new('int[?]', C)
+  hip.check(hip.C.b7_gp_slice_sample(hip.ctx, C, U, torch.data(start), torch.data(lo), torch.data(hi),
+                                     torch.data(widths), sopt.max_step or 1000, sopt.max_evals or 512, dev.seed, dev.update0,
+                                     torch.data(theta), torch.data(value), status, nevals))
+  dev.update0 = dev.update0 + U
+  for c = 1, C do
+    self.nEvals = self.nEvals + nevals[c - 1]
+    for u = 1, U do
+      if bit.band(status[(c - 1) * U + u - 1], 8) ~= 0 then   -- failed pivot: the rest of this chain's updates on the host
+        local Samplers = require('bot7.samplers')
+        local sampler  = Samplers['slice']()
+        local opt = sampler.configure({widths = widths:view(1, -1), max_step = sopt.max_step})
+        opt.nSamples = 1
+        local f = function(t, _) return self:log_posterior(t, X_obs, Y_obs) end
+        local t = theta[c][u]:clone()
+        for v = u, U do
+          t = sampler.sample(f, t:view(1, -1), opt, nil)[1]:clone()
+          theta[c][v]:copy(t)
+        end
+        break
+      end
+    end
+  end
+  dev.thetas = theta:select(2, U):clone()
+  return theta
+end
+
+function model:sample_hypers_device(X_obs, Y_obs, state)
+  local N, d = X_obs:size(1), X_obs:size(2)
+  if N > 128 or d > 32 or (Y_obs:dim() == 2 and Y_obs:size(2) > 1) then
+    error("bot7hip: sampler 'slice_device' runs N <= 128 observations, d <= 32 and one response column: use sampler = 'slice'")
+  end
+  local C = self.config.chains or 1
+  local lo, hi = self:bounds(X_obs, Y_obs)
+  if not self.dev then
+    if self.config.noiseless and not (self.hyp.noise > 0) then self.hyp.noise = math.exp(lo[d + 2]) end
+    local t0 = to_theta(self.hyp)
+    local thetas = torch.DoubleTensor(C, d + 3)
+    for c = 1, C do   -- chain 1 starts at the point estimate, the others a little off it (inside the bounds)
+      thetas[c]:copy(t0)
+      if c > 1 then thetas[c]:add(0.1, torch.randn(d + 3)):cmax(lo):cmin(hi) end
+    end
+    self.dev = {thetas = thetas, update0 = 0, pool = {}, seed = self.config.seed or 0, hyp = self.hyp}
+  elseif C == 1 and self.dev.hyp ~= self.hyp then
+    self.dev.thetas = to_theta(self.hyp):view(1, -1):clone()
+    self.dev.pool = {}
+  end
+  local dev = self.dev
+  if not state then
+    local n = self.config.nBurnin or 0
+    if n > 0 then
+      self:device_updates(X_obs, Y_obs, n)
+      self.hyp = from_theta(dev.thetas[1]); dev.hyp = self.hyp
+    end
+    dev.pool = {}
+  else
+    self:stage_data(X_obs, Y_obs)
+    if #dev.pool == 0 or dev.pool_data ~= self._data then
+      local P = self.config.prefetch or 1
+      local drawn = self:device_updates(X_obs, Y_obs, P)
+      dev.pool = {}
+      for u = 1, P do for c = 1, C do dev.pool[#dev.pool + 1] = drawn[c][u]:clone() end end
+      dev.pool_data = self._data
+    end
+    self.hyp = from_theta(table.remove(dev.pool, 1)); dev.hyp = self.hyp
+  end
+  local h = self.hyp
+  return torch.cat(h.lenscale_sq, torch.DoubleTensor{h.amp, h.noise, h.mean})
+end
+
 function model:sample_hypers(X_obs, Y_obs, _, _, state) -- bots/bayesopt.lua:68 (burn-in) and :74 (state = true)
   if not self.hyp then self:init(X_obs, Y_obs) end
+  if self.config.sample and self.config.sampler == 'slice_device' then return self:sample_hypers_device(X_obs, Y_obs, state) end
   if self.config.sample and (self.config.chains or 1) > 1 then return self:sample_hypers_chains(X_obs, Y_obs, state) end
   if self.config.sample then
     local Samplers = require('bot7.samplers')
