@@ -25,6 +25,7 @@ SYMBOLS = [
     "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_mes", "b7_mes_set_levels", "b7_mes_last_ystar", "b7_mes_ystar", "b7_mes_compute", "b7_score_cb", "b7_score_finish",
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_eval_nominate_batch", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
     "b7_ts_nominate", "b7_ts_last_paths", "b7_ts_last_draws", "b7_rff_compute",
+    "b7_refine_default_opts", "b7_eval_nominate_refine", "b7_refine_last", "b7_refine_shape", "b7_refine_trace_enable", "b7_refine_trace", "b7_gp_grad_at", "b7_score_grad_compute",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
     "b7_group_grid_sobol", "b7_group_grid_random", "b7_group_grid_onesided", "b7_group_grid_upload", "b7_group_grid_shape", "b7_group_grid_download",
@@ -50,7 +51,15 @@ class ScoreSpec(C.Structure):
                 ("fmin", C.POINTER(C.c_double))]
 
 
+class RefineOpts(C.Structure):
+    _fields_ = [("starts", C.c_int), ("iters", C.c_int), ("eta0", C.c_double), ("lo", C.POINTER(C.c_double)),
+                ("hi", C.POINTER(C.c_double))]
+
+
 SCORE_EI, SCORE_CB, SCORE_LOGEI, SCORE_MES = 1, 2, 3, 4
+# b7_eval_nominate_refine: limits, the trace's record width and the status bits of a start
+REFINE_MAX_STARTS, REFINE_MAX_ITERS, REFINE_TRACE_WIDTH = 16, 256, 200
+REFINE_NOT_RUN, REFINE_FLAT, REFINE_CONVERGED, REFINE_MOVED = 1, 2, 4, 8
 # b7_gp_slice_sample: the trace's record width and the status bits of an update
 SLICE_TRACE_WIDTH = 136
 SLICE_NAN, SLICE_ZERO, SLICE_CAP, SLICE_PIVOT, SLICE_NOT_RUN = 1, 2, 4, 8, 16
@@ -171,6 +180,15 @@ def load(which=None):
         "b7_eval_nominate_batch": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), i32, vp, vp, vp, vp]),
         "b7_ts_nominate": (i32, [vp, i32, C.POINTER(Hyp), i32, i32, C.c_uint64, vp, vp, vp, vp]),
         "b7_ts_last_paths": (i32, [vp, vp]),
+        "b7_refine_default_opts": (i32, [C.POINTER(RefineOpts)]),
+        "b7_eval_nominate_refine": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), C.POINTER(RefineOpts), C.POINTER(dbl),
+                                          C.POINTER(i64), vp, C.POINTER(dbl), C.POINTER(i64), vp, vp]),
+        "b7_refine_last": (i32, [vp, C.POINTER(i32), vp, vp, vp, vp]),
+        "b7_refine_shape": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "b7_refine_trace_enable": (i32, [vp, i32]),
+        "b7_refine_trace": (i32, [vp, i32, vp, C.POINTER(i32)]),
+        "b7_gp_grad_at": (i32, [vp, vp, i64, vp, vp, vp, vp]),
+        "b7_score_grad_compute": (i32, [vp, C.POINTER(ScoreSpec), i32, vp, vp, vp, vp, i64, i32, vp, vp]),
         "b7_ts_last_draws": (i32, [vp, i32, vp, vp, vp, vp]),
         "b7_rff_compute": (i32, [vp, vp, i64, i32, vp, vp, vp, i32, i32, vp]),
         "b7_blr_eval_nominate": (i32, [vp, C.POINTER(Mlp), vp, vp, i32, dbl, dbl, dbl, C.POINTER(ScoreSpec), i64, C.POINTER(dbl),
@@ -877,6 +895,95 @@ class Context(object):
         if want_report:
             return vals, idx, {"jitter": jit, "info": info}
         return vals, idx
+
+    def eval_nominate_refine(self, hyps, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0, starts=16, iters=16,
+                             eta0=1.0 / 16.0, lo=None, hi=None, want_report=False):
+        """eval_nominate, then the nominee refined off the grid by gradient ascent on the marginalised acquisition from `starts`
+        starts for `iters` iterations inside the box [lo, hi] (None: the unit cube) (b7_eval_nominate_refine).  hyps, score, fmin,
+        tradeoff, upper, sign as eval_nominate (score "mes" reaches the library, which answers "unsupported").
+        Returns (value, 1-based index, x[d], refined value, 1-based index of the winner's start[, report]); the grid is not modified."""
+        S = len(hyps)
+        d = getattr(self, "_data_d", -1)
+        arr, keep = self._pack_hyps(hyps, d)
+        spec, fm = self._pack_spec(score, fmin, tradeoff, upper, sign)
+        lo = None if lo is None else _f64(lo).ravel()
+        hi = None if hi is None else _f64(hi).ravel()
+        for b in (lo, hi):
+            if b is not None and b.size != d:
+                raise Bot7HipError(-1, "lo / hi must have d entries")
+        dp = C.POINTER(C.c_double)
+        opts = RefineOpts(int(starts), int(iters), float(eta0), None if lo is None else lo.ctypes.data_as(dp),
+                          None if hi is None else hi.ctypes.data_as(dp))
+        jit = np.zeros(S, dtype=np.float64) if want_report else None
+        info = np.zeros(S, dtype=np.int32) if want_report else None
+        v, i, rv, ri = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
+        x = np.zeros(max(d, 1), dtype=np.float64)
+        self._ck(self._L.b7_eval_nominate_refine(self._h, S, arr, C.byref(spec), C.byref(opts), C.byref(v), C.byref(i), _ptr(x),
+                                                 C.byref(rv), C.byref(ri), _ptr(jit), _ptr(info)))
+        self.fit_token += 1
+        if want_report:
+            return v.value, i.value, x, rv.value, ri.value, {"jitter": jit, "info": info}
+        return v.value, i.value, x, rv.value, ri.value
+
+    def refine_last(self):
+        """Every start of the last eval_nominate_refine: dict(x P x d, val P, start_idx1 P, status P) (b7_refine_last)."""
+        P, d, _, _ = self.refine_shape()
+        n = C.c_int()
+        x, val = np.zeros((REFINE_MAX_STARTS, d), dtype=np.float64), np.zeros(REFINE_MAX_STARTS, dtype=np.float64)
+        idx, status = np.zeros(REFINE_MAX_STARTS, dtype=np.int64), np.zeros(REFINE_MAX_STARTS, dtype=np.int32)
+        self._ck(self._L.b7_refine_last(self._h, C.byref(n), _ptr(x), _ptr(val), _ptr(idx), _ptr(status)))
+        P = n.value
+        return {"x": x[:P].copy(), "val": val[:P].copy(), "start_idx1": idx[:P].copy(), "status": status[:P].copy()}
+
+    def refine_shape(self):
+        """(starts, d, iters, traced) of the last eval_nominate_refine, from the library (b7_refine_shape)."""
+        P, d, it, tr = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._ck(self._L.b7_refine_shape(self._h, C.byref(P), C.byref(d), C.byref(it), C.byref(tr)))
+        return P.value, d.value, it.value, bool(tr.value)
+
+    def refine_trace_enable(self, on=True):
+        """Keep one record per start and iteration of the eval_nominate_refine calls that follow (b7_refine_trace_enable)."""
+        self._ck(self._L.b7_refine_trace_enable(self._h, int(bool(on))))
+
+    def refine_trace(self, start):
+        """Start `start`'s records of the last traced eval_nominate_refine, iteration 0..iters, as a dict of arrays: x (n x d, the
+        point after the iteration), val, grad (n x d), eta (before the step), cand (n x 4, NaN where no ladder ran), rung (-1:
+        stayed), status (b7_refine_trace)."""
+        _, d, iters, _ = self.refine_shape()
+        buf = np.zeros((iters + 1, REFINE_TRACE_WIDTH), dtype=np.float64)
+        n = C.c_int()
+        self._ck(self._L.b7_refine_trace(self._h, int(start), _ptr(buf), C.byref(n)))
+        r = buf[:n.value]
+        return {"x": r[:, :d].copy(), "val": r[:, d].copy(), "grad": r[:, d + 1:2 * d + 1].copy(), "eta": r[:, 2 * d + 1].copy(),
+                "cand": r[:, 2 * d + 2:2 * d + 6].copy(), "rung": r[:, 2 * d + 6].astype(np.int64),
+                "status": r[:, 2 * d + 7].astype(np.int64)}
+
+    def gp_grad_at(self, X1):
+        """The current fit's posterior at the rows of X1 with gradients: (mean M1, var M1, dmean M1 x d, dvar M1 x d); var is the
+        latent variance (b7_gp_grad_at)."""
+        X1 = _f64(X1)
+        if X1.ndim == 1:
+            X1 = X1.reshape(1, -1)
+        M1, d = X1.shape
+        mean, var = np.empty(M1, dtype=np.float64), np.empty(M1, dtype=np.float64)
+        dmean, dvar = np.empty((M1, d), dtype=np.float64), np.empty((M1, d), dtype=np.float64)
+        self._ck(self._L.b7_gp_grad_at(self._h, _ptr(X1), M1, _ptr(mean), _ptr(var), _ptr(dmean), _ptr(dvar)))
+        return mean, var, dmean, dvar
+
+    def score_grad_compute(self, mean, var, dmean, dvar, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0):
+        """The marginal score and its gradient from S samples' mean / var (S x M1) and their gradients (S x M1 x d) on host
+        arrays -> (value M1, grad M1 x d) (b7_score_grad_compute)."""
+        dmean, dvar = _f64(dmean), _f64(dvar)
+        if dmean.ndim == 2:
+            dmean, dvar = dmean[None], dvar[None]
+        S, M1, d = dmean.shape
+        mean, var = _f64(mean).reshape(S, M1), _f64(var).reshape(S, M1)
+        dvar = dvar.reshape(S, M1, d)
+        spec, fm = self._pack_spec(score, fmin, tradeoff, upper, sign)
+        value, grad = np.empty(M1, dtype=np.float64), np.empty((M1, d), dtype=np.float64)
+        self._ck(self._L.b7_score_grad_compute(self._h, C.byref(spec), S, _ptr(mean), _ptr(var), _ptr(dmean), _ptr(dvar), M1, d,
+                                               _ptr(value), _ptr(grad)))
+        return value, grad
 
     def ts_nominate(self, hyps, q, n_features=1024, seed=0, want_report=False):
         """Thompson sampling (b7_ts_nominate): q pathwise posterior samples over the resident data and grid, path j under hyper

@@ -120,6 +120,15 @@ struct ScoreParams {
   double fmin0 = 0.0, tradeoff = 0.0, sign = 0.0;
 };
 
+// b7_eval_nominate_refine (refine.hip, score.hip): the starts' state on the device, downloaded whole at the end of a call
+struct RefState {
+  double x[B7_REFINE_MAX_STARTS][B7_MAX_D], g[B7_REFINE_MAX_STARTS][B7_MAX_D];  // point and marginal gradient
+  double v[B7_REFINE_MAX_STARTS], eta[B7_REFINE_MAX_STARTS], score[B7_REFINE_MAX_STARTS];  // marginal value, step, the grid's score at the start
+  long long idx[B7_REFINE_MAX_STARTS];  // the grid row it started from (0-based)
+  int status[B7_REFINE_MAX_STARTS];     // B7_REFINE_* bits
+  int active[B7_REFINE_MAX_STARTS];     // the queries in flight are this start's ladder (else: the start itself, four times)
+};
+
 struct b7_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -244,6 +253,12 @@ struct b7_ctx {
   bool ts_valid = false;  // a b7_ts_nominate has succeeded; the shapes of what it left:
   int64_t ts_M = 0;
   int ts_q = 0, ts_S = 0, ts_F = 0, ts_N = 0, ts_d = 0;
+  // ---- b7_eval_nominate_refine / b7_gp_grad_at (refine.hip): the workspace of 64 query columns, the last call's trace and result
+  DevBuf refine_ws, refine_trace;
+  DevBuf refine_user;       // b7_score_grad_compute's staging, apart from them
+  bool refine_trace_on = false, refine_valid = false;
+  int refine_P = 0, refine_d = 0, refine_iters = 0, refine_trace_P = 0, refine_trace_iters = 0;  // shapes of what the last call left (trace_P 0: no trace)
+  RefState refine_last;     // the last call's final state
   DevBuf feat;   // DNGO basis features of the resident grid: Mfeat x Npad (zero-padded columns)
   size_t feat_zeroed_bytes = 0;  // how much of `feat` was zeroed when it was laid out for feat_z columns
   int feat_z = -1;
@@ -471,6 +486,22 @@ int acc_write_zeros(b7_ctx *c);
 void acc_forget(b7_ctx *c);
 int acc_materialize(b7_ctx *c);
 int launch_keep_record(b7_ctx *c, uint64_t *tab_dev, int rank, int world);
+// the refinement's score pieces (grad<K> beside value<K>).  launch_score_grad: S samples' mean / var [S][M1] and gradients [S][M1][d]
+// on the device -> the marginal value [M1] and gradient [M1][d].  launch_refine_step: the same over the 64 query columns, then the
+// ladder decision per start, the next 64 query rows, the state and the trace record (refine_step_kernel)
+int launch_score_grad(b7_ctx *c, const ScoreParams &p, const double *mu, const double *var, const double *dmu, const double *dvar,
+                      int64_t M1, int d, double *value, double *grad);
+struct RefStep {
+  const double *mu, *var, *dmu, *dvar;  // [S][64], [S][64][d]
+  const double *xq;                     // the 64 query rows just evaluated (column = 4 start + rung)
+  double *xq_next;                      // the next ones
+  RefState *st;
+  double *trace;                        // [P][iters + 1][B7_REFINE_TRACE_WIDTH], or null
+  const double *lo, *hi;                // the box, d entries each
+  int d, P, iter, iters;
+  double eta0;
+};
+int launch_refine_step(b7_ctx *c, const ScoreParams &p, const RefStep &r);
 int launch_row_slot(b7_ctx *c, uint64_t *tab_dev, int rank, int world, int64_t idx1_global, int64_t local0, const double *grid,
                     int d);
 
@@ -542,7 +573,9 @@ struct BelKeep {
   double *mu = nullptr, *var = nullptr;  // [S][M]
   // the S fits afterwards, sample s at base + s * (dpad | Npad dpad | Npad | Npad^2): the batch slots, or (S == 1) the context's own
   const double *w = nullptr, *zsc = nullptr, *zss = nullptr, *Linv = nullptr;
-};
+  const double *alpha = nullptr;  // ... and their alpha (stride Npad): what b7_eval_nominate_refine's mean gradient contracts with
+  bool want_alpha = false;        // copy alpha into its batch slot where a fit does not live there yet (the believer does not read it)
+};  // mu == nullptr: the means and variances are not kept (b7_eval_nominate_refine reads the fits alone)
 int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend, BelKeep *keep = nullptr);
 bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist);
 int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out,

@@ -160,3 +160,50 @@ __device__ __forceinline__ void cov_nonpos4(const double (&arg)[4], const double
     amp_matern52_nonpos4(arg, tab, out);
 }
 
+// The covariance AND its radial factor g, with dk/dx_c = -g (x_c - z_c) / lenscale_sq_c, for the kernels that need the posterior's
+// gradient (refine.hip; nothing else instantiates it).  k is cov_nonpos4<KERN>'s own bits: the ARD-SE branch calls it (g = k); the
+// Matern branch is amp_matern52_nonpos4 stage by stage, sharing its s and exponential, with one more polynomial on the way out:
+//   g = (5/3) amp (1 + s) exp(-s)          finite at D = 0, where the difference factor is 0
+template <int KERN>
+__device__ __forceinline__ void cov_grad_nonpos4(const double (&arg)[4], const double *__restrict__ tab, double (&out)[4],
+                                                 double (&g)[4]) {
+  static_assert(KERN == B7_KERNEL_ARDSE || KERN == B7_KERNEL_MATERN52, "covariance kernel");
+  if constexpr (KERN == B7_KERNEL_ARDSE) {
+    amp_exp_nonpos4(arg, tab, out);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g[i] = out[i];
+  } else {
+    double a[4], s[4], nb[4], nf[4], r[4], p[4], q[4], t[4], m[4], m2[4];
+    int n[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = __builtin_fmin(arg[i], 0.0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = __builtin_fmin(__builtin_sqrt(-10.0 * a[i]), 1000.0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) nb[i] = __builtin_fma(s[i], -B7_EXP_INV, B7_EXP_MAGIC);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      n[i] = __double2loint(nb[i]);
+      t[i] = tab[n[i] & 127];
+      nf[i] = nb[i] - B7_EXP_MAGIC;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = __builtin_fma(nf[i], -B7_EXP_TAIL, __builtin_fma(nf[i], -B7_EXP_HEAD, -s[i]));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      p[i] = __builtin_fma(r[i], 1.0 / 120.0, 1.0 / 24.0);
+      p[i] = __builtin_fma(p[i], r[i], 1.0 / 6.0);
+      p[i] = __builtin_fma(p[i], r[i], 0.5);
+      p[i] = __builtin_fma(p[i], r[i], 1.0);
+      q[i] = __builtin_fma(arg[i], 0.0, r[i] * p[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      m[i] = __builtin_fma(s[i], __builtin_fma(s[i], 1.0 / 3.0, 1.0), 1.0);
+      m2[i] = __builtin_fma(s[i], 5.0 / 3.0, 5.0 / 3.0);
+      t[i] = __builtin_fma(t[i], q[i], t[i]);
+      out[i] = __builtin_ldexp(m[i] * t[i], n[i] >> 7);
+      g[i] = __builtin_ldexp(m2[i] * t[i], n[i] >> 7);
+    }
+  }
+}

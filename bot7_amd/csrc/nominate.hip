@@ -102,26 +102,31 @@ int pending_score(b7_ctx *c, int S, const b7_score_spec *spec, const double *fd,
 // score:add is left to the caller's exchange step in *pend.
 // b7_eval_nominate_batch's hook (keep, nullable): sample s of S has just been fitted into the context's own slots and predicted
 // into c->mu / c->var; its mean and variance go to keep's arrays, its fit to batch slot s (S == 1: it stays where it is)
-static int keep_slots_ensure(b7_ctx *c, int S) {
+static int keep_slots_ensure(b7_ctx *c, int S, bool with_alpha) {
   const size_t n = (size_t)c->Npad;
   B7_TRY(b7_ensure(c, c->bw, sizeof(double) * (size_t)S * c->dpad));
   B7_TRY(b7_ensure(c, c->bzsc, sizeof(double) * (size_t)S * n * c->dpad));
   B7_TRY(b7_ensure(c, c->bzss, sizeof(double) * (size_t)S * n));
+  if (with_alpha) B7_TRY(b7_ensure(c, c->balpha, sizeof(double) * (size_t)S * n));
   return b7_ensure(c, c->bLinv, sizeof(double) * (size_t)S * n * n);
 }
 static int keep_sample(b7_ctx *c, BelKeep *keep, int S, int s) {
   if (!keep) return B7_OK;
   const size_t n = (size_t)c->Npad, mb = sizeof(double) * (size_t)c->M;
-  B7_HIP(c, hipMemcpyAsync(keep->mu + (size_t)s * c->M, c->mu.p, mb, hipMemcpyDeviceToDevice, c->stream));
-  B7_HIP(c, hipMemcpyAsync(keep->var + (size_t)s * c->M, c->var.p, mb, hipMemcpyDeviceToDevice, c->stream));
+  if (keep->mu) {
+    B7_HIP(c, hipMemcpyAsync(keep->mu + (size_t)s * c->M, c->mu.p, mb, hipMemcpyDeviceToDevice, c->stream));
+    B7_HIP(c, hipMemcpyAsync(keep->var + (size_t)s * c->M, c->var.p, mb, hipMemcpyDeviceToDevice, c->stream));
+  }
   if (S == 1) {
     keep->w = (const double *)c->w.p, keep->zsc = (const double *)c->zsc.p, keep->zss = (const double *)c->zss.p;
-    keep->Linv = (const double *)c->Linv.p;
+    keep->Linv = (const double *)c->Linv.p, keep->alpha = (const double *)c->alpha.p;
     return B7_OK;
   }
   keep->w = (const double *)c->bw.p, keep->zsc = (const double *)c->bzsc.p, keep->zss = (const double *)c->bzss.p;
-  keep->Linv = (const double *)c->bLinv.p;
+  keep->Linv = (const double *)c->bLinv.p, keep->alpha = (const double *)c->balpha.p;
   if (c->w.p == (double *)c->bw.p + (size_t)s * c->dpad) return B7_OK;  // the fit already lives in its batch slot
+  if (keep->want_alpha)
+    B7_HIP(c, hipMemcpyAsync((double *)c->balpha.p + s * n, c->alpha.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
   B7_HIP(c, hipMemcpyAsync((double *)c->bw.p + (size_t)s * c->dpad, c->w.p, sizeof(double) * c->dpad, hipMemcpyDeviceToDevice, c->stream));
   B7_HIP(c, hipMemcpyAsync((double *)c->bzsc.p + s * n * c->dpad, c->zsc.p, sizeof(double) * n * c->dpad, hipMemcpyDeviceToDevice, c->stream));
   B7_HIP(c, hipMemcpyAsync((double *)c->bzss.p + s * n, c->zss.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
@@ -132,10 +137,12 @@ static int keep_sample(b7_ctx *c, BelKeep *keep, int S, int s) {
 static int keep_batch(b7_ctx *c, BelKeep *keep, int S) {
   if (!keep) return B7_OK;
   const size_t bytes = sizeof(double) * (size_t)S * c->M;
-  B7_HIP(c, hipMemcpyAsync(keep->mu, c->bmu.p, bytes, hipMemcpyDeviceToDevice, c->stream));
-  B7_HIP(c, hipMemcpyAsync(keep->var, c->bvar.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (keep->mu) {
+    B7_HIP(c, hipMemcpyAsync(keep->mu, c->bmu.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    B7_HIP(c, hipMemcpyAsync(keep->var, c->bvar.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+  }
   keep->w = (const double *)c->bw.p, keep->zsc = (const double *)c->bzsc.p, keep->zss = (const double *)c->bzss.p;
-  keep->Linv = (const double *)c->bLinv.p;
+  keep->Linv = (const double *)c->bLinv.p, keep->alpha = (const double *)c->balpha.p;
   return B7_OK;
 }
 
@@ -280,7 +287,7 @@ int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec
       B7_TRY(rc);
     }
   } else {
-    if (keep && S > 1) B7_TRY(keep_slots_ensure(c, S));
+    if (keep && S > 1) B7_TRY(keep_slots_ensure(c, S, keep->want_alpha));
     for (int s = 0; s < S; ++s) {
       B7_TRY(fit_front(c, &hyps[s], (const double *)c->bhyp.p + (size_t)s * d));
       int *report = static_cast<int *>(c->pin_eval.dev) + 4 * s;  // a one-block factorisation mirrors its report itself
@@ -317,7 +324,7 @@ bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist) {
 // the same nomination through the per-sample path, jitter schedule (utils/math.lua:159-218) included; synchronous
 int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out, BelKeep *keep) {
   B7_HIP(c, hipSetDevice(c->device));
-  if (keep && S > 1) B7_TRY(keep_slots_ensure(c, S));
+  if (keep && S > 1) B7_TRY(keep_slots_ensure(c, S, keep->want_alpha));
   B7_TRY(acc_write_zeros(c));
   if (spec->kind == B7_SCORE_MES) B7_TRY(mes_begin(c, S, c->M, c->mes_levels));
   double *fd = nullptr;

@@ -168,6 +168,227 @@ __device__ __forceinline__ double row_sign(double v, const ScoreParams &p) {
 __device__ __forceinline__ double fmin_of(const ScoreParams &p, int k) {  // fmin == nullptr: one column, its f_min a kernel argument
   return p.fmin ? p.fmin[k] : p.fmin0;
 }
+// the score's derivatives at one candidate of one hyper sample, for b7_eval_nominate_refine (nothing else instantiates it):
+// cm = dv/dmu and cs = dv/dsigma of row_sign(value<K>), so that grad v = cm grad mu + cs grad sigma, grad sigma = grad var / (2 sigma).
+//   EI     -Phi(z), phi(z) with the score's own A&S Phi and phi: the exact-EI formula; it proposes directions, decisions are on values
+//   CB     the row sign times (1, +-kappa), following value<CB>
+//   LogEI  -(Phi/h)/sigma, (phi/h)/sigma, h = phi + z Phi; Phi/phi = sqrt(pi/2) erfcx(-z/sqrt2) (no exponential),
+//          phi/h = 1/(1 + z Phi/phi), Phi/h = (Phi/phi)(phi/h); for z >= 0 the same two through phi/Phi, which stays finite
+template <int K>
+__device__ __forceinline__ void grad(double mu, double var, double fmin, const ScoreParams &p, double *cm, double *cs) {
+  if constexpr (K == B7_SCORE_EI) {
+    const double h = sqrt(var);
+    const double z = ((fmin + (-mu)) + (-p.tradeoff)) / h;
+    *cm = -b7_norm_cdf(z), *cs = b7_norm_pdf(z);
+  } else if constexpr (K == B7_SCORE_CB) {
+    const double sg = (p.sign > 0.0) ? 1.0 : -1.0;
+    *cm = sg, *cs = sg * (p.upper ? p.tradeoff : -p.tradeoff);
+  } else {
+    static_assert(K == B7_SCORE_LOGEI, "grad<K>: EI, CB and LogEI have a gradient piece");
+    const double sigma = sqrt(var);
+    const double z = ((fmin + (-mu)) + (-p.tradeoff)) / sigma;
+    const double R = 1.2533141373155002512 * erfcx(z * -0.70710678118654752440);  // Phi(z) / phi(z)
+    double ph, Ph;                                                                // phi / h, Phi / h
+    if (z < 0.0) {
+      ph = 1.0 / (1.0 + (z * R));
+      Ph = R * ph;
+    } else {
+      const double iR = 1.0 / R, den = z + iR;
+      Ph = 1.0 / den;
+      ph = iR / den;
+    }
+    *cm = -(Ph / sigma), *cs = ph / sigma;
+  }
+}
+// candidate j's marginal value over the S samples -- fold / div in sample order, the grid's accumulator -- and NC components of its
+// gradient, c = sub, sub + 16, ..: the mean of the per-sample gradients for a linear accumulator, sum_s softmax_s grad v_s with the
+// weights exp(v_s - logsumexp) for LogEI.  mu / var: [S][M1], dmu / dvar: [S][M1][d].
+// SIXTEEN threads serve a candidate (sub = 0 .. 15) and EVERY thread of the block calls: the samples go through in chunks of 16, a
+// thread evaluating ONE sample's value<K> / grad<K> -- the transcendental work, done once per sample -- into the candidate's LDS
+// slots sc[16][4] (v or weight | dv/dmu | dv/dsigma | 2 sigma); between two barriers every thread then adds the chunk onto its own
+// gradient components in sample order.  LogEI: thread 0 of the candidate folds the log-sum-exp (into *sa), a second pass makes the
+// weights.  The sums are those of a loop over s on one thread, in the same order.
+template <int K, int NC>
+__device__ __forceinline__ double marg_value_grad(const ScoreParams &p, const double *__restrict__ mu, const double *__restrict__ var,
+                                                  const double *__restrict__ dmu, const double *__restrict__ dvar, long long M1,
+                                                  long long j, int d, int sub, double (*sc)[4], double *sa, double (&G)[NC]) {
+  constexpr bool LOG = score_acc_kind(K) == B7_ACC_LOG;
+  const double fmin = fmin_of(p, 0);
+  double a = empty<K>();
+#pragma unroll
+  for (int i = 0; i < NC; ++i) G[i] = 0.0;
+  for (int pass = 0; pass < (LOG ? 2 : 1); ++pass) {
+    for (int s0 = 0; s0 < p.S; s0 += 16) {
+      const int s = s0 + sub, ns = (p.S - s0 < 16) ? p.S - s0 : 16;
+      if (s < p.S) {
+        const double m = mu[s * M1 + j], vr = var[s * M1 + j];
+        const double v = row_sign<K>(value<K>(m, hoist<K>(vr, p), fmin, p, s), p);
+        sc[sub][0] = (LOG && pass == 1) ? exp(v + (-a)) : v;
+        if (!LOG || pass == 1) {
+          double cm, cs;
+          grad<K>(m, vr, fmin, p, &cm, &cs);
+          sc[sub][1] = cm, sc[sub][2] = cs, sc[sub][3] = 2.0 * sqrt(vr);
+        }
+      }
+      __syncthreads();
+      if (!LOG) {
+        for (int i = 0; i < ns; ++i) a = fold<K>(a, sc[i][0]);
+      } else if (pass == 0 && sub == 0) {
+        for (int i = 0; i < ns; ++i) a = fold<K>(a, sc[i][0]);
+      }
+      if (!LOG || pass == 1) {
+        for (int i = 0; i < ns; ++i) {
+          const double cm = sc[i][1], cs = sc[i][2], s2 = sc[i][3];
+          const long long row = ((s0 + i) * M1 + j) * d;
+#pragma unroll
+          for (int e = 0; e < NC; ++e) {
+            const int c = sub + 16 * e;
+            if (c < d) {
+              const double t = (cm * dmu[row + c]) + (cs * (dvar[row + c] / s2));
+              G[e] = G[e] + (LOG ? sc[i][0] * t : t);
+            }
+          }
+        }
+      }
+      __syncthreads();
+    }
+    if (LOG && pass == 0) {  // the log-sum-exp to every thread of the candidate
+      if (sub == 0) *sa = a;
+      __syncthreads();
+      a = *sa;
+    }
+  }
+  if (!LOG) {
+#pragma unroll
+    for (int i = 0; i < NC; ++i) G[i] = G[i] / (double)p.S;
+  }
+  return div<K>(a, (double)p.S);
+}
+constexpr int GRAD_NC = B7_MAX_D / 16;  // gradient components per thread: 16 threads to a candidate
+
+// b7_score_grad_compute: 16 candidates per block, 16 threads each
+template <int K>
+__global__ void __launch_bounds__(256) score_grad_kernel(ScoreParams p, const double *__restrict__ mu, const double *__restrict__ var,
+                                                         const double *__restrict__ dmu, const double *__restrict__ dvar, long long M1,
+                                                         int d, double *__restrict__ value_out, double *__restrict__ grad_out) {
+  __shared__ double sc[16][16][4], sa[16];
+  const int r = threadIdx.x >> 4, sub = threadIdx.x & 15;
+  const long long jj = (long long)blockIdx.x * 16 + r, j = (jj < M1) ? jj : M1 - 1;  // a row past the end repeats the last (no store)
+  double G[GRAD_NC];
+  const double v = marg_value_grad<K, GRAD_NC>(p, mu, var, dmu, dvar, M1, j, d, sub, sc[r], &sa[r], G);
+  if (jj >= M1) return;
+  if (sub == 0) value_out[j] = v;
+#pragma unroll
+  for (int i = 0; i < GRAD_NC; ++i)
+    if (sub + 16 * i < d) grad_out[j * d + sub + 16 * i] = G[i];
+}
+
+// One iteration of b7_eval_nominate_refine after the posterior's launches: the marginal value and gradient of the 64 query columns
+// (column = 4 start + rung), the ladder decision per start, the start's new state, its trace record and the next 64 query rows.
+// One workgroup of 1024 threads = 64 columns x 16 (a sample's score pieces once per column, not once per thread); the only
+// cross-thread traffic is LDS between barriers.
+template <int K>
+__global__ void __launch_bounds__(1024) refine_step_kernel(ScoreParams p, RefStep r) {
+  __shared__ double sv[64];
+  __shared__ double sx[B7_REFINE_MAX_STARTS][B7_MAX_D], sg[B7_REFINE_MAX_STARTS][B7_MAX_D];
+  __shared__ double ssc[64][16][4], ssa[64];  // marg_value_grad's slots
+  const int col = threadIdx.x >> 4, sub = threadIdx.x & 15, st = col >> 2, k = col & 3, d = r.d;
+  double G[GRAD_NC];
+  const double mv = marg_value_grad<K, GRAD_NC>(p, r.mu, r.var, r.dmu, r.dvar, 64, col, d, sub, ssc[col], &ssa[col], G);
+  if (sub == 0) sv[col] = mv;
+  // the start's state, read by every thread before any of them writes it
+  double v = r.st->v[st];
+  const double eta = r.st->eta[st];
+  int status = r.st->status[st];
+  const int active = r.st->active[st];
+  __syncthreads();
+  double cand[4] = {NAN, NAN, NAN, NAN}, eta_new = eta;
+  int taken = -1;
+  if (r.iter == 0) {
+    taken = 0;  // the start itself
+    v = sv[4 * st];
+    if (!(status & B7_REFINE_NOT_RUN) && !(fabs(v) < INFINITY)) status |= B7_REFINE_NOT_RUN;
+  } else if (active) {
+    int kb = -1;
+    double bv = 0.0;
+    for (int q = 0; q < 4; ++q) {
+      cand[q] = sv[4 * st + q];
+      if (cand[q] == cand[q] && (kb < 0 || cand[q] > bv)) kb = q, bv = cand[q];  // the highest, the lowest rung on ties, never a NaN
+    }
+    if (kb >= 0 && bv > v) {
+      const double tk = eta * (kb == 0 ? 1.0 : kb == 1 ? 0.25 : kb == 2 ? 0.0625 : 0.015625);
+      taken = kb, v = bv, status |= B7_REFINE_MOVED;
+      eta_new = (4.0 * tk < 1.0) ? 4.0 * tk : 1.0;
+    } else {
+      eta_new = eta / 256.0;
+    }
+    if (eta_new < 0x1p-40) status |= B7_REFINE_CONVERGED;
+  }
+  // the start's point and gradient after this iteration
+  if (taken >= 0 ? k == taken : k == 0) {
+#pragma unroll
+    for (int i = 0; i < GRAD_NC; ++i) {
+      const int c = sub + 16 * i;
+      if (c < d) {
+        sx[st][c] = (taken >= 0) ? r.xq[col * d + c] : r.st->x[st][c];
+        sg[st][c] = (taken >= 0) ? G[i] : r.st->g[st][c];
+      }
+    }
+  }
+  __syncthreads();
+  // the next ladder: g~ = grad o (hi - lo), m = max |g~|
+  bool next = r.iter < r.iters && st < r.P && !(status & (B7_REFINE_NOT_RUN | B7_REFINE_CONVERGED));
+  double m = 0.0;
+  if (next) {
+    bool bad = false;
+    for (int c = 0; c < d; ++c) {
+      const double a = fabs(sg[st][c] * (r.hi[c] + (-r.lo[c])));
+      bad = bad || a != a;
+      if (a > m) m = a;
+    }
+    if (bad || m == 0.0 || !(m < INFINITY)) status |= B7_REFINE_FLAT, next = false;
+  }
+  const double tk = eta_new * (k == 0 ? 1.0 : k == 1 ? 0.25 : k == 2 ? 0.0625 : 0.015625);
+#pragma unroll
+  for (int i = 0; i < GRAD_NC; ++i) {
+    const int c = sub + 16 * i;
+    if (c < d) {
+      double x = sx[st][c];
+      if (next) {
+        const double b = r.hi[c] + (-r.lo[c]);
+        const double rc = (sg[st][c] * b) / m;
+        x = x + ((tk * rc) * b);
+        x = (x > r.lo[c]) ? x : r.lo[c];
+        x = (x < r.hi[c]) ? x : r.hi[c];
+      }
+      r.xq_next[col * d + c] = x;
+    }
+  }
+  if (k != 0 || st >= r.P) return;
+  double *rec = r.trace ? r.trace + ((long long)st * (r.iters + 1) + r.iter) * B7_REFINE_TRACE_WIDTH : nullptr;
+#pragma unroll
+  for (int i = 0; i < GRAD_NC; ++i) {
+    const int c = sub + 16 * i;
+    if (c < d) {
+      r.st->x[st][c] = sx[st][c];
+      r.st->g[st][c] = sg[st][c];
+      if (rec) rec[c] = sx[st][c], rec[d + 1 + c] = sg[st][c];
+    }
+  }
+  if (sub == 0) {
+    r.st->v[st] = v;
+    r.st->eta[st] = eta_new;
+    r.st->status[st] = status;
+    r.st->active[st] = next ? 1 : 0;
+    if (rec) {
+      rec[d] = v;
+      rec[2 * d + 1] = eta;
+      for (int q = 0; q < 4; ++q) rec[2 * d + 2 + q] = cand[q];
+      rec[2 * d + 6] = (r.iter == 0) ? -1.0 : (double)taken;
+      rec[2 * d + 7] = (double)status;
+    }
+  }
+}
 
 // The score of ONE hyper sample (p.S == 1) over c response columns, the row mean if c > 1.  accumulate 0 writes it, 1 folds it
 // onto out, 2 folds it onto an empty accumulator that is not read: the first score:add onto torch.zeros (0.0 + v, not v)
@@ -602,6 +823,38 @@ int launch_row_slot(b7_ctx *c, uint64_t *tab_dev, int rank, int world, int64_t i
 
 int launch_keep_record(b7_ctx *c, uint64_t *tab_dev, int rank, int world) {
   hipLaunchKernelGGL(keep_record_kernel, dim3(1), dim3(256), 0, c->stream, (unsigned long long *)tab_dev, rank, world);
+  B7_HIP(c, hipGetLastError());
+  return B7_OK;
+}
+
+// ---- the refinement's score pieces (b7_eval_nominate_refine, b7_score_grad_compute) ----
+template <class F>
+static int with_grad_kind(b7_ctx *c, int kind, F f) {
+  switch (kind) {
+    case B7_SCORE_EI: f(std::integral_constant<int, B7_SCORE_EI>()); return B7_OK;
+    case B7_SCORE_LOGEI: f(std::integral_constant<int, B7_SCORE_LOGEI>()); return B7_OK;
+    case B7_SCORE_CB: f(std::integral_constant<int, B7_SCORE_CB>()); return B7_OK;
+    default: return b7_fail(c, B7_ERR_UNSUPPORTED, "score gradient: kind %d has no gradient piece", kind);
+  }
+}
+
+int launch_score_grad(b7_ctx *c, const ScoreParams &p, const double *mu, const double *var, const double *dmu, const double *dvar,
+                      int64_t M1, int d, double *value, double *grad) {
+  PhaseScope ps(c, "refine:score");
+  if (M1 <= 0) return B7_OK;
+  B7_TRY(with_grad_kind(c, p.kind, [&](auto k) {
+    hipLaunchKernelGGL(score_grad_kernel<decltype(k)::value>, dim3((unsigned)((M1 + 15) / 16)), dim3(256), 0, c->stream, p, mu, var, dmu,
+                       dvar, (long long)M1, d, value, grad);
+  }));
+  B7_HIP(c, hipGetLastError());
+  return B7_OK;
+}
+
+int launch_refine_step(b7_ctx *c, const ScoreParams &p, const RefStep &r) {
+  PhaseScope ps(c, "refine:step");
+  B7_TRY(with_grad_kind(c, p.kind, [&](auto k) {
+    hipLaunchKernelGGL(refine_step_kernel<decltype(k)::value>, dim3(1), dim3(1024), 0, c->stream, p, r);
+  }));
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }

@@ -14,7 +14,12 @@ subtraction of log(nSamples).  'max_value_entropy_search' (not in the reference 
 level count (config.score.nLevels) and as b7_score_mes in the per-sample loop, each hyper sample with its own y* search on the
 device; on one GPU only -- a sharded candidate set or a batch (config.bot.batch > 1) answers "unsupported".
 'thompson_sampling' (not in the reference) is not a per-point score: nominate and nominate_batch, q = 1 included, go through
-b7_ts_nominate with a seed from the bot's own generator, and eval(want_scores=True) raises -- there is no score vector."""
+b7_ts_nominate with a seed from the bot's own generator, and eval(want_scores=True) raises -- there is no score vector.
+
+config.bot.refine (ours; False = the reference's loop, untouched) is a dict of starts / iters / eta0: a model-based trial then goes
+through b7_eval_nominate_refine, which climbs the marginalised acquisition from the best grid rows inside the grid's box
+(config.grid.mins / maxes); the trial steals the grid row the winner started from, evaluates the objective at the refined point
+and observes that point.  What the library refuses is refused here by name (refine_refusal)."""
 import numpy as np
 
 from .abstract import abstract
@@ -22,6 +27,25 @@ from .. import tensor as T
 from bot7_amd.grids.abstract import DeviceGrid
 from bot7_amd import models as Models
 from bot7_amd import scores as Scores
+
+
+REFINE_DEFAULTS = {"starts": 16, "iters": 16, "eta0": 1.0 / 16.0}
+
+
+def refine_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
+    """Why this configuration cannot refine its nominee off the grid (b7_eval_nominate_refine's own refusals, by name), or None."""
+    if int(config["bot"].get("batch", 1)) > 1:
+        return "config.bot.refine with config.bot.batch > 1: refinement of a batch is not built"
+    if sharded:
+        return "config.bot.refine over sharded candidates: refinement over a sharded grid is not built"
+    if model_class == "bot7.models.dngo":
+        return "config.bot.refine with the dngo model: the Bayesian-linear head has no gradient kernels"
+    kind = config["score"]["type"]
+    if kind == "thompson_sampling":
+        return "config.bot.refine with thompson_sampling: a sample path is not a per-point score"
+    if kind == "max_value_entropy_search":
+        return "config.bot.refine with max_value_entropy_search: the score has no gradient piece"
+    return None
 
 
 class bayesopt(abstract):
@@ -51,6 +75,10 @@ class bayesopt(abstract):
         score.setdefault("type", "expected_improvement")  # :49
         config["score"] = score
         config["bot"].setdefault("batch", 1)            # ours: nominees per trial (nominate_batch); 1 is the reference's loop
+        config["bot"].setdefault("refine", False)       # ours: False, or a dict of starts / iters / eta0 (nominate_refine)
+        if config["bot"]["refine"]:
+            given = config["bot"]["refine"] if isinstance(config["bot"]["refine"], dict) else {}
+            config["bot"]["refine"] = dict(REFINE_DEFAULTS, **given)
         return config
 
     def eval(self, candidates=None, want_scores=True):
@@ -153,9 +181,53 @@ class bayesopt(abstract):
         self.last_scores = None
         return [int(i) for i in idx]
 
+    def nominate_refine(self, candidates=None):
+        """The nominee refined off the grid (b7_eval_nominate_refine; no counterpart in the reference) -> (refined point x[d], the
+        1-based grid row its start came from).  Sampling as eval's fused branch (bots/bayesopt.lua:68, :73-75); the box is the
+        grid's (config.grid.mins / maxes)."""
+        cand = self.candidates if candidates is None else candidates
+        X_obs, Y_obs, model = self.observed, self.responses, self.model
+        why = refine_refusal(self.config, model.class_(), hasattr(cand, "commit"))
+        if why:
+            raise NotImplementedError(why)
+        spec = getattr(self.score, "device_spec", None)
+        assert spec is not None and hasattr(model, "stage"), "config.bot.refine: a GP model with a device score on one GPU"
+        model.sample_hypers(X_obs, Y_obs)                         # :68 (burn-in call)
+        hyps = [model.parse_hypers(model.sample_hypers(X_obs, Y_obs, None, None, True))
+                for _ in range(self.config["bot"]["nSamples"])]   # :73-75
+        model.stage(X_obs, Y_obs, cand)
+        grid, ref = self.config["grid"], self.config["bot"]["refine"]
+        _, _, x, _, start = model.ctx.eval_nominate_refine(hyps, starts=ref["starts"], iters=ref["iters"], eta0=ref["eta0"],
+                                                           lo=np.asarray(grid["mins"], dtype=np.float64),
+                                                           hi=np.asarray(grid["maxes"], dtype=np.float64), **spec(Y_obs))
+        self.last_scores = None
+        return np.array(x, dtype=np.float64), int(start)
+
+    def _run_trial_refined(self):
+        """bots/abstract.lua:112-152 with the nominee refined off the grid: the grid row the winner started from is stolen (:118),
+        so the grid stops offering that neighbourhood; the objective is evaluated at the refined point (:124) and that point is
+        observed (:143-144)."""
+        why = refine_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
+        if why:
+            raise NotImplementedError(why)
+        if self.nTrials + 1 <= self.config["bot"]["nInitial"]:     # :90-91: the initial picks are grid rows
+            return super().run_trial()
+        self.nTrials += 1
+        x, start = self.nominate_refine()                          # :117
+        self._steal_candidate(start)                               # :118
+        idx = self.pending.shape[0]
+        self.pending[idx - 1] = x
+        y = self.objective(x)                                      # :124
+        y = np.asarray(y, dtype=np.float64).reshape(1, -1) if np.ndim(y) < 2 else np.asarray(y, dtype=np.float64)
+        self.responses = y if self.responses is None else np.concatenate([self.responses, y], 0)
+        self.observed, self.pending = T.steal(self.observed, self.pending, [idx])  # :143-144
+        return x, y
+
     def run_trial(self):
         """bots/abstract.lua:112-152 with config.bot.batch nominees per trial: all of them are stolen from the candidates in one
         stable pass (:118), evaluated and observed (:124-144).  batch = 1 is the parent's loop, untouched."""
+        if self.config["bot"]["refine"]:
+            return self._run_trial_refined()
         q = int(self.config["bot"]["batch"])
         if q == 1:
             return super().run_trial()

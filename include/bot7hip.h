@@ -490,6 +490,72 @@ int b7_eval_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec
 int b7_eval_nominate_batch(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int q, double *best_val /*q*/,
                            int64_t *best_idx1 /*q*/, double *jitter_out, int *info_out);
 
+/* The nominee REFINED OFF THE GRID by gradient ascent on the marginalised acquisition.  No counterpart in this reference's bots,
+ * which nominate a grid row (bots/abstract.lua:118); Spearmint, which it descends from, hands its best grid rows to a local
+ * optimiser.  b7_eval_nominate runs first: best_val, best_idx1, jitter_out and info_out are its outputs with global_row_offset
+ * = 0, bit for bit, the jitter redo included.  Then `starts` starts -- the nominee, then the next winners of the same accumulator
+ * under score:max(1)'s rule with the earlier ones left out; nothing is rescored -- climb for `iters` iterations on the posterior's
+ * analytic gradient (both covariance kernels; EI with the score's own Phi and phi, LogEI through erfcx, CB), marginalised over
+ * the S samples as the grid's score is.  Per start: a point x, its value v and gradient, a step eta in box widths (from eta0):
+ *   iteration 0     value and gradient at the start itself (a start is not clipped);
+ *   iteration t     g~_c = grad_c (hi_c - lo_c), m = max_c |g~_c|; m zero or not finite: the start stays (FLAT).  Otherwise four
+ *                   rungs k = 0..3 at x'_c = min(max(x_c + (eta 4^-k g~_c / m)(hi_c - lo_c), lo_c), hi_c) are evaluated; the best
+ *                   is the highest value, the lowest k on ties, a NaN never wins.  Strictly above v: the start moves there and
+ *                   eta <- min(1, 4 eta 4^-k); otherwise it stays and eta <- eta / 256.  eta < 2^-40: CONVERGED, it moves no more.
+ * A start's value never decreases.  The result is the start with the highest final value (lowest start order on ties, non-finite
+ * values left out): x_out (d entries), val_out, start_idx1_out = the 1-based grid row it started from.  If no start moved, x_out is
+ * the nominee's grid row bit for bit, val_out the refinement's own value there and start_idx1_out = best_idx1.  A start whose grid
+ * score is NaN or whose iteration-0 value is not finite is NOT RUN and cannot win.  Deterministic: every sum has one order, so the
+ * same call twice gives the same bits.  Afterwards the accumulator holds score / S as after b7_eval_nominate, the grid is not
+ * modified, and the context's own fit slot holds none of the samples.
+ * b7_refine_opts: starts in 1..B7_REFINE_MAX_STARTS and <= the grid's rows, iters in 0..B7_REFINE_MAX_ITERS, eta0 in (0, 1],
+ * lo / hi d entries each (both NULL: the unit cube), finite, lo < hi; otherwise, or with a NULL argument other than jitter_out /
+ * info_out: B7_ERR_INVALID.  B7_ERR_UNSUPPORTED, the case named: B7_SCORE_MES, more than one response column,
+ * b7_gp_opts.var_with_noise / var_clamp, a communicator of more than one rank.  B7_ERR_STATE: a member of a group.
+ * Device memory: a few S Npad 64 doubles, allocated on demand (B7_ERR_NOMEM) and freed with the context.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_REFINE_MAX_STARTS 16
+#define B7_REFINE_MAX_ITERS 256
+typedef struct {
+  int starts;       /* [16] */
+  int iters;        /* [16] */
+  double eta0;      /* [1/16] first step, in box widths */
+  const double *lo; /* [NULL] d entries; NULL (with hi): the unit cube */
+  const double *hi;
+} b7_refine_opts;
+int b7_refine_default_opts(b7_refine_opts *out);
+int b7_eval_nominate_refine(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, const b7_refine_opts *opts,
+                            double *best_val, int64_t *best_idx1, double *x_out /*d*/, double *val_out, int64_t *start_idx1_out,
+                            double *jitter_out, int *info_out);
+/* Every start of the last b7_eval_nominate_refine: their number, final points P x d, final values, 1-based grid rows and status
+ * bits (all nullable).  B7_ERR_STATE before a successful call. */
+#define B7_REFINE_NOT_RUN 1   /* grid score NaN or iteration-0 value not finite */
+#define B7_REFINE_FLAT 2      /* the gradient was zero or not finite at some iteration */
+#define B7_REFINE_CONVERGED 4 /* eta fell below 2^-40 */
+#define B7_REFINE_MOVED 8     /* moved at least once */
+int b7_refine_last(b7_ctx *ctx, int *P, double *x /*P x d*/, double *val /*P*/, int64_t *start_idx1 /*P*/, int *status /*P*/);
+/* The shapes of what the last b7_eval_nominate_refine left, for a caller that sizes b7_refine_last's and b7_refine_trace's buffers:
+ * starts, d, iters, and whether it was traced (all nullable).  B7_ERR_STATE before a successful call. */
+int b7_refine_shape(b7_ctx *ctx, int *P, int *d, int *iters, int *traced);
+/* Trace of the calls that follow (on != 0): one record per start and iteration 0..iters, B7_REFINE_TRACE_WIDTH doubles each:
+ * x after the iteration (d) | its value | its gradient (d) | eta before the step | the four rungs' values (NaN where no ladder was
+ * run) | the rung taken (-1: stayed) | status bits | zeros.  b7_refine_trace: start `start`'s records of the last call (nullable)
+ * and their number, iters + 1.  B7_ERR_STATE without a traced call. */
+#define B7_REFINE_TRACE_WIDTH 200
+int b7_refine_trace_enable(b7_ctx *ctx, int on);
+int b7_refine_trace(b7_ctx *ctx, int start, double *records, int *n_records);
+/* b7_gp_predict_at with gradients, on the context's CURRENT fit (one response column): mean[M1], var[M1] (the latent variance, amp -
+ * |inv(L) k*|^2), dmean and dvar M1 x d (all nullable), by the refinement's kernels in chunks of 64 rows.  It disturbs nothing.
+ * B7_ERR_STATE without a GP fit; B7_ERR_UNSUPPORTED as b7_eval_nominate_refine. */
+int b7_gp_grad_at(b7_ctx *ctx, const double *X1, int64_t M1, double *mean, double *var, double *dmean /*M1 x d*/,
+                  double *dvar /*M1 x d*/);
+/* The refinement's score piece on host arrays (the b7_ei_compute of the refinement): S samples' mean / var (S x M1) and their
+ * gradients (S x M1 x d) -> the marginal value[M1] (the grid's fold / div in sample order) and its gradient M1 x d (EI, CB: the mean
+ * of the per-sample gradients; LogEI: their softmax-weighted sum).  spec->fmin: one entry.  d in 1..96. */
+int b7_score_grad_compute(b7_ctx *ctx, const b7_score_spec *spec, int S, const double *mean, const double *var /*S x M1*/,
+                          const double *dmean, const double *dvar /*S x M1 x d*/, int64_t M1, int d, double *value /*M1*/,
+                          double *grad /*M1 x d*/);
+
 /* THOMPSON SAMPLING: q nominees from q pathwise (decoupled) posterior samples.  No counterpart in the reference; Wilson,
  * Borovitskiy, Terenin, Mostowsky, Deisenroth (ICML 2020).  A sample path of the posterior is
  *   f_j(x) = m + phi(x)' w_j + K(x, X) v_j,        v_j = inv(K) (y - m - Phi(X) w_j - eps_j)

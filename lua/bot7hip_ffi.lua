@@ -79,6 +79,15 @@ int b7_exchange_info(b7_ctx *ctx, int *world, int64_t *rows_per_rank, int64_t *w
 typedef struct { int kind; double tradeoff; int upper; double sign; const double *fmin; } b7_score_spec;
 int b7_eval_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out);
 int b7_eval_nominate_batch(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int q, double *best_val , int64_t *best_idx1 , double *jitter_out, int *info_out);
+typedef struct { int starts; int iters; double eta0; const double *lo; const double *hi; } b7_refine_opts;
+int b7_refine_default_opts(b7_refine_opts *out);
+int b7_eval_nominate_refine(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, const b7_refine_opts *opts, double *best_val, int64_t *best_idx1, double *x_out , double *val_out, int64_t *start_idx1_out, double *jitter_out, int *info_out);
+int b7_refine_last(b7_ctx *ctx, int *P, double *x , double *val , int64_t *start_idx1 , int *status );
+int b7_refine_shape(b7_ctx *ctx, int *P, int *d, int *iters, int *traced);
+int b7_refine_trace_enable(b7_ctx *ctx, int on);
+int b7_refine_trace(b7_ctx *ctx, int start, double *records, int *n_records);
+int b7_gp_grad_at(b7_ctx *ctx, const double *X1, int64_t M1, double *mean, double *var, double *dmean , double *dvar );
+int b7_score_grad_compute(b7_ctx *ctx, const b7_score_spec *spec, int S, const double *mean, const double *var , const double *dmean, const double *dvar , int64_t M1, int d, double *value , double *grad );
 int b7_ts_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *path_min , int64_t *best_idx1 , double *jitter_out , int *info_out );
 int b7_ts_last_paths(b7_ctx *ctx, double *paths_host );
 int b7_ts_last_draws(b7_ctx *ctx, int path, double *omega , double *phase , double *weight , double *eps );
@@ -148,6 +157,13 @@ M.SCORE_CB = 2
 M.SCORE_LOGEI = 3
 M.SCORE_MES = 4
 M.BATCH_MAX = 16
+M.REFINE_MAX_STARTS = 16
+M.REFINE_MAX_ITERS = 256
+M.REFINE_NOT_RUN = 1
+M.REFINE_FLAT = 2
+M.REFINE_CONVERGED = 4
+M.REFINE_MOVED = 8
+M.REFINE_TRACE_WIDTH = 200
 M.TS_MAX_FEATURES = 4096
 M.MAX_TIMERS = 16
 -- END generated constants

@@ -164,6 +164,49 @@ function bot:nominate_batch(q, candidates)
   return out
 end
 
+-- The nominee refined off the grid (b7_eval_nominate_refine; no counterpart in the reference's bots): nominate's pick, then
+-- gradient ascent on the marginalised acquisition from config.bot.refine.starts grid rows for .iters iterations inside the grid's
+-- box.  Returns the refined point (a d-vector) and the index into `candidates` of the row its start came from: the caller steals
+-- that row, evaluates the objective at the point and observes the point.  One rank, no group, a gp_hip model and an EI / LogEI /
+-- CB score: the library refuses the rest by name.
+function bot:nominate_refine(candidates)
+  local candidates = candidates or self.candidates
+  assert(D.world == 1 and not hip.group, 'nominate_refine: one rank, no group (sharded refinement is not built)')
+  local ref = self.config.bot.refine or {}
+  local model, keep = self.model, {}
+  local Y_obs = self.responses
+  if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
+  local spec = (torch.type(model) == 'bot7.models.gp_hip') and score_spec(self.score, Y_obs, keep) or nil
+  assert(spec ~= nil, 'nominate_refine: needs the gp_hip model and a *_hip score')
+  local X_obs, S = self.observed, self.config.bot.nSamples
+  model:sample_hypers(X_obs, Y_obs)                                          -- :68
+  local hyps = ffi.new('b7_hyp[?]', S)
+  for s = 1, S do                                                            -- :73-75
+    local hyp = model:parse_hypers(model:sample_hypers(X_obs, Y_obs, nil, nil, true))
+    local ls  = hip.pin(hyp.lenscale_sq)
+    keep[#keep + 1] = ls
+    hyps[s-1].lenscale_sq, hyps[s-1].amp, hyps[s-1].noise, hyps[s-1].mean = hip.data(ls), hyp.amp, hyp.noise, hyp.mean
+  end
+  model:stage(X_obs, Y_obs, candidates)
+  hip.set_kernel(model.kernel_code)
+  local d = candidates:size(2)
+  local opts = ffi.new('b7_refine_opts[1]')
+  hip.check(hip.C.b7_refine_default_opts(opts))
+  opts[0].starts = ref.starts or opts[0].starts
+  opts[0].iters  = ref.iters or opts[0].iters
+  opts[0].eta0   = ref.eta0 or opts[0].eta0
+  local lo, hi = hip.pin(torch.Tensor(self.config.grid.mins)), hip.pin(torch.Tensor(self.config.grid.maxes))
+  keep[#keep + 1], keep[#keep + 2] = lo, hi
+  opts[0].lo, opts[0].hi = hip.data(lo), hip.data(hi)
+  local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
+  local rv, ri = ffi.new('double[1]'), ffi.new('int64_t[1]')
+  local x = torch.Tensor(d)
+  local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+  hip.check(hip.C.b7_eval_nominate_refine(hip.ctx, S, hyps, spec, opts, v, i, hip.data(x), rv, ri, jit, info))
+  self.best_score = rv[0]
+  return x, tonumber(ri[0])
+end
+
 -- bots/abstract.lua:112-152 for candidates sharded one process per GPU.  Only line 118 differs: `idx` is 1-based in the
 -- union of the shards, so it must not index this rank's shard; dist_hip.commit returns the nominee on every rank and
 -- deletes the row where it lives.  With one rank (or a group) the parent's code is right as it stands.
