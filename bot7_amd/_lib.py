@@ -31,6 +31,7 @@ SYMBOLS = [
     "b7_group_grid_sobol", "b7_group_grid_random", "b7_group_grid_onesided", "b7_group_grid_upload", "b7_group_grid_shape", "b7_group_grid_download",
     "b7_group_grid_remove_rows", "b7_group_gp_set_data", "b7_group_eval_nominate", "b7_group_nominate_commit",
     "b7_ei_compute", "b7_cb_compute", "b7_logei_compute", "b7_argmax",
+    "b7_score_logpi", "b7_logpi_compute", "b7_feas_reset", "b7_feas_add", "b7_feas_add_acc", "b7_feas_get", "b7_feas_nominate", "b7_eval_nominate_feasible",
     "b7_timer_start", "b7_timer_stop", "b7_timer_ms", "b7_profile_enable", "b7_profile_reset", "b7_profile_get", "b7_persist_fallbacks",
 ]
 
@@ -56,7 +57,8 @@ class RefineOpts(C.Structure):
                 ("hi", C.POINTER(C.c_double))]
 
 
-SCORE_EI, SCORE_CB, SCORE_LOGEI, SCORE_MES = 1, 2, 3, 4
+SCORE_EI, SCORE_CB, SCORE_LOGEI, SCORE_MES, SCORE_LOGPI = 1, 2, 3, 4, 5
+_FMIN_SCORES = {"ei": SCORE_EI, "logei": SCORE_LOGEI, "logpi": SCORE_LOGPI}   # the score= keywords whose kind takes fmin and tradeoff = xi
 # b7_eval_nominate_refine: limits, the trace's record width and the status bits of a start
 REFINE_MAX_STARTS, REFINE_MAX_ITERS, REFINE_TRACE_WIDTH = 16, 256, 200
 REFINE_NOT_RUN, REFINE_FLAT, REFINE_CONVERGED, REFINE_MOVED = 1, 2, 4, 8
@@ -224,6 +226,14 @@ def load(which=None):
         "b7_cb_compute": (i32, [vp, vp, vp, dbl, i32, dbl, i64, i32, vp]),
         "b7_logei_compute": (i32, [vp, vp, vp, vp, dbl, i64, i32, vp]),
         "b7_argmax": (i32, [vp, vp, i64, C.POINTER(dbl), C.POINTER(i64)]),
+        "b7_score_logpi": (i32, [vp, vp, dbl]),
+        "b7_logpi_compute": (i32, [vp, vp, vp, vp, dbl, i64, i32, vp]),
+        "b7_feas_reset": (i32, [vp]),
+        "b7_feas_add": (i32, [vp, vp, i64]),
+        "b7_feas_add_acc": (i32, [vp, vp]),
+        "b7_feas_get": (i32, [vp, vp]),
+        "b7_feas_nominate": (i32, [vp, C.POINTER(dbl), C.POINTER(i64)]),
+        "b7_eval_nominate_feasible": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), C.POINTER(dbl), C.POINTER(i64), vp, vp]),
         "b7_timer_start": (i32, [vp, i32]),
         "b7_timer_stop": (i32, [vp, i32]),
         "b7_timer_ms": (i32, [vp, i32, C.POINTER(C.c_float)]),
@@ -740,6 +750,13 @@ class Context(object):
         f = _f64(fmin).ravel()
         self._ck(self._L.b7_score_logei(self._h, _ptr(f), float(tradeoff)))
 
+    def score_logpi(self, fmin, tradeoff=0.0):
+        """Log probability of improvement of the last predict, log Phi(z), folded into the accumulator as a running log-sum-exp
+        (b7_score_logpi).  With fmin = a constraint's threshold and tradeoff = 0 on that constraint's GP: its log probability of
+        feasibility."""
+        f = _f64(fmin).ravel()
+        self._ck(self._L.b7_score_logpi(self._h, _ptr(f), float(tradeoff)))
+
     def score_mes(self):
         """Max-value entropy search of the last predict: the y* search on the device, then score:add (b7_score_mes)."""
         self._ck(self._L.b7_score_mes(self._h))
@@ -843,23 +860,23 @@ class Context(object):
 
     @staticmethod
     def _pack_spec(score, fmin, tradeoff, upper, sign):
-        if score in ("ei", "logei"):
+        if score in _FMIN_SCORES:
             if fmin is None:
-                raise Bot7HipError(-1, "EI needs fmin")
+                raise Bot7HipError(-1, "%s needs fmin" % ("LogPI" if score == "logpi" else "EI"))
             fm = _f64(fmin).ravel()
-            return ScoreSpec(SCORE_EI if score == "ei" else SCORE_LOGEI, 0.0 if tradeoff is None else float(tradeoff), 0, 0.0,
+            return ScoreSpec(_FMIN_SCORES[score], 0.0 if tradeoff is None else float(tradeoff), 0, 0.0,
                              fm.ctypes.data_as(C.POINTER(C.c_double))), fm
         if score == "mes":  # fmin, tradeoff, upper and sign are ignored
             return ScoreSpec(SCORE_MES, 0.0, 0, 0.0, None), None
         if score == "cb":
             return ScoreSpec(SCORE_CB, 1.0 if tradeoff is None else float(tradeoff), int(bool(upper)), float(sign),
                              None), None
-        raise Bot7HipError(-1, "score must be 'ei', 'logei', 'mes' or 'cb'")
+        raise Bot7HipError(-1, "score must be 'ei', 'logei', 'logpi', 'mes' or 'cb'")
 
     def eval_nominate(self, hyps, score="ei", fmin=None, tradeoff=None, upper=False, sign=-1.0,
                       global_row_offset=0, want_report=False, levels=None):
         """bayesopt:eval + nominate in one call: hyps is a sequence of (lenscale_sq, amp, noise, mean) or dicts
-        with those keys; score "ei" / "logei" (need fmin), "cb" or "mes" (levels: mes_set_levels first).  Returns (value, 1-based
+        with those keys; score "ei" / "logei" / "logpi" (need fmin), "cb" or "mes" (levels: mes_set_levels first).  Returns (value, 1-based
         global index[, report])."""
         if levels is not None:
             self.mes_set_levels(levels)
@@ -871,6 +888,54 @@ class Context(object):
         v, i = C.c_double(), C.c_int64()
         self._ck(self._L.b7_eval_nominate(self._h, S, arr, C.byref(spec), int(global_row_offset), C.byref(v),
                                           C.byref(i), _ptr(jit), _ptr(info)))
+        self.fit_token += 1
+        if want_report:
+            return v.value, i.value, {"jitter": jit, "info": info}
+        return v.value, i.value
+
+    # ---- constrained nomination: the feasibility column (log-weights over the resident grid) and the weighted arg-max
+    def feas_reset(self):
+        """L := 0.0 over the resident grid (b7_feas_reset).  Any change of the grid forgets the column."""
+        self._ck(self._L.b7_feas_reset(self._h))
+
+    def feas_add(self, logw):
+        """L[j] += logw[j] from a host vector with one entry per grid row; -inf masks a row (b7_feas_add)."""
+        w = _f64(logw).ravel()
+        self._ck(self._L.b7_feas_add(self._h, _ptr(w), w.size))
+
+    def feas_add_acc(self, src):
+        """L[j] += the accumulator of the context `src`, device to device: what src.eval_nominate(score="logpi") leaves, the
+        marginal log probability already divided (b7_feas_add_acc).  Both contexts must hold the same grid rows: the caller's
+        contract, only the row count is checked."""
+        if not isinstance(src, Context) or src._L is not self._L:
+            raise Bot7HipError(-1, "feas_add_acc: src must be a Context of the same library")
+        self._ck(self._L.b7_feas_add_acc(self._h, src._h))
+
+    def feas_get(self):
+        """The column L, one entry per grid row (b7_feas_get)."""
+        M, _ = self.grid_shape()
+        out = np.empty(M, dtype=np.float64)
+        self._ck(self._L.b7_feas_get(self._h, _ptr(out)))
+        return out
+
+    def feas_nominate(self):
+        """score:max(1) of the column alone -> (value, 1-based index): the nomination while no feasible observation exists
+        (b7_feas_nominate).  The column is left untouched."""
+        v, i = C.c_double(), C.c_int64()
+        self._ck(self._L.b7_feas_nominate(self._h, C.byref(v), C.byref(i)))
+        return v.value, i.value
+
+    def eval_nominate_feasible(self, hyps, score="logei", fmin=None, tradeoff=None, upper=False, sign=-1.0, want_report=False):
+        """eval_nominate with the feasibility column weighted in between score:div and score:max(1): score + L for the log kinds
+        ("logei", "logpi"), score * exp(L) for "ei" (b7_eval_nominate_feasible; "cb" and "mes" reach the library, which answers
+        "unsupported").  Returns (value, 1-based index[, report]); the accumulator holds the weighted score afterwards."""
+        S = len(hyps)
+        arr, keep = self._pack_hyps(hyps, getattr(self, "_data_d", -1))
+        spec, fm = self._pack_spec(score, fmin, tradeoff, upper, sign)
+        jit = np.zeros(S, dtype=np.float64) if want_report else None
+        info = np.zeros(S, dtype=np.int32) if want_report else None
+        v, i = C.c_double(), C.c_int64()
+        self._ck(self._L.b7_eval_nominate_feasible(self._h, S, arr, C.byref(spec), C.byref(v), C.byref(i), _ptr(jit), _ptr(info)))
         self.fit_token += 1
         if want_report:
             return v.value, i.value, {"jitter": jit, "info": info}
@@ -1047,6 +1112,16 @@ class Context(object):
         var, fmin = _f64(var).ravel(), _f64(fmin).ravel()
         out = np.empty(M, dtype=np.float64)
         self._ck(self._L.b7_logei_compute(self._h, _ptr(mean), _ptr(var), _ptr(fmin), float(tradeoff), M, c, _ptr(out)))
+        return out
+
+    def logpi_compute(self, mean, var, fmin, tradeoff=0.0):
+        """log Phi(z) on caller-provided mean (M or M x c) / var (M); c > 1: the log of the row mean of Phi (b7_logpi_compute)."""
+        mean = _f64(mean)
+        M = mean.shape[0]
+        c = 1 if mean.ndim == 1 else mean.shape[1]
+        var, fmin = _f64(var).ravel(), _f64(fmin).ravel()
+        out = np.empty(M, dtype=np.float64)
+        self._ck(self._L.b7_logpi_compute(self._h, _ptr(mean), _ptr(var), _ptr(fmin), float(tradeoff), M, c, _ptr(out)))
         return out
 
     def cb_compute(self, mean, var, tradeoff=1.0, upper=False, sign=-1.0):

@@ -236,6 +236,12 @@ struct b7_ctx {
   int mes_slot = 0;         // the sample slot the next score_add of kind MES searches into (the nomination's per-sample loops set it)
   bool mes_valid = false;   // a search has filled the buffer since it was laid out (b7_mes_last_ystar)
   DevBuf ticket; // score_finish_slot_kernel's arrival counter (zero between launches)
+  // ---- the feasibility column (score.hip: b7_feas_*): log-weights L[M] over the resident grid, allocated on demand, forgotten with
+  // the accumulator whenever the grid changes (feas_valid changes only through score.hip's feas_* helpers)
+  DevBuf feas;
+  DevBuf feas_stage;        // b7_feas_add's host vector on its way onto the column
+  bool feas_valid = false;
+  hipEvent_t ev_feas[2] = {nullptr, nullptr};  // b7_feas_add_acc: the source's stream -> this one, and back (created on first use)
   DevBuf scratch; // a ScratchBlock (b7_scratch)
   DevBuf tmpgrid; // predict_at temporary grid
   DevBuf tmpmu, tmpvar;
@@ -466,18 +472,20 @@ int launch_score_batch(b7_ctx *c, const ScoreParams &p, double *acc, int64_t M);
 // logacc: acc is a log accumulator -- score:div is acc - log(divisor)
 int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *best_val, int64_t *best_idx1, bool logacc = false);
 int launch_fill(b7_ctx *c, double *p, int64_t n, double v);
+// feas (nullable): the feasibility column; every row becomes w(acc / divisor, feas[j]) before the arg-max (score.hip's header)
 int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64_t *tab_dev, int rank, int world,
                        int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
-                       unsigned *host_done = nullptr, bool logacc = false);
+                       unsigned *host_done = nullptr, bool logacc = false, const double *feas = nullptr);
 
 // excl (nullable): rows that take no part in the arg-max (their score is still written to acc)
+// feas (nullable, not together with excl): the feasibility column, applied between score:div and the arg-max
 struct ExclRows {
   int n = 0;
   long long row[B7_BATCH_MAX];  // 0-based
 };
 int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
                              int rank, int world, int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec = nullptr,
-                             unsigned *host_done = nullptr, const ExclRows *excl = nullptr);
+                             unsigned *host_done = nullptr, const ExclRows *excl = nullptr, const double *feas = nullptr);
 // the accumulator's state: zeros declared (bots/bayesopt.lua:69 without a launch of its own: the first score launch onto it
 // starts from 0.0; score_kind: the B7_SCORE_* it will add), zeros written now, no accumulator (the grid changed), declared zeros
 // written before anybody reads them
@@ -485,6 +493,10 @@ void acc_declare_zeros(b7_ctx *c, int score_kind);
 int acc_write_zeros(b7_ctx *c);
 void acc_forget(b7_ctx *c);
 int acc_materialize(b7_ctx *c);
+void feas_forget(b7_ctx *c);  // the grid changed: there is no feasibility column until the next b7_feas_reset
+int feas_write_zeros(b7_ctx *c);                      // L := 0.0 over the resident grid (allocates on demand)
+int launch_feas_add(b7_ctx *c, const double *src);    // L[j] += src[j], src: c->M doubles on the device
+int launch_feas_best(b7_ctx *c, double *best_val, int64_t *best_idx1);  // score:max(1) of L alone (waits)
 int launch_keep_record(b7_ctx *c, uint64_t *tab_dev, int rank, int world);
 // the refinement's score pieces (grad<K> beside value<K>).  launch_score_grad: S samples' mean / var [S][M1] and gradients [S][M1][d]
 // on the device -> the marginal value [M1] and gradient [M1][d].  launch_refine_step: the same over the 64 query columns, then the
@@ -510,8 +522,9 @@ int launch_row_slot(b7_ctx *c, uint64_t *tab_dev, int rank, int world, int64_t i
 int exch_table_ensure(b7_ctx *c, int world);
 // enqueue: score:div, local arg-max, this rank's record; pend (nullable): the nomination's batched score, run fused with them
 // excl (nullable, with pend): rows kept out of the arg-max (b7_eval_nominate_batch: the rows already picked)
+// feas (nullable): the feasibility column weighted in ahead of the arg-max (b7_eval_nominate_feasible), with or without pend
 int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, bool all_slots, bool mirror = false,
-               const ScoreParams *pend = nullptr, const ExclRows *excl = nullptr);
+               const ScoreParams *pend = nullptr, const ExclRows *excl = nullptr, const double *feas = nullptr);
 int exch_wait_mirror(b7_ctx *c);  // after exch_local(..., mirror = true): spin on the completion word, then (or instead, when it takes long) the stream
 int exch_fail_record(b7_ctx *c, int rank, int world, int code);  // enqueue: this rank's record says "could not score"
 int exch_allreduce(b7_ctx *c);                                   // enqueue: the collective (no-op without a communicator)
@@ -549,9 +562,12 @@ static inline HypPack hyp_pack(void *base, int B, int d) {
 // the per-sample redo
 int nominate_args(b7_ctx *c, const char *who, const b7_score_spec *spec, int64_t offset);
 int stage_fmin(b7_ctx *c, const double *fmin, double **fd_out);
-static inline bool score_needs_fmin(int kind) { return kind == B7_SCORE_EI || kind == B7_SCORE_LOGEI; }
-// what a score of this kind leaves in an accumulator: a linear sum (EI, CB) or a log-sum-exp (LogEI)
-constexpr int score_acc_kind(int kind) { return kind == B7_SCORE_LOGEI ? B7_ACC_LOG : B7_ACC_LINEAR; }
+static inline bool score_needs_fmin(int kind) { return kind == B7_SCORE_EI || kind == B7_SCORE_LOGEI || kind == B7_SCORE_LOGPI; }
+// what a score of this kind leaves in an accumulator: a linear sum (EI, CB, MES) or a log-sum-exp (LogEI, LogPI)
+constexpr int score_acc_kind(int kind) { return (kind == B7_SCORE_LOGEI || kind == B7_SCORE_LOGPI) ? B7_ACC_LOG : B7_ACC_LINEAR; }
+static inline const char *score_kind_name(int kind) {  // for the messages
+  return kind == B7_SCORE_EI ? "ei" : kind == B7_SCORE_LOGEI ? "logei" : kind == B7_SCORE_LOGPI ? "logpi" : kind == B7_SCORE_MES ? "mes" : "cb";
+}
 // mes.hip: c->ystar laid out for S samples of M rows at K levels; y* of nS samples (sample s at mu / var + s * stride) searched into
 // slots [slot0, slot0 + nS) of that layout, R + 1 launches; the device address of a slot's K values
 int mes_begin(b7_ctx *c, int S, int64_t M, int K);
@@ -600,21 +616,22 @@ int grid_drop_row(b7_ctx *c, int64_t local_idx1, double *row_out_sync);  // stab
 // The protocol of the three eval + nominate entry points, once.  rc: their argument checks.  enqueue(&pend): the local
 // bayesopt:eval as stream work, its batched score possibly left pending; clean(): after the stream has drained, did every fit
 // factor at the first attempt; redo(): the same nomination again, synchronously, through the jitter schedule.  The redo starts
-// from nothing pending: what the failed fits left is dropped with them.
+// from nothing pending: what the failed fits left is dropped with them.  feas (nullable; one rank only): the feasibility column
+// that b7_eval_nominate_feasible weights in ahead of the arg-max, on the first pass and on the redo alike.
 template <class Enqueue, class Clean, class Redo>
 static inline int nominate_run(b7_ctx *c, const char *who, int rc, int64_t offset, double divisor, Enqueue enqueue, Clean clean,
-                        Redo redo, double *best_val, int64_t *best_idx1) {
+                        Redo redo, double *best_val, int64_t *best_idx1, const double *feas = nullptr) {
   const int world = c->comm ? c->comm_world : 1, rank = c->comm ? c->comm_rank : 0;
   ScoreParams pend;
   if (!(c->comm && c->comm_world > 1)) {
     // the arg-max and the copy of its record are enqueued before the host has seen any report: one synchronisation
     B7_TRY(rc);
     B7_TRY(enqueue(&pend));
-    B7_TRY(exch_local(c, divisor, offset, rank, world, true, true, &pend));  // record mirrored into mapped host memory
+    B7_TRY(exch_local(c, divisor, offset, rank, world, true, true, &pend, nullptr, feas));  // record mirrored into mapped host memory
     B7_TRY(exch_wait_mirror(c));
     if (!clean()) {
       B7_TRY(redo());
-      B7_TRY(exch_local(c, divisor, offset, rank, world, true, true));
+      B7_TRY(exch_local(c, divisor, offset, rank, world, true, true, nullptr, nullptr, feas));
       B7_TRY(exch_wait_mirror(c));
     }
     return exch_conclude(c, c->tab_host, world, best_val, best_idx1);

@@ -309,6 +309,7 @@ int b7_blr_features(b7_ctx *c, const double *Z1, int64_t M, int z) {
     c->M = M;
     c->d = 0;
     acc_forget(c);
+    feas_forget(c);
   }
   return B7_OK;
 }

@@ -82,8 +82,9 @@ void exch_forget(b7_ctx *c) { c->win_valid = false; }
 // mirror: the kernel also writes this rank's record into the mapped host table and raises the completion word behind it
 // (a context that nominates by itself: no copy launch and no stream wait between the arg-max and the answer; exch_wait_mirror)
 // pend (nullable): the nomination's batched score, still owed -- score:add x S, div, arg-max and record then go in ONE launch
+// feas (nullable): the feasibility column, weighted in between score:div and the arg-max on either route
 int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, bool all_slots, bool mirror, const ScoreParams *pend,
-               const ExclRows *excl) {
+               const ExclRows *excl, const double *feas) {
   B7_TRY(exch_table_ensure(c, world));
   uint64_t *host_rec = nullptr;
   unsigned *host_done = nullptr;
@@ -94,11 +95,11 @@ int exch_local(b7_ctx *c, double divisor, int64_t offset, int rank, int world, b
   }
   if (c->M > 0 && pend && pend->S > 0)
     return launch_score_finish_slot(c, *pend, (double *)c->acc.p, c->M, divisor, (uint64_t *)c->slots.p, rank, world, offset,
-                                    (const double *)c->grid[c->grid_cur].p, c->d, all_slots, host_rec, host_done, excl);
+                                    (const double *)c->grid[c->grid_cur].p, c->d, all_slots, host_rec, host_done, excl, feas);
   if (c->M > 0) B7_TRY(acc_materialize(c));
   return launch_finish_slot(c, c->M > 0 ? (double *)c->acc.p : nullptr, c->M, divisor, (uint64_t *)c->slots.p, rank, world,
                             offset, c->M > 0 ? (const double *)c->grid[c->grid_cur].p : nullptr, c->d, all_slots, host_rec,
-                            host_done, c->acc_kind == B7_ACC_LOG);
+                            host_done, c->acc_kind == B7_ACC_LOG, c->M > 0 ? feas : nullptr);
 }
 
 // Everything enqueued before the mirrored arg-max has completed once its word is up (one stream).  Short nominations are

@@ -68,9 +68,11 @@ int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumul
 // The score spec and the global row offset of an eval + nominate entry point (`who` in the messages).  Only a shard of a
 // larger candidate set -- a rank of a communicator, a member of a group -- may be empty: the exchange covers the others.
 int nominate_args(b7_ctx *c, const char *who, const b7_score_spec *spec, int64_t offset) {
-  if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB && spec->kind != B7_SCORE_LOGEI && spec->kind != B7_SCORE_MES)
+  if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB && spec->kind != B7_SCORE_LOGEI && spec->kind != B7_SCORE_MES &&
+      spec->kind != B7_SCORE_LOGPI)
     return b7_fail(c, B7_ERR_INVALID, "%s: unknown score kind %d", who, spec->kind);
-  if (score_needs_fmin(spec->kind) && !spec->fmin) return b7_fail(c, B7_ERR_INVALID, "%s: EI needs fmin", who);
+  if (score_needs_fmin(spec->kind) && !spec->fmin)
+    return b7_fail(c, B7_ERR_INVALID, "%s: %s needs fmin", who, spec->kind == B7_SCORE_LOGPI ? "LogPI" : "EI");
   if (offset < 0) return b7_fail(c, B7_ERR_INVALID, "%s: negative row offset", who);
   if (c->M == 0 && !(c->comm && c->comm_world > 1) && !c->group)
     return b7_fail(c, B7_ERR_STATE, "%s: no candidate grid on this context", who);
@@ -391,6 +393,98 @@ int b7_eval_nominate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *
       [&]() { return eval_redo(c, S, hyps, spec, jitter_out, info_out); }, best_val, best_idx1);
 }
 
+// b7_eval_nominate with global_row_offset = 0 and the feasibility column weighted in between score:div and score:max(1)
+// (score.hip's header): the same routes, the same single host wait, the same jitter redo; L is read, not modified.
+int b7_eval_nominate_feasible(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *best_val, int64_t *best_idx1,
+                              double *jitter_out, int *info_out) {
+  if (!c) return B7_ERR_INVALID;
+  if (c->group) return b7_fail(c, B7_ERR_STATE, "eval_nominate_feasible: this context belongs to a group (constrained nomination over a sharded grid is not built)");
+  if (jitter_out && S > 0) std::fill(jitter_out, jitter_out + S, 0.0);
+  if (info_out && S > 0) std::fill(info_out, info_out + S, 0);
+  if (c->comm && c->comm_world > 1)
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "eval_nominate_feasible: a communicator of %d ranks (constrained nomination over a sharded grid is not built)", c->comm_world);
+  if (spec && spec->kind == B7_SCORE_CB)
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "eval_nominate_feasible: a confidence bound is a signed score and has no product form with a feasibility weight (EI, LogEI and LogPI are built)");
+  if (spec && spec->kind == B7_SCORE_MES)
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "eval_nominate_feasible: max-value entropy search is not built with a feasibility weight (EI, LogEI and LogPI are built)");
+  B7_TRY(eval_validate(c, S, hyps, spec, 0));
+  if (c->ycols != 1) return b7_fail(c, B7_ERR_UNSUPPORTED, "eval_nominate_feasible: %d response columns (one is built)", c->ycols);
+  if (!c->feas_valid)
+    return b7_fail(c, B7_ERR_STATE, "eval_nominate_feasible: no feasibility column on this grid (call b7_feas_reset; a grid change forgets it)");
+  return nominate_run(
+      c, "eval_nominate_feasible", B7_OK, 0, (double)S, [&](ScoreParams *pend) { return eval_enqueue(c, S, hyps, spec, pend); },
+      [&]() { return reports_clean(c, static_cast<const int *>(c->pin_eval.host), S, true); },
+      [&]() { return eval_redo(c, S, hyps, spec, jitter_out, info_out); }, best_val, best_idx1, (const double *)c->feas.p);
+}
+
+// ---- the feasibility column (score.hip's header) -----------------------------------------------------------
+static int feas_guard(b7_ctx *c, const char *who, bool need_column) {
+  if (c->group) return b7_fail(c, B7_ERR_STATE, "%s: this context belongs to a group (a feasibility column over a sharded grid is not built)", who);
+  if (c->M <= 0) return b7_fail(c, B7_ERR_STATE, "%s: no candidate grid", who);
+  if (need_column && !c->feas_valid)
+    return b7_fail(c, B7_ERR_STATE, "%s: no feasibility column on this grid (call b7_feas_reset; a grid change forgets it)", who);
+  B7_HIP(c, hipSetDevice(c->device));
+  return B7_OK;
+}
+
+int b7_feas_reset(b7_ctx *c) {
+  if (!c) return B7_ERR_INVALID;
+  B7_TRY(feas_guard(c, "feas_reset", false));
+  return feas_write_zeros(c);
+}
+
+int b7_feas_add(b7_ctx *c, const double *logw, int64_t M) {
+  if (!c) return B7_ERR_INVALID;
+  if (!logw) return b7_fail(c, B7_ERR_INVALID, "feas_add: logw is NULL");
+  B7_TRY(feas_guard(c, "feas_add", true));
+  if (M != c->M) return b7_fail(c, B7_ERR_INVALID, "feas_add: %lld log-weights for a grid of %lld rows", (long long)M, (long long)c->M);
+  B7_TRY(b7_ensure(c, c->feas_stage, sizeof(double) * (size_t)M));
+  B7_HIP(c, hipMemcpyAsync(c->feas_stage.p, logw, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+  B7_TRY(launch_feas_add(c, (const double *)c->feas_stage.p));
+  B7_HIP(c, hipStreamSynchronize(c->stream));  // the caller's vector need not outlive the call
+  return B7_OK;
+}
+
+// L += src's accumulator, device to device.  The two streams are ordered by events both ways: the add waits for what src's stream
+// has been given (b7_eval_nominate may return before its stream is formally idle), and whatever src enqueues next waits for the add.
+int b7_feas_add_acc(b7_ctx *c, b7_ctx *src) {
+  if (!c) return B7_ERR_INVALID;
+  if (!src) return b7_fail(c, B7_ERR_INVALID, "feas_add_acc: the source context is NULL");
+  B7_TRY(feas_guard(c, "feas_add_acc", true));
+  if (src->device != c->device)
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "feas_add_acc: the source context is on device %d, this one on device %d (a copy across devices is not built)", src->device, c->device);
+  if (!src->acc_valid) return b7_fail(c, B7_ERR_STATE, "feas_add_acc: the source context holds no accumulator (its grid changed, or nothing was scored)");
+  if (src->acc_kind != B7_ACC_LOG)
+    return b7_fail(c, B7_ERR_STATE, "feas_add_acc: the source's accumulator is a linear sum, not a log one (LogPI or LogEI leaves a log accumulator)");
+  if (src->acc_fresh) return b7_fail(c, B7_ERR_STATE, "feas_add_acc: the source's log accumulator is declared but nothing has been added onto it");
+  if (src->M != c->M)
+    return b7_fail(c, B7_ERR_INVALID, "feas_add_acc: the source's grid has %lld rows, this one %lld", (long long)src->M, (long long)c->M);
+  if (src == c) return launch_feas_add(c, (const double *)c->acc.p);
+  for (hipEvent_t &e : c->ev_feas)
+    if (!e) B7_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  B7_HIP(c, hipEventRecord(c->ev_feas[0], src->stream));
+  B7_HIP(c, hipStreamWaitEvent(c->stream, c->ev_feas[0], 0));
+  B7_TRY(launch_feas_add(c, (const double *)src->acc.p));
+  B7_HIP(c, hipEventRecord(c->ev_feas[1], c->stream));
+  B7_HIP(c, hipStreamWaitEvent(src->stream, c->ev_feas[1], 0));
+  return B7_OK;
+}
+
+int b7_feas_get(b7_ctx *c, double *out) {
+  if (!c) return B7_ERR_INVALID;
+  if (!out) return b7_fail(c, B7_ERR_INVALID, "feas_get: out is NULL");
+  B7_TRY(feas_guard(c, "feas_get", true));
+  B7_HIP(c, hipMemcpyAsync(out, c->feas.p, sizeof(double) * (size_t)c->M, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  return B7_OK;
+}
+
+int b7_feas_nominate(b7_ctx *c, double *best_val, int64_t *best_idx1) {
+  if (!c) return B7_ERR_INVALID;
+  B7_TRY(feas_guard(c, "feas_nominate", true));
+  return launch_feas_best(c, best_val, best_idx1);
+}
+
 // ---- scores --------------------------------------------------------------------------------------------
 int b7_score_reset(b7_ctx *c) {
   if (!c) return B7_ERR_INVALID;
@@ -422,6 +516,11 @@ int b7_score_ei(b7_ctx *c, const double *fmin, double tradeoff) {
 // log-space EI of the last predict, folded into the accumulator as a running log-sum-exp (score.hip's header)
 int b7_score_logei(b7_ctx *c, const double *fmin, double tradeoff) {
   return score_entry(c, "score_logei", b7_score_spec{B7_SCORE_LOGEI, tradeoff, 0, 0.0, fmin});
+}
+
+// log probability of improvement of the last predict, folded into the accumulator as a running log-sum-exp (score.hip's header)
+int b7_score_logpi(b7_ctx *c, const double *fmin, double tradeoff) {
+  return score_entry(c, "score_logpi", b7_score_spec{B7_SCORE_LOGPI, tradeoff, 0, 0.0, fmin});
 }
 
 // max-value entropy search of the last predict: the y* search (K = b7_mes_set_levels' value), then score:add (score.hip's header)
@@ -467,6 +566,14 @@ int b7_logei_compute(b7_ctx *c, const double *mean, const double *var, const dou
   if (M < 0 || cc < 1 || cc > 256 || (M > 0 && (!mean || !var || !fmin || !out)))
     return b7_fail(c, B7_ERR_INVALID, "logei_compute: bad arguments");
   return score_compute(c, b7_score_spec{B7_SCORE_LOGEI, tradeoff, 0, 0.0, fmin}, mean, var, M, cc, out);
+}
+
+int b7_logpi_compute(b7_ctx *c, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M,
+                     int cc, double *out) {
+  if (!c) return B7_ERR_INVALID;
+  if (M < 0 || cc < 1 || cc > 256 || (M > 0 && (!mean || !var || !fmin || !out)))
+    return b7_fail(c, B7_ERR_INVALID, "logpi_compute: bad arguments");
+  return score_compute(c, b7_score_spec{B7_SCORE_LOGPI, tradeoff, 0, 0.0, fmin}, mean, var, M, cc, out);
 }
 
 int b7_cb_compute(b7_ctx *c, const double *mean, const double *var, double tradeoff, int upper, double sign, int64_t M,

@@ -405,6 +405,8 @@ int refine_refuse(b7_ctx *c, const char *who, const b7_score_spec *spec) {
     return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: a communicator of %d ranks (refinement over a sharded grid is not built)", who, c->comm_world);
   if (spec && spec->kind == B7_SCORE_MES)
     return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: max-value entropy search has no gradient piece (EI, LogEI and CB are built)", who);
+  if (spec && spec->kind == B7_SCORE_LOGPI)
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: log probability of improvement (LogPI) has no gradient piece (EI, LogEI and CB are built)", who);
   if (c->ycols != 1) return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: %d response columns (one is built)", who, c->ycols);
   if (c->opts.var_with_noise || c->opts.var_clamp)
     return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: the gradient is the latent variance's (var_with_noise / var_clamp are set)", who);
@@ -612,6 +614,8 @@ int b7_score_grad_compute(b7_ctx *c, const b7_score_spec *spec, int S, const dou
   if (!spec || S < 1 || M1 < 0 || d < 1 || d > B7_MAX_D || (M1 > 0 && (!mean || !var || !dmean || !dvar || !value || !grad)))
     return b7_fail(c, B7_ERR_INVALID, "score_grad_compute: bad arguments");
   if (spec->kind == B7_SCORE_MES) return b7_fail(c, B7_ERR_UNSUPPORTED, "score_grad_compute: max-value entropy search has no gradient piece");
+  if (spec->kind == B7_SCORE_LOGPI)
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "score_grad_compute: log probability of improvement (LogPI) has no gradient piece");
   if (spec->kind != B7_SCORE_EI && spec->kind != B7_SCORE_CB && spec->kind != B7_SCORE_LOGEI)
     return b7_fail(c, B7_ERR_INVALID, "score_grad_compute: unknown score kind %d", spec->kind);
   if (score_needs_fmin(spec->kind) && !spec->fmin) return b7_fail(c, B7_ERR_INVALID, "score_grad_compute: EI needs fmin");

@@ -43,6 +43,31 @@
 // A y* found by the search keeps g >= -Phi^-1(1 - 1/(2K)) >= -2.5; with a caller's y* (b7_mes_compute) the accuracy bar holds for
 // g >= -8 and the value stays finite below.
 //
+// Log probability of improvement (B7_SCORE_LOGPI) has NO counterpart in the reference's scores/ either.  With EI's first three
+// operations -- sigma = sqrt(var); imprv = (fmin - mu) - xi; z = imprv/sigma -- the value is log Phi(z), evaluated so that it neither
+// underflows nor loses the upper tail (ocml's fp64 erfc, erfcx, log1p and log):
+//   z >= 0:       log1p(-erfc(z/sqrt2)/2)
+//   -1 < z < 0:   log(erfc(-z/sqrt2)/2)
+//   z <= -1:      (-z^2/2 - log 2) + log(erfcx(-z/sqrt2))
+// On a constraint's GP, with fmin = the threshold t_k and xi = 0, it is log Pr[c_k(x) <= t_k]: the log probability of feasibility of
+// Gelbart et al. 2014 / Gardner et al. 2014 in the log-space form of Ament et al. 2023.  The accumulator is the log one, as LogEI's:
+// the marginal is log((1/S) sum_s Phi(z_s)); c > 1 response columns fold as LogEI's do.  Row classes:
+//   var NaN or var < 0        NaN (sigma is NaN)            mu NaN                NaN
+//   var == 0, imprv >= 0      0.0                           var == 0, imprv < 0   -inf
+//   z = +inf (sigma > 0)      0.0                           z = -inf              -inf
+// A finite (mu, var, fmin, xi) with var >= 0 never scores NaN.  Beyond |z| ~ 1.3e154, z^2/2 overflows and the value is -inf.
+// Relative accuracy is not promised where |log Phi| < 1e-300 (z beyond ~37: erfc has underflowed, the value is -0.0).
+//
+// The feasibility column (b7_feas_*, b7_eval_nominate_feasible): a per-context vector L[M] of log-weights over the resident grid.
+// Between score:div and score:max(1) each row's score v becomes w(v, L[j]):
+//   log accumulator (LogEI, LogPI)   w = v + L            linear accumulator (EI)   w = v * exp(L)
+//   either operand NaN: NaN.  Otherwise L = -inf: -inf / 0.0 whatever v is, so that +inf - inf and inf * 0 are never formed for a
+//   masked row.  (A FINITE L whose exp underflows against v = +inf, or L = +inf against v = -inf, follow IEEE: NaN.)
+// score_finish_slot_feas_kernel is score_finish_slot_kernel with that one step ahead of the block reduction (the pending route of
+// the small regime stays one launch); feas_finish_kernel is finish_kernel with it (the routes whose score has already been added).
+// L is read, never written, by both.  That two contexts whose columns are combined (b7_feas_add_acc) hold the same grid rows is the
+// caller's contract: only the row COUNT can be checked.
+//
 // Every score kind is written ONCE, as the per-kind pieces below (hoist / value / row_sign over the accumulator algebra empty / fold /
 // div); the per-sample kernel, the S-batch kernel and the fused nomination kernel are templates over the kind that only arrange
 // those pieces, which is what makes the one-call nomination equal the per-sample loop bit for bit.
@@ -111,6 +136,27 @@ __device__ __forceinline__ double b7_logaddexp(double a, double v) {
   if (m == -INFINITY || n == INFINITY) return m;  // both -inf, both +inf: n - m would be NaN
   return m + log1p(exp(n + (-m)));
 }
+// ---- log probability of improvement (see the header) ----
+__device__ __forceinline__ double b7_logpi(double mu, double var, double fmin, double xi) {
+  const double sigma = sqrt(var);
+  const double imprv = (fmin + (-mu)) + (-xi);
+  const double z = imprv / sigma;
+  if (sigma == 0.0) return (imprv >= 0.0) ? 0.0 : ((imprv != imprv) ? imprv : -INFINITY);
+  if (z == INFINITY) return 0.0;
+  if (z == -INFINITY) return -INFINITY;
+  if (z >= 0.0) return log1p(erfc(z * 0.70710678118654752440) * -0.5);  // 1 - Phi(z) = erfc(z/sqrt2)/2
+  if (z > -1.0) return log(erfc(z * -0.70710678118654752440) * 0.5);    // Phi(z) = erfc(-z/sqrt2)/2
+  // z <= -1; NaN comes this way too, and stays NaN
+  return (((z * z) * -0.5) + -0.69314718055994530942) + log(erfcx(z * -0.70710678118654752440));
+}
+// ---- the feasibility weight (see the header): v = a row's score after score:div, L = its log-weight ----
+template <bool LOG>
+__device__ __forceinline__ double feas_weight(double v, double L) {
+  if (v != v || L != L) return v + L;
+  if (L == -INFINITY) return LOG ? -INFINITY : 0.0;
+  if constexpr (LOG) return v + L;
+  else return v * exp(L);
+}
 // ---- max-value entropy search (see the header): y = the sample's nlev quantiles of the grid minimum ----
 __device__ __forceinline__ double b7_mes(double mu, double var, const double *__restrict__ y, int nlev) {
   if (!(var >= 0.0) || mu != mu) return NAN;
@@ -136,7 +182,8 @@ __device__ __forceinline__ double div(double a, double divisor) {  // score:div,
   if constexpr (score_acc_kind(K) == B7_ACC_LOG) return a + (-log(divisor));
   else return a / divisor;
 }
-// what a candidate's variance contributes to every response column: sigma (EI), sqrt(var) * kappa (CB), the variance itself (LogEI, MES)
+// what a candidate's variance contributes to every response column: sigma (EI), sqrt(var) * kappa (CB), the variance itself (LogEI,
+// LogPI, MES)
 template <int K>
 __device__ __forceinline__ double hoist(double var, const ScoreParams &p) {
   if constexpr (K == B7_SCORE_EI) return sqrt(var);
@@ -155,6 +202,8 @@ __device__ __forceinline__ double value(double mu, double h, double fmin, const 
     return p.upper ? (mu + h) : (mu + (-h));
   } else if constexpr (K == B7_SCORE_MES) {
     return b7_mes(mu, h, p.ystar + (long long)s * p.nlev, p.nlev);
+  } else if constexpr (K == B7_SCORE_LOGPI) {
+    return b7_logpi(mu, h, fmin, p.tradeoff);
   } else {
     return b7_logei(mu, h, fmin, p.tradeoff);
   }
@@ -621,6 +670,65 @@ __global__ void __launch_bounds__(256)
   block_best_ticket_record(b, sh, &last, part, ticket, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
 }
 
+// The same with the feasibility column weighted in ahead of the block reduction (b7_eval_nominate_feasible): the row's score after
+// score:div becomes w(v, feas[j]) (see the header), and that is what the accumulator holds and the arg-max sees.
+template <int K>
+__global__ void __launch_bounds__(256)
+    score_finish_slot_feas_kernel(ScoreParams p, int fresh, double *__restrict__ acc, long long M, double divisor, Best *__restrict__ part,
+                                  unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank, int world,
+                                  long long offset, const double *__restrict__ grid, int d, int all_slots,
+                                  unsigned long long *__restrict__ host_rec, unsigned *__restrict__ host_done,
+                                  const double *__restrict__ feas) {
+  __shared__ Best sh[4];
+  __shared__ unsigned last;
+  Best b{0.0, -1};
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
+    const double v = div<K>(fold_samples<K>(p, j, fresh ? empty<K>() : acc[j]), divisor);
+    const double w = feas_weight<score_acc_kind(K) == B7_ACC_LOG>(v, feas[j]);
+    acc[j] = w;
+    Best cnd{w, j};
+    if (better(cnd, b)) b = cnd;
+  }
+  block_best_ticket_record(b, sh, &last, part, ticket, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
+}
+
+// finish_kernel with the feasibility column: acc[j] <- w(acc[j] / divisor, feas[j]) (a log accumulator: - log(divisor)), then the
+// per-block best; argmax_slot_kernel follows, a launch boundary away.
+__global__ void __launch_bounds__(256) feas_finish_kernel(double *__restrict__ acc, const double *__restrict__ feas, int64_t M,
+                                                          double divisor, Best *__restrict__ part, int logacc) {
+  __shared__ Best sh[4];
+  Best b{0.0, -1};
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
+    const double v = logacc ? acc[j] + (-log(divisor)) : acc[j] / divisor;
+    const double w = logacc ? feas_weight<true>(v, feas[j]) : feas_weight<false>(v, feas[j]);
+    acc[j] = w;
+    Best cnd{w, j};
+    if (better(cnd, b)) b = cnd;
+  }
+  b = block_best(b, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = b;
+}
+
+// the column's own kernels: L[j] += src[j] (b7_feas_add, b7_feas_add_acc) and the per-block best of L, which is only read
+// (b7_feas_nominate; argmax_final_kernel follows)
+__global__ void __launch_bounds__(256) feas_add_kernel(double *__restrict__ L, const double *__restrict__ src, int64_t M) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) L[j] = L[j] + src[j];
+}
+__global__ void __launch_bounds__(256) feas_best_kernel(const double *__restrict__ L, int64_t M, Best *__restrict__ part) {
+  __shared__ Best sh[4];
+  Best b{0.0, -1};
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
+    Best cnd{L[j], j};
+    if (better(cnd, b)) b = cnd;
+  }
+  b = block_best(b, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = b;
+}
+
 __global__ void __launch_bounds__(256) keep_record_kernel(unsigned long long *__restrict__ tab, int rank, int world) {
   for (int e = threadIdx.x; e < world * B7_TAB_W; e += blockDim.x)
     if (e / B7_TAB_W != rank) tab[e] = 0ull;
@@ -652,19 +760,21 @@ static int acc_mode_or_fail(b7_ctx *c, const double *out, bool accumulate, int k
   *mode = acc_mode(c, out, accumulate, kind);
   if (*mode < 0)
     return b7_fail(c, B7_ERR_STATE, "score: the accumulator holds a %s; a %s cannot be added onto it (b7_score_reset first)",
-                   c->acc_kind == B7_ACC_LOG ? "log-sum-exp (LogEI)" : "linear sum (EI / CB)",
+                   c->acc_kind == B7_ACC_LOG ? "log-sum-exp (LogEI / LogPI)" : "linear sum (EI / CB)",
                    kind == B7_ACC_LOG ? "log score" : "linear score");
   return B7_OK;
 }
 
-// THE step from a run-time score kind to its template instance: f(std::integral_constant<int, B7_SCORE_*>)
+// THE step from a run-time score kind to its template instance: f(std::integral_constant<int, B7_SCORE_*>).  An unknown kind would
+// run as CB: the entry points validate the kind (nominate_args, score_entry's fixed specs) before any launcher is reached
 template <class F>
 static void with_score_kind(int kind, F f) {
   switch (kind) {
     case B7_SCORE_EI: return f(std::integral_constant<int, B7_SCORE_EI>());
     case B7_SCORE_LOGEI: return f(std::integral_constant<int, B7_SCORE_LOGEI>());
     case B7_SCORE_MES: return f(std::integral_constant<int, B7_SCORE_MES>());
-    default: return f(std::integral_constant<int, B7_SCORE_CB>());
+    case B7_SCORE_LOGPI: return f(std::integral_constant<int, B7_SCORE_LOGPI>());
+    default: return f(std::integral_constant<int, B7_SCORE_CB>());  // (every launcher is reached only after nominate_args / its entry point has validated the kind)
   }
 }
 
@@ -673,7 +783,7 @@ int launch_score(b7_ctx *c, ScoreParams p, const double *mu, const double *var, 
   PhaseScope ps(c, "score");
   if (M <= 0) return B7_OK;
   if (score_needs_fmin(p.kind) && !p.fmin && ycols != 1)
-    return b7_fail(c, B7_ERR_INVALID, "%s: f_min of %d columns must be staged on the device", p.kind == B7_SCORE_EI ? "ei" : "logei", ycols);
+    return b7_fail(c, B7_ERR_INVALID, "%s: f_min of %d columns must be staged on the device", score_kind_name(p.kind), ycols);
   int mode;
   B7_TRY(acc_mode_or_fail(c, out, accumulate, score_acc_kind(p.kind), &mode));
   p.mu = mu, p.var = var, p.S = 1, p.stride = 0;
@@ -739,6 +849,42 @@ int acc_materialize(b7_ctx *c) {
   return B7_OK;
 }
 
+// ---- the feasibility column's state: set here and nowhere else ----
+void feas_forget(b7_ctx *c) { c->feas_valid = false; }
+
+// L := 0.0 over the resident grid
+int feas_write_zeros(b7_ctx *c) {
+  B7_TRY(b7_ensure(c, c->feas, sizeof(double) * (size_t)c->M));
+  B7_TRY(launch_fill(c, (double *)c->feas.p, c->M, 0.0));
+  c->feas_valid = true;
+  return B7_OK;
+}
+
+// L[j] += src[j], src a device vector of c->M doubles, on c's stream
+int launch_feas_add(b7_ctx *c, const double *src) {
+  PhaseScope ps(c, "feas");
+  hipLaunchKernelGGL(feas_add_kernel, dim3(nblocks(c, c->M)), dim3(256), 0, c->stream, (double *)c->feas.p, src, (int64_t)c->M);
+  B7_HIP(c, hipGetLastError());
+  return B7_OK;
+}
+
+// score:max(1) of L alone; L is read only
+int launch_feas_best(b7_ctx *c, double *best_val, int64_t *best_idx1) {
+  PhaseScope ps(c, "argmax");
+  const int nb = nblocks(c, c->M);
+  B7_TRY(b7_ensure(c, c->part, sizeof(Best) * (size_t)(nb + 1)));
+  Best *part = (Best *)c->part.p;
+  hipLaunchKernelGGL(feas_best_kernel, dim3(nb), dim3(256), 0, c->stream, (const double *)c->feas.p, (int64_t)c->M, part);
+  Best *res_dev = reinterpret_cast<Best *>(&c->pinned_dev->best);
+  const BestPair &h = c->pinned->best;
+  hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, c->stream, (const Best *)part, nb, res_dev);
+  B7_HIP(c, hipGetLastError());
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  if (best_val) *best_val = h.v;
+  if (best_idx1) *best_idx1 = h.i + 1;
+  return B7_OK;
+}
+
 int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *best_val, int64_t *best_idx1, bool logacc) {
   PhaseScope ps(c, "argmax");
   if (M <= 0) return b7_fail(c, B7_ERR_INVALID, "finish: empty score vector");
@@ -763,12 +909,15 @@ int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *bes
 // sets once that copy is complete (comm.hip: exch_local with a mirror).
 int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64_t *tab_dev, int rank, int world,
                        int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec, unsigned *host_done,
-                       bool logacc) {
+                       bool logacc, const double *feas) {
   PhaseScope ps(c, "argmax");
   const int nb = M > 0 ? nblocks(c, M) : 0;
   B7_TRY(b7_ensure(c, c->part, sizeof(Best) * (size_t)(nb + 1)));
   Best *part = (Best *)c->part.p;
-  if (nb > 0) hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, M, divisor, part, logacc ? 1 : 0);
+  if (nb > 0 && feas)
+    hipLaunchKernelGGL(feas_finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, feas, M, divisor, part, logacc ? 1 : 0);
+  else if (nb > 0)
+    hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, M, divisor, part, logacc ? 1 : 0);
   hipLaunchKernelGGL(argmax_slot_kernel, dim3(1), dim3(256), 0, c->stream, (const Best *)part, nb,
                      (unsigned long long *)tab_dev, rank, world, (long long)offset, (long long)M, grid, d, all_slots ? 1 : 0,
                      -1ll, (unsigned long long *)host_rec, host_done);
@@ -779,8 +928,10 @@ int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64
 // The fused form: the S-sample score, score:div, the local arg-max and the record in one launch.
 int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64_t M, double divisor, uint64_t *tab_dev,
                              int rank, int world, int64_t offset, const double *grid, int d, bool all_slots, uint64_t *host_rec,
-                             unsigned *host_done, const ExclRows *excl) {
+                             unsigned *host_done, const ExclRows *excl, const double *feas) {
   PhaseScope scope(c, "score");
+  if (feas && (p.kind == B7_SCORE_CB || p.kind == B7_SCORE_MES || (excl && excl->n > 0)))
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "score: the feasibility weight is built for EI, LogEI and LogPI, without excluded rows");
   // (one-wave blocks for small grids -- 313 instead of 79 workgroups for 2e4 candidates -- measured SLOWER: 145 vs 139 us per
   // nomination at N = 100, S = 10; the last block's pass over four times as many partials costs more than the spread saves.
   // Likewise the S scores of a candidate on S threads side by side, parked in LDS and added in order by one of them, over 512
@@ -797,6 +948,15 @@ int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64
   int mode;
   B7_TRY(acc_mode_or_fail(c, acc, true, score_acc_kind(p.kind), &mode));
   with_score_kind(p.kind, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    if constexpr (K == B7_SCORE_EI || K == B7_SCORE_LOGEI || K == B7_SCORE_LOGPI) {  // the kinds the weight has a form for
+      if (feas) {
+        hipLaunchKernelGGL(score_finish_slot_feas_kernel<K>, dim3(nb), dim3(threads), 0, c->stream, p, mode == 2 ? 1 : 0, acc, (long long)M,
+                           divisor, part, ticket, (unsigned long long *)tab_dev, rank, world, (long long)offset, grid, d,
+                           all_slots ? 1 : 0, (unsigned long long *)host_rec, host_done, feas);
+        return;
+      }
+    }
     if (excl && excl->n > 0)
       hipLaunchKernelGGL(score_finish_slot_excl_kernel<decltype(k)::value>, dim3(nb), dim3(threads), 0, c->stream, p, mode == 2 ? 1 : 0,
                          acc, (long long)M, divisor, part, ticket, (unsigned long long *)tab_dev, rank, world, (long long)offset, grid,

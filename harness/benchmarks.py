@@ -49,4 +49,19 @@ def rastrigin(X):
     return ((Z ** 2 + np.cos(Z * b) * -a).sum(1) + a * Z.shape[1]).reshape(-1, 1)
 
 
-registry = {"braninhoo": braninhoo, "hartmann6": hartmann6, "ackley": ackley, "rastrigin": rastrigin}
+GARDNER1_THRESHOLD = 0.5
+
+
+def gardner1(X):
+    """A CONSTRAINED toy (no counterpart in benchmarks/): the first simulation of Gardner et al., "Bayesian Optimization with
+    Inequality Constraints", ICML 2014.  With x = 6 X over [0, 6]^2: minimise cos(2 x1) cos(x2) + sin(x1) subject to
+    cos(x1) cos(x2) - sin(x1) sin(x2) <= 0.5.  Returns rows [y, c]: the objective and the constraint function, whose threshold is
+    GARDNER1_THRESHOLD (config.bot.constraints = [{"threshold": 0.5, "model": {...}}])."""
+    Z = _rows(X, 2) * 6.0
+    x1, x2 = Z[:, 0], Z[:, 1]
+    y = np.cos(2.0 * x1) * np.cos(x2) + np.sin(x1)
+    c = np.cos(x1) * np.cos(x2) - np.sin(x1) * np.sin(x2)
+    return np.stack([y, c], axis=1)
+
+
+registry = {"braninhoo": braninhoo, "hartmann6": hartmann6, "ackley": ackley, "rastrigin": rastrigin, "gardner1": gardner1}

@@ -19,7 +19,16 @@ b7_ts_nominate with a seed from the bot's own generator, and eval(want_scores=Tr
 config.bot.refine (ours; False = the reference's loop, untouched) is a dict of starts / iters / eta0: a model-based trial then goes
 through b7_eval_nominate_refine, which climbs the marginalised acquisition from the best grid rows inside the grid's box
 (config.grid.mins / maxes); the trial steals the grid row the winner started from, evaluates the objective at the refined point
-and observes that point.  What the library refuses is refused here by name (refine_refusal)."""
+and observes that point.  What the library refuses is refused here by name (refine_refusal).
+
+config.bot.constraints (ours; None = the reference's loop, untouched) is a list of {"threshold": t, "model": {...}}: CONSTRAINED
+nomination after Gelbart et al. 2014 / Gardner et al. 2014.  The objective returns a row [y, c_1 .. c_C]; the objective's model sees
+column 0, constraint model k -- a GP with a context and sampler state of its own -- column k.  Per model-based trial every
+constraint model samples its hypers, stages data and grid on its context and leaves log Pr[c_k(x) <= t_k], marginalised over its
+samples, in that context's accumulator (eval_nominate(score="logpi", fmin=[t_k], tradeoff=0)); the objective's context sums them
+into its feasibility column (feas_reset, feas_add_acc) and nominates with the weight (eval_nominate_feasible), fmin being the best
+response among the rows that satisfy every constraint -- or, while no row does, by feasibility alone (feas_nominate).  The stolen
+row leaves every context's resident grid.  What is not built is refused by name (constraint_refusal)."""
 import numpy as np
 
 from .abstract import abstract
@@ -48,6 +57,62 @@ def refine_refusal(config, model_class="bot7.models.gp_regressor", sharded=False
     return None
 
 
+CONSTRAINED_SCORES = ("expected_improvement", "log_expected_improvement", "log_probability_of_improvement")
+
+
+def constraint_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
+    """Why this configuration cannot nominate under config.bot.constraints (what b7_eval_nominate_feasible does not do, by name), or
+    None."""
+    if int(config["bot"].get("batch", 1)) > 1:
+        return "config.bot.constraints with config.bot.batch > 1: feasibility-weighted believer batches are not built"
+    if config["bot"].get("refine"):
+        return "config.bot.constraints with config.bot.refine: refinement of a constrained nominee is not built"
+    if sharded:
+        return "config.bot.constraints over sharded candidates: constrained nomination over a sharded grid is not built"
+    if model_class == "bot7.models.dngo":
+        return "config.bot.constraints with the dngo model: the Bayesian-linear head has no feasibility weight"
+    kind = config["score"]["type"]
+    if kind == "thompson_sampling":
+        return "config.bot.constraints with thompson_sampling: a sample path has no feasibility weight"
+    if kind == "confidence_bound":
+        return "config.bot.constraints with confidence_bound: a signed score has no product form with a feasibility weight"
+    if kind == "max_value_entropy_search":
+        return "config.bot.constraints with max_value_entropy_search: the score has no feasibility weight"
+    if kind not in CONSTRAINED_SCORES:
+        return "config.bot.constraints with %s: only %s are built" % (kind, ", ".join(CONSTRAINED_SCORES))
+    for k, con in enumerate(config["bot"]["constraints"]):
+        if (con.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
+            return "config.bot.constraints[%d] with the %s model: a constraint is modelled by a gp_regressor" % (k, con["model"]["type"])
+    return None
+
+
+def split_columns(responses, C):
+    """The objective's rows [y, c_1 .. c_C] -> (Y N x 1, [c_k N x 1 for each constraint])."""
+    R = np.asarray(responses, dtype=np.float64)
+    R = R.reshape(-1, 1 + C) if R.ndim < 2 else R
+    if R.shape[1] != 1 + C:
+        raise ValueError("config.bot.constraints: the objective must return rows of 1 + %d columns [y, c_1 .. c_C], got %d"
+                         % (C, R.shape[1]))
+    return np.ascontiguousarray(R[:, :1]), [np.ascontiguousarray(R[:, k:k + 1]) for k in range(1, C + 1)]
+
+
+def feasible_rows(responses, thresholds):
+    """Which observed rows satisfy every constraint, c_k <= t_k (a NaN satisfies nothing)."""
+    _, cols = split_columns(responses, len(thresholds))
+    ok = np.ones(cols[0].shape[0] if cols else np.asarray(responses).shape[0], dtype=bool)
+    for c, t in zip(cols, thresholds):
+        ok &= c[:, 0] <= float(t)
+    return ok
+
+
+def best_feasible_fmin(responses, thresholds):
+    """fmin of the constrained nomination: the best objective value among the feasible rows, as a 1-vector -- or None when no row
+    is feasible (the nomination then goes by feasibility alone)."""
+    Y, _ = split_columns(responses, len(thresholds))
+    ok = feasible_rows(responses, thresholds)
+    return np.array([Y[ok, 0].min()]) if ok.any() else None
+
+
 class bayesopt(abstract):
     title = "bot7.bots.bayesopt"
 
@@ -59,18 +124,11 @@ class bayesopt(abstract):
         self.score = cache.get("score") or Scores.registry[config["score"]["type"]](config["score"])  # :32
         self._rng = np.random.default_rng(config["bot"]["seed"])
         self.last_scores = None
+        self.constraints = None   # per constraint: threshold, model, ctx, grid (the DeviceGrid view of that context); set up on first use
 
     def configure(self, config):
         config = super().configure(config)
-        model = dict(config.get("model") or {})
-        model.setdefault("type", "gp_regressor")        # bots/bayesopt.lua:40
-        model.setdefault("kernel", "ardse")             # :41
-        model.setdefault("nzModel", "GaussianNoise_iso")  # :42
-        model.setdefault("mean", "constant")            # :43
-        model.setdefault("sampler", "slice")            # :44
-        if model["sampler"] == "slice_device":          # ours: the chain on the device draws a trial's samples in one launch
-            model["prefetch"] = config["bot"]["nSamples"]
-        config["model"] = model
+        config["model"] = self._model_defaults(config.get("model"), config["bot"]["nSamples"])
         score = dict(config.get("score") or {})
         score.setdefault("type", "expected_improvement")  # :49
         config["score"] = score
@@ -79,7 +137,26 @@ class bayesopt(abstract):
         if config["bot"]["refine"]:
             given = config["bot"]["refine"] if isinstance(config["bot"]["refine"], dict) else {}
             config["bot"]["refine"] = dict(REFINE_DEFAULTS, **given)
+        config["bot"].setdefault("constraints", None)   # ours: None, or a list of {"threshold": t, "model": {...}} (nominate_constrained)
+        if not config["bot"]["constraints"]:            # (an empty list constrains nothing: the reference's loop)
+            config["bot"]["constraints"] = None
+        if config["bot"]["constraints"] is not None:
+            config["bot"]["constraints"] = [{"threshold": float(c["threshold"]),
+                                             "model": self._model_defaults(c.get("model"), config["bot"]["nSamples"])}
+                                            for c in config["bot"]["constraints"]]
         return config
+
+    @staticmethod
+    def _model_defaults(model, nSamples):
+        model = dict(model or {})
+        model.setdefault("type", "gp_regressor")        # bots/bayesopt.lua:40
+        model.setdefault("kernel", "ardse")             # :41
+        model.setdefault("nzModel", "GaussianNoise_iso")  # :42
+        model.setdefault("mean", "constant")            # :43
+        model.setdefault("sampler", "slice")            # :44
+        if model["sampler"] == "slice_device":          # ours: the chain on the device draws a trial's samples in one launch
+            model["prefetch"] = nSamples
+        return model
 
     def eval(self, candidates=None, want_scores=True):
         """bots/bayesopt.lua:56-82.  Returns (scores or None, best_value, best_index_1based)."""
@@ -203,6 +280,113 @@ class bayesopt(abstract):
         self.last_scores = None
         return np.array(x, dtype=np.float64), int(start)
 
+    # ---- constrained nomination (config.bot.constraints) ----------------------------------------------------------------------
+    def _constrained(self):
+        """THE predicate: does this bot nominate under constraints (run_trial, update_best and progress_report all ask here)."""
+        return self.config["bot"].get("constraints") is not None
+
+    def _constraint_refusal(self):
+        return constraint_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
+
+    def _constraints_setup(self):
+        """One GP model with a context (same device) and sampler state of its own per constraint."""
+        if self.constraints is None:
+            from bot7_amd import Context
+            self.constraints = []
+            for con in self.config["bot"]["constraints"]:
+                ctx = Context(self.model.ctx.device_id)
+                self.constraints.append({"threshold": con["threshold"], "ctx": ctx, "grid": None,
+                                         "model": Models.registry[con["model"]["type"]](con["model"], context=ctx)})
+        return self.constraints
+
+    def _sample_hyps(self, model, X_obs, Y_obs):
+        model.sample_hypers(X_obs, Y_obs)                         # :68 (burn-in call)
+        return [model.parse_hypers(model.sample_hypers(X_obs, Y_obs, None, None, True))
+                for _ in range(self.config["bot"]["nSamples"])]   # :73-75
+
+    def nominate_constrained(self, candidates=None):
+        """The constrained nominee (module docstring) -> 1-based index into the candidates as they stand.  self.last_constrained
+        keeps what the call used: every model's hyper samples, fmin (None: feasibility alone) and the value."""
+        cand = self.candidates if candidates is None else candidates
+        why = self._constraint_refusal()
+        if why:
+            raise NotImplementedError(why)
+        if self.nTrials <= self.config["bot"]["nInitial"]:        # :90-91 floor(rand*M)+1
+            return int(np.floor(self._rng.random() * cand.shape[0])) + 1
+        cons = self._constraints_setup()
+        thresholds = [c["threshold"] for c in cons]
+        X_obs, model = self.observed, self.model
+        Y_obs, C_obs = split_columns(self.responses, len(cons))
+        host = np.asarray(cand, dtype=np.float64)
+        con_hyps = []
+        for con, Ck in zip(cons, C_obs):
+            hyps = self._sample_hyps(con["model"], X_obs, Ck)
+            if con["grid"] is None or con["grid"].version != con["ctx"].grid_version or not np.array_equal(np.asarray(con["grid"]), host):
+                con["ctx"].grid_upload(host)
+                con["grid"] = DeviceGrid(host, con["ctx"], con["ctx"].grid_version)
+            con["model"].stage(X_obs, Ck, con["grid"])
+            con["ctx"].eval_nominate(hyps, score="logpi", fmin=[con["threshold"]], tradeoff=0.0)   # log Pr[c_k <= t_k] in the accumulator
+            con_hyps.append(hyps)
+        hyps = self._sample_hyps(model, X_obs, Y_obs)
+        model.stage(X_obs, Y_obs, cand)
+        ctx = model.ctx
+        ctx.feas_reset()
+        for con in cons:
+            ctx.feas_add_acc(con["ctx"])
+        fmin = best_feasible_fmin(self.responses, thresholds)
+        if fmin is None:                                          # no feasible observation yet: Gelbart et al. 2014, section 3.2
+            val, idx = ctx.feas_nominate()
+        else:
+            spec = dict(self.score.device_spec(Y_obs), fmin=fmin)
+            val, idx = ctx.eval_nominate_feasible(hyps, **spec)
+        self.last_scores = None
+        self.last_constrained = {"hyps": hyps, "constraint_hyps": con_hyps, "fmin": fmin, "value": val, "index": int(idx)}
+        return int(idx)
+
+    def _run_trial_constrained(self):
+        """bots/abstract.lua:112-152 with the constrained nominee: the stolen row (:118) leaves every constraint context's resident
+        grid too, the objective's row [y, c_1 .. c_C] is kept whole (:137-141), and at nInitial every model is initialised on its
+        own column (:147-149)."""
+        why = self._constraint_refusal()
+        if why:
+            raise NotImplementedError(why)
+        self.nTrials += 1
+        idx = self.nominate_constrained()                          # :117
+        self._steal_candidate(idx)                                 # :118
+        for con in self.constraints or []:
+            if con["grid"] is not None and con["grid"].version == con["ctx"].grid_version:
+                con["ctx"].grid_remove(idx)
+                con["grid"] = DeviceGrid(np.asarray(self.candidates), con["ctx"], con["ctx"].grid_version)
+        k = self.pending.shape[0]
+        nominee = self.pending[k - 1]
+        C = len(self.config["bot"]["constraints"])
+        y = np.asarray(self.objective(nominee), dtype=np.float64).reshape(1, -1)   # :124
+        split_columns(y, C)                                        # (the shape check)
+        self.responses = y if self.responses is None else np.concatenate([self.responses, y], 0)
+        self.observed, self.pending = T.steal(self.observed, self.pending, [k])  # :143-144
+        if self.model is not None and self.nTrials == self.config["bot"]["nInitial"]:
+            Y_obs, C_obs = split_columns(self.responses, C)
+            self.model.init(self.observed, Y_obs)                  # :147-149
+            for con, Ck in zip(self._constraints_setup(), C_obs):
+                con["model"].init(self.observed, Ck)
+        return nominee, y
+
+    def update_best(self, x, y):
+        """bots/abstract.lua:171-177; under constraints the best is the best FEASIBLE trial (column 0 among the rows with c_k <= t_k)."""
+        if not self._constrained():
+            return super().update_best(x, y)
+        y = np.asarray(y, dtype=np.float64).reshape(1, -1)
+        if feasible_rows(y, [c["threshold"] for c in self.config["bot"]["constraints"]])[0] and (
+                self.best.get("y") is None or float(np.ravel(self.best["y"])[0]) > y[0, 0]):
+            self.best["t"], self.best["x"], self.best["y"] = self.nTrials, x, y
+
+    def progress_report(self, t, x, y):
+        if self._constrained() and self.best.get("y") is None:
+            if self.config["bot"]["verbose"] > 0 and t % self.config["bot"]["msg_freq"] == 0:
+                print("trial %4d  y = %-14.8g (no feasible trial yet)" % (t, float(np.ravel(y)[0])))
+            return
+        super().progress_report(t, x, y)
+
     def _run_trial_refined(self):
         """bots/abstract.lua:112-152 with the nominee refined off the grid: the grid row the winner started from is stolen (:118),
         so the grid stops offering that neighbourhood; the objective is evaluated at the refined point (:124) and that point is
@@ -226,6 +410,8 @@ class bayesopt(abstract):
     def run_trial(self):
         """bots/abstract.lua:112-152 with config.bot.batch nominees per trial: all of them are stolen from the candidates in one
         stable pass (:118), evaluated and observed (:124-144).  batch = 1 is the parent's loop, untouched."""
+        if self._constrained():
+            return self._run_trial_constrained()
         if self.config["bot"]["refine"]:
             return self._run_trial_refined()
         q = int(self.config["bot"]["batch"])

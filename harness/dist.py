@@ -145,6 +145,8 @@ class ShardedScorer(object):
                     self.ctx.score_ei(spec["fmin"], spec.get("tradeoff") or 0.0)
                 elif spec["score"] == "logei":
                     self.ctx.score_logei(spec["fmin"], spec.get("tradeoff") or 0.0)
+                elif spec["score"] == "logpi":
+                    self.ctx.score_logpi(spec["fmin"], spec.get("tradeoff") or 0.0)
                 else:
                     self.ctx.score_cb(spec.get("tradeoff", 1.0), spec.get("upper", False), spec.get("sign", -1.0))
         return self.nominate(float(len(hyps)), device=device, group=group)

@@ -323,6 +323,17 @@ int b7_score_cb(b7_ctx *ctx, double tradeoff, int upper, double sign);
  * mean of the logs; ycols > 1 (fantasies): the log of the row mean of EI.  The first add after b7_score_reset decides
  * whether the accumulator is linear (b7_score_ei / _cb) or logarithmic; adding the other kind onto it is B7_ERR_STATE. */
 int b7_score_logei(b7_ctx *ctx, const double *fmin, double tradeoff);
+/* Log probability of improvement of the last predict -- NO counterpart in scores/ of the reference.  With sigma, imprv and z as
+ * b7_score_ei forms them the value is log Phi(z), evaluated so that it neither underflows nor loses the upper tail:
+ * log1p(-erfc(z/sqrt2)/2) for z >= 0, log(erfc(-z/sqrt2)/2) for -1 < z < 0, (-z^2/2 - log 2) + log(erfcx(-z/sqrt2)) for z <= -1;
+ * finite and ordered down to z ~ -1.3e154 (z^2/2 overflows: -inf), never NaN for finite inputs with var >= 0.  var == 0: 0.0 for
+ * imprv >= 0, else -inf; z = +inf: 0.0; z = -inf: -inf; var < 0, var NaN or mean NaN: NaN.  Relative accuracy is not promised where
+ * |log Phi| < 1e-300 (z beyond ~37).  As an acquisition it is log-PI; on the GP of a constraint c_k, with fmin = the threshold t_k
+ * and tradeoff = 0, it is the log probability of feasibility log Pr[c_k(x) <= t_k] (Gelbart et al. 2014, Gardner et al. 2014; the
+ * log-space form of Ament et al. 2023).  The accumulator is a log one, exactly as b7_score_logei's: the marginal is
+ * log((1/S) sum_s Phi(z_s)); ycols > 1: the log of the row mean.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+int b7_score_logpi(b7_ctx *ctx, const double *fmin, double tradeoff);
 /* Max-value entropy search of the last predict -- NO counterpart in scores/ of the reference (Wang & Jegelka, "Max-value
  * Entropy Search for Efficient Bayesian Optimization", ICML 2017): the expected reduction of the entropy of the optimum's VALUE.
  * The library minimises, so the paper's maximum is the minimum y*, and its distribution is that of the minimum over the
@@ -455,6 +466,14 @@ int b7_exchange_info(b7_ctx *ctx, int *world, int64_t *rows_per_rank, int64_t *w
  * b7_eval_nominate_batch, more than one response column.
  * Added without a change of B7_ABI_VERSION: the change is additive. */
 #define B7_SCORE_MES 4
+/* Log probability of improvement, as b7_score_logpi: log Phi(z); fmin and tradeoff as for B7_SCORE_EI, upper and sign ignored; a
+ * log accumulator, as B7_SCORE_LOGEI's.  Which entry point does what with it:
+ *   accepted   b7_eval_nominate (every route, the jitter redo included; equals the loop { b7_gp_predict_hyp; b7_score_logpi } x S
+ *              + b7_score_finish(S) bit for bit), b7_eval_nominate_feasible, b7_eval_nominate_batch, b7_group_eval_nominate,
+ *              b7_blr_eval_nominate, b7_blr_eval_nominate_marg (all templates over the kind)
+ *   refused    b7_eval_nominate_refine and b7_score_grad_compute: B7_ERR_UNSUPPORTED, "no gradient piece"
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_SCORE_LOGPI 5
 typedef struct {
   int kind;
   double tradeoff;
@@ -464,6 +483,45 @@ typedef struct {
 } b7_score_spec;
 int b7_eval_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset,
                      double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out);
+
+/* ---- constrained nomination: the feasibility column and the weighted arg-max ------------------- *
+ * No counterpart in the reference.  Gelbart et al. 2014 and Gardner et al. 2014 weight the acquisition by the probability that
+ * every constraint c_k(x) <= t_k holds, EIC(x) = EI(x) prod_k Pr[c_k(x) <= t_k], each constraint with a GP and hyper samples of
+ * its own; in log space (Ament et al. 2023) log EI + sum_k log PoF_k, which still ranks where the product underflows.
+ * A context carries a device vector L[M] of LOG-WEIGHTS over its resident grid, allocated on demand, freed with the context and
+ * FORGOTTEN whenever the grid changes (upload, generation, removal, commit, a one-sided map), as the accumulator is.
+ *   b7_feas_reset     L := 0.0.  B7_ERR_STATE without a grid.
+ *   b7_feas_add       L[j] += logw[j] from a host vector of M entries; M must be the grid's row count (B7_ERR_INVALID).  -inf
+ *                     masks a row.  The general door for known constraints, masks and penalties.
+ *   b7_feas_add_acc   L[j] += src's accumulator, device to device, no host copy.  src must be on the same device
+ *                     (B7_ERR_UNSUPPORTED otherwise) and hold a valid, materialised LOG accumulator (B7_ERR_STATE otherwise) of
+ *                     the same M (B7_ERR_INVALID otherwise): what b7_eval_nominate(src, ..., B7_SCORE_LOGPI) leaves, the marginal
+ *                     already divided.  The two streams are ordered by events, both ways.  That both contexts hold the SAME GRID
+ *                     ROWS is the caller's contract: only the row count can be checked.
+ *   b7_feas_get       download L (M entries).
+ *   b7_feas_nominate  score:max(1) of L alone (first NaN wins, else the first maximum); L is left untouched.  The nomination
+ *                     while no feasible observation exists (Gelbart et al. 2014, section 3.2).
+ * All but b7_feas_reset answer B7_ERR_STATE without a valid column; all answer B7_ERR_STATE on a member of a group.
+ *   b7_eval_nominate_feasible   b7_eval_nominate with global_row_offset = 0 in every respect -- the routes, the single host wait,
+ *                     the jitter redo behind a failed pivot, jitter_out / info_out -- except that between score:div and
+ *                     score:max(1) each row's score v becomes w(v, L[j]):
+ *                       a log accumulator (B7_SCORE_LOGEI, B7_SCORE_LOGPI)   w = v + L
+ *                       B7_SCORE_EI                                          w = v * exp(L)
+ *                     NaN if either operand is NaN; otherwise L = -inf gives -inf / 0.0 whatever v is (+inf - inf is never
+ *                     formed).  The accumulator holds the WEIGHTED score afterwards; L is read, not modified.
+ *                     B7_ERR_STATE: no valid column; a member of a group.  B7_ERR_UNSUPPORTED, the case named: B7_SCORE_CB (a
+ *                     signed score has no product form), B7_SCORE_MES, more than one response column, a communicator of more
+ *                     than one rank.
+ * Not built in this version: sharded grids and groups, feasibility-weighted believer batches, refinement, Thompson paths,
+ * decoupled evaluation of objective and constraints, the BLR head.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+int b7_feas_reset(b7_ctx *ctx);
+int b7_feas_add(b7_ctx *ctx, const double *logw, int64_t M);
+int b7_feas_add_acc(b7_ctx *ctx, b7_ctx *src);
+int b7_feas_get(b7_ctx *ctx, double *out /*M*/);
+int b7_feas_nominate(b7_ctx *ctx, double *best_val, int64_t *best_idx1);
+int b7_eval_nominate_feasible(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *best_val,
+                              int64_t *best_idx1, double *jitter_out, int *info_out);
 
 /* A greedy BATCH of q nominees from one call: b7_eval_nominate's pick, then q - 1 more by KRIGING-BELIEVER variance downdates.
  * No counterpart in the reference, whose bots nominate one point per trial (bots/abstract.lua:118).  The believer pretends that
@@ -675,6 +733,10 @@ int b7_cb_compute(b7_ctx *ctx, const double *mean, const double *var, double tra
  * out[j] = log(sigma_j) + log(phi(z) + z Phi(z)), z = ((fmin - mean_j) - tradeoff) / sigma_j, evaluated as b7_score_logei
  * describes; c > 1 columns: out[j] = log((1/c) sum_k EI_jk) by log-sum-exp over the columns. */
 int b7_logei_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff,
+                     int64_t M, int c, double *out);
+/* b7_logei_compute's sibling for the log probability of improvement: out[j] = log Phi(z), z as above, evaluated as
+ * b7_score_logpi describes; c > 1 columns: out[j] = log((1/c) sum_k Phi(z_jk)) by log-sum-exp over the columns. */
+int b7_logpi_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff,
                      int64_t M, int c, double *out);
 int b7_argmax(b7_ctx *ctx, const double *scores, int64_t M, double *best_val, int64_t *best_idx1);
 

@@ -60,6 +60,7 @@ int b7_score_reset(b7_ctx *ctx);
 int b7_score_ei(b7_ctx *ctx, const double *fmin, double tradeoff);
 int b7_score_cb(b7_ctx *ctx, double tradeoff, int upper, double sign);
 int b7_score_logei(b7_ctx *ctx, const double *fmin, double tradeoff);
+int b7_score_logpi(b7_ctx *ctx, const double *fmin, double tradeoff);
 int b7_score_mes(b7_ctx *ctx);
 int b7_mes_set_levels(b7_ctx *ctx, int K);
 int b7_mes_last_ystar(b7_ctx *ctx, int *S, int *K, double *ystar, double *bracket);
@@ -78,6 +79,12 @@ int b7_shard_commit_rule(int64_t idx1_global, int64_t offset, int64_t M_local, i
 int b7_exchange_info(b7_ctx *ctx, int *world, int64_t *rows_per_rank, int64_t *winner_idx1, int *winner_rank, double *winner_row);
 typedef struct { int kind; double tradeoff; int upper; double sign; const double *fmin; } b7_score_spec;
 int b7_eval_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out);
+int b7_feas_reset(b7_ctx *ctx);
+int b7_feas_add(b7_ctx *ctx, const double *logw, int64_t M);
+int b7_feas_add_acc(b7_ctx *ctx, b7_ctx *src);
+int b7_feas_get(b7_ctx *ctx, double *out );
+int b7_feas_nominate(b7_ctx *ctx, double *best_val, int64_t *best_idx1);
+int b7_eval_nominate_feasible(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *best_val, int64_t *best_idx1, double *jitter_out, int *info_out);
 int b7_eval_nominate_batch(b7_ctx *ctx, int S, const b7_hyp *hyps, const b7_score_spec *spec, int q, double *best_val , int64_t *best_idx1 , double *jitter_out, int *info_out);
 typedef struct { int starts; int iters; double eta0; const double *lo; const double *hi; } b7_refine_opts;
 int b7_refine_default_opts(b7_refine_opts *out);
@@ -116,6 +123,7 @@ int b7_group_nominate_commit(b7_group *g, int64_t idx1_global, double *row_out);
 int b7_ei_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M, int c, double *out);
 int b7_cb_compute(b7_ctx *ctx, const double *mean, const double *var, double tradeoff, int upper, double sign, int64_t M, int c, double *out);
 int b7_logei_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M, int c, double *out);
+int b7_logpi_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M, int c, double *out);
 int b7_argmax(b7_ctx *ctx, const double *scores, int64_t M, double *best_val, int64_t *best_idx1);
 int b7_timer_start(b7_ctx *ctx, int slot);
 int b7_timer_stop(b7_ctx *ctx, int slot);
@@ -156,6 +164,7 @@ M.SCORE_EI = 1
 M.SCORE_CB = 2
 M.SCORE_LOGEI = 3
 M.SCORE_MES = 4
+M.SCORE_LOGPI = 5
 M.BATCH_MAX = 16
 M.REFINE_MAX_STARTS = 16
 M.REFINE_MAX_ITERS = 256
@@ -175,6 +184,7 @@ if C.b7_create(ctxp, dev) ~= 0 then
   error('bot7hip: ' .. ffi.string(C.b7_last_error(nil)))   -- hard error: there is no CPU fallback
 end
 M.ctx = ffi.gc(ctxp[0], C.b7_destroy)
+M.device = dev   -- the device M.ctx sits on: further contexts of this process (a constraint's model) are created there
 
 -- status -> Lua error(), the reference's hard-error convention (utils/math.lua:168 pcall catches it)
 function M.check(rc)

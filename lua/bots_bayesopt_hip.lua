@@ -35,10 +35,12 @@ end
 -- b7_score_spec of a *_hip score object, or nil when the score has no device form
 local function score_spec(score, Y_obs, keep)
   local cfg, kind = score.config or {}, torch.type(score)
-  if kind == 'bot7.scores.expected_improvement_hip' or kind == 'bot7.scores.log_expected_improvement_hip' then
+  if kind == 'bot7.scores.expected_improvement_hip' or kind == 'bot7.scores.log_expected_improvement_hip'
+     or kind == 'bot7.scores.log_probability_of_improvement_hip' then
     local fmins = hip.pin(Y_obs:min(1):view(-1))            -- scores/expected_improvement.lua:64
     keep[#keep + 1] = fmins
     local code = (kind == 'bot7.scores.expected_improvement_hip') and hip.SCORE_EI or hip.SCORE_LOGEI   -- log-space EI: no original
+    if kind == 'bot7.scores.log_probability_of_improvement_hip' then code = hip.SCORE_LOGPI end          -- log PI: no original
     return ffi.new('b7_score_spec', {code, cfg.tradeoff or 0.0, 0, 0.0, hip.data(fmins)})
   elseif kind == 'bot7.scores.max_value_entropy_search_hip' then   -- no original; one GPU only (a sharded grid answers "unsupported")
     hip.check(hip.C.b7_mes_set_levels(hip.ctx, cfg.nLevels or 8))
@@ -205,6 +207,114 @@ function bot:nominate_refine(candidates)
   hip.check(hip.C.b7_eval_nominate_refine(hip.ctx, S, hyps, spec, opts, v, i, hip.data(x), rv, ri, jit, info))
   self.best_score = rv[0]
   return x, tonumber(ri[0])
+end
+
+-- S hyper tables of `model` over (X_obs, Y_obs) as a b7_hyp array, sampled as bots/bayesopt.lua:68,73-75 does
+local function sample_hyps(model, X_obs, Y_obs, S, keep)
+  model:sample_hypers(X_obs, Y_obs)                                          -- :68
+  local hyps = ffi.new('b7_hyp[?]', S)
+  for s = 1, S do                                                            -- :73-75
+    local hyp = model:parse_hypers(model:sample_hypers(X_obs, Y_obs, nil, nil, true))
+    local ls  = hip.pin(hyp.lenscale_sq)
+    keep[#keep + 1] = ls
+    hyps[s-1].lenscale_sq, hyps[s-1].amp, hyps[s-1].noise, hyps[s-1].mean = hip.data(ls), hyp.amp, hyp.noise, hyp.mean
+  end
+  return hyps
+end
+
+-- fn() with the library's current context switched to a constraint's own, together with EVERY per-context cache bot7hip_ffi
+-- keeps beside it: the "resident grid" record and the covariance kernel last set (hip.set_kernel skips the library when the
+-- code equals its cache: with the objective's cache left in place a Matern constraint model on a new context, which starts
+-- on ARD-SE, would never reach b7_gp_set_kernel)
+local function on_context(con, fn)
+  local ctx0, res0, ker0 = hip.ctx, hip.resident, hip.kernel
+  hip.ctx, hip.resident, hip.kernel = con.ctx, con.resident, con.kernel
+  local ok, err = pcall(fn)
+  con.resident, con.kernel = hip.resident, hip.kernel
+  hip.ctx, hip.resident, hip.kernel = ctx0, res0, ker0
+  if not ok then error(err, 2) end
+end
+
+-- The driver has stolen the row this bot nominated last (bots/abstract.lua:118) and self.candidates is a NEW host tensor, one
+-- row shorter: the same stable deletion on the constraint's context, whose "resident grid" record then names the new tensor, so
+-- that model:stage uploads nothing (the steal hook does this for hip.ctx alone).  Anything else -- another shape, no nominee on
+-- record -- forgets the record and the grid is uploaded again.
+local function follow_steal(con, idx, candidates)
+  local r = con.resident
+  if r == nil then return end
+  if idx ~= nil and candidates:isContiguous() and r.rows == candidates:size(1) + 1 and r.cols == candidates:size(2) then
+    local arr = ffi.new('int64_t[1]', idx)
+    hip.check(hip.C.b7_grid_remove_rows(con.ctx, arr, 1, nil))
+    con.resident = {ptr = torch.data(candidates), rows = candidates:size(1), cols = candidates:size(2)}
+  elseif not (r.rows == candidates:size(1) and r.ptr == torch.data(candidates)) then
+    con.resident = nil
+  end
+end
+
+-- CONSTRAINED nomination (b7_eval_nominate_feasible; no counterpart in the reference; Gelbart et al. 2014, Gardner et al. 2014):
+-- config.bot.constraints = {{threshold = t_1, model = {...}}, ...}; the objective returns a row {y, c_1 .. c_C}; self.responses
+-- keeps all 1 + C columns.  self.constraints[k] = {threshold, model (a gp_hip), ctx (a context of its own)} is set up on first
+-- use.  Per model-based trial every constraint model samples its hypers and stages data and grid on ITS context, where
+-- b7_eval_nominate(LogPI, fmin = t_k, tradeoff 0) leaves log Pr[c_k <= t_k] in the accumulator; the objective's context sums them
+-- into its feasibility column (b7_feas_reset, b7_feas_add_acc) and nominates with the weight, fmin = the best response among the
+-- rows that satisfy every constraint -- or by feasibility alone (b7_feas_nominate) while there is none.  The driver steals the
+-- returned row from self.candidates (bots/abstract.lua:118: the contract follow_steal relies on); the next call deletes it from
+-- every constraint context's grid before anything is staged there.  One rank, no group, EI / LogEI / LogPI; at parity with
+-- harness/bots/bayesopt.py's nominate_constrained.
+function bot:nominate_constrained(candidates)
+  local candidates = candidates or self.candidates
+  assert(D.world == 1 and not hip.group, 'nominate_constrained: one rank, no group (sharded constrained nomination is not built)')
+  local cons = assert(self.config.bot.constraints, 'nominate_constrained: config.bot.constraints is not set')
+  if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91
+    return torch.rand(1):mul(candidates:size(1)):long():add(1)
+  end
+  local model, keep = self.model, {}
+  assert(torch.type(model) == 'bot7.models.gp_hip', 'nominate_constrained: needs the gp_hip model')
+  local R, S = self.responses, self.config.bot.nSamples
+  local X_obs, Y_obs = self.observed, R:narrow(2, 1, 1):contiguous()
+  if self.constraints == nil then
+    self.constraints = {}
+    for k, cfg in ipairs(cons) do
+      local ctxp = ffi.new('b7_ctx*[1]')
+      assert(hip.C.b7_create(ctxp, hip.device) == 0, 'nominate_constrained: b7_create failed')   -- the objective's device
+      self.constraints[k] = {threshold = cfg.threshold, model = bot7.models.gp_hip(cfg.model), ctx = ffi.gc(ctxp[0], hip.C.b7_destroy),
+                             kernel = hip.KERNEL_ARDSE}   -- a new context starts on ARD-SE: the constraint's own kernel cache
+    end
+  end
+  local feasible = torch.ByteTensor(R:size(1)):fill(1)
+  for k, con in ipairs(self.constraints) do
+    local C_obs = R:narrow(2, k + 1, 1):contiguous()
+    feasible:cmul(C_obs:view(-1):le(con.threshold))
+    follow_steal(con, self.constrained_idx, candidates)
+    on_context(con, function()
+      if not con.inited then con.model:init(X_obs, C_obs); con.inited = true end
+      local hyps = sample_hyps(con.model, X_obs, C_obs, S, keep)
+      con.model:stage(X_obs, C_obs, candidates)
+      hip.set_kernel(con.model.kernel_code)
+      local t = hip.pin(torch.Tensor{con.threshold})
+      keep[#keep + 1] = t
+      local spec = ffi.new('b7_score_spec', {hip.SCORE_LOGPI, 0.0, 0, 0.0, hip.data(t)})
+      local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
+      hip.check(hip.C.b7_eval_nominate(hip.ctx, S, hyps, spec, 0, v, i, nil, nil))
+    end)
+  end
+  local hyps = sample_hyps(model, X_obs, Y_obs, S, keep)
+  model:stage(X_obs, Y_obs, candidates)
+  hip.set_kernel(model.kernel_code)
+  hip.check(hip.C.b7_feas_reset(hip.ctx))
+  for _, con in ipairs(self.constraints) do hip.check(hip.C.b7_feas_add_acc(hip.ctx, con.ctx)) end
+  local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
+  if feasible:sum() == 0 then                                                -- Gelbart et al. 2014, section 3.2
+    hip.check(hip.C.b7_feas_nominate(hip.ctx, v, i))
+  else
+    local Y_feas = Y_obs:index(1, feasible:nonzero():view(-1))
+    local spec = assert(score_spec(self.score, Y_feas, keep), 'nominate_constrained: needs a *_hip score')
+    local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+    hip.check(hip.C.b7_eval_nominate_feasible(hip.ctx, S, hyps, spec, v, i, jit, info))
+  end
+  self.best_score = v[0]
+  self.constrained_idx = tonumber(i[0])   -- what the driver steals next: follow_steal
+  return torch.LongTensor{self.constrained_idx}
 end
 
 -- bots/abstract.lua:112-152 for candidates sharded one process per GPU.  Only line 118 differs: `idx` is 1-based in the

@@ -3,6 +3,7 @@ Drop-ins for bot7.scores.expected_improvement / confidence_bound (scores/*.lua) 
 Register:  local S = require('bot7hip.scores_hip')
            bot7.scores.expected_improvement = S.expected_improvement ; bot7.scores.confidence_bound = S.confidence_bound
 S.max_value_entropy_search has no original either (b7_score_mes; Wang & Jegelka, ICML 2017): register it as a new score.
+S.log_probability_of_improvement has no original either (b7_score_logpi): log Phi(z), a constraint's log probability of feasibility.
 S.log_expected_improvement has no original to replace: log-space EI (b7_score_logei; Ament et al., NeurIPS 2023), which still
 ranks the candidates where EI has underflowed to 0.  Register it as a new score: bot7.scores.log_expected_improvement = ...
 They return the M-element score tensor like the originals (bots/bayesopt.lua:76 adds it); with a gp_hip model the
@@ -85,6 +86,32 @@ do
     return finish(X_hid:size(1))
   end
   S.log_expected_improvement = LEI
+end
+
+do
+  -- log PI = log Phi(z) (b7_score_logpi; no original).  On a constraint's model, with Y_obs' minimum replaced by the threshold
+  -- (config.threshold) and tradeoff 0, it is that constraint's log probability of feasibility: what bots_bayesopt_hip's
+  -- nominate_constrained adds onto the feasibility column.  A LOG score like log EI: meant for the fused nomination, which
+  -- marginalises by log-sum-exp on the device.  No pending points: one response column
+  local LPI, parent = torch.class('bot7.scores.log_probability_of_improvement_hip', 'bot7.scores.abstract')
+  function LPI:__init(config)
+    parent.__init(self)
+    local config = config or {}
+    config['tradeoff'] = config.tradeoff or 0.0
+    self.config = config
+  end
+  function LPI:__call__(model, hyp, X_obs, Y_obs, X_hid, X_pend, config)
+    local hyp, config = hyp or model.hyp, config or self.config
+    if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
+    assert(not (torch.isTensor(X_pend) and X_pend:dim() > 0 and X_pend:size(1) > 0),
+           'log_probability_of_improvement_hip: pending points (fantasies) are not supported')
+    model:predict_device(X_obs, Y_obs, X_hid, hyp)
+    local fmins = hip.pin(config.threshold and torch.Tensor{config.threshold} or Y_obs:min(1):view(-1))
+    hip.check(hip.C.b7_score_reset(hip.ctx))
+    hip.check(hip.C.b7_score_logpi(hip.ctx, hip.data(fmins), config.tradeoff or 0.0))
+    return finish(X_hid:size(1))
+  end
+  S.log_probability_of_improvement = LPI
 end
 
 do
