@@ -340,6 +340,32 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
 // b7_create, like every switch): 128 always.
 int npad_of(const b7_ctx *c, int64_t n);
 
+// ---- where fits live ----------------------------------------------------------------------------------------
+// A read-only view of S >= 1 fits of the resident data, side by side on the device: what every posterior launcher is told instead
+// of reading the context's fit fields.  Sample s sits at base + s * stride; THE STRIDES ARE WRITTEN HERE AND NOWHERE ELSE on the
+// host.  The fit scalars come in one of two forms: on the host (amp_dev == nullptr; one fit), or as device arrays of S entries
+// (the HypPack of c->bhyp).  It owns nothing.  Built by ctx_fit / batch_fits / fit_at alone.
+struct FitSet {
+  const double *w = nullptr, *zsc = nullptr, *zss = nullptr, *Linv = nullptr, *alpha = nullptr;
+  int S = 1, Npad = 0, dpad = 0;  // the padded shape of the data the fits are of (the context's, when the view was made)
+  double amp = 0.0, noise = 0.0, mean = 0.0;
+  const double *amp_dev = nullptr, *noise_dev = nullptr, *mean_dev = nullptr;
+  static int64_t s_w(int, int dpad) { return dpad; }
+  static int64_t s_zsc(int Npad, int dpad) { return (int64_t)Npad * dpad; }
+  static int64_t s_zss(int Npad, int) { return Npad; }
+  static int64_t s_Linv(int Npad, int) { return (int64_t)Npad * Npad; }
+  static int64_t s_alpha(int Npad, int) { return Npad; }
+};
+// the context's own slot: what the fit producers (fit_front, launch_potrf*, launch_alpha, launch_fit_small) leave
+static inline FitSet ctx_fit(const b7_ctx *c) {
+  FitSet f;
+  f.w = (const double *)c->w.p, f.zsc = (const double *)c->zsc.p, f.zss = (const double *)c->zss.p;
+  f.Linv = (const double *)c->Linv.p, f.alpha = (const double *)c->alpha.p;
+  f.Npad = c->Npad, f.dpad = c->dpad;
+  f.amp = c->amp, f.noise = c->noise, f.mean = c->mean;
+  return f;
+}
+
 // ---- kernel launchers (each enqueues on c->stream and returns a B7 code) ----------------------------
 // sobol.hip
 int launch_sobol(b7_ctx *c, double *out, int64_t size, int dims, int64_t skip, const double *mins,
@@ -373,12 +399,12 @@ int launch_prep_obs_aux(b7_ctx *c, const double *xobs, const double *ls_dev, int
 int launch_k_generic(b7_ctx *c, const double *xq, int64_t rows, int64_t Mtotal, const ObsSet &o, double *out);
 int launch_prep_obs(b7_ctx *c, const double *xobs, const double *lenscale_sq_dev, int N, int d);
 int launch_kxx(b7_ctx *c, double diag_add);
-int launch_ksx_batch(b7_ctx *c, int S, const double *xq, int64_t rows, int64_t Mtotal, const double *w, const double *zsc,
-                     const double *zss, const double *amp_dev, const double *mean_dev, const double *alpha, double *ks,
-                     int64_t s_out, double *mu, int64_t s_mu);
+// K(X*,X) and the mean of f's S fits (device scalars) over the same rows in one launch: K*_s = ks + s s_out, mu_s = mu + s s_mu
+int launch_ksx_batch(b7_ctx *c, const FitSet &f, const double *xq, int64_t rows, int64_t Mtotal, double *ks, int64_t s_out,
+                     double *mu, int64_t s_mu);
 int launch_kxx_batch(b7_ctx *c, int B, const double *ls_dev, const double *amp_dev, const double *noise_dev, double *w,
                      double *zsc, double *zss, double *K);
-int launch_ksx(b7_ctx *c, const double *xq, int64_t row0, int64_t rows, int64_t Mtotal, int d, double *ks,
+int launch_ksx(b7_ctx *c, const FitSet &f, const double *xq, int64_t row0, int64_t rows, int64_t Mtotal, int d, double *ks,
                double *mu, int ycols);
 
 // potrf.hip
@@ -414,9 +440,7 @@ int launch_nll_small(b7_ctx *c, int B, const double *hyp_dev, const double *hyp_
                      unsigned *done_dev);
 // kpost_small.hip
 bool kpost_small_applies(const b7_ctx *c);
-int launch_kpost_small(b7_ctx *c, int S, const double *xq, int64_t M, const double *w, const double *zsc, const double *zss,
-                       const double *Linv, const double *alpha, const double *hyp_dev, double amp, double noise, double mean,
-                       double *mu, double *var, int64_t sout);
+int launch_kpost_small(b7_ctx *c, const FitSet &f, const double *xq, int64_t M, double *mu, double *var, int64_t sout);
 // gp_small.hip
 bool gp_small_applies(const b7_ctx *c);
 // ... and the whole fit of a hyper vector runs as one workgroup of one launch (launch_fit_small)
@@ -439,12 +463,13 @@ int launch_fro_norm_sq(b7_ctx *c, const double *A, int n, int ld, double *out_de
 int launch_set_identity(b7_ctx *c);    // L = I (Npad x Npad), dinv = identity blocks: the chol(I) fallback
 
 // posterior.hip
-int launch_post(b7_ctx *c, const double *ks, int64_t row0, int64_t rows, int64_t Mtotal, double *var);
-int launch_post_batch(b7_ctx *c, int S, const double *Linv, const double *ks, int64_t sks, int64_t rows, int64_t Mtotal,
-                      double *var, int64_t svar, const double *amp_dev, const double *noise_dev);
+// the variance of one fit (host scalars; c->model_kind == 1: f.Linv and f.noise are a Bayesian linear head's, ks its features)
+int launch_post(b7_ctx *c, const FitSet &f, const double *ks, int64_t row0, int64_t rows, int64_t Mtotal, double *var);
+int launch_post_batch(b7_ctx *c, const FitSet &f, const double *ks, int64_t sks, int64_t rows, int64_t Mtotal, double *var,
+                      int64_t svar);
 
 // extras.hip
-int launch_mean_multi(b7_ctx *c, const double *ks, int64_t row0, int64_t rows, int64_t Mtotal, double *mu);
+int launch_mean_multi(b7_ctx *c, const FitSet &f, const double *ks, int64_t row0, int64_t rows, int64_t Mtotal, double *mu);
 int launch_gemm_nt(b7_ctx *c, const double *A, int lda, const double *B, int ldb, double *C, int ldc, int m, int n,
                    int k);
 int launch_fantasy_cov(b7_ctx *c, const double *kpp, const double *g, double *S, int P, double diag_add);
@@ -546,7 +571,7 @@ void launch_resid_batch(b7_ctx *c, int B, const double *mean_dev);  // c->bresid
 int fit_front(b7_ctx *c, const b7_hyp *hyp, const double *ls_dev);  // residual, observation scaling and K(X,X) of one hyper sample
 int fit_hyp_core(b7_ctx *c, const b7_hyp *hyp, double *nll_out, double *jitter_used, int *info_out, bool then_predict);
 int64_t predict_chunk(const b7_ctx *c, int64_t M);  // candidate rows per pass of predict_into: what c->ks has to hold
-int predict_into(b7_ctx *c, const double *xq, int64_t M, double *mu, double *var);
+int predict_into(b7_ctx *c, const FitSet &fit, const double *xq, int64_t M, double *mu, double *var);  // one fit, host scalars
 // mean (M x cols) / variance (M) to the caller (either may be null), then one synchronisation if either was asked for, or `wait`
 int copy_out_mu_var(b7_ctx *c, const void *mu, const void *var, int64_t M, int cols, double *mean_host, double *var_host,
                     bool wait = false);
@@ -556,6 +581,32 @@ struct HypPack { double *ls, *amp, *noise, *mean; };
 static inline HypPack hyp_pack(void *base, int B, int d) {
   double *amp = static_cast<double *>(base) + (size_t)B * d;
   return {static_cast<double *>(base), amp, amp + B, amp + 2 * (size_t)B};
+}
+// The batch slots (c->bw ... c->bresid) sized for B fits of the resident data, the groups named by `groups`, in this order
+constexpr int B7_SLOTS_OPERANDS = 1;  // bw, bzsc, bzss
+constexpr int B7_SLOTS_LINV = 2;      // bLinv
+constexpr int B7_SLOTS_ALPHA = 4;     // balpha
+constexpr int B7_SLOTS_FACTOR = 8;    // bK, bL, bdinv, bresid: what a factorisation outside the one-launch fit works in
+int batch_slots_ensure(b7_ctx *c, int B, int groups);
+// the S fits in the batch slots, their scalars in the packed hypers of c->bhyp
+static inline FitSet batch_fits(const b7_ctx *c, int S) {
+  const HypPack hd = hyp_pack(c->bhyp.p, S, c->dfit);
+  FitSet f;
+  f.w = (const double *)c->bw.p, f.zsc = (const double *)c->bzsc.p, f.zss = (const double *)c->bzss.p;
+  f.Linv = (const double *)c->bLinv.p, f.alpha = (const double *)c->balpha.p;
+  f.S = S, f.Npad = c->Npad, f.dpad = c->dpad;
+  f.amp_dev = hd.amp, f.noise_dev = hd.noise, f.mean_dev = hd.mean;
+  return f;
+}
+// sample s of a set on its own, its scalars taken from the host's copy of that sample's hypers
+static inline FitSet fit_at(const FitSet &set, int s, const b7_hyp &hyp) {
+  const int Npad = set.Npad, dpad = set.dpad;
+  FitSet f;
+  f.Npad = Npad, f.dpad = dpad;
+  f.w = set.w + s * FitSet::s_w(Npad, dpad), f.zsc = set.zsc + s * FitSet::s_zsc(Npad, dpad), f.zss = set.zss + s * FitSet::s_zss(Npad, dpad);
+  f.Linv = set.Linv + s * FitSet::s_Linv(Npad, dpad), f.alpha = set.alpha + s * FitSet::s_alpha(Npad, dpad);
+  f.amp = hyp.amp, f.noise = hyp.noise, f.mean = hyp.mean;
+  return f;
 }
 
 // nominate.hip: bayesopt:eval as stream work without a host wait (its batched score left in *pend), the pivot reports' check and
@@ -583,15 +634,19 @@ int score_add(b7_ctx *c, const b7_score_spec *sp, const double *fd, bool accumul
 // (kind MES: the y* search of the S samples is enqueued here, ahead of the score that reads it)
 int pending_score(b7_ctx *c, int S, const b7_score_spec *spec, const double *fd, ScoreParams *out);
 int eval_validate(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, int64_t offset);
-// keep (nullable; b7_eval_nominate_batch): where every sample's posterior mean and variance over the grid, and its fit, are left
-// for the picks that follow the first.  The enqueued work is the same with and without it, copies aside.
+// eval_enqueue picks one of four routes.  Where the fits of all S samples can run side by side (the one-launch small fit, or S > 1
+// single-column fits within the persistent schedule's size) they are produced straight into the batch slots, batch_fits(c, S), and
+// the posterior follows as the one-kernel small posterior, as K* / variance / score of all samples in one launch each when K* fits
+// the workspace S times over, or else sample by sample through predict_into(c, fit_at(batch_fits(c, S), s, hyps[s]), ...).
+// Otherwise every sample is fitted in the context's own slot, one after the other, and predicted from ctx_fit(c).
+// keep (nullable; b7_eval_nominate_batch, b7_eval_nominate_refine): where every sample's posterior mean and variance over the
+// grid are left, and a view of the S fits, for what follows the first pick.  The enqueued work is the same with and without it,
+// copies aside: a route that fits in the context's own slot copies each fit to its batch slot (S == 1: it stays, fits = ctx_fit(c)).
 struct BelKeep {
-  double *mu = nullptr, *var = nullptr;  // [S][M]
-  // the S fits afterwards, sample s at base + s * (dpad | Npad dpad | Npad | Npad^2): the batch slots, or (S == 1) the context's own
-  const double *w = nullptr, *zsc = nullptr, *zss = nullptr, *Linv = nullptr;
-  const double *alpha = nullptr;  // ... and their alpha (stride Npad): what b7_eval_nominate_refine's mean gradient contracts with
-  bool want_alpha = false;        // copy alpha into its batch slot where a fit does not live there yet (the believer does not read it)
-};  // mu == nullptr: the means and variances are not kept (b7_eval_nominate_refine reads the fits alone)
+  double *mu = nullptr, *var = nullptr;  // [S][M]; mu == nullptr: not kept (b7_eval_nominate_refine reads the fits alone)
+  FitSet fits;                           // out: the S fits afterwards (only the pointers are meant: the scalars travel with the caller's hypers)
+  bool want_alpha = false;               // copy alpha into its batch slot where a fit does not live there yet (the believer does not read it)
+};
 int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend, BelKeep *keep = nullptr);
 bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist);
 int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out,

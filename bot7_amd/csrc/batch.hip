@@ -328,13 +328,13 @@ int b7_eval_nominate_batch(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_
   for (int j = 1; j < q; ++j) {
     BelPass p;
     p.xj = grid + (best_idx1[j - 1] - 1) * c->d;
-    p.w = keep.w, p.zsc = keep.zsc, p.zss = keep.zss;
+    p.w = keep.fits.w, p.zsc = keep.fits.zsc, p.zss = keep.fits.zss;
     p.wj = st.wj, p.par = st.par, p.scal = st.scal, p.kcol = st.kcol;
     p.var = st.var, p.u = st.u, p.sgrid = c->M;
     p.idx = best_idx1[j - 1] - 1, p.j = j - 1;
     p.xq = (const double *)c->xobs.p, p.rows = c->N;
     B7_TRY(launch_believer(c, S, p, true));
-    B7_TRY(launch_alpha_batch(c, S, keep.Linv, st.kcol, st.wj));
+    B7_TRY(launch_alpha_batch(c, S, keep.fits.Linv, st.kcol, st.wj));
     p.xq = grid, p.rows = c->M;
     B7_TRY(launch_believer(c, S, p, false));
     // the whole grid again: the kept means, the downdated variances, the caller's spec; the picked rows stay out of the arg-max

@@ -75,7 +75,7 @@ static int blr_predict_enqueue(b7_ctx *c, int64_t M, bool mean_done = false) {
   if (!mean_done)
     B7_TRY(launch_gemv_rows(c, (const double *)c->feat.p, c->Npad, (const double *)c->alpha.p, c->Npad, c->mean, 0, M, M,
                             (double *)c->mu.p));
-  B7_TRY(launch_post(c, (const double *)c->feat.p, 0, round_up(M, B7_MROWS), M, (double *)c->var.p));
+  B7_TRY(launch_post(c, ctx_fit(c), (const double *)c->feat.p, 0, round_up(M, B7_MROWS), M, (double *)c->var.p));
   c->predicted = true;
   c->Mpred = M;
   return B7_OK;

@@ -340,7 +340,7 @@ int ensure_exp_table(b7_ctx *c) {
 
 template <int DPAD, int KERN>
 int ksx_launch(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
-               const double *alpha, double meanc, double *out, double *mu) {
+               const double *alpha, double amp, double meanc, double *out, double *mu) {
   const size_t lds = ksx_lds_bytes(DPAD);
   auto kern = ksx_kernel<DPAD, KERN>;
   B7_TRY(ensure_exp_table(c));
@@ -348,30 +348,30 @@ int ksx_launch(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mto
   B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds));
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, c->stream, xq, row0, Mtotal, d, c->dpad, o.w ? o.w : (const double *)c->w.p,
-                     o.zsc, o.zsh, alpha, c->amp, meanc, o.npad, out, mu, o.batch);
+                     o.zsc, o.zsh, alpha, amp, meanc, o.npad, out, mu, o.batch);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
 
 template <int KERN>
 int ksx_dispatch_k(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
-                   const double *alpha, double meanc, double *out, double *mu) {
+                   const double *alpha, double amp, double meanc, double *out, double *mu) {
   switch (c->dpad) {
-    case 4: return ksx_launch<4, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 8: return ksx_launch<8, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 16: return ksx_launch<16, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 32: return ksx_launch<32, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 48: return ksx_launch<48, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 64: return ksx_launch<64, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-    case 96: return ksx_launch<96, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+    case 4: return ksx_launch<4, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
+    case 8: return ksx_launch<8, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
+    case 16: return ksx_launch<16, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
+    case 32: return ksx_launch<32, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
+    case 48: return ksx_launch<48, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
+    case 64: return ksx_launch<64, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
+    case 96: return ksx_launch<96, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
     default: return b7_fail(c, B7_ERR_UNSUPPORTED, "covariance kernel: dpad %d is not a built class", c->dpad);
   }
 }
 
 int ksx_dispatch(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
-                 const double *alpha, double meanc, double *out, double *mu) {
-  if (c->kernel == B7_KERNEL_MATERN52) return ksx_dispatch_k<B7_KERNEL_MATERN52>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
-  return ksx_dispatch_k<B7_KERNEL_ARDSE>(c, grid, xq, row0, Mtotal, d, o, alpha, meanc, out, mu);
+                 const double *alpha, double amp, double meanc, double *out, double *mu) {
+  if (c->kernel == B7_KERNEL_MATERN52) return ksx_dispatch_k<B7_KERNEL_MATERN52>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
+  return ksx_dispatch_k<B7_KERNEL_ARDSE>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
 }
 
 }  // namespace
@@ -399,17 +399,17 @@ int launch_prep_obs_aux(b7_ctx *c, const double *xobs, const double *ls_dev, int
 // K(Xq, Xobs-set) for an arbitrary observation set: rows x o.npad, no mean.
 int launch_k_generic(b7_ctx *c, const double *xq, int64_t rows, int64_t Mtotal, const ObsSet &o, double *out) {
   if (rows % KQ || o.npad % 64) return b7_fail(c, B7_ERR_INVALID, "k_generic: extents not multiples of 64");
-  return ksx_dispatch(c, dim3((unsigned)(rows / KQ), 1), xq, 0, Mtotal, c->dfit, o, nullptr, 0.0, out, nullptr);
+  return ksx_dispatch(c, dim3((unsigned)(rows / KQ), 1), xq, 0, Mtotal, c->dfit, o, nullptr, c->amp, 0.0, out, nullptr);
 }
 
-int launch_ksx(b7_ctx *c, const double *xq, int64_t row0, int64_t rows, int64_t Mtotal, int d, double *ks,
+int launch_ksx(b7_ctx *c, const FitSet &f, const double *xq, int64_t row0, int64_t rows, int64_t Mtotal, int d, double *ks,
                double *mu, int ycols) {
   PhaseScope ps(c, "ksx");
   if (rows % KQ) return b7_fail(c, B7_ERR_INVALID, "ksx: rows %lld not a multiple of %d", (long long)rows, KQ);
   if (ycols != 1) mu = nullptr;  // the multi-column mean is a GEMM of its own (launch_mean_multi)
-  const ObsSet o{(const double *)c->zsc.p, (const double *)c->zss.p, c->Npad};
-  return ksx_dispatch(c, dim3((unsigned)(rows / KQ), 1), xq, row0, Mtotal, d, o,
-                      mu ? (const double *)c->alpha.p : nullptr, c->mean, ks, mu);
+  ObsSet o{f.zsc, f.zss, c->Npad};
+  o.w = f.w;
+  return ksx_dispatch(c, dim3((unsigned)(rows / KQ), 1), xq, row0, Mtotal, d, o, mu ? f.alpha : nullptr, f.amp, f.mean, ks, mu);
 }
 
 int launch_kxx(b7_ctx *c, double diag_add) {
@@ -419,7 +419,7 @@ int launch_kxx(b7_ctx *c, double diag_add) {
   int ny = 1;
   while (ny < 16 && (Npad / 64) % (ny * 2) == 0 && (Npad / KQ) * ny < 2 * c->cus) ny *= 2;
   const ObsSet o{(const double *)c->zsc.p, (const double *)c->zss.p, Npad};
-  B7_TRY(ksx_dispatch(c, dim3(Npad / KQ, ny), (const double *)c->xobs.p, 0, c->N, c->dfit, o, nullptr, 0.0,
+  B7_TRY(ksx_dispatch(c, dim3(Npad / KQ, ny), (const double *)c->xobs.p, 0, c->N, c->dfit, o, nullptr, c->amp, 0.0,
                       (double *)c->K.p, nullptr));
   int64_t total = (int64_t)Npad * Npad;
   hipLaunchKernelGGL(kxx_fix_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, (double *)c->K.p,
@@ -432,22 +432,21 @@ int launch_kxx(b7_ctx *c, double diag_add) {
 // ls: B x d, amp / noise: B (device).  zsc: B x Npad x dpad, zss: B x Npad, w: B x dpad, K: B x Npad x Npad.
 // K(X*, X) and the posterior mean of S fits over the same candidate rows in one launch (grid.z = fit): the hyper samples
 // of a nomination whose K* fits the workspace S times over (b7_eval_nominate)
-int launch_ksx_batch(b7_ctx *c, int S, const double *xq, int64_t rows, int64_t Mtotal, const double *w, const double *zsc,
-                     const double *zss, const double *amp_dev, const double *mean_dev, const double *alpha, double *ks,
-                     int64_t s_out, double *mu, int64_t s_mu) {
+int launch_ksx_batch(b7_ctx *c, const FitSet &f, const double *xq, int64_t rows, int64_t Mtotal, double *ks, int64_t s_out,
+                     double *mu, int64_t s_mu) {
   PhaseScope ps(c, "ksx");
   if (rows % KQ) return b7_fail(c, B7_ERR_INVALID, "ksx: rows %lld not a multiple of %d", (long long)rows, KQ);
-  ObsSet o{zsc, zss, c->Npad};
-  o.w = w;
-  o.batch.s_w = c->dpad;
-  o.batch.s_zsc = (int64_t)c->Npad * c->dpad;
-  o.batch.s_zsh = c->Npad;
+  ObsSet o{f.zsc, f.zss, c->Npad};
+  o.w = f.w;
+  o.batch.s_w = FitSet::s_w(c->Npad, c->dpad);
+  o.batch.s_zsc = FitSet::s_zsc(c->Npad, c->dpad);
+  o.batch.s_zsh = FitSet::s_zss(c->Npad, c->dpad);
   o.batch.s_out = s_out;
-  o.batch.amp = amp_dev;
-  o.batch.s_alpha = c->Npad;
+  o.batch.amp = f.amp_dev;
+  o.batch.s_alpha = FitSet::s_alpha(c->Npad, c->dpad);
   o.batch.s_mu = s_mu;
-  o.batch.mean = mean_dev;
-  return ksx_dispatch(c, dim3((unsigned)(rows / KQ), 1, S), xq, 0, Mtotal, c->dfit, o, alpha, 0.0, ks, mu);
+  o.batch.mean = f.mean_dev;
+  return ksx_dispatch(c, dim3((unsigned)(rows / KQ), 1, f.S), xq, 0, Mtotal, c->dfit, o, f.alpha, f.amp, 0.0, ks, mu);
 }
 
 int launch_kxx_batch(b7_ctx *c, int B, const double *ls_dev, const double *amp_dev, const double *noise_dev, double *w,
@@ -459,15 +458,15 @@ int launch_kxx_batch(b7_ctx *c, int B, const double *ls_dev, const double *amp_d
                      w, zsc, zss, c->N, Npad, d, dpad);
   ObsSet o{zsc, zss, Npad};
   o.w = w;
-  o.batch.s_w = dpad;
-  o.batch.s_zsc = (int64_t)Npad * dpad;
-  o.batch.s_zsh = Npad;
-  o.batch.s_out = (int64_t)Npad * Npad;
+  o.batch.s_w = FitSet::s_w(Npad, dpad);
+  o.batch.s_zsc = FitSet::s_zsc(Npad, dpad);
+  o.batch.s_zsh = FitSet::s_zss(Npad, dpad);
+  o.batch.s_out = (int64_t)Npad * Npad;  // of K
   o.batch.amp = amp_dev;
   // as launch_kxx: with few fits the observations are split over blockIdx.y so that the grid still covers the chip
   int ny = 1;
   while (ny < 16 && (Npad / 64) % (ny * 2) == 0 && (Npad / KQ) * ny * B < 2 * c->cus) ny *= 2;
-  B7_TRY(ksx_dispatch(c, dim3(Npad / KQ, ny, B), (const double *)c->xobs.p, 0, c->N, d, o, nullptr, 0.0, K, nullptr));
+  B7_TRY(ksx_dispatch(c, dim3(Npad / KQ, ny, B), (const double *)c->xobs.p, 0, c->N, d, o, nullptr, c->amp, 0.0, K, nullptr));
   const int64_t total = (int64_t)Npad * Npad;
   hipLaunchKernelGGL(kxx_fix_kernel, dim3((unsigned)((total + 255) / 256), B), dim3(256), 0, c->stream, K, c->N, Npad, 0.0,
                      noise_dev, total);

@@ -749,11 +749,11 @@ int launch_blr_assemble(b7_ctx *c, const double *G, double *K, int z, int zpad, 
   return B7_OK;
 }
 
-int launch_mean_multi(b7_ctx *c, const double *ks, int64_t row0, int64_t rows, int64_t Mtotal, double *mu) {
+int launch_mean_multi(b7_ctx *c, const FitSet &f, const double *ks, int64_t row0, int64_t rows, int64_t Mtotal, double *mu) {
   PhaseScope ps(c, "mean");
   if (rows % 128) return b7_fail(c, B7_ERR_INVALID, "mean_multi: rows %lld not a multiple of 128", (long long)rows);
-  hipLaunchKernelGGL(mean_multi_kernel, dim3((unsigned)(rows / 128), c->yld / 64), dim3(256), 0, c->stream, ks,
-                     (const double *)c->alpha.p, c->Npad, c->yld, c->ycols, row0, Mtotal, c->mean, mu);
+  hipLaunchKernelGGL(mean_multi_kernel, dim3((unsigned)(rows / 128), c->yld / 64), dim3(256), 0, c->stream, ks, f.alpha, c->Npad,
+                     c->yld, c->ycols, row0, Mtotal, f.mean, mu);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }

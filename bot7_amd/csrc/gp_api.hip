@@ -109,18 +109,35 @@ int64_t predict_chunk(const b7_ctx *c, int64_t M) {
   return chunk > Mpad ? Mpad : chunk;
 }
 
-int predict_into(b7_ctx *c, const double *xq, int64_t M, double *mu, double *var) {
+int predict_into(b7_ctx *c, const FitSet &fit, const double *xq, int64_t M, double *mu, double *var) {
   if (M == 0) return B7_OK;
   if (c->kpost_small && c->model_kind == 0 && kpost_small_applies(c))  // small fits: one kernel, K* never stored
-    return launch_kpost_small(c, 1, xq, M, (const double *)c->w.p, (const double *)c->zsc.p, (const double *)c->zss.p,
-                              (const double *)c->Linv.p, (const double *)c->alpha.p, nullptr, c->amp, c->noise, c->mean, mu, var, M);
+    return launch_kpost_small(c, fit, xq, M, mu, var, M);
   const int64_t chunk = predict_chunk(c, M), Mpad = round_up(M, B7_MROWS);
   B7_TRY(b7_ensure(c, c->ks, sizeof(double) * (size_t)chunk * c->Npad));
   for (int64_t row0 = 0; row0 < M; row0 += chunk) {
     int64_t rows = Mpad - row0 < chunk ? Mpad - row0 : chunk;
-    B7_TRY(launch_ksx(c, xq, row0, rows, M, c->dfit, (double *)c->ks.p, mu, c->ycols));
-    if (c->ycols > 1) B7_TRY(launch_mean_multi(c, (const double *)c->ks.p, row0, rows, M, mu));
-    B7_TRY(launch_post(c, (const double *)c->ks.p, row0, rows, M, var));
+    B7_TRY(launch_ksx(c, fit, xq, row0, rows, M, c->dfit, (double *)c->ks.p, mu, c->ycols));
+    if (c->ycols > 1) B7_TRY(launch_mean_multi(c, fit, (const double *)c->ks.p, row0, rows, M, mu));
+    B7_TRY(launch_post(c, fit, (const double *)c->ks.p, row0, rows, M, var));
+  }
+  return B7_OK;
+}
+
+int batch_slots_ensure(b7_ctx *c, int B, int groups) {
+  const size_t n = (size_t)c->Npad, one = sizeof(double) * (size_t)B;
+  if (groups & B7_SLOTS_OPERANDS) {
+    B7_TRY(b7_ensure(c, c->bw, one * FitSet::s_w(c->Npad, c->dpad)));
+    B7_TRY(b7_ensure(c, c->bzsc, one * FitSet::s_zsc(c->Npad, c->dpad)));
+    B7_TRY(b7_ensure(c, c->bzss, one * FitSet::s_zss(c->Npad, c->dpad)));
+  }
+  if (groups & B7_SLOTS_LINV) B7_TRY(b7_ensure(c, c->bLinv, one * FitSet::s_Linv(c->Npad, c->dpad)));
+  if (groups & B7_SLOTS_ALPHA) B7_TRY(b7_ensure(c, c->balpha, one * FitSet::s_alpha(c->Npad, c->dpad)));
+  if (groups & B7_SLOTS_FACTOR) {
+    B7_TRY(b7_ensure(c, c->bK, one * n * n));
+    B7_TRY(b7_ensure(c, c->bL, one * n * n));
+    B7_TRY(b7_ensure(c, c->bdinv, one * n * B7_PANEL));
+    B7_TRY(b7_ensure(c, c->bresid, one * n));
   }
   return B7_OK;
 }
@@ -211,7 +228,7 @@ int fit_hyp_core(b7_ctx *c, const b7_hyp *hyp, double *nll_out, double *jitter_u
     if (then_predict && tail_done) {
       B7_HIP(c, hipEventRecord(c->ev_fit, c->stream));
       c->fitted = true;  // for the launchers; withdrawn below if the report says otherwise
-      B7_TRY(predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
+      B7_TRY(predict_into(c, ctx_fit(c), (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
       B7_HIP(c, hipEventSynchronize(c->ev_fit));
     } else {
       B7_HIP(c, hipStreamSynchronize(c->stream));
@@ -242,7 +259,7 @@ int fit_hyp_core(b7_ctx *c, const b7_hyp *hyp, double *nll_out, double *jitter_u
   }
   if (then_predict && !predicted) {
     c->fitted = true;
-    B7_TRY(predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
+    B7_TRY(predict_into(c, ctx_fit(c), (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
   }
   if (nll_out)
     for (int k = 0; k < ycols; ++k) nll_out[k] = 0.5 * blk.terms[1 + k] + blk.terms[0] + 0.5 * N * log(2.0 * M_PI);
@@ -338,7 +355,7 @@ int b7_gp_nll_batch(b7_ctx *c, int B, const double *lenscale_sq, const double *a
   if (B < 1 || !lenscale_sq || !amp || !noise || !mean || !nll_out) return b7_fail(c, B7_ERR_INVALID, "gp_nll_batch: bad arguments");
   if (c->ycols != 1) return b7_fail(c, B7_ERR_UNSUPPORTED, "gp_nll_batch: one response column only");
   if (c->Npad > B7_PERSIST_NMAX) return b7_fail(c, B7_ERR_UNSUPPORTED, "gp_nll_batch: N > 4096 (evaluate with b7_gp_fit_hyp one by one)");
-  const int N = c->N, n = c->Npad, d = c->dfit, dpad = c->dpad, nb = n / B7_PANEL;
+  const int N = c->N, n = c->Npad, d = c->dfit, nb = n / B7_PANEL;
   for (int b = 0; b < B; ++b) {
     for (int k = 0; k < d; ++k)
       if (!(lenscale_sq[(size_t)b * d + k] > 0.0)) return b7_fail(c, B7_ERR_INVALID, "gp_nll_batch: lenscale_sq[%d][%d] must be > 0", b, k);
@@ -398,17 +415,11 @@ int b7_gp_nll_batch(b7_ctx *c, int B, const double *lenscale_sq, const double *a
   }
   const size_t fw = persist_flag_words_host(nb), nn = (size_t)n * n;
   B7_TRY(b7_ensure(c, c->bhyp, sizeof(double) * (size_t)B * (d + 3)));
-  B7_TRY(b7_ensure(c, c->bw, sizeof(double) * (size_t)B * dpad));
-  B7_TRY(b7_ensure(c, c->bzsc, sizeof(double) * (size_t)B * n * dpad));
-  B7_TRY(b7_ensure(c, c->bzss, sizeof(double) * (size_t)B * n));
-  B7_TRY(b7_ensure(c, c->bK, sizeof(double) * B * nn));
-  B7_TRY(b7_ensure(c, c->bL, sizeof(double) * B * nn));
-  B7_TRY(b7_ensure(c, c->bdinv, sizeof(double) * (size_t)B * n * B7_PANEL));
+  B7_TRY(batch_slots_ensure(c, B, B7_SLOTS_OPERANDS | B7_SLOTS_FACTOR));
   // one block: [2 B doubles of likelihood terms][4 B ints of pivot reports][B x fw flag words] -- reports and flags are zeroed
   // by one memset, terms and reports come back in one copy; the jitter schedule's norm goes into bterms
   const size_t head_bytes = sizeof(double) * 2 * (size_t)B + sizeof(int) * 4 * (size_t)B;
   B7_TRY(b7_ensure(c, c->bflags, head_bytes + sizeof(unsigned) * B * fw));
-  B7_TRY(b7_ensure(c, c->bresid, sizeof(double) * (size_t)B * n));
   B7_TRY(b7_ensure(c, c->bterms, 64));
   // all hypers in one upload from the pinned block (no pageable staging)
   double *hyp_dev = (double *)c->bhyp.p;
@@ -561,7 +572,7 @@ int b7_gp_predict(b7_ctx *c, double *mean_host, double *var_host) {
   B7_HIP(c, hipSetDevice(c->device));
   B7_TRY(b7_ensure(c, c->mu, sizeof(double) * (size_t)c->M * c->ycols));
   B7_TRY(b7_ensure(c, c->var, sizeof(double) * (size_t)c->M));
-  B7_TRY(predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
+  B7_TRY(predict_into(c, ctx_fit(c), (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
   c->predicted = true;
   c->Mpred = c->M;
   return copy_out_mu_var(c, c->mu.p, c->var.p, c->M, c->ycols, mean_host, var_host);
@@ -577,7 +588,7 @@ int b7_gp_predict_at(b7_ctx *c, const double *X1, int64_t M1, double *mean_host,
   B7_TRY(b7_ensure(c, c->tmpmu, sizeof(double) * (size_t)M1 * c->ycols));
   B7_TRY(b7_ensure(c, c->tmpvar, sizeof(double) * (size_t)M1));
   B7_HIP(c, hipMemcpyAsync(c->tmpgrid.p, X1, sizeof(double) * (size_t)M1 * c->dfit, hipMemcpyHostToDevice, c->stream));
-  B7_TRY(predict_into(c, (const double *)c->tmpgrid.p, M1, (double *)c->tmpmu.p, (double *)c->tmpvar.p));
+  B7_TRY(predict_into(c, ctx_fit(c), (const double *)c->tmpgrid.p, M1, (double *)c->tmpmu.p, (double *)c->tmpvar.p));
   return copy_out_mu_var(c, c->tmpmu.p, c->tmpvar.p, M1, c->ycols, mean_host, var_host, true);  // the wait also releases X1
 }
 
@@ -600,7 +611,7 @@ int b7_gp_fantasize(b7_ctx *c, const double *X_pend, int P, int n, uint64_t seed
   int *info_dev = (int *)(out + (size_t)P * n + 2);
   B7_HIP(c, hipMemcpyAsync(xp, X_pend, sizeof(double) * (size_t)P * d, hipMemcpyHostToDevice, c->stream));
   // K(Xp, X) with the fused mean, then V' = K(Xp,X) L^-T and G = V'V
-  B7_TRY(launch_ksx(c, xp, 0, 64, P, d, kp, mu, 1));
+  B7_TRY(launch_ksx(c, ctx_fit(c), xp, 0, 64, P, d, kp, mu, 1));
   B7_TRY(launch_gemm_nt(c, kp, np, (const double *)c->Linv.p, np, vt, np, 64, np, np));
   B7_TRY(launch_gemm_nt(c, vt, np, vt, np, g, 64, 64, 64, np));
   // K(Xp, Xp): the pending points as their own observation set, scaled with the fit's lengthscales
@@ -662,7 +673,7 @@ int b7_gp_append(b7_ctx *c, const double *x_new, const double *y_new) {
   double *krows = (double *)c->fant.p, *lvec = krows + (size_t)64 * np, *uvec = lvec + np, *evec = uvec + np;
   double *part = evec + np;
   int *status_dev = (int *)(part + (size_t)np * nslices);
-  B7_TRY(launch_ksx(c, (const double *)c->xobs.p + (size_t)N * d, 0, 64, 1, d, krows, nullptr, 1));
+  B7_TRY(launch_ksx(c, ctx_fit(c), (const double *)c->xobs.p + (size_t)N * d, 0, 64, 1, d, krows, nullptr, 1));
   B7_TRY(launch_append_vectors(c, krows, lvec, uvec, part, evec));
   B7_TRY(launch_append_finalize(c, krows, lvec, uvec, evec, status_dev));
   int status = 0;

@@ -257,17 +257,16 @@ int kp_dispatch(b7_ctx *c, const KpArgs &a) {
 
 bool kpost_small_applies(const b7_ctx *c) { return c->Npad <= 128 && c->dfit <= 32 && c->ycols == 1; }
 
-// S fits (S = 1 with hyp_dev == nullptr: the scalars amp / noise / mean) over the M candidates at xq: mu[s][M], var[s][M]
-// (stride sout).  Strides of the per-fit arrays: w dpad, zsc Npad dpad, zss Npad, Linv Npad^2, alpha Npad.
-int launch_kpost_small(b7_ctx *c, int S, const double *xq, int64_t M, const double *w, const double *zsc, const double *zss,
-                       const double *Linv, const double *alpha, const double *hyp_dev, double amp, double noise, double mean,
-                       double *mu, double *var, int64_t sout) {
+// f's fits over the M candidates at xq: mu[s][M], var[s][M] (stride sout)
+int launch_kpost_small(b7_ctx *c, const FitSet &f, const double *xq, int64_t M, double *mu, double *var, int64_t sout) {
   PhaseScope ps(c, "kpost");
   if (M <= 0) return B7_OK;
   KpArgs a = {};
-  a.xq = xq, a.M = M, a.d = c->dfit, a.N = c->N, a.npad = c->Npad, a.S = S;
-  a.w = w, a.zsc = zsc, a.zss = zss, a.Linv = Linv, a.alpha = alpha, a.hyp = hyp_dev;
-  a.amp = amp, a.noise = noise, a.mean = mean;
+  a.xq = xq, a.M = M, a.d = c->dfit, a.N = c->N, a.npad = c->Npad, a.S = f.S;
+  a.w = f.w, a.zsc = f.zsc, a.zss = f.zss, a.Linv = f.Linv, a.alpha = f.alpha;
+  // the kernel takes device scalars as the base of their packed block (hyp_pack: S x d lengthscales ahead of the amplitudes)
+  a.hyp = f.amp_dev ? f.amp_dev - (size_t)f.S * c->dfit : nullptr;
+  a.amp = f.amp, a.noise = f.noise, a.mean = f.mean;
   a.mu = mu, a.var = var, a.sout = sout;
   a.var_with_noise = c->opts.var_with_noise, a.clamp = c->opts.var_clamp, a.var_min = c->opts.var_min;
   switch (c->dpad) {

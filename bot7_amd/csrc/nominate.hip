@@ -99,43 +99,41 @@ int pending_score(b7_ctx *c, int S, const b7_score_spec *spec, const double *fd,
   return B7_OK;
 }
 
-// bots/bayesopt.lua:69-78 as stream work: zero the accumulator, then fit + posterior + score:add per hyper sample, each
-// fit's pivot report copied to its pinned slot in stream order.  Returns without waiting for any of it; the small regime's
-// score:add is left to the caller's exchange step in *pend.
-// b7_eval_nominate_batch's hook (keep, nullable): sample s of S has just been fitted into the context's own slots and predicted
-// into c->mu / c->var; its mean and variance go to keep's arrays, its fit to batch slot s (S == 1: it stays where it is)
-static int keep_slots_ensure(b7_ctx *c, int S, bool with_alpha) {
-  const size_t n = (size_t)c->Npad;
-  B7_TRY(b7_ensure(c, c->bw, sizeof(double) * (size_t)S * c->dpad));
-  B7_TRY(b7_ensure(c, c->bzsc, sizeof(double) * (size_t)S * n * c->dpad));
-  B7_TRY(b7_ensure(c, c->bzss, sizeof(double) * (size_t)S * n));
-  if (with_alpha) B7_TRY(b7_ensure(c, c->balpha, sizeof(double) * (size_t)S * n));
-  return b7_ensure(c, c->bLinv, sizeof(double) * (size_t)S * n * n);
+// ---- eval_enqueue: bots/bayesopt.lua:69-78 as stream work, and its pieces ---------------------------------------------------
+// b7_eval_nominate_batch's and b7_eval_nominate_refine's hook (keep, nullable).  A sample fitted in the context's own slot is
+// copied to batch slot s; these are sized for that (S == 1: the fit stays where it is)
+static int keep_slots_ensure(b7_ctx *c, const BelKeep *keep, int S) {
+  if (!keep || S == 1) return B7_OK;
+  return batch_slots_ensure(c, S, B7_SLOTS_OPERANDS | B7_SLOTS_LINV | (keep->want_alpha ? B7_SLOTS_ALPHA : 0));
 }
-static int keep_sample(b7_ctx *c, BelKeep *keep, int S, int s) {
+// Sample s of S has just been predicted into c->mu / c->var: its mean and variance go to keep's arrays.  in_slot: its fit was
+// produced in batch slot s; otherwise it sits in the context's own slot and is copied there (S == 1: it stays, and is kept as that)
+static int keep_sample(b7_ctx *c, BelKeep *keep, int S, int s, bool in_slot) {
   if (!keep) return B7_OK;
-  const size_t n = (size_t)c->Npad, mb = sizeof(double) * (size_t)c->M;
+  const size_t mb = sizeof(double) * (size_t)c->M;
   if (keep->mu) {
     B7_HIP(c, hipMemcpyAsync(keep->mu + (size_t)s * c->M, c->mu.p, mb, hipMemcpyDeviceToDevice, c->stream));
     B7_HIP(c, hipMemcpyAsync(keep->var + (size_t)s * c->M, c->var.p, mb, hipMemcpyDeviceToDevice, c->stream));
   }
-  if (S == 1) {
-    keep->w = (const double *)c->w.p, keep->zsc = (const double *)c->zsc.p, keep->zss = (const double *)c->zss.p;
-    keep->Linv = (const double *)c->Linv.p, keep->alpha = (const double *)c->alpha.p;
+  if (S == 1 && !in_slot) {
+    keep->fits = ctx_fit(c);
     return B7_OK;
   }
-  keep->w = (const double *)c->bw.p, keep->zsc = (const double *)c->bzsc.p, keep->zss = (const double *)c->bzss.p;
-  keep->Linv = (const double *)c->bLinv.p, keep->alpha = (const double *)c->balpha.p;
-  if (c->w.p == (double *)c->bw.p + (size_t)s * c->dpad) return B7_OK;  // the fit already lives in its batch slot
-  if (keep->want_alpha)
-    B7_HIP(c, hipMemcpyAsync((double *)c->balpha.p + s * n, c->alpha.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
-  B7_HIP(c, hipMemcpyAsync((double *)c->bw.p + (size_t)s * c->dpad, c->w.p, sizeof(double) * c->dpad, hipMemcpyDeviceToDevice, c->stream));
-  B7_HIP(c, hipMemcpyAsync((double *)c->bzsc.p + s * n * c->dpad, c->zsc.p, sizeof(double) * n * c->dpad, hipMemcpyDeviceToDevice, c->stream));
-  B7_HIP(c, hipMemcpyAsync((double *)c->bzss.p + s * n, c->zss.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
-  B7_HIP(c, hipMemcpyAsync((double *)c->bLinv.p + s * n * n, c->Linv.p, sizeof(double) * n * n, hipMemcpyDeviceToDevice, c->stream));
+  keep->fits = batch_fits(c, S);
+  if (in_slot) return B7_OK;
+  const FitSet src = ctx_fit(c), dst = fit_at(keep->fits, s, b7_hyp{nullptr, c->amp, c->noise, c->mean});
+  const int n = c->Npad, dp = c->dpad;
+  auto put = [&](const double *to, const double *from, int64_t doubles) {  // the batch slots are the context's own memory
+    return hipMemcpyAsync(const_cast<double *>(to), from, sizeof(double) * (size_t)doubles, hipMemcpyDeviceToDevice, c->stream);
+  };
+  if (keep->want_alpha) B7_HIP(c, put(dst.alpha, src.alpha, FitSet::s_alpha(n, dp)));
+  B7_HIP(c, put(dst.w, src.w, FitSet::s_w(n, dp)));
+  B7_HIP(c, put(dst.zsc, src.zsc, FitSet::s_zsc(n, dp)));
+  B7_HIP(c, put(dst.zss, src.zss, FitSet::s_zss(n, dp)));
+  B7_HIP(c, put(dst.Linv, src.Linv, FitSet::s_Linv(n, dp)));
   return B7_OK;
 }
-// ... or all S at once, from the batched posterior's arrays
+// ... or all S at once, from the batched posterior's arrays; the fits were produced in the batch slots
 static int keep_batch(b7_ctx *c, BelKeep *keep, int S) {
   if (!keep) return B7_OK;
   const size_t bytes = sizeof(double) * (size_t)S * c->M;
@@ -143,172 +141,177 @@ static int keep_batch(b7_ctx *c, BelKeep *keep, int S) {
     B7_HIP(c, hipMemcpyAsync(keep->mu, c->bmu.p, bytes, hipMemcpyDeviceToDevice, c->stream));
     B7_HIP(c, hipMemcpyAsync(keep->var, c->bvar.p, bytes, hipMemcpyDeviceToDevice, c->stream));
   }
-  keep->w = (const double *)c->bw.p, keep->zsc = (const double *)c->bzsc.p, keep->zss = (const double *)c->bzss.p;
-  keep->Linv = (const double *)c->bLinv.p, keep->alpha = (const double *)c->balpha.p;
+  keep->fits = batch_fits(c, S);
   return B7_OK;
 }
 
-int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend, BelKeep *keep) {
+// The pinned staging block of a nomination: [S][4] pivot reports | the hypers of all S samples, packed ([S][d] lengthscales, then
+// S amp, S noise, S mean), as the host addresses it and (the block is mapped) as the device does
+struct EvalStage {
+  int *reports, *reports_dev;
+  double *hyp_host;
+  const double *hyp_map;
+  size_t hyp_bytes, rep_bytes;
+};
+// sizes the block and c->bhyp, packs the hypers and marks every report "not written"
+static int eval_stage(b7_ctx *c, int S, const b7_hyp *hyps, EvalStage *st) {
   const int d = c->dfit;
-  B7_HIP(c, hipSetDevice(c->device));
-  B7_TRY(b7_ensure(c, c->mu, sizeof(double) * (size_t)c->M * c->ycols));
-  B7_TRY(b7_ensure(c, c->var, sizeof(double) * (size_t)c->M));
-  B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
-  // predict_into's workspace, sized now: a reallocation inside the loop would synchronise
-  B7_TRY(b7_ensure(c, c->ks, sizeof(double) * (size_t)predict_chunk(c, c->M) * c->Npad));
-  if (spec->kind == B7_SCORE_MES) B7_TRY(mes_begin(c, S, c->M, c->mes_levels));  // y*[S][K], brackets and partials, sized before anything is in flight
-  // pinned staging: [S][4] pivot reports | hypers of all S samples ([S][d] lengthscales, then S amp, S noise, S mean)
-  const size_t hyp_doubles = (size_t)S * (d + 3), ls_bytes = sizeof(double) * hyp_doubles, rep_bytes = 16 * (size_t)S;
-  B7_TRY(b7_pin_ensure(c, c->pin_eval, ls_bytes + rep_bytes, true));
-  B7_TRY(b7_ensure(c, c->bhyp, ls_bytes));
-  int *reports = static_cast<int *>(c->pin_eval.host);                                        // [S][4]
-  double *ls_host = reinterpret_cast<double *>(static_cast<char *>(c->pin_eval.host) + rep_bytes);  // the packed hypers
-  const HypPack hp = hyp_pack(ls_host, S, d);
+  st->hyp_bytes = sizeof(double) * (size_t)S * (d + 3), st->rep_bytes = 16 * (size_t)S;
+  B7_TRY(b7_pin_ensure(c, c->pin_eval, st->hyp_bytes + st->rep_bytes, true));
+  B7_TRY(b7_ensure(c, c->bhyp, st->hyp_bytes));
+  st->reports = static_cast<int *>(c->pin_eval.host), st->reports_dev = static_cast<int *>(c->pin_eval.dev);
+  st->hyp_host = reinterpret_cast<double *>(static_cast<char *>(c->pin_eval.host) + st->rep_bytes);
+  st->hyp_map = reinterpret_cast<const double *>(static_cast<const char *>(c->pin_eval.dev) + st->rep_bytes);
+  const HypPack hp = hyp_pack(st->hyp_host, S, d);
   for (int s = 0; s < S; ++s) {
     memcpy(hp.ls + (size_t)s * d, hyps[s].lenscale_sq, sizeof(double) * d);
     hp.amp[s] = hyps[s].amp;
     hp.noise[s] = hyps[s].noise;
     hp.mean[s] = hyps[s].mean;
   }
-  memset(reports, 0xff, rep_bytes);
-  // the fits of all samples side by side in one persistent launch (one critical workgroup each) when that schedule serves
-  // this size and the responses are a single column; otherwise one after the other
+  memset(st->reports, 0xff, st->rep_bytes);
+  return B7_OK;
+}
+
+// The fits of all S samples side by side, produced in the batch slots (batch_fits(c, S) afterwards), the pivot reports on their
+// way into the staging block
+static int fits_side_by_side(b7_ctx *c, int S, bool small, const EvalStage &st) {
+  double *bw = (double *)c->bw.p, *bzsc = (double *)c->bzsc.p, *bzss = (double *)c->bzss.p, *bLinv = (double *)c->bLinv.p;
+  double *balpha = (double *)c->balpha.p;
+  int *binfo = (int *)c->binfo.p;
   // N <= 128, d <= 32 (the reference's own regime): the whole fit of every hyper sample is one workgroup of ONE launch
   // (gp_small.hip), for any S -- observation scaling, K(X,X), factorisation, inverse, alpha, the pivot reports into the mapped
   // block; the kernel reads the hypers straight from that block and leaves the device copy the kernels downstream read
+  if (small)
+    return launch_fit_small(c, S, st.hyp_map, st.hyp_host, (double *)c->bhyp.p, bw, bzsc, bzss, nullptr, bLinv, nullptr, balpha, nullptr,
+                            binfo, st.reports_dev);
+  const int n = c->Npad;
+  const int64_t sq = FitSet::s_Linv(n, c->dpad);  // K, L and inv(L) of a fit: Npad x Npad each
+  const HypPack hd = hyp_pack(c->bhyp.p, S, c->dfit);
+  const double *bK = (const double *)c->bK.p, *bresid = (const double *)c->bresid.p;
+  double *bL = (double *)c->bL.p, *bdinv = (double *)c->bdinv.p;
+  launch_resid_batch(c, S, hd.mean);
+  B7_TRY(launch_kxx_batch(c, S, hd.ls, hd.amp, hd.noise, bw, bzsc, bzss, (double *)c->bK.p));
+  // one 64-block per fit: factorisation, inverse, alpha and the pivot report (mirrored into the mapped block) of all S fits in
+  // ONE launch of S workgroups
+  if (n == 64 && c->potrf_small)
+    return launch_potrf_small(c, S, bK, bL, bLinv, bdinv, bresid, balpha, 0.0, binfo, st.reports_dev, sq, sq, (int64_t)n * B7_PANEL,
+                              FitSet::s_alpha(n, c->dpad), 4);
+  // otherwise one persistent launch with grid.y = sample (one critical workgroup each)
+  B7_TRY(launch_fit_batch(c, S, bK, bL, bLinv, bdinv, (unsigned *)c->bflags.p, binfo));
+  if (4 * S <= 256)  // the reports ride on the last kernel of the fits into the mapped block: no copy launch
+    return launch_alpha_batch(c, S, bLinv, bresid, balpha, binfo, st.reports_dev, 4 * S);
+  B7_TRY(launch_alpha_batch(c, S, bLinv, bresid, balpha));
+  B7_HIP(c, hipMemcpyAsync(st.reports, binfo, st.rep_bytes, hipMemcpyDeviceToHost, c->stream));
+  return B7_OK;
+}
+
+// The three posteriors of fits that sit side by side in the batch slots.
+// N <= 128, d <= 32: K(X*,X), mean and variance of all S samples in ONE kernel that never stores K* (kpost_small.hip); score:add
+// is left to the caller's exchange step in *pend
+static int post_side_by_side_small(b7_ctx *c, int S, const b7_score_spec *spec, const double *fd, ScoreParams *pend, BelKeep *keep) {
+  B7_TRY(b7_ensure(c, c->bmu, sizeof(double) * (size_t)S * c->M));
+  B7_TRY(b7_ensure(c, c->bvar, sizeof(double) * (size_t)S * c->M));
+  B7_TRY(launch_kpost_small(c, batch_fits(c, S), (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->bmu.p, (double *)c->bvar.p, c->M));
+  B7_TRY(keep_batch(c, keep, S));
+  B7_TRY(pending_score(c, S, spec, fd, pend));
+  c->fitted = false;  // neither the context's fit slot nor its mean / variance vectors hold any of these samples
+  c->predicted = false;
+  return B7_OK;
+}
+// K* of all S samples fits the workspace at once (the reference's default sizes: 2e4 candidates, tens to hundreds of
+// observations, 10 samples): K*, posterior and score:add of all samples in ONE launch each (grid.z / grid.y = sample), the score
+// summed over the samples in order inside the kernel
+static int post_side_by_side(b7_ctx *c, int S, const b7_score_spec *spec, const double *fd, BelKeep *keep) {
+  const int64_t Mpad = round_up(c->M, B7_MROWS), sks = Mpad * c->Npad;
+  const FitSet fits = batch_fits(c, S);
+  B7_TRY(b7_ensure(c, c->ks, sizeof(double) * (size_t)sks * S));
+  B7_TRY(b7_ensure(c, c->bmu, sizeof(double) * (size_t)S * c->M));
+  B7_TRY(b7_ensure(c, c->bvar, sizeof(double) * (size_t)S * c->M));
+  B7_TRY(launch_ksx_batch(c, fits, (const double *)c->grid[c->grid_cur].p, Mpad, c->M, (double *)c->ks.p, sks, (double *)c->bmu.p, c->M));
+  B7_TRY(launch_post_batch(c, fits, (const double *)c->ks.p, sks, Mpad, c->M, (double *)c->bvar.p, c->M));
+  B7_TRY(keep_batch(c, keep, S));
+  ScoreParams all;
+  B7_TRY(pending_score(c, S, spec, fd, &all));
+  B7_TRY(launch_score_batch(c, all, (double *)c->acc.p, c->M));
+  c->fitted = false;  // neither the context's fit slot nor its mean / variance vectors hold any of these samples
+  c->predicted = false;
+  return B7_OK;
+}
+// K* of one sample at a time: the chunked posterior of batch slot s into c->mu / c->var, then its score:add.  The context's own
+// fit slot is not touched and stays declared empty; its scalars are left as the last sample's, c->mu / c->var as that sample's
+// prediction (b7_score_* may follow), which is what this route has always left behind
+static int post_in_turn(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, const double *fd, BelKeep *keep) {
+  const FitSet fits = batch_fits(c, S);
+  c->model_kind = 0;
+  int rc = B7_OK;
+  for (int s = 0; s < S && rc == B7_OK; ++s) {
+    c->amp = hyps[s].amp, c->noise = hyps[s].noise, c->mean = hyps[s].mean;
+    rc = predict_into(c, fit_at(fits, s, hyps[s]), (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p);
+    c->mes_slot = s;
+    if (rc == B7_OK) rc = score_add(c, spec, fd);
+    if (rc == B7_OK) rc = keep_sample(c, keep, S, s, true);
+  }
+  c->fitted = false;
+  c->predicted = true;
+  c->Mpred = c->M;
+  return rc;
+}
+
+// The fits one after the other in the context's own slot (several response columns, a size or a schedule the side-by-side fits
+// do not serve), each followed by its posterior and its score:add
+static int fits_in_turn(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, const double *fd, BelKeep *keep) {
+  B7_TRY(keep_slots_ensure(c, keep, S));
+  for (int s = 0; s < S; ++s) {
+    B7_TRY(fit_front(c, &hyps[s], (const double *)c->bhyp.p + (size_t)s * c->dfit));
+    int *report = static_cast<int *>(c->pin_eval.dev) + 4 * s;  // a one-block factorisation mirrors its report itself
+    FactorNote note;
+    B7_TRY(launch_potrf(c, 0.0, true, report, &note));
+    if (!c->linv_done) B7_TRY(launch_trtri(c));  // on a failed factor this inverts rubbish; the report discards it
+    B7_TRY(launch_alpha(c, report, 4, note));  // + this fit's pivot report, no copy launch
+    c->fitted = true;
+    B7_TRY(predict_into(c, ctx_fit(c), (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
+    c->predicted = true;
+    c->Mpred = c->M;
+    c->mes_slot = s;
+    B7_TRY(score_add(c, spec, fd));
+    B7_TRY(keep_sample(c, keep, S, s, false));
+  }
+  // this fit's lengthscales sit in the batch staging block, not in ScratchBlock::lenscale: the fit slot is declared empty
+  c->fitted = false;
+  return B7_OK;
+}
+
+// Zero the accumulator, then fit + posterior + score:add per hyper sample, each fit's pivot report on its way to its pinned slot
+// in stream order.  Returns without waiting for any of it; the small regime's score:add is left to the caller's exchange step in
+// *pend.  Everything is sized before anything is in flight: a reallocation between launches would synchronise.
+int eval_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, ScoreParams *pend, BelKeep *keep) {
+  B7_HIP(c, hipSetDevice(c->device));
+  B7_TRY(b7_ensure(c, c->mu, sizeof(double) * (size_t)c->M * c->ycols));
+  B7_TRY(b7_ensure(c, c->var, sizeof(double) * (size_t)c->M));
+  B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
+  B7_TRY(b7_ensure(c, c->ks, sizeof(double) * (size_t)predict_chunk(c, c->M) * c->Npad));  // predict_into's workspace
+  if (spec->kind == B7_SCORE_MES) B7_TRY(mes_begin(c, S, c->M, c->mes_levels));  // y*[S][K], brackets and partials
+  EvalStage st;
+  B7_TRY(eval_stage(c, S, hyps, &st));
+  // side by side: the one-launch small fit for any S, or S > 1 single-column fits in one persistent launch when that schedule
+  // serves this size
   const bool small = fit_small_applies(c);
   const bool batch = small || (S > 1 && c->ycols == 1 && c->potrf_sched == 3 && c->Npad <= B7_PERSIST_NMAX && c->inverse_inline);
-  const int n = c->Npad;
-  const size_t nn = (size_t)n * n;
   if (batch) {
-    const size_t fw = persist_flag_words_host(n / B7_PANEL);
-    B7_TRY(b7_ensure(c, c->bw, sizeof(double) * (size_t)S * c->dpad));
-    B7_TRY(b7_ensure(c, c->bzsc, sizeof(double) * (size_t)S * n * c->dpad));
-    B7_TRY(b7_ensure(c, c->bzss, sizeof(double) * (size_t)S * n));
-    B7_TRY(b7_ensure(c, c->bLinv, sizeof(double) * S * nn));
+    B7_TRY(batch_slots_ensure(c, S, B7_SLOTS_OPERANDS | B7_SLOTS_LINV | B7_SLOTS_ALPHA | (small ? 0 : B7_SLOTS_FACTOR)));
     B7_TRY(b7_ensure(c, c->binfo, sizeof(int) * 4 * (size_t)S));
-    B7_TRY(b7_ensure(c, c->balpha, sizeof(double) * (size_t)S * n));
-    if (!small) {
-      B7_TRY(b7_ensure(c, c->bK, sizeof(double) * S * nn));
-      B7_TRY(b7_ensure(c, c->bL, sizeof(double) * S * nn));
-      B7_TRY(b7_ensure(c, c->bdinv, sizeof(double) * (size_t)S * n * B7_PANEL));
-      B7_TRY(b7_ensure(c, c->bflags, sizeof(unsigned) * S * fw));
-      B7_TRY(b7_ensure(c, c->bresid, sizeof(double) * (size_t)S * n));
-    }
+    if (!small) B7_TRY(b7_ensure(c, c->bflags, sizeof(unsigned) * S * persist_flag_words_host(c->Npad / B7_PANEL)));
   }
-  if (!small) B7_HIP(c, hipMemcpyAsync(c->bhyp.p, ls_host, ls_bytes, hipMemcpyHostToDevice, c->stream));
+  if (!small) B7_HIP(c, hipMemcpyAsync(c->bhyp.p, st.hyp_host, st.hyp_bytes, hipMemcpyHostToDevice, c->stream));
   double *fd = nullptr;
   if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
-
   acc_declare_zeros(c, spec->kind);
-  if (batch) {
-    const HypPack hd = hyp_pack(c->bhyp.p, S, d);
-    const double *hyp_dev = hd.ls, *amp_dev = hd.amp, *noise_dev = hd.noise, *mean_dev = hd.mean;
-    int *reports_dev = static_cast<int *>(c->pin_eval.dev);
-    if (small) {
-      const double *hyp_map = reinterpret_cast<const double *>(static_cast<const char *>(c->pin_eval.dev) + rep_bytes);
-      B7_TRY(launch_fit_small(c, S, hyp_map, ls_host, (double *)c->bhyp.p, (double *)c->bw.p, (double *)c->bzsc.p, (double *)c->bzss.p,
-                              nullptr, (double *)c->bLinv.p, nullptr, (double *)c->balpha.p, nullptr, (int *)c->binfo.p, reports_dev));
-    } else {
-      launch_resid_batch(c, S, mean_dev);
-      B7_TRY(launch_kxx_batch(c, S, hyp_dev, amp_dev, noise_dev, (double *)c->bw.p, (double *)c->bzsc.p, (double *)c->bzss.p,
-                              (double *)c->bK.p));
-      if (n == 64 && c->potrf_small) {
-        // one 64-block per fit: factorisation, inverse, alpha and the pivot report (mirrored into the mapped block) of all S
-        // fits in ONE launch of S workgroups
-        B7_TRY(launch_potrf_small(c, S, (const double *)c->bK.p, (double *)c->bL.p, (double *)c->bLinv.p, (double *)c->bdinv.p,
-                                  (const double *)c->bresid.p, (double *)c->balpha.p, 0.0, (int *)c->binfo.p, reports_dev, (int64_t)nn,
-                                  (int64_t)nn, (int64_t)n * B7_PANEL, (int64_t)n, 4));
-      } else {
-        B7_TRY(launch_fit_batch(c, S, (const double *)c->bK.p, (double *)c->bL.p, (double *)c->bLinv.p, (double *)c->bdinv.p,
-                                (unsigned *)c->bflags.p, (int *)c->binfo.p));
-        if (4 * S <= 256) {  // the reports ride on the last kernel of the fits into the mapped block: no copy launch
-          B7_TRY(launch_alpha_batch(c, S, (const double *)c->bLinv.p, (const double *)c->bresid.p, (double *)c->balpha.p,
-                                    (const int *)c->binfo.p, reports_dev, 4 * S));
-        } else {
-          B7_TRY(launch_alpha_batch(c, S, (const double *)c->bLinv.p, (const double *)c->bresid.p, (double *)c->balpha.p));
-          B7_HIP(c, hipMemcpyAsync(reports, c->binfo.p, rep_bytes, hipMemcpyDeviceToHost, c->stream));
-        }
-      }
-    }
-    const size_t row_bytes = sizeof(double) * (size_t)n;
-    const int64_t Mpad = round_up(c->M, B7_MROWS);
-    if (c->kpost_small && kpost_small_applies(c)) {
-      // N <= 128, d <= 32: K(X*,X), mean and variance of all S samples in ONE kernel that never stores K* (kpost_small.hip)
-      B7_TRY(b7_ensure(c, c->bmu, sizeof(double) * (size_t)S * c->M));
-      B7_TRY(b7_ensure(c, c->bvar, sizeof(double) * (size_t)S * c->M));
-      B7_TRY(launch_kpost_small(c, S, (const double *)c->grid[c->grid_cur].p, c->M, (const double *)c->bw.p, (const double *)c->bzsc.p,
-                                (const double *)c->bzss.p, (const double *)c->bLinv.p, (const double *)c->balpha.p, hyp_dev, 0.0, 0.0, 0.0,
-                                (double *)c->bmu.p, (double *)c->bvar.p, c->M));
-      B7_TRY(keep_batch(c, keep, S));
-      B7_TRY(pending_score(c, S, spec, fd, pend));
-      c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
-      c->predicted = false;
-    } else if ((size_t)Mpad * S * row_bytes <= c->ks_bytes) {
-      // K* of all S samples fits the workspace at once (the reference's default sizes: 2e4 candidates, tens to hundreds
-      // of observations, 10 samples): K*, posterior and score:add of all samples in ONE launch each (grid.z / grid.y =
-      // sample), the score summed over the samples in order inside the kernel
-      B7_TRY(b7_ensure(c, c->ks, (size_t)Mpad * S * row_bytes));
-      B7_TRY(b7_ensure(c, c->bmu, sizeof(double) * (size_t)S * c->M));
-      B7_TRY(b7_ensure(c, c->bvar, sizeof(double) * (size_t)S * c->M));
-      B7_TRY(launch_ksx_batch(c, S, (const double *)c->grid[c->grid_cur].p, Mpad, c->M, (const double *)c->bw.p,
-                              (const double *)c->bzsc.p, (const double *)c->bzss.p, amp_dev, mean_dev,
-                              (const double *)c->balpha.p, (double *)c->ks.p, (int64_t)Mpad * n, (double *)c->bmu.p, c->M));
-      B7_TRY(launch_post_batch(c, S, (const double *)c->bLinv.p, (const double *)c->ks.p, (int64_t)Mpad * n, Mpad, c->M,
-                               (double *)c->bvar.p, c->M, amp_dev, noise_dev));
-      B7_TRY(keep_batch(c, keep, S));
-      ScoreParams all;
-      B7_TRY(pending_score(c, S, spec, fd, &all));
-      B7_TRY(launch_score_batch(c, all, (double *)c->acc.p, c->M));
-      c->fitted = false;     // neither the context's fit slot nor its mean / variance vectors hold any of these samples
-      c->predicted = false;
-    } else {
-      // the posterior kernels read the fit through the context: point it at one sample's slot after the other
-      void *const zsc0 = c->zsc.p, *const zss0 = c->zss.p, *const w0 = c->w.p, *const alpha0 = c->alpha.p, *const linv0 = c->Linv.p;
-      int rc = B7_OK;
-      for (int s = 0; s < S && rc == B7_OK; ++s) {
-        c->zsc.p = (double *)c->bzsc.p + (size_t)s * n * c->dpad;
-        c->zss.p = (double *)c->bzss.p + (size_t)s * n;
-        c->w.p = (double *)c->bw.p + (size_t)s * c->dpad;
-        c->alpha.p = (double *)c->balpha.p + (size_t)s * n;
-        c->Linv.p = (double *)c->bLinv.p + s * nn;
-        c->amp = hyps[s].amp;
-        c->noise = hyps[s].noise;
-        c->mean = hyps[s].mean;
-        c->model_kind = 0;
-        c->fitted = true;
-        rc = predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p);
-        c->mes_slot = s;
-        if (rc == B7_OK) rc = score_add(c, spec, fd);
-        if (rc == B7_OK) rc = keep_sample(c, keep, S, s);
-      }
-      c->zsc.p = zsc0, c->zss.p = zss0, c->w.p = w0, c->alpha.p = alpha0, c->Linv.p = linv0;
-      c->fitted = false;  // the context's own fit slot does not hold any of these fits
-      c->predicted = true;
-      c->Mpred = c->M;
-      B7_TRY(rc);
-    }
-  } else {
-    if (keep && S > 1) B7_TRY(keep_slots_ensure(c, S, keep->want_alpha));
-    for (int s = 0; s < S; ++s) {
-      B7_TRY(fit_front(c, &hyps[s], (const double *)c->bhyp.p + (size_t)s * d));
-      int *report = static_cast<int *>(c->pin_eval.dev) + 4 * s;  // a one-block factorisation mirrors its report itself
-      FactorNote note;
-      B7_TRY(launch_potrf(c, 0.0, true, report, &note));
-      if (!c->linv_done) B7_TRY(launch_trtri(c));  // on a failed factor this inverts rubbish; the report discards it
-      B7_TRY(launch_alpha(c, report, 4, note));  // + this fit's pivot report, no copy launch
-      c->fitted = true;
-      B7_TRY(predict_into(c, (const double *)c->grid[c->grid_cur].p, c->M, (double *)c->mu.p, (double *)c->var.p));
-      c->predicted = true;
-      c->Mpred = c->M;
-      c->mes_slot = s;
-      B7_TRY(score_add(c, spec, fd));
-      B7_TRY(keep_sample(c, keep, S, s));
-    }
-    // this fit's lengthscales sit in the batch staging block, not in ScratchBlock::lenscale: the fit slot is declared empty
-    c->fitted = false;
-  }
-  return B7_OK;
+  if (!batch) return fits_in_turn(c, S, hyps, spec, fd, keep);
+  B7_TRY(fits_side_by_side(c, S, small, st));
+  if (c->kpost_small && kpost_small_applies(c)) return post_side_by_side_small(c, S, spec, fd, pend, keep);
+  if ((size_t)round_up(c->M, B7_MROWS) * S * sizeof(double) * (size_t)c->Npad <= c->ks_bytes) return post_side_by_side(c, S, spec, fd, keep);
+  return post_in_turn(c, S, hyps, spec, fd, keep);
 }
 
 // after the stream has drained: did each of S fits ([S][4] report words) factor at the first attempt, without a hand-off
@@ -326,7 +329,7 @@ bool reports_clean(b7_ctx *c, const int *reports, int S, bool persist) {
 // the same nomination through the per-sample path, jitter schedule (utils/math.lua:159-218) included; synchronous
 int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, double *jitter_out, int *info_out, BelKeep *keep) {
   B7_HIP(c, hipSetDevice(c->device));
-  if (keep && S > 1) B7_TRY(keep_slots_ensure(c, S, keep->want_alpha));
+  B7_TRY(keep_slots_ensure(c, keep, S));
   B7_TRY(acc_write_zeros(c));
   if (spec->kind == B7_SCORE_MES) B7_TRY(mes_begin(c, S, c->M, c->mes_levels));
   double *fd = nullptr;
@@ -337,7 +340,7 @@ int eval_redo(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score_spec *spec, d
     if (score_needs_fmin(spec->kind)) B7_TRY(stage_fmin(c, spec->fmin, &fd));
     c->mes_slot = s;
     B7_TRY(score_add(c, spec, fd));
-    B7_TRY(keep_sample(c, keep, S, s));
+    B7_TRY(keep_sample(c, keep, S, s, false));
   }
   return B7_OK;
 }

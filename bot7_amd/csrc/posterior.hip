@@ -725,25 +725,24 @@ int dispatch_post(b7_ctx *c, const PostArgs &a, int64_t row0, int64_t rows, int6
 }
 }  // namespace
 
-int launch_post(b7_ctx *c, const double *ks, int64_t row0, int64_t rows, int64_t Mtotal, double *var) {
+int launch_post(b7_ctx *c, const FitSet &f, const double *ks, int64_t row0, int64_t rows, int64_t Mtotal, double *var) {
   PhaseScope ps(c, "post");
   const bool blr = c->model_kind == 1;
-  PostArgs a{(const double *)c->Linv.p, ks, var, blr ? 0.0 : c->amp, blr ? 1.0 : -1.0,
-             blr ? c->noise : (c->opts.var_with_noise ? c->noise : 0.0), 1, PostBatch{}};
+  PostArgs a{f.Linv, ks, var, blr ? 0.0 : f.amp, blr ? 1.0 : -1.0, blr ? f.noise : (c->opts.var_with_noise ? f.noise : 0.0), 1,
+             PostBatch{}};
   return dispatch_post(c, a, row0, rows, Mtotal);
 }
 
-// S GP fits over the same rows: Linv_s = Linv + s Npad^2, K*_s = ks + s sks, var_s = var + s svar; amp_s (and noise_s) on
-// the device
-int launch_post_batch(b7_ctx *c, int S, const double *Linv, const double *ks, int64_t sks, int64_t rows, int64_t Mtotal,
-                      double *var, int64_t svar, const double *amp_dev, const double *noise_dev) {
+// f's S GP fits (device scalars) over the same rows: K*_s = ks + s sks, var_s = var + s svar
+int launch_post_batch(b7_ctx *c, const FitSet &f, const double *ks, int64_t sks, int64_t rows, int64_t Mtotal, double *var,
+                      int64_t svar) {
   PhaseScope ps(c, "post");
-  PostArgs a{Linv, ks, var, 0.0, -1.0, 0.0, S, PostBatch{}};
-  a.pb.sLinv = (int64_t)c->Npad * c->Npad;
+  PostArgs a{f.Linv, ks, var, 0.0, -1.0, 0.0, f.S, PostBatch{}};
+  a.pb.sLinv = FitSet::s_Linv(c->Npad, c->dpad);
   a.pb.sks = sks;
   a.pb.svar = svar;
-  a.pb.base = amp_dev;
-  a.pb.var_add = c->opts.var_with_noise ? noise_dev : nullptr;
+  a.pb.base = f.amp_dev;
+  a.pb.var_add = c->opts.var_with_noise ? f.noise_dev : nullptr;
   return dispatch_post(c, a, 0, rows, Mtotal);
 }
 
@@ -753,7 +752,7 @@ int launch_post_heads(b7_ctx *c, int S, const double *Linv, const double *feat, 
                       const double *zero_dev, const double *invbeta_dev) {
   PhaseScope ps(c, "post");
   PostArgs a{Linv, feat, var, 0.0, 1.0, 0.0, S, PostBatch{}};
-  a.pb.sLinv = (int64_t)c->Npad * c->Npad;
+  a.pb.sLinv = FitSet::s_Linv(c->Npad, c->dpad);  // the heads sit in the batch slot of the fits' inverses
   a.pb.sks = 0;
   a.pb.svar = svar;
   a.pb.base = zero_dev;

@@ -366,12 +366,10 @@ int ref_work(b7_ctx *c, int S, int nparts, RefWork *wk) {
   return B7_OK;
 }
 
-// the S fits a launch set reads (strides dpad | Npad dpad | Npad | Npad^2 | Npad)
-struct RefFits { const double *w, *zsc, *zss, *Linv, *alpha; };
-
-// phases A-C and the gather for the 64 query rows in xq: mu, var, dmu, dvar of every sample into the workspace
-int ref_posterior(b7_ctx *c, int S, const RefFits &f, const RefWork &wk, const double *xq) {
-  const int n = c->Npad, nb = n / RB, d = c->dfit, dpad = c->dpad;
+// phases A-C and the gather for the 64 query rows in xq: mu, var, dmu, dvar of every sample of f into the workspace (the fits'
+// amplitudes and means are read from wk.par)
+int ref_posterior(b7_ctx *c, const FitSet &f, const RefWork &wk, const double *xq) {
+  const int n = c->Npad, nb = n / RB, d = c->dfit, dpad = c->dpad, S = f.S;
   const bool se = c->kernel != B7_KERNEL_MATERN52;
   {
     PhaseScope ps(c, "refine:k");
@@ -466,7 +464,6 @@ int b7_eval_nominate_refine(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score
   RefWork wk;
   B7_TRY(ref_work(c, S, nparts, &wk));
   B7_TRY(ensure_ref_table(c));
-  const RefFits fits{keep.w, keep.zsc, keep.zss, keep.Linv, keep.alpha};
   std::vector<double> par(2 * (size_t)S);
   for (int s = 0; s < S; ++s) par[2 * s] = hyps[s].amp, par[2 * s + 1] = hyps[s].mean;
   B7_HIP(c, hipMemcpyAsync(wk.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, c->stream));
@@ -499,7 +496,7 @@ int b7_eval_nominate_refine(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score
   sp.S = S;
   for (int it = 0; it <= iters; ++it) {
     const double *xq = wk.xq[it & 1];
-    B7_TRY(ref_posterior(c, S, fits, wk, xq));
+    B7_TRY(ref_posterior(c, keep.fits, wk, xq));
     RefStep rs;
     rs.mu = wk.mu, rs.var = wk.var, rs.dmu = wk.dmu, rs.dvar = wk.dvar;
     rs.xq = xq, rs.xq_next = wk.xq[(it + 1) & 1], rs.st = wk.st, rs.trace = trace;
@@ -588,9 +585,8 @@ int b7_gp_grad_at(b7_ctx *c, const double *X1, int64_t M1, double *mean, double 
   RefWork wk;
   B7_TRY(ref_work(c, 1, 1, &wk));
   B7_TRY(ensure_ref_table(c));
-  const RefFits fits{(const double *)c->w.p, (const double *)c->zsc.p, (const double *)c->zss.p, (const double *)c->Linv.p,
-                     (const double *)c->alpha.p};
-  const double par[2] = {c->amp, c->mean};
+  const FitSet fit = ctx_fit(c);
+  const double par[2] = {fit.amp, fit.mean};
   B7_HIP(c, hipMemcpyAsync(wk.par, par, sizeof(par), hipMemcpyHostToDevice, c->stream));
   std::vector<double> chunk((size_t)RQ * d);
   for (int64_t r0 = 0; r0 < M1; r0 += RQ) {
@@ -598,7 +594,7 @@ int b7_gp_grad_at(b7_ctx *c, const double *X1, int64_t M1, double *mean, double 
     for (int r = 0; r < RQ; ++r)  // a short chunk repeats its last row
       memcpy(&chunk[(size_t)r * d], X1 + (size_t)(r0 + std::min(r, rows - 1)) * d, sizeof(double) * d);
     B7_HIP(c, hipMemcpyAsync(wk.xq[0], chunk.data(), sizeof(double) * chunk.size(), hipMemcpyHostToDevice, c->stream));
-    B7_TRY(ref_posterior(c, 1, fits, wk, wk.xq[0]));
+    B7_TRY(ref_posterior(c, fit, wk, wk.xq[0]));
     if (mean) B7_HIP(c, hipMemcpyAsync(mean + r0, wk.mu, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
     if (var) B7_HIP(c, hipMemcpyAsync(var + r0, wk.var, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
     if (dmean) B7_HIP(c, hipMemcpyAsync(dmean + (size_t)r0 * d, wk.dmu, sizeof(double) * rows * d, hipMemcpyDeviceToHost, c->stream));

@@ -320,8 +320,8 @@ int ts_mean_over_grid(b7_ctx *c) {
   const double *grid = (const double *)c->grid[c->grid_cur].p;
   for (int64_t row0 = 0; row0 < M; row0 += chunk) {
     const int64_t rows = Mpad - row0 < chunk ? Mpad - row0 : chunk;
-    B7_TRY(launch_ksx(c, grid, row0, rows, M, c->dfit, (double *)c->ks.p, (double *)c->mu.p, c->ycols));
-    if (c->ycols > 1) B7_TRY(launch_mean_multi(c, (const double *)c->ks.p, row0, rows, M, (double *)c->mu.p));
+    B7_TRY(launch_ksx(c, ctx_fit(c), grid, row0, rows, M, c->dfit, (double *)c->ks.p, (double *)c->mu.p, c->ycols));
+    if (c->ycols > 1) B7_TRY(launch_mean_multi(c, ctx_fit(c), (const double *)c->ks.p, row0, rows, M, (double *)c->mu.p));
   }
   return B7_OK;
 }
