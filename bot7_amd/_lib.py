@@ -25,6 +25,7 @@ SYMBOLS = [
     "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_mes", "b7_mes_set_levels", "b7_mes_last_ystar", "b7_mes_ystar", "b7_mes_compute", "b7_score_cb", "b7_score_finish",
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_eval_nominate_batch", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
     "b7_ts_nominate", "b7_ts_last_paths", "b7_ts_last_draws", "b7_rff_compute",
+    "b7_kg_nominate", "b7_kg_trace_enable", "b7_kg_last", "b7_kg_compute",
     "b7_refine_default_opts", "b7_eval_nominate_refine", "b7_refine_last", "b7_refine_shape", "b7_refine_trace_enable", "b7_refine_trace", "b7_gp_grad_at", "b7_score_grad_compute",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
@@ -34,6 +35,9 @@ SYMBOLS = [
     "b7_score_logpi", "b7_logpi_compute", "b7_feas_reset", "b7_feas_add", "b7_feas_add_acc", "b7_feas_get", "b7_feas_nominate", "b7_eval_nominate_feasible",
     "b7_timer_start", "b7_timer_stop", "b7_timer_ms", "b7_profile_enable", "b7_profile_reset", "b7_profile_get", "b7_persist_fallbacks",
 ]
+
+
+KG_MAX_POINTS = 16  # B7_KG_MAX_POINTS
 
 
 class Bot7HipError(RuntimeError):
@@ -182,6 +186,10 @@ def load(which=None):
         "b7_eval_nominate_batch": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), i32, vp, vp, vp, vp]),
         "b7_ts_nominate": (i32, [vp, i32, C.POINTER(Hyp), i32, i32, C.c_uint64, vp, vp, vp, vp]),
         "b7_ts_last_paths": (i32, [vp, vp]),
+        "b7_kg_nominate": (i32, [vp, i32, C.POINTER(Hyp), i32, vp, vp, vp, vp, vp]),
+        "b7_kg_trace_enable": (i32, [vp, i32]),
+        "b7_kg_last": (i32, [vp, vp, vp, vp, vp, vp]),
+        "b7_kg_compute": (i32, [vp, C.c_int64, i32, vp, vp, vp]),
         "b7_refine_default_opts": (i32, [C.POINTER(RefineOpts)]),
         "b7_eval_nominate_refine": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), C.POINTER(RefineOpts), C.POINTER(dbl),
                                           C.POINTER(i64), vp, C.POINTER(dbl), C.POINTER(i64), vp, vp]),
@@ -1081,6 +1089,50 @@ class Context(object):
         out = {"omega": np.empty((F, d), dtype=np.float64), "phase": np.empty(F, dtype=np.float64),
                "weight": np.empty(F, dtype=np.float64), "eps": np.empty(N, dtype=np.float64)}
         self._ck(self._L.b7_ts_last_draws(self._h, int(path), _ptr(out["omega"]), _ptr(out["phase"]), _ptr(out["weight"]), _ptr(out["eps"])))
+        return out
+
+    def kg_nominate(self, hyps, points=KG_MAX_POINTS, rows=None, want_report=False, trace=False):
+        """The knowledge gradient (b7_kg_nominate): the row of the resident grid whose evaluation is expected to lower the minimum of
+        the posterior mean the most, marginalised over hyps.  points: the size n of the discretisation set (1..KG_MAX_POINTS);
+        rows: its n distinct 1-based grid rows (None: the library takes the n rows of lowest marginal mean).  trace: keep the
+        slopes for kg_last.  Returns (value, 1-based index[, report]); the grid is not modified."""
+        S = len(hyps)
+        arr, keep = self._pack_hyps(hyps, getattr(self, "_data_d", -1))
+        rows1 = None
+        if rows is not None:
+            rows1 = np.ascontiguousarray(np.asarray(rows).ravel(), dtype=np.int64)
+            points = rows1.size
+        jit = np.zeros(max(S, 1), dtype=np.float64) if want_report else None
+        info = np.zeros(max(S, 1), dtype=np.int32) if want_report else None
+        val, idx = C.c_double(), C.c_int64()
+        self._ck(self._L.b7_kg_trace_enable(self._h, 1 if trace else 0))
+        self._ck(self._L.b7_kg_nominate(self._h, S, arr, int(points), _ptr(rows1), C.byref(val), C.byref(idx), _ptr(jit), _ptr(info)))
+        self.fit_token += 1
+        self._kg_shape = (S, self.grid_shape()[0], int(points))   # what kg_last returns
+        if want_report:
+            return val.value, idx.value, {"jitter": jit[:S], "info": info[:S]}
+        return val.value, idx.value
+
+    def kg_last(self, slopes=False):
+        """What the last kg_nominate used and made (b7_kg_last): dict(rows n (1-based), alpha S x n, values S x M, own_alpha S x M[,
+        slopes S x M x (n + 1): column 0 the own line, NaN where the row is in the discretisation set]); slopes needs trace=True."""
+        S, M, n = getattr(self, "_kg_shape", (1, 1, 1))
+        out = {"rows": np.zeros(n, dtype=np.int64), "alpha": np.empty((S, n), dtype=np.float64),
+               "values": np.empty((S, M), dtype=np.float64), "own_alpha": np.empty((S, M), dtype=np.float64)}
+        if slopes:
+            out["slopes"] = np.empty((S, M, n + 1), dtype=np.float64)
+        self._ck(self._L.b7_kg_last(self._h, _ptr(out["rows"]), _ptr(out["alpha"]), _ptr(out.get("slopes")), _ptr(out["values"]),
+                                    _ptr(out["own_alpha"])))
+        return out
+
+    def kg_compute(self, alpha, b):
+        """min_i alpha_i - E[min_i (alpha_i + b_i Z)] per row of alpha, b (M1 x L, L <= KG_MAX_POINTS + 1) by the nomination's own
+        code (b7_kg_compute); column 0 is the own line, a NaN slope there means the row has none."""
+        alpha, b = _f64(alpha), _f64(b)
+        if alpha.ndim != 2 or alpha.shape != b.shape:
+            raise Bot7HipError(-1, "kg_compute: alpha and b are M1 x L")
+        out = np.empty(alpha.shape[0], dtype=np.float64)
+        self._ck(self._L.b7_kg_compute(self._h, alpha.shape[0], alpha.shape[1], _ptr(alpha), _ptr(b), _ptr(out)))
         return out
 
     def rff_compute(self, X, omega, phase, W):

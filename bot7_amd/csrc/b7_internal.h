@@ -265,6 +265,16 @@ struct b7_ctx {
   bool refine_trace_on = false, refine_valid = false;
   int refine_P = 0, refine_d = 0, refine_iters = 0, refine_trace_P = 0, refine_trace_iters = 0;  // shapes of what the last call left (trace_P 0: no trace)
   RefState refine_last;     // the last call's final state
+  // ---- b7_kg_nominate (kg.hip): what the last call left for b7_kg_last, and b7_kg_compute's staging, apart from it
+  DevBuf kg;         // mu [S][M] | var [S][M] | v [S][M]: every sample's posterior and its knowledge gradient over the grid
+  DevBuf kgvec;      // the small arrays of a call (kg.hip: KgState)
+  DevBuf kg_slopes;  // [S][M][n + 1], written only while b7_kg_trace_enable is on
+  DevBuf kg_user;
+  PinBuf pin_kg;     // amp, noise + jitter of the S samples on their way to kgvec (not mapped)
+  bool kg_trace_on = false, kg_valid = false, kg_traced = false;
+  int kg_S = 0, kg_n = 0;  // the shapes of what the last successful call left
+  int64_t kg_M = 0;
+  size_t kg_al_off = 0;    // where that call's alpha [S][16] sits in kgvec (doubles); the rows of A follow it
   DevBuf feat;   // DNGO basis features of the resident grid: Mfeat x Npad (zero-padded columns)
   size_t feat_zeroed_bytes = 0;  // how much of `feat` was zeroed when it was laid out for feat_z columns
   int feat_z = -1;

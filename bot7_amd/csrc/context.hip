@@ -196,7 +196,7 @@ void b7_destroy(b7_ctx *c) {
                    &c->bhyp, &c->bw, &c->bzsc, &c->bzss, &c->bK, &c->bL, &c->bdinv, &c->bflags, &c->binfo, &c->bresid, &c->bterms,
                    &c->bLinv, &c->balpha, &c->bmu, &c->bvar, &c->ticket, &c->bel, &c->belvec, &c->ystar, &c->mes_ticket, &c->mes_user,
                    &c->ts_paths, &c->ts_draw, &c->ts_work, &c->ts_user, &c->slice_trace, &c->slice_state, &c->refine_ws, &c->refine_trace, &c->refine_user,
-                   &c->feas, &c->feas_stage};
+                   &c->feas, &c->feas_stage, &c->kg, &c->kgvec, &c->kg_slopes, &c->kg_user};
   for (auto &kv : c->pjobs_cache) b7_release(kv.second.buf);
   for (DevBuf *b : all) b7_release(*b);
   if (c->tev_init)
@@ -206,7 +206,7 @@ void b7_destroy(b7_ctx *c) {
     }
   resolve_phases(c);
   if (c->pinned) (void)hipHostFree(c->pinned);
-  for (PinBuf *b : {&c->pin_eval, &c->pin_blr, &c->pin_nll, &c->pin_bel, &c->pin_slice})
+  for (PinBuf *b : {&c->pin_eval, &c->pin_blr, &c->pin_nll, &c->pin_bel, &c->pin_slice, &c->pin_kg})
     if (b->host) (void)hipHostFree(b->host);
   if (c->tab_host) (void)hipHostFree(c->tab_host);
   for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);

@@ -15,6 +15,10 @@ level count (config.score.nLevels) and as b7_score_mes in the per-sample loop, e
 device; on one GPU only -- a sharded candidate set or a batch (config.bot.batch > 1) answers "unsupported".
 'thompson_sampling' (not in the reference) is not a per-point score: nominate and nominate_batch, q = 1 included, go through
 b7_ts_nominate with a seed from the bot's own generator, and eval(want_scores=True) raises -- there is no score vector.
+'knowledge_gradient' (not in the reference) is a policy too: eval and nominate go through b7_kg_nominate with config.score.points
+discretisation rows (default 16), chosen by config.score.discretisation: 'mean' (default; the library takes the rows of lowest
+marginal posterior mean) or 'thompson' (the minimisers of that many b7_ts_nominate paths, drawn with a seed from the bot's own
+generator, are handed over).  What is not built is refused by name (kg_refusal, refine_refusal, constraint_refusal).
 
 config.bot.refine (ours; False = the reference's loop, untouched) is a dict of starts / iters / eta0: a model-based trial then goes
 through b7_eval_nominate_refine, which climbs the marginalised acquisition from the best grid rows inside the grid's box
@@ -54,6 +58,8 @@ def refine_refusal(config, model_class="bot7.models.gp_regressor", sharded=False
         return "config.bot.refine with thompson_sampling: a sample path is not a per-point score"
     if kind == "max_value_entropy_search":
         return "config.bot.refine with max_value_entropy_search: the score has no gradient piece"
+    if kind == "knowledge_gradient":
+        return "config.bot.refine with knowledge_gradient: refinement of a knowledge-gradient nominee is not built"
     return None
 
 
@@ -78,11 +84,34 @@ def constraint_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
         return "config.bot.constraints with confidence_bound: a signed score has no product form with a feasibility weight"
     if kind == "max_value_entropy_search":
         return "config.bot.constraints with max_value_entropy_search: the score has no feasibility weight"
+    if kind == "knowledge_gradient":
+        return "config.bot.constraints with knowledge_gradient: the knowledge gradient has no feasibility weight"
     if kind not in CONSTRAINED_SCORES:
         return "config.bot.constraints with %s: only %s are built" % (kind, ", ".join(CONSTRAINED_SCORES))
     for k, con in enumerate(config["bot"]["constraints"]):
         if (con.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
             return "config.bot.constraints[%d] with the %s model: a constraint is modelled by a gp_regressor" % (k, con["model"]["type"])
+    return None
+
+
+KG_DISCRETISATIONS = ("mean", "thompson")
+
+
+def kg_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
+    """Why this configuration cannot nominate by the knowledge gradient (b7_kg_nominate's own refusals, by name), or None."""
+    if int(config["bot"].get("batch", 1)) > 1:
+        return "knowledge_gradient with config.bot.batch > 1: knowledge-gradient batches are not built"
+    if config["bot"].get("refine"):
+        return refine_refusal(config, model_class, sharded)
+    if config["bot"].get("constraints"):
+        return constraint_refusal(config, model_class, sharded)
+    if sharded:
+        return "knowledge_gradient over sharded candidates: the knowledge gradient over a sharded grid is not built"
+    if model_class == "bot7.models.dngo":
+        return "knowledge_gradient with the dngo model: the Bayesian-linear head has no posterior-covariance kernel"
+    kind = config["score"].get("discretisation", "mean")
+    if kind not in KG_DISCRETISATIONS:
+        return "knowledge_gradient with config.score.discretisation = %r: %s are built" % (kind, ", ".join(KG_DISCRETISATIONS))
     return None
 
 
@@ -168,6 +197,11 @@ class bayesopt(abstract):
                 raise NotImplementedError("thompson_sampling has no score vector (eval with want_scores=False, or nominate)")
             idx = self._ts_nominate(1, X_hid)[0]
             return None, None, idx
+        if self._kg():
+            val, idx = self._kg_nominate(X_hid)
+            scores = ctx.score_finish(1.0, download=True)[2] if want_scores else None   # the accumulator holds the marginal KG
+            self.last_scores = scores
+            return scores, val, idx
         if model.class_() == "bot7.models.dngo":                  # :65-66: one score call, no marginalisation loop
             model.predict_device(X_obs, Y_obs, X_hid, None)
             ctx.score_reset()
@@ -226,6 +260,29 @@ class bayesopt(abstract):
         self.last_scores = None
         return [int(i) for i in idx]
 
+    def _kg(self):
+        return self.config["score"]["type"] == "knowledge_gradient"
+
+    def _kg_nominate(self, cand):
+        """(value, 1-based nominee) by the knowledge gradient (b7_kg_nominate): the hyper samples as eval's fused branch draws them
+        (bots/bayesopt.lua:68, :73-75); under discretisation = 'thompson' the rows of A are the minimisers of `points` sample paths
+        under those same hyper samples.  self.last_kg keeps what the call used."""
+        X_obs, Y_obs, model = self.observed, self.responses, self.model
+        why = kg_refusal(self.config, model.class_(), hasattr(cand, "commit"))
+        if why:
+            raise NotImplementedError(why)
+        hyps = self._sample_hyps(model, X_obs, Y_obs)
+        model.stage(X_obs, Y_obs, cand)
+        points = min(int(self.score.config["points"]), cand.shape[0])
+        rows, seed = None, None
+        if self.score.config["discretisation"] == "thompson":
+            seed = int(self._rng.integers(0, 2 ** 63))
+            rows = [int(i) for i in model.ctx.ts_nominate(hyps, points, n_features=int(self.score.config["nFeatures"]), seed=seed)[1]]
+        val, idx = self.score.nominate(model.ctx, hyps, points, rows)
+        self.last_scores = None
+        self.last_kg = {"hyps": hyps, "points": points, "rows": rows, "seed": seed, "value": val, "index": int(idx)}
+        return val, int(idx)
+
     def nominate(self, candidates=None):
         """bots/bayesopt.lua:85-99."""
         cand = self.candidates if candidates is None else candidates
@@ -246,6 +303,8 @@ class bayesopt(abstract):
             return [int(i) + 1 for i in self._rng.choice(cand.shape[0], size=q, replace=False)]
         if self._thompson():
             return self._ts_nominate(q, cand)
+        if self._kg():
+            raise NotImplementedError(kg_refusal(dict(self.config, bot=dict(self.config["bot"], batch=q))))
         X_obs, Y_obs, model = self.observed, self.responses, self.model
         spec = getattr(self.score, "device_spec", None)
         assert spec is not None and hasattr(model, "stage") and not hasattr(cand, "commit"), \
@@ -410,6 +469,10 @@ class bayesopt(abstract):
     def run_trial(self):
         """bots/abstract.lua:112-152 with config.bot.batch nominees per trial: all of them are stolen from the candidates in one
         stable pass (:118), evaluated and observed (:124-144).  batch = 1 is the parent's loop, untouched."""
+        if self._kg():
+            why = kg_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
+            if why:
+                raise NotImplementedError(why)
         if self._constrained():
             return self._run_trial_constrained()
         if self.config["bot"]["refine"]:

@@ -656,6 +656,44 @@ int b7_ts_last_draws(b7_ctx *ctx, int path, double *omega /*F x d*/, double *pha
 int b7_rff_compute(b7_ctx *ctx, const double *X /*M1 x d*/, int64_t M1, int d, const double *omega /*F x d*/,
                    const double *phase /*F*/, const double *W /*F x q*/, int F, int q, double *out /*M1 x q*/);
 
+/* THE KNOWLEDGE GRADIENT: a one-step look-ahead nomination.  No counterpart in the reference; Frazier, Powell & Dayanik (2009),
+ * Scott, Frazier & Powell (2011).  The expected decrease of the MINIMUM OF THE POSTERIOR MEAN after one more, possibly noisy,
+ * evaluation at x -- it needs no incumbent f_min and values a point for what it teaches about other points.  Under hyper sample
+ * s, with a discretisation set A of n grid rows a_1 .. a_n:
+ *   KG_s(x) = min_i alpha_i - E_Z[min_i (alpha_i + b_i Z)] >= 0,       Z ~ N(0, 1),
+ *   alpha_i = mu_s(a_i),  b_i = c_i(x) / sqrt(t(x)),  c_i(x) = k_s(x, a_i) - K*_s(x, X) inv(K_s) k_s(X, a_i)  (the posterior covariance),
+ *   t(x) = var_s(x) + noise_s (+ the jitter its factorisation may have needed);
+ *   line 0 is x's own: alpha_0 = mu_s(x), b_0 = var_s(x) / sqrt(t(x)); it is left out when x is itself a row of A (by row index).
+ * The expectation is exact (the lower envelope of the n + 1 lines, in Frazier's positive-term form: a small KG keeps its relative
+ * accuracy).  var NaN or < 0, or mu NaN: NaN; t(x) = 0: 0.  The nominee is the arg-max of the linear mean over the S samples in
+ * sample order, by b7_eval_nominate's rule (the first NaN, else the maximum, ties to the lowest index).
+ *   rows1   n distinct 1-based grid rows, e.g. the minimisers b7_ts_nominate returned; NULL: the library takes the n rows of lowest
+ *           (1/S) sum_s mu_s (ties to the lowest index), chosen on the device.
+ * Fits, routes, the single host wait and the jitter redo are b7_eval_nominate's; jitter_out / info_out as there (nullable, S).
+ * Runs over the resident data (one response column) and grid, both covariance kernels.  Deterministic: the same call twice gives the
+ * same bits, and a row's value does not depend on how many rows the grid has.  The grid is not modified; the context's fit slot
+ * holds none of the samples afterwards; the score accumulator holds the marginal knowledge gradient (b7_score_finish reads it).
+ * B7_ERR_INVALID: n outside 1..B7_KG_MAX_POINTS or above the grid's rows; a duplicate or out-of-range row; S < 1; NULL hyps,
+ * best_val or best_idx1.  B7_ERR_UNSUPPORTED, the case named: more than one response column, var_with_noise / var_clamp, a
+ * communicator of more than one rank.  B7_ERR_STATE: a member of a group, no resident data or grid.
+ * Device memory beside the posterior's own buffers: 3 S M doubles and 32 S Npad for the columns, allocated on demand.
+ * Not built: sharded grids and groups, batches, refinement of the nominee, the Bayesian-linear head, constraints, a continuous
+ * discretisation.  Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_KG_MAX_POINTS 16
+int b7_kg_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int n, const int64_t *rows1 /* n, 1-based grid rows; nullable */,
+                   double *best_val, int64_t *best_idx1, double *jitter_out /*S*/, int *info_out /*S*/);
+/* Inspection (tests): what the last successful b7_kg_nominate used and made -- the rows of A (1-based), alpha (S x n), the slopes
+ * (S x M x (n + 1), column 0 the own line: NaN where the row is in A and has none), the per-sample values (S x M) and the own
+ * lines' intercepts mu_s(x) (S x M); each nullable.  The slopes are kept only by calls made while b7_kg_trace_enable is on (the
+ * nomination stores nothing extra otherwise).  B7_ERR_STATE before a successful call, or for slopes the call did not keep. */
+int b7_kg_trace_enable(b7_ctx *ctx, int on);
+int b7_kg_last(b7_ctx *ctx, int64_t *rows1 /*n*/, double *alpha /*S x n*/, double *slopes /*S x M x (n+1), column 0 = own line*/,
+               double *values /*S x M*/, double *own_alpha /*S x M*/);
+/* The envelope expectation alone on host arrays (the b7_ei_compute of the knowledge gradient), by the nomination's own code:
+ * out[j] = min_i alpha[j][i] - E[min_i (alpha[j][i] + b[j][i] Z)] over L lines, L in 1..B7_KG_MAX_POINTS + 1.  Column 0 is the own
+ * line; a NaN slope there means the row has none (b7_kg_last's convention).  Finite input gives a finite result >= 0. */
+int b7_kg_compute(b7_ctx *ctx, int64_t M1, int L, const double *alpha /*M1 x L*/, const double *b /*M1 x L*/, double *out);
+
 /* bayesopt:eval's DNGO branch + nominate as ONE call (bots/bayesopt.lua:65-66, :96 over models/dngo.lua:155-175):
  * b7_blr_fit_x(net, X0, Y0, ...) + b7_blr_basis(net, resident grid) + b7_blr_predict + the acquisition of `spec` (written,
  * not accumulated: ONE point (alpha_prec, beta, mean); b7_blr_eval_nominate_marg below marginalises over S of them) +

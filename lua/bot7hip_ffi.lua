@@ -99,6 +99,10 @@ int b7_ts_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_
 int b7_ts_last_paths(b7_ctx *ctx, double *paths_host );
 int b7_ts_last_draws(b7_ctx *ctx, int path, double *omega , double *phase , double *weight , double *eps );
 int b7_rff_compute(b7_ctx *ctx, const double *X , int64_t M1, int d, const double *omega , const double *phase , const double *W , int F, int q, double *out );
+int b7_kg_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int n, const int64_t *rows1 , double *best_val, int64_t *best_idx1, double *jitter_out , int *info_out );
+int b7_kg_trace_enable(b7_ctx *ctx, int on);
+int b7_kg_last(b7_ctx *ctx, int64_t *rows1 , double *alpha , double *slopes , double *values , double *own_alpha );
+int b7_kg_compute(b7_ctx *ctx, int64_t M1, int L, const double *alpha , const double *b , double *out);
 int b7_blr_eval_nominate(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, double alpha_prec, double beta, double mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *jitter_used);
 int b7_blr_eval_nominate_marg(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *alpha_prec, const double *beta, const double *mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *nll_out, double *jitter_used);
 typedef struct b7_group b7_group;
@@ -174,6 +178,7 @@ M.REFINE_CONVERGED = 4
 M.REFINE_MOVED = 8
 M.REFINE_TRACE_WIDTH = 200
 M.TS_MAX_FEATURES = 4096
+M.KG_MAX_POINTS = 16
 M.MAX_TIMERS = 16
 -- END generated constants
 

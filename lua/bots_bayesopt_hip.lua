@@ -82,6 +82,51 @@ local function ts_nominate(self, q, candidates)
   return out
 end
 
+-- The knowledge gradient (b7_kg_nominate; no original): the row whose evaluation is expected to lower the minimum of the posterior
+-- mean the most, over config.score.points discretisation rows (default 16).  config.score.discretisation = 'mean' (default): the
+-- library takes the rows of lowest marginal mean; 'thompson': the minimisers of that many b7_ts_nominate paths under the same hyper
+-- samples are handed over.  One rank, no group, no batch.  Returns a LongTensor of one index into `candidates` as it stands.
+local function nominate_kg(self, candidates)
+  assert(D.world == 1 and not hip.group, 'knowledge_gradient: one rank, no group (the knowledge gradient over a sharded grid is not built)')
+  assert((self.config.bot.batch or 1) == 1, 'knowledge_gradient: config.bot.batch > 1 (knowledge-gradient batches are not built)')
+  local model, keep = self.model, {}
+  assert(torch.type(model) == 'bot7.models.gp_hip', 'knowledge_gradient: needs the gp_hip model')
+  local Y_obs = self.responses
+  if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
+  local X_obs, S = self.observed, self.config.bot.nSamples
+  model:sample_hypers(X_obs, Y_obs)                                          -- :68
+  local hyps = ffi.new('b7_hyp[?]', S)
+  for s = 1, S do                                                            -- :73-75
+    local hyp = model:parse_hypers(model:sample_hypers(X_obs, Y_obs, nil, nil, true))
+    local ls  = hip.pin(hyp.lenscale_sq)
+    keep[#keep + 1] = ls
+    hyps[s-1].lenscale_sq, hyps[s-1].amp, hyps[s-1].noise, hyps[s-1].mean = hip.data(ls), hyp.amp, hyp.noise, hyp.mean
+  end
+  model:stage(X_obs, Y_obs, candidates)
+  hip.set_kernel(model.kernel_code)
+  local cfg = self.score.config or {}
+  local n = math.min(cfg.points or 16, hip.KG_MAX_POINTS, candidates:size(1))
+  local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+  local rows = nil
+  if (cfg.discretisation or 'mean') == 'thompson' then
+    local seed = ffi.new('uint64_t', torch.random())
+    local pv = ffi.new('double[?]', n)
+    rows = ffi.new('int64_t[?]', n)
+    hip.check(hip.C.b7_ts_nominate(hip.ctx, S, hyps, n, cfg.nFeatures or 1024, seed, pv, rows, jit, info))
+  else
+    assert((cfg.discretisation or 'mean') == 'mean', "knowledge_gradient: config.score.discretisation is 'mean' or 'thompson'")
+  end
+  local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
+  hip.check(hip.C.b7_kg_nominate(hip.ctx, S, hyps, n, rows, v, i, jit, info))
+  for s = 0, S - 1 do
+    if jit[s] > 0 then   -- the reference's warning text, utils/math.lua:210-212
+      print(string.format('Warning: utils.math.chol succeeded in factorizing the\ninput matrix after applying a jitter of %.2e', jit[s]))
+    end
+  end
+  self.best_score = v[0]
+  return torch.LongTensor{tonumber(i[0])}
+end
+
 function bot:nominate(candidates)
   local candidates = candidates or self.candidates
   if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91
@@ -90,6 +135,7 @@ function bot:nominate(candidates)
     return torch.rand(1):mul(rows):long():add(1)
   end
   if torch.type(self.score) == 'bot7.scores.thompson_sampling_hip' then return ts_nominate(self, 1, candidates) end
+  if torch.type(self.score) == 'bot7.scores.knowledge_gradient_hip' then return nominate_kg(self, candidates) end
   local model, keep = self.model, {}
   local Y_obs = self.responses
   if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
@@ -141,6 +187,7 @@ function bot:nominate_batch(q, candidates)
     return torch.randperm(candidates:size(1)):narrow(1, 1, q):long()
   end
   if torch.type(self.score) == 'bot7.scores.thompson_sampling_hip' then return ts_nominate(self, q, candidates) end
+  assert(torch.type(self.score) ~= 'bot7.scores.knowledge_gradient_hip', 'nominate_batch: knowledge-gradient batches are not built')
   local model, keep = self.model, {}
   local Y_obs = self.responses
   if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end

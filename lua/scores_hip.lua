@@ -157,6 +157,25 @@ do
 end
 
 do
+  -- The knowledge gradient (b7_kg_nominate; no original): not a per-point score either -- it needs the posterior covariance against
+  -- its discretisation set.  The class carries config.points / discretisation / nFeatures to bots_bayesopt_hip.lua, whose
+  -- nominate calls the library in place of eval + arg-max.  Checked by the static checker only.
+  local KG, parent = torch.class('bot7.scores.knowledge_gradient_hip', 'bot7.scores.abstract')
+  function KG:__init(config)
+    parent.__init(self)
+    local config = config or {}
+    config['points']         = config.points or 16
+    config['discretisation'] = config.discretisation or 'mean'
+    config['nFeatures']      = config.nFeatures or 1024
+    self.config = config
+  end
+  function KG:__call__(model, hyp, X_obs, Y_obs, X_hid, X_pend, config)
+    error('knowledge_gradient_hip is not a per-point score: nominate through bot7.bots.bayesopt_hip (b7_kg_nominate)')
+  end
+  S.knowledge_gradient = KG
+end
+
+do
   local CB, parent = torch.class('bot7.scores.confidence_bound_hip', 'bot7.scores.abstract')
   function CB:__init(config)
     parent.__init(self)
