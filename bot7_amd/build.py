@@ -22,7 +22,7 @@ SOURCES = ["context.hip", "grid_api.hip", "gp_api.hip", "nominate.hip", "blr_api
 # a bit-for-bit reference.  Only translation units that mention B7_DIAG are compiled a second time; the rest are shared.
 DIAG_ONLY_SOURCES = ["nll_small.hip"]
 DIAG_OUT = os.path.join(ROOT, "tools", "_build", "libbot7hip_diag.so")
-HEADERS = [os.path.join(CSRC, "b7_internal.h"), os.path.join(CSRC, "gemm_f64.h"), os.path.join(CSRC, "potrf_diag.h"), os.path.join(CSRC, "comm_rccl.h"), os.path.join(CSRC, "ksx_exp.h"), os.path.join(CSRC, "exp_table.h"), os.path.join(CSRC, "mes_math.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "gp_small_body.h"),
+HEADERS = [os.path.join(CSRC, "b7_internal.h"), os.path.join(CSRC, "gemm_f64.h"), os.path.join(CSRC, "potrf_diag.h"), os.path.join(CSRC, "comm_rccl.h"), os.path.join(CSRC, "ksx_exp.h"), os.path.join(CSRC, "exp_table.h"), os.path.join(CSRC, "mes_math.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "gp_small_body.h"), os.path.join(CSRC, "post_ring_layout.h"),
            os.path.join(ROOT, "include", "bot7hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-fast-math", "-Wall",
@@ -115,6 +115,8 @@ def check_agpr_discipline():
                 stats["acc_reads"] += "v_accvgpr_read_b32" in code
             else:
                 if re.search(r"(?<![A-Za-z0-9_.])a(\[|\d)", code):
+                    bad.append(line.strip())
+                if nj == 16 and re.search(r"\bm0\b", code):    # the tall shape's LDS-DMA statements own M0 the same way
                     bad.append(line.strip())
                 stats["scratch"] += "scratch_" in code
         if bad or stats["scratch"] or stats["mfma_from_zero"] != ntiles or stats["acc_reads"] != 8 * ntiles:

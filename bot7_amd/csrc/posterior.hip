@@ -24,11 +24,13 @@
 // had inferred from counters -- and the workgroup NOT issuing MFMAs for 14 % of its cycles: the two waves of a SIMD
 // run in lock step, sit in the same LDS wait at mid-stage and at the barrier, and 256 registers per wave leave no room
 // to fetch fragments ahead.  The kernels below: 96 % issue efficiency at 2.31-2.33 GHz, 71.7 TF (128-row n-tiles) and
-// 73 TF (256-row n-tiles) = 91-93 % of the 78.6 TF peak.
+// 73 TF (256-row n-tiles) = 91-93 % of the 78.6 TF peak.  The 256-row shape has since been given LDS-DMA staging into a ring
+// of three images (its header below): 98.5 % issue efficiency, 2.5 % fewer cycles at the same clock.
 //
 // Algorithmic work per launch: rows * Npad^2 flops (triangle exploited), bytes: the K* chunk is read
 // (t+1)/T-weighted ~ (T+1)/2 times from L2/MALL/HBM (T = Npad/128 n-tiles), Linv once per workgroup from L2.
 #include "b7_internal.h"
+#include "post_ring_layout.h"
 #include <utility>
 
 #ifdef B7_POST_STAMPS
@@ -337,26 +339,68 @@ constexpr int lds_bytes() { return 2 * (BM + 64 * NJ) * LD * 8; }
 // Same stream, same 32 accumulator tiles per wave (16 strips of rows x 2 strips of candidates), but an n-tile of 256 rows:
 // the K* rows of a workgroup are walked Npad/256 times instead of Npad/128, which halves the K* bytes the kernel pulls
 // through the L2 (the traffic the counters price at 8.6x the algorithmic bytes) at the price of reading L^-1 twice as
-// often from the L2 it is resident in.  18 fragments per k-step do not fit twice over as two-k-step sets in 256 VGPRs,
-// so the fragment sets hold ONE k-step each and alternate per k-step; the barrier moves to three quarters of the stage:
-//   k-step 0: MFMAs(set 0) | read set 1 = k-step 1 | first half of the LDS stores of the next stage
-//   k-step 1: MFMAs(set 1) | read set 0 = k-step 2 | second half of the stores
-//   k-step 2: MFMAs(set 0) | read set 1 = k-step 3 | global loads of the stage after next
-//   barrier
-//   k-step 3: MFMAs(set 1) | read set 0 = k-step 0 of the next stage
+// often from the L2 it is resident in.  The fragment sets hold ONE k-step each and alternate per k-step.
+//
+// Operands reach LDS by LDS-DMA (global_load_lds_dwordx4), never through registers: a stage image is 384 rows at a
+// 128-byte pitch, XOR-swizzled (post_ring_layout.h: the one map the DMA source addresses and the fragment reads share),
+// 48 pieces of 1 KiB; a wave issues twelve of them per stage, M0 = the piece's LDS address, source = a scalar base
+// (n-tile row, k block and the piece's row offset, advanced on the SALU) + ONE 32-bit per-lane offset that is constant
+// for the whole kernel.  Three images form a ring:
+//   k-step 0: MFMAs(set 0) | read set 1 = k-step 1 | DMA pieces 0..3 of stage n+2 into buffer (n+2) % 3
+//   k-step 1: MFMAs(set 1) | read set 0 = k-step 2 | DMA pieces 4..7
+//   k-step 2: MFMAs(set 0) | read set 1 = k-step 3 | DMA pieces 8..11; the last three MFMAs carry nothing
+//   s_waitcnt vmcnt(12) lgkmcnt(0); s_barrier
+//   k-step 3: MFMAs(set 1) | read set 0 = k-step 0 of stage n+1 from buffer (n+1) % 3
+// (the pieces sit evenly between the reads).  Ring invariant.  RAW: a wave's pieces of stage n+1 were issued during stage
+// n-1; vmcnt(12) in front of stage n's barrier leaves only the twelve of stage n+2 in flight (loads retire in order), so
+// behind that barrier every wave's part of image n+1 is in LDS, and nothing reads it earlier.  WAR: buffer (n+2) % 3 =
+// (n-1) % 3 was last read by stage n-1's fragment reads, all of them issued -- and, by lgkmcnt(0), returned -- in front of
+// stage n-1's barrier; every DMA into it is issued behind that barrier.  Only s_barrier and s_waitcnt order anything: a slip
+// here gives wrong bits, never a hang.  The pieces requested past the last stage (the cursor clamps) are waited for before
+// the workgroup ends and its LDS goes to the next one.
+// No VALU instruction is left in the stream: every LDS address a lane reads through (3 ring positions x 4 k-steps x 2
+// operands, strips as immediates) sits in a register for the whole kernel, and the stages name their ring position at
+// compile time, a tile starting at position 0.  A tile has 16 (t + 1) stages, not a multiple of three, so once or twice
+// per tile Lane::rotate renames the buffers (24 register moves) instead.  (With one runtime base added per k-step and
+// operand -- eight v_add_u32 per stage -- the kernel kept 1.5 % of its cycles: DESIGN section 8.)
 // The fold runs over the two 128-row halves of the tile in the order of the 128-row kernels, so the bits are the same.
 template <int NJ, int NR>
 struct Tall {
-  static constexpr int BMT = 16 * NR, BN = 64 * NJ, A_DBLT = BMT * LD, STAGE_DBL = (BMT + BN) * LD;
-  static constexpr int NCA = BMT / 32, NC = NCA + 2 * NJ, NP = NR + NJ;
-  static constexpr int LDS_BYTES = 2 * STAGE_DBL * 8;
+  static constexpr int BMT = 16 * NR, BN = 64 * NJ, ROWS = BMT + BN;
+  static constexpr int STAGE_BYTES = ROWS * post_ring::ROW_BYTES, NBUF = 3;
+  static constexpr int ND = ROWS / post_ring::PIECE_ROWS / post_ring::WAVES;  // DMA pieces per wave and stage
+  static constexpr int NDA = BMT / post_ring::PIECE_ROWS / post_ring::WAVES;  // of them L^-1 rows
+  static constexpr int NP = NR + NJ;
+  static constexpr int LDS_BYTES = NBUF * STAGE_BYTES;
   static_assert(NJ * NR == 32, "32 accumulator tiles per wave");
+  static_assert(ND == 12 && ND % 3 == 0, "vmcnt(12) below is ND; a third of the pieces per k-step");
+  static_assert(LDS_BYTES <= 160 * 1024, "three stage images in 160 KiB");
 
   struct Set {
     double a[NR], b[NJ];
   };
-  struct Data {
-    d2_t c[NC];
+  typedef __attribute__((address_space(3))) double lds_double;  // fragment reads go through LDS ADDRESSES held in registers
+  // per-lane constants: fragment byte addresses per ring position and k-step (L^-1 strips; candidates strips), the DMA
+  // source offset; wave-uniform: the LDS address of the wave's first piece per ring position.  Ring positions are LOGICAL:
+  // the stages of a tile name them at compile time, position 0 first, so that no address is formed inside the stream;
+  // where the stream's stage count is not a multiple of three (once or twice per tile) rotate() renames the buffers.
+  struct Lane {
+    int fa[NBUF][4], fb[NBUF][4];
+    unsigned src, dst[NBUF];
+    __device__ __forceinline__ void rotate1() {  // position p becomes what p + 1 was
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int a = fa[0][s], b = fb[0][s];
+        fa[0][s] = fa[1][s], fa[1][s] = fa[2][s], fa[2][s] = a;
+        fb[0][s] = fb[1][s], fb[1][s] = fb[2][s], fb[2][s] = b;
+      }
+      const unsigned d = dst[0];
+      dst[0] = dst[1], dst[1] = dst[2], dst[2] = d;
+    }
+    __device__ __forceinline__ void rotate(int k) {  // k wave-uniform
+      if (k >= 1) rotate1();
+      if (k >= 2) rotate1();
+    }
   };
   struct Cursor {
     int t, kb, ntiles;
@@ -370,81 +414,76 @@ struct Tall {
     }
   };
 
-  // fragment P of k-step S: P < NJ candidates strip P, else rows strip P - NJ
-  template <int P, int S>
-  static __device__ __forceinline__ void read_one(Set &f, const double *__restrict__ sa, const double *__restrict__ sb) {
+  // fragment P of k-step S from the image at ring position B: P < NJ candidates strip P, else rows strip P - NJ
+  template <int P, int S, int B>
+  static __device__ __forceinline__ void read_one(Set &f, const Lane &ln) {
+    constexpr int strip = (P < NJ ? P : P - NJ) * 16 * post_ring::ROW_BYTES;
     if constexpr (P < NJ)
-      f.b[P] = sb[P * 16 * LD + 4 * S];
+      f.b[P] = *reinterpret_cast<const lds_double *>((uintptr_t)(unsigned)(ln.fb[B][S] + strip));
     else
-      f.a[P - NJ] = sa[(P - NJ) * 16 * LD + 4 * S];
+      f.a[P - NJ] = *reinterpret_cast<const lds_double *>((uintptr_t)(unsigned)(ln.fa[B][S] + strip));
   }
+  // piece C of this wave: C < NDA rows 32 C + 8 wave .. + 7 of the L^-1 tile, else candidates 32 (C - NDA) + 8 wave .. + 7
+  // (ga, gb: the wave's first piece of either operand; dst: LDS byte address of the wave's first piece in the image)
   template <int C>
-  static __device__ __forceinline__ void load_chunk(Data &g, const double *__restrict__ qa, const double *__restrict__ qb,
-                                                    int64_t lda) {
-    if constexpr (C < NCA)
-      g.c[C] = *reinterpret_cast<const d2_t *>(qa + (int64_t)(32 * C) * lda);
-    else
-      g.c[C] = *reinterpret_cast<const d2_t *>(qb + (int64_t)(32 * (C - NCA)) * lda);
-  }
-  template <int C>
-  static __device__ __forceinline__ void store_chunk(const Data &g, double *__restrict__ w) {
-    constexpr int o = C < NCA ? 32 * C * LD : A_DBLT + 32 * (C - NCA) * LD;
-    w[o] = g.c[C][0];
-    w[o + 1] = g.c[C][1];
+  static __device__ __forceinline__ void dma_piece(const char *__restrict__ ga, const char *__restrict__ gb, int64_t step,
+                                                   unsigned src, unsigned dst) {
+    const char *g = C < NDA ? ga + C * step : gb + (C - NDA) * step;
+    const unsigned m0 = dst + C * post_ring::WAVES * post_ring::PIECE_BYTES;
+    // M0 is written in the statement that uses it (s_nop 0: SALU write of M0 -> LDS-DMA); nothing else in the kernel uses M0
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0), "v"(src), "s"(g) : "memory");
   }
 
-  // one k-step: NJ * (NR - FIRST) MFMAs from set `use`, NSIDE side operations spread between them
-  template <int FIRST, bool ZERO, int NSIDE, class Side>
+  // one k-step: NJ * (NR - FIRST) MFMAs from set `use`, NSIDE side operations spread between all but the last TAIL of them
+  template <int FIRST, bool ZERO, int NSIDE, int TAIL, class Side>
   static __device__ __forceinline__ void kstep(const Set &use, Side &&side) {
-    constexpr int NI = NR - FIRST, NM = NJ * NI;
-    constexpr int KMAX = (NSIDE + NM - 1) / NM + 1;  // side operations behind one MFMA: [m NSIDE / NM, (m + 1) NSIDE / NM)
+    constexpr int NI = NR - FIRST, NM = NJ * NI, NMS = NM > 2 * TAIL ? NM - TAIL : NM;
+    constexpr int KMAX = (NSIDE + NMS - 1) / NMS + 1;  // side operations behind one MFMA: [m NSIDE / NMS, (m + 1) NSIDE / NMS)
     static_for<NM>([&](auto m_) {
       constexpr int m = decltype(m_)::value, i = FIRST + m / NJ, j = m % NJ;
       mfma_tile<NJ, i, j, ZERO>(use.a[i], use.b[j]);
-      static_for<KMAX>([&](auto k_) {
-        constexpr int sidx = m * NSIDE / NM + decltype(k_)::value;
-        if constexpr (sidx < (m + 1) * NSIDE / NM) side(std::integral_constant<int, sidx>{});
-      });
+      if constexpr (m < NMS)
+        static_for<KMAX>([&](auto k_) {
+          constexpr int sidx = m * NSIDE / NMS + decltype(k_)::value;
+          if constexpr (sidx < (m + 1) * NSIDE / NMS) side(std::integral_constant<int, sidx>{});
+        });
     });
   }
+  // the side slots of a k-step that carries NP fragment reads and H DMA pieces: the pieces sit evenly between the reads
+  static constexpr int H = ND / 3, NS = NP + H;
+  static constexpr int dma_before(int x) {  // DMA slots among the slots below x
+    int n = 0;
+    for (int d = 0; d < H; ++d) n += (d + 1) * NS / (H + 1) < x;
+    return n;
+  }
+  static constexpr bool is_dma(int x) { return dma_before(x + 1) > dma_before(x); }
 
-  // FIRST / NEXT_FIRST: first strip with anything to do in this stage / in the next one
-  template <int FIRST, int NEXT_FIRST, bool ZERO>
-  static __device__ __forceinline__ void stage(Set &s0, Set &s1, Data &g, double *__restrict__ cur, double *__restrict__ nxt,
-                                               int fa, int fb, int wofs, const double *__restrict__ pa,
-                                               const double *__restrict__ pb, int64_t lda, Cursor &ld) {
-    constexpr int H = NC / 2;
-    const double *qa = pa + ((int64_t)ld.t * BMT) * lda + ld.kb * BK, *qb = pb + ld.kb * BK;
+  // FIRST / NEXT_FIRST: first strip with anything to do in this stage / in the next one.  POS: ring position of this
+  // stage's image; the next one's is POS + 1, the DMA pieces of the one after go to POS + 2
+  template <int FIRST, int NEXT_FIRST, bool ZERO, int POS>
+  static __device__ __forceinline__ void stage(Set &s0, Set &s1, const Lane &ln,
+                                               const char *__restrict__ pa, const char *__restrict__ pb, int64_t lda, Cursor &ld) {
+    constexpr int CUR = POS % NBUF, NXT = (POS + 1) % NBUF, DST = (POS + 2) % NBUF;
+    const int64_t step = 32 * lda * 8;
+    const char *ga = pa + (((int64_t)ld.t * BMT) * lda + ld.kb * BK) * 8, *gb = pb + (int64_t)(ld.kb * BK) * 8;
     ld.advance();
-    kstep<FIRST, ZERO, NP + H>(s0, [&](auto s_) {
-      constexpr int x = decltype(s_)::value;
-      if constexpr (x < NP) {
-        if constexpr (x < NJ || x - NJ >= FIRST) read_one<x, 1>(s1, cur + fa, cur + fb);
-      } else {
-        store_chunk<x - NP>(g, nxt + wofs);
-      }
-    });
-    kstep<FIRST, false, NP + NC - H>(s1, [&](auto s_) {
-      constexpr int x = decltype(s_)::value;
-      if constexpr (x < NP) {
-        if constexpr (x < NJ || x - NJ >= FIRST) read_one<x, 2>(s0, cur + fa, cur + fb);
-      } else {
-        store_chunk<H + x - NP>(g, nxt + wofs);
-      }
-    });
-    kstep<FIRST, false, NP + NC>(s0, [&](auto s_) {
-      constexpr int x = decltype(s_)::value;
-      if constexpr (x < NP) {
-        if constexpr (x < NJ || x - NJ >= FIRST) read_one<x, 3>(s1, cur + fa, cur + fb);
-      } else {
-        load_chunk<x - NP>(g, qa, qb, lda);
-      }
-    });
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's part of the next image is in LDS (the loads stay in flight)
+    auto sides = [&](auto ks_, Set &into, auto x_) {  // k-step ks: read the set of k-step ks + 1, pieces H ks .. H ks + H - 1
+      constexpr int ks = decltype(ks_)::value, x = decltype(x_)::value, r = x - dma_before(x);
+      if constexpr (is_dma(x))
+        dma_piece<H * ks + dma_before(x)>(ga, gb, step, ln.src, ln.dst[DST]);
+      else if constexpr (r < NJ || r - NJ >= FIRST)
+        read_one<r, ks + 1, CUR>(into, ln);
+    };
+    kstep<FIRST, ZERO, NS, 0>(s0, [&](auto x_) { sides(std::integral_constant<int, 0>{}, s1, x_); });
+    kstep<FIRST, false, NS, 0>(s1, [&](auto x_) { sides(std::integral_constant<int, 1>{}, s0, x_); });
+    // the last MFMAs in front of the barrier carry nothing: the reads are back when lgkmcnt(0) asks
+    kstep<FIRST, false, NS, 3>(s0, [&](auto x_) { sides(std::integral_constant<int, 2>{}, s1, x_); });
+    // this wave's pieces of the next image have landed (the twelve just issued stay in flight); its reads of this image are back
+    asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    kstep<FIRST, false, NP>(s1, [&](auto s_) {
+    kstep<FIRST, false, NP, 0>(s1, [&](auto s_) {
       constexpr int x = decltype(s_)::value;
-      if constexpr (x < NJ || x - NJ >= NEXT_FIRST) read_one<x, 0>(s0, nxt + fa, nxt + fb);
+      if constexpr (x < NJ || x - NJ >= NEXT_FIRST) read_one<x, 0, NXT>(s0, ln);
     });
   }
 };
@@ -455,7 +494,7 @@ __global__ void __launch_bounds__(256)
                     double base, double sgn, double var_add, int clamp, double var_min, double *__restrict__ var,
                     PostBatch bat) {
   using T = Tall<NJ, NR>;
-  constexpr int BMT = T::BMT, BN = T::BN, NC = T::NC, NP = T::NP;
+  constexpr int BMT = T::BMT, BN = T::BN, NP = T::NP;
   extern __shared__ __align__(16) double sm[];
   if (bat.base) {
     const int64_t y = blockIdx.y;
@@ -471,50 +510,66 @@ __global__ void __launch_bounds__(256)
   __builtin_amdgcn_s_waitcnt(0xC07F);
 #endif
   const int64_t lda = Npad;
-  const int r0 = threadIdx.x >> 3, kc = threadIdx.x & 7;
-  const double *pa = Linv + (int64_t)r0 * lda + 2 * kc;
-  const double *pb = ks + ((int64_t)blockIdx.x * BN + r0) * lda + 2 * kc;
-  const int wofs = r0 * LD + 2 * kc;
-  const int fa = (lane & 15) * LD + (lane >> 4);
-  const int fb = T::A_DBLT + (wave * 16 * NJ + (lane & 15)) * LD + (lane >> 4);
+  // DMA: the wave's first piece of either operand (rows 8 wave .. + 7); a lane's source offset is the same for all its pieces
+  const char *pa = reinterpret_cast<const char *>(Linv + (int64_t)(post_ring::PIECE_ROWS * wave) * lda);
+  const char *pb = reinterpret_cast<const char *>(ks + ((int64_t)blockIdx.x * BN + post_ring::PIECE_ROWS * wave) * lda);
+  typename T::Lane ln;
+  {
+    const post_ring::Chunk c = post_ring::dma_src(wave, lane);
+    ln.src = (unsigned)(((c.row - post_ring::PIECE_ROWS * wave) * Npad + 2 * c.chunk) * 8);
+  }
+  // fragments: lane -> (row or candidate lane & 15 of a strip, k = 4 s + (lane >> 4)); the swizzle does not depend on the strip
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void *)sm;
+#pragma unroll
+  for (int b = 0; b < T::NBUF; ++b) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      ln.fa[b][s] = lds0 + b * T::STAGE_BYTES + post_ring::frag_byte(lane & 15, 4 * s + (lane >> 4));
+      ln.fb[b][s] = ln.fa[b][s] + (BMT + wave * 16 * NJ) * post_ring::ROW_BYTES;
+      asm volatile("" : "+v"(ln.fa[b][s]), "+v"(ln.fb[b][s]));  // registers, not sums formed again at every read
+    }
+    ln.dst[b] = lds0 + b * T::STAGE_BYTES + wave * post_ring::PIECE_BYTES;
+  }
 
   const int ntiles = Npad / BMT;
   typename T::Cursor ld{0, 0, ntiles};
-  typename T::Data g;
   typename T::Set s0, s1;
-  double *const b0 = sm, *const b1 = sm + T::STAGE_DBL;
-  static_for<NC>([&](auto c_) { T::template load_chunk<decltype(c_)::value>(g, pa, pb, lda); });  // stage 0
-  ld.advance();
-  static_for<NC>([&](auto c_) { T::template store_chunk<decltype(c_)::value>(g, b0 + wofs); });
   {
-    const double *qa = pa + ((int64_t)ld.t * BMT) * lda + ld.kb * BK, *qb = pb + ld.kb * BK;
-    static_for<NC>([&](auto c_) { T::template load_chunk<decltype(c_)::value>(g, qa, qb, lda); });  // stage 1
+    const int64_t step = 32 * lda * 8;
+    static_for<T::ND>([&](auto c_) { T::template dma_piece<decltype(c_)::value>(pa, pb, step, ln.src, ln.dst[0]); });  // stage 0
+    ld.advance();
+    const char *ga = pa + (((int64_t)ld.t * BMT) * lda + ld.kb * BK) * 8, *gb = pb + (int64_t)(ld.kb * BK) * 8;
+    static_for<T::ND>([&](auto c_) { T::template dma_piece<decltype(c_)::value>(ga, gb, step, ln.src, ln.dst[1]); });  // stage 1
     ld.advance();
   }
-  __builtin_amdgcn_s_waitcnt(0xC07F);
+  asm volatile("s_waitcnt vmcnt(12)" ::: "memory");  // stage 0 has landed
   __builtin_amdgcn_s_barrier();
-  static_for<NP>([&](auto p_) { T::template read_one<decltype(p_)::value, 0>(s0, b0 + fa, b0 + fb); });
+  static_for<NP>([&](auto p_) { T::template read_one<decltype(p_)::value, 0, 0>(s0, ln); });
 
   double colss[2][NJ] = {};
-#define B7_STAGE(F, NF, Z, CUR, NXT) T::template stage<F, NF, Z>(s0, s1, g, CUR, NXT, fa, fb, wofs, pa, pb, lda, ld)
+#define B7_STAGE(F, NF, Z, POS) T::template stage<F, NF, Z, POS>(s0, s1, ln, pa, pb, lda, ld)
   for (int t = 0; t < ntiles; ++t) {
-    B7_STAGE(0, 0, true, b0, b1);
+    // a tile starts at ring position 0: the zeroing stage, 16 t - 1 more stages away from the diagonal block three at a
+    // time, the block's 16 stages from position 0 again
+    B7_STAGE(0, 0, true, 0);
     if (t > 0) {
-      for (int p = 0; p < (NR / 2) * t - 1; ++p) {
-        B7_STAGE(0, 0, false, b1, b0);
-        B7_STAGE(0, 0, false, b0, b1);
+      const int n = NR * t - 1;
+      for (int p = 0; p < n / 3; ++p) {
+        B7_STAGE(0, 0, false, 1);
+        B7_STAGE(0, 0, false, 2);
+        B7_STAGE(0, 0, false, 0);
       }
-      B7_STAGE(0, 0, false, b1, b0);
-      B7_STAGE(0, 1, false, b0, b1);  // diagonal stage 0
+      if (n % 3 >= 1) B7_STAGE(0, 0, false, 1);
+      if (n % 3 == 2) B7_STAGE(0, 0, false, 2);
+      ln.rotate((n + 1) % 3);
+      B7_STAGE(0, 1, false, 0);  // diagonal stage 0
     }
     // diagonal stages 1 .. NR-1 (for t == 0 the zeroing stage above was diagonal stage 0; it read the next set in full)
     static_for<NR - 1>([&](auto q_) {
       constexpr int Q = decltype(q_)::value + 1;
-      if constexpr (Q % 2 == 1)
-        B7_STAGE(Q, (Q + 1) % NR, false, b1, b0);
-      else
-        B7_STAGE(Q, (Q + 1) % NR, false, b0, b1);
+      B7_STAGE(Q, (Q + 1) % NR, false, Q % 3);
     });
+    ln.rotate(NR % 3);  // the next tile's position 0
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
     // the tile is NR/8 128-row tiles of the fold, each as (rows 0..63, rows 64..127), in ascending order
     static_for<(NR / 4) * NJ>([&](auto qj_) {
@@ -530,6 +585,8 @@ __global__ void __launch_bounds__(256)
     });
   }
 #undef B7_STAGE
+  // the pieces requested past the last stage (the cursor clamps there) land before the workgroup gives up its LDS
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
