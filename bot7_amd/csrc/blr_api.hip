@@ -172,8 +172,11 @@ static int blr_enqueue_fit(b7_ctx *c, const b7_mlp *net, const double *X0, const
   return B7_OK;
 }
 
-// features of the resident grid (recomputed, as models/dngo.lua:155-171 does on every predict), mean, variance, score
-static int blr_enqueue_score(b7_ctx *c, const b7_mlp *net, int z, const b7_score_spec *spec) {
+// features of the resident grid (recomputed, as models/dngo.lua:155-171 does on every predict), mean, variance, score.
+// fused_mean: the basis kernel forms the mean on its way (four fma chains per row); otherwise launch_gemv_rows does, in
+// b7_blr_predict's order of summation -- the failed-pivot redo asks for that, so that it IS b7_blr_fit_x + b7_blr_basis +
+// b7_blr_predict + the score, bit for bit (tests/test_gpu_blr.py holds it to that).
+static int blr_enqueue_score(b7_ctx *c, const b7_mlp *net, int z, const b7_score_spec *spec, bool fused_mean = true) {
   const int zpad = npad_of(c, z);
   B7_TRY(feat_alloc(c, c->M, z));
   B7_TRY(b7_ensure(c, c->mu, sizeof(double) * (size_t)c->M));
@@ -181,8 +184,8 @@ static int blr_enqueue_score(b7_ctx *c, const b7_mlp *net, int z, const b7_score
   B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
   bool mean_done = false;
   B7_TRY(launch_mlp_forward_mean(c, (const double *)c->grid[c->grid_cur].p, c->M, c->d, (const double *)c->netbuf.p, net->dims,
-                                 net->n_layers, net->activation, (double *)c->feat.p, zpad, (const double *)c->alpha.p, c->mean,
-                                 (double *)c->mu.p, &mean_done));
+                                 net->n_layers, net->activation, (double *)c->feat.p, zpad,
+                                 fused_mean ? (const double *)c->alpha.p : nullptr, c->mean, (double *)c->mu.p, &mean_done));
   B7_TRY(blr_predict_enqueue(c, c->M, mean_done));
   // bots/bayesopt.lua:65-66: the score of the one model, no accumulation over samples -> written, not added (which makes the
   // accumulator valid: score.hip, acc_mode)
@@ -396,7 +399,7 @@ int b7_blr_eval_nominate(b7_ctx *c, const b7_mlp *net, const double *X0, const d
       [&]() {  // the jitter schedule of utils/math.lua:159-218, through the synchronous fit
         B7_TRY(b7_blr_fit_x(c, net, X0, Y0, N, alpha_prec, beta, mean, nullptr));
         if (jitter_used) *jitter_used = -2.0;  // "a jitter was needed" (its size is the fit's business; see b7_blr_fit_x)
-        return blr_enqueue_score(c, net, z, spec);
+        return blr_enqueue_score(c, net, z, spec, false);
       },
       best_val, best_idx1);
 }

@@ -491,10 +491,14 @@ __global__ void __launch_bounds__(256)
 // The same for 64-column rows (the 64-padded features of a DNGO head) with ONE pass over A for all S heads: a THREAD takes a
 // row (64 doubles in registers, 512 contiguous bytes) and, per head, walks the binary tree the wave butterfly of
 // gemv_rows_kernel adds its 64 products in (level o adds element l and l + o) -- the same sums, no second read of the
-// features (ten heads over 65536 x 64 features: 335 MB -> 34 MB of reads).
+// features (ten heads over 65536 x 64 features: 335 MB -> 34 MB of reads).  Contraction is off in the body: left on, the first
+// level of the tree became fma(v[l + 32], x[l + 32], p[l]) -- 32 of the 64 products never rounded, which the butterfly cannot do
+// (its products sit in other lanes) -- and the S means differed from b7_blr_predict's in the last bits
+// (tests/test_gpu_blr.py::test_e_marginalised_heads).
 __global__ void __launch_bounds__(256)
     gemv_rows64_multi_kernel(const double *__restrict__ A, const double *__restrict__ x, int S, const double *__restrict__ base,
                              int64_t Mtotal, double *__restrict__ y, int64_t sy) {
+#pragma clang fp contract(off)
   extern __shared__ double xs[];  // [S][64]
   for (int e = threadIdx.x; e < S * 64; e += blockDim.x) xs[e] = x[e];
   __syncthreads();
