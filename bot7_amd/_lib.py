@@ -26,6 +26,7 @@ SYMBOLS = [
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_eval_nominate_batch", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
     "b7_ts_nominate", "b7_ts_last_paths", "b7_ts_last_draws", "b7_rff_compute",
     "b7_kg_nominate", "b7_kg_trace_enable", "b7_kg_last", "b7_kg_compute",
+    "b7_eval_posterior", "b7_posterior_get", "b7_pareto_front2", "b7_hypervolume2", "b7_ehvi_compute", "b7_ehvi_nominate",
     "b7_refine_default_opts", "b7_eval_nominate_refine", "b7_refine_last", "b7_refine_shape", "b7_refine_trace_enable", "b7_refine_trace", "b7_gp_grad_at", "b7_score_grad_compute",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
@@ -38,6 +39,7 @@ SYMBOLS = [
 
 
 KG_MAX_POINTS = 16  # B7_KG_MAX_POINTS
+EHVI_PMAX, EHVI_SMAX, EHVI_SREG = 256, 32, 10  # B7_EHVI_PMAX (front points), B7_EHVI_SMAX (hyper samples per objective), B7_EHVI_SREG (of them in registers)
 
 
 class Bot7HipError(RuntimeError):
@@ -190,6 +192,12 @@ def load(which=None):
         "b7_kg_trace_enable": (i32, [vp, i32]),
         "b7_kg_last": (i32, [vp, vp, vp, vp, vp, vp]),
         "b7_kg_compute": (i32, [vp, C.c_int64, i32, vp, vp, vp]),
+        "b7_eval_posterior": (i32, [vp, i32, C.POINTER(Hyp), vp, vp]),
+        "b7_posterior_get": (i32, [vp, i32, vp, vp]),
+        "b7_pareto_front2": (i32, [vp, i64, vp, vp, vp, C.POINTER(i32)]),
+        "b7_hypervolume2": (i32, [vp, i32, vp, C.POINTER(dbl)]),
+        "b7_ehvi_compute": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, i64, vp]),
+        "b7_ehvi_nominate": (i32, [vp, vp, vp, i32, vp, C.POINTER(dbl), C.POINTER(i64)]),
         "b7_refine_default_opts": (i32, [C.POINTER(RefineOpts)]),
         "b7_eval_nominate_refine": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), C.POINTER(RefineOpts), C.POINTER(dbl),
                                           C.POINTER(i64), vp, C.POINTER(dbl), C.POINTER(i64), vp, vp]),
@@ -1135,6 +1143,53 @@ class Context(object):
         self._ck(self._L.b7_kg_compute(self._h, alpha.shape[0], alpha.shape[1], _ptr(alpha), _ptr(b), _ptr(out)))
         return out
 
+    # ---- two objectives: the kept posterior and the expected hypervolume improvement (csrc/ehvi.hip)
+    def eval_posterior(self, hyps, want_report=False):
+        """The posterior half of eval_nominate, kept (b7_eval_posterior): mean and variance of every hyper sample over the resident
+        grid stay on the device for ehvi_nominate / posterior_get; no score, no arg-max, no accumulator afterwards.  A change of
+        the grid or the data forgets it.  Returns None, or the report dict(jitter, info)."""
+        S = len(hyps)
+        arr, keep = self._pack_hyps(hyps, getattr(self, "_data_d", -1))
+        jit = np.zeros(max(S, 1), dtype=np.float64) if want_report else None
+        info = np.zeros(max(S, 1), dtype=np.int32) if want_report else None
+        self._ck(self._L.b7_eval_posterior(self._h, S, arr, _ptr(jit), _ptr(info)))
+        self.fit_token += 1
+        return {"jitter": jit[:S], "info": info[:S]} if want_report else None
+
+    def posterior_get(self, s):
+        """(mean, var), one entry per grid row, of sample s (0-based) of the kept posterior (b7_posterior_get)."""
+        M, _ = self.grid_shape()
+        mean, var = np.empty(M, dtype=np.float64), np.empty(M, dtype=np.float64)
+        self._ck(self._L.b7_posterior_get(self._h, int(s), _ptr(mean), _ptr(var)))
+        return mean, var
+
+    def ehvi_compute(self, mu1, var1, mu2, var2, front, ref):
+        """The marginal expected hypervolume improvement on host arrays by the nomination's own kernel (b7_ehvi_compute): mu1 / var1
+        S1 x M of objective 1, mu2 / var2 S2 x M of objective 2, front P x 2 canonical (pareto_front2), ref (r1, r2) -> M scores."""
+        mu1, var1, mu2, var2 = (np.atleast_2d(_f64(a)) for a in (mu1, var1, mu2, var2))
+        front, ref = _f64(front).reshape(-1, 2), _f64(ref).ravel()
+        M = mu1.shape[1]
+        if var1.shape != mu1.shape or var2.shape != mu2.shape or mu2.shape[1] != M or ref.size != 2:
+            raise Bot7HipError(-1, "ehvi_compute: mu1 / var1 S1 x M, mu2 / var2 S2 x M, front P x 2, ref 2")
+        out = np.empty(M, dtype=np.float64)
+        self._ck(self._L.b7_ehvi_compute(self._h, _ptr(mu1), _ptr(var1), mu1.shape[0], _ptr(mu2), _ptr(var2), mu2.shape[0],
+                                         _ptr(front), front.shape[0], _ptr(ref), M, _ptr(out)))
+        return out
+
+    def ehvi_nominate(self, other, front, ref):
+        """The two-objective nomination (b7_ehvi_nominate): this context holds objective 1's kept posterior (eval_posterior), `other`
+        objective 2's (other may be this context).  Both must hold the same grid rows: the caller's contract, only the row count is
+        checked.  The marginal score stays in this context's accumulator (score_finish(1, download=True) reads it).  Returns (value,
+        1-based index); neither grid is modified."""
+        if not isinstance(other, Context) or other._L is not self._L:
+            raise Bot7HipError(-1, "ehvi_nominate: other must be a Context of the same library")
+        front, ref = _f64(front).reshape(-1, 2), _f64(ref).ravel()
+        if ref.size != 2:
+            raise Bot7HipError(-1, "ehvi_nominate: ref has two entries")
+        val, idx = C.c_double(), C.c_int64()
+        self._ck(self._L.b7_ehvi_nominate(self._h, other._h, _ptr(front), front.shape[0], _ptr(ref), C.byref(val), C.byref(idx)))
+        return val.value, idx.value
+
     def rff_compute(self, X, omega, phase, W):
         """cos(X omega' + phase) W on host arrays (b7_rff_compute): X M1 x d, omega F x d, phase F, W F x q -> M1 x q."""
         X, omega, phase, W = _f64(X), _f64(omega), _f64(phase).ravel(), _f64(W)
@@ -1380,6 +1435,36 @@ def comm_pick_winner(pairs):
     if rc != B7_OK:
         raise Bot7HipError(rc, "every shard is empty")
     return v.value, i.value
+
+
+def pareto_front2(Y, ref):
+    """The canonical front of n rows of two responses (minimised) under the reference point ref = (r1, r2): rows with a non-finite
+    entry or not strictly inside the box dropped, dominated rows dropped, of equal rows the lowest kept, sorted with the first
+    objective ascending.  Returns (front P x 2, rows P: each point's 1-based source row).  Host-only (b7_pareto_front2); more than
+    EHVI_PMAX points raise."""
+    Y, ref = _f64(Y).reshape(-1, 2), _f64(ref).ravel()
+    if ref.size != 2:
+        raise Bot7HipError(-1, "pareto_front2: ref has two entries")
+    cap = max(1, min(Y.shape[0], EHVI_PMAX))
+    front, rows, P = np.empty((cap, 2), dtype=np.float64), np.zeros(cap, dtype=np.int64), C.c_int()
+    rc = load().b7_pareto_front2(_ptr(Y), Y.shape[0], _ptr(ref), _ptr(front), _ptr(rows), C.byref(P))
+    if rc != B7_OK:
+        raise Bot7HipError(rc, "pareto_front2: a front of %d points (at most %d are built)" % (P.value, EHVI_PMAX) if P.value > EHVI_PMAX
+                           else "pareto_front2: the reference point must be finite")
+    return front[:P.value].copy(), rows[:P.value].copy()
+
+
+def hypervolume2(front, ref):
+    """The area a canonical front (pareto_front2) dominates inside the reference box.  Host-only (b7_hypervolume2)."""
+    front, ref = _f64(front).reshape(-1, 2), _f64(ref).ravel()
+    if ref.size != 2:
+        raise Bot7HipError(-1, "hypervolume2: ref has two entries")
+    hv = C.c_double()
+    rc = load().b7_hypervolume2(_ptr(front), front.shape[0], _ptr(ref), C.byref(hv))
+    if rc != B7_OK:
+        raise Bot7HipError(rc, "hypervolume2: the front is not canonical (strictly inside a finite reference box, the first objective "
+                               "strictly ascending, the second strictly descending)")
+    return hv.value
 
 
 def sobol_direction_numbers(dims):

@@ -275,6 +275,15 @@ struct b7_ctx {
   int kg_S = 0, kg_n = 0;  // the shapes of what the last successful call left
   int64_t kg_M = 0;
   size_t kg_al_off = 0;    // where that call's alpha [S][16] sits in kgvec (doubles); the rows of A follow it
+  // ---- b7_eval_posterior / b7_ehvi_* (ehvi.hip): the kept posterior of the last b7_eval_posterior, forgotten with the accumulator
+  // whenever the grid changes and whenever the data does (post_forget); the front's staging; b7_ehvi_compute's staging, apart
+  DevBuf post;       // mu [S][M] | var [S][M]
+  bool post_valid = false;
+  int post_S = 0;
+  int64_t post_M = 0;
+  DevBuf ehvi_front; // a_1 .. a_P, r1 | r2, b_1 .. b_P: 2 (P + 1) doubles as the kernel reads them
+  DevBuf ehvi_user;
+  hipEvent_t ev_ehvi[2] = {nullptr, nullptr};  // b7_ehvi_nominate: the other context's stream -> this one, and back (created on first use)
   DevBuf feat;   // DNGO basis features of the resident grid: Mfeat x Npad (zero-padded columns)
   size_t feat_zeroed_bytes = 0;  // how much of `feat` was zeroed when it was laid out for feat_z columns
   int feat_z = -1;
@@ -529,6 +538,8 @@ int acc_write_zeros(b7_ctx *c);
 void acc_forget(b7_ctx *c);
 int acc_materialize(b7_ctx *c);
 void feas_forget(b7_ctx *c);  // the grid changed: there is no feasibility column until the next b7_feas_reset
+// the grid or the data changed: there is no kept posterior until the next b7_eval_posterior (ehvi.hip)
+static inline void post_forget(b7_ctx *c) { c->post_valid = false; }
 int feas_write_zeros(b7_ctx *c);                      // L := 0.0 over the resident grid (allocates on demand)
 int launch_feas_add(b7_ctx *c, const double *src);    // L[j] += src[j], src: c->M doubles on the device
 int launch_feas_best(b7_ctx *c, double *best_val, int64_t *best_idx1);  // score:max(1) of L alone (waits)

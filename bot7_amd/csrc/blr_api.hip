@@ -63,6 +63,7 @@ static int blr_head_setup(b7_ctx *c, int z, int nk, double mean, double noise, b
   }
   B7_TRY(b7_ensure(c, c->info, B7_INFO_BYTES));
   c->have_data = false, c->fitted = false, c->predicted = false;
+  post_forget(c);
   c->N = z, c->Npad = (int)np, c->ycols = 1, c->yld = 1, c->model_kind = 1;
   c->mean = mean, c->noise = noise, c->amp = 0.0;
   return B7_OK;
@@ -313,6 +314,7 @@ int b7_blr_features(b7_ctx *c, const double *Z1, int64_t M, int z) {
     c->d = 0;
     acc_forget(c);
     feas_forget(c);
+    post_forget(c);
   }
   return B7_OK;
 }

@@ -321,6 +321,7 @@ int b7_gp_set_data(b7_ctx *c, const double *X, const double *Y, int N, int d, in
   c->fitted = false;
   c->have_data = false;
   c->predicted = false;  // the score accumulator survives: marginalisation adds across fits (bots/bayesopt.lua:73-78)
+  post_forget(c);        // a kept posterior (b7_eval_posterior) is of the data it was made from
   c->N = N;
   c->Npad = npad_of(c, N);
   c->dfit = d;
@@ -538,6 +539,7 @@ int b7_chol(b7_ctx *c, const double *src, int n, double *res, double *jitter_use
   c->fitted = false;
   c->have_data = false;
   c->predicted = false;
+  post_forget(c);
   c->N = n;
   c->Npad = npad_of(c, n);
   const size_t np = (size_t)c->Npad, nn = np * np * sizeof(double);
@@ -655,6 +657,7 @@ int b7_gp_append(b7_ctx *c, const double *x_new, const double *y_new) {
   B7_HIP(c, hipSetDevice(c->device));
   const int N = c->N, np = c->Npad, d = c->dfit, yc = c->ycols;
   c->predicted = false;
+  post_forget(c);
   // the new observation joins the observation set (raw row, scaled row, half norm, residual row)
   B7_HIP(c, hipMemcpyAsync((double *)c->xobs.p + (size_t)N * d, x_new, sizeof(double) * d, hipMemcpyHostToDevice,
                            c->stream));

@@ -13,6 +13,7 @@ static void invalidate_predictions(b7_ctx *c) {
   c->predicted = false;
   acc_forget(c);
   feas_forget(c);
+  post_forget(c);
   c->Mfeat = 0;  // DNGO features belong to the grid they were computed from
   c->win_valid = false;  // so does the winner's row of the last exchange
 }

@@ -64,4 +64,12 @@ def gardner1(X):
     return np.stack([y, c], axis=1)
 
 
-registry = {"braninhoo": braninhoo, "hartmann6": hartmann6, "ackley": ackley, "rastrigin": rastrigin, "gardner1": gardner1}
+def two_spheres(X):
+    """A TWO-OBJECTIVE toy (no counterpart in benchmarks/), any dims: rows [y1, y2] = (|x - a|^2, |x - b|^2) with a = 0.25 * 1 and
+    b = 0.75 * 1, both minimised.  Its Pareto set is the segment between a and b (config.bot.objectives = {"ref": ..., "model": ...})."""
+    X = _rows(X)
+    return np.stack([((X - 0.25) ** 2).sum(1), ((X - 0.75) ** 2).sum(1)], axis=1)
+
+
+registry = {"braninhoo": braninhoo, "hartmann6": hartmann6, "ackley": ackley, "rastrigin": rastrigin, "gardner1": gardner1,
+            "two_spheres": two_spheres}

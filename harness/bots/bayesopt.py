@@ -32,7 +32,17 @@ constraint model samples its hypers, stages data and grid on its context and lea
 samples, in that context's accumulator (eval_nominate(score="logpi", fmin=[t_k], tradeoff=0)); the objective's context sums them
 into its feasibility column (feas_reset, feas_add_acc) and nominates with the weight (eval_nominate_feasible), fmin being the best
 response among the rows that satisfy every constraint -- or, while no row does, by feasibility alone (feas_nominate).  The stolen
-row leaves every context's resident grid.  What is not built is refused by name (constraint_refusal)."""
+row leaves every context's resident grid.  What is not built is refused by name (constraint_refusal).
+
+config.bot.objectives (ours; None = the reference's loop, untouched) is {"ref": [r1, r2] | None, "model": {...}}: TWO-OBJECTIVE
+nomination by the exact expected hypervolume improvement (Emmerich, Yang & Deutz 2016; config.score.type =
+'expected_hypervolume_improvement', a policy like the knowledge gradient).  The objective returns a row [y1, y2], both minimised;
+the bot's own model sees column 0, a second gp_regressor -- with a context and sampler state of its own -- column 1.  Per
+model-based trial both models sample their hypers, both contexts keep their posterior (eval_posterior), the front of the
+observations comes from pareto_front2 and the objective's context nominates (ehvi_nominate); the stolen row leaves both grids.
+ref = None recomputes the reference point every trial as the per-column maximum of the observations plus 10 % of the column's
+range (default_ref).  update_best / progress_report report the hypervolume and the front's size.  What is not built is refused
+by name (objectives_refusal)."""
 import numpy as np
 
 from .abstract import abstract
@@ -115,6 +125,55 @@ def kg_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
     return None
 
 
+EHVI = "expected_hypervolume_improvement"
+
+
+def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
+    """Why this configuration cannot nominate for two objectives (what b7_ehvi_nominate does not do, by name), or None."""
+    kind = config["score"]["type"]
+    obj = config["bot"].get("objectives")
+    if obj is None:
+        if kind == EHVI:
+            return "%s without config.bot.objectives: the score needs two objectives, each with a model of its own" % EHVI
+        return None
+    if int(config["bot"].get("batch", 1)) > 1:
+        return "config.bot.objectives with config.bot.batch > 1: two-objective batches are not built"
+    if config["bot"].get("refine"):
+        return "config.bot.objectives with config.bot.refine: refinement of a two-objective nominee is not built"
+    if config["bot"].get("constraints"):
+        return "config.bot.objectives with config.bot.constraints: constraints combined with objectives are not built"
+    if sharded:
+        return "config.bot.objectives over sharded candidates: two objectives over a sharded grid are not built"
+    if model_class == "bot7.models.dngo":
+        return "config.bot.objectives with the dngo model: the Bayesian-linear head keeps no posterior for a second objective"
+    if kind != EHVI:
+        return "config.bot.objectives with %s: only %s is built" % (kind, EHVI)
+    if (obj.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
+        return "config.bot.objectives with the %s model: the second objective is modelled by a gp_regressor" % obj["model"]["type"]
+    return None
+
+
+def split_objectives(responses):
+    """The objective's rows [y1, y2] -> (Y1 N x 1, Y2 N x 1)."""
+    R = np.asarray(responses, dtype=np.float64)
+    R = R.reshape(-1, 2) if R.ndim < 2 else R
+    if R.shape[1] != 2:
+        raise ValueError("config.bot.objectives: the objective must return rows of 2 columns [y1, y2], got %d" % R.shape[1])
+    return np.ascontiguousarray(R[:, :1]), np.ascontiguousarray(R[:, 1:2])
+
+
+def default_ref(responses):
+    """The reference point when config.bot.objectives.ref is None: per column the maximum of the observations plus 10 % of the
+    column's range (the common nadir heuristic; a column without a range takes 10 % of max(|maximum|, 1) instead).  Rows with a NaN
+    take no part."""
+    Y1, Y2 = split_objectives(responses)
+    R = np.concatenate([Y1, Y2], axis=1)
+    R = R[~np.isnan(R).any(axis=1)]
+    hi, lo = R.max(axis=0), R.min(axis=0)
+    span = np.where(hi > lo, hi - lo, np.maximum(np.abs(hi), 1.0))
+    return hi + 0.1 * span
+
+
 def split_columns(responses, C):
     """The objective's rows [y, c_1 .. c_C] -> (Y N x 1, [c_k N x 1 for each constraint])."""
     R = np.asarray(responses, dtype=np.float64)
@@ -154,6 +213,7 @@ class bayesopt(abstract):
         self._rng = np.random.default_rng(config["bot"]["seed"])
         self.last_scores = None
         self.constraints = None   # per constraint: threshold, model, ctx, grid (the DeviceGrid view of that context); set up on first use
+        self.objective2 = None    # the second objective: model, ctx, grid (the DeviceGrid view of that context); set up on first use
 
     def configure(self, config):
         config = super().configure(config)
@@ -173,6 +233,12 @@ class bayesopt(abstract):
             config["bot"]["constraints"] = [{"threshold": float(c["threshold"]),
                                              "model": self._model_defaults(c.get("model"), config["bot"]["nSamples"])}
                                             for c in config["bot"]["constraints"]]
+        config["bot"].setdefault("objectives", None)    # ours: None, or {"ref": [r1, r2] | None, "model": {...}} (nominate_objectives)
+        if config["bot"]["objectives"] is not None:
+            obj = dict(config["bot"]["objectives"])
+            ref = obj.get("ref")
+            config["bot"]["objectives"] = {"ref": None if ref is None else [float(ref[0]), float(ref[1])],
+                                           "model": self._model_defaults(obj.get("model"), config["bot"]["nSamples"])}
         return config
 
     @staticmethod
@@ -430,8 +496,104 @@ class bayesopt(abstract):
                 con["model"].init(self.observed, Ck)
         return nominee, y
 
+    # ---- two objectives (config.bot.objectives) --------------------------------------------------------------------------------
+    def _objectives(self):
+        """THE predicate: does this bot nominate for two objectives (run_trial, update_best and progress_report all ask here)."""
+        return self.config["bot"].get("objectives") is not None
+
+    def _objectives_refusal(self):
+        return objectives_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
+
+    def _objectives_setup(self):
+        """A GP model with a context (same device) and sampler state of its own for the second objective."""
+        if self.objective2 is None:
+            from bot7_amd import Context
+            ctx = Context(self.model.ctx.device_id)
+            mcfg = self.config["bot"]["objectives"]["model"]
+            self.objective2 = {"ctx": ctx, "grid": None, "model": Models.registry[mcfg["type"]](mcfg, context=ctx)}
+        return self.objective2
+
+    def objectives_ref(self):
+        """The reference point of this trial: config.bot.objectives.ref, or default_ref of the observations so far."""
+        ref = self.config["bot"]["objectives"]["ref"]
+        return default_ref(self.responses) if ref is None else np.asarray(ref, dtype=np.float64)
+
+    def nominate_objectives(self, candidates=None):
+        """The two-objective nominee -> 1-based index into the candidates as they stand.  The objective returns rows [y1, y2], both
+        minimised; the bot's own model sees column 0, the second objective's model -- a GP with a context and sampler state of its
+        own -- column 1.  Per model-based trial both models sample their hypers and both contexts keep their posterior over the
+        same grid rows (eval_posterior); the front of the observations under the reference point comes from pareto_front2, and
+        the objective's context nominates by the exact expected hypervolume improvement (ehvi_nominate), marginalised over both
+        models' samples.  With config.bot.objectives.ref = None the reference point is recomputed EVERY trial as the per-column
+        maximum of the observations plus 10 % of the column's range (default_ref): hypervolumes of different trials are then
+        measured against different boxes.  self.last_objectives keeps what the call used."""
+        from bot7_amd import _lib
+        cand = self.candidates if candidates is None else candidates
+        why = self._objectives_refusal()
+        if why:
+            raise NotImplementedError(why)
+        if self.nTrials <= self.config["bot"]["nInitial"]:        # :90-91 floor(rand*M)+1
+            return int(np.floor(self._rng.random() * cand.shape[0])) + 1
+        o2 = self._objectives_setup()
+        X_obs, model = self.observed, self.model
+        Y1, Y2 = split_objectives(self.responses)
+        ref = self.objectives_ref()
+        front, rows = _lib.pareto_front2(self.responses, ref)     # P = 0 while nothing observed lies inside the box
+        host = np.asarray(cand, dtype=np.float64)
+        hyps1 = self._sample_hyps(model, X_obs, Y1)
+        hyps2 = self._sample_hyps(o2["model"], X_obs, Y2)
+        model.stage(X_obs, Y1, cand)
+        model.ctx.eval_posterior(hyps1)
+        if o2["grid"] is None or o2["grid"].version != o2["ctx"].grid_version or not np.array_equal(np.asarray(o2["grid"]), host):
+            o2["ctx"].grid_upload(host)
+            o2["grid"] = DeviceGrid(host, o2["ctx"], o2["ctx"].grid_version)
+        o2["model"].stage(X_obs, Y2, o2["grid"])
+        o2["ctx"].eval_posterior(hyps2)
+        val, idx = self.score.nominate(model.ctx, o2["ctx"], front, ref)
+        self.last_scores = None
+        self.last_objectives = {"hyps": hyps1, "hyps2": hyps2, "ref": np.array(ref, dtype=np.float64), "front": front, "rows": rows,
+                                "value": val, "index": int(idx)}
+        return int(idx)
+
+    def _run_trial_objectives(self):
+        """bots/abstract.lua:112-152 with the two-objective nominee: the stolen row (:118) leaves the second context's resident
+        grid too, the objective's row [y1, y2] is kept whole (:137-141), and at nInitial each model is initialised on its own
+        column (:147-149)."""
+        why = self._objectives_refusal()
+        if why:
+            raise NotImplementedError(why)
+        self.nTrials += 1
+        idx = self.nominate_objectives()                           # :117
+        self._steal_candidate(idx)                                 # :118
+        o2 = self.objective2
+        if o2 is not None and o2["grid"] is not None and o2["grid"].version == o2["ctx"].grid_version:
+            o2["ctx"].grid_remove(idx)
+            o2["grid"] = DeviceGrid(np.asarray(self.candidates), o2["ctx"], o2["ctx"].grid_version)
+        k = self.pending.shape[0]
+        nominee = self.pending[k - 1]
+        y = np.asarray(self.objective(nominee), dtype=np.float64).reshape(1, -1)   # :124
+        split_objectives(y)                                        # (the shape check)
+        self.responses = y if self.responses is None else np.concatenate([self.responses, y], 0)
+        self.observed, self.pending = T.steal(self.observed, self.pending, [k])  # :143-144
+        if self.model is not None and self.nTrials == self.config["bot"]["nInitial"]:
+            Y1, Y2 = split_objectives(self.responses)
+            self.model.init(self.observed, Y1)                     # :147-149
+            self._objectives_setup()["model"].init(self.observed, Y2)
+        return nominee, y
+
     def update_best(self, x, y):
-        """bots/abstract.lua:171-177; under constraints the best is the best FEASIBLE trial (column 0 among the rows with c_k <= t_k)."""
+        """bots/abstract.lua:171-177; under constraints the best is the best FEASIBLE trial (column 0 among the rows with c_k <= t_k);
+        under two objectives there is no single best: best["front"] / ["rows"] are the front of all trials so far under this
+        trial's reference point, best["hv"] the area it dominates, best["t"] the last trial that entered the front."""
+        if self._objectives():
+            from bot7_amd import _lib
+            ref = self.objectives_ref()
+            front, rows = _lib.pareto_front2(self.responses, ref)
+            self.best["ref"], self.best["front"], self.best["rows"] = ref, front, rows
+            self.best["hv"] = _lib.hypervolume2(front, ref)
+            if self.nTrials in rows:
+                self.best["t"], self.best["x"], self.best["y"] = self.nTrials, x, np.asarray(y, dtype=np.float64).reshape(1, -1)
+            return
         if not self._constrained():
             return super().update_best(x, y)
         y = np.asarray(y, dtype=np.float64).reshape(1, -1)
@@ -440,6 +602,12 @@ class bayesopt(abstract):
             self.best["t"], self.best["x"], self.best["y"] = self.nTrials, x, y
 
     def progress_report(self, t, x, y):
+        if self._objectives():
+            if self.config["bot"]["verbose"] > 0 and t % self.config["bot"]["msg_freq"] == 0:
+                yy = np.ravel(y)
+                print("trial %4d  y = (%.8g, %.8g)  hypervolume = %-14.8g front of %d (last entry: trial %d)" %
+                      (t, float(yy[0]), float(yy[1]), self.best.get("hv", 0.0), len(self.best.get("front", ())), self.best["t"]))
+            return
         if self._constrained() and self.best.get("y") is None:
             if self.config["bot"]["verbose"] > 0 and t % self.config["bot"]["msg_freq"] == 0:
                 print("trial %4d  y = %-14.8g (no feasible trial yet)" % (t, float(np.ravel(y)[0])))
@@ -473,6 +641,8 @@ class bayesopt(abstract):
             why = kg_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
             if why:
                 raise NotImplementedError(why)
+        if self._objectives() or self.config["score"]["type"] == EHVI:
+            return self._run_trial_objectives()
         if self._constrained():
             return self._run_trial_constrained()
         if self.config["bot"]["refine"]:

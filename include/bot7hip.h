@@ -694,6 +694,68 @@ int b7_kg_last(b7_ctx *ctx, int64_t *rows1 /*n*/, double *alpha /*S x n*/, doubl
  * line; a NaN slope there means the row has none (b7_kg_last's convention).  Finite input gives a finite result >= 0. */
 int b7_kg_compute(b7_ctx *ctx, int64_t M1, int L, const double *alpha /*M1 x L*/, const double *b /*M1 x L*/, double *out);
 
+/* TWO OBJECTIVES: the exact expected hypervolume improvement (EHVI).  No counterpart in the reference; the two-objective case of
+ * Emmerich, Yang & Deutz (2016).  Both objectives are MINIMISED.  ref = (r1, r2) is the reference point; a CANONICAL FRONT is P
+ * points (a_k, b_k), k = 1..P, finite, strictly inside the reference box (a_k < r1, b_k < r2), a strictly ascending and b strictly
+ * descending (so mutually non-dominated), stored P x 2 row-major.  With a_0 = -inf, a_P+1 = r1, b_0 = r2 and independent posteriors
+ * y1 ~ N(mu1, var1), y2 ~ N(mu2, var2):
+ *   EHVI = sum_{k=0..P} [Psi(a_k+1; mu1, sigma1) - Psi(a_k; mu1, sigma1)] Psi(b_k; mu2, sigma2),
+ *   Psi(a; mu, sigma) = E[(a - y)+] = (a - mu) Phi(z) + sigma phi(z),  z = (a - mu) / sigma,  Psi(-inf) = 0.
+ * The marginal over S1 hyper samples of objective 1 and S2 of objective 2 (independent chains) factorises strip by strip:
+ *   score = sum_{k=0..P} A_k B_k,  A_k = (1/S1) sum_s max(Psi(a_k+1; s) - Psi(a_k; s), 0),  B_k = (1/S2) sum_t Psi(b_k; t),
+ * which is (1/(S1 S2)) sum_s sum_t EHVI_st exactly, at O((S1 + S2) P) per candidate.  Fixed order: k ascending, s / t ascending within
+ * it, each sum divided once by its sample count, one rounded operation per operator, every Psi(a_k; s) evaluated once.
+ * Psi in the positive-term form: with d = a - mu, t = |d| / sigma and f = max(phi(t) - t erfc(t / sqrt2) / 2, 0) (ocml's erfc and exp),
+ * Psi = sigma f for d <= 0 and d + sigma f for d > 0; sigma == 0: max(d, 0) exactly; t > 37.5 (phi(t) below the smallest normal
+ * double): f = 0.
+ * Row classes: any mu or var NaN, or any var < 0, in either objective: NaN (the first NaN wins the arg-max, as everywhere);
+ * otherwise the score is finite and >= 0 (as long as no a - mu overflows), P = 0 included: Psi1(r1) Psi2(r2).
+ * Limits: P <= B7_EHVI_PMAX; S1, S2 in 1..B7_EHVI_SMAX.  The first B7_EHVI_SREG samples of each objective are held in registers
+ * across the strips, the rest in LDS.
+ * Not built, each refused by name where it can be asked for: more than two objectives, correlated objectives / multi-task GPs, a
+ * log-space EHVI, batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
+ * ParEGO-style scalarisation.  Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_EHVI_PMAX 256
+#define B7_EHVI_SMAX 32
+#define B7_EHVI_SREG 10
+/* The posterior half of b7_eval_nominate, KEPT: fits and posteriors of all S hyper samples over the resident data (one response
+ * column) and grid by b7_eval_nominate's routes (the one-launch route for N <= 128, side-by-side fits with batched K*, per-sample
+ * posteriors when the workspace does not hold K*, the jitter redo), mean and variance of every sample left as [S][M] in a buffer
+ * the context owns.  No arg-max is taken; the routes that score inline score a confidence bound whose values are dropped, and the
+ * context holds NO accumulator afterwards.  var_with_noise and var_clamp of b7_gp_opts apply as in b7_gp_predict_hyp; jitter_out /
+ * info_out (nullable, S entries) as b7_eval_nominate's.  The kept posterior is forgotten when the grid or the data changes.
+ * B7_ERR_UNSUPPORTED, the case named: more than one response column, a communicator of more than one rank.  B7_ERR_STATE: a member
+ * of a group, no resident data or grid.  Device memory: 2 S M doubles, allocated on demand.  No counterpart in the reference. */
+int b7_eval_posterior(b7_ctx *ctx, int S, const b7_hyp *hyps, double *jitter_out /*S*/, int *info_out /*S*/);
+/* Sample s (0-based) of the kept posterior: mean and var, M entries each (either nullable).  B7_ERR_STATE without a kept posterior,
+ * B7_ERR_INVALID for s outside it.  No counterpart in the reference. */
+int b7_posterior_get(b7_ctx *ctx, int s, double *mean /*M*/, double *var /*M*/);
+/* Host-only (no context, no GPU): the canonical front of n rows of two responses, Y n x 2.  Rows with a non-finite entry and rows
+ * not strictly inside the reference box are dropped, dominated rows are dropped, of equal rows the lowest stays; the rest sorted.
+ * front_out: room for min(n, B7_EHVI_PMAX) points (P x 2); rows1_out (nullable, same count): each point's 1-based source row.
+ * B7_ERR_INVALID: a NULL argument, n < 0, a non-finite ref, or a front of more than B7_EHVI_PMAX points (nothing is written but
+ * *P_out, the count).  No counterpart in the reference. */
+int b7_pareto_front2(const double *Y /*n x 2*/, int64_t n, const double *ref /*2*/, double *front_out, int64_t *rows1_out, int *P_out);
+/* Host-only: the area dominated by a canonical front inside the reference box, sum_k (a_k+1 - a_k)(r2 - b_k), k ascending; P = 0: 0.
+ * B7_ERR_INVALID for a front that is not canonical (any P >= 0 is taken).  No counterpart in the reference. */
+int b7_hypervolume2(const double *front /*P x 2*/, int P, const double *ref /*2*/, double *hv_out);
+/* The score alone on host arrays (the b7_ei_compute of EHVI), by the nomination's own kernel: mu1 / var1 S1 x M, mu2 / var2 S2 x M,
+ * out M.  B7_ERR_INVALID: a front that is not canonical or longer than B7_EHVI_PMAX, a non-finite ref, S1 or S2 outside
+ * 1..B7_EHVI_SMAX, NULL arguments.  No counterpart in the reference. */
+int b7_ehvi_compute(b7_ctx *ctx, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2,
+                    const double *front /*P x 2*/, int P, const double *ref /*2*/, int64_t M, double *out /*M*/);
+/* The nomination: ctx holds objective 1's kept posterior (b7_eval_posterior), other objective 2's; other == ctx is allowed (one
+ * posterior for both).  Both on the same device with the same number of grid rows -- that the rows are the same is the caller's
+ * contract, as for b7_feas_add_acc; the two streams are ordered by events both ways.  The marginal score is written to ctx's
+ * accumulator (a linear one, already divided: b7_score_finish(1) downloads it), the nominee is its score:max(1) by
+ * b7_eval_nominate's rule (the first NaN, else the maximum, ties to the lowest index).  Neither grid is modified.  Deterministic:
+ * the same call twice gives the same bits, and a row's value does not depend on how many rows the grid has.
+ * B7_ERR_INVALID: a front that is not canonical or longer than B7_EHVI_PMAX, a non-finite ref, a kept posterior of more than
+ * B7_EHVI_SMAX samples, different row counts, NULL arguments.  B7_ERR_STATE: no kept posterior on either side, a member of a
+ * group.  B7_ERR_UNSUPPORTED: contexts on different devices.  No counterpart in the reference. */
+int b7_ehvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front /*P x 2*/, int P, const double *ref /*2*/, double *best_val,
+                     int64_t *best_idx1);
+
 /* bayesopt:eval's DNGO branch + nominate as ONE call (bots/bayesopt.lua:65-66, :96 over models/dngo.lua:155-175):
  * b7_blr_fit_x(net, X0, Y0, ...) + b7_blr_basis(net, resident grid) + b7_blr_predict + the acquisition of `spec` (written,
  * not accumulated: ONE point (alpha_prec, beta, mean); b7_blr_eval_nominate_marg below marginalises over S of them) +

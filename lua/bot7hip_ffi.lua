@@ -103,6 +103,12 @@ int b7_kg_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int n, const int64_t 
 int b7_kg_trace_enable(b7_ctx *ctx, int on);
 int b7_kg_last(b7_ctx *ctx, int64_t *rows1 , double *alpha , double *slopes , double *values , double *own_alpha );
 int b7_kg_compute(b7_ctx *ctx, int64_t M1, int L, const double *alpha , const double *b , double *out);
+int b7_eval_posterior(b7_ctx *ctx, int S, const b7_hyp *hyps, double *jitter_out , int *info_out );
+int b7_posterior_get(b7_ctx *ctx, int s, double *mean , double *var );
+int b7_pareto_front2(const double *Y , int64_t n, const double *ref , double *front_out, int64_t *rows1_out, int *P_out);
+int b7_hypervolume2(const double *front , int P, const double *ref , double *hv_out);
+int b7_ehvi_compute(b7_ctx *ctx, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2, const double *front , int P, const double *ref , int64_t M, double *out );
+int b7_ehvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front , int P, const double *ref , double *best_val, int64_t *best_idx1);
 int b7_blr_eval_nominate(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, double alpha_prec, double beta, double mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *jitter_used);
 int b7_blr_eval_nominate_marg(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *alpha_prec, const double *beta, const double *mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *nll_out, double *jitter_used);
 typedef struct b7_group b7_group;
@@ -179,6 +185,9 @@ M.REFINE_MOVED = 8
 M.REFINE_TRACE_WIDTH = 200
 M.TS_MAX_FEATURES = 4096
 M.KG_MAX_POINTS = 16
+M.EHVI_PMAX = 256
+M.EHVI_SMAX = 32
+M.EHVI_SREG = 10
 M.MAX_TIMERS = 16
 -- END generated constants
 

@@ -129,6 +129,7 @@ end
 
 function bot:nominate(candidates)
   local candidates = candidates or self.candidates
+  if self.config.bot.objectives then return self:nominate_objectives(candidates) end   -- two objectives: below
   if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91
     -- sharded one process per GPU: against the UNION's rows (every rank draws the same number from the same stream)
     local rows = (D.world > 1) and assert(D.M_global, 'dist_hip.shard_range first') or candidates:size(1)
@@ -362,6 +363,82 @@ function bot:nominate_constrained(candidates)
   self.best_score = v[0]
   self.constrained_idx = tonumber(i[0])   -- what the driver steals next: follow_steal
   return torch.LongTensor{self.constrained_idx}
+end
+
+-- TWO-OBJECTIVE nomination (b7_ehvi_nominate; no counterpart in the reference; Emmerich, Yang & Deutz 2016):
+-- config.bot.objectives = {ref = {r1, r2} | nil, model = {...}}, config.score.type = 'expected_hypervolume_improvement'; the
+-- objective returns a row {y1, y2}, both minimised; self.responses keeps both columns.  The bot's own model sees column 1,
+-- self.objective2 = {model (a gp_hip), ctx (a context of its own)}, set up on first use, column 2.  Per model-based trial both
+-- models sample their hypers and both contexts keep their posterior over the same grid rows (b7_eval_posterior); the front of the
+-- observations under the reference point comes from b7_pareto_front2 and the objective's context nominates (b7_ehvi_nominate).
+-- ref = nil: per column the maximum of the observations plus 10 % of the column's range (of max(|maximum|, 1) where there is no
+-- range), recomputed every trial.  The driver steals the returned row from self.candidates (bots/abstract.lua:118); the next call
+-- deletes it from the second context's grid before anything is staged there (follow_steal).  One rank, no group, no batch, no
+-- refinement, no constraints; at parity with harness/bots/bayesopt.py's nominate_objectives.
+function bot:nominate_objectives(candidates)
+  local candidates = candidates or self.candidates
+  assert(D.world == 1 and not hip.group, 'nominate_objectives: one rank, no group (two objectives over a sharded grid are not built)')
+  local obj = assert(self.config.bot.objectives, 'nominate_objectives: config.bot.objectives is not set')
+  assert((self.config.bot.batch or 1) == 1, 'nominate_objectives: config.bot.batch > 1 (two-objective batches are not built)')
+  assert(not self.config.bot.refine, 'nominate_objectives: config.bot.refine (refinement of a two-objective nominee is not built)')
+  assert(not self.config.bot.constraints, 'nominate_objectives: config.bot.constraints (constraints combined with objectives are not built)')
+  assert(torch.type(self.score) == 'bot7.scores.expected_hypervolume_improvement_hip',
+         'nominate_objectives: config.score.type must be expected_hypervolume_improvement')
+  if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91
+    return torch.rand(1):mul(candidates:size(1)):long():add(1)
+  end
+  local model, keep = self.model, {}
+  assert(torch.type(model) == 'bot7.models.gp_hip', 'nominate_objectives: needs the gp_hip model (the Bayesian-linear head is not built)')
+  local R, S = self.responses, self.config.bot.nSamples
+  assert(R:dim() == 2 and R:size(2) == 2, 'nominate_objectives: the objective must return rows of 2 columns {y1, y2}')
+  local X_obs, Y1, Y2 = self.observed, R:narrow(2, 1, 1):contiguous(), R:narrow(2, 2, 1):contiguous()
+  if self.objective2 == nil then
+    local ctxp = ffi.new('b7_ctx*[1]')
+    assert(hip.C.b7_create(ctxp, hip.device) == 0, 'nominate_objectives: b7_create failed')   -- the objective's device
+    self.objective2 = {model = bot7.models.gp_hip(obj.model), ctx = ffi.gc(ctxp[0], hip.C.b7_destroy),
+                       kernel = hip.KERNEL_ARDSE}   -- a new context starts on ARD-SE: the second objective's own kernel cache
+  end
+  local o2 = self.objective2
+  local ref = hip.pin(torch.Tensor(2))
+  keep[#keep + 1] = ref
+  if obj.ref then
+    ref[1], ref[2] = obj.ref[1], obj.ref[2]
+  else
+    local hi, lo = R:max(1):view(-1), R:min(1):view(-1)
+    for k = 1, 2 do
+      local span = hi[k] - lo[k]
+      if not (span > 0) then span = math.max(math.abs(hi[k]), 1) end
+      ref[k] = hi[k] + 0.1 * span
+    end
+  end
+  local Rc = hip.pin(R:contiguous())
+  keep[#keep + 1] = Rc
+  local front, P = ffi.new('double[?]', 2 * math.max(1, math.min(R:size(1), hip.EHVI_PMAX))), ffi.new('int[1]')
+  assert(hip.C.b7_pareto_front2(hip.data(Rc), R:size(1), hip.data(ref), front, nil, P) == 0,
+         'nominate_objectives: a front of more than EHVI_PMAX points, or a reference point that is not finite')
+  local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+  local hyps = sample_hyps(model, X_obs, Y1, S, keep)
+  model:stage(X_obs, Y1, candidates)
+  hip.set_kernel(model.kernel_code)
+  hip.check(hip.C.b7_eval_posterior(hip.ctx, S, hyps, jit, info))
+  follow_steal(o2, self.objectives_idx, candidates)
+  on_context(o2, function()
+    if not o2.inited then o2.model:init(X_obs, Y2); o2.inited = true end
+    local hyps2 = sample_hyps(o2.model, X_obs, Y2, S, keep)
+    o2.model:stage(X_obs, Y2, candidates)
+    hip.set_kernel(o2.model.kernel_code)
+    hip.check(hip.C.b7_eval_posterior(hip.ctx, S, hyps2, nil, nil))
+  end)
+  local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
+  hip.check(hip.C.b7_ehvi_nominate(hip.ctx, o2.ctx, front, P[0], hip.data(ref), v, i))
+  for s = 0, S - 1 do
+    if jit[s] > 0 then   -- the reference's warning text, utils/math.lua:210-212
+      print(string.format('Warning: utils.math.chol succeeded in factorizing the\ninput matrix after applying a jitter of %.2e', jit[s]))
+    end
+  end
+  self.best_score = v[0]
+  self.objectives_idx = tonumber(i[0])   -- what the driver steals next: follow_steal
+  return torch.LongTensor{self.objectives_idx}
 end
 
 -- bots/abstract.lua:112-152 for candidates sharded one process per GPU.  Only line 118 differs: `idx` is 1-based in the

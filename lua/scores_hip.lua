@@ -176,6 +176,21 @@ do
 end
 
 do
+  -- The exact two-objective expected hypervolume improvement (b7_ehvi_nominate; no original): not a per-point score of one posterior
+  -- -- it needs the kept posteriors of two objectives, a front and a reference point.  bots_bayesopt_hip.lua's nominate_objectives
+  -- calls the library in place of eval + arg-max (config.bot.objectives).  Checked by the static checker only.
+  local EHVI, parent = torch.class('bot7.scores.expected_hypervolume_improvement_hip', 'bot7.scores.abstract')
+  function EHVI:__init(config)
+    parent.__init(self)
+    self.config = config or {}
+  end
+  function EHVI:__call__(model, hyp, X_obs, Y_obs, X_hid, X_pend, config)
+    error('expected_hypervolume_improvement_hip is not a per-point score: nominate through bot7.bots.bayesopt_hip (b7_ehvi_nominate)')
+  end
+  S.expected_hypervolume_improvement = EHVI
+end
+
+do
   local CB, parent = torch.class('bot7.scores.confidence_bound_hip', 'bot7.scores.abstract')
   function CB:__init(config)
     parent.__init(self)
