@@ -10,10 +10,10 @@
 // triangular mat-vecs that make alpha (launch_alpha_batch), the downdate (believer_kernel over the grid), and one rescoring of
 // all samples (score.hip's fused kernel, the rows already picked left out of its arg-max).  No factorisation, no variance product.
 //
-// believer_kernel is the mean half of ksx_kernel (covar.hip) with w_j in alpha's place and WITHOUT its stores of K*: the same
-// MFMA distance product (query rows as A, the pre-scaled observations as B, slabs of 64 -- 32 for dpad >= 48 -- double-buffered in
-// LDS), the same epilogue arg = (c - xs/2) - zs/2 -> cov_nonpos4<KERN>, so a downdated variance is made of the covariance entries
-// the variance itself was made of, under either kernel.  k(x, x_j) comes out of one more 16x16 tile whose only live column is the
+// believer_kernel is the slab walk of ksx_walk.h with w_j as the rider: the mean half of ksx_kernel (covar.hip) WITHOUT its stores
+// of K*.  Prologue, slab loop and the tile (KsxWalk::cov_tile: MFMA distance product, arg = (c - xs/2) - zs/2 -> cov_nonpos4<KERN>)
+// are the text ksx_kernel runs, so a downdated variance is made of the covariance entries the variance itself was made of, under
+// either kernel.  k(x, x_j) comes out of one more 16x16 tile whose only live column is the
 // believed point, scaled as prep_obs_kernel scales an observation.  The sum over the observations has ONE order -- per lane the
 // columns lr, lr + 16, .. in slab order, then the xor-shuffle tree -- whatever the grid's size.  One text serves the general
 // layout (Npad a multiple of 128) and the small regime (Npad 64 or 128): DESIGN.md section 3's padding and width classes.
@@ -24,15 +24,16 @@
 #include "b7_internal.h"
 #include "gemm_f64.h"
 #include "ksx_exp.h"
+#include "ksx_walk.h"
 
 namespace {
 
-__constant__ double exp2_tab_bel[128];  // b7_exp2_tab (ensure_bel_table)
-
-constexpr int BQ = 64;                  // query rows per block (16 per wave), as ksx_kernel's KQ
 constexpr int BSC = 1 + B7_BATCH_MAX;   // a sample's scalars of one pick: t_j, then u_i(x_j) for i < j
-__host__ __device__ constexpr int bel_slab(int dpad) { return dpad >= 48 ? 32 : 64; }
 
+// the kernel's own LDS behind the walk's: DPAD the believed point, scaled: x_j .* w | 1 + BSC zs/2 of the believed point | t_j, u_i(x_j)
+constexpr int bel_extra(int dpad) { return dpad + 1 + BSC + 1; }
+
+// The walk's rider is w_j: one word per row.
 template <int DPAD, int KERN>
 __global__ void __launch_bounds__(256) believer_kernel(BelPass p, int d, int Npad, int N, int column) {
   extern __shared__ __align__(16) double sm[];
@@ -42,143 +43,58 @@ __global__ void __launch_bounds__(256) believer_kernel(BelPass p, int d, int Npa
   const double amp = p.par[2 * s], tnoise = p.par[2 * s + 1];
   double *scal = p.scal + s * BSC;
   const int64_t Mtotal = p.rows;
-  constexpr int KO = bel_slab(DPAD);
-  constexpr int TPR = 256 / KO;
-  constexpr int dpad = DPAD, NCH = (DPAD / 2 + TPR - 1) / TPR, KSTEPS = DPAD / 4;
-  constexpr int stride = DPAD + 1;
-  constexpr int R0 = (BQ * stride > 2 * KO * stride) ? BQ * stride : 2 * KO * stride;
-  double *sq = sm;                          // BQ x stride, prologue only
-  double *so = sm;                          // 2 x KO x stride, from the first slab on
-  double *sh = sm + R0;                     // 2 x KO   zs/2 of the slab
-  double *sal = sh + 2 * KO;                // 2 x KO   w_j of the slab
-  double *shq = sal + 2 * KO;               // BQ       xs/2 of the queries
-  double *stab = shq + BQ;                  // 128      amp * 2^(j/128)
-  double *sxj = stab + 128;                 // DPAD     the believed point, scaled: x_j .* w
+  using T = KsxTile<DPAD, 1>;
+  constexpr int KO = T::KO, dpad = DPAD;
+  KsxWalk<DPAD, 1> wk(sm, zsc, zsh);
+  const int tid = wk.tid, wave = wk.wave, lr = wk.lr, lq = wk.lq;
+  const double *sh = wk.zs();
+  double *sal = wk.rider();                 // 2 x KO   w_j of the slab
+  double *sxj = wk.extra();                 // DPAD     the believed point, scaled: x_j .* w
   double *ssc = sxj + DPAD;                 // 1 + BSC  zs/2 of the believed point | t_j, u_i(x_j)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, lq = lane >> 4;
-  const int64_t qbase = (int64_t)blockIdx.x * BQ;
-  const int srow = tid / TPR, sq4 = tid % TPR;
-  const int qrow = tid >> 2, qq4 = tid & 3;
-  constexpr int half = DPAD >> 1;
-
-  if (tid < 128) stab[tid] = amp * exp2_tab_bel[tid];
-  {
-    int64_t g = qbase + qrow;
-    if (g > Mtotal - 1) g = Mtotal - 1;
-    for (int k = qq4; k < dpad; k += 4) sq[qrow * stride + k] = (k < d) ? p.xq[g * d + k] : 0.0;
-  }
-  // the believed point as prep_obs_kernel makes an observation: z .* w, and (sum z^2 w)/2 in ascending k
-  if (tid >= 128 && tid < 128 + dpad) {
-    const int k = tid - 128;
-    sxj[k] = (k < d) ? p.xj[k] * w[k] : 0.0;
-  }
-  if (tid == 255) {
-    double a = 0.0;
-    for (int k = 0; k < d; ++k) {
-      const double z = p.xj[k];
-      a += (z * z) * w[k];
-    }
-    ssc[0] = 0.5 * a;
-  }
-  if (!column && tid >= 192 && tid < 192 + 1 + p.j) ssc[1 + (tid - 192)] = scal[tid - 192];
+  const int64_t qbase = (int64_t)blockIdx.x * KSX_Q;
   const int nslab = column ? 0 : Npad / KO;
 
-  d2_t pre[NCH];
-  double pre_h = 0.0, pre_a = 0.0;
-  auto load_slab = [&](int sl) {
-    const double *src = zsc + (int64_t)(sl * KO + srow) * dpad;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int kc = i * TPR + sq4;
-      if (kc < half) pre[i] = *reinterpret_cast<const d2_t *>(src + 2 * kc);
+  double pre_a = 0.0;
+  auto rider_load = [&](int sl) { pre_a = wj[sl * KO + tid]; };
+  auto rider_store = [&](int buf) { sal[buf * KO + tid] = pre_a; };
+  wk.begin(p.xq, qbase, Mtotal, d, w, amp, 0, nslab, [&] {
+    // the believed point as prep_obs_kernel makes an observation: z .* w, and (sum z^2 w)/2 in ascending k
+    if (tid >= 128 && tid < 128 + dpad) {
+      const int k = tid - 128;
+      sxj[k] = (k < d) ? p.xj[k] * w[k] : 0.0;
     }
-    if (tid < KO) {
-      pre_h = zsh[sl * KO + tid];
-      pre_a = wj[sl * KO + tid];
-    }
-  };
-  auto store_slab = [&](int buf) {
-    double *dst = so + buf * KO * stride + srow * stride;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int kc = i * TPR + sq4;
-      if (kc < half) {
-        dst[2 * kc] = pre[i][0];
-        dst[2 * kc + 1] = pre[i][1];
+    if (tid == 255) {
+      double a = 0.0;
+      for (int k = 0; k < d; ++k) {
+        const double z = p.xj[k];
+        a += (z * z) * w[k];
       }
+      ssc[0] = 0.5 * a;
     }
-    if (tid < KO) {
-      sh[buf * KO + tid] = pre_h;
-      sal[buf * KO + tid] = pre_a;
-    }
-  };
-
-  if (nslab > 0) load_slab(0);
-  __syncthreads();  // query tile visible
-  if (tid < BQ) {
-    double a = 0.0;
-    for (int k = 0; k < dpad; ++k) {
-      double x = sq[tid * stride + k];
-      a += (x * x) * w[k];
-    }
-    shq[tid] = 0.5 * a;
-  }
-  double qf[KSTEPS];  // this lane's A fragments: query row (wave*16 + lr), k = 4 k4 + lq
-#pragma unroll
-  for (int k4 = 0; k4 < KSTEPS; ++k4) qf[k4] = sq[(wave * 16 + lr) * stride + lq + 4 * k4];
-  __syncthreads();  // every wave holds its fragments, shq is complete: the region now belongs to the slabs
-  if (nslab > 0) store_slab(0);
-  __syncthreads();
+    if (!column && tid >= 192 && tid < 192 + 1 + p.j) ssc[1 + (tid - 192)] = scal[tid - 192];
+  }, rider_load, rider_store);
 
   double hq[4], macc[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-  for (int r = 0; r < 4; ++r) hq[r] = shq[wave * 16 + lq + 4 * r];
+  for (int r = 0; r < 4; ++r) hq[r] = wk.xs()[wave * 16 + lq + 4 * r];
 
-  int cur = 0;
-  for (int sl = 0; sl < nslab; ++sl) {
-    const bool more = (sl + 1) < nslab;
-    if (more) load_slab(sl + 1);
-    const double *sob = so + cur * KO * stride;
+  wk.run(0, nslab, rider_load, rider_store, [&](int, int cur, int t, const double (&bf)[T::KSTEPS]) {
+    const d4_t c = wk.dist(bf);
+    const double hk = sh[cur * KO + t * 16 + lr];
+    const double al = sal[cur * KO + t * 16 + lr];
+    double kv[4];
+    wk.template cov<KERN>(c, hq, hk, kv);
 #pragma unroll
-    for (int t = 0; t < KO / 16; ++t) {
-      const double *ob = sob + (t * 16 + lr) * stride + lq;
-      d4_t c = {0.0, 0.0, 0.0, 0.0};
-      {
-        double bf[KSTEPS];
-#pragma unroll
-        for (int k4 = 0; k4 < KSTEPS; ++k4) bf[k4] = ob[4 * k4];
-#pragma unroll
-        for (int k4 = 0; k4 < KSTEPS; ++k4) c = mfma_f64(qf[k4], bf[k4], c);
-      }
-      const double hk = sh[cur * KO + t * 16 + lr];
-      const double al = sal[cur * KO + t * 16 + lr];
-      double kv[4], arg[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) arg[r] = (c[r] - hq[r]) - hk;
-      cov_nonpos4<KERN>(arg, stab, kv);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) macc[r] = __builtin_fma(kv[r], al, macc[r]);
-    }
-    if (more) store_slab(cur ^ 1);
-    __syncthreads();
-    cur ^= 1;
-  }
+    for (int r = 0; r < 4; ++r) macc[r] = __builtin_fma(kv[r], al, macc[r]);
+  });
 
   // k(x, x_j): one more tile; column 0 is the believed point, the other fifteen are padding (zs/2 = 1e300 -> exactly 0)
   double kx[4];
   {
-    d4_t c = {0.0, 0.0, 0.0, 0.0};
-    double bf[KSTEPS];
+    double bf[T::KSTEPS];
 #pragma unroll
-    for (int k4 = 0; k4 < KSTEPS; ++k4) bf[k4] = (lr == 0) ? sxj[lq + 4 * k4] : 0.0;
-#pragma unroll
-    for (int k4 = 0; k4 < KSTEPS; ++k4) c = mfma_f64(qf[k4], bf[k4], c);
-    const double hk = (lr == 0) ? ssc[0] : 1e300;
-    double arg[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) arg[r] = (c[r] - hq[r]) - hk;
-    cov_nonpos4<KERN>(arg, stab, kx);
+    for (int k4 = 0; k4 < T::KSTEPS; ++k4) bf[k4] = (lr == 0) ? sxj[lq + 4 * k4] : 0.0;
+    wk.template cov<KERN>(wk.dist(bf), hq, (lr == 0) ? ssc[0] : 1e300, kx);
   }
 
   if (column) {
@@ -216,44 +132,17 @@ __global__ void __launch_bounds__(256) believer_kernel(BelPass p, int d, int Npa
   }
 }
 
-size_t bel_lds_bytes(int dpad) {
-  const int KO = bel_slab(dpad);
-  const size_t r0 = (size_t)(BQ > 2 * KO ? BQ : 2 * KO) * (dpad + 1);
-  return sizeof(double) * (r0 + 4 * KO + BQ + 128 + dpad + 1 + BSC + 1);
-}
-
-int ensure_bel_table(b7_ctx *c) {
-  static bool done[64] = {false};
-  if (c->device < 64 && done[c->device]) return B7_OK;
-  B7_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(exp2_tab_bel), b7_exp2_tab, sizeof(b7_exp2_tab)));
-  if (c->device < 64) done[c->device] = true;
-  return B7_OK;
-}
-
-template <int DPAD, int KERN>
 int bel_launch(b7_ctx *c, int S, const BelPass &p, bool column) {
-  const size_t lds = bel_lds_bytes(DPAD);
-  auto kern = believer_kernel<DPAD, KERN>;
-  B7_TRY(ensure_bel_table(c));
-  B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t blocks = column ? c->Npad / BQ : (p.rows + BQ - 1) / BQ;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks, 1, S), dim3(256), lds, c->stream, p, c->dfit, c->Npad, c->N, column ? 1 : 0);
-  B7_HIP(c, hipGetLastError());
-  return B7_OK;
-}
-
-template <int KERN>
-int bel_dispatch(b7_ctx *c, int S, const BelPass &p, bool column) {
-  switch (c->dpad) {
-    case 4: return bel_launch<4, KERN>(c, S, p, column);
-    case 8: return bel_launch<8, KERN>(c, S, p, column);
-    case 16: return bel_launch<16, KERN>(c, S, p, column);
-    case 32: return bel_launch<32, KERN>(c, S, p, column);
-    case 48: return bel_launch<48, KERN>(c, S, p, column);
-    case 64: return bel_launch<64, KERN>(c, S, p, column);
-    case 96: return bel_launch<96, KERN>(c, S, p, column);
-    default: return b7_fail(c, B7_ERR_UNSUPPORTED, "believer kernel: dpad %d is not a built class", c->dpad);
-  }
+  return ksx_for_class(c, "believer kernel", [&](auto cls) {
+    using C = decltype(cls);
+    const size_t lds = KsxTile<C::DPAD, 1>::lds_bytes(bel_extra(C::DPAD));
+    auto kern = believer_kernel<C::DPAD, C::KERN>;
+    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t blocks = column ? c->Npad / KSX_Q : (p.rows + KSX_Q - 1) / KSX_Q;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, 1, S), dim3(256), lds, c->stream, p, c->dfit, c->Npad, c->N, column ? 1 : 0);
+    B7_HIP(c, hipGetLastError());
+    return B7_OK;
+  });
 }
 
 // the per-sample arrays of a call, carved out of c->bel and c->belvec
@@ -276,8 +165,7 @@ int bel_state(b7_ctx *c, int S, int q, BelState *st) {
 
 int launch_believer(b7_ctx *c, int S, const BelPass &p, bool column) {
   PhaseScope ps(c, "believer");
-  if (c->kernel == B7_KERNEL_MATERN52) return bel_dispatch<B7_KERNEL_MATERN52>(c, S, p, column);
-  return bel_dispatch<B7_KERNEL_ARDSE>(c, S, p, column);
+  return bel_launch(c, S, p, column);
 }
 
 extern "C" {

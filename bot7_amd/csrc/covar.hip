@@ -8,11 +8,10 @@
 //   mean part of model:predict (scores/expected_improvement.lua:63): mu = m + K(X*,X) alpha
 //
 // Layout: the inner product X (Z' .* w) runs on v_mfma_f64_16x16x4_f64 with the query rows as the A operand
-// and the pre-scaled observations (z .* w, zero-padded to the class dpad in {4,8,16,32,48,64,96}) as B.  A block
-// owns 64 query rows and walks observations in slabs of 64 (32 for dpad >= 48), double-buffered in LDS with the
-// next slab prefetched into registers while the current one is consumed (one barrier per slab), so it sees whole
-// rows of K(X*,X): the posterior-mean dot product with alpha is accumulated in registers on the way and needs no
-// second pass over K*.
+// and the pre-scaled observations (z .* w, zero-padded to the class dpad in {4,8,16,32,48,64,96}) as B.  ksx_kernel is
+// the slab walk of ksx_walk.h (64 query rows per block, the observations past them slab by slab) with alpha as the
+// rider: a block sees whole rows of K(X*,X), so the posterior-mean dot product with alpha is accumulated in
+// registers on the way and needs no second pass over K*.
 // Epilogue per element: arg = (c - xs/2) - zs/2 (the reference's ((-2c + xs) + zs) scaled by the exact factor
 // -1/2, same rounding points), clamp to <= 0 (NaN passes, as TH's clamp), amp * exp(arg).  Lane pairs swap one
 // value (DPP quad_perm) so every lane stores 16 bytes: 2 stores per 16x16 tile instead of 4.
@@ -25,10 +24,9 @@
 #include "b7_internal.h"
 #include "gemm_f64.h"
 #include "ksx_exp.h"
+#include "ksx_walk.h"
 
 namespace {
-
-__constant__ double exp2_tab_dev[128];  // b7_exp2_tab, uploaded once per process (ensure_exp_table)
 
 // ---- observation pre-scaling: zsc = z .* w (padded), zsh = (sum z^2 w)/2 ---------------------------------------
 // One wave per 64 observations: the rows are loaded and stored through an LDS tile (coalesced both ways; a thread
@@ -107,16 +105,11 @@ __device__ __forceinline__ void pair_pack(double a, double b, d2_t &out) {
 // Mtotal-1 are clamped: they produce values nobody reads).  out: rows x Npad (leading dimension Npad).
 // mu (nullable): mean + K* alpha for ycols == 1.  blockIdx.y splits the observations into gridDim.y equal
 // ranges of whole slabs (used for K(X,X), where there are few query rows; mu must then be null).
-constexpr int KQ = 64;  // query rows per block (16 per wave)
-// observation slab: 64 rows, 32 for the wide classes so that two blocks still fit a CU's LDS
-// (measured at DPAD = 64 with 64-row slabs: 1 block/CU, 2.07 TB/s against 3.97 TB/s at DPAD = 32)
-__host__ __device__ constexpr int ksx_slab(int dpad) { return dpad >= 48 ? 32 : 64; }
-
 // DPAD = padded input dimension, one of the classes {4, 8, 16, 32, 48, 64, 96} (b7_dpad_class): compile-time so that
 // the MFMA chain over DPAD/4 k-steps unrolls and the query fragments stay in registers for the whole block.
 // blockIdx.z = fit index of a batch over the same observations (b7_gp_nll_batch); all zero / null for a single fit
 using KBatch = KBatchDesc;
-// KERN: the covariance kernel (B7_KERNEL_*, ksx_exp.h cov_nonpos4)
+// KERN: the covariance kernel (B7_KERNEL_*, ksx_exp.h cov_nonpos4).  The walk's rider is alpha (0 when null): one word per row.
 template <int DPAD, int KERN>
 __global__ void __launch_bounds__(256)
     ksx_kernel(const double *__restrict__ xq, int64_t row0, int64_t Mtotal, int d, int dpad_rt, const double *w,
@@ -136,157 +129,76 @@ __global__ void __launch_bounds__(256)
       meanc = kb.mean[bz];
     }
   }
-  constexpr int KO = ksx_slab(DPAD);
-  constexpr int TPR = 256 / KO;                       // staging threads per slab row
-  constexpr int dpad = DPAD, NCH = (DPAD / 2 + TPR - 1) / TPR, KSTEPS = DPAD / 4;
-  constexpr int stride = DPAD + 1;  // odd: conflict-free for the fused ds_read2_b64 fragment reads (gemm_f64.h)
   (void)dpad_rt;
-  // The query tile is dead once its fragments sit in registers (before the first slab is consumed), so the two slab buffers
-  // live in the SAME LDS region: 50 -> 34 KB per workgroup at DPAD 32, 67 -> 34 at 64, 99 -> 50 at 96, i.e. three workgroups
-  // per CU (the register file's limit) instead of two at d = 64 and one at d = 96.  Costs two barriers in the prologue.
-  constexpr int R0 = (KQ * stride > 2 * KO * stride) ? KQ * stride : 2 * KO * stride;
-  double *sq = sm;                          // KQ x stride, prologue only
-  double *so = sm;                          // 2 x KO x stride, from the first slab on
-  double *sh = sm + R0;                     // 2 x KO   zs/2 of the slab
-  double *sal = sh + 2 * KO;                // 2 x KO   alpha of the slab
-  double *shq = sal + 2 * KO;               // KQ       xs/2 of the queries
-  double *stab = shq + KQ;                  // 128      amp * 2^(j/128)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, lq = lane >> 4;
-  const int64_t qbase = row0 + (int64_t)blockIdx.x * KQ;
-  const int srow = tid / TPR, sq4 = tid % TPR;  // slab staging: TPR threads per row
-  const int qrow = tid >> 2, qq4 = tid & 3;     // query staging: 64 rows, 4 threads per row
-  constexpr int half = DPAD >> 1;            // 16-byte chunks per row
-
-  if (tid < 128) stab[tid] = amp * exp2_tab_dev[tid];
-  // query tile (zero-padded columns)
-  {
-    int64_t g = qbase + qrow;
-    if (g > Mtotal - 1) g = Mtotal - 1;
-    for (int k = qq4; k < dpad; k += 4) sq[qrow * stride + k] = (k < d) ? xq[g * d + k] : 0.0;
-  }
+  using T = KsxTile<DPAD, 1>;
+  constexpr int KO = T::KO;
+  KsxWalk<DPAD, 1> wk(sm, zsc, zsh);
+  const int tid = wk.tid, lane = wk.lane, wave = wk.wave, lr = wk.lr, lq = wk.lq;
+  const int64_t qbase = row0 + (int64_t)blockIdx.x * KSX_Q;
   const int nslab_total = Npad / KO;
   const int nslab = nslab_total / gridDim.y;
   const int slab0 = blockIdx.y * nslab;
+  // the walk guards its first slab by nslab > 0 (a column pass has none); this kernel never had that branch, and its launchers
+  // split whole slabs of an Npad >= 64, so the guard is assumed away: without this line the kernel has one branch more
+  __builtin_assume(nslab > 0);
 
-  d2_t pre[NCH];
-  double pre_h = 0.0, pre_a = 0.0;
-  auto load_slab = [&](int s) {
-    const double *src = zsc + (int64_t)(s * KO + srow) * dpad;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int kc = i * TPR + sq4;
-      if (kc < half) pre[i] = *reinterpret_cast<const d2_t *>(src + 2 * kc);
-    }
-    if (tid < KO) {
-      pre_h = zsh[s * KO + tid];
-      pre_a = alpha ? alpha[s * KO + tid] : 0.0;
-    }
-  };
-  auto store_slab = [&](int buf) {
-    double *dst = so + buf * KO * stride + srow * stride;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int kc = i * TPR + sq4;
-      if (kc < half) {
-        dst[2 * kc] = pre[i][0];
-        dst[2 * kc + 1] = pre[i][1];
-      }
-    }
-    if (tid < KO) {
-      sh[buf * KO + tid] = pre_h;
-      sal[buf * KO + tid] = pre_a;
-    }
-  };
-
-  load_slab(slab0);
-  __syncthreads();  // query tile visible
-  if (tid < KQ) {
-    double s = 0.0;
-    for (int k = 0; k < dpad; ++k) {
-      double x = sq[tid * stride + k];
-      s += (x * x) * w[k];  // X_ss = (X.^2) * inv_ls, :78
-    }
-    shq[tid] = 0.5 * s;
-  }
-  double qf[KSTEPS];  // this lane's A fragments: query row (wave*16 + lr), k = 4 k4 + lq
-#pragma unroll
-  for (int k4 = 0; k4 < KSTEPS; ++k4) qf[k4] = sq[(wave * 16 + lr) * stride + lq + 4 * k4];
-  __syncthreads();  // every wave holds its fragments, shq is complete: the region now belongs to the slabs
-  store_slab(0);
-  __syncthreads();
+  const double *sh = wk.zs();
+  double *sal = wk.rider();  // 2 x KO   alpha of the slab
+  double pre_a = 0.0;
+  auto rider_load = [&](int s) { pre_a = alpha ? alpha[s * KO + tid] : 0.0; };
+  auto rider_store = [&](int buf) { sal[buf * KO + tid] = pre_a; };
+  wk.begin(xq, qbase, Mtotal, d, w, amp, slab0, nslab, [] {}, rider_load, rider_store);
 
   double hq[4], macc[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-  for (int r = 0; r < 4; ++r) hq[r] = shq[wave * 16 + lq + 4 * r];
+  for (int r = 0; r < 4; ++r) hq[r] = wk.xs()[wave * 16 + lq + 4 * r];
   // this lane's 16-byte store slots: even lanes write rows r = 0 and 2, odd lanes rows r = 1 and 3, two columns
   const bool odd = lane & 1;
-  double *orow = out + ((int64_t)blockIdx.x * KQ + wave * 16 + lq + (odd ? 4 : 0)) * Npad + (lr & ~1);
+  double *orow = out + ((int64_t)blockIdx.x * KSX_Q + wave * 16 + lq + (odd ? 4 : 0)) * Npad + (lr & ~1);
 
-  int cur = 0;
-  for (int s = 0; s < nslab; ++s) {
-    const bool more = (s + 1) < nslab;
-    if (more) load_slab(slab0 + s + 1);
-    const double *sob = so + cur * KO * stride;
-    const int o0 = (slab0 + s) * KO;
-#pragma unroll
-    for (int t = 0; t < KO / 16; ++t) {
-      const double *ob = sob + (t * 16 + lr) * stride + lq;
-      d4_t c = {0.0, 0.0, 0.0, 0.0};
-      {
-        double bf[KSTEPS];
-#pragma unroll
-        for (int k4 = 0; k4 < KSTEPS; ++k4) bf[k4] = ob[4 * k4];
-#if B7_KSX_ABLATE & 8   // one MFMA per tile instead of DPAD / 4
-        c = mfma_f64(qf[0], bf[0], c);
+  wk.run(slab0, nslab, rider_load, rider_store, [&](int s, int cur, int t, const double (&bf)[T::KSTEPS]) {
+    const int o0 = s * KO;
+#if B7_KSX_ABLATE & 8   // diagnostic builds only (tools/ksx_ablate.py): one MFMA per tile instead of DPAD / 4
+    const d4_t c = mfma_f64(wk.qf[0], bf[0], d4_t{0.0, 0.0, 0.0, 0.0});
 #else
-#pragma unroll
-        for (int k4 = 0; k4 < KSTEPS; ++k4) c = mfma_f64(qf[k4], bf[k4], c);
+    const d4_t c = wk.dist(bf);
 #endif
-      }
-      const double hk = sh[cur * KO + t * 16 + lr];
-      const double al = sal[cur * KO + t * 16 + lr];
-      double kv[4], arg[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) arg[r] = (c[r] - hq[r]) - hk;  // = -1/2 * (((-2 c) + xs) + zs), utils/math.lua:82
-#if B7_KSX_ABLATE & 4   // diagnostic builds only (tools/ksx_ablate.py): no exp
-#pragma unroll
-      for (int r = 0; r < 4; ++r) kv[r] = arg[r];
+    const double hk = sh[cur * KO + t * 16 + lr];
+    const double al = sal[cur * KO + t * 16 + lr];
+    double kv[4];
+#if B7_KSX_ABLATE & 4   // no exp
+    wk.arg4(c, hq, hk, kv);
 #else
-      cov_nonpos4<KERN>(arg, stab, kv);  // :106 clamp(0, huge) on the distance (NaN passes), amp * exp(-D/2) (ARD-SE)
+    wk.template cov<KERN>(c, hq, hk, kv);
 #endif
 #pragma unroll
-      for (int r = 0; r < 4; ++r) macc[r] = __builtin_fma(kv[r], al, macc[r]);
-      // rows (lq, lq+4, lq+8, lq+12) x column lr  ->  16-byte stores of two adjacent columns: even lanes write rows r = 0
-      // and 2 (their own value, then the odd neighbour's), odd lanes rows r = 1 and 3 (the even neighbour's, then their own)
-      d2_t v01, v23;
-      pair_pack(kv[0], kv[1], v01);
-      pair_pack(kv[2], kv[3], v23);
-      {
-        double *p = orow + o0 + t * 16;
+    for (int r = 0; r < 4; ++r) macc[r] = __builtin_fma(kv[r], al, macc[r]);
+    // rows (lq, lq+4, lq+8, lq+12) x column lr  ->  16-byte stores of two adjacent columns: even lanes write rows r = 0
+    // and 2 (their own value, then the odd neighbour's), odd lanes rows r = 1 and 3 (the even neighbour's, then their own)
+    d2_t v01, v23;
+    pair_pack(kv[0], kv[1], v01);
+    pair_pack(kv[2], kv[3], v23);
+    {
+      double *p = orow + o0 + t * 16;
 #if B7_KSX_ABLATE & 1   // no stores (a condition that never holds keeps the values alive)
-        if (v01[0] == 1.2345e-300) {
+      if (v01[0] == 1.2345e-300) {
 #endif
 #if B7_KSX_ABLATE & 16  // the same bytes to row-contiguous addresses (2 rows x 512 B per instruction; wrong placement)
-        double *pi = out + ((int64_t)blockIdx.x * KQ + wave * 16 + 4 * t + (lane >> 5)) * Npad + o0 + (lane & 31) * 2;
-        *reinterpret_cast<d2_t *>(pi) = v01;
-        *reinterpret_cast<d2_t *>(pi + (int64_t)2 * Npad) = v23;
+      double *pi = out + ((int64_t)blockIdx.x * KSX_Q + wave * 16 + 4 * t + (lane >> 5)) * Npad + o0 + (lane & 31) * 2;
+      *reinterpret_cast<d2_t *>(pi) = v01;
+      *reinterpret_cast<d2_t *>(pi + (int64_t)2 * Npad) = v23;
 #elif B7_KSX_ABLATE & 32  // non-temporal stores
-        __builtin_nontemporal_store(v01, reinterpret_cast<d2_t *>(p));
-        __builtin_nontemporal_store(v23, reinterpret_cast<d2_t *>(p + (int64_t)8 * Npad));
+      __builtin_nontemporal_store(v01, reinterpret_cast<d2_t *>(p));
+      __builtin_nontemporal_store(v23, reinterpret_cast<d2_t *>(p + (int64_t)8 * Npad));
 #else
-        *reinterpret_cast<d2_t *>(p) = v01;
-        *reinterpret_cast<d2_t *>(p + (int64_t)8 * Npad) = v23;
+      *reinterpret_cast<d2_t *>(p) = v01;
+      *reinterpret_cast<d2_t *>(p + (int64_t)8 * Npad) = v23;
 #endif
 #if B7_KSX_ABLATE & 1
-        }
-#endif
       }
+#endif
     }
-    if (more) store_slab(cur ^ 1);
-    __syncthreads();
-    cur ^= 1;
-  }
+  });
 
   if (mu) {
 #pragma unroll
@@ -318,10 +230,9 @@ __global__ void __launch_bounds__(256)
     K[e] += diag_add;
 }
 
-size_t ksx_lds_bytes(int dpad) {
-  const int KO = ksx_slab(dpad);
-  const size_t r0 = (size_t)(KQ > 2 * KO ? KQ : 2 * KO) * (dpad + 1);  // query tile and slab buffers share a region
-  size_t bytes = sizeof(double) * (r0 + 4 * KO + KQ + 128);
+template <int DPAD>
+size_t ksx_lds_bytes() {
+  size_t bytes = KsxTile<DPAD, 1>::lds_bytes(0);
 #if B7_KSX_ABLATE & 128   // diagnostic: pad the request so that one workgroup fewer fits a CU (sensitivity to occupancy)
   const size_t per_cu = 160 * 1024, fit = per_cu / bytes;
   if (fit > 1) bytes = per_cu / (fit - 1) - 512;
@@ -329,49 +240,20 @@ size_t ksx_lds_bytes(int dpad) {
   return bytes;
 }
 
-// the 2^(j/128) table goes to constant memory once per process and device
-int ensure_exp_table(b7_ctx *c) {
-  static bool done[64] = {false};
-  if (c->device < 64 && done[c->device]) return B7_OK;
-  B7_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(exp2_tab_dev), b7_exp2_tab, sizeof(b7_exp2_tab)));
-  if (c->device < 64) done[c->device] = true;
-  return B7_OK;
-}
-
-template <int DPAD, int KERN>
 int ksx_launch(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
                const double *alpha, double amp, double meanc, double *out, double *mu) {
-  const size_t lds = ksx_lds_bytes(DPAD);
-  auto kern = ksx_kernel<DPAD, KERN>;
-  B7_TRY(ensure_exp_table(c));
-  // dynamic LDS above the 64 KiB default needs an explicit opt-in (gfx950 has 160 KiB per workgroup)
-  B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, c->stream, xq, row0, Mtotal, d, c->dpad, o.w ? o.w : (const double *)c->w.p,
-                     o.zsc, o.zsh, alpha, amp, meanc, o.npad, out, mu, o.batch);
-  B7_HIP(c, hipGetLastError());
-  return B7_OK;
-}
-
-template <int KERN>
-int ksx_dispatch_k(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
-                   const double *alpha, double amp, double meanc, double *out, double *mu) {
-  switch (c->dpad) {
-    case 4: return ksx_launch<4, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
-    case 8: return ksx_launch<8, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
-    case 16: return ksx_launch<16, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
-    case 32: return ksx_launch<32, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
-    case 48: return ksx_launch<48, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
-    case 64: return ksx_launch<64, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
-    case 96: return ksx_launch<96, KERN>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
-    default: return b7_fail(c, B7_ERR_UNSUPPORTED, "covariance kernel: dpad %d is not a built class", c->dpad);
-  }
-}
-
-int ksx_dispatch(b7_ctx *c, dim3 grid, const double *xq, int64_t row0, int64_t Mtotal, int d, const ObsSet &o,
-                 const double *alpha, double amp, double meanc, double *out, double *mu) {
-  if (c->kernel == B7_KERNEL_MATERN52) return ksx_dispatch_k<B7_KERNEL_MATERN52>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
-  return ksx_dispatch_k<B7_KERNEL_ARDSE>(c, grid, xq, row0, Mtotal, d, o, alpha, amp, meanc, out, mu);
+  return ksx_for_class(c, "covariance kernel", [&](auto cls) {
+    using C = decltype(cls);
+    const size_t lds = ksx_lds_bytes<C::DPAD>();
+    auto kern = ksx_kernel<C::DPAD, C::KERN>;
+    // dynamic LDS above the 64 KiB default needs an explicit opt-in (gfx950 has 160 KiB per workgroup)
+    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, c->stream, xq, row0, Mtotal, d, c->dpad, o.w ? o.w : (const double *)c->w.p,
+                       o.zsc, o.zsh, alpha, amp, meanc, o.npad, out, mu, o.batch);
+    B7_HIP(c, hipGetLastError());
+    return B7_OK;
+  });
 }
 
 }  // namespace
@@ -398,18 +280,18 @@ int launch_prep_obs_aux(b7_ctx *c, const double *xobs, const double *ls_dev, int
 
 // K(Xq, Xobs-set) for an arbitrary observation set: rows x o.npad, no mean.
 int launch_k_generic(b7_ctx *c, const double *xq, int64_t rows, int64_t Mtotal, const ObsSet &o, double *out) {
-  if (rows % KQ || o.npad % 64) return b7_fail(c, B7_ERR_INVALID, "k_generic: extents not multiples of 64");
-  return ksx_dispatch(c, dim3((unsigned)(rows / KQ), 1), xq, 0, Mtotal, c->dfit, o, nullptr, c->amp, 0.0, out, nullptr);
+  if (rows % KSX_Q || o.npad % 64) return b7_fail(c, B7_ERR_INVALID, "k_generic: extents not multiples of 64");
+  return ksx_launch(c, dim3((unsigned)(rows / KSX_Q), 1), xq, 0, Mtotal, c->dfit, o, nullptr, c->amp, 0.0, out, nullptr);
 }
 
 int launch_ksx(b7_ctx *c, const FitSet &f, const double *xq, int64_t row0, int64_t rows, int64_t Mtotal, int d, double *ks,
                double *mu, int ycols) {
   PhaseScope ps(c, "ksx");
-  if (rows % KQ) return b7_fail(c, B7_ERR_INVALID, "ksx: rows %lld not a multiple of %d", (long long)rows, KQ);
+  if (rows % KSX_Q) return b7_fail(c, B7_ERR_INVALID, "ksx: rows %lld not a multiple of %d", (long long)rows, KSX_Q);
   if (ycols != 1) mu = nullptr;  // the multi-column mean is a GEMM of its own (launch_mean_multi)
   ObsSet o{f.zsc, f.zss, c->Npad};
   o.w = f.w;
-  return ksx_dispatch(c, dim3((unsigned)(rows / KQ), 1), xq, row0, Mtotal, d, o, mu ? f.alpha : nullptr, f.amp, f.mean, ks, mu);
+  return ksx_launch(c, dim3((unsigned)(rows / KSX_Q), 1), xq, row0, Mtotal, d, o, mu ? f.alpha : nullptr, f.amp, f.mean, ks, mu);
 }
 
 int launch_kxx(b7_ctx *c, double diag_add) {
@@ -417,9 +299,9 @@ int launch_kxx(b7_ctx *c, double diag_add) {
   const int Npad = c->Npad;
   // few query rows: split the observations over blockIdx.y so that the grid covers the chip
   int ny = 1;
-  while (ny < 16 && (Npad / 64) % (ny * 2) == 0 && (Npad / KQ) * ny < 2 * c->cus) ny *= 2;
+  while (ny < 16 && (Npad / 64) % (ny * 2) == 0 && (Npad / KSX_Q) * ny < 2 * c->cus) ny *= 2;
   const ObsSet o{(const double *)c->zsc.p, (const double *)c->zss.p, Npad};
-  B7_TRY(ksx_dispatch(c, dim3(Npad / KQ, ny), (const double *)c->xobs.p, 0, c->N, c->dfit, o, nullptr, c->amp, 0.0,
+  B7_TRY(ksx_launch(c, dim3(Npad / KSX_Q, ny), (const double *)c->xobs.p, 0, c->N, c->dfit, o, nullptr, c->amp, 0.0,
                       (double *)c->K.p, nullptr));
   int64_t total = (int64_t)Npad * Npad;
   hipLaunchKernelGGL(kxx_fix_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, (double *)c->K.p,
@@ -435,7 +317,7 @@ int launch_kxx(b7_ctx *c, double diag_add) {
 int launch_ksx_batch(b7_ctx *c, const FitSet &f, const double *xq, int64_t rows, int64_t Mtotal, double *ks, int64_t s_out,
                      double *mu, int64_t s_mu) {
   PhaseScope ps(c, "ksx");
-  if (rows % KQ) return b7_fail(c, B7_ERR_INVALID, "ksx: rows %lld not a multiple of %d", (long long)rows, KQ);
+  if (rows % KSX_Q) return b7_fail(c, B7_ERR_INVALID, "ksx: rows %lld not a multiple of %d", (long long)rows, KSX_Q);
   ObsSet o{f.zsc, f.zss, c->Npad};
   o.w = f.w;
   o.batch.s_w = FitSet::s_w(c->Npad, c->dpad);
@@ -446,7 +328,7 @@ int launch_ksx_batch(b7_ctx *c, const FitSet &f, const double *xq, int64_t rows,
   o.batch.s_alpha = FitSet::s_alpha(c->Npad, c->dpad);
   o.batch.s_mu = s_mu;
   o.batch.mean = f.mean_dev;
-  return ksx_dispatch(c, dim3((unsigned)(rows / KQ), 1, f.S), xq, 0, Mtotal, c->dfit, o, f.alpha, f.amp, 0.0, ks, mu);
+  return ksx_launch(c, dim3((unsigned)(rows / KSX_Q), 1, f.S), xq, 0, Mtotal, c->dfit, o, f.alpha, f.amp, 0.0, ks, mu);
 }
 
 int launch_kxx_batch(b7_ctx *c, int B, const double *ls_dev, const double *amp_dev, const double *noise_dev, double *w,
@@ -465,8 +347,8 @@ int launch_kxx_batch(b7_ctx *c, int B, const double *ls_dev, const double *amp_d
   o.batch.amp = amp_dev;
   // as launch_kxx: with few fits the observations are split over blockIdx.y so that the grid still covers the chip
   int ny = 1;
-  while (ny < 16 && (Npad / 64) % (ny * 2) == 0 && (Npad / KQ) * ny * B < 2 * c->cus) ny *= 2;
-  B7_TRY(ksx_dispatch(c, dim3(Npad / KQ, ny, B), (const double *)c->xobs.p, 0, c->N, d, o, nullptr, c->amp, 0.0, K, nullptr));
+  while (ny < 16 && (Npad / 64) % (ny * 2) == 0 && (Npad / KSX_Q) * ny * B < 2 * c->cus) ny *= 2;
+  B7_TRY(ksx_launch(c, dim3(Npad / KSX_Q, ny, B), (const double *)c->xobs.p, 0, c->N, d, o, nullptr, c->amp, 0.0, K, nullptr));
   const int64_t total = (int64_t)Npad * Npad;
   hipLaunchKernelGGL(kxx_fix_kernel, dim3((unsigned)((total + 255) / 256), B), dim3(256), 0, c->stream, K, c->N, Npad, 0.0,
                      noise_dev, total);

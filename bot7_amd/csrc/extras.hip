@@ -214,7 +214,6 @@ __global__ void __launch_bounds__(256)
 // (expm1 form below: no cancellation near zero).  The epilogue writes the z real feature columns (the padding columns of
 // the feature matrix are zeroed once, when it is allocated) and, when the head's weights m are given, the posterior mean
 // mean0 + phi . m of each input (models/dngo.lua:174's predictive mean; otherwise a second pass over the features).
-__constant__ double exp2_tab_blr[256];   // [0, 128): 2^(j/128);  [128, 256): 2^(j/128) - 1, correctly rounded
 
 // tanh|x| = t / (t + 2) with t = e^{2|x|} - 1:  n = rint(y 128/ln2) for y = 2|x| <= 45, r = y - n ln2/128, q = e^r - 1
 // (degree-5 Taylor, |r| <= ln2/256), s = 2^(n >> 7):  t = s T (1 + q) - 1 = fma(s T, q, s T - 1), with (T - 1) taken from
@@ -346,7 +345,7 @@ __global__ void __launch_bounds__(512)
     const int z = dims[n_layers];
     if (mvec)
       for (int k = tid; k < z; k += 512) rsm[lay.m_off + k] = mvec[k];
-    if (tid < 256) rsm[lay.tab_off + tid] = exp2_tab_blr[tid];
+    if (tid < 256) rsm[lay.tab_off + tid] = tid < 128 ? b7_exp2_tab_dev[tid] : b7_exp2m1_tab_dev[tid - 128];  // [0, 128): 2^(j/128);  [128, 256): 2^(j/128) - 1
   }
   __syncthreads();
   const double *tab = rsm + lay.tab_off;
@@ -620,16 +619,6 @@ int launch_append_finalize(b7_ctx *c, const double *krow, const double *lvec, co
   return B7_OK;
 }
 
-// 2^(j/128) and 2^(j/128) - 1 for tanh_fast, uploaded once per process and device
-static int ensure_blr_tables(b7_ctx *c) {
-  static bool done[64] = {false};
-  if (c->device < 64 && done[c->device]) return B7_OK;
-  B7_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(exp2_tab_blr), b7_exp2_tab, sizeof(b7_exp2_tab), 0));
-  B7_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(exp2_tab_blr), b7_exp2m1_tab, sizeof(b7_exp2m1_tab), sizeof(b7_exp2_tab)));
-  if (c->device < 64) done[c->device] = true;
-  return B7_OK;
-}
-
 // mvec (nullable, device, z entries) + mean0: also write mu[i] = mean0 + phi_i . mvec (only the resident-weights kernel does
 // that; *mean_done tells the caller whether it happened)
 int launch_mlp_forward_mean(b7_ctx *c, const double *X, int64_t M, int d, const double *net_dev, const int *dims,
@@ -670,7 +659,6 @@ int launch_mlp_forward_mean(b7_ctx *c, const double *X, int64_t M, int d, const 
     off += 8 * 16 * lay.as;
     const size_t lds = sizeof(double) * (size_t)off;
     if (lds <= 160 * 1024 && maxn <= 128) {
-      B7_TRY(ensure_blr_tables(c));
       const int64_t ntiles = (M + 15) / 16;
       int64_t blocks = (ntiles + 7) / 8;
       if (blocks > c->cus) blocks = c->cus;   // persistent: one block per CU stages the weights once

@@ -75,7 +75,6 @@ __global__ void __launch_bounds__(GS_THREADS) gp_small_kernel(GsArgs a, GsInline
 
 template <int MODE, bool TWO, int KERN>
 int gs_launch2(b7_ctx *c, const GsArgs &a, const double *hyp_host) {
-  B7_TRY(ensure_gs_table(c));
   const size_t lds = sizeof(double) * GS_LDS_DOUBLES;
   // the opt-in to > 64 KiB of dynamic LDS is per device: once per process AND device (a process may hold contexts on several)
   static bool attr_done[64] = {false};

@@ -1,7 +1,7 @@
 // The likelihood / fit body of the one-workgroup GP kernels, shared by gp_small.hip (gp_small_kernel: one evaluation per launch)
 // and slice.hip (slice_chain_kernel: the slice sampler's loop of evaluations inside one launch): layout constants, the K sub-tile
-// and block helpers, gs_body and the table upload.  Everything sits in an unnamed namespace: each translation unit has its own
-// copy (and its own exp2_tab_gs, uploaded by its own ensure_gs_table).  gp_small.hip's header comment describes the algorithm.
+// and block helpers, gs_body.  Everything sits in an unnamed namespace: each translation unit has its own
+// copy.  gp_small.hip's header comment describes the algorithm.
 #pragma once
 #include "b7_internal.h"
 #include "ksx_exp.h"
@@ -13,8 +13,6 @@
 
 namespace {
 using namespace b7diag;  // NB = 64, DLD, TLD, diag_core, diag_bystander
-
-__constant__ double exp2_tab_gs[128];  // b7_exp2_tab (ensure_gs_table)
 
 constexpr int OLD = 33;         // row stride of the observation image [128][OLD] (32 columns, zero padded)
 constexpr int BUF = NB * DLD;   // one 64 x 66 image
@@ -224,7 +222,7 @@ __device__ __forceinline__ void gs_body(const GsArgs a, const int b, const doubl
     w[tid] = tid < d ? 1.0 / lsv : 0.0;  // inv_ls = ones:cdiv(lenscale), utils/math.lua:72
   }
   if (tid < 128) {
-    tab[tid] = amp * exp2_tab_gs[tid];
+    tab[tid] = amp * b7_exp2_tab_dev[tid];
     r[tid] = tid < N ? a.y[tid] - mean : 0.0;
   }
   {
@@ -646,14 +644,6 @@ __device__ __forceinline__ void gs_body(const GsArgs a, const int b, const doubl
     if (a.resid && tid < npad) a.resid[(size_t)b * npad + tid] = r[tid];
   }
   GS_STAMP(13);
-}
-
-int ensure_gs_table(b7_ctx *c) {
-  static bool done[64] = {false};
-  if (c->device < 64 && done[c->device]) return B7_OK;
-  B7_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(exp2_tab_gs), b7_exp2_tab, sizeof(b7_exp2_tab)));
-  if (c->device < 64) done[c->device] = true;
-  return B7_OK;
 }
 
 }  // namespace

@@ -13,6 +13,8 @@
 //
 // kg_kernel is believer_kernel (batch.hip) with sixteen columns in w_j's place: the same slabs of 64 observations (32 for dpad >=
 // 48) double-buffered in LDS, the same argument (c - xs/2) - zs/2, the same epilogue function cov_nonpos4<KERN>, K* never stored.
+// It keeps a text of its own beside the slab walk of ksx_walk.h: written on the walk, its 32-row classes (dpad >= 48) came out with
+// one LDS read more per slab than this text (a paired read of W's rows split in two); only the dpad / covariance switch is shared.
 // OPERAND ORDER, fixed whatever the grid's size: the distance product takes the OBSERVATIONS as its A operand and the queries as
 // its B operand, so that a 16 x 16 tile of K* comes out as D[obs = lq + 4 r][query = lr] -- which is, register r by register r,
 // the A operand (row = query lr, k = lq) of the next product over the observations 16 t + 4 r + {0, 1, 2, 3}: four MFMAs per tile
@@ -35,10 +37,9 @@
 #include "b7_internal.h"
 #include "gemm_f64.h"
 #include "ksx_exp.h"
+#include "ksx_walk.h"
 
 namespace {
-
-__constant__ double exp2_tab_kg[128];  // b7_exp2_tab (ensure_kg_table)
 
 constexpr int KQ = 64;                 // query rows per block (16 per wave), as believer_kernel's BQ
 constexpr int KL = B7_KG_MAX_POINTS;   // lines beside the own one = columns of W = lanes of a row
@@ -153,7 +154,7 @@ __global__ void __launch_bounds__(256) kg_kernel(KgPass p, int d, int Npad, int 
   const int qrow = tid >> 2, qq4 = tid & 3;
   constexpr int half = DPAD >> 1;
 
-  if (tid < 128) stab[tid] = amp * exp2_tab_kg[tid];
+  if (tid < 128) stab[tid] = amp * b7_exp2_tab_dev[tid];
   {
     int64_t g = qbase + qrow;
     if (g > Mtotal - 1) g = Mtotal - 1;
@@ -308,44 +309,18 @@ size_t kg_lds_bytes(int dpad) {
   return sizeof(double) * (r0 + 2 * KO + 2 * KO * WST + KQ + 128 + KL * (dpad + 1) + KL);
 }
 
-int ensure_kg_table(b7_ctx *c) {
-  static bool done[64] = {false};
-  if (c->device < 64 && done[c->device]) return B7_OK;
-  B7_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(exp2_tab_kg), b7_exp2_tab, sizeof(b7_exp2_tab)));
-  if (c->device < 64) done[c->device] = true;
-  return B7_OK;
-}
-
-template <int DPAD, int KERN>
-int kg_launch(b7_ctx *c, int S, const KgPass &p, bool column) {
-  const size_t lds = kg_lds_bytes(DPAD);
-  auto kern = kg_kernel<DPAD, KERN>;
-  B7_TRY(ensure_kg_table(c));
-  B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t blocks = column ? c->Npad / KQ : (p.rows + KQ - 1) / KQ;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks, 1, S), dim3(256), lds, c->stream, p, c->dfit, c->Npad, c->N, column ? 1 : 0);
-  B7_HIP(c, hipGetLastError());
-  return B7_OK;
-}
-
-template <int KERN>
-int kg_dispatch(b7_ctx *c, int S, const KgPass &p, bool column) {
-  switch (c->dpad) {
-    case 4: return kg_launch<4, KERN>(c, S, p, column);
-    case 8: return kg_launch<8, KERN>(c, S, p, column);
-    case 16: return kg_launch<16, KERN>(c, S, p, column);
-    case 32: return kg_launch<32, KERN>(c, S, p, column);
-    case 48: return kg_launch<48, KERN>(c, S, p, column);
-    case 64: return kg_launch<64, KERN>(c, S, p, column);
-    case 96: return kg_launch<96, KERN>(c, S, p, column);
-    default: return b7_fail(c, B7_ERR_UNSUPPORTED, "knowledge-gradient kernel: dpad %d is not a built class", c->dpad);
-  }
-}
-
 int launch_kg(b7_ctx *c, int S, const KgPass &p, bool column) {
   PhaseScope ps(c, column ? "kg_cols" : "kg");
-  if (c->kernel == B7_KERNEL_MATERN52) return kg_dispatch<B7_KERNEL_MATERN52>(c, S, p, column);
-  return kg_dispatch<B7_KERNEL_ARDSE>(c, S, p, column);
+  return ksx_for_class(c, "knowledge-gradient kernel", [&](auto cls) {
+    using C = decltype(cls);
+    const size_t lds = kg_lds_bytes(C::DPAD);
+    auto kern = kg_kernel<C::DPAD, C::KERN>;
+    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t blocks = column ? c->Npad / KQ : (p.rows + KQ - 1) / KQ;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, 1, S), dim3(256), lds, c->stream, p, c->dfit, c->Npad, c->N, column ? 1 : 0);
+    B7_HIP(c, hipGetLastError());
+    return B7_OK;
+  });
 }
 
 // ---- the small kernels around it -------------------------------------------------------------------------------------------

@@ -26,8 +26,6 @@
 
 namespace {
 
-__constant__ double exp2_tab_kp[128];  // b7_exp2_tab (ensure_kp_table)
-
 constexpr int KP_THREADS = 512;  // eight waves share one LDS copy of a fit; one workgroup per CU (two waves per SIMD)
 
 struct KpArgs {
@@ -92,7 +90,7 @@ kpost_small_kernel(KpArgs a) {
       al[tid] = a.alpha[(size_t)s * npad + tid];
     }
     if (tid < DPAD) wv[tid] = a.w[(size_t)s * DPAD + tid];
-    if (tid < 128) tab[tid] = amp * exp2_tab_kp[tid];
+    if (tid < 128) tab[tid] = amp * b7_exp2_tab_dev[tid];
   }
   __syncthreads();
   const double var_add = a.var_with_noise ? noise : 0.0;
@@ -191,17 +189,8 @@ kpost_small_kernel(KpArgs a) {
   }
 }
 
-int ensure_kp_table(b7_ctx *c) {
-  static bool done[64] = {false};
-  if (c->device < 64 && done[c->device]) return B7_OK;
-  B7_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(exp2_tab_kp), b7_exp2_tab, sizeof(b7_exp2_tab)));
-  if (c->device < 64) done[c->device] = true;
-  return B7_OK;
-}
-
 template <int DPAD, int NT, int KERN>
 int kp_launch(b7_ctx *c, const KpArgs &a) {
-  B7_TRY(ensure_kp_table(c));
   const size_t lds = sizeof(double) * (size_t)kp_lds_doubles<DPAD>(NT);
   // the opt-in to > 64 KiB of dynamic LDS is per device: once per instantiation AND device (a process may hold contexts on several)
   static bool attr_done[64] = {false};

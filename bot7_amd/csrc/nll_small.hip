@@ -24,8 +24,6 @@
 namespace {
 using namespace b7diag;  // NB = 64, DLD, TLD, diag_core
 
-__constant__ double exp2_tab_small[128];  // b7_exp2_tab (ensure_small_table)
-
 constexpr int OLD = 33;  // row stride of the observation image [128][OLD] (32 columns, zero padded)
 constexpr int NLL_SMALL_LDS_DOUBLES = 128 * OLD + 3 * NB * DLD + 32 * TLD + 128 * 4 + 32 + 128 + 512;
 static_assert(128 * OLD <= NB * DLD, "the observation image is reused as the inverse's tile");
@@ -151,7 +149,7 @@ __global__ void __launch_bounds__(256)
   if (tid < 4) inf[tid] = 0;
   if (tid < 32) w[tid] = tid < d ? 1.0 / ls[tid] : 0.0;  // inv_ls = ones:cdiv(lenscale), utils/math.lua:72
   if (tid < 128) {
-    tab[tid] = amp * exp2_tab_small[tid];
+    tab[tid] = amp * b7_exp2_tab_dev[tid];
     r[tid] = tid < N ? y[tid] - mean : 0.0;
   }
   {
@@ -321,18 +319,9 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-int ensure_small_table(b7_ctx *c) {
-  static bool done[64] = {false};
-  if (c->device < 64 && done[c->device]) return B7_OK;
-  B7_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(exp2_tab_small), b7_exp2_tab, sizeof(b7_exp2_tab)));
-  if (c->device < 64) done[c->device] = true;
-  return B7_OK;
-}
-
 template <int KERN>
 int nll_small_launch(b7_ctx *c, int B, const double *hyp_dev, const double *hyp_host, double *terms_dev, int *info_dev,
                      unsigned *done_dev) {
-  B7_TRY(ensure_small_table(c));
   const size_t lds = sizeof(double) * NLL_SMALL_LDS_DOUBLES;
   // the opt-in to > 64 KiB of dynamic LDS is per device: once per process AND device (a process may hold contexts on several)
   static bool attr_done[64] = {false};

@@ -35,8 +35,6 @@
 
 namespace {
 
-__constant__ double exp2_tab_ref[128];  // b7_exp2_tab (ensure_ref_table)
-
 constexpr int RQ = 64;   // query columns of a launch set
 constexpr int RB = 64;   // observations per block
 constexpr int RLS = 65;  // LDS row stride of a staged 64 x 64 block of L^-1 (odd: conflict-free fragment reads)
@@ -55,7 +53,7 @@ __global__ void __launch_bounds__(256) refine_k_kernel(const double *__restrict_
   double *kt = kt_ + s * (int64_t)Npad * RQ, *gt = gt_ ? gt_ + s * (int64_t)Npad * RQ : nullptr;
   const double amp = par[2 * s];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lq = lane >> 4;
-  if (tid < 128) stab[tid] = amp * exp2_tab_ref[tid];
+  if (tid < 128) stab[tid] = amp * b7_exp2_tab_dev[tid];
   const int q = wave * 16 + lr;  // this lane's query column
   double hq = 0.0;               // xs/2 in ascending k, as the grid's kernels form it
   for (int k = 0; k < d; ++k) {
@@ -324,14 +322,6 @@ __global__ void __launch_bounds__(256) refine_init_kernel(RefState *__restrict__
   }
 }
 
-int ensure_ref_table(b7_ctx *c) {
-  static bool done[64] = {false};
-  if (c->device < 64 && done[c->device]) return B7_OK;
-  B7_HIP(c, hipMemcpyToSymbol(HIP_SYMBOL(exp2_tab_ref), b7_exp2_tab, sizeof(b7_exp2_tab)));
-  if (c->device < 64) done[c->device] = true;
-  return B7_OK;
-}
-
 // the workspace of 64 query columns against S fits, carved out of c->refine_ws
 struct RefWork {
   double *xq[2];               // [64][d], ping-pong
@@ -463,7 +453,6 @@ int b7_eval_nominate_refine(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score
   const int nparts = (int)std::min<int64_t>((c->M + 255) / 256, (int64_t)c->cus * 8);
   RefWork wk;
   B7_TRY(ref_work(c, S, nparts, &wk));
-  B7_TRY(ensure_ref_table(c));
   std::vector<double> par(2 * (size_t)S);
   for (int s = 0; s < S; ++s) par[2 * s] = hyps[s].amp, par[2 * s + 1] = hyps[s].mean;
   B7_HIP(c, hipMemcpyAsync(wk.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, c->stream));
@@ -584,7 +573,6 @@ int b7_gp_grad_at(b7_ctx *c, const double *X1, int64_t M1, double *mean, double 
   const int d = c->dfit;
   RefWork wk;
   B7_TRY(ref_work(c, 1, 1, &wk));
-  B7_TRY(ensure_ref_table(c));
   const FitSet fit = ctx_fit(c);
   const double par[2] = {fit.amp, fit.mean};
   B7_HIP(c, hipMemcpyAsync(wk.par, par, sizeof(par), hipMemcpyHostToDevice, c->stream));

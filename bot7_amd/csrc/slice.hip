@@ -252,7 +252,6 @@ __global__ void __launch_bounds__(GS_THREADS) slice_chain_kernel(GsArgs a, Slice
 
 template <bool TWO, int KERN>
 int slice_launch2(b7_ctx *c, const GsArgs &a, const SliceArgs &s, int C) {
-  B7_TRY(ensure_gs_table(c));
   const size_t lds = sizeof(double) * GS_LDS_DOUBLES;
   static bool attr_done[64] = {false};
   if (c->device >= 64 || !attr_done[c->device]) {
