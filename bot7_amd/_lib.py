@@ -21,6 +21,7 @@ SYMBOLS = [
     "b7_abi_version", "b7_create", "b7_destroy", "b7_last_error", "b7_device_info", "b7_sync", "b7_set_workspace",
     "b7_sobol_direction_numbers", "b7_grid_sobol", "b7_grid_random", "b7_grid_upload", "b7_grid_download", "b7_grid_shape", "b7_grid_remove", "b7_grid_remove_rows",
     "b7_grid_colrange", "b7_grid_apply_onesided", "b7_grid_random_torch", "b7_torch_rand",
+    "b7_grid_trust_region", "b7_tr_box", "b7_tr_init", "b7_tr_update",
     "b7_gp_default_opts", "b7_gp_set_opts", "b7_gp_set_kernel", "b7_gp_fit", "b7_gp_set_data", "b7_gp_fit_hyp", "b7_gp_predict_hyp", "b7_gp_nll_batch", "b7_gp_slice_sample", "b7_gp_slice_trace_enable", "b7_gp_slice_trace", "b7_chol", "b7_gp_predict", "b7_gp_predict_at", "b7_gp_fantasize", "b7_gp_append", "b7_gp_download",
     "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_mes", "b7_mes_set_levels", "b7_mes_last_ystar", "b7_mes_ystar", "b7_mes_compute", "b7_score_cb", "b7_score_finish",
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_eval_nominate_batch", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
@@ -51,6 +52,12 @@ class Bot7HipError(RuntimeError):
 class Hyp(C.Structure):
     _fields_ = [("lenscale_sq", C.POINTER(C.c_double)), ("amp", C.c_double), ("noise", C.c_double),
                 ("mean", C.c_double)]
+
+
+class TrState(C.Structure):   # b7_tr_state
+    _fields_ = [("length", C.c_double), ("length_init", C.c_double), ("length_min", C.c_double), ("length_max", C.c_double),
+                ("best", C.c_double), ("succ", C.c_int), ("fail", C.c_int), ("succ_tol", C.c_int), ("fail_tol", C.c_int),
+                ("restarts", C.c_int)]
 
 
 class ScoreSpec(C.Structure):
@@ -141,6 +148,10 @@ def load(which=None):
         "b7_grid_random": (i32, [vp, i64, i32, C.c_uint64, i64, vp, vp, vp]),
         "b7_grid_upload": (i32, [vp, vp, i64, i32]),
         "b7_grid_download": (i32, [vp, i64, i64, vp]),
+        "b7_grid_trust_region": (i32, [vp, vp, vp, vp, dbl, vp, C.c_uint64, i64]),
+        "b7_tr_box": (i32, [i32, i32, C.POINTER(Hyp), vp, dbl, vp, vp, vp, vp]),
+        "b7_tr_init": (i32, [C.POINTER(TrState), i32, i32, dbl, dbl, dbl, i32, i32]),
+        "b7_tr_update": (i32, [C.POINTER(TrState), vp, i32, C.POINTER(i32)]),
         "b7_grid_shape": (i32, [vp, C.POINTER(i64), C.POINTER(i32)]),
         "b7_grid_remove": (i32, [vp, i64, vp]),
         "b7_grid_remove_rows": (i32, [vp, vp, i64, vp]),
@@ -408,6 +419,16 @@ class Context(object):
         mx = None if maxes is None else _f64(maxes).ravel()
         ext = _f64(col_ext).ravel()
         self._ck(self._L.b7_grid_apply_onesided(self._h, _ptr(mn), _ptr(mx), _ptr(ext)))
+        self.grid_version += 1
+
+    def grid_trust_region(self, center, lo, hi, prob, shift=None, seed=0, row_offset=0):
+        """The resident grid of base points in [0, 1), mapped in place into a trust-region candidate set (b7_grid_trust_region)."""
+        M, d = self.grid_shape()
+        vecs = [None if v is None else _f64(v).ravel() for v in (center, lo, hi, shift)]
+        if M > 0 and any(v is not None and v.size != d for v in vecs):   # (without a grid the library answers B7_ERR_STATE)
+            raise Bot7HipError(-1, "grid_trust_region: center, lo, hi and shift have the grid's %d entries" % d)
+        self._ck(self._L.b7_grid_trust_region(self._h, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), float(prob), _ptr(vecs[3]),
+                                              int(seed) & (2 ** 64 - 1), int(row_offset)))
         self.grid_version += 1
 
     # ---- model
@@ -1435,6 +1456,52 @@ def comm_pick_winner(pairs):
     if rc != B7_OK:
         raise Bot7HipError(rc, "every shard is empty")
     return v.value, i.value
+
+
+def tr_box(hyps, center, length, mins, maxes):
+    """The trust region's box (lo, hi) around `center` from the hyper samples' ARD lengthscales: hyps as eval_nominate takes them
+    (dicts or (lenscale_sq, amp, noise, mean)), or bare lenscale_sq vectors -- only the lengthscales are read.  Host-only (b7_tr_box)."""
+    center, mins, maxes = _f64(center).ravel(), _f64(mins).ravel(), _f64(maxes).ravel()
+    d = center.size
+    if mins.size != d or maxes.size != d:
+        raise Bot7HipError(-1, "tr_box: center, mins and maxes have the same number of entries")
+    arr, keep = Context._pack_hyps([h if isinstance(h, (dict, tuple)) else (h, 1.0, 0.0, 0.0) for h in hyps], d)
+    lo, hi = np.empty(d), np.empty(d)
+    rc = load().b7_tr_box(d, len(keep), arr, _ptr(center), float(length), _ptr(mins), _ptr(maxes), _ptr(lo), _ptr(hi))
+    if rc != B7_OK:
+        raise Bot7HipError(rc, "tr_box: S >= 1, lenscale_sq > 0, maxes > mins, length > 0, all finite, and the center inside [mins, maxes]")
+    return lo, hi
+
+
+class TrustRegionState(object):
+    """The trust region's side length and the success / failure counters that resize it (b7_tr_state, b7_tr_init, b7_tr_update).
+    A parameter <= 0 (or None) takes the library's default."""
+
+    FIELDS = ("length", "length_init", "length_min", "length_max", "best", "succ", "fail", "succ_tol", "fail_tol", "restarts")
+
+    def __init__(self, d, q=1, length_init=None, length_min=None, length_max=None, succ_tol=None, fail_tol=None):
+        self._st, self.q = TrState(), int(q)
+        rc = load().b7_tr_init(C.byref(self._st), int(d), int(q), float(length_init or 0.0), float(length_min or 0.0),
+                               float(length_max or 0.0), int(succ_tol or 0), int(fail_tol or 0))
+        if rc != B7_OK:
+            raise Bot7HipError(rc, "tr_init: d >= 1, q >= 1, finite lengths with length_min <= length_init <= length_max")
+
+    def __getattr__(self, name):
+        if name in TrustRegionState.FIELDS:
+            return getattr(self._st, name)
+        raise AttributeError(name)
+
+    def update(self, y):
+        """One trial's responses (minimised) -> True when the region collapsed and the state restarted."""
+        y = _f64(y).ravel()
+        restart = C.c_int(0)
+        rc = load().b7_tr_update(C.byref(self._st), _ptr(y), y.size, C.byref(restart))
+        if rc != B7_OK:
+            raise Bot7HipError(rc, "tr_update: at least one response")
+        return bool(restart.value)
+
+    def as_dict(self):
+        return {k: getattr(self._st, k) for k in TrustRegionState.FIELDS}
 
 
 def pareto_front2(Y, ref):

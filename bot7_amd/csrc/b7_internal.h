@@ -73,9 +73,10 @@ struct PinnedBlock {
   alignas(4096) double fmin[256];     // f_min of several response columns on their way to the device (stage_fmin)
   alignas(4096) double vec[B7_MAX_D + 3];  // a small vector on its way to the device: a fit's lengthscales (the one-launch fit reads
                                            // amp, noise and mean behind them), a grid map's per-column shift / scale
+  alignas(4096) double tr[5 * B7_MAX_D];   // the trust-region map's center | lo | span | shift | hi on their way to the device
 };
 static_assert(offsetof(PinnedBlock, fit) == 0 && offsetof(PinnedBlock, best) == 2304 && offsetof(PinnedBlock, fmin) == 4096 &&
-                  offsetof(PinnedBlock, vec) == 8192 && sizeof(PinnedBlock) <= B7_PINNED_BYTES,
+                  offsetof(PinnedBlock, vec) == 8192 && offsetof(PinnedBlock, tr) == 12288 && sizeof(PinnedBlock) <= B7_PINNED_BYTES,
               "pinned block: kernels and copies address these slots");
 
 // c->scratch: 64 KiB of device memory, never regrown.
@@ -89,10 +90,11 @@ struct ScratchBlock {
   SobolTable sobol;                   // launch_sobol
   double minmax[2 * B7_MAX_D];        // a generated grid's mins | maxes (sobol.hip: upload_minmax)
   alignas(4096) double colvec[2 * B7_MAX_D];  // column minima | maxima out (b7_grid_colrange), a grid map's per-column vector in
+  double trvec[5 * B7_MAX_D];         // the trust-region map's center | lo | span | shift | hi, d entries each (trust_region.hip)
 };
 static_assert(offsetof(ScratchBlock, lenscale) == 0 && offsetof(ScratchBlock, fmin) == 2048 && offsetof(ScratchBlock, sobol) == 4096 &&
                   offsetof(ScratchBlock, minmax) == 4096 + sizeof(SobolTable) && offsetof(ScratchBlock, colvec) == 12288 &&
-                  sizeof(ScratchBlock) <= B7_SCRATCH_BYTES,
+                  offsetof(ScratchBlock, trvec) == 12288 + sizeof(double) * 2 * B7_MAX_D && sizeof(ScratchBlock) <= B7_SCRATCH_BYTES,
               "scratch block: the layout every earlier build used");
 
 constexpr int B7_ACC_NONE = 0, B7_ACC_LINEAR = 1, B7_ACC_LOG = 2;  // b7_ctx::acc_kind
@@ -396,6 +398,9 @@ int launch_remove_rows(b7_ctx *c, const double *src, double *dst, int64_t M, int
 int launch_colrange(b7_ctx *c, const double *grid, int64_t M, int d, double *out_dev);
 int launch_col_affine(b7_ctx *c, double *grid, int64_t M, int d, const double *v_dev, bool mul);
 int launch_gather_rows(b7_ctx *c, const double *src, double *out, const int64_t *idx0_dev, int64_t n, int d);
+// trust_region.hip: the map of b7_grid_trust_region over M x d base points in place; vec_dev = center | lo | span | shift | hi (d each)
+int launch_trust_region(b7_ctx *c, double *grid, int64_t M, int d, const double *vec_dev, bool rotate, double prob, uint64_t seed,
+                        int64_t row_offset);
 
 // covar.hip
 struct KBatchDesc {   // a batch of fits over the same observations: strides (doubles) per fit, per-fit amplitudes

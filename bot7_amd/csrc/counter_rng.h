@@ -17,6 +17,10 @@
 //                      4096 g + 128 + k  (k < D)     the uniform of right_k
 //                      4096 g + 256 + i  (i < 3840)  the uniform of shrink step i
 //     Nothing depends on C, U or how a run is split into calls: a draw is a function of (seed, chain, g).
+//   b7_grid_trust_region (trust_region.hip: trust_region_kernel)   g = row_offset + i is a row's GLOBAL number, d the grid's dims:
+//       key(seed, 0)   counter g d + k   the uniform of the mask of element (g, k): perturbed iff it is < prob        (counter_uniform)
+//       key(seed, 1)   counter g         the uniform u of the row's forced column f(g) = min(d - 1, (int)(u d))       (counter_uniform)
+//     Nothing depends on M or on how rows are split between calls: an element is a function of (seed, g, k).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

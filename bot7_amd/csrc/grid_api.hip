@@ -258,6 +258,41 @@ int b7_grid_apply_onesided(b7_ctx *c, const double *mins, const double *maxes, c
   return B7_OK;
 }
 
+int b7_grid_trust_region(b7_ctx *c, const double *center, const double *lo, const double *hi, double prob, const double *shift,
+                         uint64_t seed, int64_t row_offset) {
+  if (!c) return B7_ERR_INVALID;
+  B7_TRY(group_guard(c, "grid_trust_region"));
+  if (c->M <= 0) return b7_fail(c, B7_ERR_STATE, "grid_trust_region: no candidate grid on this context");
+  if (!center || !lo || !hi) return b7_fail(c, B7_ERR_INVALID, "grid_trust_region: center, lo or hi is NULL");
+  if (!(prob >= 0.0 && prob <= 1.0)) return b7_fail(c, B7_ERR_INVALID, "grid_trust_region: prob %g outside [0, 1]", prob);
+  if (row_offset < 0) return b7_fail(c, B7_ERR_INVALID, "grid_trust_region: row_offset %lld is negative", (long long)row_offset);
+  const int d = c->d;
+  for (int k = 0; k < d; ++k) {
+    if (!isfinite(center[k]) || !isfinite(lo[k]) || !isfinite(hi[k]) || (shift && !isfinite(shift[k])))
+      return b7_fail(c, B7_ERR_INVALID, "grid_trust_region: column %d has a non-finite entry", k);
+    if (lo[k] > hi[k]) return b7_fail(c, B7_ERR_INVALID, "grid_trust_region: column %d has lo %g > hi %g", k, lo[k], hi[k]);
+    if (center[k] < lo[k] || center[k] > hi[k])
+      return b7_fail(c, B7_ERR_INVALID, "grid_trust_region: column %d has its center %g outside [%g, %g]", k, center[k], lo[k], hi[k]);
+    if (shift && !(shift[k] >= 0.0 && shift[k] < 1.0))
+      return b7_fail(c, B7_ERR_INVALID, "grid_trust_region: column %d has shift %g outside [0, 1)", k, shift[k]);
+  }
+  B7_HIP(c, hipSetDevice(c->device));
+  double *stage = c->pinned->tr, *v_dev = b7_scratch(c)->trvec;
+  B7_HIP(c, hipStreamSynchronize(c->stream));  // nothing in flight reads the stage
+  for (int k = 0; k < d; ++k) {
+    stage[k] = center[k];
+    stage[d + k] = lo[k];
+    stage[2 * d + k] = hi[k] + (-lo[k]);  // the span as random_grid_kernel forms it
+    stage[3 * d + k] = shift ? shift[k] : 0.0;
+    stage[4 * d + k] = hi[k];
+  }
+  B7_HIP(c, hipMemcpyAsync(v_dev, stage, sizeof(double) * 5 * d, hipMemcpyHostToDevice, c->stream));
+  B7_TRY(launch_trust_region(c, cur_grid(c), c->M, d, v_dev, shift != nullptr, prob, seed, row_offset));
+  invalidate_predictions(c);
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  return B7_OK;
+}
+
 int b7_grid_upload(b7_ctx *c, const double *X, int64_t M, int d) {
   if (!c) return B7_ERR_INVALID;
   if (!X && M > 0) return b7_fail(c, B7_ERR_INVALID, "grid_upload: X is NULL");

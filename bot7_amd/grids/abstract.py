@@ -25,6 +25,41 @@ class DeviceGrid(np.ndarray):
         self.version = -1
 
 
+class ResidentGrid(object):
+    """A candidate grid that lives on the device only: the handle of a grid regenerated every trial (trust-region nomination),
+    which must never cross PCIe whole.  No host rows; ``row`` / ``rows`` download just the rows asked for (b7_grid_download).
+    ``version`` is the context's grid_version when the handle was made: a handle of a grid that has since changed is stale."""
+
+    def __init__(self, ctx, version, shape):
+        self.ctx, self.version, self.shape = ctx, int(version), (int(shape[0]), int(shape[1]))
+
+    def __len__(self):
+        return self.shape[0]
+
+    def _live(self):
+        if self.version != self.ctx.grid_version:
+            raise RuntimeError("ResidentGrid: the context's grid has changed since this handle was made (version %d, now %d)"
+                               % (self.version, self.ctx.grid_version))
+
+    def row(self, i1):
+        """Row i1 (1-based) as a vector of d entries."""
+        return self.rows([i1])[0]
+
+    def rows(self, idx1):
+        """The rows named by 1-based indices, in the order given -> len(idx1) x d."""
+        self._live()
+        out = np.empty((len(idx1), self.shape[1]), dtype=np.float64)
+        for j, i1 in enumerate(idx1):
+            if not 1 <= int(i1) <= self.shape[0]:
+                raise IndexError("ResidentGrid: row %d outside [1, %d]" % (int(i1), self.shape[0]))
+            out[j] = self.ctx.grid_download(int(i1) - 1, 1)[0]
+        return out
+
+    def __array__(self, *args, **kwargs):
+        raise TypeError("ResidentGrid: the grid lives on the device and has no host rows (%d x %d); fetch rows with .rows(idx1)"
+                        % self.shape)
+
+
 class abstract(object):
     """grid:__call__(config) -> self:generate(config or self.config) (grids/abstract.lua:20-23)."""
 

@@ -32,7 +32,7 @@ import numpy as np
 
 from .abstract import abstract
 from .._lib import KERNELS, default_context
-from ..grids.abstract import DeviceGrid
+from ..grids.abstract import DeviceGrid, ResidentGrid
 
 
 class gp_regressor(abstract):
@@ -472,7 +472,7 @@ class gp_regressor(abstract):
         return self.last_fit
 
     def _is_resident(self, X1):
-        return isinstance(X1, DeviceGrid) and X1.ctx is self.ctx and X1.shape[0] == self.ctx.grid_shape()[0] \
+        return isinstance(X1, (DeviceGrid, ResidentGrid)) and X1.ctx is self.ctx and X1.shape[0] == self.ctx.grid_shape()[0] \
             and getattr(X1, "version", -1) == self.ctx.grid_version
 
     @staticmethod

@@ -22,7 +22,7 @@ class abstract(object):
         self.config = self.configure(cache.get("config") or config or {})  # :26
         config = self.config
         self.candidates = cache.get("candidates")                 # :30
-        if self.candidates is None:
+        if self.candidates is None and not config["bot"].get("trust_region"):   # (a trust region makes its grid per trial, on the device)
             if config["bot"]["verbose"] > 1:
                 print("> Generating candidate grid...")
             self.candidates = Grids.registry[config["grid"]["type"]](config["grid"])()  # :35

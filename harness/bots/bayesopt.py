@@ -42,12 +42,21 @@ model-based trial both models sample their hypers, both contexts keep their post
 observations comes from pareto_front2 and the objective's context nominates (ehvi_nominate); the stolen row leaves both grids.
 ref = None recomputes the reference point every trial as the per-column maximum of the observations plus 10 % of the column's
 range (default_ref).  update_best / progress_report report the hypervolume and the front's size.  What is not built is refused
-by name (objectives_refusal)."""
+by name (objectives_refusal).
+
+config.bot.trust_region (ours; None = the reference's loop, untouched) is a dict of length_init / length_min / length_max /
+success_tolerance / failure_tolerance / perturb / base: TRUST-REGION nomination (TuRBO-1: Eriksson et al. 2019).  No grid is made
+up front; config.grid.size is the number of candidates per trial.  Per model-based trial the hyper samples are drawn on the
+observations since the last restart, the box around the best of them comes from tr_box, a fresh base grid ('sobol', rotated, or
+'random') is made on the device and mapped into the box (grid_trust_region), and the nomination goes through the branches above
+unchanged on a ResidentGrid handle; the nominees' rows are downloaded, nothing is stolen, and the q responses resize the box
+(TrustRegionState.update).  A restart moves the model's window, not the record.  self.tr_trace keeps a record per trial.  What is not
+built is refused by name (trust_region_refusal)."""
 import numpy as np
 
 from .abstract import abstract
 from .. import tensor as T
-from bot7_amd.grids.abstract import DeviceGrid
+from bot7_amd.grids.abstract import DeviceGrid, ResidentGrid
 from bot7_amd import models as Models
 from bot7_amd import scores as Scores
 
@@ -153,6 +162,65 @@ def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
     return None
 
 
+TR_BASES = ("sobol", "random")
+TR_KEYS = ("length_init", "length_min", "length_max", "success_tolerance", "failure_tolerance", "perturb", "base")
+BATCH_MAX = 16  # B7_BATCH_MAX
+
+
+def trust_region_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
+    """Why this configuration cannot nominate inside a trust region (what _run_trial_trust_region does not do, by name), or None."""
+    tr = config["bot"].get("trust_region")
+    if not tr:
+        return None
+    if config["bot"].get("refine"):
+        return "config.bot.trust_region with config.bot.refine: refinement inside a trust region is not built"
+    if config["bot"].get("constraints"):
+        return "config.bot.trust_region with config.bot.constraints: constraints inside a trust region are not built"
+    if config["bot"].get("objectives") or config["score"]["type"] == EHVI:
+        return "config.bot.trust_region with config.bot.objectives / %s: two objectives inside a trust region are not built" % EHVI
+    if sharded:
+        return "config.bot.trust_region over sharded candidates or a group: the sharded trust-region loop is not built"
+    if model_class == "bot7.models.dngo":
+        return "config.bot.trust_region with the dngo model: the box is shaped by a GP's ARD lengthscales"
+    unknown = sorted(set(tr) - set(TR_KEYS))
+    if unknown:
+        return "config.bot.trust_region with unknown entries %s: %s are read" % (", ".join(unknown), ", ".join(TR_KEYS))
+    base = tr.get("base", config["grid"].get("type", "sobol"))
+    if base not in TR_BASES:
+        return "config.bot.trust_region with base = %r: %s are built" % (base, ", ".join(TR_BASES))
+    if base == "sobol" and int(config["grid"]["dims"]) >= 40:
+        return "config.bot.trust_region with base = 'sobol' in %d dimensions: the sobol grid is built for fewer than 40 (base = 'random' takes any)" \
+            % int(config["grid"]["dims"])
+    q = int(config["bot"].get("batch", 1))
+    if q > BATCH_MAX:
+        return "config.bot.trust_region with config.bot.batch = %d: at most %d nominees per trial are built" % (q, BATCH_MAX)
+    if q > int(config["grid"]["size"]):
+        return "config.bot.trust_region with config.bot.batch = %d above config.grid.size = %d candidates per trial" % (q, int(config["grid"]["size"]))
+    if not 0.0 <= float(tr.get("perturb", 1.0)) <= 1.0:
+        return "config.bot.trust_region with perturb = %r: a probability" % (tr["perturb"],)
+    return None
+
+
+class _KeptHypers(object):
+    """The model as a nomination branch sees it during a trust-region trial: the trial's hyper samples were drawn before the box
+    could be made, so the branch's own draws (the burn-in call, then one sample_hypers + parse_hypers per sample) hand those out
+    again instead of advancing the sampler a second time.  Everything else is the model's."""
+
+    def __init__(self, model, hyps):
+        self._model, self._hyps, self._next = model, hyps, 0
+
+    def sample_hypers(self, *args):
+        return None
+
+    def parse_hypers(self, _vec):
+        hyp = self._hyps[self._next % len(self._hyps)]
+        self._next += 1
+        return hyp
+
+    def __getattr__(self, name):
+        return getattr(self._model, name)
+
+
 def split_objectives(responses):
     """The objective's rows [y1, y2] -> (Y1 N x 1, Y2 N x 1)."""
     R = np.asarray(responses, dtype=np.float64)
@@ -214,6 +282,10 @@ class bayesopt(abstract):
         self.last_scores = None
         self.constraints = None   # per constraint: threshold, model, ctx, grid (the DeviceGrid view of that context); set up on first use
         self.objective2 = None    # the second objective: model, ctx, grid (the DeviceGrid view of that context); set up on first use
+        self.tr_state = None      # the trust region's TrustRegionState; set up on the first trust-region trial
+        self.tr_start = 0         # the model's window: observations [tr_start:] are those since the last restart
+        self.tr_since = 0         # trials since the last restart (the first nInitial of them nominate at random)
+        self.tr_trace = []        # per trial: what it takes to regenerate the trial's grid and nominees
 
     def configure(self, config):
         config = super().configure(config)
@@ -239,6 +311,14 @@ class bayesopt(abstract):
             ref = obj.get("ref")
             config["bot"]["objectives"] = {"ref": None if ref is None else [float(ref[0]), float(ref[1])],
                                            "model": self._model_defaults(obj.get("model"), config["bot"]["nSamples"])}
+        config["bot"].setdefault("trust_region", None)  # ours: None, or a dict of TR_KEYS (_run_trial_trust_region)
+        if config["bot"]["trust_region"] is not None:
+            tr = dict(config["bot"]["trust_region"]) if isinstance(config["bot"]["trust_region"], dict) else {}
+            for key in TR_KEYS[:5]:
+                tr.setdefault(key, None)                # None: the library's default (b7_tr_init)
+            tr.setdefault("perturb", min(1.0, 20.0 / config["grid"]["dims"]))
+            tr.setdefault("base", config["grid"]["type"])
+            config["bot"]["trust_region"] = tr
         return config
 
     @staticmethod
@@ -634,6 +714,95 @@ class bayesopt(abstract):
         self.observed, self.pending = T.steal(self.observed, self.pending, [idx])  # :143-144
         return x, y
 
+    # ---- trust-region nomination (config.bot.trust_region) -------------------------------------------------------------------
+    def _trust_region(self):
+        """THE predicate: does this bot nominate inside a trust region."""
+        return self.config["bot"].get("trust_region") is not None
+
+    def _tr_base_grid(self, ctx, base, mins=None, maxes=None):
+        """A fresh base grid of config.grid.size rows, resident only -> what it takes to make it again.  Sobol: the sequence from
+        point 1 (the caller rotates it); random: a seed from the bot's generator."""
+        M, d = int(self.config["grid"]["size"]), int(self.config["grid"]["dims"])
+        if base == "sobol":
+            made = {"base": "sobol", "skip": 1}
+            ctx.grid_sobol(M, d, 1, mins, maxes, download=False)
+        else:
+            made = {"base": "random", "base_seed": int(self._rng.integers(0, 2 ** 63))}
+            ctx.grid_random(M, d, made["base_seed"], 0, mins, maxes, download=False)
+        return made
+
+    def nominate_trust_region(self):
+        """One trust-region trial's nominees (TuRBO-1: Eriksson et al., NeurIPS 2019) -> (rows q x d, the trial's trace record).
+        The first nInitial trials of a run and after a restart: random rows of a fresh global base grid.  Afterwards: the hyper
+        samples as _sample_hyps draws them, on the observations since the last restart; the box around the best of those
+        (tr_box); a fresh base grid mapped into it on the device (grid_trust_region); the nomination through the branch the
+        configuration names, on the ResidentGrid; the nominees' rows downloaded.  No row is removed: the grid is discarded."""
+        from bot7_amd import _lib
+        cfg, tr = self.config, self.config["bot"]["trust_region"]
+        q, d, M = int(cfg["bot"]["batch"]), int(cfg["grid"]["dims"]), int(cfg["grid"]["size"])
+        mins, maxes = np.asarray(cfg["grid"]["mins"], dtype=np.float64), np.asarray(cfg["grid"]["maxes"], dtype=np.float64)
+        ctx = self.model.ctx
+        if self.tr_state is None:
+            self.tr_state = _lib.TrustRegionState(d, q, tr["length_init"], tr["length_min"], tr["length_max"], tr["success_tolerance"],
+                                                  tr["failure_tolerance"])
+        rec = {"trial": self.nTrials, "length_before": self.tr_state.length, "center": None, "lo": None, "hi": None, "shift": None,
+               "map_seed": None, "prob": float(tr["perturb"]), "restart": False}
+        if self.tr_since < cfg["bot"]["nInitial"]:
+            made = self._tr_base_grid(ctx, tr["base"], mins, maxes)
+            grid = ResidentGrid(ctx, ctx.grid_version, (M, d))
+            if q == 1:
+                idx = [int(np.floor(self._rng.random() * grid.shape[0])) + 1]      # bots/bayesopt.lua:90-91 floor(rand*M)+1
+            else:
+                idx = [int(i) + 1 for i in self._rng.choice(grid.shape[0], size=q, replace=False)]
+            rec.update(made, kind="initial", index=idx)
+            return grid.rows(idx), rec
+        X_win, Y_win = self.observed[self.tr_start:], self.responses[self.tr_start:]
+        hyps = self._sample_hyps(self.model, X_win, Y_win)
+        col = np.where(np.isnan(Y_win[:, 0]), np.inf, Y_win[:, 0])                 # a NaN response never is the best
+        center = np.array(X_win[int(np.argmin(col))], dtype=np.float64)            # the best row since the restart (the first of equals)
+        lo, hi = _lib.tr_box(hyps, center, self.tr_state.length, mins, maxes)
+        made = self._tr_base_grid(ctx, tr["base"])
+        shift = self._rng.random(d) if tr["base"] == "sobol" else None             # a fresh Cranley-Patterson rotation per trial
+        seed = int(self._rng.integers(0, 2 ** 63))
+        ctx.grid_trust_region(center, lo, hi, tr["perturb"], shift=shift, seed=seed)
+        grid = ResidentGrid(ctx, ctx.grid_version, (M, d))
+        # the existing branches, unchanged: they see the window as the observations and the trial's hyper samples as their draws
+        kept = (self.observed, self.responses, self.model)
+        self.observed, self.responses, self.model = X_win, Y_win, _KeptHypers(self.model, hyps)
+        try:
+            if q > 1:
+                idx = self.nominate_batch(q, grid)
+            else:
+                idx = [int(self.eval(grid, want_scores=False)[2])]
+        finally:
+            self.observed, self.responses, self.model = kept
+        rec.update(made, kind="model", index=[int(i) for i in idx], center=center, lo=lo, hi=hi, shift=shift, map_seed=seed,
+                   hyps=hyps)
+        return grid.rows(idx), rec
+
+    def _run_trial_trust_region(self):
+        """bots/abstract.lua:112-152 with the candidates made per trial inside a trust region: nothing is stolen (the grid is
+        discarded), the q nominees are evaluated and observed (:124-144), the q responses resize the region (tr_update), and a
+        restart moves the model's window -- observed / responses / best stay the run's record."""
+        why = trust_region_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
+        if why:
+            raise NotImplementedError(why)
+        self.nTrials += 1
+        rows, rec = self.nominate_trust_region()                   # :117
+        ys = np.concatenate([np.asarray(self.objective(r), dtype=np.float64).reshape(1, -1) for r in rows], 0)   # :124
+        self.responses = ys if self.responses is None else np.concatenate([self.responses, ys], 0)
+        self.observed = rows if self.observed is None else np.concatenate([self.observed, rows], 0)            # :143-144
+        self.tr_since += 1
+        if self.model is not None and self.tr_since == self.config["bot"]["nInitial"]:
+            self.model.init(self.observed[self.tr_start:], self.responses[self.tr_start:])   # :147-149, on the window
+        restart = self.tr_state.update(ys[:, 0])
+        if restart:
+            self.tr_start, self.tr_since = self.observed.shape[0], 0
+        rec.update(length_after=self.tr_state.length, restart=restart, x=rows.copy(), y=ys.copy())
+        self.tr_trace.append(rec)
+        best = int(np.nanargmin(ys[:, 0])) if not np.isnan(ys[:, 0]).all() else 0
+        return rows[best], ys[best:best + 1]
+
     def run_trial(self):
         """bots/abstract.lua:112-152 with config.bot.batch nominees per trial: all of them are stolen from the candidates in one
         stable pass (:118), evaluated and observed (:124-144).  batch = 1 is the parent's loop, untouched."""
@@ -641,6 +810,8 @@ class bayesopt(abstract):
             why = kg_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
             if why:
                 raise NotImplementedError(why)
+        if self._trust_region():
+            return self._run_trial_trust_region()
         if self._objectives() or self.config["score"]["type"] == EHVI:
             return self._run_trial_objectives()
         if self._constrained():

@@ -91,6 +91,25 @@ int b7_torch_rand(uint64_t seed, int64_t n, int resolution, double *out);
 int b7_grid_colrange(b7_ctx *ctx, double *col_min, double *col_max);
 int b7_grid_apply_onesided(b7_ctx *ctx, const double *mins, const double *maxes, const double *col_ext);
 
+/* The trust-region map (TuRBO: Eriksson et al., NeurIPS 2019; no counterpart in the reference): maps the resident grid IN PLACE.
+ * Its entries are taken as base points u in [0, 1), as b7_grid_sobol / b7_grid_random / b7_grid_random_torch leave them without
+ * mins / maxes; the result is a candidate set inside the box [lo, hi] around `center`.  Per element (row i, column k), with
+ * g = row_offset + i, in this order:
+ *   rotation (Cranley-Patterson; only with `shift`, 0 <= shift[k] < 1):  t = u + shift[k]; if (t >= 1.0) t -= 1.0;
+ *   mask:   perturbed iff counter_uniform(counter_key(seed, 0), g d + k) < prob, or k == f(g),
+ *           f(g) = min(d - 1, (int)(counter_uniform(counter_key(seed, 1), g) * d))        (the generator of csrc/counter_rng.h)
+ *   value:  perturbed: x = t * (hi[k] + (-lo[k])); x = x + lo[k]  (two rounded operations), clamped into [lo[k], hi[k]];
+ *           otherwise x = center[k], bit for bit.
+ * Column f(g) of EVERY row is perturbed.  Eriksson et al. force a column only when the draw perturbed none of the row; here an
+ * element is a pure function of (seed, g, k), so nothing is reduced across a row and nothing depends on M or on how rows are split
+ * between calls: a shard passes its first row's global number as row_offset, as for b7_grid_random.
+ * Synchronous; drops predictions, accumulator, feasibility column and kept posterior as every grid change does.  A local call: a
+ * communicator of any size is no obstacle and nothing is exchanged.  B7_ERR_STATE: no grid; a member of a group.  B7_ERR_INVALID: a
+ * NULL center / lo / hi, a non-finite entry, lo[k] > hi[k], a center outside [lo, hi], prob outside [0, 1], a shift outside
+ * [0, 1), a negative row_offset.  Added without a change of B7_ABI_VERSION: the change is additive. */
+int b7_grid_trust_region(b7_ctx *ctx, const double *center /*d*/, const double *lo /*d*/, const double *hi /*d*/, double prob,
+                         const double *shift /*d, nullable*/, uint64_t seed, int64_t row_offset);
+
 /* A caller-made grid (cache.candidates, bots/abstract.lua:30). */
 int b7_grid_upload(b7_ctx *ctx, const double *X_hid, int64_t M, int d);
 int b7_grid_download(b7_ctx *ctx, int64_t row0 /*0-based*/, int64_t rows, double *out_host);
@@ -755,6 +774,34 @@ int b7_ehvi_compute(b7_ctx *ctx, const double *mu1, const double *var1, int S1, 
  * group.  B7_ERR_UNSUPPORTED: contexts on different devices.  No counterpart in the reference. */
 int b7_ehvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front /*P x 2*/, int P, const double *ref /*2*/, double *best_val,
                      int64_t *best_idx1);
+
+/* ---- trust-region nomination (TuRBO: Eriksson, Pearce, Gardner, Turner & Poloczek, NeurIPS 2019).  No counterpart in the
+ * reference.  Three host-only pieces (no context, no GPU) that both host languages share, and the device map b7_grid_trust_region
+ * (with the grids, above).
+ *
+ * b7_tr_box: the box around `center` from S hyper samples' ARD lengthscales.  With range_k = maxes_k - mins_k,
+ *   log r_k = (1/S) sum_s (1/2) log lenscale_sq[s][k] - log range_k      (geometric mean of the lengthscale relative to the range)
+ *   w_k = exp(log r_k - (1/d) sum_j log r_j)                              (prod w = 1: volume length^d prod range before clipping)
+ *   half_k = w_k length range_k / 2,   lo_k = max(mins_k, center_k - half_k),   hi_k = min(maxes_k, center_k + half_k).
+ * B7_ERR_INVALID: a NULL argument, d outside 1..96, S < 1, lenscale_sq <= 0 or non-finite, range <= 0, length <= 0 or non-finite,
+ * a center outside [mins, maxes]. */
+int b7_tr_box(int d, int S, const b7_hyp *hyps, const double *center /*d*/, double length, const double *mins /*d*/,
+              const double *maxes /*d*/, double *lo /*d*/, double *hi /*d*/);
+/* The box's side length and the counters that resize it.  best is NaN while unset (after init and after a restart). */
+typedef struct {
+  double length, length_init, length_min, length_max, best;
+  int succ, fail, succ_tol, fail_tol;
+  int restarts;
+} b7_tr_state;
+/* Defaults (Eriksson et al.'s), each selected by passing <= 0: length_init 0.8, length_min 2^-7, length_max 1.6, succ_tol 3,
+ * fail_tol ceil(max(4 / q, d / q)).  B7_ERR_INVALID: NULL, d < 1, q < 1, a NaN or infinite length, or not
+ * length_min <= length_init <= length_max. */
+int b7_tr_init(b7_tr_state *st, int d, int q, double length_init, double length_min, double length_max, int succ_tol, int fail_tol);
+/* One trial's q responses (minimised).  Success iff min y < best - 1e-3 |best|; a NaN never succeeds; the first update after init
+ * or a restart sets best and counts as a success.  Success: best updated, succ + 1, fail = 0; otherwise fail + 1, succ = 0.
+ * succ == succ_tol: length = min(2 length, length_max), counters zeroed; fail == fail_tol: length /= 2, counters zeroed.
+ * length < length_min: *restart_out = 1 (nullable; else 0), length = length_init, best unset, counters zeroed, restarts + 1. */
+int b7_tr_update(b7_tr_state *st, const double *y /*q*/, int q, int *restart_out);
 
 /* bayesopt:eval's DNGO branch + nominate as ONE call (bots/bayesopt.lua:65-66, :96 over models/dngo.lua:155-175):
  * b7_blr_fit_x(net, X0, Y0, ...) + b7_blr_basis(net, resident grid) + b7_blr_predict + the acquisition of `spec` (written,

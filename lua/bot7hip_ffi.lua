@@ -26,6 +26,7 @@ int b7_grid_random_torch(b7_ctx *ctx, int64_t size, int dims, uint64_t seed, int
 int b7_torch_rand(uint64_t seed, int64_t n, int resolution, double *out);
 int b7_grid_colrange(b7_ctx *ctx, double *col_min, double *col_max);
 int b7_grid_apply_onesided(b7_ctx *ctx, const double *mins, const double *maxes, const double *col_ext);
+int b7_grid_trust_region(b7_ctx *ctx, const double *center , const double *lo , const double *hi , double prob, const double *shift , uint64_t seed, int64_t row_offset);
 int b7_grid_upload(b7_ctx *ctx, const double *X_hid, int64_t M, int d);
 int b7_grid_download(b7_ctx *ctx, int64_t row0 , int64_t rows, double *out_host);
 int b7_grid_shape(b7_ctx *ctx, int64_t *M, int *d);
@@ -109,6 +110,10 @@ int b7_pareto_front2(const double *Y , int64_t n, const double *ref , double *fr
 int b7_hypervolume2(const double *front , int P, const double *ref , double *hv_out);
 int b7_ehvi_compute(b7_ctx *ctx, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2, const double *front , int P, const double *ref , int64_t M, double *out );
 int b7_ehvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front , int P, const double *ref , double *best_val, int64_t *best_idx1);
+int b7_tr_box(int d, int S, const b7_hyp *hyps, const double *center , double length, const double *mins , const double *maxes , double *lo , double *hi );
+typedef struct { double length, length_init, length_min, length_max, best; int succ, fail, succ_tol, fail_tol; int restarts; } b7_tr_state;
+int b7_tr_init(b7_tr_state *st, int d, int q, double length_init, double length_min, double length_max, int succ_tol, int fail_tol);
+int b7_tr_update(b7_tr_state *st, const double *y , int q, int *restart_out);
 int b7_blr_eval_nominate(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, double alpha_prec, double beta, double mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *jitter_used);
 int b7_blr_eval_nominate_marg(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *alpha_prec, const double *beta, const double *mean, const b7_score_spec *spec, int64_t global_row_offset, double *best_val, int64_t *best_idx1, double *nll_out, double *jitter_used);
 typedef struct b7_group b7_group;
@@ -269,8 +274,20 @@ function M.data(c) if c == nil then return nil end return torch.data(c) end
 M.resident = nil
 function M.set_resident(t) M.resident = {ptr = torch.data(t), rows = t:size(1), cols = t:size(2)} end
 function M.forget_resident() M.resident = nil end
+-- A grid that lives on the device ONLY (a trust-region trial's candidate set, made and mapped there: b7_grid_sobol /
+-- b7_grid_random without a download, b7_grid_trust_region): a handle with the tensor methods the bot's nominations use
+-- (size, dim) and no host rows.  It is "the resident grid" until anything else becomes it; rows come back through
+-- b7_grid_download.  The Python mirror is bot7_amd.grids.abstract.ResidentGrid.
+function M.resident_only(rows, cols)
+  local h = {resident_only = true, rows = rows, cols = cols}
+  function h:size(k) if k == 1 then return self.rows elseif k == 2 then return self.cols end return torch.LongStorage{self.rows, self.cols} end
+  function h:dim() return 2 end
+  M.resident = {handle = h, rows = rows, cols = cols}
+  return h
+end
 function M.is_resident(t)
   local r = M.resident
+  if type(t) == 'table' and t.resident_only then return r ~= nil and r.handle == t end
   return r ~= nil and torch.isTensor(t) and t:dim() == 2 and t:isContiguous() and r.rows == t:size(1)
          and r.cols == t:size(2) and r.ptr == torch.data(t)
 end

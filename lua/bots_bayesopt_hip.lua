@@ -260,14 +260,15 @@ end
 -- S hyper tables of `model` over (X_obs, Y_obs) as a b7_hyp array, sampled as bots/bayesopt.lua:68,73-75 does
 local function sample_hyps(model, X_obs, Y_obs, S, keep)
   model:sample_hypers(X_obs, Y_obs)                                          -- :68
-  local hyps = ffi.new('b7_hyp[?]', S)
+  local hyps, tabs = ffi.new('b7_hyp[?]', S), {}
   for s = 1, S do                                                            -- :73-75
     local hyp = model:parse_hypers(model:sample_hypers(X_obs, Y_obs, nil, nil, true))
     local ls  = hip.pin(hyp.lenscale_sq)
     keep[#keep + 1] = ls
     hyps[s-1].lenscale_sq, hyps[s-1].amp, hyps[s-1].noise, hyps[s-1].mean = hip.data(ls), hyp.amp, hyp.noise, hyp.mean
+    tabs[s] = hyp
   end
-  return hyps
+  return hyps, tabs   -- the array for the library, and the tables model:parse_hypers returned (a trust-region trial hands them out again)
 end
 
 -- fn() with the library's current context switched to a constraint's own, together with EVERY per-context cache bot7hip_ffi
@@ -441,10 +442,145 @@ function bot:nominate_objectives(candidates)
   return torch.LongTensor{self.objectives_idx}
 end
 
+-- ---- trust-region nomination (TuRBO-1: Eriksson, Pearce, Gardner, Turner & Poloczek, NeurIPS 2019; no original) --------------
+-- config.bot.trust_region = nil (the reference's loop, untouched) or a table {length_init, length_min, length_max,
+-- success_tolerance, failure_tolerance, perturb, base}; absent entries take the library's defaults (b7_tr_init), perturb
+-- min(1, 20 / d), base config.grid.type.  config.grid.size is the number of candidates per trial: the grid is made per trial on
+-- the device and never crosses to the host.  The box (b7_tr_box) and the counters that resize it (b7_tr_init, b7_tr_update) are
+-- the library's own, shared with harness/bots/bayesopt.py, which this mirrors.
+
+-- a fresh base grid of config.grid.size rows on the device, resident only; with mins / maxes mapped there by the generator
+local function tr_base_grid(self, rec, mins, maxes)
+  local M, d = self.config.grid.size, self.config.grid.dims
+  hip.forget_resident()
+  if rec.base == 'sobol' then   -- the sequence from point 1: the caller rotates it
+    rec.skip = 1
+    hip.check(hip.C.b7_grid_sobol(hip.ctx, M, d, 1, hip.data(mins), hip.data(maxes), nil))
+  else                          -- a seed from torch's generator
+    rec.base_seed = torch.random()
+    hip.check(hip.C.b7_grid_random(hip.ctx, M, d, ffi.new('uint64_t', rec.base_seed), 0, hip.data(mins), hip.data(maxes), nil))
+  end
+end
+
+-- rows idx (a LongTensor, 1-based) of the resident grid -> an idx:nElement() x d tensor; just those rows cross
+local function tr_rows(idx, d)
+  local out = torch.Tensor(idx:nElement(), d)
+  for k = 1, idx:nElement() do
+    local row = out:select(1, k)
+    hip.check(hip.C.b7_grid_download(hip.ctx, idx[k] - 1, 1, torch.data(row)))
+  end
+  return out
+end
+
+-- One trial's nominees -> (rows q x d, the trial's trace record).  The first nInitial trials of a run and after a restart:
+-- random rows of a fresh global base grid.  Afterwards: the hyper samples as sample_hyps draws them on the observations since the
+-- last restart, the box around the best of those, a fresh base grid mapped into it on the device, and the nomination through
+-- nominate_batch / nominate UNCHANGED on a resident-only handle -- they see the window as the observations and the trial's hyper
+-- samples as their own draws.  No row is removed: the grid is discarded.  One rank, no group, a gp_hip model; no refinement, no
+-- constraints, no second objective.
+function bot:nominate_trust_region()
+  local cfg, tr = self.config, self.config.bot.trust_region
+  assert(D.world == 1 and not hip.group, 'nominate_trust_region: one rank, no group (the sharded trust-region loop is not built)')
+  assert(not cfg.bot.refine, 'nominate_trust_region: config.bot.refine (refinement inside a trust region is not built)')
+  assert(not cfg.bot.constraints, 'nominate_trust_region: config.bot.constraints (constraints inside a trust region are not built)')
+  assert(not cfg.bot.objectives, 'nominate_trust_region: config.bot.objectives (two objectives inside a trust region are not built)')
+  local model, keep = self.model, {}
+  assert(torch.type(model) == 'bot7.models.gp_hip', 'nominate_trust_region: needs the gp_hip model (the box is shaped by ARD lengthscales)')
+  local q, d, M, S = cfg.bot.batch or 1, cfg.grid.dims, cfg.grid.size, cfg.bot.nSamples
+  local base = tr.base or cfg.grid.type or 'sobol'
+  assert(base == 'sobol' or base == 'random', 'nominate_trust_region: config.bot.trust_region.base is sobol or random')
+  assert(base ~= 'sobol' or d < 40, 'nominate_trust_region: the sobol base is built for fewer than 40 dimensions (base = random takes any)')
+  local mins, maxes = hip.pin(torch.Tensor(cfg.grid.mins)), hip.pin(torch.Tensor(cfg.grid.maxes))
+  if self.tr_state == nil then
+    self.tr_state = ffi.new('b7_tr_state[1]')
+    assert(hip.C.b7_tr_init(self.tr_state, d, q, tr.length_init or 0, tr.length_min or 0, tr.length_max or 0,
+                            tr.success_tolerance or 0, tr.failure_tolerance or 0) == 0,
+           'nominate_trust_region: length_min <= length_init <= length_max, all finite')
+    self.tr_start, self.tr_since, self.tr_trace = 0, 0, {}
+  end
+  local rec = {trial = self.nTrials, length_before = self.tr_state[0].length, base = base, prob = tr.perturb or math.min(1, 20 / d),
+               restart = false}
+  if self.tr_since < cfg.bot.nInitial then                                   -- bots/bayesopt.lua:90-91 on a fresh global grid
+    tr_base_grid(self, rec, mins, maxes)
+    hip.resident_only(M, d)
+    local idx
+    if q == 1 then idx = torch.rand(1):mul(M):long():add(1) else idx = torch.randperm(M):narrow(1, 1, q):long() end
+    rec.kind, rec.index = 'initial', idx
+    return tr_rows(idx, d), rec
+  end
+  local n = self.observed:size(1) - self.tr_start
+  local R = self.responses
+  if R:dim() == 1 then R = R:view(-1, 1) end
+  local X_win, Y_win = self.observed:narrow(1, self.tr_start + 1, n), R:narrow(1, self.tr_start + 1, n)
+  local hyps, tabs = sample_hyps(model, X_win, Y_win, S, keep)
+  local col, at, low = Y_win:select(2, 1), 1, math.huge                      -- the best row since the restart: the first of equals,
+  for k = 1, n do                                                            -- and a NaN response never is the best
+    if col[k] < low then at, low = k, col[k] end
+  end
+  local center = hip.pin(X_win:select(1, at):clone())
+  local lo, hi = torch.Tensor(d), torch.Tensor(d)
+  assert(hip.C.b7_tr_box(d, S, hyps, hip.data(center), self.tr_state[0].length, hip.data(mins), hip.data(maxes), hip.data(lo),
+                         hip.data(hi)) == 0, 'nominate_trust_region: b7_tr_box refused the hyper samples, the bounds or the center')
+  tr_base_grid(self, rec, nil, nil)
+  local shift = nil
+  if base == 'sobol' then shift = torch.rand(d) end                          -- a fresh Cranley-Patterson rotation per trial
+  rec.map_seed = torch.random()
+  hip.check(hip.C.b7_grid_trust_region(hip.ctx, hip.data(center), hip.data(lo), hip.data(hi), rec.prob, hip.data(shift),
+                                       ffi.new('uint64_t', rec.map_seed), 0))
+  local grid = hip.resident_only(M, d)
+  -- the existing nominations, unchanged: the window as the observations, the hyper samples above as their draws
+  local obs0, resp0, handed = self.observed, self.responses, 0
+  self.observed, self.responses = X_win, Y_win
+  model.sample_hypers = function() return nil end
+  model.parse_hypers  = function() handed = handed % S + 1; return tabs[handed] end
+  local ok, idx = pcall(function() return self:nominate_batch(q, grid) end)
+  model.sample_hypers, model.parse_hypers = nil, nil                         -- the class's methods again
+  self.observed, self.responses = obs0, resp0
+  if not ok then error(idx, 2) end
+  rec.kind, rec.index, rec.center, rec.lo, rec.hi, rec.shift, rec.hyps = 'model', idx, center, lo, hi, shift, tabs
+  return tr_rows(idx, d), rec
+end
+
+-- bots/abstract.lua:112-152 with the candidates made per trial inside the trust region: nothing is stolen, the q nominees are
+-- evaluated and observed (:124-144), their responses resize the region (b7_tr_update), and a restart moves the model's window
+-- (self.tr_start) -- observed / responses / best stay the run's record.  self.tr_trace keeps a record per trial.
+function bot:run_trial_trust_region()
+  self.nTrials = self.nTrials + 1                                            -- :114
+  local rows, rec = self:nominate_trust_region()                             -- :117
+  local q, ys = rows:size(1), nil
+  for k = 1, q do
+    local y = self.objective(rows:select(1, k))                              -- :124
+    if not torch.isTensor(y) then                                            -- :127-133
+      if type(y) == 'number' then y = torch.Tensor{{y}} elseif type(y) == 'table' then y = torch.Tensor(y) end
+    end
+    if y:dim() == 1 then y:resize(y:nElement(), 1) end                       -- :134
+    if ys == nil then ys = y else ys = ys:cat(y, 1) end
+  end
+  if self.responses == nil then self.responses = ys else self.responses = self.responses:cat(ys, 1) end   -- :137-141
+  if self.observed == nil then self.observed = rows else self.observed = self.observed:cat(rows, 1) end   -- :143-144
+  self.tr_since = self.tr_since + 1
+  if self.model and self.tr_since == self.config.bot.nInitial then           -- :147-149, on the window
+    local n = self.observed:size(1) - self.tr_start
+    self.model:init(self.observed:narrow(1, self.tr_start + 1, n), self.responses:narrow(1, self.tr_start + 1, n))
+  end
+  local yq = hip.pin(ys:select(2, 1))
+  local restart = ffi.new('int[1]')
+  assert(hip.C.b7_tr_update(self.tr_state, hip.data(yq), q, restart) == 0, 'run_trial_trust_region: b7_tr_update refused the responses')
+  if restart[0] == 1 then self.tr_start, self.tr_since = self.observed:size(1), 0 end
+  rec.length_after, rec.restart, rec.x, rec.y = self.tr_state[0].length, restart[0] == 1, rows, ys
+  self.tr_trace[#self.tr_trace + 1] = rec
+  local col, at, low = ys:select(2, 1), 1, math.huge
+  for k = 1, q do
+    if col[k] < low then at, low = k, col[k] end
+  end
+  return rows:select(1, at), ys:narrow(1, at, 1)
+end
+
 -- bots/abstract.lua:112-152 for candidates sharded one process per GPU.  Only line 118 differs: `idx` is 1-based in the
 -- union of the shards, so it must not index this rank's shard; dist_hip.commit returns the nominee on every rank and
 -- deletes the row where it lives.  With one rank (or a group) the parent's code is right as it stands.
 function bot:run_trial()
+  if self.config.bot.trust_region then return self:run_trial_trust_region() end   -- trust-region nomination: above
   if D.world == 1 then return parent.run_trial(self) end
   local utils = require('bot7.utils')
   self.nTrials = self.nTrials + 1                                            -- :114
