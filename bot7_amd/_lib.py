@@ -636,7 +636,8 @@ class Context(object):
         return mean, var
 
     def gp_fantasize(self, X_pend, nFantasies, seed=0, want_moments=False):
-        """nFantasies joint posterior draws at the pending points: P x nFantasies (+ mu_P, Sigma_P)."""
+        """nFantasies joint posterior draws at the pending points: P x nFantasies (+ mu_P, Sigma_P).  A draw depends on
+        nFantasies as well as on the seed: z(k, s) = counter_normal(seed, k * nFantasies + s)."""
         Xp = _f64(X_pend)
         if Xp.ndim == 1:
             Xp = Xp.reshape(1, -1)
