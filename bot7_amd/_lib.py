@@ -28,6 +28,7 @@ SYMBOLS = [
     "b7_ts_nominate", "b7_ts_last_paths", "b7_ts_last_draws", "b7_rff_compute",
     "b7_kg_nominate", "b7_kg_trace_enable", "b7_kg_last", "b7_kg_compute",
     "b7_eval_posterior", "b7_posterior_get", "b7_pareto_front2", "b7_hypervolume2", "b7_ehvi_compute", "b7_ehvi_nominate",
+    "b7_pareto_front3", "b7_nondominated_boxes3", "b7_hypervolume3", "b7_ehvi3_compute", "b7_ehvi3_nominate",
     "b7_refine_default_opts", "b7_eval_nominate_refine", "b7_refine_last", "b7_refine_shape", "b7_refine_trace_enable", "b7_refine_trace", "b7_gp_grad_at", "b7_score_grad_compute",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
@@ -41,6 +42,7 @@ SYMBOLS = [
 
 KG_MAX_POINTS = 16  # B7_KG_MAX_POINTS
 EHVI_PMAX, EHVI_SMAX, EHVI_SREG = 256, 32, 10  # B7_EHVI_PMAX (front points), B7_EHVI_SMAX (hyper samples per objective), B7_EHVI_SREG (of them in registers)
+EHVI3_PMAX = 256  # B7_EHVI3_PMAX (front points of three objectives)
 
 
 class Bot7HipError(RuntimeError):
@@ -209,6 +211,11 @@ def load(which=None):
         "b7_hypervolume2": (i32, [vp, i32, vp, C.POINTER(dbl)]),
         "b7_ehvi_compute": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, i64, vp]),
         "b7_ehvi_nominate": (i32, [vp, vp, vp, i32, vp, C.POINTER(dbl), C.POINTER(i64)]),
+        "b7_pareto_front3": (i32, [vp, i64, vp, vp, vp, C.POINTER(i32)]),
+        "b7_nondominated_boxes3": (i32, [vp, i32, vp, vp, C.POINTER(i32)]),
+        "b7_hypervolume3": (i32, [vp, i32, vp, C.POINTER(dbl)]),
+        "b7_ehvi3_compute": (i32, [vp, vp, vp, vp, vp, i32, vp, i64, vp]),
+        "b7_ehvi3_nominate": (i32, [vp, vp, vp, vp, i32, vp, C.POINTER(dbl), C.POINTER(i64)]),
         "b7_refine_default_opts": (i32, [C.POINTER(RefineOpts)]),
         "b7_eval_nominate_refine": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), C.POINTER(RefineOpts), C.POINTER(dbl),
                                           C.POINTER(i64), vp, C.POINTER(dbl), C.POINTER(i64), vp, vp]),
@@ -1212,6 +1219,40 @@ class Context(object):
         self._ck(self._L.b7_ehvi_nominate(self._h, other._h, _ptr(front), front.shape[0], _ptr(ref), C.byref(val), C.byref(idx)))
         return val.value, idx.value
 
+    # ---- three objectives: the expected hypervolume improvement over a box decomposition (csrc/ehvi3.hip)
+    def ehvi3_compute(self, mu, var, front, ref):
+        """The marginal three-objective expected hypervolume improvement on host arrays by the nomination's own kernels
+        (b7_ehvi3_compute): mu / var three arrays each, S_m x M of objective m, front P x 3 canonical (pareto_front3), ref
+        (r1, r2, r3) -> M scores."""
+        if len(mu) != 3 or len(var) != 3:
+            raise Bot7HipError(-1, "ehvi3_compute: mu and var hold one array per objective, three each")
+        mu, var = [np.atleast_2d(_f64(a)) for a in mu], [np.atleast_2d(_f64(a)) for a in var]
+        front, ref = _f64(front).reshape(-1, 3), _f64(ref).ravel()
+        M = mu[0].shape[1]
+        if any(v.shape != m.shape or m.shape[1] != M for m, v in zip(mu, var)) or ref.size != 3:
+            raise Bot7HipError(-1, "ehvi3_compute: mu[m] / var[m] S_m x M, front P x 3, ref 3")
+        pm = (C.c_void_p * 3)(*[a.ctypes.data for a in mu])
+        pv = (C.c_void_p * 3)(*[a.ctypes.data for a in var])
+        S = (C.c_int * 3)(*[a.shape[0] for a in mu])
+        out = np.empty(M, dtype=np.float64)
+        self._ck(self._L.b7_ehvi3_compute(self._h, pm, pv, S, _ptr(front), front.shape[0], _ptr(ref), M, _ptr(out)))
+        return out
+
+    def ehvi3_nominate(self, other2, other3, front, ref):
+        """The three-objective nomination (b7_ehvi3_nominate): this context holds objective 1's kept posterior (eval_posterior),
+        other2 / other3 those of objectives 2 and 3 (contexts may coincide).  All must hold the same grid rows: the caller's
+        contract, only the row count is checked.  The marginal score stays in this context's accumulator (score_finish(1,
+        download=True) reads it).  Returns (value, 1-based index); no grid is modified."""
+        for o in (other2, other3):
+            if not isinstance(o, Context) or o._L is not self._L:
+                raise Bot7HipError(-1, "ehvi3_nominate: other2 and other3 must be Contexts of the same library")
+        front, ref = _f64(front).reshape(-1, 3), _f64(ref).ravel()
+        if ref.size != 3:
+            raise Bot7HipError(-1, "ehvi3_nominate: ref has three entries")
+        val, idx = C.c_double(), C.c_int64()
+        self._ck(self._L.b7_ehvi3_nominate(self._h, other2._h, other3._h, _ptr(front), front.shape[0], _ptr(ref), C.byref(val), C.byref(idx)))
+        return val.value, idx.value
+
     def rff_compute(self, X, omega, phase, W):
         """cos(X omega' + phase) W on host arrays (b7_rff_compute): X M1 x d, omega F x d, phase F, W F x q -> M1 x q."""
         X, omega, phase, W = _f64(X), _f64(omega), _f64(phase).ravel(), _f64(W)
@@ -1532,6 +1573,52 @@ def hypervolume2(front, ref):
     if rc != B7_OK:
         raise Bot7HipError(rc, "hypervolume2: the front is not canonical (strictly inside a finite reference box, the first objective "
                                "strictly ascending, the second strictly descending)")
+    return hv.value
+
+
+def pareto_front3(Y, ref):
+    """The canonical front of n rows of three responses (minimised) under the reference point ref = (r1, r2, r3): rows with a
+    non-finite entry or not strictly inside the box dropped, dominated rows dropped, of equal rows the lowest kept, sorted by (third,
+    first, second) objective.  Returns (front P x 3, rows P: each point's 1-based source row).  Host-only (b7_pareto_front3); more
+    than EHVI3_PMAX points raise."""
+    Y, ref = _f64(Y).reshape(-1, 3), _f64(ref).ravel()
+    if ref.size != 3:
+        raise Bot7HipError(-1, "pareto_front3: ref has three entries")
+    cap = max(1, min(Y.shape[0], EHVI3_PMAX))
+    front, rows, P = np.empty((cap, 3), dtype=np.float64), np.zeros(cap, dtype=np.int64), C.c_int()
+    rc = load().b7_pareto_front3(_ptr(Y), Y.shape[0], _ptr(ref), _ptr(front), _ptr(rows), C.byref(P))
+    if rc != B7_OK:
+        raise Bot7HipError(rc, "pareto_front3: a front of %d points (at most %d are built)" % (P.value, EHVI3_PMAX) if P.value > EHVI3_PMAX
+                           else "pareto_front3: the reference point must be finite")
+    return front[:P.value].copy(), rows[:P.value].copy()
+
+
+_CANONICAL3 = ("the front is not canonical (strictly inside a finite reference box, mutually non-dominated, strictly ascending by the "
+               "third, then the first, then the second objective, at most %d points)" % EHVI3_PMAX)
+
+
+def nondominated_boxes3(front, ref):
+    """The region no point of a canonical front (pareto_front3) dominates, inside (-inf, ref], as disjoint boxes B x 5: l1, u1, l2, u2,
+    u3 (the lower edge in the third objective is -inf; -inf is a legal l1 / l2).  Host-only (b7_nondominated_boxes3)."""
+    front, ref = _f64(front).reshape(-1, 3), _f64(ref).ravel()
+    if ref.size != 3:
+        raise Bot7HipError(-1, "nondominated_boxes3: ref has three entries")
+    boxes, B = np.empty((3 * front.shape[0] + 1, 5), dtype=np.float64), C.c_int()
+    rc = load().b7_nondominated_boxes3(_ptr(front), front.shape[0], _ptr(ref), _ptr(boxes), C.byref(B))
+    if rc != B7_OK:
+        raise Bot7HipError(rc, "nondominated_boxes3: " + _CANONICAL3)
+    return boxes[:B.value].copy()
+
+
+def hypervolume3(front, ref):
+    """The volume a canonical front (pareto_front3) dominates inside the reference box.  Host-only (b7_hypervolume3)."""
+    front, ref = _f64(front).reshape(-1, 3), _f64(ref).ravel()
+    if ref.size != 3:
+        raise Bot7HipError(-1, "hypervolume3: ref has three entries")
+    hv = C.c_double()
+    rc = load().b7_hypervolume3(_ptr(front), front.shape[0], _ptr(ref), C.byref(hv))
+    if rc != B7_OK:
+        raise Bot7HipError(rc, "hypervolume3: " + _CANONICAL3)
     return hv.value
 
 

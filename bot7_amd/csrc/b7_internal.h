@@ -286,6 +286,11 @@ struct b7_ctx {
   DevBuf ehvi_front; // a_1 .. a_P, r1 | r2, b_1 .. b_P: 2 (P + 1) doubles as the kernel reads them
   DevBuf ehvi_user;
   hipEvent_t ev_ehvi[2] = {nullptr, nullptr};  // b7_ehvi_nominate: the other context's stream -> this one, and back (created on first use)
+  // ---- b7_ehvi3_* (ehvi3.hip): three objectives over the same kept posteriors
+  DevBuf ehvi3_front;  // the cuts of the three objectives (3 (PMAX + 1) doubles), then the boxes as five table rows each (ints)
+  DevBuf ehvi3_table;  // T [rows][C] of one chunk of C candidates, then the row-class flags [3][C] (ints)
+  DevBuf ehvi3_user;   // b7_ehvi3_compute's staging, apart from the kept posterior
+  hipEvent_t ev_ehvi3[3] = {nullptr, nullptr, nullptr};  // b7_ehvi3_nominate: the second / third context's stream -> this one, and back
   DevBuf feat;   // DNGO basis features of the resident grid: Mfeat x Npad (zero-padded columns)
   size_t feat_zeroed_bytes = 0;  // how much of `feat` was zeroed when it was laid out for feat_z columns
   int feat_z = -1;

@@ -197,7 +197,7 @@ void b7_destroy(b7_ctx *c) {
                    &c->bLinv, &c->balpha, &c->bmu, &c->bvar, &c->ticket, &c->bel, &c->belvec, &c->ystar, &c->mes_ticket, &c->mes_user,
                    &c->ts_paths, &c->ts_draw, &c->ts_work, &c->ts_user, &c->slice_trace, &c->slice_state, &c->refine_ws, &c->refine_trace, &c->refine_user,
                    &c->feas, &c->feas_stage, &c->kg, &c->kgvec, &c->kg_slopes, &c->kg_user,
-                   &c->post, &c->ehvi_front, &c->ehvi_user};
+                   &c->post, &c->ehvi_front, &c->ehvi_user, &c->ehvi3_front, &c->ehvi3_table, &c->ehvi3_user};
   for (auto &kv : c->pjobs_cache) b7_release(kv.second.buf);
   for (DevBuf *b : all) b7_release(*b);
   if (c->tev_init)
@@ -216,6 +216,8 @@ void b7_destroy(b7_ctx *c) {
   for (hipEvent_t e : c->ev_feas)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_ehvi)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_ehvi3)
     if (e) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(c->stream);
   delete c;

@@ -22,7 +22,8 @@
 // conflict, no barrier -- a lane reads only what it wrote), up to B7_EHVI_SMAX per objective: (3 x1 + 2 x2) 512 bytes of dynamic LDS
 // for x1 / x2 samples beyond the registers, 56320 at most.  The summation order is the same on both sides of the limit.
 //
-// Out of scope, refused by name where it can be asked for: more than two objectives, correlated objectives / multi-task GPs, a
+// Out of scope, refused by name where it can be asked for: more than two objectives here (three through ehvi3.hip's b7_ehvi3_*, four
+// and more nowhere), correlated objectives / multi-task GPs, a
 // log-space EHVI, batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
 // ParEGO-style scalarisation.
 #pragma clang fp contract(off)

@@ -8,7 +8,14 @@ dominates inside a reference box (both objectives minimised; Emmerich, Yang & De
 over the strips of the canonical front (a_k, b_k) (bot7_amd._lib.pareto_front2), marginalised exactly over the hyper samples of TWO
 independent models, one per objective.  It needs two posteriors, which one accumulator's (mean, variance) pair does not carry:
 each model's context keeps its posterior (Context.eval_posterior) and the bot calls Context.ehvi_nominate in place of its eval +
-arg-max.  One GPU, two objectives, independent GP models only."""
+arg-max.  One GPU, independent GP models only.
+
+With THREE objectives (nominate's `other` a pair of contexts) the strips have no counterpart; the region no front point dominates is
+cut into boxes [l_b, u_b] first (bot7_amd._lib.nondominated_boxes3) and
+
+    EHVI(x) = sum_b prod_m [Psi_m(u_bm) - Psi_m(l_bm)],    Psi(-inf) = 0,
+
+marginalised exactly, box by box and objective by objective, by Context.ehvi3_nominate.  Four or more objectives are not built."""
 from .abstract import abstract
 
 
@@ -30,5 +37,12 @@ class expected_hypervolume_improvement(abstract):
 
     def nominate(self, ctx, other, front, ref, config=None):
         """(value, 1-based nominee) over the kept posteriors of ctx (objective 1) and other (objective 2) (Context.eval_posterior on
-        each first), the canonical front P x 2 and the reference point (r1, r2) (Context.ehvi_nominate)."""
+        each first), the canonical front P x 2 and the reference point (r1, r2) (Context.ehvi_nominate).  `other` may be a pair
+        (objective 2's context, objective 3's): three objectives, front P x 3, ref (r1, r2, r3) (Context.ehvi3_nominate)."""
+        if isinstance(other, (tuple, list)):
+            # THREE objectives: other = (objective 2's context, objective 3's), front P x 3 (bot7_amd._lib.pareto_front3), ref
+            # (r1, r2, r3): the sum over the boxes of the non-dominated region (Context.ehvi3_nominate)
+            if len(other) != 2:
+                raise NotImplementedError("expected_hypervolume_improvement: %d objectives (two and three are built)" % (1 + len(other)))
+            return ctx.ehvi3_nominate(other[0], other[1], front, ref)
         return ctx.ehvi_nominate(other, front, ref)

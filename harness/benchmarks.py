@@ -71,5 +71,14 @@ def two_spheres(X):
     return np.stack([((X - 0.25) ** 2).sum(1), ((X - 0.75) ** 2).sum(1)], axis=1)
 
 
+def three_spheres(X):
+    """A THREE-OBJECTIVE toy (no counterpart in benchmarks/), any dims: rows [y1, y2, y3] = (|x - a|^2, |x - b|^2, |x - c|^2) with
+    a = 0.25 * 1, b = 0.5 * 1 and c = 0.75 * 1, all minimised.  The three centres lie on one line, so the Pareto set is their convex
+    hull, the segment between a and c: off the diagonal every distance shrinks under projection onto it, and beyond either end moving
+    to the end lowers all three (config.bot.objectives = {"ref": ..., "models": [..., ...]})."""
+    X = _rows(X)
+    return np.stack([((X - 0.25) ** 2).sum(1), ((X - 0.5) ** 2).sum(1), ((X - 0.75) ** 2).sum(1)], axis=1)
+
+
 registry = {"braninhoo": braninhoo, "hartmann6": hartmann6, "ackley": ackley, "rastrigin": rastrigin, "gardner1": gardner1,
-            "two_spheres": two_spheres}
+            "two_spheres": two_spheres, "three_spheres": three_spheres}

@@ -43,6 +43,11 @@ observations comes from pareto_front2 and the objective's context nominates (ehv
 ref = None recomputes the reference point every trial as the per-column maximum of the observations plus 10 % of the column's
 range (default_ref).  update_best / progress_report report the hypervolume and the front's size.  What is not built is refused
 by name (objectives_refusal).
+config.bot.objectives = {"ref": [r1, r2, r3] | None, "models": [{...}, {...}]} means THREE objectives: the objective returns a row
+[y1, y2, y3], the two further gp_regressors -- each with a context and sampler state of its own -- see columns 1 and 2, the front
+comes from pareto_front3 and the objective's context nominates over the boxes of the non-dominated region (ehvi3_nominate); the
+stolen row leaves all three grids; the reports carry hypervolume3.  Four or more objectives, and with three also trust regions,
+are refused by name (objectives3_refusal).
 
 config.bot.trust_region (ours; None = the reference's loop, untouched) is a dict of length_init / length_min / length_max /
 success_tolerance / failure_tolerance / perturb / base: TRUST-REGION nomination (TuRBO-1: Eriksson et al. 2019).  No grid is made
@@ -145,6 +150,8 @@ def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
         if kind == EHVI:
             return "%s without config.bot.objectives: the score needs two objectives, each with a model of its own" % EHVI
         return None
+    if "models" in obj:
+        return objectives3_refusal(config, model_class, sharded)
     if int(config["bot"].get("batch", 1)) > 1:
         return "config.bot.objectives with config.bot.batch > 1: two-objective batches are not built"
     if config["bot"].get("refine"):
@@ -159,6 +166,33 @@ def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
         return "config.bot.objectives with %s: only %s is built" % (kind, EHVI)
     if (obj.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
         return "config.bot.objectives with the %s model: the second objective is modelled by a gp_regressor" % obj["model"]["type"]
+    return None
+
+
+def objectives3_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
+    """Why this configuration cannot nominate for three objectives (what b7_ehvi3_nominate does not do, by name), or None."""
+    kind = config["score"]["type"]
+    models = config["bot"]["objectives"].get("models") or []
+    if len(models) != 2:
+        return "config.bot.objectives with %d models: models holds the second and the third objective's (four or more objectives are not built)" \
+            % len(models)
+    if int(config["bot"].get("batch", 1)) > 1:
+        return "config.bot.objectives with config.bot.batch > 1: three-objective batches are not built"
+    if config["bot"].get("refine"):
+        return "config.bot.objectives with config.bot.refine: refinement of a three-objective nominee is not built"
+    if config["bot"].get("constraints"):
+        return "config.bot.objectives with config.bot.constraints: constraints combined with objectives are not built"
+    if config["bot"].get("trust_region"):
+        return "config.bot.objectives with config.bot.trust_region: three objectives inside a trust region are not built"
+    if sharded:
+        return "config.bot.objectives over sharded candidates: three objectives over a sharded grid are not built"
+    if model_class == "bot7.models.dngo":
+        return "config.bot.objectives with the dngo model: the Bayesian-linear head keeps no posterior for further objectives"
+    if kind != EHVI:
+        return "config.bot.objectives with %s: only %s is built" % (kind, EHVI)
+    for m in models:
+        if (m or {}).get("type", "gp_regressor") != "gp_regressor":
+            return "config.bot.objectives with the %s model: the second and third objectives are modelled by a gp_regressor" % m["type"]
     return None
 
 
@@ -230,12 +264,22 @@ def split_objectives(responses):
     return np.ascontiguousarray(R[:, :1]), np.ascontiguousarray(R[:, 1:2])
 
 
+def split_objectives3(responses):
+    """The objective's rows [y1, y2, y3] -> (Y1 N x 1, Y2 N x 1, Y3 N x 1)."""
+    R = np.asarray(responses, dtype=np.float64)
+    R = R.reshape(-1, 3) if R.ndim < 2 else R
+    if R.shape[1] != 3:
+        raise ValueError("config.bot.objectives: with two further models the objective must return rows of 3 columns [y1, y2, y3], got %d" % R.shape[1])
+    return tuple(np.ascontiguousarray(R[:, k:k + 1]) for k in range(3))
+
+
 def default_ref(responses):
     """The reference point when config.bot.objectives.ref is None: per column the maximum of the observations plus 10 % of the
     column's range (the common nadir heuristic; a column without a range takes 10 % of max(|maximum|, 1) instead).  Rows with a NaN
     take no part."""
-    Y1, Y2 = split_objectives(responses)
-    R = np.concatenate([Y1, Y2], axis=1)
+    R = np.asarray(responses, dtype=np.float64)
+    three = R.ndim == 2 and R.shape[1] == 3      # (rows of three objectives: split_objectives3; anything else is judged as two)
+    R = np.concatenate(split_objectives3(responses) if three else split_objectives(responses), axis=1)
     R = R[~np.isnan(R).any(axis=1)]
     hi, lo = R.max(axis=0), R.min(axis=0)
     span = np.where(hi > lo, hi - lo, np.maximum(np.abs(hi), 1.0))
@@ -282,6 +326,7 @@ class bayesopt(abstract):
         self.last_scores = None
         self.constraints = None   # per constraint: threshold, model, ctx, grid (the DeviceGrid view of that context); set up on first use
         self.objective2 = None    # the second objective: model, ctx, grid (the DeviceGrid view of that context); set up on first use
+        self.objectives23 = None  # three objectives: the second and the third, each as objective2 is; set up on first use
         self.tr_state = None      # the trust region's TrustRegionState; set up on the first trust-region trial
         self.tr_start = 0         # the model's window: observations [tr_start:] are those since the last restart
         self.tr_since = 0         # trials since the last restart (the first nInitial of them nominate at random)
@@ -306,7 +351,13 @@ class bayesopt(abstract):
                                              "model": self._model_defaults(c.get("model"), config["bot"]["nSamples"])}
                                             for c in config["bot"]["constraints"]]
         config["bot"].setdefault("objectives", None)    # ours: None, or {"ref": [r1, r2] | None, "model": {...}} (nominate_objectives)
-        if config["bot"]["objectives"] is not None:
+        if config["bot"]["objectives"] is not None and "models" in config["bot"]["objectives"]:
+            # THREE objectives: {"ref": [r1, r2, r3] | None, "models": [{...}, {...}]}, the second and the third objective's models
+            obj = dict(config["bot"]["objectives"])
+            ref = obj.get("ref")
+            config["bot"]["objectives"] = {"ref": None if ref is None else [float(r) for r in ref],
+                                           "models": [self._model_defaults(m, config["bot"]["nSamples"]) for m in (obj.get("models") or [])]}
+        elif config["bot"]["objectives"] is not None:
             obj = dict(config["bot"]["objectives"])
             ref = obj.get("ref")
             config["bot"]["objectives"] = {"ref": None if ref is None else [float(ref[0]), float(ref[1])],
@@ -642,6 +693,8 @@ class bayesopt(abstract):
         why = self._objectives_refusal()
         if why:
             raise NotImplementedError(why)
+        if self._objectives3():
+            return self._run_trial_objectives3()
         self.nTrials += 1
         idx = self.nominate_objectives()                           # :117
         self._steal_candidate(idx)                                 # :118
@@ -661,10 +714,90 @@ class bayesopt(abstract):
             self._objectives_setup()["model"].init(self.observed, Y2)
         return nominee, y
 
+    # ---- three objectives (config.bot.objectives = {"ref", "models": [m2, m3]}) ------------------------------------------------
+    def _objectives3(self):
+        """Does this bot nominate for THREE objectives: config.bot.objectives carries "models" (two of them) in place of "model"."""
+        return self._objectives() and "models" in self.config["bot"]["objectives"]
+
+    def _objectives3_setup(self):
+        """For the second and the third objective each a GP model with a context (same device) and sampler state of its own."""
+        if self.objectives23 is None:
+            from bot7_amd import Context
+            self.objectives23 = []
+            for mcfg in self.config["bot"]["objectives"]["models"]:
+                ctx = Context(self.model.ctx.device_id)
+                self.objectives23.append({"ctx": ctx, "grid": None, "model": Models.registry[mcfg["type"]](mcfg, context=ctx)})
+        return self.objectives23
+
+    def nominate_objectives3(self, candidates=None):
+        """The three-objective nominee -> 1-based index into the candidates as they stand: nominate_objectives with a third column,
+        a third model and context, the front from pareto_front3 and the nomination by ehvi3_nominate (the exact expected
+        hypervolume improvement over the boxes of the non-dominated region, marginalised over the three models' samples).
+        self.last_objectives keeps what the call used ("hyps" a list of three)."""
+        from bot7_amd import _lib
+        cand = self.candidates if candidates is None else candidates
+        why = self._objectives_refusal()
+        if why:
+            raise NotImplementedError(why)
+        if self.nTrials <= self.config["bot"]["nInitial"]:        # :90-91 floor(rand*M)+1
+            return int(np.floor(self._rng.random() * cand.shape[0])) + 1
+        others = self._objectives3_setup()
+        X_obs, model = self.observed, self.model
+        Ys = split_objectives3(self.responses)
+        ref = self.objectives_ref()
+        front, rows = _lib.pareto_front3(self.responses, ref)     # P = 0 while nothing observed lies inside the box
+        host = np.asarray(cand, dtype=np.float64)
+        hyps = [self._sample_hyps(model, X_obs, Ys[0])] + [self._sample_hyps(o["model"], X_obs, Y) for o, Y in zip(others, Ys[1:])]
+        model.stage(X_obs, Ys[0], cand)
+        model.ctx.eval_posterior(hyps[0])
+        for o, Y, h in zip(others, Ys[1:], hyps[1:]):
+            if o["grid"] is None or o["grid"].version != o["ctx"].grid_version or not np.array_equal(np.asarray(o["grid"]), host):
+                o["ctx"].grid_upload(host)
+                o["grid"] = DeviceGrid(host, o["ctx"], o["ctx"].grid_version)
+            o["model"].stage(X_obs, Y, o["grid"])
+            o["ctx"].eval_posterior(h)
+        val, idx = self.score.nominate(model.ctx, (others[0]["ctx"], others[1]["ctx"]), front, ref)
+        self.last_scores = None
+        self.last_objectives = {"hyps": hyps, "ref": np.array(ref, dtype=np.float64), "front": front, "rows": rows,
+                                "value": val, "index": int(idx)}
+        return int(idx)
+
+    def _run_trial_objectives3(self):
+        """_run_trial_objectives with three columns: the stolen row leaves the second and the third context's resident grid too."""
+        self.nTrials += 1
+        idx = self.nominate_objectives3()                          # :117
+        self._steal_candidate(idx)                                 # :118
+        for o in self.objectives23 or ():
+            if o["grid"] is not None and o["grid"].version == o["ctx"].grid_version:
+                o["ctx"].grid_remove(idx)
+                o["grid"] = DeviceGrid(np.asarray(self.candidates), o["ctx"], o["ctx"].grid_version)
+        k = self.pending.shape[0]
+        nominee = self.pending[k - 1]
+        y = np.asarray(self.objective(nominee), dtype=np.float64).reshape(1, -1)   # :124
+        split_objectives3(y)                                       # (the shape check)
+        self.responses = y if self.responses is None else np.concatenate([self.responses, y], 0)
+        self.observed, self.pending = T.steal(self.observed, self.pending, [k])  # :143-144
+        if self.model is not None and self.nTrials == self.config["bot"]["nInitial"]:
+            Ys = split_objectives3(self.responses)
+            self.model.init(self.observed, Ys[0])                  # :147-149
+            for o, Y in zip(self._objectives3_setup(), Ys[1:]):
+                o["model"].init(self.observed, Y)
+        return nominee, y
+
     def update_best(self, x, y):
         """bots/abstract.lua:171-177; under constraints the best is the best FEASIBLE trial (column 0 among the rows with c_k <= t_k);
         under two objectives there is no single best: best["front"] / ["rows"] are the front of all trials so far under this
-        trial's reference point, best["hv"] the area it dominates, best["t"] the last trial that entered the front."""
+        trial's reference point, best["hv"] the area it dominates, best["t"] the last trial that entered the front; under three
+        objectives the same with pareto_front3 and hypervolume3 (best["hv"] a volume)."""
+        if self._objectives3():
+            from bot7_amd import _lib
+            ref = self.objectives_ref()
+            front, rows = _lib.pareto_front3(self.responses, ref)
+            self.best["ref"], self.best["front"], self.best["rows"] = ref, front, rows
+            self.best["hv"] = _lib.hypervolume3(front, ref)
+            if self.nTrials in rows:
+                self.best["t"], self.best["x"], self.best["y"] = self.nTrials, x, np.asarray(y, dtype=np.float64).reshape(1, -1)
+            return
         if self._objectives():
             from bot7_amd import _lib
             ref = self.objectives_ref()
@@ -682,6 +815,12 @@ class bayesopt(abstract):
             self.best["t"], self.best["x"], self.best["y"] = self.nTrials, x, y
 
     def progress_report(self, t, x, y):
+        if self._objectives3():
+            if self.config["bot"]["verbose"] > 0 and t % self.config["bot"]["msg_freq"] == 0:
+                yy = np.ravel(y)
+                print("trial %4d  y = (%.8g, %.8g, %.8g)  hypervolume3 = %-14.8g front of %d (last entry: trial %d)" %
+                      (t, float(yy[0]), float(yy[1]), float(yy[2]), self.best.get("hv", 0.0), len(self.best.get("front", ())), self.best["t"]))
+            return
         if self._objectives():
             if self.config["bot"]["verbose"] > 0 and t % self.config["bot"]["msg_freq"] == 0:
                 yy = np.ravel(y)

@@ -731,7 +731,8 @@ int b7_kg_compute(b7_ctx *ctx, int64_t M1, int L, const double *alpha /*M1 x L*/
  * otherwise the score is finite and >= 0 (as long as no a - mu overflows), P = 0 included: Psi1(r1) Psi2(r2).
  * Limits: P <= B7_EHVI_PMAX; S1, S2 in 1..B7_EHVI_SMAX.  The first B7_EHVI_SREG samples of each objective are held in registers
  * across the strips, the rest in LDS.
- * Not built, each refused by name where it can be asked for: more than two objectives, correlated objectives / multi-task GPs, a
+ * Not built, each refused by name where it can be asked for: more than two objectives by these entry points (three only through
+ * b7_ehvi3_* below, four and more nowhere), correlated objectives / multi-task GPs, a
  * log-space EHVI, batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
  * ParEGO-style scalarisation.  Added without a change of B7_ABI_VERSION: the change is additive. */
 #define B7_EHVI_PMAX 256
@@ -774,6 +775,62 @@ int b7_ehvi_compute(b7_ctx *ctx, const double *mu1, const double *var1, int S1, 
  * group.  B7_ERR_UNSUPPORTED: contexts on different devices.  No counterpart in the reference. */
 int b7_ehvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front /*P x 2*/, int P, const double *ref /*2*/, double *best_val,
                      int64_t *best_idx1);
+
+/* THREE OBJECTIVES: the exact EHVI over a box decomposition.  No counterpart in the reference.  All objectives are MINIMISED;
+ * ref = (r1, r2, r3).  A CANONICAL FRONT here is P points, finite, strictly inside the reference box, mutually non-dominated, sorted
+ * strictly ascending by (third, first, second) objective, stored P x 3 row-major.  Two non-dominated points may share a coordinate in
+ * ONE objective.  The region that no front point dominates, inside (-inf, r], is cut into disjoint boxes [l_b, u_b], every l_b3 = -inf
+ * (b7_nondominated_boxes3).  With independent posteriors and Psi as above,
+ *   EHVI = sum_b prod_m [Psi_m(u_bm) - Psi_m(l_bm)],   Psi(-inf) = 0,
+ * and the marginal over S1 x S2 x S3 hyper samples (independent chains) factorises box by box and objective by objective:
+ *   T_m(c) = (1/S_m) sum_s Psi(c; mu_ms, sigma_ms),  T_m(-inf) = 0,
+ *   score  = sum_b max(T_1(u_b1) - T_1(l_b1), 0) max(T_2(u_b2) - T_2(l_b2), 0) T_3(u_b3),
+ * exact, no random numbers, every term non-negative; the dominated volume is never subtracted from the box's.  Fixed order: s ascending
+ * within a T, each T divided once by its sample count; the boxes in the decomposition's order, ((d1 d2) T_3) added to the running sum;
+ * one rounded operation per operator, Psi's arithmetic as above.  T_m is evaluated once per distinct cut (the front's coordinates and
+ * r_m, at most P + 1 per objective) into a table of sum_m (cuts_m + 1) doubles per candidate, which a second kernel walks box by box;
+ * the candidates are cut into chunks so that the table stays within min(b7_set_workspace's bytes, 256 MiB), and a row's bits do not depend
+ * on the chunking.
+ * Row classes: any mu or var NaN, or any var < 0, in any objective: NaN; otherwise the score is finite and >= 0, P = 0 included:
+ * T_1(r1) T_2(r2) T_3(r3).  Limits: P <= B7_EHVI3_PMAX; S1, S2, S3 in 1..B7_EHVI_SMAX.
+ * Not built, each refused by name where it can be asked for: four or more objectives, correlated objectives / multi-task GPs, a
+ * log-space EHVI, batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
+ * trust regions.  Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_EHVI3_PMAX 256
+/* Host-only (no context, no GPU): the canonical front of n rows of three responses, Y n x 3.  Rows with a non-finite entry and rows
+ * not strictly inside the reference box are dropped, dominated rows are dropped, of equal rows the lowest stays; the rest sorted by
+ * (third, first, second) objective.  front_out: room for min(n, B7_EHVI3_PMAX) points (P x 3); rows1_out (nullable, same count): each
+ * point's 1-based source row.  B7_ERR_INVALID: a NULL argument, n < 0, a non-finite ref, or a front of more than B7_EHVI3_PMAX points
+ * (nothing is written but *P_out, the count).  No counterpart in the reference. */
+int b7_pareto_front3(const double *Y /*n x 3*/, int64_t n, const double *ref /*3*/, double *front_out, int64_t *rows1_out, int *P_out);
+/* Host-only: the non-dominated region of a canonical front inside (-inf, ref] as B disjoint boxes, each l1, u1, l2, u2, u3 (the lower
+ * edge in the third objective is -inf throughout; -inf is a legal l1 / l2 too).  Deterministic: the front is swept in its order over
+ * the two-dimensional staircase of the projections seen so far; a point's projection newly dominates a part of [a, r1] x [b, .], cut
+ * into vertical rectangles at the staircase points it passes, each extended to (-inf, c]; the |F| + 1 strips of the final staircase
+ * extended to (-inf, r3] follow.  B = 2P + 1 in general position, fewer with tied coordinates; boxes_out: room for 3P + 1 boxes is
+ * always enough.  B7_ERR_INVALID: a NULL argument, P outside 0..B7_EHVI3_PMAX, a front that is not canonical.
+ * No counterpart in the reference. */
+int b7_nondominated_boxes3(const double *front /*P x 3*/, int P, const double *ref /*3*/, double *boxes_out /*B x 5*/, int *B_out);
+/* Host-only: the volume dominated by a canonical front inside the reference box, as the sum over the slabs between consecutive
+ * distinct third coordinates (the last up to r3) of the two-dimensional area dominated by the points at or below the slab, times the
+ * slab's height; all terms positive; P = 0: 0.  B7_ERR_INVALID for a front that is not canonical.  No counterpart in the reference. */
+int b7_hypervolume3(const double *front /*P x 3*/, int P, const double *ref /*3*/, double *hv_out);
+/* The score alone on host arrays, by the nomination's own kernels: mu[m] / var[m] S[m] x M of objective m = 0, 1, 2, out M.
+ * B7_ERR_INVALID: a front that is not canonical or longer than B7_EHVI3_PMAX, a non-finite ref, an S[m] outside 1..B7_EHVI_SMAX, NULL
+ * arguments.  No counterpart in the reference. */
+int b7_ehvi3_compute(b7_ctx *ctx, const double *const *mu /*3*/, const double *const *var /*3*/, const int *S /*3*/,
+                     const double *front /*P x 3*/, int P, const double *ref /*3*/, int64_t M, double *out /*M*/);
+/* The nomination: ctx holds objective 1's kept posterior (b7_eval_posterior), other2 objective 2's, other3 objective 3's; the contexts
+ * may coincide.  All on the same device with the same number of grid rows -- that the rows are the same is the caller's contract; the
+ * streams are ordered by events both ways, as b7_ehvi_nominate orders them.  The marginal score is written to ctx's accumulator (a
+ * linear one, already divided: b7_score_finish(1) downloads it), the nominee is its score:max(1) by b7_eval_nominate's rule.  No grid
+ * is modified, the other contexts' posteriors are only read.  Deterministic: the same call twice gives the same bits, and a row's value
+ * does not depend on how many rows the grid has.
+ * B7_ERR_INVALID: a front that is not canonical or longer than B7_EHVI3_PMAX, a non-finite ref, a kept posterior of more than
+ * B7_EHVI_SMAX samples, different row counts, NULL arguments.  B7_ERR_STATE: no kept posterior on one of the three, a member of a
+ * group.  B7_ERR_UNSUPPORTED: contexts on different devices.  No counterpart in the reference. */
+int b7_ehvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const double *front /*P x 3*/, int P, const double *ref /*3*/,
+                      double *best_val, int64_t *best_idx1);
 
 /* ---- trust-region nomination (TuRBO: Eriksson, Pearce, Gardner, Turner & Poloczek, NeurIPS 2019).  No counterpart in the
  * reference.  Three host-only pieces (no context, no GPU) that both host languages share, and the device map b7_grid_trust_region

@@ -110,6 +110,11 @@ int b7_pareto_front2(const double *Y , int64_t n, const double *ref , double *fr
 int b7_hypervolume2(const double *front , int P, const double *ref , double *hv_out);
 int b7_ehvi_compute(b7_ctx *ctx, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2, const double *front , int P, const double *ref , int64_t M, double *out );
 int b7_ehvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front , int P, const double *ref , double *best_val, int64_t *best_idx1);
+int b7_pareto_front3(const double *Y , int64_t n, const double *ref , double *front_out, int64_t *rows1_out, int *P_out);
+int b7_nondominated_boxes3(const double *front , int P, const double *ref , double *boxes_out , int *B_out);
+int b7_hypervolume3(const double *front , int P, const double *ref , double *hv_out);
+int b7_ehvi3_compute(b7_ctx *ctx, const double *const *mu , const double *const *var , const int *S , const double *front , int P, const double *ref , int64_t M, double *out );
+int b7_ehvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const double *front , int P, const double *ref , double *best_val, int64_t *best_idx1);
 int b7_tr_box(int d, int S, const b7_hyp *hyps, const double *center , double length, const double *mins , const double *maxes , double *lo , double *hi );
 typedef struct { double length, length_init, length_min, length_max, best; int succ, fail, succ_tol, fail_tol; int restarts; } b7_tr_state;
 int b7_tr_init(b7_tr_state *st, int d, int q, double length_init, double length_min, double length_max, int succ_tol, int fail_tol);
@@ -193,6 +198,7 @@ M.KG_MAX_POINTS = 16
 M.EHVI_PMAX = 256
 M.EHVI_SMAX = 32
 M.EHVI_SREG = 10
+M.EHVI3_PMAX = 256
 M.MAX_TIMERS = 16
 -- END generated constants
 

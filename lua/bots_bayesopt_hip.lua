@@ -380,6 +380,7 @@ function bot:nominate_objectives(candidates)
   local candidates = candidates or self.candidates
   assert(D.world == 1 and not hip.group, 'nominate_objectives: one rank, no group (two objectives over a sharded grid are not built)')
   local obj = assert(self.config.bot.objectives, 'nominate_objectives: config.bot.objectives is not set')
+  if obj.models then return self:nominate_objectives3(candidates) end       -- {ref, models = {m2, m3}}: three objectives, below
   assert((self.config.bot.batch or 1) == 1, 'nominate_objectives: config.bot.batch > 1 (two-objective batches are not built)')
   assert(not self.config.bot.refine, 'nominate_objectives: config.bot.refine (refinement of a two-objective nominee is not built)')
   assert(not self.config.bot.constraints, 'nominate_objectives: config.bot.constraints (constraints combined with objectives are not built)')
@@ -432,6 +433,87 @@ function bot:nominate_objectives(candidates)
   end)
   local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
   hip.check(hip.C.b7_ehvi_nominate(hip.ctx, o2.ctx, front, P[0], hip.data(ref), v, i))
+  for s = 0, S - 1 do
+    if jit[s] > 0 then   -- the reference's warning text, utils/math.lua:210-212
+      print(string.format('Warning: utils.math.chol succeeded in factorizing the\ninput matrix after applying a jitter of %.2e', jit[s]))
+    end
+  end
+  self.best_score = v[0]
+  self.objectives_idx = tonumber(i[0])   -- what the driver steals next: follow_steal
+  return torch.LongTensor{self.objectives_idx}
+end
+
+-- THREE-OBJECTIVE nomination (b7_ehvi3_nominate; no counterpart in the reference): config.bot.objectives = {ref = {r1, r2, r3} | nil,
+-- models = {{...}, {...}}}; the objective returns a row {y1, y2, y3}, all minimised.  The bot's own model sees column 1,
+-- self.objectives23[k] = {model (a gp_hip), ctx (a context of its own)}, set up on first use, columns 2 and 3.  Per model-based trial
+-- the three models sample their hypers and the three contexts keep their posterior over the same grid rows (b7_eval_posterior); the
+-- front comes from b7_pareto_front3 and the objective's context nominates over the box decomposition (b7_ehvi3_nominate).  ref = nil:
+-- as for two objectives, per column.  One rank, no group, no batch, no refinement, no constraints, no trust region; at parity with
+-- harness/bots/bayesopt.py's nominate_objectives3.
+function bot:nominate_objectives3(candidates)
+  local candidates = candidates or self.candidates
+  assert(D.world == 1 and not hip.group, 'nominate_objectives3: one rank, no group (three objectives over a sharded grid are not built)')
+  local obj = assert(self.config.bot.objectives, 'nominate_objectives3: config.bot.objectives is not set')
+  assert(type(obj.models) == 'table' and #obj.models == 2,
+         'nominate_objectives3: config.bot.objectives.models holds two models, the second and the third objective (four or more objectives are not built)')
+  assert((self.config.bot.batch or 1) == 1, 'nominate_objectives3: config.bot.batch > 1 (three-objective batches are not built)')
+  assert(not self.config.bot.refine, 'nominate_objectives3: config.bot.refine (refinement of a three-objective nominee is not built)')
+  assert(not self.config.bot.constraints, 'nominate_objectives3: config.bot.constraints (constraints combined with objectives are not built)')
+  assert(not self.config.bot.trust_region, 'nominate_objectives3: config.bot.trust_region (three objectives inside a trust region are not built)')
+  assert(torch.type(self.score) == 'bot7.scores.expected_hypervolume_improvement_hip',
+         'nominate_objectives3: config.score.type must be expected_hypervolume_improvement')
+  if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91
+    return torch.rand(1):mul(candidates:size(1)):long():add(1)
+  end
+  local model, keep = self.model, {}
+  assert(torch.type(model) == 'bot7.models.gp_hip', 'nominate_objectives3: needs the gp_hip model (the Bayesian-linear head is not built)')
+  local R, S = self.responses, self.config.bot.nSamples
+  assert(R:dim() == 2 and R:size(2) == 3, 'nominate_objectives3: the objective must return rows of 3 columns {y1, y2, y3}')
+  local X_obs, Y1 = self.observed, R:narrow(2, 1, 1):contiguous()
+  if self.objectives23 == nil then
+    self.objectives23 = {}
+    for k = 1, 2 do
+      local ctxp = ffi.new('b7_ctx*[1]')
+      assert(hip.C.b7_create(ctxp, hip.device) == 0, 'nominate_objectives3: b7_create failed')   -- the objective's device
+      self.objectives23[k] = {model = bot7.models.gp_hip(obj.models[k]), ctx = ffi.gc(ctxp[0], hip.C.b7_destroy),
+                              kernel = hip.KERNEL_ARDSE}
+    end
+  end
+  local ref = hip.pin(torch.Tensor(3))
+  keep[#keep + 1] = ref
+  if obj.ref then
+    ref[1], ref[2], ref[3] = obj.ref[1], obj.ref[2], obj.ref[3]
+  else
+    local hi, lo = R:max(1):view(-1), R:min(1):view(-1)
+    for k = 1, 3 do
+      local span = hi[k] - lo[k]
+      if not (span > 0) then span = math.max(math.abs(hi[k]), 1) end
+      ref[k] = hi[k] + 0.1 * span
+    end
+  end
+  local Rc = hip.pin(R:contiguous())
+  keep[#keep + 1] = Rc
+  local front, P = ffi.new('double[?]', 3 * math.max(1, math.min(R:size(1), hip.EHVI3_PMAX))), ffi.new('int[1]')
+  assert(hip.C.b7_pareto_front3(hip.data(Rc), R:size(1), hip.data(ref), front, nil, P) == 0,
+         'nominate_objectives3: a front of more than EHVI3_PMAX points, or a reference point that is not finite')
+  local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+  local hyps = sample_hyps(model, X_obs, Y1, S, keep)
+  model:stage(X_obs, Y1, candidates)
+  hip.set_kernel(model.kernel_code)
+  hip.check(hip.C.b7_eval_posterior(hip.ctx, S, hyps, jit, info))
+  for k = 1, 2 do
+    local o, Yk = self.objectives23[k], R:narrow(2, k + 1, 1):contiguous()
+    follow_steal(o, self.objectives_idx, candidates)
+    on_context(o, function()
+      if not o.inited then o.model:init(X_obs, Yk); o.inited = true end
+      local hypsk = sample_hyps(o.model, X_obs, Yk, S, keep)
+      o.model:stage(X_obs, Yk, candidates)
+      hip.set_kernel(o.model.kernel_code)
+      hip.check(hip.C.b7_eval_posterior(hip.ctx, S, hypsk, nil, nil))
+    end)
+  end
+  local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
+  hip.check(hip.C.b7_ehvi3_nominate(hip.ctx, self.objectives23[1].ctx, self.objectives23[2].ctx, front, P[0], hip.data(ref), v, i))
   for s = 0, S - 1 do
     if jit[s] > 0 then   -- the reference's warning text, utils/math.lua:210-212
       print(string.format('Warning: utils.math.chol succeeded in factorizing the\ninput matrix after applying a jitter of %.2e', jit[s]))

@@ -178,7 +178,8 @@ end
 do
   -- The exact two-objective expected hypervolume improvement (b7_ehvi_nominate; no original): not a per-point score of one posterior
   -- -- it needs the kept posteriors of two objectives, a front and a reference point.  bots_bayesopt_hip.lua's nominate_objectives
-  -- calls the library in place of eval + arg-max (config.bot.objectives).  Checked by the static checker only.
+  -- calls the library in place of eval + arg-max (config.bot.objectives); with config.bot.objectives.models it hands over to
+  -- nominate_objectives3 (three objectives, b7_ehvi3_nominate).  Checked by the static checker only.
   local EHVI, parent = torch.class('bot7.scores.expected_hypervolume_improvement_hip', 'bot7.scores.abstract')
   function EHVI:__init(config)
     parent.__init(self)
