@@ -29,6 +29,7 @@ SYMBOLS = [
     "b7_kg_nominate", "b7_kg_trace_enable", "b7_kg_last", "b7_kg_compute",
     "b7_eval_posterior", "b7_posterior_get", "b7_pareto_front2", "b7_hypervolume2", "b7_ehvi_compute", "b7_ehvi_nominate",
     "b7_pareto_front3", "b7_nondominated_boxes3", "b7_hypervolume3", "b7_ehvi3_compute", "b7_ehvi3_nominate",
+    "b7_logehvi_compute", "b7_logehvi_nominate", "b7_logehvi3_compute", "b7_logehvi3_nominate",
     "b7_refine_default_opts", "b7_eval_nominate_refine", "b7_refine_last", "b7_refine_shape", "b7_refine_trace_enable", "b7_refine_trace", "b7_gp_grad_at", "b7_score_grad_compute",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
@@ -216,6 +217,10 @@ def load(which=None):
         "b7_hypervolume3": (i32, [vp, i32, vp, C.POINTER(dbl)]),
         "b7_ehvi3_compute": (i32, [vp, vp, vp, vp, vp, i32, vp, i64, vp]),
         "b7_ehvi3_nominate": (i32, [vp, vp, vp, vp, i32, vp, C.POINTER(dbl), C.POINTER(i64)]),
+        "b7_logehvi_compute": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, i64, vp]),
+        "b7_logehvi_nominate": (i32, [vp, vp, vp, i32, vp, C.POINTER(dbl), C.POINTER(i64)]),
+        "b7_logehvi3_compute": (i32, [vp, vp, vp, vp, vp, i32, vp, i64, vp]),
+        "b7_logehvi3_nominate": (i32, [vp, vp, vp, vp, i32, vp, C.POINTER(dbl), C.POINTER(i64)]),
         "b7_refine_default_opts": (i32, [C.POINTER(RefineOpts)]),
         "b7_eval_nominate_refine": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), C.POINTER(RefineOpts), C.POINTER(dbl),
                                           C.POINTER(i64), vp, C.POINTER(dbl), C.POINTER(i64), vp, vp]),
@@ -1192,66 +1197,85 @@ class Context(object):
         self._ck(self._L.b7_posterior_get(self._h, int(s), _ptr(mean), _ptr(var)))
         return mean, var
 
-    def ehvi_compute(self, mu1, var1, mu2, var2, front, ref):
+    def ehvi_compute(self, mu1, var1, mu2, var2, front, ref, _who="ehvi_compute"):
         """The marginal expected hypervolume improvement on host arrays by the nomination's own kernel (b7_ehvi_compute): mu1 / var1
         S1 x M of objective 1, mu2 / var2 S2 x M of objective 2, front P x 2 canonical (pareto_front2), ref (r1, r2) -> M scores."""
         mu1, var1, mu2, var2 = (np.atleast_2d(_f64(a)) for a in (mu1, var1, mu2, var2))
         front, ref = _f64(front).reshape(-1, 2), _f64(ref).ravel()
         M = mu1.shape[1]
         if var1.shape != mu1.shape or var2.shape != mu2.shape or mu2.shape[1] != M or ref.size != 2:
-            raise Bot7HipError(-1, "ehvi_compute: mu1 / var1 S1 x M, mu2 / var2 S2 x M, front P x 2, ref 2")
+            raise Bot7HipError(-1, _who + ": mu1 / var1 S1 x M, mu2 / var2 S2 x M, front P x 2, ref 2")
         out = np.empty(M, dtype=np.float64)
-        self._ck(self._L.b7_ehvi_compute(self._h, _ptr(mu1), _ptr(var1), mu1.shape[0], _ptr(mu2), _ptr(var2), mu2.shape[0],
+        self._ck(getattr(self._L, "b7_" + _who)(self._h, _ptr(mu1), _ptr(var1), mu1.shape[0], _ptr(mu2), _ptr(var2), mu2.shape[0],
                                          _ptr(front), front.shape[0], _ptr(ref), M, _ptr(out)))
         return out
 
-    def ehvi_nominate(self, other, front, ref):
+    def ehvi_nominate(self, other, front, ref, _who="ehvi_nominate"):
         """The two-objective nomination (b7_ehvi_nominate): this context holds objective 1's kept posterior (eval_posterior), `other`
         objective 2's (other may be this context).  Both must hold the same grid rows: the caller's contract, only the row count is
         checked.  The marginal score stays in this context's accumulator (score_finish(1, download=True) reads it).  Returns (value,
         1-based index); neither grid is modified."""
         if not isinstance(other, Context) or other._L is not self._L:
-            raise Bot7HipError(-1, "ehvi_nominate: other must be a Context of the same library")
+            raise Bot7HipError(-1, _who + ": other must be a Context of the same library")
         front, ref = _f64(front).reshape(-1, 2), _f64(ref).ravel()
         if ref.size != 2:
-            raise Bot7HipError(-1, "ehvi_nominate: ref has two entries")
+            raise Bot7HipError(-1, _who + ": ref has two entries")
         val, idx = C.c_double(), C.c_int64()
-        self._ck(self._L.b7_ehvi_nominate(self._h, other._h, _ptr(front), front.shape[0], _ptr(ref), C.byref(val), C.byref(idx)))
+        self._ck(getattr(self._L, "b7_" + _who)(self._h, other._h, _ptr(front), front.shape[0], _ptr(ref), C.byref(val), C.byref(idx)))
         return val.value, idx.value
 
     # ---- three objectives: the expected hypervolume improvement over a box decomposition (csrc/ehvi3.hip)
-    def ehvi3_compute(self, mu, var, front, ref):
+    def ehvi3_compute(self, mu, var, front, ref, _who="ehvi3_compute"):
         """The marginal three-objective expected hypervolume improvement on host arrays by the nomination's own kernels
         (b7_ehvi3_compute): mu / var three arrays each, S_m x M of objective m, front P x 3 canonical (pareto_front3), ref
         (r1, r2, r3) -> M scores."""
         if len(mu) != 3 or len(var) != 3:
-            raise Bot7HipError(-1, "ehvi3_compute: mu and var hold one array per objective, three each")
+            raise Bot7HipError(-1, _who + ": mu and var hold one array per objective, three each")
         mu, var = [np.atleast_2d(_f64(a)) for a in mu], [np.atleast_2d(_f64(a)) for a in var]
         front, ref = _f64(front).reshape(-1, 3), _f64(ref).ravel()
         M = mu[0].shape[1]
         if any(v.shape != m.shape or m.shape[1] != M for m, v in zip(mu, var)) or ref.size != 3:
-            raise Bot7HipError(-1, "ehvi3_compute: mu[m] / var[m] S_m x M, front P x 3, ref 3")
+            raise Bot7HipError(-1, _who + ": mu[m] / var[m] S_m x M, front P x 3, ref 3")
         pm = (C.c_void_p * 3)(*[a.ctypes.data for a in mu])
         pv = (C.c_void_p * 3)(*[a.ctypes.data for a in var])
         S = (C.c_int * 3)(*[a.shape[0] for a in mu])
         out = np.empty(M, dtype=np.float64)
-        self._ck(self._L.b7_ehvi3_compute(self._h, pm, pv, S, _ptr(front), front.shape[0], _ptr(ref), M, _ptr(out)))
+        self._ck(getattr(self._L, "b7_" + _who)(self._h, pm, pv, S, _ptr(front), front.shape[0], _ptr(ref), M, _ptr(out)))
         return out
 
-    def ehvi3_nominate(self, other2, other3, front, ref):
+    def ehvi3_nominate(self, other2, other3, front, ref, _who="ehvi3_nominate"):
         """The three-objective nomination (b7_ehvi3_nominate): this context holds objective 1's kept posterior (eval_posterior),
         other2 / other3 those of objectives 2 and 3 (contexts may coincide).  All must hold the same grid rows: the caller's
         contract, only the row count is checked.  The marginal score stays in this context's accumulator (score_finish(1,
         download=True) reads it).  Returns (value, 1-based index); no grid is modified."""
         for o in (other2, other3):
             if not isinstance(o, Context) or o._L is not self._L:
-                raise Bot7HipError(-1, "ehvi3_nominate: other2 and other3 must be Contexts of the same library")
+                raise Bot7HipError(-1, _who + ": other2 and other3 must be Contexts of the same library")
         front, ref = _f64(front).reshape(-1, 3), _f64(ref).ravel()
         if ref.size != 3:
-            raise Bot7HipError(-1, "ehvi3_nominate: ref has three entries")
+            raise Bot7HipError(-1, _who + ": ref has three entries")
         val, idx = C.c_double(), C.c_int64()
-        self._ck(self._L.b7_ehvi3_nominate(self._h, other2._h, other3._h, _ptr(front), front.shape[0], _ptr(ref), C.byref(val), C.byref(idx)))
+        self._ck(getattr(self._L, "b7_" + _who)(self._h, other2._h, other3._h, _ptr(front), front.shape[0], _ptr(ref), C.byref(val), C.byref(idx)))
         return val.value, idx.value
+
+    # ---- log-space EHVI (csrc/logehvi.hip): the four calls above, in log space
+    def logehvi_compute(self, mu1, var1, mu2, var2, front, ref):
+        """log of ehvi_compute's marginal, evaluated so that it never underflows (b7_logehvi_compute); -inf is a legal value."""
+        return self.ehvi_compute(mu1, var1, mu2, var2, front, ref, _who="logehvi_compute")
+
+    def logehvi_nominate(self, other, front, ref):
+        """ehvi_nominate by the log score (b7_logehvi_nominate): it still ranks the rows whose linear score is 0.  The marginal log
+        score stays in this context's accumulator as a LOG accumulator: score_finish(1, download=True) reads it, and
+        feas_add_acc(self) takes it (constrained multi-objective nomination: feas_reset, feas_add / feas_add_acc, feas_nominate)."""
+        return self.ehvi_nominate(other, front, ref, _who="logehvi_nominate")
+
+    def logehvi3_compute(self, mu, var, front, ref):
+        """log of ehvi3_compute's marginal (b7_logehvi3_compute)."""
+        return self.ehvi3_compute(mu, var, front, ref, _who="logehvi3_compute")
+
+    def logehvi3_nominate(self, other2, other3, front, ref):
+        """ehvi3_nominate by the log score (b7_logehvi3_nominate); the accumulator is a log one, as logehvi_nominate leaves it."""
+        return self.ehvi3_nominate(other2, other3, front, ref, _who="logehvi3_nominate")
 
     def rff_compute(self, X, omega, phase, W):
         """cos(X omega' + phase) W on host arrays (b7_rff_compute): X M1 x d, omega F x d, phase F, W F x q -> M1 x q."""

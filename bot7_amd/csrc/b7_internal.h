@@ -545,6 +545,8 @@ int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64
 // written before anybody reads them
 void acc_declare_zeros(b7_ctx *c, int score_kind);
 int acc_write_zeros(b7_ctx *c);
+// the caller writes every row of c->acc with a finished log score on c's stream (logehvi.hip): a log accumulator, valid, not fresh
+void acc_declare_log_written(b7_ctx *c);
 void acc_forget(b7_ctx *c);
 int acc_materialize(b7_ctx *c);
 void feas_forget(b7_ctx *c);  // the grid changed: there is no feasibility column until the next b7_feas_reset
@@ -650,6 +652,23 @@ constexpr int score_acc_kind(int kind) { return (kind == B7_SCORE_LOGEI || kind 
 static inline const char *score_kind_name(int kind) {  // for the messages
   return kind == B7_SCORE_EI ? "ei" : kind == B7_SCORE_LOGEI ? "logei" : kind == B7_SCORE_LOGPI ? "logpi" : kind == B7_SCORE_MES ? "mes" : "cb";
 }
+// ehvi.hip / ehvi3.hip: the checks and the staging of a front that logehvi.hip's twins share with them.  front_stage: the front as the
+// two-objective kernels read it, on its way to c->ehvi_front on c's stream (the host block must outlive the copy).  Staged3: what
+// the three-objective kernels read of a front, on the host: the cuts of the three objectives one after the other and the boxes as
+// table rows.  chunk3: candidates per chunk, the table within min(workspace, 256 MiB), whole waves, at least one.
+int front_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref);
+int front_stage(b7_ctx *c, const double *front, int P, const double *ref, std::vector<double> *host);
+int samples_refuse(b7_ctx *c, const char *who, int S1, int S2);
+int front3_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref);
+int samples3_refuse(b7_ctx *c, const char *who, const int *S);
+constexpr int EHVI3_BOXES_MAX = 3 * B7_EHVI3_PMAX + 1;
+struct Staged3 {
+  std::vector<double> cuts;
+  std::vector<int> box;
+  int ncut[3], rows, B;
+};
+void stage3_host(const double *front, int P, const double *ref, Staged3 *st);
+int64_t chunk3(const b7_ctx *c, int rows, int64_t M);
 // mes.hip: c->ystar laid out for S samples of M rows at K levels; y* of nS samples (sample s at mu / var + s * stride) searched into
 // slots [slot0, slot0 + nS) of that layout, R + 1 launches; the device address of a slot's K values
 int mes_begin(b7_ctx *c, int S, int64_t M, int K);

@@ -22,9 +22,10 @@
 // conflict, no barrier -- a lane reads only what it wrote), up to B7_EHVI_SMAX per objective: (3 x1 + 2 x2) 512 bytes of dynamic LDS
 // for x1 / x2 samples beyond the registers, 56320 at most.  The summation order is the same on both sides of the limit.
 //
+// The log-space EHVI, which still ranks the rows where this score underflows to 0, is logehvi.hip's b7_logehvi_*.
 // Out of scope, refused by name where it can be asked for: more than two objectives here (three through ehvi3.hip's b7_ehvi3_*, four
-// and more nowhere), correlated objectives / multi-task GPs, a
-// log-space EHVI, batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
+// and more nowhere), correlated objectives / multi-task GPs,
+// batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
 // ParEGO-style scalarisation.
 #pragma clang fp contract(off)
 #include <math.h>
@@ -149,6 +150,9 @@ int front_defect(const double *front, int P, const double *ref, int *k_out) {
   return 0;
 }
 
+}  // namespace
+
+// front_refuse, front_stage and samples_refuse are logehvi.hip's too (b7_internal.h)
 int front_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref) {
   if (!ref) return b7_fail(c, B7_ERR_INVALID, "%s: ref is NULL", who);
   if (P < 0 || P > B7_EHVI_PMAX) return b7_fail(c, B7_ERR_INVALID, "%s: a front of %d points (0..%d are built)", who, P, B7_EHVI_PMAX);
@@ -181,6 +185,8 @@ int front_stage(b7_ctx *c, const double *front, int P, const double *ref, std::v
   return B7_OK;
 }
 
+namespace {
+
 // the score of M rows onto out (device), on c's stream; the front staged by front_stage
 int launch_ehvi(b7_ctx *c, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2, int P, int64_t M,
                 double *out) {
@@ -196,13 +202,13 @@ int launch_ehvi(b7_ctx *c, const double *mu1, const double *var1, int S1, const 
   return B7_OK;
 }
 
+}  // namespace
+
 int samples_refuse(b7_ctx *c, const char *who, int S1, int S2) {
   if (S1 < 1 || S1 > B7_EHVI_SMAX || S2 < 1 || S2 > B7_EHVI_SMAX)
     return b7_fail(c, B7_ERR_INVALID, "%s: S1 = %d, S2 = %d hyper samples (1..%d each are built)", who, S1, S2, B7_EHVI_SMAX);
   return B7_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

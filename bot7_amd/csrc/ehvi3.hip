@@ -29,8 +29,9 @@
 // An LDS-resident table ([cut][lane], one wave per workgroup) would cap P near 41 in 64 KiB and was not built: fronts up to
 // B7_EHVI3_PMAX need the table in memory either way.
 //
-// Out of scope, refused by name where it can be asked for: four or more objectives, correlated objectives / multi-task GPs, a
-// log-space EHVI, batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
+// The log-space EHVI, which still ranks the rows where this score underflows to 0, is logehvi.hip's b7_logehvi3_* over the same boxes.
+// Out of scope, refused by name where it can be asked for: four or more objectives, correlated objectives / multi-task GPs,
+// batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
 // trust regions.
 #pragma clang fp contract(off)
 #include <math.h>
@@ -50,7 +51,6 @@ constexpr int EHVI3_CB = 8;                            // cuts per work item of 
 #define B7_EHVI3_TABLE_MIB 256                         // (a build-time switch for the comparison of 16 / 64 / 256 / 1024 in DESIGN section 8 only)
 #endif
 constexpr size_t EHVI3_TABLE_BYTES = (size_t)B7_EHVI3_TABLE_MIB << 20;  // the table's share of a chunk, at most
-constexpr int EHVI3_BOXES_MAX = 3 * B7_EHVI3_PMAX + 1;
 
 // ehvi.hip's ehvi_f / ehvi_psi, operation for operation
 __device__ __forceinline__ double ehvi3_f(double t) {
@@ -173,6 +173,9 @@ int front3_defect(const double *front, int P, const double *ref, int *k_out, int
   return 0;
 }
 
+}  // namespace
+
+// front3_refuse, samples3_refuse, stage3_host and chunk3 are logehvi.hip's too (b7_internal.h, with Staged3 and EHVI3_BOXES_MAX)
 int front3_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref) {
   if (!ref) return b7_fail(c, B7_ERR_INVALID, "%s: ref is NULL", who);
   if (P < 0 || P > B7_EHVI3_PMAX) return b7_fail(c, B7_ERR_INVALID, "%s: a front of %d points (0..%d are built)", who, P, B7_EHVI3_PMAX);
@@ -203,6 +206,8 @@ int samples3_refuse(b7_ctx *c, const char *who, const int *S) {
   return B7_OK;
 }
 
+namespace {
+
 // The decomposition (bot7hip.h): boxes as l1, u1, l2, u2, u3 appended to `out`.  The front is canonical.
 void boxes3(const double *front, int P, const double *ref, std::vector<double> *out) {
   std::vector<std::pair<double, double>> st;  // the staircase of the projections seen so far: a ascending, b descending, both strictly
@@ -232,12 +237,7 @@ void boxes3(const double *front, int P, const double *ref, std::vector<double> *
   }
 }
 
-// What the kernels read of a front, on the host: the cuts of the three objectives one after the other and the boxes as table rows
-struct Staged3 {
-  std::vector<double> cuts;
-  std::vector<int> box;
-  int ncut[3], rows, B;
-};
+}  // namespace
 
 void stage3_host(const double *front, int P, const double *ref, Staged3 *st) {
   int row0[3], cut0[3];
@@ -275,6 +275,8 @@ int64_t chunk3(const b7_ctx *c, int rows, int64_t M) {
   C = std::max<int64_t>(C, EHVI3_LANES);
   return std::min<int64_t>(C, round_up(M, EHVI3_LANES));
 }
+
+namespace {
 
 // the score of M rows onto out (device), on c's stream: mu[m] / var[m] [S_m][M] on the device.  The host block `st` must outlive the
 // copies (the callers wait)

@@ -75,6 +75,7 @@
 #include <type_traits>
 
 #include "b7_internal.h"
+#include "logei_math.h"
 #include "mes_math.h"
 
 namespace {
@@ -105,37 +106,7 @@ __device__ __forceinline__ double b7_norm_pdf(double z) {
   return exp((z * z) * -0.5) * 0.3989422804014327;  // 1/math.sqrt(2*math.pi), utils/math.lua:15
 }
 
-// ---- log-space EI (see the header) ----
-__device__ __forceinline__ double b7_logei(double mu, double var, double fmin, double xi) {
-  const double sigma = sqrt(var);
-  const double imprv = (fmin + (-mu)) + (-xi);
-  const double z = imprv / sigma;
-  if (sigma == 0.0 || z == INFINITY) return (imprv > 0.0) ? log(imprv) : ((imprv != imprv) ? imprv : -INFINITY);
-  if (z == -INFINITY) return -INFINITY;
-  double lh;
-  if (z > -1.0) {
-    const double pdf = exp((z * z) * -0.5) * 0.39894228040143267794;  // 1/sqrt(2 pi)
-    const double cdf = erfc(z * -0.70710678118654752440) * 0.5;       // Phi(z) = erfc(-z/sqrt2)/2
-    lh = log(pdf + (z * cdf));
-  } else {  // NaN comes this way too, and stays NaN
-    const double t = -z;
-    double l1r;  // log(1 - r), r = t sqrt(pi/2) erfcx(t/sqrt2) = -z Phi(z)/phi(z)
-    if (t >= 1e5) {
-      l1r = (log(t) * -2.0) + log1p(-3.0 / (t * t));  // 1 - r = (1 - 3/t^2 + ..)/t^2: r itself rounds to 1 or past it out here
-    } else {
-      const double r = (t * 1.2533141373155002512) * erfcx(t * 0.70710678118654752440);
-      l1r = log1p(-r);
-    }
-    lh = (((z * z) * -0.5) + -0.91893853320467274178) + l1r;  // log phi(z) + log(1 - r)
-  }
-  return log(sigma) + lh;
-}
-__device__ __forceinline__ double b7_logaddexp(double a, double v) {
-  if (a != a || v != v) return a + v;
-  const double m = (a > v) ? a : v, n = (a > v) ? v : a;
-  if (m == -INFINITY || n == INFINITY) return m;  // both -inf, both +inf: n - m would be NaN
-  return m + log1p(exp(n + (-m)));
-}
+// (log-space EI and the log-sum-exp step, b7_logei / b7_logaddexp: logei_math.h, shared with logehvi.hip)
 // ---- log probability of improvement (see the header) ----
 __device__ __forceinline__ double b7_logpi(double mu, double var, double fmin, double xi) {
   const double sigma = sqrt(var);
@@ -830,6 +801,14 @@ int acc_write_zeros(b7_ctx *c) {
   c->acc_fresh = false;
   c->acc_kind = B7_ACC_NONE;  // the first add decides (acc_mode)
   return B7_OK;
+}
+
+// a finished log score is being written over every row of the accumulator (b7_logehvi_nominate, b7_logehvi3_nominate): what
+// b7_score_finish and b7_feas_add_acc then find is a log accumulator with something in it
+void acc_declare_log_written(b7_ctx *c) {
+  c->acc_valid = true;
+  c->acc_fresh = false;
+  c->acc_kind = B7_ACC_LOG;
 }
 
 // the grid changed: there is no accumulator until the next reset or nomination

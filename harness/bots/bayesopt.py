@@ -48,6 +48,10 @@ config.bot.objectives = {"ref": [r1, r2, r3] | None, "models": [{...}, {...}]} m
 comes from pareto_front3 and the objective's context nominates over the boxes of the non-dominated region (ehvi3_nominate); the
 stolen row leaves all three grids; the reports carry hypervolume3.  Four or more objectives, and with three also trust regions,
 are refused by name (objectives3_refusal).
+config.score.type = 'log_expected_hypervolume_improvement' runs the same trials, two or three objectives, by the LOG score
+(logehvi_nominate / logehvi3_nominate): it still ranks the candidates where the linear score is 0 in every row -- a fixed ref that no
+observation has reached yet, late trials, a large grid -- and the linear arg-max would take row 1.  last_objectives["value"] is then
+the log value.  Everything refused with the linear type is refused with this one.
 
 config.bot.trust_region (ours; None = the reference's loop, untouched) is a dict of length_init / length_min / length_max /
 success_tolerance / failure_tolerance / perturb / base: TRUST-REGION nomination (TuRBO-1: Eriksson et al. 2019).  No grid is made
@@ -140,6 +144,8 @@ def kg_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
 
 
 EHVI = "expected_hypervolume_improvement"
+LOG_EHVI = "log_expected_hypervolume_improvement"   # the same trials by the log score (b7_logehvi_nominate / b7_logehvi3_nominate)
+EHVI_KINDS = (EHVI, LOG_EHVI)
 
 
 def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
@@ -147,8 +153,8 @@ def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
     kind = config["score"]["type"]
     obj = config["bot"].get("objectives")
     if obj is None:
-        if kind == EHVI:
-            return "%s without config.bot.objectives: the score needs two objectives, each with a model of its own" % EHVI
+        if kind in EHVI_KINDS:
+            return "%s without config.bot.objectives: the score needs two objectives, each with a model of its own" % kind
         return None
     if "models" in obj:
         return objectives3_refusal(config, model_class, sharded)
@@ -162,7 +168,7 @@ def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
         return "config.bot.objectives over sharded candidates: two objectives over a sharded grid are not built"
     if model_class == "bot7.models.dngo":
         return "config.bot.objectives with the dngo model: the Bayesian-linear head keeps no posterior for a second objective"
-    if kind != EHVI:
+    if kind not in EHVI_KINDS:
         return "config.bot.objectives with %s: only %s is built" % (kind, EHVI)
     if (obj.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
         return "config.bot.objectives with the %s model: the second objective is modelled by a gp_regressor" % obj["model"]["type"]
@@ -188,7 +194,7 @@ def objectives3_refusal(config, model_class="bot7.models.gp_regressor", sharded=
         return "config.bot.objectives over sharded candidates: three objectives over a sharded grid are not built"
     if model_class == "bot7.models.dngo":
         return "config.bot.objectives with the dngo model: the Bayesian-linear head keeps no posterior for further objectives"
-    if kind != EHVI:
+    if kind not in EHVI_KINDS:
         return "config.bot.objectives with %s: only %s is built" % (kind, EHVI)
     for m in models:
         if (m or {}).get("type", "gp_regressor") != "gp_regressor":
@@ -210,7 +216,7 @@ def trust_region_refusal(config, model_class="bot7.models.gp_regressor", sharded
         return "config.bot.trust_region with config.bot.refine: refinement inside a trust region is not built"
     if config["bot"].get("constraints"):
         return "config.bot.trust_region with config.bot.constraints: constraints inside a trust region are not built"
-    if config["bot"].get("objectives") or config["score"]["type"] == EHVI:
+    if config["bot"].get("objectives") or config["score"]["type"] in EHVI_KINDS:
         return "config.bot.trust_region with config.bot.objectives / %s: two objectives inside a trust region are not built" % EHVI
     if sharded:
         return "config.bot.trust_region over sharded candidates or a group: the sharded trust-region loop is not built"
@@ -951,7 +957,7 @@ class bayesopt(abstract):
                 raise NotImplementedError(why)
         if self._trust_region():
             return self._run_trial_trust_region()
-        if self._objectives() or self.config["score"]["type"] == EHVI:
+        if self._objectives() or self.config["score"]["type"] in EHVI_KINDS:
             return self._run_trial_objectives()
         if self._constrained():
             return self._run_trial_constrained()

@@ -732,8 +732,8 @@ int b7_kg_compute(b7_ctx *ctx, int64_t M1, int L, const double *alpha /*M1 x L*/
  * Limits: P <= B7_EHVI_PMAX; S1, S2 in 1..B7_EHVI_SMAX.  The first B7_EHVI_SREG samples of each objective are held in registers
  * across the strips, the rest in LDS.
  * Not built, each refused by name where it can be asked for: more than two objectives by these entry points (three only through
- * b7_ehvi3_* below, four and more nowhere), correlated objectives / multi-task GPs, a
- * log-space EHVI, batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
+ * b7_ehvi3_* below, four and more nowhere), correlated objectives / multi-task GPs, a log-space EHVI by these entry points
+ * (b7_logehvi_* below), batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
  * ParEGO-style scalarisation.  Added without a change of B7_ABI_VERSION: the change is additive. */
 #define B7_EHVI_PMAX 256
 #define B7_EHVI_SMAX 32
@@ -794,7 +794,7 @@ int b7_ehvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front /*P x 2*/, 
  * Row classes: any mu or var NaN, or any var < 0, in any objective: NaN; otherwise the score is finite and >= 0, P = 0 included:
  * T_1(r1) T_2(r2) T_3(r3).  Limits: P <= B7_EHVI3_PMAX; S1, S2, S3 in 1..B7_EHVI_SMAX.
  * Not built, each refused by name where it can be asked for: four or more objectives, correlated objectives / multi-task GPs, a
- * log-space EHVI, batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
+ * log-space EHVI by these entry points (b7_logehvi3_* below), batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
  * trust regions.  Added without a change of B7_ABI_VERSION: the change is additive. */
 #define B7_EHVI3_PMAX 256
 /* Host-only (no context, no GPU): the canonical front of n rows of three responses, Y n x 3.  Rows with a non-finite entry and rows
@@ -831,6 +831,45 @@ int b7_ehvi3_compute(b7_ctx *ctx, const double *const *mu /*3*/, const double *c
  * group.  B7_ERR_UNSUPPORTED: contexts on different devices.  No counterpart in the reference. */
 int b7_ehvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const double *front /*P x 3*/, int P, const double *ref /*3*/,
                       double *best_val, int64_t *best_idx1);
+
+/* LOG-SPACE EHVI for two and three objectives: the logarithm of the two marginal scores above, evaluated so that it never underflows
+ * (the multi-objective twin of b7_score_logei; Ament et al., NeurIPS 2023).  No counterpart in the reference.  The linear scores are
+ * exactly 0 wherever every strip or box has a Psi with z < -37.5 -- a reference point that no observation has reached, late trials with
+ * small posterior variance, most rows of a large grid -- and score:max(1) then nominates row 1; these still rank such rows.
+ *   logPsi(a; mu, var) = log EI(mu, var, fmin = a, xi = 0) as b7_score_logei evaluates it (its three branches and edge cases); a = -inf: -inf
+ *   ldiff(u, l) = log(e^u - e^l):  l == -inf: u exactly;  !(l < u): -inf (the linear code's clamp at 0);  otherwise, d = l - u:
+ *                 u + log(-expm1(d)) if d > -ln 2, else u + log1p(-exp(d))
+ *   LSE: a log-sum-exp in a fixed order in the running-max form -- (m, acc) = (-inf, 0); a term t == -inf is skipped; otherwise
+ *        e = exp(-|t - m|) and (m, acc) = (t, acc e + 1) if t > m, else (m, acc + e); the value is -inf if m == -inf, else m + log(acc).
+ *        An empty sum is -inf, a single term comes back exactly.
+ *   two objectives:    log score = LSE_k[(LSE_s ldiff(logPsi(a_k+1; s), logPsi(a_k; s)) - log S1) + (LSE_t logPsi(b_k; t) - log S2)],
+ *                      k ascending, s / t ascending within it, every logPsi(a_k; s) evaluated once
+ *   three objectives:  LT_m(c) = LSE_s logPsi(c; s) - log S_m per distinct cut, LT_m(-inf) = -inf, and over b7_nondominated_boxes3's
+ *                      boxes in their order  log score = LSE_b[(ldiff(LT1(u1), LT1(l1)) + ldiff(LT2(u2), LT2(l2))) + LT3(u3)]
+ * log S_m is the logarithm of the sample count (S_m = 1: exactly 0); one rounded operation per operator; erfc, erfcx, exp, expm1, log and
+ * log1p are ocml's.  Row classes: NaN exactly where the linear score is NaN (any mu or var NaN, or any var < 0, in any objective);
+ * otherwise, for finite input, never NaN and never +inf; -inf is a legal value (every var == 0 and the point dominated).
+ * Signatures, limits (B7_EHVI_PMAX / B7_EHVI3_PMAX, B7_EHVI_SMAX, B7_EHVI_SREG), the canonical-front checks, the refusals and the
+ * ordering of the streams are those of the linear twins; the three-objective table is chunked the same way and a row's bits do not
+ * depend on the chunking.  Not built: as listed for the linear twins, the log form aside.  Added without a change of B7_ABI_VERSION:
+ * the change is additive. */
+/* b7_ehvi_compute's twin: the log score alone on host arrays, by the nomination's own kernel.  No counterpart in the reference. */
+int b7_logehvi_compute(b7_ctx *ctx, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2,
+                       const double *front /*P x 2*/, int P, const double *ref /*2*/, int64_t M, double *out /*M*/);
+/* b7_ehvi_nominate's twin.  The marginal log score is written to ctx's accumulator as a LOG accumulator, already divided:
+ * b7_score_finish(1) downloads it, and b7_feas_add_acc(any, ctx) takes it, so that constrained multi-objective nomination is
+ * b7_feas_reset, b7_feas_add / b7_feas_add_acc of the constraints' log-weights, b7_feas_add_acc(ctx, ctx), b7_feas_nominate.  The
+ * nominee is score:max(1) by b7_eval_nominate's rule (the first NaN, else the maximum, ties to the lowest index).  Errors as
+ * b7_ehvi_nominate's.  No counterpart in the reference. */
+int b7_logehvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front /*P x 2*/, int P, const double *ref /*2*/, double *best_val,
+                        int64_t *best_idx1);
+/* b7_ehvi3_compute's twin: the log score alone on host arrays, by the nomination's own kernels.  No counterpart in the reference. */
+int b7_logehvi3_compute(b7_ctx *ctx, const double *const *mu /*3*/, const double *const *var /*3*/, const int *S /*3*/,
+                        const double *front /*P x 3*/, int P, const double *ref /*3*/, int64_t M, double *out /*M*/);
+/* b7_ehvi3_nominate's twin; the accumulator is a LOG one, as b7_logehvi_nominate leaves it.  Errors as b7_ehvi3_nominate's.
+ * No counterpart in the reference. */
+int b7_logehvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const double *front /*P x 3*/, int P, const double *ref /*3*/,
+                         double *best_val, int64_t *best_idx1);
 
 /* ---- trust-region nomination (TuRBO: Eriksson, Pearce, Gardner, Turner & Poloczek, NeurIPS 2019).  No counterpart in the
  * reference.  Three host-only pieces (no context, no GPU) that both host languages share, and the device map b7_grid_trust_region

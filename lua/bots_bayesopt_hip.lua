@@ -367,7 +367,8 @@ function bot:nominate_constrained(candidates)
 end
 
 -- TWO-OBJECTIVE nomination (b7_ehvi_nominate; no counterpart in the reference; Emmerich, Yang & Deutz 2016):
--- config.bot.objectives = {ref = {r1, r2} | nil, model = {...}}, config.score.type = 'expected_hypervolume_improvement'; the
+-- config.bot.objectives = {ref = {r1, r2} | nil, model = {...}}, config.score.type = 'expected_hypervolume_improvement' (or
+-- 'log_expected_hypervolume_improvement': the same trial by the log score, b7_logehvi_nominate / b7_logehvi3_nominate); the
 -- objective returns a row {y1, y2}, both minimised; self.responses keeps both columns.  The bot's own model sees column 1,
 -- self.objective2 = {model (a gp_hip), ctx (a context of its own)}, set up on first use, column 2.  Per model-based trial both
 -- models sample their hypers and both contexts keep their posterior over the same grid rows (b7_eval_posterior); the front of the
@@ -384,8 +385,9 @@ function bot:nominate_objectives(candidates)
   assert((self.config.bot.batch or 1) == 1, 'nominate_objectives: config.bot.batch > 1 (two-objective batches are not built)')
   assert(not self.config.bot.refine, 'nominate_objectives: config.bot.refine (refinement of a two-objective nominee is not built)')
   assert(not self.config.bot.constraints, 'nominate_objectives: config.bot.constraints (constraints combined with objectives are not built)')
-  assert(torch.type(self.score) == 'bot7.scores.expected_hypervolume_improvement_hip',
-         'nominate_objectives: config.score.type must be expected_hypervolume_improvement')
+  local logkind = torch.type(self.score) == 'bot7.scores.log_expected_hypervolume_improvement_hip'   -- the log score: b7_logehvi*_nominate
+  assert(logkind or torch.type(self.score) == 'bot7.scores.expected_hypervolume_improvement_hip',
+         'nominate_objectives: config.score.type must be expected_hypervolume_improvement or log_expected_hypervolume_improvement')
   if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91
     return torch.rand(1):mul(candidates:size(1)):long():add(1)
   end
@@ -432,7 +434,11 @@ function bot:nominate_objectives(candidates)
     hip.check(hip.C.b7_eval_posterior(hip.ctx, S, hyps2, nil, nil))
   end)
   local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
-  hip.check(hip.C.b7_ehvi_nominate(hip.ctx, o2.ctx, front, P[0], hip.data(ref), v, i))
+  if logkind then
+    hip.check(hip.C.b7_logehvi_nominate(hip.ctx, o2.ctx, front, P[0], hip.data(ref), v, i))
+  else
+    hip.check(hip.C.b7_ehvi_nominate(hip.ctx, o2.ctx, front, P[0], hip.data(ref), v, i))
+  end
   for s = 0, S - 1 do
     if jit[s] > 0 then   -- the reference's warning text, utils/math.lua:210-212
       print(string.format('Warning: utils.math.chol succeeded in factorizing the\ninput matrix after applying a jitter of %.2e', jit[s]))
@@ -460,8 +466,9 @@ function bot:nominate_objectives3(candidates)
   assert(not self.config.bot.refine, 'nominate_objectives3: config.bot.refine (refinement of a three-objective nominee is not built)')
   assert(not self.config.bot.constraints, 'nominate_objectives3: config.bot.constraints (constraints combined with objectives are not built)')
   assert(not self.config.bot.trust_region, 'nominate_objectives3: config.bot.trust_region (three objectives inside a trust region are not built)')
-  assert(torch.type(self.score) == 'bot7.scores.expected_hypervolume_improvement_hip',
-         'nominate_objectives3: config.score.type must be expected_hypervolume_improvement')
+  local logkind = torch.type(self.score) == 'bot7.scores.log_expected_hypervolume_improvement_hip'   -- the log score: b7_logehvi*_nominate
+  assert(logkind or torch.type(self.score) == 'bot7.scores.expected_hypervolume_improvement_hip',
+         'nominate_objectives3: config.score.type must be expected_hypervolume_improvement or log_expected_hypervolume_improvement')
   if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91
     return torch.rand(1):mul(candidates:size(1)):long():add(1)
   end
@@ -513,7 +520,11 @@ function bot:nominate_objectives3(candidates)
     end)
   end
   local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
-  hip.check(hip.C.b7_ehvi3_nominate(hip.ctx, self.objectives23[1].ctx, self.objectives23[2].ctx, front, P[0], hip.data(ref), v, i))
+  if logkind then
+    hip.check(hip.C.b7_logehvi3_nominate(hip.ctx, self.objectives23[1].ctx, self.objectives23[2].ctx, front, P[0], hip.data(ref), v, i))
+  else
+    hip.check(hip.C.b7_ehvi3_nominate(hip.ctx, self.objectives23[1].ctx, self.objectives23[2].ctx, front, P[0], hip.data(ref), v, i))
+  end
   for s = 0, S - 1 do
     if jit[s] > 0 then   -- the reference's warning text, utils/math.lua:210-212
       print(string.format('Warning: utils.math.chol succeeded in factorizing the\ninput matrix after applying a jitter of %.2e', jit[s]))

@@ -192,6 +192,20 @@ do
 end
 
 do
+  -- The same policy by the log score (b7_logehvi_nominate / b7_logehvi3_nominate; no original): it still ranks the candidates where
+  -- the linear score is 0 in every row.  nominate_objectives / nominate_objectives3 tell the two kinds apart by this class's name.
+  local LogEHVI, parent = torch.class('bot7.scores.log_expected_hypervolume_improvement_hip', 'bot7.scores.abstract')
+  function LogEHVI:__init(config)
+    parent.__init(self)
+    self.config = config or {}
+  end
+  function LogEHVI:__call__(model, hyp, X_obs, Y_obs, X_hid, X_pend, config)
+    error('log_expected_hypervolume_improvement_hip is not a per-point score: nominate through bot7.bots.bayesopt_hip (b7_logehvi_nominate)')
+  end
+  S.log_expected_hypervolume_improvement = LogEHVI
+end
+
+do
   local CB, parent = torch.class('bot7.scores.confidence_bound_hip', 'bot7.scores.abstract')
   function CB:__init(config)
     parent.__init(self)
