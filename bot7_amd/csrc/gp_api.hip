@@ -308,6 +308,7 @@ int b7_gp_set_kernel(b7_ctx *c, int kernel) {
   c->kernel = kernel;
   c->fitted = false;
   c->predicted = false;
+  post_forget(c);  // a kept posterior (b7_eval_posterior) is of the kernel it was made under
   return B7_OK;
 }
 

@@ -145,6 +145,10 @@ typedef struct {
   double var_min;       /* [0.0] */
 } b7_gp_opts;
 int b7_gp_default_opts(b7_gp_opts *out);
+/* The options of the calls that FOLLOW.  What earlier calls left stays as they made it: the predictions of b7_gp_predict, the score
+ * accumulator and a kept posterior (b7_eval_posterior) hold the variance under the options in force when they were computed, and
+ * are served as such (a caller that changes var_with_noise / var_clamp between b7_eval_posterior and b7_ehvi_nominate scores the
+ * earlier variance). */
 int b7_gp_set_opts(b7_ctx *ctx, const b7_gp_opts *opts);
 
 /* The covariance kernel (bots/bayesopt.lua:41 config.model.kernel; the kernels themselves live in the absent `gp` package).
@@ -154,7 +158,9 @@ int b7_gp_set_opts(b7_ctx *ctx, const b7_gp_opts *opts);
  * Every entry point below that forms a covariance uses the context's kernel; k(x, x) = amp under both.  Context state, not a
  * field of the hyper or option structs above (hosts allocate those): a context that never calls this stays on ARD-SE.  Setting a DIFFERENT
  * kernel drops the fit and the predictions made from it (predict, fantasize, append and download answer B7_ERR_STATE until the
- * next fit); the resident data and grid stay.  Setting the current one again does nothing.  Unknown values: B7_ERR_INVALID.
+ * next fit) and a kept posterior (b7_eval_posterior: b7_posterior_get and the EHVI nominations answer B7_ERR_STATE until the
+ * next one); the resident data and grid stay, and so does the score accumulator (the last call's result).  Setting the current
+ * one again does nothing.  Unknown values: B7_ERR_INVALID.
  * Added without a change of B7_ABI_VERSION: the change is additive. */
 #define B7_KERNEL_ARDSE 0
 #define B7_KERNEL_MATERN52 1
