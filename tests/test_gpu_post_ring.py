@@ -4,7 +4,8 @@ images) at the smallest shapes at which the ring can go wrong.  Needs an MI355X:
 A tile of the stream has 16 (t + 1) stages, so the ring position at a tile switch is not a multiple of three: N <= 256
 is one tile (diagonal stages only), 257..512 two, 513..768 three.  The reference is the 128-candidate kernel
 (post_kernel_w4<2>: register staging, two buffers), which runs whenever the grid has fewer than one 256-candidate
-workgroup per CU, and the CPU oracle."""
+workgroup per CU, and the CPU oracle.  The same shapes against exact arithmetic, with bars below 1e-9 of the scale instead of the
+1e-5 here: tests/test_gpu_post_exact.py."""
 import numpy as np
 import pytest
 
