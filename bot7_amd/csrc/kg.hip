@@ -610,4 +610,18 @@ int b7_kg_compute(b7_ctx *c, int64_t M1, int L, const double *alpha, const doubl
   return B7_OK;
 }
 
+#ifdef B7_DIAG
+// diagnostic build only: the columns k_s(X, a_i) and W_s[:, i] = inv(K_s) k_s(X, a_i) of the last b7_kg_nominate, [KL][S][Npad] each,
+// as they stay resident in c->kgvec (kg_state lays them out first)
+int b7dbg_kg_operands(b7_ctx *c, double *kcol_host, double *W_host) {
+  if (!c || !c->kg_valid || !c->kgvec.p) return B7_ERR_INVALID;
+  const size_t col = (size_t)KL * c->kg_S * c->Npad;
+  if (c->kgvec.cap < sizeof(double) * 2 * col) return B7_ERR_INVALID;
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  if (kcol_host) B7_HIP(c, hipMemcpy(kcol_host, c->kgvec.p, sizeof(double) * col, hipMemcpyDeviceToHost));
+  if (W_host) B7_HIP(c, hipMemcpy(W_host, (const double *)c->kgvec.p + col, sizeof(double) * col, hipMemcpyDeviceToHost));
+  return B7_OK;
+}
+#endif
+
 }  // extern "C"

@@ -326,6 +326,24 @@ int ts_mean_over_grid(b7_ctx *c) {
   return B7_OK;
 }
 
+// c->ts_work: one hyper sample's operands, each piece on a 256-byte boundary (the multi-column mean reads alpha in 16-byte pairs):
+// omf F dpad | wf 16 F | phiw N qmax | ycols np qmax | alpha np yldmax | resid np qmax | inv_ls d | pmin q | taken q | part 2 nblk
+// The diagnostic build keeps every hyper sample's alpha (ns of them, sample s at alpha + s np yldmax) for b7dbg_ts_alpha; the
+// shipped build has the one, which the next sample overwrites.
+constexpr int TS_ALPHA_PIECE = 4;
+void ts_work_layout(int F, int dpad, int N, int np, int qmax, int yldmax, int d, int q, int nblk, int ns, size_t off[11]) {
+#ifdef B7_DIAG
+  const size_t nalpha = (size_t)ns;
+#else
+  const size_t nalpha = 1;
+  (void)ns;
+#endif
+  const size_t pieces[10] = {(size_t)F * dpad, 16 * (size_t)F, (size_t)N * qmax, (size_t)np * qmax, nalpha * np * yldmax, (size_t)np * qmax,
+                             (size_t)d,        (size_t)q,      (size_t)q,        2 * (size_t)nblk};
+  off[0] = 0;
+  for (int i = 0; i < 10; ++i) off[i + 1] = off[i] + (size_t)round_up((int64_t)pieces[i], 32);
+}
+
 // The context's response columns while a hyper sample's pseudo-responses are being fitted: put back on every way out.
 struct YSwap {
   b7_ctx *c;
@@ -372,12 +390,8 @@ int b7_ts_nominate(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t 
   const int nblk = (int)std::min<int64_t>(1024, (M + 255) / 256);
   B7_TRY(b7_ensure(c, c->ts_paths, sizeof(double) * (size_t)M * q));
   B7_TRY(b7_ensure(c, c->ts_draw, sizeof(double) * ((size_t)ns * F * d + F + (size_t)q * F + (size_t)q * N)));
-  // one hyper sample's operands, each piece on a 256-byte boundary (the multi-column mean reads alpha in 16-byte pairs):
-  // omf F dpad | wf 16 F | phiw N qmax | ycols np qmax | alpha np yldmax | resid np qmax | inv_ls d | pmin q | taken q | part 2 nblk
-  const size_t pieces[10] = {(size_t)F * dpad, 16 * (size_t)F, (size_t)N * qmax, (size_t)np * qmax, (size_t)np * yldmax, (size_t)np * qmax,
-                             (size_t)d,        (size_t)q,      (size_t)q,        2 * (size_t)nblk};
-  size_t off[11] = {0};
-  for (int i = 0; i < 10; ++i) off[i + 1] = off[i] + (size_t)round_up((int64_t)pieces[i], 32);
+  size_t off[11];
+  ts_work_layout(F, dpad, N, np, qmax, yldmax, d, q, nblk, ns, off);
   B7_TRY(b7_ensure(c, c->ts_work, sizeof(double) * off[10]));
   const TsDraws dr = ts_draws(c, ns, q, F, d, N);
   double *wk = (double *)c->ts_work.p;
@@ -417,7 +431,12 @@ int b7_ts_nominate(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t 
       hipLaunchKernelGGL(ts_pseudo_kernel, dim3((unsigned)((N * qs + 255) / 256)), dim3(256), 0, c->stream, (const double *)swap.ybuf.p,
                          (const double *)phiw, dr.eps, N, qs, s, S, sqrt(h.noise), ycols);
       B7_HIP(c, hipGetLastError());
-      c->ybuf.p = ycols, c->alpha.p = alpha, c->resid.p = resid;  // (capacities are not consulted while swapped: nothing regrows these)
+#ifdef B7_DIAG
+      double *alpha_s = alpha + (size_t)s * np * yldmax;
+#else
+      double *alpha_s = alpha;
+#endif
+      c->ybuf.p = ycols, c->alpha.p = alpha_s, c->resid.p = resid;  // (capacities are not consulted while swapped: nothing regrows these)
       c->ycols = qs;
       c->yld = qs == 1 ? 1 : (int)round_up(qs, 64);
       double jit = 0.0;
@@ -473,6 +492,27 @@ int b7_ts_last_draws(b7_ctx *c, int path, double *omega, double *phase, double *
   B7_HIP(c, hipStreamSynchronize(c->stream));
   return B7_OK;
 }
+
+#ifdef B7_DIAG
+// diagnostic build only: the alpha columns (N x qs, row-major; qs = the paths j = s, s + S, .. < q) of hyper sample s's
+// pseudo-response fit in the last b7_ts_nominate; *qs_out (nullable) receives qs
+int b7dbg_ts_alpha(b7_ctx *c, int s, double *out_host, int *qs_out) {
+  if (!c || !out_host || !c->ts_valid || c->ts_N != c->N) return B7_ERR_INVALID;
+  const int q = c->ts_q, S = c->ts_S, F = c->ts_F, N = c->ts_N, d = c->ts_d, np = c->Npad, ns = S < q ? S : q;
+  if (s < 0 || s >= ns) return B7_ERR_INVALID;
+  const int qmax = (q + ns - 1) / ns, yldmax = qmax == 1 ? 1 : (int)round_up(qmax, 64);
+  const int nblk = (int)std::min<int64_t>(1024, (c->ts_M + 255) / 256);
+  const int qs = (q - s + S - 1) / S, yld = qs == 1 ? 1 : (int)round_up(qs, 64);
+  size_t off[11];
+  ts_work_layout(F, rff_dpad(d), N, np, qmax, yldmax, d, q, nblk, ns, off);
+  if (!c->ts_work.p || c->ts_work.cap < sizeof(double) * off[10]) return B7_ERR_INVALID;
+  const double *alpha = (const double *)c->ts_work.p + off[TS_ALPHA_PIECE] + (size_t)s * np * yldmax;
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  B7_HIP(c, hipMemcpy2D(out_host, sizeof(double) * qs, alpha, sizeof(double) * yld, sizeof(double) * qs, N, hipMemcpyDeviceToHost));
+  if (qs_out) *qs_out = qs;
+  return B7_OK;
+}
+#endif
 
 int b7_rff_compute(b7_ctx *c, const double *X, int64_t M1, int d, const double *omega, const double *phase, const double *W, int F, int q,
                    double *out) {

@@ -240,3 +240,166 @@ def nominee_ref(marginal):
     """b7_eval_nominate's rule: the first NaN, else the maximum, ties to the lowest index (0-based)."""
     nan = np.flatnonzero(np.isnan(marginal))
     return int(nan[0]) if len(nan) else int(np.argmax(marginal))
+
+
+def lowest_rows(own_alpha, n):
+    """kg_rows_part_kernel's rule on the device's own means (S x M): the n lowest of ((mu_0 + mu_1) + ..) / S, the lower index
+    first among equals, a NaN counting as +inf."""
+    m = own_alpha[0].copy()
+    for s in range(1, len(own_alpha)):
+        m = m + own_alpha[s]
+    m = m / float(len(own_alpha))
+    return np.argsort(np.where(np.isnan(m), np.inf, m), kind="stable")[:n]
+
+
+# ---- the lines held to exact arithmetic (tests/test_kg_exact_host.py, tests/test_gpu_kg_exact.py) -------------------------------
+# What kg_kernel must return for one grid row x under one hyper sample, GIVEN the device's own W = inv(K) k(X, a_i) (diagnostic
+# build: b7dbg_kg_operands), its own latent variance var(x) (b7_eval_posterior) and t's second operand fl(noise + jitter):
+#     c_i(x) = k(x, a_i) - sum_j k(x, x_j) W_ji       k as (hi, lo) pairs from 50 digits on an exact argument, error-free products, exact sums
+#     b_i = c_i / sqrt(t),  b_0 = var / sqrt(t),  t = var + fl(noise + jitter)                                       at 50 digits
+# The bar of c_i, nothing of it from the device's output: gp_bar(e_np, scale_c) + dk(x, a_i) + sum_j |W_ji| dk_j, with scale_c =
+# |k(x, a_i)| + sum_j |k(x, x_j) W_ji|, e_np numpy float64's own error on k_hi(x, a) - k_hi W over the judged rows, dk
+# _post_ref.kstar_bound.  The bar of b_i: that over sqrt(t), plus SLOPE_ROUNDINGS u |b_i| for what follows c_i on the device: the add
+# in t (u on t, u / 2 on b), the square root (within one ulp, 2 u) and the division (correctly rounded, u): 3.5 u, taken as 4.
+# b_0 has those roundings alone.  bar / scale <= CAP on every judged row, scale = scale_c / sqrt(t).
+import _exact as E  # noqa: E402
+import _post_ref as PR  # noqa: E402
+from _blr_ref import _dd_sum, _two_prod  # noqa: E402
+
+U = 2.0 ** -53
+CAP = PR.CAP
+SLOPE_ROUNDINGS = 4.0
+KL = 16
+#               N    d   kernel        n  S   M     test_gpu_kg.CASES, then one per dpad class of kg_slab at N = 24
+EXACT_CASES = [(5, 1, "ardse", 1, 1, 200), (64, 6, "ardmatern52", 5, 3, 257), (65, 33, "ardse", 16, 1, 200), (128, 6, "ardse", 16, 3, 257),
+               (129, 65, "ardmatern52", 5, 1, 200), (300, 6, "ardse", 16, 1, 257), (300, 33, "ardmatern52", 1, 3, 200),
+               (24, 3, "ardmatern52", 1, 2, 257), (24, 12, "ardse", 5, 2, 200), (24, 24, "ardmatern52", 16, 2, 257),
+               (24, 40, "ardse", 1, 2, 200), (24, 60, "ardmatern52", 5, 2, 257), (24, 96, "ardse", 16, 2, 200)]
+ROUTES_CASE = (150, 5, "ardse", 16, 3, 200)
+#         name      N    d  S          the jitter redo: the small regime, the general layout, the general layout by d > 32
+REDO = {"small": (40, 3, 3), "general": (150, 5, 3), "wide": (24, 33, 2)}
+
+
+def exact_problem(N, d, M, S, n, dup=0):
+    """tests/test_gpu_kg.py's problem and hyper samples at given sizes; grid rows 1, 16 and M - 2 are observations; the n rows of A
+    are seeded, two of them among the judged rows 0 .. 16.  dup > 0: the last dup observations repeat the first dup, and the second
+    hyper sample has noise 0 (the plain factorisation fails, the jitter schedule takes over)."""
+    rng = np.random.default_rng(7 * N + d)
+    X, Xc = rng.random((N, d)), rng.random((M, d))
+    if dup:
+        X[N - dup:] = X[:dup]
+    y = np.sin(3.0 * X.sum(axis=1, keepdims=True)) + X[:, -1:] ** 2 + 0.05 * rng.standard_normal((N, 1))
+    if dup:
+        y[N - dup:] = y[:dup]
+    amp = float(np.var(y)) if N > 1 else 1.0
+    hyp = {"lenscale_sq": np.full(d, d / 8.0), "amp": amp, "noise": 1e-2 * amp, "mean": float(np.mean(y))}
+    hyps = [dict(hyp, lenscale_sq=hyp["lenscale_sq"] * (1.0 + 0.3 * s), amp=hyp["amp"] * (1.0 + 0.2 * s), mean=hyp["mean"] + 0.05 * s,
+                 noise=hyp["noise"] * (1.0 + 0.5 * s)) for s in range(S)]
+    if dup:
+        hyps[1] = dict(hyps[1], noise=0.0)
+    Xc[1], Xc[16], Xc[M - 2] = X[0], X[N - 1], X[N // 2]
+    pool = np.setdiff1d(np.arange(M), [0, 15])
+    arows = np.sort(np.concatenate([[0, 15][:min(n, 2)], rng.choice(pool, size=max(n - 2, 0), replace=False)])).astype(np.int64)
+    rows = np.unique(np.concatenate([PR.judged_rows(M), arows]))
+    return X, y, Xc, hyps, arows, rows
+
+
+class LineRef(object):
+    __slots__ = ("b", "b0", "bar", "bar0", "scale", "e_np", "e_np_u", "share", "cap")
+
+
+def lines_exact(X, Xs, A, hyp, kernel, W, var, tnoise):
+    """Reference slopes of the rows Xs under one hyper sample: b (hi, lo) R x n, b0 (hi, lo) R, their bars and scale_c / sqrt(t).
+    A: the n points of A; W: N x n; var: the R variances; tnoise: fl(noise + jitter)."""
+    X, Xs, A, W = (np.asarray(v, dtype=np.float64) for v in (X, Xs, A, W))
+    var = np.asarray(var, dtype=np.float64)
+    ls, amp = hyp["lenscale_sq"], hyp["amp"]
+    R, n = len(Xs), len(A)
+    cov, covA = PR.true_cov_rows(Xs, X, ls, amp, kernel), PR.true_cov_rows(Xs, A, ls, amp, kernel)
+    dk, dkA = PR.kstar_bound(cov, PR.arg_bound(Xs, X, ls), kernel), PR.kstar_bound(covA, PR.arg_bound(Xs, A, ls), kernel)
+    ch, cl, scale_c = np.empty((R, n)), np.empty((R, n)), np.empty((R, n))
+    for i in range(n):
+        P, Er = _two_prod(cov.hi, W[None, :, i])
+        Lm = cov.lo * W[None, :, i]
+        for r in range(R):
+            ch[r, i], cl[r, i] = _dd_sum([covA.hi[r, i], covA.lo[r, i]] + (-P[r]).tolist() + (-Er[r]).tolist() + (-Lm[r]).tolist())
+        scale_c[:, i] = np.abs(covA.hi[:, i]) + np.abs(P).sum(1)
+    ref = LineRef()
+    ref.e_np = float(np.max(E.abs_errors(covA.hi - cov.hi @ W, ch, cl)))
+    ref.e_np_u = ref.e_np / (U * float(scale_c.max()))   # numpy's error in u of the largest scale_c
+    ks = dk @ np.abs(W) + dkA
+    bar_c = E.gp_bar(ref.e_np, scale_c) + ks
+    ref.share = ks / bar_c
+    bh, bl, b0h, b0l = np.empty((R, n)), np.empty((R, n)), np.empty(R), np.empty(R)
+    with mpmath.workdps(50):
+        for r in range(R):
+            rs = mpmath.sqrt(mpmath.mpf(float(var[r])) + mpmath.mpf(float(tnoise)))
+            b0h[r], b0l[r] = E.mp_to_pair(mpmath.mpf(float(var[r])) / rs)
+            for i in range(n):
+                bh[r, i], bl[r, i] = E.mp_to_pair((mpmath.mpf(ch[r, i]) + mpmath.mpf(cl[r, i])) / rs)
+    rt = np.sqrt(var + tnoise)[:, None]
+    ref.b, ref.b0 = (bh, bl), (b0h, b0l)
+    ref.bar = bar_c / rt + SLOPE_ROUNDINGS * U * np.abs(bh)
+    ref.bar0 = SLOPE_ROUNDINGS * U * np.abs(b0h)
+    ref.scale = scale_c / rt
+    ref.cap = float(np.max(ref.bar / ref.scale))
+    return ref
+
+
+def judge_lines(ref, slopes, own):
+    """error / bar of slopes (R x (n + 1), column 0 the own line) against the reference: (R x n ratios, R own-line ratios -- 0 where
+    the row has no own line, which must then be a NaN)."""
+    slopes = np.asarray(slopes, dtype=np.float64)
+    r0 = np.where(own, E.abs_errors(slopes[:, 0], *ref.b0) / np.maximum(ref.bar0, 1e-300), np.where(np.isnan(slopes[:, 0]), 0.0, np.inf))
+    return E.abs_errors(slopes[:, 1:], *ref.b) / ref.bar, r0
+
+
+def kcol_ratio(X, A, hyp, kernel, kcol):
+    """error / bar, entry by entry, of kcol (N x n) = k(x_j, a_i) against 50 digits: cov_entry_bar at the value the device's own
+    argument can reach, plus the argument's counted roundings (_post_ref.kstar_bound)."""
+    cov = PR.true_cov_rows(X, A, hyp["lenscale_sq"], hyp["amp"], kernel)
+    return E.abs_errors(kcol, cov.hi, cov.lo) / PR.kstar_bound(cov, PR.arg_bound(X, A, hyp["lenscale_sq"]), kernel)
+
+
+def w_residual(X, hyp, kernel, tnoise, kcol, W):
+    """max_j |((K + tnoise I) W[:, i] - kcol[:, i])_j| per column in long double, and the bound 64 N 2^-53 ||K||_inf max |W[:, i]|."""
+    N = len(X)
+    K = cov_ld(X, X, hyp["lenscale_sq"], hyp["amp"], kernel)
+    res = np.abs(K @ np.asarray(W, dtype=LD) + LD(tnoise) * np.asarray(W, dtype=LD) - np.asarray(kcol, dtype=LD)).max(axis=0)
+    knorm = float(np.abs(K).sum(axis=1).max()) + tnoise
+    return np.asarray(res, dtype=np.float64), 64.0 * N * U * knorm * np.abs(W).max(axis=0)
+
+
+# ---- the device algebra restated in float64 (host tests) -------------------------------------------------------------------------
+def host_operands(X, Xs, A, hyp, kernel, tnoise):
+    """kcol (N x n), W (N x n) and the latent variance at Xs as the device makes them, in float64 with LAPACK."""
+    from scipy.linalg import cho_factor, cho_solve, solve_triangular
+    K = PR.device_kstar(X, X, hyp["lenscale_sq"], hyp["amp"], kernel)
+    K[np.diag_indices(len(X))] = hyp["amp"] + tnoise
+    kcol = PR.device_kstar(X, A, hyp["lenscale_sq"], hyp["amp"], kernel)
+    cf = cho_factor(K, lower=True)
+    V = solve_triangular(np.tril(cf[0]), PR.device_kstar(Xs, X, hyp["lenscale_sq"], hyp["amp"], kernel).T, lower=True)
+    return kcol, cho_solve(cf, kcol), hyp["amp"] - (V * V).sum(axis=0)
+
+
+def lines_host(X, Xs, A, hyp, kernel, W, var, tnoise, wrong=None, Xs_next=None, ls0=None):
+    """The float64 restatement of kg_kernel's slopes at the rows Xs: R x (n + 1), column 0 the own line.  wrong names one way the
+    kernel goes wrong (tests/test_kg_exact_host.py): ("slab", start, width), ("swap", i), ("hql",) with Xs_next the neighbouring
+    queries, ("ls0",) with ls0 sample 0's lengthscales in the k(x, a_i) tile, ("nojit", noise) with t = var + noise."""
+    kind = wrong[0] if wrong else None
+    ls, amp = hyp["lenscale_sq"], hyp["amp"]
+    Ks = PR.device_kstar(Xs, X, ls, amp, kernel)
+    if kind == "hql":
+        w = 1.0 / np.asarray(ls, dtype=np.float64).ravel()
+        hq, hk = 0.5 * ((Xs_next * Xs_next) @ w), 0.5 * ((X * X) @ w)
+        arg = np.minimum(((Xs @ (X * w).T) - hq[:, None]) - hk[None, :], 0.0)
+        sq = np.sqrt(-10.0 * arg)
+        Ks = amp * np.exp(arg) if kernel == PR.SE else amp * (1.0 + sq * (1.0 + sq / 3.0)) * np.exp(-sq)
+    if kind == "slab":
+        Ks[:, wrong[1]:wrong[1] + wrong[2]] = 0.0
+    W = np.array(W, dtype=np.float64)
+    if kind == "swap":
+        W[:, [wrong[1], wrong[1] + 1]] = W[:, [wrong[1] + 1, wrong[1]]]
+    KA = PR.device_kstar(Xs, A, ls0 if kind == "ls0" else ls, amp, kernel)
+    rs = np.sqrt(var + (wrong[1] if kind == "nojit" else tnoise))
+    return np.concatenate([(var / rs)[:, None], (KA - Ks @ W) / rs[:, None]], axis=1)

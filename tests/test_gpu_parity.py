@@ -149,6 +149,19 @@ def test_argmax_semantics(ctx, orc):
     v, i = ctx.argmax(s)
     assert np.isnan(v) and i == 50001 == orc.c.argmax_first(s)[0]
     assert ctx.argmax(np.full(1000, -np.inf))[1] == 1
+    # finish_kernel launches at most 8 blocks of 256 threads per compute unit: beyond that many rows its grid-stride loop takes a
+    # second lap.  The tie and the NaN lie in that lap.
+    lap = 8 * 256 * ctx.device_info()["compute_units"]
+    s = rng.normal(size=lap + 300)
+    assert ctx.argmax(s)[1] == orc.c.argmax_first(s)[0]
+    top = s.max() + 1.0
+    s[[lap + 7, lap + 200]] = top                     # both in the second lap -> first occurrence
+    assert ctx.argmax(s) == (top, lap + 8) and orc.c.argmax_first(s)[0] == lap + 8
+    s[7] = top                                        # the same thread's first-lap row ties with its second-lap row
+    assert ctx.argmax(s) == (top, 8)
+    s[[lap + 100, lap + 250]] = np.nan                # first NaN wins
+    v, i = ctx.argmax(s)
+    assert np.isnan(v) and i == lap + 101 == orc.c.argmax_first(s)[0]
 
 
 # ---- GP fit / predict -----------------------------------------------------------------------------------------
