@@ -1258,7 +1258,7 @@ class Context(object):
         self._ck(getattr(self._L, "b7_" + _who)(self._h, other2._h, other3._h, _ptr(front), front.shape[0], _ptr(ref), C.byref(val), C.byref(idx)))
         return val.value, idx.value
 
-    # ---- log-space EHVI (csrc/logehvi.hip): the four calls above, in log space
+    # ---- log-space EHVI (csrc/ehvi_math.h's EhviLog): the four calls above, in log space
     def logehvi_compute(self, mu1, var1, mu2, var2, front, ref):
         """log of ehvi_compute's marginal, evaluated so that it never underflows (b7_logehvi_compute); -inf is a legal value."""
         return self.ehvi_compute(mu1, var1, mu2, var2, front, ref, _who="logehvi_compute")

@@ -285,12 +285,12 @@ struct b7_ctx {
   int64_t post_M = 0;
   DevBuf ehvi_front; // a_1 .. a_P, r1 | r2, b_1 .. b_P: 2 (P + 1) doubles as the kernel reads them
   DevBuf ehvi_user;
-  hipEvent_t ev_ehvi[2] = {nullptr, nullptr};  // b7_ehvi_nominate: the other context's stream -> this one, and back (created on first use)
+  // ehvi_nominate of n objectives: the other contexts' streams -> this one (0 .. n - 2), and back (n - 1); created on first use
+  hipEvent_t ev_ehvi[3] = {nullptr, nullptr, nullptr};
   // ---- b7_ehvi3_* (ehvi3.hip): three objectives over the same kept posteriors
   DevBuf ehvi3_front;  // the cuts of the three objectives (3 (PMAX + 1) doubles), then the boxes as five table rows each (ints)
   DevBuf ehvi3_table;  // T [rows][C] of one chunk of C candidates, then the row-class flags [3][C] (ints)
   DevBuf ehvi3_user;   // b7_ehvi3_compute's staging, apart from the kept posterior
-  hipEvent_t ev_ehvi3[3] = {nullptr, nullptr, nullptr};  // b7_ehvi3_nominate: the second / third context's stream -> this one, and back
   DevBuf feat;   // DNGO basis features of the resident grid: Mfeat x Npad (zero-padded columns)
   size_t feat_zeroed_bytes = 0;  // how much of `feat` was zeroed when it was laid out for feat_z columns
   int feat_z = -1;
@@ -545,7 +545,7 @@ int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64
 // written before anybody reads them
 void acc_declare_zeros(b7_ctx *c, int score_kind);
 int acc_write_zeros(b7_ctx *c);
-// the caller writes every row of c->acc with a finished log score on c's stream (logehvi.hip): a log accumulator, valid, not fresh
+// the caller writes every row of c->acc with a finished log score on c's stream (ehvi_nominate): a log accumulator, valid, not fresh
 void acc_declare_log_written(b7_ctx *c);
 void acc_forget(b7_ctx *c);
 int acc_materialize(b7_ctx *c);
@@ -652,23 +652,22 @@ constexpr int score_acc_kind(int kind) { return (kind == B7_SCORE_LOGEI || kind 
 static inline const char *score_kind_name(int kind) {  // for the messages
   return kind == B7_SCORE_EI ? "ei" : kind == B7_SCORE_LOGEI ? "logei" : kind == B7_SCORE_LOGPI ? "logpi" : kind == B7_SCORE_MES ? "mes" : "cb";
 }
-// ehvi.hip / ehvi3.hip: the checks and the staging of a front that logehvi.hip's twins share with them.  front_stage: the front as the
-// two-objective kernels read it, on its way to c->ehvi_front on c's stream (the host block must outlive the copy).  Staged3: what
-// the three-objective kernels read of a front, on the host: the cuts of the three objectives one after the other and the boxes as
-// table rows.  chunk3: candidates per chunk, the table within min(workspace, 256 MiB), whole waves, at least one.
-int front_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref);
-int front_stage(b7_ctx *c, const double *front, int P, const double *ref, std::vector<double> *host);
-int samples_refuse(b7_ctx *c, const char *who, int S1, int S2);
+// ehvi.hip: the nomination of n = 2 or 3 objectives, linear or in log space, over the kept posteriors of o[0 .. n - 1] (o[0] takes
+// the accumulator and the messages, which name the call as `who`); the four b7_[log]ehvi[3]_nominate entries are this.
+int ehvi_nominate(b7_ctx *const *o, int n, bool log, const char *who, const double *front, int P, const double *ref, double *best_val,
+                  int64_t *best_idx1);
+// ehvi3.hip: what that driver needs of three objectives.  Staged3: what the three-objective kernels read of a front, on the host: the
+// cuts of the three objectives one after the other and the boxes as table rows.  launch_ehvi3: the score of M rows onto out (device),
+// on c's stream; `st` must outlive its copies.
 int front3_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref);
 int samples3_refuse(b7_ctx *c, const char *who, const int *S);
-constexpr int EHVI3_BOXES_MAX = 3 * B7_EHVI3_PMAX + 1;
 struct Staged3 {
   std::vector<double> cuts;
   std::vector<int> box;
   int ncut[3], rows, B;
 };
 void stage3_host(const double *front, int P, const double *ref, Staged3 *st);
-int64_t chunk3(const b7_ctx *c, int rows, int64_t M);
+int launch_ehvi3(b7_ctx *c, bool log, const double *const *mu, const double *const *var, const int *S, const Staged3 &st, int64_t M, double *out);
 // mes.hip: c->ystar laid out for S samples of M rows at K levels; y* of nS samples (sample s at mu / var + s * stride) searched into
 // slots [slot0, slot0 + nS) of that layout, R + 1 launches; the device address of a slot's K values
 int mes_begin(b7_ctx *c, int S, int64_t M, int K);

@@ -217,8 +217,6 @@ void b7_destroy(b7_ctx *c) {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_ehvi)
     if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ev_ehvi3)
-    if (e) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(c->stream);
   delete c;
 }

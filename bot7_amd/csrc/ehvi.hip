@@ -1,28 +1,25 @@
 // Two-objective nomination: the exact expected hypervolume improvement (the two-objective case of Emmerich, Yang & Deutz 2016),
-// marginalised over the hyper samples of two independent GPs, and the kept posterior it reads.  No counterpart in the reference's
-// scores/.  Both objectives are minimised.
+// marginalised over the hyper samples of two independent GPs, linear (b7_ehvi_*) and in log space (b7_logehvi_*), and the kept
+// posterior it reads.  No counterpart in the reference's scores/.  Both objectives are minimised.
 //
 // Front (a_k, b_k), k = 1..P, canonical (bot7hip.h): strictly inside the reference box, a ascending, b descending, both strictly.
 // a_0 = -inf, a_P+1 = r1, b_0 = r2.  Strip k = 0..P is [a_k, a_k+1] x (-inf, b_k]:
 //   score_j = sum_k A_k B_k,   A_k = (1/S1) sum_s max(Psi(a_k+1; s) - Psi(a_k; s), 0),   B_k = (1/S2) sum_t Psi(b_k; t),
-//   Psi(a; mu, sigma) = E[(a - y)+] = (a - mu) Phi(z) + sigma phi(z),  z = (a - mu) / sigma,  Psi(-inf) = 0.
-// Psi in the POSITIVE-TERM FORM of kg.hip's kg_f: with d = a - mu and t = |d| / sigma,
-//   f = max(phi(t) - t erfc(t / sqrt2) / 2, 0)        (= phi(-t) - t Phi(-t), the one subtraction there is); f = 0 for t > 37.5,
-//                                                      where both terms are below the smallest normal double
-//   Psi = sigma f (d <= 0),   d + sigma f (d > 0: two positive terms);   sigma == 0: max(d, 0) exactly.
-// erfc and exp are ocml's, contraction off: one rounded operation per operator.  Order: k ascending, s / t ascending within it,
-// each sum divided once by its sample count; Psi(a_k+1; s) is evaluated once and kept as strip k + 1's Psi(a_k; s).  The clamp at 0
-// keeps every term non-negative (Psi is monotone in a; only rounding can break that), so the score is >= 0.
-// Row classes: any mu or var NaN, any var < 0, in either objective: NaN.  Otherwise finite for finite input, P = 0 included.
+// with Psi, the log-space form of every operation here and its row classes in ehvi_math.h.  Contraction off: one rounded operation per
+// operator.  Order: k ascending, s / t ascending within it, each sum divided once by its sample count; Psi(a_k+1; s) is evaluated once
+// and kept as strip k + 1's Psi(a_k; s).  The clamp at 0 keeps every term non-negative, so the linear score is >= 0.
+// Row classes: any mu or var NaN, any var < 0, in either objective: NaN.  Otherwise finite for finite input, P = 0 included (log
+// space: -inf is legal).
 //
-// ehvi_kernel: one candidate per lane, one wave per workgroup.  The front and ref arrive as two arrays of P + 1 doubles indexed by
-// the strip, a wave-uniform index: scalar loads.  The samples' (mu, sigma) are loaded coalesced from the [S][M] layout once; the
-// first B7_EHVI_SREG samples of each objective and their running Psi(a_k; s) live in registers across the strips (fully unrolled,
-// guarded by the wave-uniform sample counts), samples beyond that in LDS columns of the lane's own ([sample][lane]: no bank
-// conflict, no barrier -- a lane reads only what it wrote), up to B7_EHVI_SMAX per objective: (3 x1 + 2 x2) 512 bytes of dynamic LDS
-// for x1 / x2 samples beyond the registers, 56320 at most.  The summation order is the same on both sides of the limit.
+// ehvi2_kernel<Alg>, Alg = EhviLin or EhviLog: one candidate per lane, one wave per workgroup.  The front and ref arrive as two arrays
+// of P + 1 doubles indexed by the strip, a wave-uniform index: scalar loads.  A sample's NV staged values (mu, sigma; log sigma too in
+// log space) are made once from the coalesced [S][M] layout; the first B7_EHVI_SREG samples of each objective and their running
+// Psi(a_k; s) live in registers across the strips (fully unrolled, guarded by the wave-uniform sample counts), samples beyond that in
+// LDS columns of the lane's own ([value][sample][lane]: no bank conflict, no barrier -- a lane reads only what it wrote), up to
+// B7_EHVI_SMAX per objective: ((NV + 1) x1 + NV x2) 512 bytes of dynamic LDS for x1 / x2 samples beyond the registers: 3 x1 + 2 x2
+// columns, 56 320 bytes at most, linear; 4 x1 + 3 x2, 78 848 at most, in log space (above 64 KiB: opted in).  The summation order is
+// the same on both sides of the limit.
 //
-// The log-space EHVI, which still ranks the rows where this score underflows to 0, is logehvi.hip's b7_logehvi_*.
 // Out of scope, refused by name where it can be asked for: more than two objectives here (three through ehvi3.hip's b7_ehvi3_*, four
 // and more nowhere), correlated objectives / multi-task GPs,
 // batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
@@ -34,29 +31,14 @@
 #include <vector>
 
 #include "b7_internal.h"
+#include "ehvi_math.h"
 
 namespace {
 
 constexpr int SR = B7_EHVI_SREG;
 constexpr int EHVI_LANES = 64;
 
-// f(-t) = phi(t) - t Phi(-t) for t >= 0, clamped at 0.  Beyond t = 37.5 it is 0: there phi(t) and t Phi(-t) fall below 2^-1022,
-// their difference (a 1 / t^2 of either) would be made of the few bits a subnormal has left; t = inf and NaN end here too
-__device__ __forceinline__ double ehvi_f(double t) {
-  if (!(t <= 37.5)) return 0.0;
-  const double pdf = exp((t * t) * -0.5) * 0.39894228040143267794;  // 1/sqrt(2 pi)
-  const double q = erfc(t * 0.70710678118654752440) * 0.5;          // Phi(-t) = erfc(t/sqrt2)/2
-  const double f = pdf - (t * q);
-  return f > 0.0 ? f : 0.0;
-}
-__device__ __forceinline__ double ehvi_psi(double a, double m, double sd) {
-  const double d = a - m;
-  if (sd == 0.0) return d > 0.0 ? d : 0.0;
-  const double g = sd * ehvi_f(fabs(d / sd));
-  return d > 0.0 ? d + g : g;
-}
-
-struct EhviArgs {
+struct Ehvi2Args {
   const double *mu1, *var1, *mu2, *var2;  // [S1][M], [S2][M]
   const double *av, *bv;                  // [P + 1]: a_1 .. a_P, r1 | r2, b_1 .. b_P
   long long M;
@@ -64,72 +46,83 @@ struct EhviArgs {
   double *out;                            // [M]
 };
 
-__global__ void __launch_bounds__(EHVI_LANES) ehvi_kernel(EhviArgs g) {
+template <class Alg>
+__global__ void __launch_bounds__(EHVI_LANES) ehvi2_kernel(Ehvi2Args g) {
   extern __shared__ double sh[];
+  constexpr int NV = Alg::NV;
   const long long j = (long long)blockIdx.x * EHVI_LANES + threadIdx.x;
   if (j >= g.M) return;
   const int x1 = g.S1 > SR ? g.S1 - SR : 0, x2 = g.S2 > SR ? g.S2 - SR : 0;
-  double *lm1 = sh + threadIdx.x, *ls1 = lm1 + x1 * EHVI_LANES, *lp1 = ls1 + x1 * EHVI_LANES;  // sample i of the lane at [i * 64]
-  double *lm2 = lp1 + x1 * EHVI_LANES, *ls2 = lm2 + x2 * EHVI_LANES;
-  double m1[SR], s1[SR], p1[SR], m2[SR], s2[SR];
+  // value c of the lane's LDS sample i at [(c * x + i) * 64]: objective 1's NV values, its running Psi, objective 2's NV values
+  double *l1 = sh + threadIdx.x, *lp1 = l1 + NV * x1 * EHVI_LANES, *l2 = lp1 + x1 * EHVI_LANES;
+  double r1[SR][NV], p1[SR], r2[SR][NV];
   bool bad = false;
+  auto take = [&](const double *mu, const double *var, int s, double *v) {  // sample s of this candidate, and its row class
+    const double m = mu[(long long)s * g.M + j], vv = var[(long long)s * g.M + j];
+    bad = bad || !(vv >= 0.0) || m != m;
+    Alg::stage(m, vv, v);
+  };
 #pragma unroll
   for (int s = 0; s < SR; ++s)
-    if (s < g.S1) {
-      const double m = g.mu1[(long long)s * g.M + j], v = g.var1[(long long)s * g.M + j];
-      bad = bad || !(v >= 0.0) || m != m;
-      m1[s] = m, s1[s] = sqrt(v), p1[s] = 0.0;
-    }
-  for (int s = SR; s < g.S1; ++s) {
-    const double m = g.mu1[(long long)s * g.M + j], v = g.var1[(long long)s * g.M + j];
-    bad = bad || !(v >= 0.0) || m != m;
-    lm1[(s - SR) * EHVI_LANES] = m, ls1[(s - SR) * EHVI_LANES] = sqrt(v), lp1[(s - SR) * EHVI_LANES] = 0.0;
+    if (s < g.S1) take(g.mu1, g.var1, s, r1[s]), p1[s] = Alg::none();
+  for (int s = 0; s < x1; ++s) {
+    double v[NV];
+    take(g.mu1, g.var1, SR + s, v);
+#pragma unroll
+    for (int c = 0; c < NV; ++c) l1[(c * x1 + s) * EHVI_LANES] = v[c];
+    lp1[s * EHVI_LANES] = Alg::none();
   }
 #pragma unroll
   for (int t = 0; t < SR; ++t)
-    if (t < g.S2) {
-      const double m = g.mu2[(long long)t * g.M + j], v = g.var2[(long long)t * g.M + j];
-      bad = bad || !(v >= 0.0) || m != m;
-      m2[t] = m, s2[t] = sqrt(v);
-    }
-  for (int t = SR; t < g.S2; ++t) {
-    const double m = g.mu2[(long long)t * g.M + j], v = g.var2[(long long)t * g.M + j];
-    bad = bad || !(v >= 0.0) || m != m;
-    lm2[(t - SR) * EHVI_LANES] = m, ls2[(t - SR) * EHVI_LANES] = sqrt(v);
+    if (t < g.S2) take(g.mu2, g.var2, t, r2[t]);
+  for (int t = 0; t < x2; ++t) {
+    double v[NV];
+    take(g.mu2, g.var2, SR + t, v);
+#pragma unroll
+    for (int c = 0; c < NV; ++c) l2[(c * x2 + t) * EHVI_LANES] = v[c];
   }
   if (bad) {
     g.out[j] = NAN;
     return;
   }
-  const double n1 = (double)g.S1, n2 = (double)g.S2;
-  double score = 0.0;
+  const double n1 = Alg::count(g.S1), n2 = Alg::count(g.S2);
+  typename Alg::Fold score = Alg::empty();
   for (int k = 0; k <= g.P; ++k) {
     const double a = g.av[k], b = g.bv[k];
-    double A = 0.0, B = 0.0;
+    typename Alg::Fold A = Alg::empty(), B = Alg::empty();
 #pragma unroll
     for (int s = 0; s < SR; ++s)
       if (s < g.S1) {
-        const double p = ehvi_psi(a, m1[s], s1[s]), dd = p - p1[s];
-        A = A + (dd > 0.0 ? dd : 0.0);
+        const double p = Alg::psi(a, r1[s]);
+        Alg::add(A, Alg::diff(p, p1[s]));
         p1[s] = p;
       }
     for (int s = 0; s < x1; ++s) {
-      const double p = ehvi_psi(a, lm1[s * EHVI_LANES], ls1[s * EHVI_LANES]), dd = p - lp1[s * EHVI_LANES];
-      A = A + (dd > 0.0 ? dd : 0.0);
+      double v[NV];
+#pragma unroll
+      for (int c = 0; c < NV; ++c) v[c] = l1[(c * x1 + s) * EHVI_LANES];
+      const double p = Alg::psi(a, v);
+      Alg::add(A, Alg::diff(p, lp1[s * EHVI_LANES]));
       lp1[s * EHVI_LANES] = p;
     }
 #pragma unroll
     for (int t = 0; t < SR; ++t)
-      if (t < g.S2) B = B + ehvi_psi(b, m2[t], s2[t]);
-    for (int t = 0; t < x2; ++t) B = B + ehvi_psi(b, lm2[t * EHVI_LANES], ls2[t * EHVI_LANES]);
-    score = score + ((A / n1) * (B / n2));
+      if (t < g.S2) Alg::add(B, Alg::psi(b, r2[t]));
+    for (int t = 0; t < x2; ++t) {
+      double v[NV];
+#pragma unroll
+      for (int c = 0; c < NV; ++c) v[c] = l2[(c * x2 + t) * EHVI_LANES];
+      Alg::add(B, Alg::psi(b, v));
+    }
+    Alg::add(score, Alg::times(Alg::mean(A, n1), Alg::mean(B, n2)));
   }
-  g.out[j] = score;
+  g.out[j] = Alg::value(score);
 }
 
-size_t ehvi_lds_bytes(int S1, int S2) {
+template <class Alg>
+size_t lds_bytes(int S1, int S2) {
   const int x1 = S1 > SR ? S1 - SR : 0, x2 = S2 > SR ? S2 - SR : 0;
-  return sizeof(double) * EHVI_LANES * (size_t)(3 * x1 + 2 * x2);
+  return sizeof(double) * EHVI_LANES * (size_t)((Alg::NV + 1) * x1 + Alg::NV * x2);
 }
 
 bool finite2(const double *p) { return std::isfinite(p[0]) && std::isfinite(p[1]); }
@@ -150,9 +143,6 @@ int front_defect(const double *front, int P, const double *ref, int *k_out) {
   return 0;
 }
 
-}  // namespace
-
-// front_refuse, front_stage and samples_refuse are logehvi.hip's too (b7_internal.h)
 int front_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref) {
   if (!ref) return b7_fail(c, B7_ERR_INVALID, "%s: ref is NULL", who);
   if (P < 0 || P > B7_EHVI_PMAX) return b7_fail(c, B7_ERR_INVALID, "%s: a front of %d points (0..%d are built)", who, P, B7_EHVI_PMAX);
@@ -185,29 +175,134 @@ int front_stage(b7_ctx *c, const double *front, int P, const double *ref, std::v
   return B7_OK;
 }
 
-namespace {
+int samples_refuse(b7_ctx *c, const char *who, int S1, int S2) {
+  if (S1 < 1 || S1 > B7_EHVI_SMAX || S2 < 1 || S2 > B7_EHVI_SMAX)
+    return b7_fail(c, B7_ERR_INVALID, "%s: S1 = %d, S2 = %d hyper samples (1..%d each are built)", who, S1, S2, B7_EHVI_SMAX);
+  return B7_OK;
+}
 
 // the score of M rows onto out (device), on c's stream; the front staged by front_stage
-int launch_ehvi(b7_ctx *c, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2, int P, int64_t M,
-                double *out) {
-  PhaseScope ps(c, "ehvi");
-  EhviArgs g;
+template <class Alg>
+int launch_ehvi2(b7_ctx *c, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2, int P, int64_t M,
+                 double *out) {
+  PhaseScope ps(c, Alg::phase2);
+  Ehvi2Args g;
   g.mu1 = mu1, g.var1 = var1, g.mu2 = mu2, g.var2 = var2;
   g.av = (const double *)c->ehvi_front.p, g.bv = g.av + (P + 1);
   g.M = (long long)M, g.S1 = S1, g.S2 = S2, g.P = P, g.out = out;
   const int64_t nb = (M + EHVI_LANES - 1) / EHVI_LANES;
-  if (nb > 0x7fffffffLL) return b7_fail(c, B7_ERR_INVALID, "ehvi: %lld rows are more than one launch takes", (long long)M);
-  hipLaunchKernelGGL(ehvi_kernel, dim3((unsigned)nb), dim3(EHVI_LANES), ehvi_lds_bytes(S1, S2), c->stream, g);
+  if (nb > 0x7fffffffLL) return b7_fail(c, B7_ERR_INVALID, "%s: %lld rows are more than one launch takes", Alg::phase2, (long long)M);
+  const size_t lds = lds_bytes<Alg>(S1, S2);
+  // dynamic LDS above the 64 KiB default needs an explicit opt-in, per device (gfx950 has 160 KiB per workgroup)
+  if (lds > (size_t)(64 << 10))
+    B7_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(ehvi2_kernel<Alg>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(ehvi2_kernel<Alg>, dim3((unsigned)nb), dim3(EHVI_LANES), lds, c->stream, g);
   B7_HIP(c, hipGetLastError());
+  return B7_OK;
+}
+
+// b7_ehvi_compute / b7_logehvi_compute: the score of the caller's host arrays
+int ehvi2_compute(b7_ctx *c, bool log, const char *who, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2,
+                  const double *front, int P, const double *ref, int64_t M, double *out) {
+  if (!c) return B7_ERR_INVALID;
+  if (M < 0 || (M > 0 && (!mu1 || !var1 || !mu2 || !var2 || !out))) return b7_fail(c, B7_ERR_INVALID, "%s: bad arguments (M >= 0, arrays required)", who);
+  B7_TRY(samples_refuse(c, who, S1, S2));
+  B7_TRY(front_refuse(c, who, front, P, ref));
+  if (M == 0) return B7_OK;
+  B7_HIP(c, hipSetDevice(c->device));
+  const size_t m = (size_t)M, n1 = (size_t)S1 * m, n2 = (size_t)S2 * m;
+  B7_TRY(b7_ensure(c, c->ehvi_user, sizeof(double) * (2 * n1 + 2 * n2 + m)));  // a buffer of its own: the kept posterior stays
+  double *d1 = (double *)c->ehvi_user.p, *v1 = d1 + n1, *d2 = v1 + n1, *v2 = d2 + n2, *od = v2 + n2;
+  std::vector<double> fh;
+  B7_TRY(front_stage(c, front, P, ref, &fh));
+  B7_HIP(c, hipMemcpyAsync(d1, mu1, sizeof(double) * n1, hipMemcpyHostToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync(v1, var1, sizeof(double) * n1, hipMemcpyHostToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync(d2, mu2, sizeof(double) * n2, hipMemcpyHostToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync(v2, var2, sizeof(double) * n2, hipMemcpyHostToDevice, c->stream));
+  B7_TRY(log ? launch_ehvi2<EhviLog>(c, d1, v1, S1, d2, v2, S2, P, M, od) : launch_ehvi2<EhviLin>(c, d1, v1, S1, d2, v2, S2, P, M, od));
+  B7_HIP(c, hipMemcpyAsync(out, od, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipStreamSynchronize(c->stream));  // the caller's arrays and the staged front are consumed
+  return B7_OK;
+}
+
+// The streams of a nomination's contexts o[0 .. n - 1] are ordered by events both ways, as b7_feas_add_acc orders them.  before: the
+// first context's stream waits for what every other stream has been given (events 0 .. n - 2); after: whatever the other contexts
+// enqueue next waits for the kernels (event n - 1).  A context that appears twice is waited on once.
+int ehvi_order(b7_ctx *const *o, int n, bool before) {
+  b7_ctx *c = o[0];
+  bool wait[3] = {false, false, false}, any = false;
+  for (int m = 1; m < n; ++m) {
+    wait[m] = true;
+    for (int q = 0; q < m; ++q) wait[m] = wait[m] && o[m] != o[q];
+    any = any || wait[m];
+  }
+  if (!any) return B7_OK;
+  if (before) {
+    for (hipEvent_t &e : c->ev_ehvi)
+      if (!e) B7_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (int m = 1; m < n; ++m)
+      if (wait[m]) {
+        B7_HIP(c, hipEventRecord(c->ev_ehvi[m - 1], o[m]->stream));
+        B7_HIP(c, hipStreamWaitEvent(c->stream, c->ev_ehvi[m - 1], 0));
+      }
+  } else {
+    B7_HIP(c, hipEventRecord(c->ev_ehvi[n - 1], c->stream));
+    for (int m = 1; m < n; ++m)
+      if (wait[m]) B7_HIP(c, hipStreamWaitEvent(o[m]->stream, c->ev_ehvi[n - 1], 0));
+  }
   return B7_OK;
 }
 
 }  // namespace
 
-int samples_refuse(b7_ctx *c, const char *who, int S1, int S2) {
-  if (S1 < 1 || S1 > B7_EHVI_SMAX || S2 < 1 || S2 > B7_EHVI_SMAX)
-    return b7_fail(c, B7_ERR_INVALID, "%s: S1 = %d, S2 = %d hyper samples (1..%d each are built)", who, S1, S2, B7_EHVI_SMAX);
-  return B7_OK;
+int ehvi_nominate(b7_ctx *const *o, int n, bool log, const char *who, const double *front, int P, const double *ref, double *best_val,
+                  int64_t *best_idx1) {
+  static const char *const nth[3] = {"first", "second", "third"};
+  b7_ctx *c = o[0];
+  if (!c) return B7_ERR_INVALID;
+  for (int m = 1; m < n; ++m)
+    if (!o[m]) return b7_fail(c, B7_ERR_INVALID, "%s: the %s objective's context is NULL", who, nth[m]);
+  if (!best_val || !best_idx1) return b7_fail(c, B7_ERR_INVALID, "%s: NULL argument (best_val and best_idx1 are needed)", who);
+  for (int m = 0; m < n; ++m)
+    if (o[m]->group)
+      return b7_fail(c, B7_ERR_STATE, "%s: a context belongs to a group (%s objectives over a sharded grid are not built)", who, n == 2 ? "two" : "three");
+  for (int m = 1; m < n; ++m)
+    if (o[m]->device != c->device)
+      return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: the %s objective's context is on device %d, this one on device %d (a posterior across devices is not built)",
+                     who, nth[m], o[m]->device, c->device);
+  for (int m = 0; m < n; ++m)
+    if (!o[m]->post_valid)  // (the two-objective calls' first message has always been the shorter one)
+      return b7_fail(c, B7_ERR_STATE, "%s: no kept posterior of the %s objective (call b7_eval_posterior%s; a change of the grid or the data forgets it)",
+                     who, nth[m], n == 2 && m == 0 ? "" : " on its context");
+  for (int m = 1; m < n; ++m)
+    if (o[m]->post_M != c->post_M)
+      return b7_fail(c, B7_ERR_INVALID, "%s: the %s objective's grid has %lld rows, this one %lld", who, nth[m], (long long)o[m]->post_M,
+                     (long long)c->post_M);
+  int S[3] = {0, 0, 0};
+  for (int m = 0; m < n; ++m) S[m] = o[m]->post_S;
+  B7_TRY(n == 2 ? samples_refuse(c, who, S[0], S[1]) : samples3_refuse(c, who, S));
+  B7_TRY(n == 2 ? front_refuse(c, who, front, P, ref) : front3_refuse(c, who, front, P, ref));
+  B7_HIP(c, hipSetDevice(c->device));
+  const int64_t M = c->post_M;  // == c->M: a grid change would have forgotten the posterior
+  const double *mu[3], *var[3];
+  for (int m = 0; m < n; ++m) mu[m] = (const double *)o[m]->post.p, var[m] = mu[m] + (size_t)S[m] * (size_t)M;
+  B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)M));
+  double *acc = (double *)c->acc.p;
+  // the staged front's host block outlives its copy: launch_finish waits
+  std::vector<double> fh;
+  Staged3 st;
+  if (n == 2) B7_TRY(front_stage(c, front, P, ref, &fh));
+  else stage3_host(front, P, ref, &st);
+  B7_TRY(ehvi_order(o, n, true));
+  // the accumulator is declared written (linear: zeros; log space: a log accumulator); the kernel then writes every row of it
+  if (log) acc_declare_log_written(c);
+  else B7_TRY(acc_write_zeros(c));
+  if (n == 3) B7_TRY(launch_ehvi3(c, log, mu, var, S, st, M, acc));
+  else if (log) B7_TRY(launch_ehvi2<EhviLog>(c, mu[0], var[0], S[0], mu[1], var[1], S[1], P, M, acc));
+  else B7_TRY(launch_ehvi2<EhviLin>(c, mu[0], var[0], S[0], mu[1], var[1], S[1], P, M, acc));
+  B7_TRY(ehvi_order(o, n, false));
+  // score:max(1) of the accumulator, the divisor 1 (log space: log 1 == 0 is subtracted); waits, so the staged front is consumed
+  return launch_finish(c, acc, M, 1.0, best_val, best_idx1, log);
 }
 
 extern "C" {
@@ -300,65 +395,23 @@ int b7_hypervolume2(const double *front, int P, const double *ref, double *hv_ou
 
 int b7_ehvi_compute(b7_ctx *c, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2,
                     const double *front, int P, const double *ref, int64_t M, double *out) {
-  if (!c) return B7_ERR_INVALID;
-  if (M < 0 || (M > 0 && (!mu1 || !var1 || !mu2 || !var2 || !out))) return b7_fail(c, B7_ERR_INVALID, "ehvi_compute: bad arguments (M >= 0, arrays required)");
-  B7_TRY(samples_refuse(c, "ehvi_compute", S1, S2));
-  B7_TRY(front_refuse(c, "ehvi_compute", front, P, ref));
-  if (M == 0) return B7_OK;
-  B7_HIP(c, hipSetDevice(c->device));
-  const size_t m = (size_t)M, n1 = (size_t)S1 * m, n2 = (size_t)S2 * m;
-  B7_TRY(b7_ensure(c, c->ehvi_user, sizeof(double) * (2 * n1 + 2 * n2 + m)));  // a buffer of its own: the kept posterior stays
-  double *d1 = (double *)c->ehvi_user.p, *v1 = d1 + n1, *d2 = v1 + n1, *v2 = d2 + n2, *od = v2 + n2;
-  std::vector<double> fh;
-  B7_TRY(front_stage(c, front, P, ref, &fh));
-  B7_HIP(c, hipMemcpyAsync(d1, mu1, sizeof(double) * n1, hipMemcpyHostToDevice, c->stream));
-  B7_HIP(c, hipMemcpyAsync(v1, var1, sizeof(double) * n1, hipMemcpyHostToDevice, c->stream));
-  B7_HIP(c, hipMemcpyAsync(d2, mu2, sizeof(double) * n2, hipMemcpyHostToDevice, c->stream));
-  B7_HIP(c, hipMemcpyAsync(v2, var2, sizeof(double) * n2, hipMemcpyHostToDevice, c->stream));
-  B7_TRY(launch_ehvi(c, d1, v1, S1, d2, v2, S2, P, M, od));
-  B7_HIP(c, hipMemcpyAsync(out, od, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
-  B7_HIP(c, hipStreamSynchronize(c->stream));  // the caller's arrays and the staged front are consumed
-  return B7_OK;
+  return ehvi2_compute(c, false, "ehvi_compute", mu1, var1, S1, mu2, var2, S2, front, P, ref, M, out);
+}
+
+int b7_logehvi_compute(b7_ctx *c, const double *mu1, const double *var1, int S1, const double *mu2, const double *var2, int S2,
+                       const double *front, int P, const double *ref, int64_t M, double *out) {
+  return ehvi2_compute(c, true, "logehvi_compute", mu1, var1, S1, mu2, var2, S2, front, P, ref, M, out);
 }
 
 int b7_ehvi_nominate(b7_ctx *c, b7_ctx *other, const double *front, int P, const double *ref, double *best_val, int64_t *best_idx1) {
-  if (!c) return B7_ERR_INVALID;
-  if (!other) return b7_fail(c, B7_ERR_INVALID, "ehvi_nominate: the second objective's context is NULL");
-  if (!best_val || !best_idx1) return b7_fail(c, B7_ERR_INVALID, "ehvi_nominate: NULL argument (best_val and best_idx1 are needed)");
-  if (c->group || other->group)
-    return b7_fail(c, B7_ERR_STATE, "ehvi_nominate: a context belongs to a group (two objectives over a sharded grid are not built)");
-  if (other->device != c->device)
-    return b7_fail(c, B7_ERR_UNSUPPORTED, "ehvi_nominate: the second objective's context is on device %d, this one on device %d (a posterior across devices is not built)", other->device, c->device);
-  if (!c->post_valid)
-    return b7_fail(c, B7_ERR_STATE, "ehvi_nominate: no kept posterior of the first objective (call b7_eval_posterior; a change of the grid or the data forgets it)");
-  if (!other->post_valid)
-    return b7_fail(c, B7_ERR_STATE, "ehvi_nominate: no kept posterior of the second objective (call b7_eval_posterior on its context; a change of the grid or the data forgets it)");
-  if (other->post_M != c->post_M)
-    return b7_fail(c, B7_ERR_INVALID, "ehvi_nominate: the second objective's grid has %lld rows, this one %lld", (long long)other->post_M, (long long)c->post_M);
-  B7_TRY(samples_refuse(c, "ehvi_nominate", c->post_S, other->post_S));
-  B7_TRY(front_refuse(c, "ehvi_nominate", front, P, ref));
-  B7_HIP(c, hipSetDevice(c->device));
-  const int64_t M = c->post_M;  // == c->M: a grid change would have forgotten the posterior
-  const size_t SM1 = (size_t)c->post_S * (size_t)M, SM2 = (size_t)other->post_S * (size_t)M;
-  const double *mu1 = (const double *)c->post.p, *mu2 = (const double *)other->post.p;
-  B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)M));
-  std::vector<double> fh;
-  B7_TRY(front_stage(c, front, P, ref, &fh));
-  // The two streams are ordered by events both ways, as b7_feas_add_acc orders them: the kernel waits for what the other stream
-  // has been given, and whatever the other context enqueues next waits for the kernel.
-  if (other != c) {
-    for (hipEvent_t &e : c->ev_ehvi)
-      if (!e) B7_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    B7_HIP(c, hipEventRecord(c->ev_ehvi[0], other->stream));
-    B7_HIP(c, hipStreamWaitEvent(c->stream, c->ev_ehvi[0], 0));
-  }
-  B7_TRY(acc_write_zeros(c));  // the accumulator is declared written; the kernel then writes every row of it
-  B7_TRY(launch_ehvi(c, mu1, mu1 + SM1, c->post_S, mu2, mu2 + SM2, other->post_S, P, M, (double *)c->acc.p));
-  if (other != c) {
-    B7_HIP(c, hipEventRecord(c->ev_ehvi[1], c->stream));
-    B7_HIP(c, hipStreamWaitEvent(other->stream, c->ev_ehvi[1], 0));
-  }
-  return launch_finish(c, (double *)c->acc.p, M, 1.0, best_val, best_idx1);  // score:max(1); waits, so the staged front is consumed
+  b7_ctx *const o[2] = {c, other};
+  return ehvi_nominate(o, 2, false, "ehvi_nominate", front, P, ref, best_val, best_idx1);
+}
+
+int b7_logehvi_nominate(b7_ctx *c, b7_ctx *other, const double *front, int P, const double *ref, double *best_val, int64_t *best_idx1) {
+  b7_ctx *const o[2] = {c, other};
+  return ehvi_nominate(o, 2, true, "logehvi_nominate", front, P, ref, best_val, best_idx1);
 }
 
 }  // extern "C"
+

@@ -1,22 +1,25 @@
 // Three-objective nomination: the exact expected hypervolume improvement over a box decomposition of the non-dominated region,
-// marginalised over the hyper samples of three independent GPs.  No counterpart in the reference's scores/.  All objectives are
-// minimised.  The kept posteriors it reads are b7_eval_posterior's (ehvi.hip).
+// marginalised over the hyper samples of three independent GPs, linear (b7_ehvi3_*) and in log space (b7_logehvi3_*).
+// No counterpart in the reference's scores/.  All objectives are minimised.  The kept posteriors it reads are b7_eval_posterior's
+// (ehvi.hip).
 //
 // The region that no front point dominates, inside (-inf, r], is cut into disjoint boxes [l_b, u_b] with l_b3 = -inf
 // (b7_nondominated_boxes3 below: the front swept in the order of the third objective over a two-dimensional staircase, 2P + 1 boxes in
-// general position).  With Psi(a; mu, sigma) = E[(a - y)+] (ehvi.hip's ehvi_psi, copied here so that ehvi_kernel's text stays as it is)
+// general position).  With Psi(a; mu, sigma) = E[(a - y)+] (ehvi_math.h's ehvi_psi)
 //   T_m(c) = (1/S_m) sum_s Psi(c; mu_ms, sigma_ms),   T_m(-inf) = 0
 //   score  = sum_b max(T_1(u_b1) - T_1(l_b1), 0) max(T_2(u_b2) - T_2(l_b2), 0) T_3(u_b3)
 // exactly, without random numbers; every term is non-negative.  The volume of the dominated region is never subtracted from the box's.
 // Order: s ascending within a T, each T divided once by its sample count; boxes in the decomposition's order, per box
-// ((d1 * d2) * T_3) added to the running sum; contraction off, erfc and exp ocml's: one rounded operation per operator.
+// ((d1 * d2) * T_3) added to the running sum; contraction off, erfc and exp ocml's: one rounded operation per operator.  The log-space
+// form of each of these operations is ehvi_math.h's EhviLog: ((ldiff + ldiff) + LT_3) folded by log-sum-exp.
 // Row classes: any mu or var NaN, any var < 0, in any objective: NaN.  Otherwise finite for finite input and >= 0, P = 0 included:
-// T_1(r1) T_2(r2) T_3(r3).
+// T_1(r1) T_2(r2) T_3(r3) (log space: -inf is legal).
 //
-// Two kernels per chunk of candidates, on the context's stream:
+// Two kernels per chunk of candidates, on the context's stream, each one body for Alg = EhviLin and EhviLog:
 //   ehvi3_table_kernel  T[row][candidate] for the rows of the three objectives one after the other; an objective's rows are a zero row
 //                       (-inf) and its distinct cuts ascending, r_m last.  One work item per (candidate, block of EHVI3_CB cuts of one
-//                       objective): the samples are walked once, EHVI3_CB running sums in registers, stores coalesced across candidates.
+//                       objective): the samples are walked once, EHVI3_CB running sums (log space: running (m, acc) pairs) in
+//                       registers, stores coalesced across candidates.
 //                       Cut block 0 of an objective also writes the zero row and the objective's row-class flag.
 //   ehvi3_box_kernel    one candidate per lane, one wave per workgroup; the boxes as five table rows each (wave-uniform: ordinary
 //                       loads of a small device array that come out as scalar loads), five coalesced table reads and the clamped
@@ -29,7 +32,6 @@
 // An LDS-resident table ([cut][lane], one wave per workgroup) would cap P near 41 in 64 KiB and was not built: fronts up to
 // B7_EHVI3_PMAX need the table in memory either way.
 //
-// The log-space EHVI, which still ranks the rows where this score underflows to 0, is logehvi.hip's b7_logehvi3_* over the same boxes.
 // Out of scope, refused by name where it can be asked for: four or more objectives, correlated objectives / multi-task GPs,
 // batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
 // trust regions.
@@ -41,6 +43,7 @@
 #include <vector>
 
 #include "b7_internal.h"
+#include "ehvi_math.h"
 
 namespace {
 
@@ -51,32 +54,19 @@ constexpr int EHVI3_CB = 8;                            // cuts per work item of 
 #define B7_EHVI3_TABLE_MIB 256                         // (a build-time switch for the comparison of 16 / 64 / 256 / 1024 in DESIGN section 8 only)
 #endif
 constexpr size_t EHVI3_TABLE_BYTES = (size_t)B7_EHVI3_TABLE_MIB << 20;  // the table's share of a chunk, at most
-
-// ehvi.hip's ehvi_f / ehvi_psi, operation for operation
-__device__ __forceinline__ double ehvi3_f(double t) {
-  if (!(t <= 37.5)) return 0.0;
-  const double pdf = exp((t * t) * -0.5) * 0.39894228040143267794;  // 1/sqrt(2 pi)
-  const double q = erfc(t * 0.70710678118654752440) * 0.5;          // Phi(-t) = erfc(t/sqrt2)/2
-  const double f = pdf - (t * q);
-  return f > 0.0 ? f : 0.0;
-}
-__device__ __forceinline__ double ehvi3_psi(double a, double m, double sd) {
-  const double d = a - m;
-  if (sd == 0.0) return d > 0.0 ? d : 0.0;
-  const double g = sd * ehvi3_f(fabs(d / sd));
-  return d > 0.0 ? d + g : g;
-}
+constexpr int EHVI3_BOXES_MAX = 3 * B7_EHVI3_PMAX + 1;
 
 struct Ehvi3TableArgs {
   const double *mu[3], *var[3];  // [S_m][ld], already moved to the chunk's first candidate
   long long ld;                  // candidates of the whole posterior
   const double *cuts;            // cuts of objective 0 | 1 | 2, each ascending and distinct, r_m last
   int S[3], ncut[3];
-  double *T;                     // [rows][C]
+  double *T;                     // [rows][C]: T, or LT in log space
   int *flag;                     // [3][C]: the objective's row class (1: NaN)
   long long C, n;                // the table's row stride, the candidates of this chunk (n <= C)
 };
 
+template <class Alg>
 __global__ void __launch_bounds__(EHVI3_LANES) ehvi3_table_kernel(Ehvi3TableArgs g) {
   const long long j = (long long)blockIdx.x * EHVI3_LANES + threadIdx.x;
   if (j >= g.n) return;
@@ -88,25 +78,27 @@ __global__ void __launch_bounds__(EHVI3_LANES) ehvi3_table_kernel(Ehvi3TableArgs
   const int k0 = y * EHVI3_CB, nk = g.ncut[m] - k0;  // this item's cuts: k0 .. k0 + min(nk, CB) - 1
   const double *mu = g.mu[m], *var = g.var[m];
   const int S = g.S[m];
-  double cv[EHVI3_CB], acc[EHVI3_CB];
+  double cv[EHVI3_CB];
+  typename Alg::Fold acc[EHVI3_CB];
 #pragma unroll
-  for (int k = 0; k < EHVI3_CB; ++k) cv[k] = k < nk ? g.cuts[cut0 + k0 + k] : 0.0, acc[k] = 0.0;
+  for (int k = 0; k < EHVI3_CB; ++k) cv[k] = k < nk ? g.cuts[cut0 + k0 + k] : 0.0, acc[k] = Alg::empty();
   bool bad = false;
   for (int s = 0; s < S; ++s) {
     const double mm = mu[(long long)s * g.ld + j], v = var[(long long)s * g.ld + j];
     bad = bad || !(v >= 0.0) || mm != mm;
-    const double sd = sqrt(v);
+    double sv[Alg::NV];
+    Alg::stage(mm, v, sv);
 #pragma unroll
     for (int k = 0; k < EHVI3_CB; ++k)
-      if (k < nk) acc[k] = acc[k] + ehvi3_psi(cv[k], mm, sd);
+      if (k < nk) Alg::add(acc[k], Alg::psi(cv[k], sv));
   }
-  const double n = (double)S;
+  const double n = Alg::count(S);
   double *Trow = g.T + (long long)(row0 + 1 + k0) * g.C + j;  // row0: the objective's zero row
 #pragma unroll
   for (int k = 0; k < EHVI3_CB; ++k)
-    if (k < nk) Trow[(long long)k * g.C] = acc[k] / n;
+    if (k < nk) Trow[(long long)k * g.C] = Alg::mean(acc[k], n);
   if (y == 0) {
-    g.T[(long long)row0 * g.C + j] = 0.0;
+    g.T[(long long)row0 * g.C + j] = Alg::none();
     g.flag[(long long)m * g.C + j] = bad ? 1 : 0;
   }
 }
@@ -120,6 +112,7 @@ struct Ehvi3BoxArgs {
   double *out;     // [n]
 };
 
+template <class Alg>
 __global__ void __launch_bounds__(EHVI3_BOX_LANES) ehvi3_box_kernel(Ehvi3BoxArgs g) {
   const long long j = (long long)blockIdx.x * EHVI3_BOX_LANES + threadIdx.x;
   if (j >= g.n) return;
@@ -128,18 +121,16 @@ __global__ void __launch_bounds__(EHVI3_BOX_LANES) ehvi3_box_kernel(Ehvi3BoxArgs
     return;
   }
   const double *T = g.T + j;
-  double score = 0.0;
+  typename Alg::Fold score = Alg::empty();
   // four boxes' reads in flight: a lane's box walk is a chain of memory round trips, and the sum stays in box order
 #pragma unroll 4
   for (int b = 0; b < g.B; ++b) {
     const int *q = g.box + 5 * b;
     const double l1 = T[(long long)q[0] * g.C], u1 = T[(long long)q[1] * g.C], l2 = T[(long long)q[2] * g.C], u2 = T[(long long)q[3] * g.C];
     const double u3 = T[(long long)q[4] * g.C];
-    double d1 = u1 - l1, d2 = u2 - l2;
-    d1 = d1 > 0.0 ? d1 : 0.0, d2 = d2 > 0.0 ? d2 : 0.0;
-    score = score + ((d1 * d2) * u3);
+    Alg::add(score, Alg::times(Alg::times(Alg::diff(u1, l1), Alg::diff(u2, l2)), u3));
   }
-  g.out[j] = score;
+  g.out[j] = Alg::value(score);
 }
 
 bool finite3(const double *p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
@@ -175,7 +166,7 @@ int front3_defect(const double *front, int P, const double *ref, int *k_out, int
 
 }  // namespace
 
-// front3_refuse, samples3_refuse, stage3_host and chunk3 are logehvi.hip's too (b7_internal.h, with Staged3 and EHVI3_BOXES_MAX)
+// front3_refuse, samples3_refuse, stage3_host and launch_ehvi3 are ehvi.hip's ehvi_nominate's too (b7_internal.h, with Staged3)
 int front3_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref) {
   if (!ref) return b7_fail(c, B7_ERR_INVALID, "%s: ref is NULL", who);
   if (P < 0 || P > B7_EHVI3_PMAX) return b7_fail(c, B7_ERR_INVALID, "%s: a front of %d points (0..%d are built)", who, P, B7_EHVI3_PMAX);
@@ -268,6 +259,8 @@ void stage3_host(const double *front, int P, const double *ref, Staged3 *st) {
   }
 }
 
+namespace {
+
 // candidates per chunk: the table within min(workspace, EHVI3_TABLE_BYTES), whole waves of the table kernel, at least one
 int64_t chunk3(const b7_ctx *c, int rows, int64_t M) {
   const size_t per = sizeof(double) * (size_t)rows + 3 * sizeof(int);
@@ -276,17 +269,17 @@ int64_t chunk3(const b7_ctx *c, int rows, int64_t M) {
   return std::min<int64_t>(C, round_up(M, EHVI3_LANES));
 }
 
-namespace {
-
 // the score of M rows onto out (device), on c's stream: mu[m] / var[m] [S_m][M] on the device.  The host block `st` must outlive the
 // copies (the callers wait)
-int launch_ehvi3(b7_ctx *c, const double *const *mu, const double *const *var, const int *S, const Staged3 &st, int64_t M, double *out) {
-  if (M > 0x7fffffffLL * EHVI3_LANES) return b7_fail(c, B7_ERR_INVALID, "ehvi3: %lld rows are more than one launch takes", (long long)M);
+template <class Alg>
+int launch_ehvi3_as(b7_ctx *c, const double *const *mu, const double *const *var, const int *S, const Staged3 &st, int64_t M, double *out) {
+  const char *who = Alg::name3;
+  if (M > 0x7fffffffLL * EHVI3_LANES) return b7_fail(c, B7_ERR_INVALID, "%s: %lld rows are more than one launch takes", who, (long long)M);
   // what the kernels index by: every box row inside the table, the box and cut counts inside their staging
   for (int r : st.box)
-    if (r < 0 || r >= st.rows) return b7_fail(c, B7_ERR_INVALID, "ehvi3: a box edge is none of the cuts (row %d of %d)", r, st.rows);
+    if (r < 0 || r >= st.rows) return b7_fail(c, B7_ERR_INVALID, "%s: a box edge is none of the cuts (row %d of %d)", who, r, st.rows);
   if (st.B > EHVI3_BOXES_MAX || st.rows > 3 * (B7_EHVI3_PMAX + 2))
-    return b7_fail(c, B7_ERR_INVALID, "ehvi3: %d boxes over %d table rows are more than a front of %d points gives", st.B, st.rows, B7_EHVI3_PMAX);
+    return b7_fail(c, B7_ERR_INVALID, "%s: %d boxes over %d table rows are more than a front of %d points gives", who, st.B, st.rows, B7_EHVI3_PMAX);
   const size_t cut_bytes = sizeof(double) * (size_t)(3 * (B7_EHVI3_PMAX + 1));
   B7_TRY(b7_ensure(c, c->ehvi3_front, cut_bytes + sizeof(int) * 5 * (size_t)EHVI3_BOXES_MAX));
   double *cuts_d = (double *)c->ehvi3_front.p;
@@ -306,15 +299,15 @@ int launch_ehvi3(b7_ctx *c, const double *const *mu, const double *const *var, c
     t.T = (double *)c->ehvi3_table.p, t.flag = (int *)((char *)c->ehvi3_table.p + tab_bytes);
     t.C = (long long)C, t.n = (long long)n;
     {
-      PhaseScope ps(c, "ehvi3_tab");
-      hipLaunchKernelGGL(ehvi3_table_kernel, dim3((unsigned)((n + EHVI3_LANES - 1) / EHVI3_LANES), (unsigned)nblk), dim3(EHVI3_LANES), 0, c->stream, t);
+      PhaseScope ps(c, Alg::phase3_tab);
+      hipLaunchKernelGGL(ehvi3_table_kernel<Alg>, dim3((unsigned)((n + EHVI3_LANES - 1) / EHVI3_LANES), (unsigned)nblk), dim3(EHVI3_LANES), 0, c->stream, t);
       B7_HIP(c, hipGetLastError());
     }
     Ehvi3BoxArgs b;
     b.T = t.T, b.flag = t.flag, b.box = box_d, b.B = st.B, b.C = t.C, b.n = t.n, b.out = out + j0;
     {
-      PhaseScope ps(c, "ehvi3_box");
-      hipLaunchKernelGGL(ehvi3_box_kernel, dim3((unsigned)((n + EHVI3_BOX_LANES - 1) / EHVI3_BOX_LANES)), dim3(EHVI3_BOX_LANES), 0, c->stream, b);
+      PhaseScope ps(c, Alg::phase3_box);
+      hipLaunchKernelGGL(ehvi3_box_kernel<Alg>, dim3((unsigned)((n + EHVI3_BOX_LANES - 1) / EHVI3_BOX_LANES)), dim3(EHVI3_BOX_LANES), 0, c->stream, b);
       B7_HIP(c, hipGetLastError());
     }
   }
@@ -338,6 +331,39 @@ double area2(std::vector<std::pair<double, double>> pts, double r1, double r2) {
 }
 
 }  // namespace
+
+int launch_ehvi3(b7_ctx *c, bool log, const double *const *mu, const double *const *var, const int *S, const Staged3 &st, int64_t M, double *out) {
+  return log ? launch_ehvi3_as<EhviLog>(c, mu, var, S, st, M, out) : launch_ehvi3_as<EhviLin>(c, mu, var, S, st, M, out);
+}
+
+// b7_ehvi3_compute / b7_logehvi3_compute: the score of the caller's host arrays
+static int ehvi3_compute(b7_ctx *c, bool log, const char *who, const double *const *mu, const double *const *var, const int *S, const double *front,
+                         int P, const double *ref, int64_t M, double *out) {
+  if (!c) return B7_ERR_INVALID;
+  if (!mu || !var || !S) return b7_fail(c, B7_ERR_INVALID, "%s: NULL argument (mu, var and S of three objectives are needed)", who);
+  if (M < 0 || (M > 0 && (!mu[0] || !var[0] || !mu[1] || !var[1] || !mu[2] || !var[2] || !out)))
+    return b7_fail(c, B7_ERR_INVALID, "%s: bad arguments (M >= 0, arrays required)", who);
+  B7_TRY(samples3_refuse(c, who, S));
+  B7_TRY(front3_refuse(c, who, front, P, ref));
+  if (M == 0) return B7_OK;
+  B7_HIP(c, hipSetDevice(c->device));
+  const size_t m = (size_t)M, total = (size_t)(S[0] + S[1] + S[2]) * m;
+  B7_TRY(b7_ensure(c, c->ehvi3_user, sizeof(double) * (2 * total + m)));  // a buffer of its own: the kept posterior stays
+  double *p = (double *)c->ehvi3_user.p;
+  const double *dmu[3], *dvar[3];
+  for (int o = 0; o < 3; ++o) {
+    const size_t n = (size_t)S[o] * m;
+    B7_HIP(c, hipMemcpyAsync(p, mu[o], sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    B7_HIP(c, hipMemcpyAsync(p + n, var[o], sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    dmu[o] = p, dvar[o] = p + n, p += 2 * n;
+  }
+  Staged3 st;
+  stage3_host(front, P, ref, &st);
+  B7_TRY(launch_ehvi3(c, log, dmu, dvar, S, st, M, p));
+  B7_HIP(c, hipMemcpyAsync(out, p, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipStreamSynchronize(c->stream));  // the caller's arrays and the staged front are consumed
+  return B7_OK;
+}
 
 extern "C" {
 
@@ -402,88 +428,27 @@ int b7_hypervolume3(const double *front, int P, const double *ref, double *hv_ou
   return B7_OK;
 }
 
+
 int b7_ehvi3_compute(b7_ctx *c, const double *const *mu, const double *const *var, const int *S, const double *front, int P, const double *ref,
                      int64_t M, double *out) {
-  if (!c) return B7_ERR_INVALID;
-  if (!mu || !var || !S) return b7_fail(c, B7_ERR_INVALID, "ehvi3_compute: NULL argument (mu, var and S of three objectives are needed)");
-  if (M < 0 || (M > 0 && (!mu[0] || !var[0] || !mu[1] || !var[1] || !mu[2] || !var[2] || !out)))
-    return b7_fail(c, B7_ERR_INVALID, "ehvi3_compute: bad arguments (M >= 0, arrays required)");
-  B7_TRY(samples3_refuse(c, "ehvi3_compute", S));
-  B7_TRY(front3_refuse(c, "ehvi3_compute", front, P, ref));
-  if (M == 0) return B7_OK;
-  B7_HIP(c, hipSetDevice(c->device));
-  const size_t m = (size_t)M, total = (size_t)(S[0] + S[1] + S[2]) * m;
-  B7_TRY(b7_ensure(c, c->ehvi3_user, sizeof(double) * (2 * total + m)));  // a buffer of its own: the kept posterior stays
-  double *p = (double *)c->ehvi3_user.p;
-  const double *dmu[3], *dvar[3];
-  for (int o = 0; o < 3; ++o) {
-    const size_t n = (size_t)S[o] * m;
-    B7_HIP(c, hipMemcpyAsync(p, mu[o], sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    B7_HIP(c, hipMemcpyAsync(p + n, var[o], sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    dmu[o] = p, dvar[o] = p + n, p += 2 * n;
-  }
-  Staged3 st;
-  stage3_host(front, P, ref, &st);
-  B7_TRY(launch_ehvi3(c, dmu, dvar, S, st, M, p));
-  B7_HIP(c, hipMemcpyAsync(out, p, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
-  B7_HIP(c, hipStreamSynchronize(c->stream));  // the caller's arrays and the staged front are consumed
-  return B7_OK;
+  return ehvi3_compute(c, false, "ehvi3_compute", mu, var, S, front, P, ref, M, out);
+}
+
+int b7_logehvi3_compute(b7_ctx *c, const double *const *mu, const double *const *var, const int *S, const double *front, int P, const double *ref,
+                        int64_t M, double *out) {
+  return ehvi3_compute(c, true, "logehvi3_compute", mu, var, S, front, P, ref, M, out);
 }
 
 int b7_ehvi3_nominate(b7_ctx *c, b7_ctx *other2, b7_ctx *other3, const double *front, int P, const double *ref, double *best_val,
                       int64_t *best_idx1) {
-  if (!c) return B7_ERR_INVALID;
-  if (!other2) return b7_fail(c, B7_ERR_INVALID, "ehvi3_nominate: the second objective's context is NULL");
-  if (!other3) return b7_fail(c, B7_ERR_INVALID, "ehvi3_nominate: the third objective's context is NULL");
-  if (!best_val || !best_idx1) return b7_fail(c, B7_ERR_INVALID, "ehvi3_nominate: NULL argument (best_val and best_idx1 are needed)");
-  b7_ctx *o[3] = {c, other2, other3};
-  static const char *const nth[3] = {"first", "second", "third"};
-  if (c->group || other2->group || other3->group)
-    return b7_fail(c, B7_ERR_STATE, "ehvi3_nominate: a context belongs to a group (three objectives over a sharded grid are not built)");
-  for (int m = 1; m < 3; ++m)
-    if (o[m]->device != c->device)
-      return b7_fail(c, B7_ERR_UNSUPPORTED, "ehvi3_nominate: the %s objective's context is on device %d, this one on device %d (a posterior across devices is not built)",
-                     nth[m], o[m]->device, c->device);
-  for (int m = 0; m < 3; ++m)
-    if (!o[m]->post_valid)
-      return b7_fail(c, B7_ERR_STATE, "ehvi3_nominate: no kept posterior of the %s objective (call b7_eval_posterior on its context; a change of the grid or the data forgets it)",
-                     nth[m]);
-  for (int m = 1; m < 3; ++m)
-    if (o[m]->post_M != c->post_M)
-      return b7_fail(c, B7_ERR_INVALID, "ehvi3_nominate: the %s objective's grid has %lld rows, this one %lld", nth[m], (long long)o[m]->post_M,
-                     (long long)c->post_M);
-  const int S[3] = {c->post_S, other2->post_S, other3->post_S};
-  B7_TRY(samples3_refuse(c, "ehvi3_nominate", S));
-  B7_TRY(front3_refuse(c, "ehvi3_nominate", front, P, ref));
-  B7_HIP(c, hipSetDevice(c->device));
-  const int64_t M = c->post_M;  // == c->M: a grid change would have forgotten the posterior
-  const double *mu[3], *var[3];
-  for (int m = 0; m < 3; ++m) mu[m] = (const double *)o[m]->post.p, var[m] = mu[m] + (size_t)S[m] * (size_t)M;
-  B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)M));
-  Staged3 st;
-  stage3_host(front, P, ref, &st);
-  // The streams are ordered by events both ways, as b7_ehvi_nominate orders them: the kernels wait for what the other streams have
-  // been given, and whatever the other contexts enqueue next waits for the kernels.
-  const bool wait2 = other2 != c, wait3 = other3 != c && other3 != other2;
-  if (wait2 || wait3)
-    for (hipEvent_t &e : c->ev_ehvi3)
-      if (!e) B7_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if (wait2) {
-    B7_HIP(c, hipEventRecord(c->ev_ehvi3[0], other2->stream));
-    B7_HIP(c, hipStreamWaitEvent(c->stream, c->ev_ehvi3[0], 0));
-  }
-  if (wait3) {
-    B7_HIP(c, hipEventRecord(c->ev_ehvi3[1], other3->stream));
-    B7_HIP(c, hipStreamWaitEvent(c->stream, c->ev_ehvi3[1], 0));
-  }
-  B7_TRY(acc_write_zeros(c));  // the accumulator is declared written; the box kernel then writes every row of it
-  B7_TRY(launch_ehvi3(c, mu, var, S, st, M, (double *)c->acc.p));
-  if (wait2 || wait3) {
-    B7_HIP(c, hipEventRecord(c->ev_ehvi3[2], c->stream));
-    if (wait2) B7_HIP(c, hipStreamWaitEvent(other2->stream, c->ev_ehvi3[2], 0));
-    if (wait3) B7_HIP(c, hipStreamWaitEvent(other3->stream, c->ev_ehvi3[2], 0));
-  }
-  return launch_finish(c, (double *)c->acc.p, M, 1.0, best_val, best_idx1);  // score:max(1); waits, so the staged front is consumed
+  b7_ctx *const o[3] = {c, other2, other3};
+  return ehvi_nominate(o, 3, false, "ehvi3_nominate", front, P, ref, best_val, best_idx1);
+}
+
+int b7_logehvi3_nominate(b7_ctx *c, b7_ctx *other2, b7_ctx *other3, const double *front, int P, const double *ref, double *best_val,
+                         int64_t *best_idx1) {
+  b7_ctx *const o[3] = {c, other2, other3};
+  return ehvi_nominate(o, 3, true, "logehvi3_nominate", front, P, ref, best_val, best_idx1);
 }
 
 }  // extern "C"

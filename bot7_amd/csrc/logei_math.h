@@ -1,4 +1,4 @@
-// Log-space expected improvement and the log-sum-exp step, once: score.hip's B7_SCORE_LOGEI and logehvi.hip's log Psi read the same
+// Log-space expected improvement and the log-sum-exp step, once: score.hip's B7_SCORE_LOGEI and ehvi_math.h's log Psi read the same
 // text.  The formula, its three branches and its edge cases are described in score.hip's header.  Every translation unit that includes
 // this compiles with contraction off (the pragma below); erfc, erfcx, exp, log and log1p are ocml's.
 #pragma once

@@ -106,7 +106,7 @@ __device__ __forceinline__ double b7_norm_pdf(double z) {
   return exp((z * z) * -0.5) * 0.3989422804014327;  // 1/math.sqrt(2*math.pi), utils/math.lua:15
 }
 
-// (log-space EI and the log-sum-exp step, b7_logei / b7_logaddexp: logei_math.h, shared with logehvi.hip)
+// (log-space EI and the log-sum-exp step, b7_logei / b7_logaddexp: logei_math.h, shared with ehvi_math.h)
 // ---- log probability of improvement (see the header) ----
 __device__ __forceinline__ double b7_logpi(double mu, double var, double fmin, double xi) {
   const double sigma = sqrt(var);

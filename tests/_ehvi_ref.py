@@ -275,5 +275,7 @@ def make_rows(M, S1, S2, seed=0, ref=REF, extent=1.0):
 
 # (M, P, S1, S2): M = 1000 is no multiple of the 64-lane workgroup and spans 16 of them; P covers 0, 1, 2, 33 and the cap; the
 # sample counts cover 1, the register-resident limit, the first count beyond it (one sample in LDS) and the cap (22 in LDS each).
+# (65, 2, 1, SREG + 1): objective 1 entirely in registers and one sample of objective 2 in LDS (x1 = 0, x2 = 1), the one corner of the
+# kernel's computed LDS offsets that the others do not reach; 65 rows span two workgroups and end inside the second.
 KERNEL_CASES = [(1000, 2, 3, 2), (257, 0, 1, 1), (257, 1, SREG, SREG), (1, 2, 1, 1), (40, 33, 3, 2), (5, PMAX, SREG + 1, 1),
-                (257, 2, SREG + 1, 1), (70, 1, SMAX, SMAX)]
+                (257, 2, SREG + 1, 1), (70, 1, SMAX, SMAX), (65, 2, 1, SREG + 1)]

@@ -1,5 +1,5 @@
 """References for the log-space expected hypervolume improvement, two and three objectives (b7_logehvi_* / b7_logehvi3_*;
-bot7_amd/csrc/logehvi.hip).  All objectives are minimised.
+bot7_amd/csrc/ehvi_math.h).  All objectives are minimised.
 
   logehvi_mp / logehvi3_mp   log of the 50-digit marginals of _ehvi_ref / _ehvi3_ref, per row, as mpf (None: a NaN-class row; a
                              marginal of exactly 0 -- every var == 0 and the point dominated -- is -inf): the yardstick.
@@ -201,8 +201,10 @@ def make_rows3_log(M, S, seed=0, ref=R3.REF3, extent=1.0):
 
 
 # (M, P, S1, S2): _ehvi_ref.KERNEL_CASES without its (257, 2, 11, 1): M = 1000 spans sixteen workgroups and ends inside one; 11 samples
-# put one sample in LDS, 32 put twenty-two (78 848 bytes of it: beyond the 64 KiB default)
-KERNEL_CASES = [(1000, 2, 3, 2), (257, 0, 1, 1), (257, 1, 10, 10), (1, 2, 1, 1), (40, 33, 3, 2), (5, 256, 11, 1), (70, 1, 32, 32)]
+# put one sample in LDS, 32 put twenty-two (78 848 bytes of it: beyond the 64 KiB default); (65, 2, 1, 11) is _ehvi_ref's case with
+# objective 1 in registers and one sample of objective 2 in LDS
+KERNEL_CASES = [(1000, 2, 3, 2), (257, 0, 1, 1), (257, 1, 10, 10), (1, 2, 1, 1), (40, 33, 3, 2), (5, 256, 11, 1), (70, 1, 32, 32),
+                (65, 2, 1, 11)]
 KERNEL_CASES3 = R3.KERNEL_CASES3
 
 

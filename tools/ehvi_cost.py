@@ -1,7 +1,7 @@
 """What two-objective nomination costs: two b7_eval_posterior calls (one per objective's context) + b7_ehvi_nominate against two
 plain b7_eval_nominate (EI) calls on the same inputs, timed in the same run, at the default-regime shape (N = 100, d = 6, 2e4
 candidates, S = 10 + 10, P = 16) and the headline shape (N = 2048, d = 32, 2^20 candidates, S = 1 + 1, P = 32).  Per shape: wall time
-per call (median and min .. max over the rounds, after warm-up) of the pieces and of the whole, the GPU time of ehvi_kernel alone
+per call (median and min .. max over the rounds, after warm-up) of the pieces and of the whole, the GPU time of ehvi2_kernel alone
 (the "ehvi" phase event of a profiled call), and that time against the kernel's own VALU issue bound: one Psi costs VALU_PER_PSI
 vector instructions (counted in the ISA that ships: the 142-instruction body of ocml's erfc and exp around the division, plus the
 branch tails and the strip's add; 154 for objective 1, which also keeps Psi(a_k) and clamps the difference, 150 for objective 2),

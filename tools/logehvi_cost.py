@@ -4,10 +4,15 @@ default regime's (N = 100, d = 6, 2e4 candidates, S = 10 per objective, P = 16) 
 S = 1, P = 32, and P = 128 for three objectives).  Per shape and front: wall time per nomination (median, min .. max after warm-up)
 and the GPU time of each kernel alone (the "ehvi" / "logehvi", "ehvi3_tab" / "logehvi3_tab", "ehvi3_box" / "logehvi3_box" phase events
 of a profiled call, summed over the chunks), and log over linear for each.
-With --parent-tree DIR (a checkout of the parent commit with its library built: DIR/bot7_amd): the LINEAR kernels' times under this
-build and under the parent's, in child processes of this run, alternating, three times each; the linear kernels' text did not
-change, so the two should agree within the spread of the parent's own repeats, which is recorded beside them.
+With --parent-tree DIR (a checkout of the parent commit with its library built: DIR/bot7_amd): this build against the parent's, in
+fresh child processes of this run, alternating, three times each.  Every child (1) times the six kernels as above and (2) prints a
+SHA-256 of the output bytes of the four *_compute calls on the inputs of the tests' KERNEL_CASES / KERNEL_CASES3, and of the
+(value, index) pair and the accumulator's bytes of the four *_nominate calls on the tests' small two- and three-objective problems.
+The kernels compute what the parent's computed when every digest is equal in all six children ("digests_equal"), and run as fast when
+this build's median lies within the min .. max of the parent's own three repeats ("within_parent_range", with the spread and the
+difference of the medians beside it).  Exit status 1 if a digest differs.
 Prints one JSON object.  usage (GPU box): python tools/logehvi_cost.py [out.json] [--parent-tree DIR]"""
+import hashlib
 import json
 import os
 import subprocess
@@ -15,7 +20,8 @@ import sys
 import time
 
 import numpy as np
-ROOT = os.environ.get("B7_COST_TREE") or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # (the --linear-only child's tree)
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.environ.get("B7_COST_TREE") or HERE   # (the --child's library tree; the inputs are always this tree's tests')
 sys.path.insert(0, ROOT)
 import bot7_amd  # noqa: E402
 
@@ -86,8 +92,49 @@ def kernel_ms(c, fn, phases, rounds=5):
     return {p: round(float(np.median(v)), 4) for p, v in got.items()}
 
 
-def measure(kinds):
-    """kinds: ("linear",) for the child that runs against the parent's library, ("linear", "log") otherwise."""
+def digests():
+    """SHA-256 of what the eight entry points return on the tests' inputs, under whichever library this process loaded."""
+    for p in (HERE, os.path.join(HERE, "tests")):
+        if p not in sys.path:
+            sys.path.append(p)
+    import _ehvi3_ref as R3
+    import _ehvi_ref as R2
+    import _logehvi_ref as RL
+    from test_gpu_ehvi import two_objective_problem
+    from test_gpu_ehvi3 import three_objective_problem
+
+    def sha(*arrays):
+        return hashlib.sha256(b"".join(np.ascontiguousarray(a, dtype=np.float64).tobytes() for a in arrays)).hexdigest()
+    out = {}
+    cs = [bot7_amd.Context(0) for _ in range(3)]
+    c = cs[0]
+    for M, P, S1, S2 in R2.KERNEL_CASES:
+        out["ehvi_compute/%d,%d,%d,%d" % (M, P, S1, S2)] = sha(c.ehvi_compute(*R2.make_rows(M, S1, S2), R2.make_front(P), R2.REF))
+    for M, P, S1, S2 in RL.KERNEL_CASES:
+        out["logehvi_compute/%d,%d,%d,%d" % (M, P, S1, S2)] = sha(c.logehvi_compute(*RL.make_rows_log(M, S1, S2), R2.make_front(P), R2.REF))
+    for M, P, S1, S2, S3 in R3.KERNEL_CASES3:
+        key = "%d,%d,%d,%d,%d" % (M, P, S1, S2, S3)
+        out["ehvi3_compute/" + key] = sha(c.ehvi3_compute(*R3.make_rows3(M, (S1, S2, S3)), R3.make_front3(P), R3.REF3))
+        out["logehvi3_compute/" + key] = sha(c.logehvi3_compute(*RL.make_rows3_log(M, (S1, S2, S3)), R3.make_front3(P), R3.REF3))
+    for n, prob in ((2, two_objective_problem()), (3, three_objective_problem())):
+        X, Y, Xc, hyps = prob[0], prob[1], prob[2], (prob[3:] if n == 2 else prob[3])
+        ref = np.full(n, 0.9)
+        front = (bot7_amd._lib.pareto_front2 if n == 2 else bot7_amd._lib.pareto_front3)(Y, ref)[0]
+        for k in range(n):
+            cs[k].gp_set_kernel("ardse")
+            cs[k].grid_upload(Xc)
+            cs[k].gp_set_data(X, Y[:, k:k + 1])
+            cs[k].eval_posterior(hyps[k])
+        for name in ("ehvi", "logehvi"):
+            call = getattr(c, name + ("3" if n == 3 else "") + "_nominate")
+            val, idx = call(*cs[1:n], front, ref)
+            out["%s%s_nominate/P%d" % (name, "3" if n == 3 else "", len(front))] = sha([val, float(idx)], c.score_finish(1.0, download=True)[2])
+    for c in cs:
+        c.close()
+    return out
+
+
+def measure(kinds=("linear", "log")):
     cs = [bot7_amd.Context(0) for _ in range(3)]
     rng = np.random.default_rng(0)
     out = {}
@@ -127,12 +174,12 @@ def measure(kinds):
 
 
 def main(argv):
-    if "--linear-only" in argv:
-        print(json.dumps(measure(("linear",))))
+    if "--child" in argv:
+        print(json.dumps({"digests": digests(), "times": measure()}))
         return
     parent = argv[argv.index("--parent-tree") + 1] if "--parent-tree" in argv else None
     paths = [a for i, a in enumerate(argv) if not a.startswith("--") and (i == 0 or argv[i - 1] != "--parent-tree")]
-    out = measure(("linear", "log"))
+    out, same = measure(), True
     if parent:
         runs = {"this": [], "parent": []}
         for _ in range(3):
@@ -141,25 +188,35 @@ def main(argv):
                 env.pop("B7_COST_TREE", None)
                 if tree:
                     env["B7_COST_TREE"] = os.path.abspath(tree)
-                res = subprocess.run([sys.executable, os.path.abspath(__file__), "--linear-only"], env=env, capture_output=True, text=True, timeout=900)
+                res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True, timeout=900)
                 if res.returncode != 0:
-                    raise RuntimeError("linear child (%s) failed: %s" % (which, res.stderr[-2000:]))
+                    raise RuntimeError("child (%s) failed: %s" % (which, res.stderr[-2000:]))
                 runs[which].append(json.loads(res.stdout.strip().splitlines()[-1]))
+                print("child %d of 6 done (%s)" % (len(runs["this"]) + len(runs["parent"]), which), file=sys.stderr, flush=True)
+        first = runs["parent"][0]["digests"]
+        differing = sorted(k for k in first if any(x["digests"].get(k) != first[k] for w in runs for x in runs[w]))
+        same = not differing and all(set(x["digests"]) == set(first) for w in runs for x in runs[w])
+        out["digests_against_parent"] = {"digests_equal": same, "compared": len(first), "differing": differing, "sha256": first}
         cmp_ = {}
         for name in SHAPES:
-            for key in runs["parent"][0][name]:
+            for key in runs["parent"][0]["times"][name]:
                 if key == "shape":
                     continue
-                for phase in runs["parent"][0][name][key]["linear"]["kernel_ms"]:
-                    ms = {w: [x[name][key]["linear"]["kernel_ms"][phase] for x in runs[w]] for w in runs}
-                    cmp_["%s/%s/%s" % (name, key, phase)] = {
-                        "this_ms": ms["this"], "parent_ms": ms["parent"], "parent_spread_ms": round(max(ms["parent"]) - min(ms["parent"]), 4),
-                        "this_minus_parent_ms": round(float(np.median(ms["this"]) - np.median(ms["parent"])), 4)}
-        out["linear_kernels_against_parent"] = cmp_
+                for kind in ("linear", "log"):
+                    for phase in runs["parent"][0]["times"][name][key][kind]["kernel_ms"]:
+                        ms = {w: [x["times"][name][key][kind]["kernel_ms"][phase] for x in runs[w]] for w in runs}
+                        med = float(np.median(ms["this"]))
+                        cmp_["%s/%s/%s" % (name, key, phase)] = {
+                            "this_ms": ms["this"], "parent_ms": ms["parent"], "parent_spread_ms": round(max(ms["parent"]) - min(ms["parent"]), 4),
+                            "this_minus_parent_ms": round(med - float(np.median(ms["parent"])), 4),
+                            "within_parent_range": bool(min(ms["parent"]) <= med <= max(ms["parent"]))}
+        out["kernels_against_parent"] = cmp_
     print(json.dumps(out))
     if paths:
         with open(paths[0], "w") as f:
             json.dump(out, f, indent=1)
+    if not same:
+        sys.exit(1)
 
 
 if __name__ == "__main__":
