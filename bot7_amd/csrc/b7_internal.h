@@ -261,6 +261,8 @@ struct b7_ctx {
   bool ts_valid = false;  // a b7_ts_nominate has succeeded; the shapes of what it left:
   int64_t ts_M = 0;
   int ts_q = 0, ts_S = 0, ts_F = 0, ts_N = 0, ts_d = 0;
+  // ... or a b7_blr_ts_nominate (blr_ts.hip): the paths are laid out alike, ts_draw holds eps [q][z] | weight [q][z] and ts_F = z
+  bool ts_blr = false;
   // ---- b7_eval_nominate_refine / b7_gp_grad_at (refine.hip): the workspace of 64 query columns, the last call's trace and result
   DevBuf refine_ws, refine_trace;
   DevBuf refine_user;       // b7_score_grad_compute's staging, apart from them
@@ -714,6 +716,14 @@ struct BelPass {
   int64_t idx; int j;                  // the believed row (0-based), the number of earlier believer columns
 };
 int launch_believer(b7_ctx *c, int S, const BelPass &p, bool column);
+// rff.hip: path j = 0 .. q - 1 in order, each its first minimum over the rows of paths (M x q) that no earlier path took, a NaN never
+// winning, into pmin[j] / taken[j] (0-based) on the device; part: 16 nblk bytes of workspace, nblk <= 1024 blocks per pass
+int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, void *part, int nblk);
+// blr_api.hip: what b7_blr_ts_nominate (blr_ts.hip) shares with the DNGO entry points
+int blr_upload_net(b7_ctx *c, const b7_mlp *net, int *z_out);
+int blr_feat_alloc(b7_ctx *c, int64_t M, int z);
+int blr_heads_fast_enqueue(b7_ctx *c, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *ap,
+                           const double *bt, const double *mn, int z, bool want_terms, double **hdev_out);
 // grid_api.hip
 int grid_drop_row(b7_ctx *c, int64_t local_idx1, double *row_out_sync);  // stable deletion, enqueued; row_out != NULL synchronises
 

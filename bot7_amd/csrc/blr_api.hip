@@ -5,7 +5,7 @@
 #include "b7_internal.h"
 
 // ---- DNGO: basis features + Bayesian linear head --------------------------------------------------------------
-static int upload_net(b7_ctx *c, const b7_mlp *net, int *z_out) {
+int blr_upload_net(b7_ctx *c, const b7_mlp *net, int *z_out) {
   if (!net || !net->dims || !net->W || !net->b || net->n_layers < 1 || net->n_layers > 4)
     return b7_fail(c, B7_ERR_INVALID, "mlp: 1..4 layers with dims, W and b required");
   size_t total = 0;
@@ -34,7 +34,7 @@ static int upload_net(b7_ctx *c, const b7_mlp *net, int *z_out) {
 // The feature matrix: round_up(M, 256) rows x zpad columns, of which the basis kernels write the first z of the first M
 // rows.  Everything else must be zero (the variance GEMM reads whole padded rows) and is zeroed when the buffer is
 // (re)allocated or its column layout changes -- not on every call: a 67 MB memset per nomination was a sixth of a cfg5 step.
-static int feat_alloc(b7_ctx *c, int64_t M, int z) {
+int blr_feat_alloc(b7_ctx *c, int64_t M, int z) {
   const int zpad = npad_of(c, z);
   const size_t bytes = sizeof(double) * (size_t)round_up(M, B7_MROWS) * zpad;
   const bool grown = c->feat.cap < bytes;
@@ -179,7 +179,7 @@ static int blr_enqueue_fit(b7_ctx *c, const b7_mlp *net, const double *X0, const
 // b7_blr_predict + the score, bit for bit (tests/test_gpu_blr.py holds it to that).
 static int blr_enqueue_score(b7_ctx *c, const b7_mlp *net, int z, const b7_score_spec *spec, bool fused_mean = true) {
   const int zpad = npad_of(c, z);
-  B7_TRY(feat_alloc(c, c->M, z));
+  B7_TRY(blr_feat_alloc(c, c->M, z));
   B7_TRY(b7_ensure(c, c->mu, sizeof(double) * (size_t)c->M));
   B7_TRY(b7_ensure(c, c->var, sizeof(double) * (size_t)c->M));
   B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
@@ -208,7 +208,7 @@ static int blr_marg_slow(b7_ctx *c, const b7_mlp *net, const double *X0, const d
   for (int s = 0; s < S; ++s) {
     B7_TRY(b7_blr_fit_x(c, net, X0, Y0, N, ap[s], bt[s], mn[s], nll_out ? nll_out + s : nullptr));   // synchronous, jitter schedule included
     if (s == 0) {
-      B7_TRY(feat_alloc(c, c->M, z));
+      B7_TRY(blr_feat_alloc(c, c->M, z));
       B7_TRY(launch_mlp_forward(c, (const double *)c->grid[c->grid_cur].p, c->M, c->d, (const double *)c->netbuf.p, net->dims,
                                 net->n_layers, net->activation, (double *)c->feat.p, zpad));
     }
@@ -221,8 +221,12 @@ static int blr_marg_slow(b7_ctx *c, const b7_mlp *net, const double *X0, const d
   return B7_OK;
 }
 
-static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *ap,
-                         const double *bt, const double *mn, int z, const b7_score_spec *spec, bool want_terms, ScoreParams *pend) {
+// The front of that route, which b7_blr_ts_nominate (blr_ts.hip) shares: the observations' features and the S heads, enqueued.  Leaves
+// L^-1 in c->bLinv ([S][64 x 64]), the weights in c->balpha ([S][64]), the pivot reports ([S][4] ints) and, when asked for, the
+// evidence's terms ([S][3] doubles behind them) on their way into c->pin_eval, and in *hdev_out the device copy of
+// [S alpha | S beta | S mean | S zeros | S 1/beta].
+int blr_heads_fast_enqueue(b7_ctx *c, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *ap,
+                           const double *bt, const double *mn, int z, bool want_terms, double **hdev_out) {
   const int d = net->dims[0];
   const size_t up_doubles = (size_t)N * d + (size_t)N + 5 * (size_t)S;   // [X0 | y | S alpha | S beta | S mean | S zeros | S 1/beta]
   B7_TRY(b7_ensure(c, c->tmpmu, sizeof(double) * (up_doubles + (size_t)N * z)));
@@ -232,9 +236,6 @@ static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const d
   B7_TRY(b7_ensure(c, c->bresid, sizeof(double) * (size_t)S * 64));
   B7_TRY(b7_ensure(c, c->binfo, sizeof(int) * 4 * (size_t)S));
   B7_TRY(b7_ensure(c, c->bterms, sizeof(double) * 3 * (size_t)S + 64));
-  B7_TRY(b7_ensure(c, c->bmu, sizeof(double) * (size_t)S * c->M));
-  B7_TRY(b7_ensure(c, c->bvar, sizeof(double) * (size_t)S * c->M));
-  B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
   // pinned, device-mapped block for the reports and the evidence's terms: [S][4] ints | [S][3] doubles
   const size_t rep_bytes = 16 * (size_t)S, term_bytes = sizeof(double) * 3 * (size_t)S;
   B7_TRY(b7_pin_ensure(c, c->pin_eval, rep_bytes + term_bytes, true));
@@ -254,7 +255,18 @@ static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const d
                                 (double *)c->bresid.p, (int *)c->binfo.p, static_cast<int *>(c->pin_eval.dev), (double *)c->bterms.p));
   if (want_terms)
     B7_HIP(c, hipMemcpyAsync(static_cast<char *>(c->pin_eval.host) + rep_bytes, c->bterms.p, term_bytes, hipMemcpyDeviceToHost, c->stream));
-  B7_TRY(feat_alloc(c, c->M, z));
+  *hdev_out = hdev;
+  return B7_OK;
+}
+
+static int blr_marg_fast(b7_ctx *c, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *ap,
+                         const double *bt, const double *mn, int z, const b7_score_spec *spec, bool want_terms, ScoreParams *pend) {
+  B7_TRY(b7_ensure(c, c->bmu, sizeof(double) * (size_t)S * c->M));
+  B7_TRY(b7_ensure(c, c->bvar, sizeof(double) * (size_t)S * c->M));
+  B7_TRY(b7_ensure(c, c->acc, sizeof(double) * (size_t)c->M));
+  double *hdev = nullptr;
+  B7_TRY(blr_heads_fast_enqueue(c, net, X0, Y0, N, S, ap, bt, mn, z, want_terms, &hdev));
+  B7_TRY(blr_feat_alloc(c, c->M, z));
   B7_TRY(launch_mlp_forward(c, (const double *)c->grid[c->grid_cur].p, c->M, c->d, (const double *)c->netbuf.p, net->dims,
                             net->n_layers, net->activation, (double *)c->feat.p, 64));
   B7_TRY(launch_gemv_rows_batch(c, S, (const double *)c->feat.p, 64, (const double *)c->balpha.p, 64, 64, hdev + 2 * (size_t)S, c->M,
@@ -274,12 +286,12 @@ int b7_blr_basis(b7_ctx *c, const b7_mlp *net, const double *X, int64_t M, doubl
   if (!c) return B7_ERR_INVALID;
   B7_HIP(c, hipSetDevice(c->device));
   int z = 0;
-  B7_TRY(upload_net(c, net, &z));
+  B7_TRY(blr_upload_net(c, net, &z));
   if (z > 256) return b7_fail(c, B7_ERR_UNSUPPORTED, "blr: basis width %d > 256", z);
   const int zpad = npad_of(c, z);
   if (!X) {  // resident grid -> resident features
     if (c->M <= 0 || c->d <= 0) return b7_fail(c, B7_ERR_STATE, "blr_basis: no candidate grid on this context");
-    B7_TRY(feat_alloc(c, c->M, z));
+    B7_TRY(blr_feat_alloc(c, c->M, z));
     B7_TRY(launch_mlp_forward(c, (const double *)c->grid[c->grid_cur].p, c->M, c->d, (const double *)c->netbuf.p,
                               net->dims, net->n_layers, net->activation, (double *)c->feat.p, zpad));
     if (Z_host)
@@ -305,7 +317,7 @@ int b7_blr_features(b7_ctx *c, const double *Z1, int64_t M, int z) {
   if (!Z1 || M < 1 || z < 1 || z > 256) return b7_fail(c, B7_ERR_INVALID, "blr_features: bad arguments");
   B7_HIP(c, hipSetDevice(c->device));
   const int zpad = npad_of(c, z);
-  B7_TRY(feat_alloc(c, M, z));
+  B7_TRY(blr_feat_alloc(c, M, z));
   B7_HIP(c, hipMemcpy2DAsync(c->feat.p, sizeof(double) * zpad, Z1, sizeof(double) * z, sizeof(double) * z, M,
                              hipMemcpyHostToDevice, c->stream));
   B7_HIP(c, hipStreamSynchronize(c->stream));
@@ -347,7 +359,7 @@ int b7_blr_fit_x(b7_ctx *c, const b7_mlp *net, const double *X0, const double *Y
   c->fitted = false;
   c->predicted = false;
   int z = 0;
-  B7_TRY(upload_net(c, net, &z));
+  B7_TRY(blr_upload_net(c, net, &z));
   if (z > 256) return b7_fail(c, B7_ERR_UNSUPPORTED, "blr: basis width %d > 256", z);
   const int d = net->dims[0], zpad = npad_of(c, z), nk = (int)round_up(N, 16);
   B7_TRY(b7_ensure(c, c->tmpmu, sizeof(double) * ((size_t)N * d + (size_t)N * z)));
@@ -387,7 +399,7 @@ int b7_blr_eval_nominate(b7_ctx *c, const b7_mlp *net, const double *X0, const d
   if (rc == B7_OK && spec->kind == B7_SCORE_MES)
     rc = b7_fail(c, B7_ERR_UNSUPPORTED, "blr_eval_nominate: max-value entropy search is not built on this route (b7_blr_predict + b7_score_mes is)");
   if (rc == B7_OK) rc = hipSetDevice(c->device) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "hipSetDevice failed");
-  if (rc == B7_OK) rc = upload_net(c, net, &z);
+  if (rc == B7_OK) rc = blr_upload_net(c, net, &z);
   if (rc == B7_OK && z > 256) rc = b7_fail(c, B7_ERR_UNSUPPORTED, "blr: basis width %d > 256", z);
   if (rc == B7_OK && c->M > 0 && net->dims[0] != c->d)
     rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate: network input width %d != grid dims %d", net->dims[0], c->d);
@@ -420,7 +432,7 @@ int b7_blr_eval_nominate_marg(b7_ctx *c, const b7_mlp *net, const double *X0, co
   for (int s = 0; rc == B7_OK && s < S; ++s)
     if (!(ap[s] > 0.0) || !(bt[s] > 0.0)) rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: precisions must be > 0 (sample %d)", s);
   if (rc == B7_OK) rc = hipSetDevice(c->device) == hipSuccess ? B7_OK : b7_fail(c, B7_ERR_HIP, "hipSetDevice failed");
-  if (rc == B7_OK) rc = upload_net(c, net, &z);
+  if (rc == B7_OK) rc = blr_upload_net(c, net, &z);
   if (rc == B7_OK && z > 256) rc = b7_fail(c, B7_ERR_UNSUPPORTED, "blr: basis width %d > 256", z);
   if (rc == B7_OK && c->M > 0 && net->dims[0] != c->d)
     rc = b7_fail(c, B7_ERR_INVALID, "blr_eval_nominate_marg: network input width %d != grid dims %d", net->dims[0], c->d);

@@ -10,6 +10,8 @@
 //                      128 f + 101                phase[f] = 2 pi counter_uniform
 //       a = 1 + j    PATH j:   f (f < 4096)  weight[f] ~ N(0,1);   4096 + i  eps[i] / sqrt(noise) ~ N(0,1), observation i
 //     Nothing depends on q, S, F, d or N: feature f, path j and observation i have the same draws in every call with that seed.
+//   b7_blr_ts_nominate (blr_ts.hip)   PATH j draws from the stream key(seed, 2^32 + j), apart from every stream above:
+//       k (k < 256)  eps_j[k] ~ N(0,1), component k of the weight draw.  A function of (seed, j, k) alone: not of q, S, z or N.
 //   b7_gp_slice_sample (gp_small.hip: slice_chain_kernel)   chain c of a call draws from the stream key(seed, c); update number
 //       g = update0 + u owns the counters 4096 g .. 4096 g + 4095 (D = d + 3 <= 64 components, at most 3840 shrink steps):
 //                      4096 g + k        (k < D)     z_k ~ N(0,1), the direction before it is normalised (counter_normal)

@@ -27,8 +27,8 @@
 // j mod S, enter its Omega --; weight and eps are path j's own.  All of it depends on (seed, j) alone.
 //
 // Out of scope: sharded grids and groups (the q arg-mins would ride the existing all-reduce, but no world > 1 has run on
-// hardware), the Bayesian-linear head (its weight-space posterior makes Thompson sampling a different, simpler kernel), more
-// than one response column, a one-launch variant for N <= 128, and any change to the existing scores or the believer batch.
+// hardware), more than one response column, a one-launch variant for N <= 128, and any change to the existing scores or the
+// believer batch.  The Bayesian-linear head has its own entry, b7_blr_ts_nominate (blr_ts.hip), which shares the arg-mins below.
 #include <math.h>
 #include <string.h>
 
@@ -359,6 +359,17 @@ struct YSwap {
 
 }  // namespace
 
+int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, void *part, int nblk) {
+  PhaseScope ps(c, "ts_argmin");
+  for (int j = 0; j < q; ++j) {
+    hipLaunchKernelGGL(ts_argmin_part_kernel, dim3(nblk), dim3(256), 0, c->stream, paths, M, q, j, (const long long *)taken,
+                       static_cast<TsBest *>(part));
+    hipLaunchKernelGGL(ts_argmin_final_kernel, dim3(1), dim3(256), 0, c->stream, (const TsBest *)part, nblk, j, taken, pmin);
+  }
+  B7_HIP(c, hipGetLastError());
+  return B7_OK;
+}
+
 extern "C" {
 
 int b7_ts_nominate(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *path_min, int64_t *best_idx1,
@@ -383,7 +394,7 @@ int b7_ts_nominate(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t 
   const int64_t M = c->M;
   if (jitter_out) std::fill(jitter_out, jitter_out + S, 0.0);
   if (info_out) std::fill(info_out, info_out + S, 0);
-  c->ts_valid = false;
+  c->ts_valid = false, c->ts_blr = false;
 
   // device memory beyond the posterior's own: the paths (M x q), the draws, and the operands of one hyper sample
   const int qmax = (q + ns - 1) / ns, yldmax = qmax == 1 ? 1 : (int)round_up(qmax, 64);
@@ -450,14 +461,7 @@ int b7_ts_nominate(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t 
       B7_TRY(launch_rff(c, grid, M, d, omf, dr.phase, wf, F, (const double *)c->mu.p, qs, paths, q, s, S, qs));
     }
   }
-  {
-    PhaseScope ps(c, "ts_argmin");
-    for (int j = 0; j < q; ++j) {
-      hipLaunchKernelGGL(ts_argmin_part_kernel, dim3(nblk), dim3(256), 0, c->stream, (const double *)paths, M, q, j, (const long long *)taken, part);
-      hipLaunchKernelGGL(ts_argmin_final_kernel, dim3(1), dim3(256), 0, c->stream, (const TsBest *)part, nblk, j, taken, pmin);
-    }
-    B7_HIP(c, hipGetLastError());
-  }
+  B7_TRY(launch_ts_argmins(c, paths, M, q, pmin, taken, part, nblk));
   long long tk[B7_BATCH_MAX];
   B7_HIP(c, hipMemcpyAsync(path_min, pmin, sizeof(double) * q, hipMemcpyDeviceToHost, c->stream));
   B7_HIP(c, hipMemcpyAsync(tk, taken, sizeof(long long) * q, hipMemcpyDeviceToHost, c->stream));
@@ -481,6 +485,7 @@ int b7_ts_last_paths(b7_ctx *c, double *paths_host) {
 int b7_ts_last_draws(b7_ctx *c, int path, double *omega, double *phase, double *weight, double *eps) {
   if (!c) return B7_ERR_INVALID;
   if (!c->ts_valid) return b7_fail(c, B7_ERR_STATE, "ts_last_draws: no successful b7_ts_nominate on this context");
+  if (c->ts_blr) return b7_fail(c, B7_ERR_STATE, "ts_last_draws: the last nomination was b7_blr_ts_nominate's (b7_blr_ts_last_draws reads its draws)");
   if (path < 0 || path >= c->ts_q) return b7_fail(c, B7_ERR_INVALID, "ts_last_draws: path %d not in [0, %d)", path, c->ts_q);
   B7_HIP(c, hipSetDevice(c->device));
   const int F = c->ts_F, d = c->ts_d, N = c->ts_N, ns = c->ts_S < c->ts_q ? c->ts_S : c->ts_q;

@@ -12,7 +12,8 @@ precision ``config['alpha']`` and noise precision ``config['beta']``.  ``predict
 ``hyp = {'alpha', 'beta', 'mean'}``.  The reference's default hyp='marginalize' (:109, passed to the predictor at :174) is realised
 as the analogue of bayesopt:eval's GP loop by ``eval_nominate`` below: a LIST of hyp tables (drawn by the host, e.g. with
 bot7.samplers.slice over ``nll``) -> S heads over the same features, the acquisition of every head added in sample order,
-score:div(S), score:max(1) -- one library call, b7_blr_eval_nominate_marg."""
+score:div(S), score:max(1) -- one library call, b7_blr_eval_nominate_marg.  ``ts_nominate`` (no counterpart in the reference) nominates
+q points per call by Thompson sampling on the head's exact weight posterior, b7_blr_ts_nominate."""
 import numpy as np
 
 from .abstract import abstract
@@ -91,6 +92,20 @@ class dngo(abstract):
                                               Y_obs, [h["alpha"] for h in hyps], [h["beta"] for h in hyps], [h["mean"] for h in hyps],
                                               score=score, fmin=fmin, tradeoff=tradeoff, upper=upper, sign=sign, want_nll=want_nll)
         return (out[0], out[1], out[3]) if want_nll else (out[0], out[1])
+
+    def ts_nominate(self, X_obs, Y_obs, X_hid, hyps=None, q=1, seed=0, want_report=False):
+        """q nominees by Thompson sampling on the head's exact weight posterior (b7_blr_ts_nominate; no counterpart in the reference):
+        path j is f_j = mean_s + phi' w_j with w_j ~ N(m_s, inv(A_s)) under hyps[j mod S].  hyps: a hyp table, a list of them, or None
+        for the head's point hypers (as predict).  Returns (path minima[q], 1-based indices[q][, report]); the grid is not modified."""
+        if hyps is None:
+            hyps = self.hyp or self.init(X_obs, Y_obs)
+        if isinstance(hyps, dict):
+            hyps = [hyps]
+        if not self._is_resident(X_hid):
+            self.ctx.grid_upload(np.atleast_2d(np.asarray(X_hid, dtype=np.float64)))
+        return self.ctx.blr_ts_nominate(self.weights, self.biases, self.activation, np.atleast_2d(np.asarray(X_obs, dtype=np.float64)), Y_obs,
+                                        [h["alpha"] for h in hyps], [h["beta"] for h in hyps], [h["mean"] for h in hyps], q, seed=seed,
+                                        want_report=want_report)
 
     def nll(self, X_obs, Y_obs, hyp=None):
         """Negative log evidence of the head under hyp (what a host-side sampler of (alpha, beta) walks)."""

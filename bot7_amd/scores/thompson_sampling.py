@@ -8,7 +8,10 @@ Deisenroth, "Efficiently Sampling Functions from Gaussian Process Posteriors", I
 with ``nFeatures`` (default 1024; a multiple of 16) random Fourier features phi of the prior.  Path j is drawn under hyper sample
 j mod nSamples, and a path takes its first minimum among the rows no earlier path of the same call took.  There is no score
 vector to add, average or download: the bot calls Context.ts_nominate in place of its eval + arg-max.  One GPU, one response
-column, GP models only."""
+column.
+
+With the dngo model the posterior over the head's weights is a finite Gaussian and the path is exact, f_j(x) = mean + phi(x)' w_j with
+w_j ~ N(m, inv(A)): no random features (``nFeatures`` is unused), computed by b7_blr_ts_nominate through dngo.ts_nominate."""
 from .abstract import abstract
 
 
@@ -25,7 +28,11 @@ class thompson_sampling(abstract):
         raise NotImplementedError("thompson_sampling is not a per-point score: there is nothing to add to the accumulator "
                                   "(nominate through Context.ts_nominate)")
 
-    def nominate(self, ctx, hyps, q, seed, config=None):
-        """q 1-based nominees over ctx's resident data and grid (Context.ts_nominate)."""
+    def nominate(self, ctx, hyps, q, seed, config=None, model=None, observed=None, responses=None, candidates=None):
+        """q 1-based nominees.  A GP model: over ctx's resident data and grid (Context.ts_nominate).  A dngo model (passed with its
+        observations, responses and candidates): exact paths on the head's weight posterior (dngo.ts_nominate), hyps its
+        {'alpha', 'beta', 'mean'} tables; nFeatures plays no part."""
+        if model is not None and model.class_() == "bot7.models.dngo":
+            return model.ts_nominate(observed, responses, candidates, hyps, q, seed)[1]
         config = config or self.config
         return ctx.ts_nominate(hyps, q, n_features=int(config.get("nFeatures") or 1024), seed=seed)[1]

@@ -14,7 +14,9 @@ subtraction of log(nSamples).  'max_value_entropy_search' (not in the reference 
 level count (config.score.nLevels) and as b7_score_mes in the per-sample loop, each hyper sample with its own y* search on the
 device; on one GPU only -- a sharded candidate set or a batch (config.bot.batch > 1) answers "unsupported".
 'thompson_sampling' (not in the reference) is not a per-point score: nominate and nominate_batch, q = 1 included, go through
-b7_ts_nominate with a seed from the bot's own generator, and eval(want_scores=True) raises -- there is no score vector.
+b7_ts_nominate with a seed from the bot's own generator, and eval(want_scores=True) raises -- there is no score vector.  With
+the dngo model the same calls go through b7_blr_ts_nominate: exact paths on the head's weight posterior, under the head's point
+hypers or config.model.hyps, a list of {'alpha', 'beta', 'mean'} tables.
 'knowledge_gradient' (not in the reference) is a policy too: eval and nominate go through b7_kg_nominate with config.score.points
 discretisation rows (default 16), chosen by config.score.discretisation: 'mean' (default; the library takes the rows of lowest
 marginal posterior mean) or 'thompson' (the minimisers of that many b7_ts_nominate paths, drawn with a seed from the bot's own
@@ -452,8 +454,16 @@ class bayesopt(abstract):
         """q nominees by Thompson sampling (b7_ts_nominate): the hyper samples as eval's fused branch draws them
         (bots/bayesopt.lua:68, :73-75), the call's seed from the bot's own generator."""
         X_obs, Y_obs, model = self.observed, self.responses, self.model
-        assert hasattr(model, "stage") and model.class_() != "bot7.models.dngo" and not hasattr(cand, "commit"), \
-            "thompson_sampling: a GP model on one GPU (sharded Thompson sampling is not built)"
+        assert not hasattr(cand, "commit"), "thompson_sampling: one GPU (sharded Thompson sampling is not built)"
+        if model.class_() == "bot7.models.dngo":
+            # the head's exact weight-space paths (b7_blr_ts_nominate): the point hyp table eval's DNGO branch predicts under
+            # (:65-66), or config.model.hyps, a list of them (path j under table j mod S)
+            hyps = model.config.get("hyps") or [model.hyp or model.init(X_obs, Y_obs)]
+            seed = int(self._rng.integers(0, 2 ** 63))
+            idx = self.score.nominate(model.ctx, hyps, q, seed, model=model, observed=X_obs, responses=Y_obs, candidates=cand)
+            self.last_scores = None
+            return [int(i) for i in idx]
+        assert hasattr(model, "stage"), "thompson_sampling: a GP or dngo model"
         model.sample_hypers(X_obs, Y_obs)                         # :68 (burn-in call)
         hyps = [model.parse_hypers(model.sample_hypers(X_obs, Y_obs, None, None, True))
                 for _ in range(self.config["bot"]["nSamples"])]   # :73-75

@@ -664,7 +664,8 @@ int b7_score_grad_compute(b7_ctx *ctx, const b7_score_spec *spec, int S, const d
  * rank.  B7_ERR_STATE: a member of a group (as b7_eval_nominate_batch answers), no resident data or grid.
  * Device memory beside the posterior's own buffers: M q doubles for the paths (plus the draws, min(S, q) F d + (q + 1) F + q N, and
  * one hyper sample's operands), allocated on demand (B7_ERR_NOMEM) and freed with the context.
- * Not built: sharded grids and groups, the Bayesian-linear head, more than one response column, a one-launch variant for N <= 128.
+ * Not built: sharded grids and groups, more than one response column, a one-launch variant for N <= 128.  The Bayesian-linear head
+ * has an entry of its own: b7_blr_ts_nominate below.
  * Added without a change of B7_ABI_VERSION: the change is additive. */
 #define B7_TS_MAX_FEATURES 4096
 int b7_ts_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *path_min /*q*/,
@@ -680,6 +681,37 @@ int b7_ts_last_draws(b7_ctx *ctx, int path, double *omega /*F x d*/, double *pha
  * far inside. */
 int b7_rff_compute(b7_ctx *ctx, const double *X /*M1 x d*/, int64_t M1, int d, const double *omega /*F x d*/,
                    const double *phase /*F*/, const double *W /*F x q*/, int F, int q, double *out /*M1 x q*/);
+
+/* THOMPSON SAMPLING FOR THE BAYESIAN-LINEAR HEAD (DNGO): q nominees per call.  No counterpart in the reference.  The head's posterior
+ * over its z weights is a finite Gaussian, N(m_s, inv(A_s)) with A_s = alpha_s I + beta_s Z'Z = L_s L_s', so a sample path is exact:
+ *   f_j(x) = mean_s + phi(x)' w_j,      w_j = m_s + L_s^-T eps_j,      eps_j ~ N(0, I_z),      s = j mod S
+ * -- no random features, no pseudo-response fit, no M x M covariance.  Paths are of the latent function: the 1 / beta observation
+ * noise is not added, as b7_ts_nominate's paths carry none.
+ *   heads     b7_blr_eval_nominate_marg's: one basis pass over the N observations and one over the resident grid; the S heads in one
+ *             launch for z <= 64, otherwise head by head through b7_blr_fit_x.  All S are fitted (nll_out reports them), path j uses
+ *             head j mod S.  A failed pivot redoes the heads through b7_blr_fit_x's jitter schedule, the paths are drawn from the
+ *             jittered factors and *jitter_used < 0 (0 otherwise).
+ *   draws     eps_j[k] is the library's counter normal on a stream of its own, a function of (seed, j, k) alone: the paths of a
+ *             q = 3 call are the first three of a q = 5 call.
+ *   arg-mins  b7_ts_nominate's rule: paths in order, each its first minimum over the rows no earlier path of the call took; a NaN
+ *             does not win; path_min[j] is the path's value at the row it took, best_idx1[j] that row, 1-based.
+ * Deterministic; an element of a path depends on its own grid row and its own weights alone (not on M, q or the other paths).  The grid
+ * is not modified, the score accumulator is untouched, b7_ts_last_paths serves this call too.  z <= 256.
+ * B7_ERR_INVALID: q outside 1..B7_BATCH_MAX or q > the grid's rows; S < 1; NULL arguments; a precision <= 0.  B7_ERR_UNSUPPORTED, the
+ * case named: a communicator of more than one rank.  B7_ERR_STATE: a member of a group, no resident grid.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+int b7_blr_ts_nominate(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, int S,
+                       const double *alpha_prec, const double *beta, const double *mean /*S each*/, int q, uint64_t seed,
+                       double *path_min /*q*/, int64_t *best_idx1 /*q*/, double *nll_out /*S, nullable*/,
+                       double *jitter_used /*nullable*/);
+/* Inspection (tests): path `path`'s draw eps and weight vector w (z each, either nullable) of the last successful
+ * b7_blr_ts_nominate; B7_ERR_STATE before one (and after a b7_ts_nominate, whose draws b7_ts_last_draws reads). */
+int b7_blr_ts_last_draws(b7_ctx *ctx, int path, double *eps /*z*/, double *weight /*z*/);
+/* The paths kernel alone on host arrays (the b7_rff_compute of this feature): out = mean0' + Z W, M1 x q, on the fp64 matrix
+ * cores.  z in 1..256, q in 1..B7_BATCH_MAX.  The order of summation over z is fixed and mean0[j] is added once, last: an element's
+ * bits depend on its own row of Z and column of W alone. */
+int b7_blr_paths_compute(b7_ctx *ctx, const double *Z /*M1 x z*/, int64_t M1, int z, const double *W /*z x q*/,
+                         const double *mean0 /*q*/, int q, double *out /*M1 x q*/);
 
 /* THE KNOWLEDGE GRADIENT: a one-step look-ahead nomination.  No counterpart in the reference; Frazier, Powell & Dayanik (2009),
  * Scott, Frazier & Powell (2011).  The expected decrease of the MINIMUM OF THE POSTERIOR MEAN after one more, possibly noisy,

@@ -100,6 +100,9 @@ int b7_ts_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_
 int b7_ts_last_paths(b7_ctx *ctx, double *paths_host );
 int b7_ts_last_draws(b7_ctx *ctx, int path, double *omega , double *phase , double *weight , double *eps );
 int b7_rff_compute(b7_ctx *ctx, const double *X , int64_t M1, int d, const double *omega , const double *phase , const double *W , int F, int q, double *out );
+int b7_blr_ts_nominate(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *alpha_prec, const double *beta, const double *mean , int q, uint64_t seed, double *path_min , int64_t *best_idx1 , double *nll_out , double *jitter_used );
+int b7_blr_ts_last_draws(b7_ctx *ctx, int path, double *eps , double *weight );
+int b7_blr_paths_compute(b7_ctx *ctx, const double *Z , int64_t M1, int z, const double *W , const double *mean0 , int q, double *out );
 int b7_kg_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int n, const int64_t *rows1 , double *best_val, int64_t *best_idx1, double *jitter_out , int *info_out );
 int b7_kg_trace_enable(b7_ctx *ctx, int on);
 int b7_kg_last(b7_ctx *ctx, int64_t *rows1 , double *alpha , double *slopes , double *values , double *own_alpha );

@@ -58,10 +58,18 @@ end
 local function ts_nominate(self, q, candidates)
   assert(D.world == 1 and not hip.group, 'thompson_sampling: one rank, no group (sharded Thompson sampling is not built)')
   local model, keep = self.model, {}
-  assert(torch.type(model) == 'bot7.models.gp_hip', 'thompson_sampling: needs the gp_hip model')
   local Y_obs = self.responses
   if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
   local X_obs, S = self.observed, self.config.bot.nSamples
+  if torch.type(model) == 'bot7.models.dngo_hip' then
+    -- the head's exact weight-space paths (b7_blr_ts_nominate): the point hyp table predict uses, or config.model.hyps, a list of them
+    local hyps = (model.config or {}).hyps
+                 or {model.blr_hyp or {alpha = 1.0, beta = 1.0 / (1e-2 * Y_obs:var()), mean = Y_obs:mean()}}
+    local out, vmin = model:ts_nominate(X_obs, Y_obs, candidates, hyps, q, ffi.new('uint64_t', torch.random()))
+    self.best_score = vmin
+    return out
+  end
+  assert(torch.type(model) == 'bot7.models.gp_hip', 'thompson_sampling: needs the gp_hip or the dngo_hip model')
   model:sample_hypers(X_obs, Y_obs)                                          -- :68
   local hyps = ffi.new('b7_hyp[?]', S)
   for s = 1, S do                                                            -- :73-75

@@ -76,4 +76,23 @@ function dngo:eval_nominate(X0, Y0, X1, hyps, spec)
   return tonumber(idx[0]), val[0]
 end
 
+-- Thompson sampling on the head's exact weight posterior (b7_blr_ts_nominate; no original): q paths f_j = mean_s + phi' w_j with
+-- w_j ~ N(m_s, inv(A_s)), path j under hyps[j mod S + 1]; each path's first minimum among the rows no earlier path took.  `hyps` as
+-- eval_nominate's.  Returns a LongTensor of q 1-based indices into X1 (the resident grid) and the first path's minimum.
+function dngo:ts_nominate(X0, Y0, X1, hyps, q, seed)
+  self.network:evaluate()
+  local net, keep = pack_network(self)
+  local S = #hyps
+  local a, b, m = ffi.new('double[?]', S), ffi.new('double[?]', S), ffi.new('double[?]', S)
+  for s = 1, S do a[s-1] = hyps[s].alpha; b[s-1] = hyps[s].beta; m[s-1] = hyps[s].mean end
+  assert(hip.group == nil, 'bot7hip: the DNGO head runs on one GPU (no group)')
+  if not hip.is_resident(X1) then hip.upload_grid(X1) end
+  local X0c, Y0c = hip.pin(X0), hip.pin(Y0)
+  local v, i, jit = ffi.new('double[?]', q), ffi.new('int64_t[?]', q), ffi.new('double[1]')
+  hip.check(hip.C.b7_blr_ts_nominate(hip.ctx, net, hip.data(X0c), hip.data(Y0c), X0:size(1), S, a, b, m, q, seed, v, i, nil, jit))
+  local out = torch.LongTensor(q)
+  for k = 0, q - 1 do out[k + 1] = tonumber(i[k]) end
+  return out, v[0]
+end
+
 return dngo
