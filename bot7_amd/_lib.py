@@ -31,6 +31,7 @@ SYMBOLS = [
     "b7_eval_posterior", "b7_posterior_get", "b7_pareto_front2", "b7_hypervolume2", "b7_ehvi_compute", "b7_ehvi_nominate",
     "b7_pareto_front3", "b7_nondominated_boxes3", "b7_hypervolume3", "b7_ehvi3_compute", "b7_ehvi3_nominate",
     "b7_logehvi_compute", "b7_logehvi_nominate", "b7_logehvi3_compute", "b7_logehvi3_nominate",
+    "b7_ts_paths", "b7_ts_hvi_nominate", "b7_ts_hvi3_nominate", "b7_hvi_compute",
     "b7_refine_default_opts", "b7_eval_nominate_refine", "b7_refine_last", "b7_refine_shape", "b7_refine_trace_enable", "b7_refine_trace", "b7_gp_grad_at", "b7_score_grad_compute",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
@@ -203,6 +204,10 @@ def load(which=None):
         "b7_eval_nominate_batch": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), i32, vp, vp, vp, vp]),
         "b7_ts_nominate": (i32, [vp, i32, C.POINTER(Hyp), i32, i32, C.c_uint64, vp, vp, vp, vp]),
         "b7_ts_last_paths": (i32, [vp, vp]),
+        "b7_ts_paths": (i32, [vp, i32, C.POINTER(Hyp), i32, i32, C.c_uint64, vp, vp]),
+        "b7_ts_hvi_nominate": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
+        "b7_ts_hvi3_nominate": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+        "b7_hvi_compute": (i32, [vp, vp, i64, i32, vp, i32, vp, vp]),
         "b7_kg_nominate": (i32, [vp, i32, C.POINTER(Hyp), i32, vp, vp, vp, vp, vp]),
         "b7_kg_trace_enable": (i32, [vp, i32]),
         "b7_kg_last": (i32, [vp, vp, vp, vp, vp, vp]),
@@ -350,7 +355,57 @@ class BlrThompson(object):
         return out
 
 
-class Context(BlrThompson):
+class ThompsonObjectives(object):
+    """Multi-objective Thompson sampling (b7_ts_paths, b7_ts_hvi_nominate / b7_ts_hvi3_nominate, b7_hvi_compute; csrc/ts_hvi.hip), mixed
+    into Context below.  A class of its own for BlrThompson's reason: the reuse catalogue is keyed on the methods Context itself defines;
+    these are held to the same call twice giving the same bits by tests/test_gpu_ts_hvi.py."""
+
+    def ts_paths(self, hyps, q, n_features=1024, seed=0, want_report=False):
+        """The path half of ts_nominate, kept (b7_ts_paths): the same q sample paths over the resident grid for the same arguments,
+        without the arg-mins; ts_last_paths / ts_last_draws serve it and ts_hvi_nominate reads it.  A change of the grid or the data
+        makes the paths stale for ts_hvi_nominate.  Returns None, or the report dict(jitter, info)."""
+        S = len(hyps)
+        arr, keep = self._pack_hyps(hyps, getattr(self, "_data_d", -1))
+        jit = np.zeros(max(S, 1), dtype=np.float64) if want_report else None
+        info = np.zeros(max(S, 1), dtype=np.int32) if want_report else None
+        self._ck(self._L.b7_ts_paths(self._h, S, arr, int(q), int(n_features), int(seed) & (2 ** 64 - 1), _ptr(jit), _ptr(info)))
+        self.fit_token += 1
+        self._ts_shape = (self.grid_shape()[0], max(int(q), 1), int(n_features), self._data_d, getattr(self, "_data_n", 0))
+        return {"jitter": jit[:S], "info": info[:S]} if want_report else None
+
+    def ts_hvi_nominate(self, others, front, ref):
+        """q nominees for two or three objectives by Thompson sampling (b7_ts_hvi_nominate / b7_ts_hvi3_nominate): this context holds
+        objective 1's kept paths (ts_paths), `others` -- one Context, or a pair -- those of the later objectives (contexts may
+        coincide), all over the same grid rows with the same q.  Path j picks the row whose sampled values improve the hypervolume of
+        (front + the earlier picks under path j) the most, over the rows no earlier path took; where none improves it, the first
+        minimum of objective 1 + (j mod m)'s path.  Returns (hvi[q], 1-based indices[q], y[q x m]); no grid is modified."""
+        others = [others] if isinstance(others, Context) else list(others)
+        m = 1 + len(others)
+        if m not in (2, 3) or any(not isinstance(o, Context) or o._L is not self._L for o in others):
+            raise Bot7HipError(-1, "ts_hvi_nominate: others is one Context (two objectives) or a pair (three), of the same library")
+        front, ref = _f64(front).reshape(-1, m), _f64(ref).ravel()
+        if ref.size != m:
+            raise Bot7HipError(-1, "ts_hvi_nominate: ref has one entry per objective")
+        q = getattr(self, "_ts_shape", (1, 1))[1]
+        hvi, idx, y = np.zeros(q, dtype=np.float64), np.zeros(q, dtype=np.int64), np.zeros((q, m), dtype=np.float64)
+        fn = self._L.b7_ts_hvi_nominate if m == 2 else self._L.b7_ts_hvi3_nominate
+        self._ck(fn(self._h, *[o._h for o in others], _ptr(front), front.shape[0], _ptr(ref), _ptr(hvi), _ptr(idx), _ptr(y)))
+        return hvi, idx, y
+
+    def hvi_compute(self, Y, front, ref):
+        """The hypervolume improvement of each row of Y (M1 x m, m = 2 or 3) against a canonical front, by ts_hvi_nominate's own
+        kernels (b7_hvi_compute); NaN for a row with an entry that is not finite."""
+        Y, ref = _f64(Y), _f64(ref).ravel()
+        m = ref.size
+        if Y.ndim != 2 or Y.shape[1] != m:
+            raise Bot7HipError(-1, "hvi_compute: Y M1 x m, front P x m, ref m")
+        front = _f64(front).reshape(-1, m)
+        out = np.empty(Y.shape[0], dtype=np.float64)
+        self._ck(self._L.b7_hvi_compute(self._h, _ptr(Y), Y.shape[0], m, _ptr(front), front.shape[0], _ptr(ref), _ptr(out)))
+        return out
+
+
+class Context(BlrThompson, ThompsonObjectives):
     """One GPU's worth of state: the resident candidate grid, the current GP fit, the score accumulator."""
 
     def __init__(self, device_id=0, _borrowed=None, lib=None):

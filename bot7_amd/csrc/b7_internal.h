@@ -263,6 +263,13 @@ struct b7_ctx {
   int ts_q = 0, ts_S = 0, ts_F = 0, ts_N = 0, ts_d = 0;
   // ... or a b7_blr_ts_nominate (blr_ts.hip): the paths are laid out alike, ts_draw holds eps [q][z] | weight [q][z] and ts_F = z
   bool ts_blr = false;
+  // ... or a b7_ts_paths, which stops short of the arg-mins.  ts_epoch: the context's epoch (below) when the paths were made; the
+  // multi-objective nominations (ts_hvi.hip) answer B7_ERR_STATE to paths of an earlier grid or data, b7_ts_last_paths still serves them
+  uint64_t ts_epoch = 0;
+  // ---- b7_ts_hvi_nominate / b7_ts_hvi3_nominate / b7_hvi_compute (ts_hvi.hip): the staged front or boxes, the picks, the arg-max
+  // partials (ts_hvi), the [q][M] copies of the objectives' paths (ts_hvi_t) and b7_hvi_compute's staging, apart from the kept paths
+  DevBuf ts_hvi, ts_hvi_t, ts_hvi_user;
+  int ts_hvi_layout = 1;  // 1: a pick reads a contiguous column of a [q][M] copy made once per call; 0: column j of [M][q] at stride q
   // ---- b7_eval_nominate_refine / b7_gp_grad_at (refine.hip): the workspace of 64 query columns, the last call's trace and result
   DevBuf refine_ws, refine_trace;
   DevBuf refine_user;       // b7_score_grad_compute's staging, apart from them
@@ -299,6 +306,7 @@ struct b7_ctx {
   int64_t Mfeat = 0;
   int zdim = 0;
   uint64_t feat_version = 0, grid_version = 0;
+  uint64_t epoch = 0;  // counts the changes of the grid, the data or the covariance kernel (post_forget): what was kept under an earlier one is stale
   DevBuf netbuf; // MLP weights/biases of the basis network
 
   // ---- the arg-max exchange (comm.hip): RCCL communicator of this rank, one per context = per GPU = per process
@@ -553,7 +561,7 @@ void acc_forget(b7_ctx *c);
 int acc_materialize(b7_ctx *c);
 void feas_forget(b7_ctx *c);  // the grid changed: there is no feasibility column until the next b7_feas_reset
 // the grid or the data changed: there is no kept posterior until the next b7_eval_posterior (ehvi.hip)
-static inline void post_forget(b7_ctx *c) { c->post_valid = false; }
+static inline void post_forget(b7_ctx *c) { c->post_valid = false, ++c->epoch; }
 int feas_write_zeros(b7_ctx *c);                      // L := 0.0 over the resident grid (allocates on demand)
 int launch_feas_add(b7_ctx *c, const double *src);    // L[j] += src[j], src: c->M doubles on the device
 int launch_feas_best(b7_ctx *c, double *best_val, int64_t *best_idx1);  // score:max(1) of L alone (waits)
@@ -670,6 +678,10 @@ struct Staged3 {
 };
 void stage3_host(const double *front, int P, const double *ref, Staged3 *st);
 int launch_ehvi3(b7_ctx *c, bool log, const double *const *mu, const double *const *var, const int *S, const Staged3 &st, int64_t M, double *out);
+// ehvi.hip: what ts_hvi.hip shares with the two-objective nomination: the front's check (messages named `who`) and the ordering of
+// the contexts' streams around the kernels of o[0]
+int front_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref);
+int ehvi_order(b7_ctx *const *o, int n, bool before);
 // mes.hip: c->ystar laid out for S samples of M rows at K levels; y* of nS samples (sample s at mu / var + s * stride) searched into
 // slots [slot0, slot0 + nS) of that layout, R + 1 launches; the device address of a slot's K values
 int mes_begin(b7_ctx *c, int S, int64_t M, int K);
@@ -719,6 +731,8 @@ int launch_believer(b7_ctx *c, int S, const BelPass &p, bool column);
 // rff.hip: path j = 0 .. q - 1 in order, each its first minimum over the rows of paths (M x q) that no earlier path took, a NaN never
 // winning, into pmin[j] / taken[j] (0-based) on the device; part: 16 nblk bytes of workspace, nblk <= 1024 blocks per pass
 int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, void *part, int nblk);
+// ... and path j's alone, over the rows not in taken[0 .. j) (ts_hvi.hip's fallback pick)
+int launch_ts_argmin(b7_ctx *c, const double *paths, int64_t M, int q, int j, double *pmin, long long *taken, void *part, int nblk);
 // blr_api.hip: what b7_blr_ts_nominate (blr_ts.hip) shares with the DNGO entry points
 int blr_upload_net(b7_ctx *c, const b7_mlp *net, int *z_out);
 int blr_feat_alloc(b7_ctx *c, int64_t M, int z);

@@ -22,8 +22,8 @@
 //
 // Out of scope, refused by name where it can be asked for: more than two objectives here (three through ehvi3.hip's b7_ehvi3_*, four
 // and more nowhere), correlated objectives / multi-task GPs,
-// batches, refinement, constraints combined with objectives, sharded grids and groups, the Bayesian-linear head,
-// ParEGO-style scalarisation.
+// batches of expected improvements (q nominees per call come from Thompson paths: ts_hvi.hip's b7_ts_hvi_nominate), refinement,
+// constraints combined with objectives, sharded grids and groups, the Bayesian-linear head, ParEGO-style scalarisation.
 #pragma clang fp contract(off)
 #include <math.h>
 
@@ -143,6 +143,9 @@ int front_defect(const double *front, int P, const double *ref, int *k_out) {
   return 0;
 }
 
+}  // namespace
+
+// front_refuse and ehvi_order are ts_hvi.hip's too (b7_internal.h)
 int front_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref) {
   if (!ref) return b7_fail(c, B7_ERR_INVALID, "%s: ref is NULL", who);
   if (P < 0 || P > B7_EHVI_PMAX) return b7_fail(c, B7_ERR_INVALID, "%s: a front of %d points (0..%d are built)", who, P, B7_EHVI_PMAX);
@@ -163,6 +166,8 @@ int front_refuse(b7_ctx *c, const char *who, const double *front, int P, const d
                      who, k + 1, k);
   }
 }
+
+namespace {
 
 // the front as the kernel reads it, on its way to c->ehvi_front on c's stream: the host block must outlive the copy (the callers wait)
 int front_stage(b7_ctx *c, const double *front, int P, const double *ref, std::vector<double> *host) {
@@ -225,6 +230,8 @@ int ehvi2_compute(b7_ctx *c, bool log, const char *who, const double *mu1, const
   return B7_OK;
 }
 
+}  // namespace
+
 // The streams of a nomination's contexts o[0 .. n - 1] are ordered by events both ways, as b7_feas_add_acc orders them.  before: the
 // first context's stream waits for what every other stream has been given (events 0 .. n - 2); after: whatever the other contexts
 // enqueue next waits for the kernels (event n - 1).  A context that appears twice is waited on once.
@@ -252,8 +259,6 @@ int ehvi_order(b7_ctx *const *o, int n, bool before) {
   }
   return B7_OK;
 }
-
-}  // namespace
 
 int ehvi_nominate(b7_ctx *const *o, int n, bool log, const char *who, const double *front, int P, const double *ref, double *best_val,
                   int64_t *best_idx1) {
@@ -319,7 +324,7 @@ int b7_eval_posterior(b7_ctx *c, int S, const b7_hyp *hyps, double *jitter_out, 
   B7_TRY(eval_validate(c, S, hyps, &spec, 0));
   if (c->ycols != 1) return b7_fail(c, B7_ERR_UNSUPPORTED, "eval_posterior: %d response columns (one is built)", c->ycols);
   B7_HIP(c, hipSetDevice(c->device));
-  post_forget(c);
+  c->post_valid = false;  // (not post_forget: neither the grid nor the data changes here)
   const size_t SM = (size_t)S * (size_t)c->M;
   B7_TRY(b7_ensure(c, c->post, sizeof(double) * 2 * SM));
   BelKeep keep;

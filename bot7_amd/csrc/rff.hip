@@ -359,35 +359,48 @@ struct YSwap {
 
 }  // namespace
 
-int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, void *part, int nblk) {
-  PhaseScope ps(c, "ts_argmin");
-  for (int j = 0; j < q; ++j) {
-    hipLaunchKernelGGL(ts_argmin_part_kernel, dim3(nblk), dim3(256), 0, c->stream, paths, M, q, j, (const long long *)taken,
-                       static_cast<TsBest *>(part));
-    hipLaunchKernelGGL(ts_argmin_final_kernel, dim3(1), dim3(256), 0, c->stream, (const TsBest *)part, nblk, j, taken, pmin);
-  }
+int launch_ts_argmin(b7_ctx *c, const double *paths, int64_t M, int q, int j, double *pmin, long long *taken, void *part, int nblk) {
+  hipLaunchKernelGGL(ts_argmin_part_kernel, dim3(nblk), dim3(256), 0, c->stream, paths, M, q, j, (const long long *)taken,
+                     static_cast<TsBest *>(part));
+  hipLaunchKernelGGL(ts_argmin_final_kernel, dim3(1), dim3(256), 0, c->stream, (const TsBest *)part, nblk, j, taken, pmin);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
 
-extern "C" {
+int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, void *part, int nblk) {
+  PhaseScope ps(c, "ts_argmin");
+  for (int j = 0; j < q; ++j) B7_TRY(launch_ts_argmin(c, paths, M, q, j, pmin, taken, part, nblk));
+  return B7_OK;
+}
 
-int b7_ts_nominate(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *path_min, int64_t *best_idx1,
-                   double *jitter_out, int *info_out) {
-  if (!c) return B7_ERR_INVALID;
-  if (c->group) return b7_fail(c, B7_ERR_STATE, "ts_nominate: this context belongs to a group (sharded Thompson sampling is not built)");
-  if (q < 1 || q > B7_BATCH_MAX) return b7_fail(c, B7_ERR_INVALID, "ts_nominate: q = %d not in [1, %d]", q, B7_BATCH_MAX);
+namespace {
+
+// What the paths core leaves for the arg-mins: the paths and the pieces of c->ts_work they use
+struct TsArgminWork {
+  double *paths, *pmin;
+  long long *taken;
+  TsBest *part;
+  int nblk;
+};
+
+// The path half of a Thompson nomination, b7_ts_nominate's and b7_ts_paths' (`who` in the messages): validation, draws, one fit per
+// hyper sample and the paths over the grid into c->ts_paths ([M][q]); the context remembers their shapes and its epoch.  null_out:
+// an output of the entry's own is missing (answered in its place among the checks); what: the arguments the entry needs, for that message.
+int ts_paths_core(b7_ctx *c, const char *who, bool null_out, const char *what, int S, const b7_hyp *hyps, int q, int F, uint64_t seed,
+                  double *jitter_out, int *info_out, TsArgminWork *aw) {
+  if (c->group) return b7_fail(c, B7_ERR_STATE, "%s: this context belongs to a group (sharded Thompson sampling is not built)", who);
+  if (q < 1 || q > B7_BATCH_MAX) return b7_fail(c, B7_ERR_INVALID, "%s: q = %d not in [1, %d]", who, q, B7_BATCH_MAX);
   if (F < 16 || F > B7_TS_MAX_FEATURES || F % 16)
-    return b7_fail(c, B7_ERR_INVALID, "ts_nominate: F = %d features: a multiple of 16 in [16, %d]", F, B7_TS_MAX_FEATURES);
-  if (S < 1) return b7_fail(c, B7_ERR_INVALID, "ts_nominate: S = %d hyper samples (at least one)", S);
-  if (!hyps || !path_min || !best_idx1) return b7_fail(c, B7_ERR_INVALID, "ts_nominate: NULL argument (hyps, path_min and best_idx1 are needed)");
+    return b7_fail(c, B7_ERR_INVALID, "%s: F = %d features: a multiple of 16 in [16, %d]", who, F, B7_TS_MAX_FEATURES);
+  if (S < 1) return b7_fail(c, B7_ERR_INVALID, "%s: S = %d hyper samples (at least one)", who, S);
+  if (!hyps || null_out) return b7_fail(c, B7_ERR_INVALID, "%s: NULL argument (%s)", who, what);
   if (c->comm && c->comm_world > 1)
-    return b7_fail(c, B7_ERR_UNSUPPORTED, "ts_nominate: a communicator of %d ranks (sharded Thompson sampling is not built)", c->comm_world);
-  if (!c->have_data) return b7_fail(c, B7_ERR_STATE, "ts_nominate: no resident data (call b7_gp_set_data first)");
-  if (c->M <= 0) return b7_fail(c, B7_ERR_STATE, "ts_nominate: no candidate grid on this context");
-  if (c->ycols != 1) return b7_fail(c, B7_ERR_UNSUPPORTED, "ts_nominate: %d response columns (one is built)", c->ycols);
-  if (c->d != c->dfit) return b7_fail(c, B7_ERR_INVALID, "ts_nominate: grid dims %d != data dims %d", c->d, c->dfit);
-  if (q > c->M) return b7_fail(c, B7_ERR_INVALID, "ts_nominate: q = %d exceeds the grid's %lld rows", q, (long long)c->M);
+    return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: a communicator of %d ranks (sharded Thompson sampling is not built)", who, c->comm_world);
+  if (!c->have_data) return b7_fail(c, B7_ERR_STATE, "%s: no resident data (call b7_gp_set_data first)", who);
+  if (c->M <= 0) return b7_fail(c, B7_ERR_STATE, "%s: no candidate grid on this context", who);
+  if (c->ycols != 1) return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: %d response columns (one is built)", who, c->ycols);
+  if (c->d != c->dfit) return b7_fail(c, B7_ERR_INVALID, "%s: grid dims %d != data dims %d", who, c->d, c->dfit);
+  if (q > c->M) return b7_fail(c, B7_ERR_INVALID, "%s: q = %d exceeds the grid's %lld rows", who, q, (long long)c->M);
   const int ns = S < q ? S : q, N = c->N, d = c->dfit, dpad = rff_dpad(d), np = c->Npad;
   for (int s = 0; s < ns; ++s) B7_TRY(check_hyp(c, &hyps[s], d));
   B7_HIP(c, hipSetDevice(c->device));
@@ -461,21 +474,46 @@ int b7_ts_nominate(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t 
       B7_TRY(launch_rff(c, grid, M, d, omf, dr.phase, wf, F, (const double *)c->mu.p, qs, paths, q, s, S, qs));
     }
   }
-  B7_TRY(launch_ts_argmins(c, paths, M, q, pmin, taken, part, nblk));
+  c->ts_valid = true;
+  c->ts_M = M, c->ts_q = q, c->ts_S = S, c->ts_F = F, c->ts_N = N, c->ts_d = d;
+  c->ts_epoch = c->epoch;
+  aw->paths = paths, aw->pmin = pmin, aw->taken = taken, aw->part = part, aw->nblk = nblk;
+  return B7_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int b7_ts_nominate(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *path_min, int64_t *best_idx1,
+                   double *jitter_out, int *info_out) {
+  if (!c) return B7_ERR_INVALID;
+  TsArgminWork aw;
+  B7_TRY(ts_paths_core(c, "ts_nominate", !path_min || !best_idx1, "hyps, path_min and best_idx1 are needed", S, hyps, q, F, seed, jitter_out,
+                       info_out, &aw));
+  c->ts_valid = false;  // until the arg-mins have come back
+  B7_TRY(launch_ts_argmins(c, aw.paths, c->ts_M, q, aw.pmin, aw.taken, aw.part, aw.nblk));
   long long tk[B7_BATCH_MAX];
-  B7_HIP(c, hipMemcpyAsync(path_min, pmin, sizeof(double) * q, hipMemcpyDeviceToHost, c->stream));
-  B7_HIP(c, hipMemcpyAsync(tk, taken, sizeof(long long) * q, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipMemcpyAsync(path_min, aw.pmin, sizeof(double) * q, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipMemcpyAsync(tk, aw.taken, sizeof(long long) * q, hipMemcpyDeviceToHost, c->stream));
   B7_HIP(c, hipStreamSynchronize(c->stream));
   for (int j = 0; j < q; ++j) best_idx1[j] = tk[j] + 1;
   c->ts_valid = true;
-  c->ts_M = M, c->ts_q = q, c->ts_S = S, c->ts_F = F, c->ts_N = N, c->ts_d = d;
+  return B7_OK;
+}
+
+int b7_ts_paths(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *jitter_out, int *info_out) {
+  if (!c) return B7_ERR_INVALID;
+  TsArgminWork aw;
+  B7_TRY(ts_paths_core(c, "ts_paths", false, "hyps is needed", S, hyps, q, F, seed, jitter_out, info_out, &aw));
+  B7_HIP(c, hipStreamSynchronize(c->stream));  // the fits' reports (jitter_out, info_out) are complete and the paths stand
   return B7_OK;
 }
 
 int b7_ts_last_paths(b7_ctx *c, double *paths_host) {
   if (!c) return B7_ERR_INVALID;
   if (!paths_host) return b7_fail(c, B7_ERR_INVALID, "ts_last_paths: NULL argument");
-  if (!c->ts_valid) return b7_fail(c, B7_ERR_STATE, "ts_last_paths: no successful b7_ts_nominate on this context");
+  if (!c->ts_valid) return b7_fail(c, B7_ERR_STATE, "ts_last_paths: no successful b7_ts_nominate or b7_ts_paths on this context");
   B7_HIP(c, hipSetDevice(c->device));
   B7_HIP(c, hipMemcpyAsync(paths_host, c->ts_paths.p, sizeof(double) * (size_t)c->ts_M * c->ts_q, hipMemcpyDeviceToHost, c->stream));
   B7_HIP(c, hipStreamSynchronize(c->stream));
@@ -484,7 +522,7 @@ int b7_ts_last_paths(b7_ctx *c, double *paths_host) {
 
 int b7_ts_last_draws(b7_ctx *c, int path, double *omega, double *phase, double *weight, double *eps) {
   if (!c) return B7_ERR_INVALID;
-  if (!c->ts_valid) return b7_fail(c, B7_ERR_STATE, "ts_last_draws: no successful b7_ts_nominate on this context");
+  if (!c->ts_valid) return b7_fail(c, B7_ERR_STATE, "ts_last_draws: no successful b7_ts_nominate or b7_ts_paths on this context");
   if (c->ts_blr) return b7_fail(c, B7_ERR_STATE, "ts_last_draws: the last nomination was b7_blr_ts_nominate's (b7_blr_ts_last_draws reads its draws)");
   if (path < 0 || path >= c->ts_q) return b7_fail(c, B7_ERR_INVALID, "ts_last_draws: path %d not in [0, %d)", path, c->ts_q);
   B7_HIP(c, hipSetDevice(c->device));

@@ -11,7 +11,12 @@ vector to add, average or download: the bot calls Context.ts_nominate in place o
 column.
 
 With the dngo model the posterior over the head's weights is a finite Gaussian and the path is exact, f_j(x) = mean + phi(x)' w_j with
-w_j ~ N(m, inv(A)): no random features (``nFeatures`` is unused), computed by b7_blr_ts_nominate through dngo.ts_nominate."""
+w_j ~ N(m, inv(A)): no random features (``nFeatures`` is unused), computed by b7_blr_ts_nominate through dngo.ts_nominate.
+
+With two or three objectives (config.bot.objectives; TSEMO, Bradford, Schweidtmann & Lapkin 2018) every objective's context keeps q
+paths of its own (Context.ts_paths) and the first context nominates: path j picks the row whose sampled values improve the
+hypervolume of the front plus the earlier picks under path j the most (Context.ts_hvi_nominate; b7_ts_hvi_nominate /
+b7_ts_hvi3_nominate)."""
 from .abstract import abstract
 
 
@@ -36,3 +41,12 @@ class thompson_sampling(abstract):
             return model.ts_nominate(observed, responses, candidates, hyps, q, seed)[1]
         config = config or self.config
         return ctx.ts_nominate(hyps, q, n_features=int(config.get("nFeatures") or 1024), seed=seed)[1]
+
+    def nominate_objectives(self, ctxs, hyps, q, seeds, front, ref, config=None):
+        """q nominees for len(ctxs) = 2 or 3 objectives -> (hvi[q], 1-based indices[q], y[q x m]).  ctxs[k] holds objective k + 1's
+        resident data and the common grid rows; hyps[k] / seeds[k] are its hyper samples and the seed of its paths.  The paths are
+        drawn in objective order (Context.ts_paths), then the first context nominates (Context.ts_hvi_nominate)."""
+        config = config or self.config
+        for ctx, h, seed in zip(ctxs, hyps, seeds):
+            ctx.ts_paths(h, q, n_features=int(config.get("nFeatures") or 1024), seed=seed)
+        return ctxs[0].ts_hvi_nominate(ctxs[1] if len(ctxs) == 2 else tuple(ctxs[1:]), front, ref)

@@ -55,6 +55,13 @@ config.score.type = 'log_expected_hypervolume_improvement' runs the same trials,
 observation has reached yet, late trials, a large grid -- and the linear arg-max would take row 1.  last_objectives["value"] is then
 the log value.  Everything refused with the linear type is refused with this one.
 
+config.score.type = 'thompson_sampling' with either config.bot.objectives form is MULTI-OBJECTIVE THOMPSON SAMPLING (TSEMO: Bradford,
+Schweidtmann & Lapkin 2018), for any config.bot.batch >= 1: per model-based trial every objective's model samples its hypers, stages
+its column on its own context and keeps config.bot.batch sample paths (ts_paths, a seed from the bot's generator each, in objective
+order); the first context nominates (ts_hvi_nominate): path j takes the row whose sampled values improve the hypervolume of the
+observations' front plus the earlier picks under path j the most.  The stolen rows leave every objective's grid; last_objectives keeps
+hyps, seeds, ref, front, the picks and their hvi.  Everything else refused with objectives stays refused.
+
 config.bot.trust_region (ours; None = the reference's loop, untouched) is a dict of length_init / length_min / length_max /
 success_tolerance / failure_tolerance / perturb / base: TRUST-REGION nomination (TuRBO-1: Eriksson et al. 2019).  No grid is made
 up front; config.grid.size is the number of candidates per trial.  Per model-based trial the hyper samples are drawn on the
@@ -148,6 +155,8 @@ def kg_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
 EHVI = "expected_hypervolume_improvement"
 LOG_EHVI = "log_expected_hypervolume_improvement"   # the same trials by the log score (b7_logehvi_nominate / b7_logehvi3_nominate)
 EHVI_KINDS = (EHVI, LOG_EHVI)
+THOMPSON = "thompson_sampling"   # with config.bot.objectives: q nominees per trial from every objective's sample paths (b7_ts_hvi_nominate)
+BATCH_MAX = 16  # B7_BATCH_MAX
 
 
 def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
@@ -160,7 +169,7 @@ def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
         return None
     if "models" in obj:
         return objectives3_refusal(config, model_class, sharded)
-    if int(config["bot"].get("batch", 1)) > 1:
+    if int(config["bot"].get("batch", 1)) > 1 and kind != THOMPSON:
         return "config.bot.objectives with config.bot.batch > 1: two-objective batches are not built"
     if config["bot"].get("refine"):
         return "config.bot.objectives with config.bot.refine: refinement of a two-objective nominee is not built"
@@ -170,7 +179,9 @@ def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
         return "config.bot.objectives over sharded candidates: two objectives over a sharded grid are not built"
     if model_class == "bot7.models.dngo":
         return "config.bot.objectives with the dngo model: the Bayesian-linear head keeps no posterior for a second objective"
-    if kind not in EHVI_KINDS:
+    if kind == THOMPSON and int(config["bot"].get("batch", 1)) > BATCH_MAX:
+        return "config.bot.objectives with config.bot.batch = %d: at most %d nominees per trial are built" % (int(config["bot"]["batch"]), BATCH_MAX)
+    if kind not in EHVI_KINDS and kind != THOMPSON:
         return "config.bot.objectives with %s: only %s is built" % (kind, EHVI)
     if (obj.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
         return "config.bot.objectives with the %s model: the second objective is modelled by a gp_regressor" % obj["model"]["type"]
@@ -184,7 +195,7 @@ def objectives3_refusal(config, model_class="bot7.models.gp_regressor", sharded=
     if len(models) != 2:
         return "config.bot.objectives with %d models: models holds the second and the third objective's (four or more objectives are not built)" \
             % len(models)
-    if int(config["bot"].get("batch", 1)) > 1:
+    if int(config["bot"].get("batch", 1)) > 1 and kind != THOMPSON:
         return "config.bot.objectives with config.bot.batch > 1: three-objective batches are not built"
     if config["bot"].get("refine"):
         return "config.bot.objectives with config.bot.refine: refinement of a three-objective nominee is not built"
@@ -196,7 +207,9 @@ def objectives3_refusal(config, model_class="bot7.models.gp_regressor", sharded=
         return "config.bot.objectives over sharded candidates: three objectives over a sharded grid are not built"
     if model_class == "bot7.models.dngo":
         return "config.bot.objectives with the dngo model: the Bayesian-linear head keeps no posterior for further objectives"
-    if kind not in EHVI_KINDS:
+    if kind == THOMPSON and int(config["bot"].get("batch", 1)) > BATCH_MAX:
+        return "config.bot.objectives with config.bot.batch = %d: at most %d nominees per trial are built" % (int(config["bot"]["batch"]), BATCH_MAX)
+    if kind not in EHVI_KINDS and kind != THOMPSON:
         return "config.bot.objectives with %s: only %s is built" % (kind, EHVI)
     for m in models:
         if (m or {}).get("type", "gp_regressor") != "gp_regressor":
@@ -206,7 +219,6 @@ def objectives3_refusal(config, model_class="bot7.models.gp_regressor", sharded=
 
 TR_BASES = ("sobol", "random")
 TR_KEYS = ("length_init", "length_min", "length_max", "success_tolerance", "failure_tolerance", "perturb", "base")
-BATCH_MAX = 16  # B7_BATCH_MAX
 
 
 def trust_region_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
@@ -400,7 +412,7 @@ class bayesopt(abstract):
         if self._thompson():
             if want_scores:
                 raise NotImplementedError("thompson_sampling has no score vector (eval with want_scores=False, or nominate)")
-            idx = self._ts_nominate(1, X_hid)[0]
+            idx = (self.nominate_objectives_ts(1, X_hid) if self._objectives() else self._ts_nominate(1, X_hid))[0]
             return None, None, idx
         if self._kg():
             val, idx = self._kg_nominate(X_hid)
@@ -709,6 +721,8 @@ class bayesopt(abstract):
         why = self._objectives_refusal()
         if why:
             raise NotImplementedError(why)
+        if self._thompson():
+            return self._run_trial_objectives_ts()
         if self._objectives3():
             return self._run_trial_objectives3()
         self.nTrials += 1
@@ -800,6 +814,88 @@ class bayesopt(abstract):
                 o["model"].init(self.observed, Y)
         return nominee, y
 
+    # ---- two or three objectives by Thompson sampling (config.score.type = 'thompson_sampling' with config.bot.objectives) -----------
+    def _objectives_ts(self):
+        return self._objectives() and self._thompson()
+
+    def nominate_objectives_ts(self, q=None, candidates=None):
+        """q nominees for two or three objectives by Thompson sampling (TSEMO) -> q 1-based indices into the candidates as they
+        stand.  Per model-based trial every objective's model samples its hypers and stages its column on its own context, every
+        context keeps q sample paths (ts_paths) drawn with a seed from the bot's generator, in objective order, and the first context
+        nominates (ts_hvi_nominate): path j picks the row whose sampled values improve the hypervolume of the observations' front
+        plus the earlier picks under path j the most.  self.last_objectives keeps what the call used."""
+        from bot7_amd import _lib
+        cand = self.candidates if candidates is None else candidates
+        why = self._objectives_refusal()
+        if why:
+            raise NotImplementedError(why)
+        q = int(self.config["bot"]["batch"] if q is None else q)
+        if self.nTrials <= self.config["bot"]["nInitial"]:        # :90-91, q distinct rows
+            if q == 1:
+                return [int(np.floor(self._rng.random() * cand.shape[0])) + 1]
+            return [int(i) + 1 for i in self._rng.choice(cand.shape[0], size=q, replace=False)]
+        three = self._objectives3()
+        others = self._objectives3_setup() if three else [self._objectives_setup()]
+        X_obs, model = self.observed, self.model
+        Ys = split_objectives3(self.responses) if three else split_objectives(self.responses)
+        ref = self.objectives_ref()
+        front, rows = (_lib.pareto_front3 if three else _lib.pareto_front2)(self.responses, ref)
+        host = np.asarray(cand, dtype=np.float64)
+        hyps = [self._sample_hyps(model, X_obs, Ys[0])] + [self._sample_hyps(o["model"], X_obs, Y) for o, Y in zip(others, Ys[1:])]
+        model.stage(X_obs, Ys[0], cand)
+        for o, Y in zip(others, Ys[1:]):
+            if o["grid"] is None or o["grid"].version != o["ctx"].grid_version or not np.array_equal(np.asarray(o["grid"]), host):
+                o["ctx"].grid_upload(host)
+                o["grid"] = DeviceGrid(host, o["ctx"], o["ctx"].grid_version)
+            o["model"].stage(X_obs, Y, o["grid"])
+        seeds = [int(self._rng.integers(0, 2 ** 63)) for _ in range(1 + len(others))]
+        hvi, idx, y = self.score.nominate_objectives([model.ctx] + [o["ctx"] for o in others], hyps, q, seeds, front, ref)
+        self.last_scores = None
+        self.last_objectives = {"hyps": hyps, "seeds": seeds, "ref": np.array(ref, dtype=np.float64), "front": front, "rows": rows,
+                                "index": [int(i) for i in idx], "hvi": np.array(hvi), "y": np.array(y)}
+        return [int(i) for i in idx]
+
+    def _run_trial_objectives_ts(self):
+        """run_trial's batch handling with the Thompson nominees of two or three objectives: the q stolen rows leave every
+        objective's resident grid in one stable pass (:118), the objective's rows are kept whole (:137-141), and at nInitial each
+        model is initialised on its own column (:147-149)."""
+        why = self._objectives_refusal()
+        if why:
+            raise NotImplementedError(why)
+        three = self._objectives3()
+        split = split_objectives3 if three else split_objectives
+        self.nTrials += 1
+        idx = self.nominate_objectives_ts()                        # :117
+        cand = self.candidates
+        rows = np.array(np.asarray(cand)[np.asarray(idx) - 1], dtype=np.float64)
+        host = T.remove(np.asarray(cand), idx)                     # :118, an index list (utils/tensor.lua:158-193)
+        if isinstance(cand, DeviceGrid) and cand.ctx is not None and cand.version == cand.ctx.grid_version:
+            assert np.array_equal(cand.ctx.grid_remove_rows(idx), rows)   # the same stable deletion on the resident copy
+            self.candidates = None if host is None else DeviceGrid(host, cand.ctx, cand.ctx.grid_version)
+        else:
+            self.candidates = host
+        for o in (self.objectives23 or ()) if three else ([self.objective2] if self.objective2 else ()):
+            if o["grid"] is not None and o["grid"].version == o["ctx"].grid_version:
+                o["ctx"].grid_remove_rows(idx)
+                o["grid"] = None if host is None else DeviceGrid(host, o["ctx"], o["ctx"].grid_version)
+        ys = np.concatenate([np.asarray(self.objective(r), dtype=np.float64).reshape(1, -1) for r in rows], 0)   # :124
+        split(ys)                                                  # (the shape check)
+        self.responses = ys if self.responses is None else np.concatenate([self.responses, ys], 0)
+        self.observed = rows if self.observed is None else np.concatenate([self.observed, rows], 0)            # :143-144
+        if self.model is not None and self.nTrials == self.config["bot"]["nInitial"]:
+            Ys = split(self.responses)
+            self.model.init(self.observed, Ys[0])                  # :147-149
+            for o, Y in zip(self._objectives3_setup() if three else [self._objectives_setup()], Ys[1:]):
+                o["model"].init(self.observed, Y)
+        best = int(ys[:, 0].argmin())
+        return rows[best], ys[best:best + 1]
+
+    def _entered_front(self, rows):
+        """Did a row of the last trial enter the front (rows: the front's 1-based response rows)."""
+        q = int(self.config["bot"]["batch"]) if self._objectives_ts() else 1
+        n = self.responses.shape[0] if q > 1 else self.nTrials    # one response row per trial unless the trial was a batch
+        return any(r in rows for r in range(n - q + 1, n + 1))
+
     def update_best(self, x, y):
         """bots/abstract.lua:171-177; under constraints the best is the best FEASIBLE trial (column 0 among the rows with c_k <= t_k);
         under two objectives there is no single best: best["front"] / ["rows"] are the front of all trials so far under this
@@ -811,7 +907,7 @@ class bayesopt(abstract):
             front, rows = _lib.pareto_front3(self.responses, ref)
             self.best["ref"], self.best["front"], self.best["rows"] = ref, front, rows
             self.best["hv"] = _lib.hypervolume3(front, ref)
-            if self.nTrials in rows:
+            if self._entered_front(rows):
                 self.best["t"], self.best["x"], self.best["y"] = self.nTrials, x, np.asarray(y, dtype=np.float64).reshape(1, -1)
             return
         if self._objectives():
@@ -820,7 +916,7 @@ class bayesopt(abstract):
             front, rows = _lib.pareto_front2(self.responses, ref)
             self.best["ref"], self.best["front"], self.best["rows"] = ref, front, rows
             self.best["hv"] = _lib.hypervolume2(front, ref)
-            if self.nTrials in rows:
+            if self._entered_front(rows):
                 self.best["t"], self.best["x"], self.best["y"] = self.nTrials, x, np.asarray(y, dtype=np.float64).reshape(1, -1)
             return
         if not self._constrained():

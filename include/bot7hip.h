@@ -909,6 +909,50 @@ int b7_logehvi3_compute(b7_ctx *ctx, const double *const *mu /*3*/, const double
 int b7_logehvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const double *front /*P x 3*/, int P, const double *ref /*3*/,
                          double *best_val, int64_t *best_idx1);
 
+/* MULTI-OBJECTIVE THOMPSON SAMPLING: q nominees per call for two or three objectives (TSEMO: Bradford, Schweidtmann & Lapkin 2018).
+ * No counterpart in the reference.  Under a sample path the world is deterministic, so the best addition to a batch is the row whose
+ * sampled values improve the hypervolume most.  All objectives are minimised; fronts are canonical (b7_pareto_front2 / 3).
+ *
+ * b7_ts_paths: the path half of b7_ts_nominate, as b7_eval_posterior is the posterior half of b7_eval_nominate: the same validation,
+ * draws, fits and paths for the same arguments, bit for bit, without the arg-mins.  b7_ts_last_paths and b7_ts_last_draws serve it.
+ * The context remembers which grid and data the kept paths belong to: after a change of either (or of the covariance kernel) the
+ * nominations below answer B7_ERR_STATE, the way a kept posterior is forgotten; b7_ts_last_paths keeps serving the paths as they were
+ * made.  Errors as b7_ts_nominate's (its two outputs aside). */
+int b7_ts_paths(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *jitter_out /*S*/, int *info_out /*S*/);
+/* The nominations.  ctx holds objective 1's kept paths (b7_ts_paths, or a b7_ts_nominate), other / other2, other3 those of the
+ * later objectives, each drawn with its own seed and hyper samples over the same grid rows with the same q; contexts may coincide.
+ * The score of a row under path j against a front is the hypervolume improvement of its sampled values y:
+ *   two objectives    hvi(y) = sum_{k = 0 .. P} max(a_k+1 - max(a_k, y1), 0) * max(b_k - y2, 0),   a_0 = -inf, a_P+1 = r1, b_0 = r2
+ *   three objectives  hvi(y) = sum_b (max(u1 - max(l1, y1), 0) * max(u2 - max(l2, y2), 0)) * max(u3 - y3, 0)
+ * over the strips in ascending order, over the boxes of b7_nondominated_boxes3 in its order, a running sum from 0, one rounded
+ * operation per operator: the deterministic limit of b7_ehvi_compute / b7_ehvi3_compute.  A row with a value that is not finite
+ * scores NaN, and a NaN never wins.  A value depends on its own row and the front alone.
+ * The rule, for path j = 0 .. q - 1 in order:
+ *   1. the working front of path j is the canonical front (b7_pareto_front2 / 3's logic, the caller's points first) of the caller's
+ *      front and the earlier picks' values under path j, (f_1j(r_i), f_2j(r_i)[, f_3j(r_i)]) for i < j;
+ *   2. the pick r_j is the row with the largest hvi of its path-j values against that front over the rows no earlier path took, ties
+ *      to the lowest row; hvi_out[j] is that value, best_idx1[j] the row (1-based), y_out row j (nullable) its path-j values;
+ *   3. where no row has a positive hvi (the path's whole image is dominated or outside the box) the pick is the first minimum of
+ *      objective 1 + (j mod m)'s path j over the rows not taken (b7_ts_nominate's arg-min), and hvi_out[j] = 0.
+ * Deterministic; since paths depend on (seed, j) alone the picks of a q = 3 call are the first three of a q = 5 call.  No grid is
+ * modified, the score accumulator and the kept posterior are untouched.  The streams of the contexts are ordered by events both
+ * ways, as b7_ehvi_nominate orders them.
+ * B7_ERR_STATE, the case named: an objective has no kept paths, or its paths are stale; a context is a member of a group.
+ * B7_ERR_INVALID: q or M differ between the contexts; P + q - 1 exceeds B7_EHVI_PMAX / B7_EHVI3_PMAX (the working front can grow by
+ * a point per pick); the front is not canonical or ref not finite (as b7_ehvi_nominate answers); a NULL argument.
+ * B7_ERR_UNSUPPORTED: contexts on different devices; kept paths left by b7_blr_ts_nominate (the DNGO head is not built here).
+ * Device memory: small staging, plus m q M doubles for the [q][M] copies of the paths that the picks read (q > 1).
+ * Not built: sharded grids and groups, the DNGO head, four or more objectives, correlated objectives.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+int b7_ts_hvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front /*P x 2*/, int P, const double *ref /*2*/,
+                       double *hvi_out /*q*/, int64_t *best_idx1 /*q*/, double *y_out /*q x 2, nullable*/);
+int b7_ts_hvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const double *front /*P x 3*/, int P, const double *ref /*3*/,
+                        double *hvi_out /*q*/, int64_t *best_idx1 /*q*/, double *y_out /*q x 3, nullable*/);
+/* The score alone on host arrays (the b7_ei_compute of this feature), by the nomination's own kernels: out[i] = hvi(Y[i]) for m = 2
+ * or 3 objectives; NaN for a row with an entry that is not finite.  The kept paths are untouched. */
+int b7_hvi_compute(b7_ctx *ctx, const double *Y /*M1 x m*/, int64_t M1, int m, const double *front /*P x m*/, int P,
+                   const double *ref /*m*/, double *out /*M1*/);
+
 /* ---- trust-region nomination (TuRBO: Eriksson, Pearce, Gardner, Turner & Poloczek, NeurIPS 2019).  No counterpart in the
  * reference.  Three host-only pieces (no context, no GPU) that both host languages share, and the device map b7_grid_trust_region
  * (with the grids, above).

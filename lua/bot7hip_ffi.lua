@@ -122,6 +122,10 @@ int b7_logehvi_compute(b7_ctx *ctx, const double *mu1, const double *var1, int S
 int b7_logehvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front , int P, const double *ref , double *best_val, int64_t *best_idx1);
 int b7_logehvi3_compute(b7_ctx *ctx, const double *const *mu , const double *const *var , const int *S , const double *front , int P, const double *ref , int64_t M, double *out );
 int b7_logehvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const double *front , int P, const double *ref , double *best_val, int64_t *best_idx1);
+int b7_ts_paths(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *jitter_out , int *info_out );
+int b7_ts_hvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front , int P, const double *ref , double *hvi_out , int64_t *best_idx1 , double *y_out );
+int b7_ts_hvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const double *front , int P, const double *ref , double *hvi_out , int64_t *best_idx1 , double *y_out );
+int b7_hvi_compute(b7_ctx *ctx, const double *Y , int64_t M1, int m, const double *front , int P, const double *ref , double *out );
 int b7_tr_box(int d, int S, const b7_hyp *hyps, const double *center , double length, const double *mins , const double *maxes , double *lo , double *hi );
 typedef struct { double length, length_init, length_min, length_max, best; int succ, fail, succ_tol, fail_tol; int restarts; } b7_tr_state;
 int b7_tr_init(b7_tr_state *st, int d, int q, double length_init, double length_min, double length_max, int succ_tol, int fail_tol);

@@ -190,6 +190,9 @@ end
 function bot:nominate_batch(q, candidates)
   local candidates = candidates or self.candidates
   q = q or self.config.bot.batch or 1
+  if self.config.bot.objectives and torch.type(self.score) == 'bot7.scores.thompson_sampling_hip' then
+    return self:nominate_objectives_ts(q, candidates)                        -- multi-objective Thompson sampling: below
+  end
   if q == 1 then return self:nominate(candidates) end
   assert(D.world == 1 and not hip.group, 'nominate_batch: one rank, no group (sharded batches are not built)')
   if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91, q distinct rows
@@ -389,6 +392,9 @@ function bot:nominate_objectives(candidates)
   local candidates = candidates or self.candidates
   assert(D.world == 1 and not hip.group, 'nominate_objectives: one rank, no group (two objectives over a sharded grid are not built)')
   local obj = assert(self.config.bot.objectives, 'nominate_objectives: config.bot.objectives is not set')
+  if torch.type(self.score) == 'bot7.scores.thompson_sampling_hip' then      -- Thompson paths, two or three objectives, any batch: below
+    return self:nominate_objectives_ts(self.config.bot.batch or 1, candidates)
+  end
   if obj.models then return self:nominate_objectives3(candidates) end       -- {ref, models = {m2, m3}}: three objectives, below
   assert((self.config.bot.batch or 1) == 1, 'nominate_objectives: config.bot.batch > 1 (two-objective batches are not built)')
   assert(not self.config.bot.refine, 'nominate_objectives: config.bot.refine (refinement of a two-objective nominee is not built)')
@@ -541,6 +547,125 @@ function bot:nominate_objectives3(candidates)
   self.best_score = v[0]
   self.objectives_idx = tonumber(i[0])   -- what the driver steals next: follow_steal
   return torch.LongTensor{self.objectives_idx}
+end
+
+-- MULTI-OBJECTIVE THOMPSON SAMPLING (b7_ts_paths + b7_ts_hvi_nominate / b7_ts_hvi3_nominate; no counterpart in the reference; TSEMO:
+-- Bradford, Schweidtmann & Lapkin 2018): config.score.type = 'thompson_sampling' with either config.bot.objectives form, any
+-- config.bot.batch >= 1.  Per model-based trial every objective's model samples its hypers, stages its column on its own context and
+-- keeps q sample paths (b7_ts_paths, a seed from torch's generator each, in objective order); the first context nominates: path j
+-- takes the row whose sampled values improve the hypervolume of the observations' front plus the earlier picks under path j the most.
+-- Returns a LongTensor of q indices into `candidates` as it stands; the driver steals them (utils.tensor.steal takes an index list)
+-- and the next call deletes them from the other contexts' grids before anything is staged there.  One rank, no group, no refinement,
+-- no constraints, no trust region; at parity with harness/bots/bayesopt.py's nominate_objectives_ts.
+local function follow_steal_rows(con, idxs, candidates)
+  local r = con.resident
+  if r == nil then return end
+  local n = idxs and idxs:nElement() or 0
+  if n > 0 and candidates:isContiguous() and r.rows == candidates:size(1) + n and r.cols == candidates:size(2) then
+    local arr = ffi.new('int64_t[?]', n)
+    for k = 1, n do arr[k - 1] = idxs[k] end
+    hip.check(hip.C.b7_grid_remove_rows(con.ctx, arr, n, nil))
+    con.resident = {ptr = torch.data(candidates), rows = candidates:size(1), cols = candidates:size(2)}
+  elseif not (r.rows == candidates:size(1) and r.ptr == torch.data(candidates)) then
+    con.resident = nil
+  end
+end
+
+function bot:nominate_objectives_ts(q, candidates)
+  local candidates = candidates or self.candidates
+  q = q or self.config.bot.batch or 1
+  assert(D.world == 1 and not hip.group, 'nominate_objectives_ts: one rank, no group (objectives over a sharded grid are not built)')
+  local obj = assert(self.config.bot.objectives, 'nominate_objectives_ts: config.bot.objectives is not set')
+  local m = obj.models and 3 or 2
+  assert(m == 2 or (type(obj.models) == 'table' and #obj.models == 2),
+         'nominate_objectives_ts: config.bot.objectives.models holds two models, the second and the third objective (four or more objectives are not built)')
+  assert(q >= 1 and q <= hip.BATCH_MAX, 'nominate_objectives_ts: config.bot.batch outside 1 .. BATCH_MAX')
+  assert(not self.config.bot.refine, 'nominate_objectives_ts: config.bot.refine (refinement of a multi-objective nominee is not built)')
+  assert(not self.config.bot.constraints, 'nominate_objectives_ts: config.bot.constraints (constraints combined with objectives are not built)')
+  assert(not self.config.bot.trust_region, 'nominate_objectives_ts: config.bot.trust_region (objectives inside a trust region are not built)')
+  assert(torch.type(self.score) == 'bot7.scores.thompson_sampling_hip', 'nominate_objectives_ts: config.score.type must be thompson_sampling')
+  if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91, q distinct rows
+    if q == 1 then return torch.rand(1):mul(candidates:size(1)):long():add(1) end
+    return torch.randperm(candidates:size(1)):narrow(1, 1, q):long()
+  end
+  local model, keep = self.model, {}
+  assert(torch.type(model) == 'bot7.models.gp_hip', 'nominate_objectives_ts: needs the gp_hip model (the Bayesian-linear head is not built)')
+  local R, S = self.responses, self.config.bot.nSamples
+  assert(R:dim() == 2 and R:size(2) == m, 'nominate_objectives_ts: the objective must return rows of one column per objective')
+  local X_obs, Y1 = self.observed, R:narrow(2, 1, 1):contiguous()
+  if self.objectives_ts == nil then
+    self.objectives_ts = {}
+    for k = 1, m - 1 do
+      local ctxp = ffi.new('b7_ctx*[1]')
+      assert(hip.C.b7_create(ctxp, hip.device) == 0, 'nominate_objectives_ts: b7_create failed')   -- the objective's device
+      self.objectives_ts[k] = {model = bot7.models.gp_hip(m == 2 and obj.model or obj.models[k]), ctx = ffi.gc(ctxp[0], hip.C.b7_destroy),
+                               kernel = hip.KERNEL_ARDSE}
+    end
+  end
+  local others = self.objectives_ts
+  local ref = hip.pin(torch.Tensor(m))
+  keep[#keep + 1] = ref
+  if obj.ref then
+    for k = 1, m do ref[k] = obj.ref[k] end
+  else
+    local hi, lo = R:max(1):view(-1), R:min(1):view(-1)
+    for k = 1, m do
+      local span = hi[k] - lo[k]
+      if not (span > 0) then span = math.max(math.abs(hi[k]), 1) end
+      ref[k] = hi[k] + 0.1 * span
+    end
+  end
+  local Rc = hip.pin(R:contiguous())
+  keep[#keep + 1] = Rc
+  local pmax = (m == 2) and hip.EHVI_PMAX or hip.EHVI3_PMAX
+  local front, P = ffi.new('double[?]', m * math.max(1, math.min(R:size(1), pmax))), ffi.new('int[1]')
+  if m == 2 then
+    assert(hip.C.b7_pareto_front2(hip.data(Rc), R:size(1), hip.data(ref), front, nil, P) == 0,
+           'nominate_objectives_ts: a front of more than EHVI_PMAX points, or a reference point that is not finite')
+  else
+    assert(hip.C.b7_pareto_front3(hip.data(Rc), R:size(1), hip.data(ref), front, nil, P) == 0,
+           'nominate_objectives_ts: a front of more than EHVI3_PMAX points, or a reference point that is not finite')
+  end
+  local F = (self.score.config or {}).nFeatures or 1024
+  local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+  -- every model samples its hypers and stages its column, in objective order ...
+  local hyps = {}
+  hyps[1] = sample_hyps(model, X_obs, Y1, S, keep)
+  model:stage(X_obs, Y1, candidates)
+  hip.set_kernel(model.kernel_code)
+  for k = 1, m - 1 do
+    local o, Yk = others[k], R:narrow(2, k + 1, 1):contiguous()
+    follow_steal_rows(o, self.objectives_rows, candidates)
+    on_context(o, function()
+      if not o.inited then o.model:init(X_obs, Yk); o.inited = true end
+      hyps[k + 1] = sample_hyps(o.model, X_obs, Yk, S, keep)
+      o.model:stage(X_obs, Yk, candidates)
+      hip.set_kernel(o.model.kernel_code)
+    end)
+  end
+  -- ... then the paths, a seed each, in objective order, and the first context nominates
+  local seeds = {}
+  for k = 1, m do seeds[k] = ffi.new('uint64_t', torch.random()) end
+  hip.check(hip.C.b7_ts_paths(hip.ctx, S, hyps[1], q, F, seeds[1], jit, info))
+  for k = 1, m - 1 do
+    hip.check(hip.C.b7_ts_paths(others[k].ctx, S, hyps[k + 1], q, F, seeds[k + 1], nil, nil))
+  end
+  local v, i, y = ffi.new('double[?]', q), ffi.new('int64_t[?]', q), ffi.new('double[?]', q * m)
+  if m == 2 then
+    hip.check(hip.C.b7_ts_hvi_nominate(hip.ctx, others[1].ctx, front, P[0], hip.data(ref), v, i, y))
+  else
+    hip.check(hip.C.b7_ts_hvi3_nominate(hip.ctx, others[1].ctx, others[2].ctx, front, P[0], hip.data(ref), v, i, y))
+  end
+  for s = 0, S - 1 do
+    if jit[s] > 0 then   -- the reference's warning text, utils/math.lua:210-212
+      print(string.format('Warning: utils.math.chol succeeded in factorizing the\ninput matrix after applying a jitter of %.2e', jit[s]))
+    end
+  end
+  local out = torch.LongTensor(q)
+  for k = 0, q - 1 do out[k + 1] = tonumber(i[k]) end
+  self.best_score = v[0]
+  self.objectives_rows = out   -- what the driver steals next: follow_steal_rows
+  return out
 end
 
 -- ---- trust-region nomination (TuRBO-1: Eriksson, Pearce, Gardner, Turner & Poloczek, NeurIPS 2019; no original) --------------

@@ -141,8 +141,10 @@ end
 
 do
   -- Thompson sampling (b7_ts_nominate; no original): not a per-point score.  The class only carries config.nFeatures to
-  -- bots_bayesopt_hip.lua, whose nominate / nominate_batch call the library in place of eval + arg-max.  Checked by the static
-  -- checker only (no LuaJIT / Torch7 in the pipeline).
+  -- bots_bayesopt_hip.lua, whose nominate / nominate_batch call the library in place of eval + arg-max.  With config.bot.objectives
+  -- (two or three objectives, any batch) its nominate_objectives_ts keeps every objective's paths (b7_ts_paths) and nominates by the
+  -- hypervolume improvement of their values (b7_ts_hvi_nominate / b7_ts_hvi3_nominate).  Checked by the static checker only (no
+  -- LuaJIT / Torch7 in the pipeline).
   local TS, parent = torch.class('bot7.scores.thompson_sampling_hip', 'bot7.scores.abstract')
   function TS:__init(config)
     parent.__init(self)
