@@ -32,6 +32,7 @@ SYMBOLS = [
     "b7_pareto_front3", "b7_nondominated_boxes3", "b7_hypervolume3", "b7_ehvi3_compute", "b7_ehvi3_nominate",
     "b7_logehvi_compute", "b7_logehvi_nominate", "b7_logehvi3_compute", "b7_logehvi3_nominate",
     "b7_ts_paths", "b7_ts_hvi_nominate", "b7_ts_hvi3_nominate", "b7_hvi_compute",
+    "b7_ts_feas_nominate", "b7_ts_feas_compute",
     "b7_refine_default_opts", "b7_eval_nominate_refine", "b7_refine_last", "b7_refine_shape", "b7_refine_trace_enable", "b7_refine_trace", "b7_gp_grad_at", "b7_score_grad_compute",
     "b7_nominate_commit", "b7_shard_commit_rule", "b7_exchange_info",
     "b7_group_create", "b7_group_destroy", "b7_group_last_error", "b7_group_info", "b7_group_ctx", "b7_group_set_workspace", "b7_group_gp_set_opts", "b7_group_gp_set_kernel",
@@ -46,6 +47,8 @@ SYMBOLS = [
 KG_MAX_POINTS = 16  # B7_KG_MAX_POINTS
 EHVI_PMAX, EHVI_SMAX, EHVI_SREG = 256, 32, 10  # B7_EHVI_PMAX (front points), B7_EHVI_SMAX (hyper samples per objective), B7_EHVI_SREG (of them in registers)
 EHVI3_PMAX = 256  # B7_EHVI3_PMAX (front points of three objectives)
+TS_FEAS_CMAX = 8  # B7_TS_FEAS_CMAX (constraints of a constrained Thompson nomination)
+TS_FEAS_THREADS, TS_FEAS_BLOCKS_MAX = 256, 1024  # csrc/ts_feas.hip's launch shape: above their product rows the grid-stride loop wraps
 
 
 class Bot7HipError(RuntimeError):
@@ -208,6 +211,8 @@ def load(which=None):
         "b7_ts_hvi_nominate": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
         "b7_ts_hvi3_nominate": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp]),
         "b7_hvi_compute": (i32, [vp, vp, i64, i32, vp, i32, vp, vp]),
+        "b7_ts_feas_nominate": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "b7_ts_feas_compute": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
         "b7_kg_nominate": (i32, [vp, i32, C.POINTER(Hyp), i32, vp, vp, vp, vp, vp]),
         "b7_kg_trace_enable": (i32, [vp, i32]),
         "b7_kg_last": (i32, [vp, vp, vp, vp, vp, vp]),
@@ -405,7 +410,52 @@ class ThompsonObjectives(object):
         return out
 
 
-class Context(BlrThompson, ThompsonObjectives):
+class ThompsonFeasible(object):
+    """Constrained Thompson sampling (b7_ts_feas_nominate, b7_ts_feas_compute; csrc/ts_feas.hip), mixed into Context below.  A class of
+    its own for BlrThompson's reason; these are held to the same call twice giving the same bits by tests/test_gpu_ts_feas.py."""
+
+    def ts_feas_nominate(self, cons, thresholds):
+        """q feasible-first nominees under C constraints c_k <= thresholds[k] by Thompson sampling (b7_ts_feas_nominate): this context
+        holds the objective's kept paths (ts_paths), cons[k] -- Contexts of the same library, which may coincide -- those of constraint
+        k + 1, all over the same grid rows with the same q.  Path j picks the row of lowest f_j among the rows where every c_kj <= t_k
+        that no earlier path took; where the path sees no feasible row, the row of smallest total violation.  Returns dict(key[q],
+        cls[q] (0 feasible, 1 not, -1 no row), index[q] (1-based, 0 for no row), y[q x (1 + C)], reruns: 0 in the library's default arm, which
+        picks path by path); no grid is modified."""
+        cons = list(cons)
+        if any(not isinstance(o, Context) or o._L is not self._L for o in cons):
+            raise Bot7HipError(-1, "ts_feas_nominate: cons is a list of Contexts of the same library")
+        thr = _f64(thresholds).ravel()
+        if thr.size != len(cons):
+            raise Bot7HipError(-1, "ts_feas_nominate: one threshold per constraint context")
+        Cn = len(cons)
+        q = getattr(self, "_ts_shape", (1, 1))[1]
+        handles = (C.c_void_p * max(Cn, 1))(*[o._h for o in cons])
+        qmax = 16   # B7_BATCH_MAX: the library writes as many entries as the contexts keep paths
+        key, cls, idx = np.zeros(qmax, dtype=np.float64), np.zeros(qmax, dtype=np.int32), np.zeros(qmax, dtype=np.int64)
+        y, reruns = np.zeros(qmax * (1 + Cn), dtype=np.float64), C.c_int(0)
+        self._ck(self._L.b7_ts_feas_nominate(self._h, C.cast(handles, C.c_void_p) if Cn else None, _ptr(thr) if Cn else None, Cn, _ptr(key),
+                                             _ptr(cls), _ptr(idx), _ptr(y), C.c_void_p(C.addressof(reruns))))
+        return {"key": key[:q].copy(), "cls": cls[:q].copy(), "index": idx[:q].copy(), "y": y[:q * (1 + Cn)].reshape(q, 1 + Cn).copy(),
+                "reruns": int(reruns.value)}
+
+    def ts_feas_compute(self, f, cvals, thresholds, want_viol=True):
+        """ts_feas_nominate's kernels and resolution on host arrays (b7_ts_feas_compute): f M1 x q, cvals C x M1 x q (or a list of C
+        arrays M1 x q), thresholds C.  Returns dict(viol[M1 x q] (NaN where a value is NaN; None unless want_viol), key[q], cls[q],
+        index[q])."""
+        f, thr = _f64(f), _f64(thresholds).ravel()
+        Cn = thr.size
+        if f.ndim != 2:
+            raise Bot7HipError(-1, "ts_feas_compute: f M1 x q, cvals C x M1 x q, thresholds C")
+        cv = _f64(np.asarray(cvals, dtype=np.float64).reshape((Cn,) + f.shape)) if Cn else None
+        M1, q = f.shape
+        viol = np.empty((M1, q), dtype=np.float64) if want_viol else None
+        key, cls, idx = np.zeros(max(q, 1), dtype=np.float64), np.zeros(max(q, 1), dtype=np.int32), np.zeros(max(q, 1), dtype=np.int64)
+        self._ck(self._L.b7_ts_feas_compute(self._h, _ptr(f), _ptr(cv), _ptr(thr) if Cn else None, M1, q, Cn, _ptr(viol), _ptr(key), _ptr(cls),
+                                            _ptr(idx)))
+        return {"viol": viol, "key": key[:q], "cls": cls[:q], "index": idx[:q]}
+
+
+class Context(BlrThompson, ThompsonObjectives, ThompsonFeasible):
     """One GPU's worth of state: the resident candidate grid, the current GP fit, the score accumulator."""
 
     def __init__(self, device_id=0, _borrowed=None, lib=None):

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "_build")
 OUT = os.path.join(HERE, "libbot7hip.so")
-SOURCES = ["context.hip", "grid_api.hip", "gp_api.hip", "nominate.hip", "blr_api.hip", "sobol.hip", "covar.hip", "potrf.hip", "potrf_persist.hip", "posterior.hip", "score.hip", "extras.hip", "comm.hip", "group.hip", "blr_small.hip", "gp_small.hip", "kpost_small.hip", "batch.hip", "mes.hip", "rff.hip", "slice.hip", "refine.hip", "kg.hip", "ehvi.hip", "trust_region.hip", "ehvi3.hip", "blr_ts.hip", "ts_hvi.hip"]
+SOURCES = ["context.hip", "grid_api.hip", "gp_api.hip", "nominate.hip", "blr_api.hip", "sobol.hip", "covar.hip", "potrf.hip", "potrf_persist.hip", "posterior.hip", "score.hip", "extras.hip", "comm.hip", "group.hip", "blr_small.hip", "gp_small.hip", "kpost_small.hip", "batch.hip", "mes.hip", "rff.hip", "slice.hip", "refine.hip", "kg.hip", "ehvi.hip", "trust_region.hip", "ehvi3.hip", "blr_ts.hip", "ts_hvi.hip", "ts_feas.hip"]
 # The DIAGNOSTIC build (tools/_build/libbot7hip_diag.so, -DB7_DIAG): the shipped sources + round 3's likelihood kernel kept as
 # a bit-for-bit reference.  Only translation units that mention B7_DIAG are compiled a second time; the rest are shared.
 DIAG_ONLY_SOURCES = ["nll_small.hip"]

@@ -270,6 +270,12 @@ struct b7_ctx {
   // partials (ts_hvi), the [q][M] copies of the objectives' paths (ts_hvi_t) and b7_hvi_compute's staging, apart from the kept paths
   DevBuf ts_hvi, ts_hvi_t, ts_hvi_user;
   int ts_hvi_layout = 1;  // 1: a pick reads a contiguous column of a [q][M] copy made once per call; 0: column j of [M][q] at stride q
+  // ---- b7_ts_feas_nominate / b7_ts_feas_compute (ts_feas.hip): the arg-min partials, the paths' bests, the exclusion list and the
+  // picks' values (ts_feas), and b7_ts_feas_compute's staging, apart from the kept paths
+  DevBuf ts_feas, ts_feas_user;
+  int ts_feas_onepass = 0;  // 0: path by path, q chained passes (default: the faster arm on real paths); 1: all q paths scored in one pass, exclusions resolved on the host
+  // the constraint contexts' streams -> this one (0 .. C - 1), and back (the last); created on first use
+  hipEvent_t ev_ts_feas[B7_TS_FEAS_CMAX + 1] = {};
   // ---- b7_eval_nominate_refine / b7_gp_grad_at (refine.hip): the workspace of 64 query columns, the last call's trace and result
   DevBuf refine_ws, refine_trace;
   DevBuf refine_user;       // b7_score_grad_compute's staging, apart from them

@@ -166,6 +166,7 @@ int b7_create(b7_ctx **out, int device_id) {
     if (g >= 1 && g <= 8) c->potrf_group = g;
   }
   if (const char *pv = getenv("B7_TS_HVI_LAYOUT")) c->ts_hvi_layout = atoi(pv) ? 1 : 0;  // 0: a pick reads column j of [M][q] at stride q; 1: the [q][M] copy (default)
+  if (const char *pv = getenv("B7_TS_FEAS_ONEPASS")) c->ts_feas_onepass = atoi(pv) ? 1 : 0;  // 0: the constrained Thompson pick path by path, q chained passes (default); 1: one pass for all q paths, taken rows resolved on the host
 #endif
   e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fit, hipEventDisableTiming);
@@ -198,7 +199,7 @@ void b7_destroy(b7_ctx *c) {
                    &c->bLinv, &c->balpha, &c->bmu, &c->bvar, &c->ticket, &c->bel, &c->belvec, &c->ystar, &c->mes_ticket, &c->mes_user,
                    &c->ts_paths, &c->ts_draw, &c->ts_work, &c->ts_user, &c->slice_trace, &c->slice_state, &c->refine_ws, &c->refine_trace, &c->refine_user,
                    &c->feas, &c->feas_stage, &c->kg, &c->kgvec, &c->kg_slopes, &c->kg_user,
-                   &c->ts_hvi, &c->ts_hvi_t, &c->ts_hvi_user, &c->post, &c->ehvi_front, &c->ehvi_user, &c->ehvi3_front, &c->ehvi3_table, &c->ehvi3_user};
+                   &c->ts_hvi, &c->ts_hvi_t, &c->ts_hvi_user, &c->ts_feas, &c->ts_feas_user, &c->post, &c->ehvi_front, &c->ehvi_user, &c->ehvi3_front, &c->ehvi3_table, &c->ehvi3_user};
   for (auto &kv : c->pjobs_cache) b7_release(kv.second.buf);
   for (DevBuf *b : all) b7_release(*b);
   if (c->tev_init)
@@ -217,6 +218,8 @@ void b7_destroy(b7_ctx *c) {
   for (hipEvent_t e : c->ev_feas)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ev_ehvi)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ev_ts_feas)
     if (e) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(c->stream);
   delete c;

@@ -36,6 +36,14 @@ into its feasibility column (feas_reset, feas_add_acc) and nominates with the we
 response among the rows that satisfy every constraint -- or, while no row does, by feasibility alone (feas_nominate).  The stolen
 row leaves every context's resident grid.  What is not built is refused by name (constraint_refusal).
 
+config.score.type = 'constrained_thompson_sampling' with config.bot.constraints is CONSTRAINED THOMPSON SAMPLING (the selection rule of
+SCBO: Eriksson & Poloczek 2021), for any config.bot.batch from 1 to 16: per model-based trial the objective's model and every
+constraint's model sample their hypers, stage their column on their own context and keep config.bot.batch sample paths (ts_paths, a
+distinct seed from the bot's generator each); the objective's context nominates (ts_feas_nominate): path j takes the row of lowest
+f_j among the rows where every c_kj <= t_k, or the row of smallest total violation where its paths see no feasible row.  No fmin, no
+feasibility column.  The stolen rows leave every context's grid; last_constrained keeps hyps, seeds, thresholds, the picks, their
+classes, keys and values, and the rerun count.  What is not built is refused by name (constrained_thompson_refusal).
+
 config.bot.objectives (ours; None = the reference's loop, untouched) is {"ref": [r1, r2] | None, "model": {...}}: TWO-OBJECTIVE
 nomination by the exact expected hypervolume improvement (Emmerich, Yang & Deutz 2016; config.score.type =
 'expected_hypervolume_improvement', a policy like the knowledge gradient).  The objective returns a row [y1, y2], both minimised;
@@ -101,11 +109,42 @@ def refine_refusal(config, model_class="bot7.models.gp_regressor", sharded=False
 
 
 CONSTRAINED_SCORES = ("expected_improvement", "log_expected_improvement", "log_probability_of_improvement")
+CONSTRAINED_THOMPSON = "constrained_thompson_sampling"   # q nominees per trial from joint sample paths (b7_ts_feas_nominate)
+
+
+def constrained_thompson_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
+    """Why this configuration cannot nominate by constrained Thompson sampling (what b7_ts_feas_nominate does not do, by name), or
+    None.  Any config.bot.batch up to BATCH_MAX passes."""
+    kind = CONSTRAINED_THOMPSON
+    cons = config["bot"].get("constraints")
+    if not cons:
+        return "%s without config.bot.constraints: the policy needs a constraint, each with a model of its own" % kind
+    if config["bot"].get("refine"):
+        return "%s with config.bot.refine: refinement of a constrained nominee is not built" % kind
+    if config["bot"].get("objectives"):
+        return "%s with config.bot.objectives: constraints combined with objectives are not built" % kind
+    if config["bot"].get("trust_region"):
+        return "%s with config.bot.trust_region: constraints inside a trust region (SCBO's outer loop) are not built" % kind
+    if sharded:
+        return "%s over sharded candidates: constrained Thompson sampling over a sharded grid is not built" % kind
+    if model_class == "bot7.models.dngo":
+        return "%s with the dngo model: joint paths with the Bayesian-linear head are not built" % kind
+    for k, con in enumerate(cons):
+        if (con.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
+            return "%s with config.bot.constraints[%d] on the %s model: a constraint is modelled by a gp_regressor" % (kind, k, con["model"]["type"])
+    if len(cons) > TS_FEAS_CMAX:
+        return "%s with %d constraints: at most %d are built" % (kind, len(cons), TS_FEAS_CMAX)
+    q = int(config["bot"].get("batch", 1))
+    if q > BATCH_MAX:
+        return "%s with config.bot.batch = %d: at most %d nominees per trial are built" % (kind, q, BATCH_MAX)
+    return None
 
 
 def constraint_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
     """Why this configuration cannot nominate under config.bot.constraints (what b7_eval_nominate_feasible does not do, by name), or
-    None."""
+    None.  config.score.type = 'constrained_thompson_sampling' is judged by constrained_thompson_refusal."""
+    if config["score"]["type"] == CONSTRAINED_THOMPSON:
+        return constrained_thompson_refusal(config, model_class, sharded)
     if int(config["bot"].get("batch", 1)) > 1:
         return "config.bot.constraints with config.bot.batch > 1: feasibility-weighted believer batches are not built"
     if config["bot"].get("refine"):
@@ -116,7 +155,8 @@ def constraint_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
         return "config.bot.constraints with the dngo model: the Bayesian-linear head has no feasibility weight"
     kind = config["score"]["type"]
     if kind == "thompson_sampling":
-        return "config.bot.constraints with thompson_sampling: a sample path has no feasibility weight"
+        return "config.bot.constraints with thompson_sampling: a sample path has no feasibility weight (%s nominates from joint paths)" \
+            % CONSTRAINED_THOMPSON
     if kind == "confidence_bound":
         return "config.bot.constraints with confidence_bound: a signed score has no product form with a feasibility weight"
     if kind == "max_value_entropy_search":
@@ -157,6 +197,7 @@ LOG_EHVI = "log_expected_hypervolume_improvement"   # the same trials by the log
 EHVI_KINDS = (EHVI, LOG_EHVI)
 THOMPSON = "thompson_sampling"   # with config.bot.objectives: q nominees per trial from every objective's sample paths (b7_ts_hvi_nominate)
 BATCH_MAX = 16  # B7_BATCH_MAX
+TS_FEAS_CMAX = 8  # B7_TS_FEAS_CMAX
 
 
 def objectives_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
@@ -595,6 +636,8 @@ class bayesopt(abstract):
         why = self._constraint_refusal()
         if why:
             raise NotImplementedError(why)
+        if self._constrained_ts():
+            return self.nominate_constrained_ts(None, cand)       # (a list of config.bot.batch indices)
         if self.nTrials <= self.config["bot"]["nInitial"]:        # :90-91 floor(rand*M)+1
             return int(np.floor(self._rng.random() * cand.shape[0])) + 1
         cons = self._constraints_setup()
@@ -627,6 +670,85 @@ class bayesopt(abstract):
         self.last_constrained = {"hyps": hyps, "constraint_hyps": con_hyps, "fmin": fmin, "value": val, "index": int(idx)}
         return int(idx)
 
+    # ---- constrained Thompson sampling (config.score.type = 'constrained_thompson_sampling' with config.bot.constraints) ------------
+    def _constrained_ts(self):
+        return self.config["score"]["type"] == CONSTRAINED_THOMPSON
+
+    def nominate_constrained_ts(self, q=None, candidates=None):
+        """q feasible-first nominees by constrained Thompson sampling (SCBO's selection rule) -> q 1-based indices into the candidates
+        as they stand.  Per model-based trial the objective's model and every constraint's model sample their hypers and stage their
+        column on their own context, every context keeps q sample paths (ts_paths) drawn with a seed of its own from the bot's
+        generator, and the objective's context nominates (ts_feas_nominate): path j picks the row of lowest f_j among the rows its
+        constraint paths call feasible, or the row of smallest total violation where they call none.  No fmin, no feasibility column.
+        self.last_constrained keeps what the call used."""
+        cand = self.candidates if candidates is None else candidates
+        why = self._constraint_refusal()
+        if why:
+            raise NotImplementedError(why)
+        q = int(self.config["bot"]["batch"] if q is None else q)
+        if self.nTrials <= self.config["bot"]["nInitial"]:        # :90-91, q distinct rows
+            if q == 1:
+                return [int(np.floor(self._rng.random() * cand.shape[0])) + 1]
+            return [int(i) + 1 for i in self._rng.choice(cand.shape[0], size=q, replace=False)]
+        cons = self._constraints_setup()
+        thresholds = [c["threshold"] for c in cons]
+        X_obs, model = self.observed, self.model
+        Y_obs, C_obs = split_columns(self.responses, len(cons))
+        host = np.asarray(cand, dtype=np.float64)
+        hyps = [self._sample_hyps(model, X_obs, Y_obs)]
+        model.stage(X_obs, Y_obs, cand)
+        for con, Ck in zip(cons, C_obs):
+            hyps.append(self._sample_hyps(con["model"], X_obs, Ck))
+            if con["grid"] is None or con["grid"].version != con["ctx"].grid_version or not np.array_equal(np.asarray(con["grid"]), host):
+                con["ctx"].grid_upload(host)
+                con["grid"] = DeviceGrid(host, con["ctx"], con["ctx"].grid_version)
+            con["model"].stage(X_obs, Ck, con["grid"])
+        seeds = []
+        while len(seeds) < 1 + len(cons):                         # a seed per model and trial, distinct
+            seed = int(self._rng.integers(0, 2 ** 63))
+            if seed not in seeds:
+                seeds.append(seed)
+        out = self.score.nominate_constrained([model.ctx] + [con["ctx"] for con in cons], hyps, q, seeds, thresholds)
+        idx = [int(i) for i in out["index"]]
+        if min(idx) < 1:
+            raise RuntimeError("constrained_thompson_sampling: path %d has a NaN in every row: nothing to nominate" % idx.index(min(idx)))
+        self.last_scores = None
+        self.last_constrained = {"hyps": hyps[0], "constraint_hyps": hyps[1:], "seeds": seeds, "thresholds": list(thresholds), "index": idx,
+                                 "cls": np.array(out["cls"]), "key": np.array(out["key"]), "y": np.array(out["y"]), "reruns": int(out["reruns"])}
+        return idx
+
+    def _run_trial_constrained_ts(self):
+        """run_trial's batch handling with the constrained Thompson nominees: the q stolen rows leave every context's resident grid in
+        one stable pass (:118), the q response rows [y, c_1 .. c_C] are kept whole (:137-141), and at nInitial every model is
+        initialised on its own column (:147-149).  Returns the batch's best feasible row, or its best row where none is feasible."""
+        self.nTrials += 1
+        idx = self.nominate_constrained_ts()                       # :117
+        cand = self.candidates
+        rows = np.array(np.asarray(cand)[np.asarray(idx) - 1], dtype=np.float64)
+        host = T.remove(np.asarray(cand), idx)                     # :118, an index list (utils/tensor.lua:158-193)
+        if isinstance(cand, DeviceGrid) and cand.ctx is not None and cand.version == cand.ctx.grid_version:
+            assert np.array_equal(cand.ctx.grid_remove_rows(idx), rows)   # the same stable deletion on the resident copy
+            self.candidates = None if host is None else DeviceGrid(host, cand.ctx, cand.ctx.grid_version)
+        else:
+            self.candidates = host
+        for con in self.constraints or []:
+            if con["grid"] is not None and con["grid"].version == con["ctx"].grid_version:
+                con["ctx"].grid_remove_rows(idx)
+                con["grid"] = None if host is None else DeviceGrid(host, con["ctx"], con["ctx"].grid_version)
+        C = len(self.config["bot"]["constraints"])
+        ys = np.concatenate([np.asarray(self.objective(r), dtype=np.float64).reshape(1, -1) for r in rows], 0)   # :124
+        split_columns(ys, C)                                       # (the shape check)
+        self.responses = ys if self.responses is None else np.concatenate([self.responses, ys], 0)
+        self.observed = rows if self.observed is None else np.concatenate([self.observed, rows], 0)            # :143-144
+        if self.model is not None and self.nTrials == self.config["bot"]["nInitial"]:
+            Y_obs, C_obs = split_columns(self.responses, C)
+            self.model.init(self.observed, Y_obs)                  # :147-149
+            for con, Ck in zip(self._constraints_setup(), C_obs):
+                con["model"].init(self.observed, Ck)
+        ok = feasible_rows(ys, [c["threshold"] for c in self.config["bot"]["constraints"]])
+        best = int(np.where(ok, ys[:, 0], np.inf).argmin()) if ok.any() else int(ys[:, 0].argmin())
+        return rows[best], ys[best:best + 1]
+
     def _run_trial_constrained(self):
         """bots/abstract.lua:112-152 with the constrained nominee: the stolen row (:118) leaves every constraint context's resident
         grid too, the objective's row [y, c_1 .. c_C] is kept whole (:137-141), and at nInitial every model is initialised on its
@@ -634,6 +756,8 @@ class bayesopt(abstract):
         why = self._constraint_refusal()
         if why:
             raise NotImplementedError(why)
+        if self._constrained_ts():
+            return self._run_trial_constrained_ts()
         self.nTrials += 1
         idx = self.nominate_constrained()                          # :117
         self._steal_candidate(idx)                                 # :118
@@ -1061,6 +1185,8 @@ class bayesopt(abstract):
             why = kg_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
             if why:
                 raise NotImplementedError(why)
+        if self._constrained_ts():
+            return self._run_trial_constrained()                  # (every refusal of the policy, a missing constraint's included)
         if self._trust_region():
             return self._run_trial_trust_region()
         if self._objectives() or self.config["score"]["type"] in EHVI_KINDS:

@@ -953,6 +953,53 @@ int b7_ts_hvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const doubl
 int b7_hvi_compute(b7_ctx *ctx, const double *Y /*M1 x m*/, int64_t M1, int m, const double *front /*P x m*/, int P,
                    const double *ref /*m*/, double *out /*M1*/);
 
+/* CONSTRAINED THOMPSON SAMPLING: q feasible-first nominees per call under C black-box constraints c_k(x) <= t_k -- the selection rule
+ * of SCBO (Eriksson & Poloczek, AISTATS 2021).  No counterpart in the reference.  Under a joint sample path (f_j, c_1j .. c_Cj) of the
+ * objective and every constraint the world is deterministic: path j takes the row of lowest f_j among the rows where every
+ * c_kj <= t_k, and where the path sees no such row the row of smallest total violation.  No feasibility weight, no incumbent, no
+ * special case while nothing feasible has been observed; the objective is minimised.
+ *
+ * ctx holds the objective's kept paths (b7_ts_paths, or a b7_ts_nominate), cons[k] those of constraint k + 1, each drawn with its
+ * own seed and hyper samples over the same grid rows with the same q; contexts may coincide.  The key of (row i, path j), thresholds
+ * finite, one rounded operation per operator:
+ *   viol = ((0 + max(c_1j[i] - t_1, 0)) + max(c_2j[i] - t_2, 0)) + ..       k ascending, a running sum from 0
+ *   class -1: any of the 1 + C values is NaN, the row never wins;  class 0 (feasible): viol == 0, key f_j[i];  class 1: key viol.
+ * Class 0 comes before class 1, within a class the smaller key wins, equal keys go to the lowest row.  viol == 0 says "every
+ * c_k <= t_k" exactly (a difference of two distinct doubles is never 0), and +-inf need no special case: the terms are non-negative.
+ * A key depends on its own row and the thresholds alone.  C = 0 is b7_ts_nominate's rule.
+ * The rule, for path j = 0 .. q - 1 in order: the pick r_j is the best row of path j over the rows no earlier path took;
+ * key_out[j] is its key, class_out[j] its class, best_idx1[j] the row (1-based), y_out row j (nullable) its path-j values
+ * f_j, c_1j .. c_Cj.  A path with no scoring row reports index 0, class -1, a NaN key and NaN values, and excludes nothing.
+ * Two arms compute the same bits.  The library's default picks path by path: q passes chained on the device, pass j over the rows
+ * no earlier pass took, one wait; *reruns_out (nullable) is then 0.  The other arm (the diagnostic build's B7_TS_FEAS_ONEPASS = 1)
+ * scores all q paths in one pass that reads each of the 1 + C path buffers once and resolves the exclusions after one wait: where the
+ * best row of path j over ALL rows is not taken it is the pick, otherwise path j alone is run again over the rows not taken, and
+ * *reruns_out counts those second runs.  It is the faster arm only where the paths' minimisers are distinct, which paths of one
+ * posterior seldom are.  The result is the plain sequential rule's in every case.
+ * Deterministic: the same paths give the same picks, bit for bit.  The draws of path j depend on (seed, j) alone, but a hyper
+ * sample's paths are the columns of one multi-column fit, so a path's last bits depend on how many paths share its sample: the
+ * picks of a q = 3 call are the first three of a q = 5 call unless two rows tie within those last bits.  No grid is modified; the
+ * score accumulator, the feasibility column and the kept posterior are untouched.  The streams of the contexts are
+ * ordered by events both ways, as b7_ts_hvi_nominate orders them.
+ * B7_ERR_INVALID: a NULL argument (cons may be NULL iff C == 0); C outside 0..B7_TS_FEAS_CMAX; a threshold that is not finite; q or M
+ * differ between the contexts.  B7_ERR_STATE, the case named: a context has no kept paths, or its paths are stale (its grid, data or
+ * covariance kernel changed since); a context is a member of a group.  B7_ERR_UNSUPPORTED: kept paths left by b7_blr_ts_nominate (the
+ * DNGO head is not built here); contexts on different devices; a communicator of more than one rank.
+ * Not built: sharded grids and groups, the DNGO head, correlated constraints, trust regions (SCBO's outer loop).
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+#define B7_TS_FEAS_CMAX 8
+int b7_ts_feas_nominate(b7_ctx *ctx, b7_ctx *const *cons /*C, nullable iff C == 0*/, const double *thresholds /*C*/, int C,
+                        double *key_out /*q*/, int *class_out /*q*/, int64_t *best_idx1 /*q*/,
+                        double *y_out /*q x (1 + C): the pick's f_j, c_1j .. c_Cj; nullable*/, int *reruns_out /*nullable*/);
+/* The same kernels and resolution on host arrays (the b7_hvi_compute of this feature): f is M1 x q, cvals C x M1 x q (nullable iff
+ * C == 0), row-major; viol_out (nullable) receives viol as M1 x q, NaN for class -1.  B7_ERR_INVALID: a NULL argument, C outside
+ * 0..B7_TS_FEAS_CMAX, a threshold that is not finite, q outside 1..B7_BATCH_MAX, M1 < q.  Like b7_hvi_compute it reads nothing of
+ * the context but its device and stream, so a group member or a context with a communicator serves as well.  The kept paths are
+ * untouched. */
+int b7_ts_feas_compute(b7_ctx *ctx, const double *f /*M1 x q*/, const double *cvals /*C x M1 x q*/, const double *thresholds /*C*/,
+                       int64_t M1, int q, int C, double *viol_out /*M1 x q, nullable*/, double *key_out /*q*/, int *class_out /*q*/,
+                       int64_t *best_idx1 /*q*/);
+
 /* ---- trust-region nomination (TuRBO: Eriksson, Pearce, Gardner, Turner & Poloczek, NeurIPS 2019).  No counterpart in the
  * reference.  Three host-only pieces (no context, no GPU) that both host languages share, and the device map b7_grid_trust_region
  * (with the grids, above).

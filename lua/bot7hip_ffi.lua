@@ -126,6 +126,8 @@ int b7_ts_paths(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_t s
 int b7_ts_hvi_nominate(b7_ctx *ctx, b7_ctx *other, const double *front , int P, const double *ref , double *hvi_out , int64_t *best_idx1 , double *y_out );
 int b7_ts_hvi3_nominate(b7_ctx *ctx, b7_ctx *other2, b7_ctx *other3, const double *front , int P, const double *ref , double *hvi_out , int64_t *best_idx1 , double *y_out );
 int b7_hvi_compute(b7_ctx *ctx, const double *Y , int64_t M1, int m, const double *front , int P, const double *ref , double *out );
+int b7_ts_feas_nominate(b7_ctx *ctx, b7_ctx *const *cons , const double *thresholds , int C, double *key_out , int *class_out , int64_t *best_idx1 , double *y_out , int *reruns_out );
+int b7_ts_feas_compute(b7_ctx *ctx, const double *f , const double *cvals , const double *thresholds , int64_t M1, int q, int C, double *viol_out , double *key_out , int *class_out , int64_t *best_idx1 );
 int b7_tr_box(int d, int S, const b7_hyp *hyps, const double *center , double length, const double *mins , const double *maxes , double *lo , double *hi );
 typedef struct { double length, length_init, length_min, length_max, best; int succ, fail, succ_tol, fail_tol; int restarts; } b7_tr_state;
 int b7_tr_init(b7_tr_state *st, int d, int q, double length_init, double length_min, double length_max, int succ_tol, int fail_tol);
@@ -210,6 +212,7 @@ M.EHVI_PMAX = 256
 M.EHVI_SMAX = 32
 M.EHVI_SREG = 10
 M.EHVI3_PMAX = 256
+M.TS_FEAS_CMAX = 8
 M.MAX_TIMERS = 16
 -- END generated constants
 

@@ -193,6 +193,9 @@ function bot:nominate_batch(q, candidates)
   if self.config.bot.objectives and torch.type(self.score) == 'bot7.scores.thompson_sampling_hip' then
     return self:nominate_objectives_ts(q, candidates)                        -- multi-objective Thompson sampling: below
   end
+  if torch.type(self.score) == 'bot7.scores.constrained_thompson_sampling_hip' then
+    return self:nominate_constrained_ts(q, candidates)                       -- constrained Thompson sampling: below
+  end
   if q == 1 then return self:nominate(candidates) end
   assert(D.world == 1 and not hip.group, 'nominate_batch: one rank, no group (sharded batches are not built)')
   if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91, q distinct rows
@@ -323,6 +326,9 @@ end
 -- harness/bots/bayesopt.py's nominate_constrained.
 function bot:nominate_constrained(candidates)
   local candidates = candidates or self.candidates
+  if torch.type(self.score) == 'bot7.scores.constrained_thompson_sampling_hip' then
+    return self:nominate_constrained_ts(nil, candidates)                     -- constrained Thompson sampling: below
+  end
   assert(D.world == 1 and not hip.group, 'nominate_constrained: one rank, no group (sharded constrained nomination is not built)')
   local cons = assert(self.config.bot.constraints, 'nominate_constrained: config.bot.constraints is not set')
   if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91
@@ -665,6 +671,110 @@ function bot:nominate_objectives_ts(q, candidates)
   for k = 0, q - 1 do out[k + 1] = tonumber(i[k]) end
   self.best_score = v[0]
   self.objectives_rows = out   -- what the driver steals next: follow_steal_rows
+  return out
+end
+
+-- CONSTRAINED THOMPSON SAMPLING (b7_ts_paths + b7_ts_feas_nominate; no counterpart in the reference; the selection rule of SCBO:
+-- Eriksson & Poloczek, AISTATS 2021): config.score.type = 'constrained_thompson_sampling' with config.bot.constraints, any
+-- config.bot.batch from 1 to 16.  Per model-based trial the objective's model and every constraint's model sample their hypers and
+-- stage their column on their own context, every context keeps q sample paths (a distinct seed from torch's generator each), and the
+-- objective's context nominates: path j takes the row of lowest f_j among the rows where every c_kj <= t_k, or the row of smallest
+-- total violation where its paths see no feasible row.  No fmin, no feasibility column.  Returns a LongTensor of q indices into
+-- `candidates` as it stands; the driver steals them and the next call deletes them from the constraint contexts' grids before anything
+-- is staged there (follow_steal_rows).  At parity with harness/bots/bayesopt.py's nominate_constrained_ts.  Checked by the static
+-- checker only (no LuaJIT / Torch7 in the pipeline).
+local function constrained_ts_refusal(self, q)
+  local kind, b = 'constrained_thompson_sampling', self.config.bot
+  if not b.constraints or #b.constraints == 0 then
+    return kind .. ' without config.bot.constraints: the policy needs a constraint, each with a model of its own'
+  end
+  if b.refine then return kind .. ' with config.bot.refine: refinement of a constrained nominee is not built' end
+  if b.objectives then return kind .. ' with config.bot.objectives: constraints combined with objectives are not built' end
+  if b.trust_region then return kind .. ' with config.bot.trust_region: constraints inside a trust region (the outer loop of SCBO) are not built' end
+  if D.world ~= 1 or hip.group then return kind .. ' over sharded candidates: constrained Thompson sampling over a sharded grid is not built' end
+  if torch.type(self.model) == 'bot7.models.dngo_hip' then
+    return kind .. ' with the dngo model: joint paths with the Bayesian-linear head are not built'
+  end
+  if torch.type(self.model) ~= 'bot7.models.gp_hip' then return kind .. ' needs the gp_hip model' end
+  for k, cfg in ipairs(b.constraints) do
+    local mtype = cfg.model and cfg.model.type or 'gp_regressor'
+    if mtype ~= 'gp_regressor' and mtype ~= 'gp_hip' then
+      return kind .. ' with config.bot.constraints[' .. k .. '] on the ' .. mtype .. ' model: a constraint is modelled by a gp_regressor'
+    end
+  end
+  if #b.constraints > hip.TS_FEAS_CMAX then return kind .. ' with more than 8 constraints: at most 8 are built' end
+  if q > hip.BATCH_MAX then return kind .. ' with config.bot.batch above 16: at most 16 nominees per trial are built' end
+  return nil
+end
+
+function bot:nominate_constrained_ts(q, candidates)
+  local candidates = candidates or self.candidates
+  q = q or self.config.bot.batch or 1
+  local why = constrained_ts_refusal(self, q)
+  if why then error(why, 2) end
+  local cons = self.config.bot.constraints
+  if self.nTrials <= self.config.bot.nInitial then                          -- bots/bayesopt.lua:90-91, q distinct rows
+    if q == 1 then return torch.rand(1):mul(candidates:size(1)):long():add(1) end
+    return torch.randperm(candidates:size(1)):narrow(1, 1, q):long()
+  end
+  local model, keep = self.model, {}
+  local R, S, C = self.responses, self.config.bot.nSamples, #cons
+  assert(R:dim() == 2 and R:size(2) == 1 + C, 'nominate_constrained_ts: the objective must return rows {y, c_1 .. c_C}')
+  local X_obs, Y1 = self.observed, R:narrow(2, 1, 1):contiguous()
+  if self.constraints == nil then
+    self.constraints = {}
+    for k, cfg in ipairs(cons) do
+      local ctxp = ffi.new('b7_ctx*[1]')
+      assert(hip.C.b7_create(ctxp, hip.device) == 0, 'nominate_constrained_ts: b7_create failed')   -- the objective's device
+      self.constraints[k] = {threshold = cfg.threshold, model = bot7.models.gp_hip(cfg.model), ctx = ffi.gc(ctxp[0], hip.C.b7_destroy),
+                             kernel = hip.KERNEL_ARDSE}
+    end
+  end
+  local F = (self.score.config or {}).nFeatures or 1024
+  local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+  -- every model samples its hypers and stages its column, the objective first ...
+  local hyps = {}
+  hyps[1] = sample_hyps(model, X_obs, Y1, S, keep)
+  model:stage(X_obs, Y1, candidates)
+  hip.set_kernel(model.kernel_code)
+  local ctxs, thr = ffi.new('b7_ctx*[?]', C), ffi.new('double[?]', C)
+  for k, con in ipairs(self.constraints) do
+    local Ck = R:narrow(2, k + 1, 1):contiguous()
+    follow_steal_rows(con, self.constrained_rows, candidates)
+    on_context(con, function()
+      if not con.inited then con.model:init(X_obs, Ck); con.inited = true end
+      hyps[k + 1] = sample_hyps(con.model, X_obs, Ck, S, keep)
+      con.model:stage(X_obs, Ck, candidates)
+      hip.set_kernel(con.model.kernel_code)
+    end)
+    ctxs[k - 1], thr[k - 1] = con.ctx, con.threshold
+  end
+  -- ... then the paths, a distinct seed each, and the objective's context nominates
+  local seeds, seen = {}, {}
+  while #seeds < 1 + C do
+    local sd = torch.random()
+    if not seen[sd] then seen[sd] = true; seeds[#seeds + 1] = ffi.new('uint64_t', sd) end
+  end
+  hip.check(hip.C.b7_ts_paths(hip.ctx, S, hyps[1], q, F, seeds[1], jit, info))
+  for k, con in ipairs(self.constraints) do
+    hip.check(hip.C.b7_ts_paths(con.ctx, S, hyps[k + 1], q, F, seeds[k + 1], nil, nil))
+  end
+  local key, cls, i = ffi.new('double[?]', q), ffi.new('int[?]', q), ffi.new('int64_t[?]', q)
+  local y, reruns = ffi.new('double[?]', q * (1 + C)), ffi.new('int[1]')
+  hip.check(hip.C.b7_ts_feas_nominate(hip.ctx, ctxs, thr, C, key, cls, i, y, reruns))
+  for s = 0, S - 1 do
+    if jit[s] > 0 then   -- the reference's warning text, utils/math.lua:210-212
+      print(string.format('Warning: utils.math.chol succeeded in factorizing the\ninput matrix after applying a jitter of %.2e', jit[s]))
+    end
+  end
+  local out = torch.LongTensor(q)
+  for k = 0, q - 1 do
+    assert(tonumber(i[k]) >= 1, 'nominate_constrained_ts: a path has a NaN in every row: nothing to nominate')
+    out[k + 1] = tonumber(i[k])
+  end
+  self.best_score = key[0]
+  self.constrained_reruns = reruns[0]
+  self.constrained_rows = out   -- what the driver steals next: follow_steal_rows
   return out
 end
 

@@ -159,6 +159,23 @@ do
 end
 
 do
+  -- Constrained Thompson sampling (b7_ts_paths + b7_ts_feas_nominate; no original; the selection rule of SCBO, Eriksson & Poloczek
+  -- 2021): not a per-point score.  The class only carries config.nFeatures to bots_bayesopt_hip.lua, whose nominate_constrained_ts
+  -- keeps the paths of the objective and of every constraint and nominates feasible-first.  Checked by the static checker only.
+  local CTS, parent = torch.class('bot7.scores.constrained_thompson_sampling_hip', 'bot7.scores.abstract')
+  function CTS:__init(config)
+    parent.__init(self)
+    local config = config or {}
+    config['nFeatures'] = config.nFeatures or 1024
+    self.config = config
+  end
+  function CTS:__call__(model, hyp, X_obs, Y_obs, X_hid, X_pend, config)
+    error('constrained_thompson_sampling_hip is not a per-point score: nominate through bot7.bots.bayesopt_hip (b7_ts_feas_nominate)')
+  end
+  S.constrained_thompson_sampling = CTS
+end
+
+do
   -- The knowledge gradient (b7_kg_nominate; no original): not a per-point score either -- it needs the posterior covariance against
   -- its discretisation set.  The class carries config.points / discretisation / nFeatures to bots_bayesopt_hip.lua, whose
   -- nominate calls the library in place of eval + arg-max.  Checked by the static checker only.
