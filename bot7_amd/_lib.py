@@ -26,6 +26,7 @@ SYMBOLS = [
     "b7_blr_basis", "b7_blr_features", "b7_blr_fit", "b7_blr_fit_x", "b7_blr_predict", "b7_score_reset", "b7_score_ei", "b7_score_logei", "b7_score_mes", "b7_mes_set_levels", "b7_mes_last_ystar", "b7_mes_ystar", "b7_mes_compute", "b7_score_cb", "b7_score_finish",
     "b7_comm_pick_winner", "b7_comm_unique_id", "b7_comm_init", "b7_comm_info", "b7_comm_destroy", "b7_comm_allreduce_f64", "b7_score_finish_global", "b7_eval_nominate", "b7_eval_nominate_batch", "b7_blr_eval_nominate", "b7_blr_eval_nominate_marg",
     "b7_ts_nominate", "b7_ts_last_paths", "b7_ts_last_draws", "b7_rff_compute",
+    "b7_ts_nominate_refine", "b7_ts_refine_last", "b7_ts_refine_trace_enable", "b7_ts_refine_trace", "b7_ts_path_grad_at",
     "b7_blr_ts_nominate", "b7_blr_ts_last_draws", "b7_blr_paths_compute",
     "b7_kg_nominate", "b7_kg_trace_enable", "b7_kg_last", "b7_kg_compute",
     "b7_eval_posterior", "b7_posterior_get", "b7_pareto_front2", "b7_hypervolume2", "b7_ehvi_compute", "b7_ehvi_nominate",
@@ -207,6 +208,11 @@ def load(which=None):
         "b7_eval_nominate_batch": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), i32, vp, vp, vp, vp]),
         "b7_ts_nominate": (i32, [vp, i32, C.POINTER(Hyp), i32, i32, C.c_uint64, vp, vp, vp, vp]),
         "b7_ts_last_paths": (i32, [vp, vp]),
+        "b7_ts_nominate_refine": (i32, [vp, i32, C.POINTER(Hyp), i32, i32, C.c_uint64, C.POINTER(RefineOpts), vp, vp, vp, vp, vp, vp, vp]),
+        "b7_ts_refine_last": (i32, [vp, i32, C.POINTER(i32), vp, vp, vp, vp]),
+        "b7_ts_refine_trace_enable": (i32, [vp, i32]),
+        "b7_ts_refine_trace": (i32, [vp, i32, i32, vp, C.POINTER(i32)]),
+        "b7_ts_path_grad_at": (i32, [vp, vp, i64, vp, vp]),
         "b7_ts_paths": (i32, [vp, i32, C.POINTER(Hyp), i32, i32, C.c_uint64, vp, vp]),
         "b7_ts_hvi_nominate": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
         "b7_ts_hvi3_nominate": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp]),
@@ -455,7 +461,82 @@ class ThompsonFeasible(object):
         return {"viol": viol, "key": key[:q], "cls": cls[:q], "index": idx[:q]}
 
 
-class Context(BlrThompson, ThompsonObjectives, ThompsonFeasible):
+class ThompsonRefine(object):
+    """Thompson nominees refined off the grid by descent on their own sample paths (b7_ts_nominate_refine, b7_ts_refine_last,
+    b7_ts_refine_trace, b7_ts_path_grad_at): the methods of Context that serve it."""
+
+    def ts_nominate_refine(self, hyps, q, n_features=1024, seed=0, starts=16, iters=16, eta0=1.0 / 16.0, lo=None, hi=None,
+                           want_report=False):
+        """ts_nominate, then every path's nominee refined off the grid by descent on the path itself from `starts` starts (the
+        nominee, then the path's lowest rows that are no path's nominee) for `iters` iterations inside the box [lo, hi] (None: the
+        unit cube) (b7_ts_nominate_refine).  Returns (path minima[q], 1-based grid nominees[q], x[q x d], refined path values[q],
+        1-based rows of the winners' starts[q][, report]); the grid is not modified: the rows to commit are the grid nominees."""
+        S = len(hyps)
+        d = getattr(self, "_data_d", -1)
+        arr, keep = self._pack_hyps(hyps, d)
+        lo = None if lo is None else _f64(lo).ravel()
+        hi = None if hi is None else _f64(hi).ravel()
+        for b in (lo, hi):
+            if b is not None and b.size != d:
+                raise Bot7HipError(-1, "lo / hi must have d entries")
+        dp = C.POINTER(C.c_double)
+        opts = RefineOpts(int(starts), int(iters), float(eta0), None if lo is None else lo.ctypes.data_as(dp),
+                          None if hi is None else hi.ctypes.data_as(dp))
+        jit = np.zeros(max(S, 1), dtype=np.float64) if want_report else None
+        info = np.zeros(max(S, 1), dtype=np.int32) if want_report else None
+        n = max(int(q), 1)
+        vals, idx = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int64)
+        x, rv, ri = np.zeros((n, max(d, 1)), dtype=np.float64), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int64)
+        self._ck(self._L.b7_ts_nominate_refine(self._h, S, arr, int(q), int(n_features), int(seed) & (2 ** 64 - 1), C.byref(opts),
+                                               _ptr(vals), _ptr(idx), _ptr(x), _ptr(rv), _ptr(ri), _ptr(jit), _ptr(info)))
+        self.fit_token += 1
+        self._ts_shape = (self.grid_shape()[0], n, int(n_features), self._data_d, getattr(self, "_data_n", 0))
+        self._ts_refine_iters = int(iters)
+        if want_report:
+            return vals, idx, x, rv, ri, {"jitter": jit[:S], "info": info[:S]}
+        return vals, idx, x, rv, ri
+
+    def ts_refine_last(self, path):
+        """Every start of path `path` in the last ts_nominate_refine, in rank order: dict(x P x d, val P, start_idx1 P, status P)
+        (b7_ts_refine_last)."""
+        d = getattr(self, "_ts_shape", (1, 1, 1, 1, 1))[3]
+        n = C.c_int()
+        x, val = np.zeros((REFINE_MAX_STARTS, d), dtype=np.float64), np.zeros(REFINE_MAX_STARTS, dtype=np.float64)
+        idx, status = np.zeros(REFINE_MAX_STARTS, dtype=np.int64), np.zeros(REFINE_MAX_STARTS, dtype=np.int32)
+        self._ck(self._L.b7_ts_refine_last(self._h, int(path), C.byref(n), _ptr(x), _ptr(val), _ptr(idx), _ptr(status)))
+        P = n.value
+        return {"x": x[:P].copy(), "val": val[:P].copy(), "start_idx1": idx[:P].copy(), "status": status[:P].copy()}
+
+    def ts_refine_trace_enable(self, on=True):
+        """Keep one record per path, start and iteration of the ts_nominate_refine calls that follow (b7_ts_refine_trace_enable)."""
+        self._ck(self._L.b7_ts_refine_trace_enable(self._h, int(bool(on))))
+
+    def ts_refine_trace(self, path, start):
+        """The records of start `start` of path `path` in the last traced ts_nominate_refine, iteration 0..iters, as refine_trace
+        returns them: x, val and grad are the PATH's (the ladder ran on their negatives), cand the rungs' path values
+        (b7_ts_refine_trace)."""
+        d = getattr(self, "_ts_shape", (1, 1, 1, 1, 1))[3]
+        buf = np.zeros((getattr(self, "_ts_refine_iters", 0) + 1, REFINE_TRACE_WIDTH), dtype=np.float64)
+        n = C.c_int()
+        self._ck(self._L.b7_ts_refine_trace(self._h, int(path), int(start), _ptr(buf), C.byref(n)))
+        r = buf[:n.value]
+        return {"x": r[:, :d].copy(), "val": r[:, d].copy(), "grad": r[:, d + 1:2 * d + 1].copy(), "eta": r[:, 2 * d + 1].copy(),
+                "cand": r[:, 2 * d + 2:2 * d + 6].copy(), "rung": r[:, 2 * d + 6].astype(np.int64),
+                "status": r[:, 2 * d + 7].astype(np.int64)}
+
+    def ts_path_grad_at(self, X1):
+        """The kept sample paths and their gradients at the rows of X1: (val M1 x q, grad M1 x q x d) (b7_ts_path_grad_at)."""
+        X1 = _f64(X1)
+        if X1.ndim == 1:
+            X1 = X1.reshape(1, -1)
+        M1, d = X1.shape
+        q = getattr(self, "_ts_shape", (1, 1, 1, 1, 1))[1]
+        val, grad = np.empty((M1, q), dtype=np.float64), np.empty((M1, q, d), dtype=np.float64)
+        self._ck(self._L.b7_ts_path_grad_at(self._h, _ptr(X1), M1, _ptr(val), _ptr(grad)))
+        return val, grad
+
+
+class Context(BlrThompson, ThompsonObjectives, ThompsonFeasible, ThompsonRefine):
     """One GPU's worth of state: the resident candidate grid, the current GP fit, the score accumulator."""
 
     def __init__(self, device_id=0, _borrowed=None, lib=None):

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "_build")
 OUT = os.path.join(HERE, "libbot7hip.so")
-SOURCES = ["context.hip", "grid_api.hip", "gp_api.hip", "nominate.hip", "blr_api.hip", "sobol.hip", "covar.hip", "potrf.hip", "potrf_persist.hip", "posterior.hip", "score.hip", "extras.hip", "comm.hip", "group.hip", "blr_small.hip", "gp_small.hip", "kpost_small.hip", "batch.hip", "mes.hip", "rff.hip", "slice.hip", "refine.hip", "kg.hip", "ehvi.hip", "trust_region.hip", "ehvi3.hip", "blr_ts.hip", "ts_hvi.hip", "ts_feas.hip"]
+SOURCES = ["context.hip", "grid_api.hip", "gp_api.hip", "nominate.hip", "blr_api.hip", "sobol.hip", "covar.hip", "potrf.hip", "potrf_persist.hip", "posterior.hip", "score.hip", "extras.hip", "comm.hip", "group.hip", "blr_small.hip", "gp_small.hip", "kpost_small.hip", "batch.hip", "mes.hip", "rff.hip", "slice.hip", "refine.hip", "kg.hip", "ehvi.hip", "trust_region.hip", "ehvi3.hip", "blr_ts.hip", "ts_hvi.hip", "ts_feas.hip", "ts_refine.hip"]
 # The DIAGNOSTIC build (tools/_build/libbot7hip_diag.so, -DB7_DIAG): the shipped sources + round 3's likelihood kernel kept as
 # a bit-for-bit reference.  Only translation units that mention B7_DIAG are compiled a second time; the rest are shared.
 DIAG_ONLY_SOURCES = ["nll_small.hip"]
@@ -42,6 +42,8 @@ def _stale(target, deps):
 # rff.hip: rff_kernel's first product feeds the cosine (VALU) and comes back as an MFMA operand
 EXTRA_FLAGS = {"covar.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "batch.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "rff.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+               # ts_refine.hip: ts_refine_kernel's products feed the sine / cosine and the covariance and come back as MFMA operands
+               "ts_refine.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # kg.hip: kg_kernel's K* accumulator is the next MFMA's A operand
                "kg.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # slice.hip: slice_chain_kernel runs the likelihood body in a loop; machine LICM would form the body's address arithmetic

@@ -29,6 +29,9 @@ constexpr int B7_TAB_ROW0 = 4;    // d doubles: the grid row of the local maximu
 constexpr int B7_TAB_W = B7_TAB_ROW0 + B7_MAX_D;
 constexpr int B7_MAX_WORLD = 64;
 
+// Padded input dimension of the feature kernels (rff.hip, ts_refine.hip), one instantiation per class
+__host__ __device__ constexpr int rff_dpad(int d) { return d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : 96; }
+
 // Padded input dimension: the covariance kernel is instantiated per class so its MFMA chain unrolls.
 static inline int b7_dpad_class(int d) {
   return d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : d <= 48 ? 48 : d <= 64 ? 64 : 96;
@@ -129,6 +132,15 @@ struct RefState {
   long long idx[B7_REFINE_MAX_STARTS];  // the grid row it started from (0-based)
   int status[B7_REFINE_MAX_STARTS];     // B7_REFINE_* bits
   int active[B7_REFINE_MAX_STARTS];     // the queries in flight are this start's ladder (else: the start itself, four times)
+};
+
+// b7_ts_nominate_refine (ts_refine.hip): every start of every path of the last call, on the host
+struct TsRefLast {
+  bool valid = false, traced = false;
+  int q = 0, P = 0, d = 0, iters = 0;
+  std::vector<double> x, v;     // [q][16][d], [q][16]
+  std::vector<long long> idx;   // [q][16] the grid rows the starts began at (0-based)
+  std::vector<int> status;      // [q][16] B7_REFINE_* bits
 };
 
 struct b7_ctx {
@@ -266,6 +278,12 @@ struct b7_ctx {
   // ... or a b7_ts_paths, which stops short of the arg-mins.  ts_epoch: the context's epoch (below) when the paths were made; the
   // multi-objective nominations (ts_hvi.hip) answer B7_ERR_STATE to paths of an earlier grid or data, b7_ts_last_paths still serves them
   uint64_t ts_epoch = 0;
+  std::vector<double> ts_hyp;  // the min(S, q) hyper samples a GP's paths were drawn under: lenscale_sq d | amp | noise | mean each
+  // ---- b7_ts_nominate_refine / b7_ts_path_grad_at (ts_refine.hip): the packed operands and the starts' state, the last call's
+  // trace, b7_ts_path_grad_at's staging, and the last call's result on the host
+  DevBuf ts_ref_ws, ts_ref_trace, ts_ref_user;
+  bool ts_ref_trace_on = false;
+  TsRefLast ts_ref_last;
   // ---- b7_ts_hvi_nominate / b7_ts_hvi3_nominate / b7_hvi_compute (ts_hvi.hip): the staged front or boxes, the picks, the arg-max
   // partials (ts_hvi), the [q][M] copies of the objectives' paths (ts_hvi_t) and b7_hvi_compute's staging, apart from the kept paths
   DevBuf ts_hvi, ts_hvi_t, ts_hvi_user;
@@ -737,6 +755,16 @@ int launch_believer(b7_ctx *c, int S, const BelPass &p, bool column);
 // rff.hip: path j = 0 .. q - 1 in order, each its first minimum over the rows of paths (M x q) that no earlier path took, a NaN never
 // winning, into pmin[j] / taken[j] (0-based) on the device; part: 16 nblk bytes of workspace, nblk <= 1024 blocks per pass
 int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, void *part, int nblk);
+// what the last successful GP b7_ts_nominate / b7_ts_paths left on the device for the paths' refinement (ts_refine.hip): the draws
+// (omega [ns][F][d], phase [F], weight [q][F]), sample s's alpha columns at alpha + s alpha_stride ([Npad][yld], yld = 1 or the
+// sample's columns rounded up to 64; column p is v_j of path j = s + S p).  B7_ERR_STATE if
+// the buffers are not the ones that call left
+struct TsKept {
+  const double *omega, *phase, *weight, *alpha;
+  int64_t alpha_stride;
+  int ns;
+};
+int ts_kept(const b7_ctx *c, TsKept *k);
 // ... and path j's alone, over the rows not in taken[0 .. j) (ts_hvi.hip's fallback pick)
 int launch_ts_argmin(b7_ctx *c, const double *paths, int64_t M, int q, int j, double *pmin, long long *taken, void *part, int nblk);
 // blr_api.hip: what b7_blr_ts_nominate (blr_ts.hip) shares with the DNGO entry points

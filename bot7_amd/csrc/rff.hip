@@ -43,8 +43,6 @@ namespace {
 constexpr int RT = 2;            // 16-candidate tiles per wave: an Omega / W fragment is loaded once for both
 constexpr int RROWS = 4 * 16 * RT;  // candidate rows per block of four waves
 
-__host__ __device__ constexpr int rff_dpad(int d) { return d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : 96; }
-
 // cos(x) for |x| < 2^30: n = rint(x 2/pi), r = x - n pi/2 by a two-term Cody-Waite reduction whose products the fma keeps exact
 // (|r| <= pi/4 to 2^-54 absolute while n pi/2's low word matters, i.e. far beyond the |x| of a few thousand that unit-cube
 // inputs over lengthscales >= 1e-3 give), then fdlibm's kernel polynomials on [-pi/4, pi/4] (both evaluated, one selected: 13
@@ -328,16 +326,11 @@ int ts_mean_over_grid(b7_ctx *c) {
 
 // c->ts_work: one hyper sample's operands, each piece on a 256-byte boundary (the multi-column mean reads alpha in 16-byte pairs):
 // omf F dpad | wf 16 F | phiw N qmax | ycols np qmax | alpha np yldmax | resid np qmax | inv_ls d | pmin q | taken q | part 2 nblk
-// The diagnostic build keeps every hyper sample's alpha (ns of them, sample s at alpha + s np yldmax) for b7dbg_ts_alpha; the
-// shipped build has the one, which the next sample overwrites.
+// Every hyper sample's alpha is kept (ns of them, sample s at alpha + s np yldmax): column p of sample s is v_j of path j = s + S p,
+// which the refinement of the paths (ts_refine.hip, through ts_kept) and b7dbg_ts_alpha read.
 constexpr int TS_ALPHA_PIECE = 4;
 void ts_work_layout(int F, int dpad, int N, int np, int qmax, int yldmax, int d, int q, int nblk, int ns, size_t off[11]) {
-#ifdef B7_DIAG
   const size_t nalpha = (size_t)ns;
-#else
-  const size_t nalpha = 1;
-  (void)ns;
-#endif
   const size_t pieces[10] = {(size_t)F * dpad, 16 * (size_t)F, (size_t)N * qmax, (size_t)np * qmax, nalpha * np * yldmax, (size_t)np * qmax,
                              (size_t)d,        (size_t)q,      (size_t)q,        2 * (size_t)nblk};
   off[0] = 0;
@@ -370,6 +363,21 @@ int launch_ts_argmin(b7_ctx *c, const double *paths, int64_t M, int q, int j, do
 int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, void *part, int nblk) {
   PhaseScope ps(c, "ts_argmin");
   for (int j = 0; j < q; ++j) B7_TRY(launch_ts_argmin(c, paths, M, q, j, pmin, taken, part, nblk));
+  return B7_OK;
+}
+
+// What the last GP paths left for their refinement: the draws and every path's v_j (b7_internal.h: TsKept)
+int ts_kept(const b7_ctx *c, TsKept *k) {
+  const int q = c->ts_q, S = c->ts_S, F = c->ts_F, N = c->ts_N, d = c->ts_d, np = c->Npad, ns = S < q ? S : q;
+  const int qmax = (q + ns - 1) / ns, yldmax = qmax == 1 ? 1 : (int)round_up(qmax, 64);
+  const int nblk = (int)std::min<int64_t>(1024, (c->ts_M + 255) / 256);
+  size_t off[11];
+  ts_work_layout(F, rff_dpad(d), N, np, qmax, yldmax, d, q, nblk, ns, off);
+  if (!c->ts_work.p || c->ts_work.cap < sizeof(double) * off[10] || c->ts_hyp.size() != (size_t)ns * (d + 3)) return B7_ERR_STATE;
+  const TsDraws dr = ts_draws(c, ns, q, F, d, N);
+  k->omega = dr.omega, k->phase = dr.phase, k->weight = dr.weight;
+  k->alpha = (const double *)c->ts_work.p + off[TS_ALPHA_PIECE], k->alpha_stride = (int64_t)np * yldmax;
+  k->ns = ns;
   return B7_OK;
 }
 
@@ -408,6 +416,12 @@ int ts_paths_core(b7_ctx *c, const char *who, bool null_out, const char *what, i
   if (jitter_out) std::fill(jitter_out, jitter_out + S, 0.0);
   if (info_out) std::fill(info_out, info_out + S, 0);
   c->ts_valid = false, c->ts_blr = false;
+  c->ts_hyp.resize((size_t)ns * (d + 3));  // the hyper samples the paths are drawn under, for the paths' refinement
+  for (int s = 0; s < ns; ++s) {
+    double *hs = &c->ts_hyp[(size_t)s * (d + 3)];
+    std::copy(hyps[s].lenscale_sq, hyps[s].lenscale_sq + d, hs);
+    hs[d] = hyps[s].amp, hs[d + 1] = hyps[s].noise, hs[d + 2] = hyps[s].mean;
+  }
 
   // device memory beyond the posterior's own: the paths (M x q), the draws, and the operands of one hyper sample
   const int qmax = (q + ns - 1) / ns, yldmax = qmax == 1 ? 1 : (int)round_up(qmax, 64);
@@ -455,11 +469,7 @@ int ts_paths_core(b7_ctx *c, const char *who, bool null_out, const char *what, i
       hipLaunchKernelGGL(ts_pseudo_kernel, dim3((unsigned)((N * qs + 255) / 256)), dim3(256), 0, c->stream, (const double *)swap.ybuf.p,
                          (const double *)phiw, dr.eps, N, qs, s, S, sqrt(h.noise), ycols);
       B7_HIP(c, hipGetLastError());
-#ifdef B7_DIAG
       double *alpha_s = alpha + (size_t)s * np * yldmax;
-#else
-      double *alpha_s = alpha;
-#endif
       c->ybuf.p = ycols, c->alpha.p = alpha_s, c->resid.p = resid;  // (capacities are not consulted while swapped: nothing regrows these)
       c->ycols = qs;
       c->yld = qs == 1 ? 1 : (int)round_up(qs, 64);

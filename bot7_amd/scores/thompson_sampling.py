@@ -16,8 +16,14 @@ w_j ~ N(m, inv(A)): no random features (``nFeatures`` is unused), computed by b7
 With two or three objectives (config.bot.objectives; TSEMO, Bradford, Schweidtmann & Lapkin 2018) every objective's context keeps q
 paths of its own (Context.ts_paths) and the first context nominates: path j picks the row whose sampled values improve the
 hypervolume of the front plus the earlier picks under path j the most (Context.ts_hvi_nominate; b7_ts_hvi_nominate /
-b7_ts_hvi3_nominate)."""
+b7_ts_hvi3_nominate).
+
+``refine`` (default off; a dict of starts / iters / eta0) refines every nominee off the grid by descent on its own sample path
+(Context.ts_nominate_refine; b7_ts_nominate_refine): a path is an explicit differentiable function of x, and optimising it by
+gradient is how Wilson et al. use it.  The bot evaluates and observes the refined points and steals the grid nominees' rows."""
 from .abstract import abstract
+
+REFINE_DEFAULTS = {"starts": 16, "iters": 16, "eta0": 1.0 / 16.0}
 
 
 class thompson_sampling(abstract):
@@ -27,6 +33,8 @@ class thompson_sampling(abstract):
         super().__init__()
         config = dict(config or {})
         config.setdefault("nFeatures", 1024)
+        if config.get("refine"):
+            config["refine"] = dict(REFINE_DEFAULTS, **(config["refine"] if isinstance(config["refine"], dict) else {}))
         self.config = config
 
     def add_to(self, ctx, Y_obs=None, config=None):
@@ -41,6 +49,15 @@ class thompson_sampling(abstract):
             return model.ts_nominate(observed, responses, candidates, hyps, q, seed)[1]
         config = config or self.config
         return ctx.ts_nominate(hyps, q, n_features=int(config.get("nFeatures") or 1024), seed=seed)[1]
+
+    def nominate_refine(self, ctx, hyps, q, seed, lo, hi, config=None):
+        """q nominees refined on their own paths inside the box [lo, hi] -> (1-based grid nominees[q], refined points q x d)
+        (Context.ts_nominate_refine).  A GP model over ctx's resident data and grid."""
+        config = config or self.config
+        ref = dict(REFINE_DEFAULTS, **(config["refine"] if isinstance(config.get("refine"), dict) else {}))
+        _, idx, x, _, _ = ctx.ts_nominate_refine(hyps, q, n_features=int(config.get("nFeatures") or 1024), seed=seed, starts=int(ref["starts"]),
+                                                 iters=int(ref["iters"]), eta0=float(ref["eta0"]), lo=lo, hi=hi)
+        return idx, x
 
     def nominate_objectives(self, ctxs, hyps, q, seeds, front, ref, config=None):
         """q nominees for len(ctxs) = 2 or 3 objectives -> (hvi[q], 1-based indices[q], y[q x m]).  ctxs[k] holds objective k + 1's

@@ -27,6 +27,12 @@ through b7_eval_nominate_refine, which climbs the marginalised acquisition from 
 (config.grid.mins / maxes); the trial steals the grid row the winner started from, evaluates the objective at the refined point
 and observes that point.  What the library refuses is refused here by name (refine_refusal).
 
+config.score.refine (ours; absent = today's loop) under config.score.type = 'thompson_sampling' is the same dict for THOMPSON
+nominees: a model-based trial goes through b7_ts_nominate_refine, which lets every path's nominee descend on its own sample path
+(a path, unlike the acquisition, is an explicit differentiable function of x); the trial steals the q grid nominees' rows, evaluates
+the objective at the refined points and observes those.  With config.bot.trust_region the box is the trial's trust region.  What is
+not built is refused by name (ts_refine_refusal); config.bot.refine with thompson_sampling stays refused.
+
 config.bot.constraints (ours; None = the reference's loop, untouched) is a list of {"threshold": t, "model": {...}}: CONSTRAINED
 nomination after Gelbart et al. 2014 / Gardner et al. 2014.  The objective returns a row [y, c_1 .. c_C]; the objective's model sees
 column 0, constraint model k -- a GP with a context and sampler state of its own -- column k.  Per model-based trial every
@@ -108,6 +114,37 @@ def refine_refusal(config, model_class="bot7.models.gp_regressor", sharded=False
     return None
 
 
+def ts_refine_refusal(config, model_class="bot7.models.gp_regressor", sharded=False):
+    """Why this configuration cannot refine its Thompson nominees on their sample paths (config.score.refine; what
+    b7_ts_nominate_refine and _run_trial_ts_refined do not do, by name), or None."""
+    if not config["score"].get("refine"):
+        return None
+    kind = config["score"]["type"]
+    if kind == "knowledge_gradient":
+        return "config.score.refine with knowledge_gradient: the rows of the Thompson discretisation are grid rows (their refinement is not built)"
+    if kind != "thompson_sampling":
+        return "config.score.refine with %s: it refines thompson_sampling's nominees on their sample paths (config.bot.refine climbs a per-point score)" % kind
+    if config["bot"].get("refine"):
+        return refine_refusal(config, model_class, sharded)
+    if sharded:
+        return "config.score.refine over sharded candidates or a group: refinement of sample paths over a sharded grid is not built"
+    if model_class == "bot7.models.dngo":
+        return "config.score.refine with the dngo model: the gradient of the head's exact paths (the basis network's Jacobian) is not built"
+    if config["bot"].get("constraints"):
+        return "config.score.refine with config.bot.constraints: refinement of a constrained nominee is not built"
+    if config["bot"].get("objectives"):
+        return "config.score.refine with config.bot.objectives: refinement of a multi-objective nominee is not built"
+    q = int(config["bot"].get("batch", 1))
+    if q > TS_REFINE_BATCH_MAX:
+        return "config.score.refine with config.bot.batch = %d: at most %d nominees per trial are built" % (q, TS_REFINE_BATCH_MAX)
+    ref = config["score"]["refine"]
+    unknown = sorted(set(ref) - set(REFINE_DEFAULTS)) if isinstance(ref, dict) else []
+    if unknown:
+        return "config.score.refine with unknown entries %s: %s are read" % (", ".join(unknown), ", ".join(sorted(REFINE_DEFAULTS)))
+    return None
+
+
+TS_REFINE_BATCH_MAX = 16   # B7_BATCH_MAX
 CONSTRAINED_SCORES = ("expected_improvement", "log_expected_improvement", "log_probability_of_improvement")
 CONSTRAINED_THOMPSON = "constrained_thompson_sampling"   # q nominees per trial from joint sample paths (b7_ts_feas_nominate)
 
@@ -398,6 +435,8 @@ class bayesopt(abstract):
         config["model"] = self._model_defaults(config.get("model"), config["bot"]["nSamples"])
         score = dict(config.get("score") or {})
         score.setdefault("type", "expected_improvement")  # :49
+        if score.get("refine"):                         # ours: absent / False, or a dict of starts / iters / eta0 (nominate_ts_refine)
+            score["refine"] = dict(REFINE_DEFAULTS, **(score["refine"] if isinstance(score["refine"], dict) else {}))
         config["score"] = score
         config["bot"].setdefault("batch", 1)            # ours: nominees per trial (nominate_batch); 1 is the reference's loop
         config["bot"].setdefault("refine", False)       # ours: False, or a dict of starts / iters / eta0 (nominate_refine)
@@ -525,6 +564,49 @@ class bayesopt(abstract):
         idx = self.score.nominate(model.ctx, hyps, q, seed)
         self.last_scores = None
         return [int(i) for i in idx]
+
+    def _ts_refined(self):
+        """THE predicate: does this bot refine its Thompson nominees on their sample paths (config.score.refine)."""
+        return self._thompson() and bool(self.config["score"].get("refine"))
+
+    def nominate_ts_refine(self, q, cand, lo, hi):
+        """q Thompson nominees refined off the grid by descent on their own sample paths inside the box [lo, hi]
+        (b7_ts_nominate_refine; no counterpart in the reference) -> (the 1-based grid nominees, distinct, which the caller steals;
+        the refined points q x d, which it evaluates and observes).  Sampling and seed as _ts_nominate."""
+        X_obs, Y_obs, model = self.observed, self.responses, self.model
+        why = ts_refine_refusal(self.config, model.class_(), hasattr(cand, "commit"))
+        if why:
+            raise NotImplementedError(why)
+        assert hasattr(model, "stage"), "config.score.refine: a GP model on one GPU"
+        model.sample_hypers(X_obs, Y_obs)                         # :68 (burn-in call)
+        hyps = [model.parse_hypers(model.sample_hypers(X_obs, Y_obs, None, None, True))
+                for _ in range(self.config["bot"]["nSamples"])]   # :73-75
+        model.stage(X_obs, Y_obs, cand)
+        seed = int(self._rng.integers(0, 2 ** 63))
+        idx, x = self.score.nominate_refine(model.ctx, hyps, q, seed, np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64))
+        self.last_scores = None
+        return [int(i) for i in idx], np.array(x, dtype=np.float64).reshape(len(idx), -1)
+
+    def _run_trial_ts_refined(self):
+        """bots/abstract.lua:112-152 with config.bot.batch Thompson nominees refined on their sample paths: the q GRID NOMINEES' rows
+        are stolen in one stable pass (:118; distinct by construction, whichever start won), the objective is evaluated at the
+        refined points (:124) and those points are observed (:143-144).  The box is the grid's (config.grid.mins / maxes)."""
+        self.nTrials += 1
+        q, grid = int(self.config["bot"]["batch"]), self.config["grid"]
+        cand = self.candidates
+        idx, rows = self.nominate_ts_refine(q, cand, grid["mins"], grid["maxes"])       # :117
+        host = T.remove(np.asarray(cand), idx)                     # :118
+        if isinstance(cand, DeviceGrid) and cand.ctx is not None and cand.version == cand.ctx.grid_version:
+            cand.ctx.grid_remove_rows(idx)                         # the same stable deletion on the resident copy
+            self.candidates = None if host is None else DeviceGrid(host, cand.ctx, cand.ctx.grid_version)
+        else:
+            self.candidates = host
+        self.last_ts_refine = {"index": idx, "x": rows.copy()}
+        ys = np.concatenate([np.asarray(self.objective(r), dtype=np.float64).reshape(1, -1) for r in rows], 0)   # :124
+        self.responses = ys if self.responses is None else np.concatenate([self.responses, ys], 0)
+        self.observed = rows if self.observed is None else np.concatenate([self.observed, rows], 0)            # :143-144
+        best = int(ys[:, 0].argmin())
+        return rows[best], ys[best:best + 1]
 
     def _kg(self):
         return self.config["score"]["type"] == "knowledge_gradient"
@@ -1144,8 +1226,11 @@ class bayesopt(abstract):
         # the existing branches, unchanged: they see the window as the observations and the trial's hyper samples as their draws
         kept = (self.observed, self.responses, self.model)
         self.observed, self.responses, self.model = X_win, Y_win, _KeptHypers(self.model, hyps)
+        refined = None
         try:
-            if q > 1:
+            if self._ts_refined():
+                idx, refined = self.nominate_ts_refine(q, grid, lo, hi)   # the box handed to the library is the trial's trust region
+            elif q > 1:
                 idx = self.nominate_batch(q, grid)
             else:
                 idx = [int(self.eval(grid, want_scores=False)[2])]
@@ -1153,6 +1238,9 @@ class bayesopt(abstract):
             self.observed, self.responses, self.model = kept
         rec.update(made, kind="model", index=[int(i) for i in idx], center=center, lo=lo, hi=hi, shift=shift, map_seed=seed,
                    hyps=hyps)
+        if refined is not None:
+            rec.update(grid_rows=grid.rows(idx))
+            return refined, rec
         return grid.rows(idx), rec
 
     def _run_trial_trust_region(self):
@@ -1185,6 +1273,10 @@ class bayesopt(abstract):
             why = kg_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
             if why:
                 raise NotImplementedError(why)
+        if self.config["score"].get("refine"):
+            why = ts_refine_refusal(self.config, self.model.class_() if self.model is not None else "", hasattr(self.candidates, "commit"))
+            if why:
+                raise NotImplementedError(why)
         if self._constrained_ts():
             return self._run_trial_constrained()                  # (every refusal of the policy, a missing constraint's included)
         if self._trust_region():
@@ -1195,6 +1287,8 @@ class bayesopt(abstract):
             return self._run_trial_constrained()
         if self.config["bot"]["refine"]:
             return self._run_trial_refined()
+        if self._ts_refined() and self.nTrials + 1 > self.config["bot"]["nInitial"]:   # (:90-91: the initial picks are grid rows)
+            return self._run_trial_ts_refined()
         q = int(self.config["bot"]["batch"])
         if q == 1:
             return super().run_trial()

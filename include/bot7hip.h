@@ -682,6 +682,47 @@ int b7_ts_last_draws(b7_ctx *ctx, int path, double *omega /*F x d*/, double *pha
 int b7_rff_compute(b7_ctx *ctx, const double *X /*M1 x d*/, int64_t M1, int d, const double *omega /*F x d*/,
                    const double *phase /*F*/, const double *W /*F x q*/, int F, int q, double *out /*M1 x q*/);
 
+/* THOMPSON NOMINEES REFINED OFF THE GRID by descent on their own sample paths.  A pathwise sample is an explicit differentiable
+ * function of x (Wilson et al. 2020 optimise it by gradient):
+ *   f_j(x)     = m_s + sum_f W_j[f] cos(omega_s[f] . x + phase[f]) + sum_i v_j[i] k_s(x, X_i)              s = j mod S
+ *   df_j/dx_c  = -sum_f W_j[f] sin(omega_s[f] . x + phase[f]) omega_s[f][c] - w_c (x_c sum_i v_j[i] g_i - sum_i v_j[i] g_i X_ic)
+ * W = sqrt(2 amp / F) weight, w_c = 1 / lenscale_sq_c, g = k for ARD-SE and (5/3) amp (1 + s) exp(-s) for Matern-5/2.  No inv(L), no
+ * variance and no hyper-sample loop enter: one evaluation costs O((F + N) d) per point.
+ * b7_ts_nominate runs first: path_min, best_idx1, jitter_out, info_out and the kept paths and draws are its outputs, bit for bit.
+ * Then every path j is refined on its own: its starts are its grid nominee (rank 0), then the `starts` - 1 rows of lowest f_j among
+ * the rows that are none of the q grid nominees, ascending by (value, row), a NaN never chosen -- so the paths do not depend on each
+ * other.  Each start runs b7_eval_nominate_refine's ladder on -f_j: the same four rungs, point formula, decision rule (strictly
+ * better, the lowest rung on ties, a NaN never wins), eta update, 2^-40 floor and B7_REFINE_* status bits; iteration 0 evaluates the
+ * start itself, unclipped.  A start's path value never increases.  Path j's result is the start of lowest final value (the lowest
+ * rank on ties, non-finite values left out): x_out row j, val_out[j] = f_j there, start_idx1_out[j] = the 1-based grid row it
+ * started from.  If no start of the path moved, the result is its grid nominee's row bit for bit, with the refinement's own value
+ * there.  The whole refinement is one launch; every sum has one order, so a start's trajectory depends on its path's operands, its
+ * start row and the options alone: the same call twice gives the same bits, and start rank r is the same for every `starts` > r.
+ * The rows to commit (b7_grid_remove_rows) are the grid nominees best_idx1, distinct by construction.
+ * b7_refine_opts as b7_eval_nominate_refine judges them, and starts <= M - q + 1; otherwise, or with a NULL argument other than
+ * jitter_out / info_out: B7_ERR_INVALID.  B7_ERR_UNSUPPORTED: a communicator of more than one rank, more than one response column.
+ * B7_ERR_STATE: a member of a group.  Everything else as b7_ts_nominate answers it.
+ * Added without a change of B7_ABI_VERSION: the change is additive. */
+int b7_ts_nominate_refine(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, const b7_refine_opts *opts,
+                          double *path_min /*q*/, int64_t *best_idx1 /*q*/, double *x_out /*q x d*/, double *val_out /*q*/,
+                          int64_t *start_idx1_out /*q*/, double *jitter_out /*S*/, int *info_out /*S*/);
+/* Every start of path `path` in the last b7_ts_nominate_refine, in rank order: their number, final points P x d, final path values,
+ * 1-based grid rows (0: no row was left for that rank) and status bits (all nullable).  B7_ERR_STATE before a successful call. */
+int b7_ts_refine_last(b7_ctx *ctx, int path, int *P, double *x /*P x d*/, double *val /*P*/, int64_t *start_idx1 /*P*/,
+                      int *status /*P*/);
+/* Trace of the b7_ts_nominate_refine calls that follow (on != 0): one record per path, start and iteration 0..iters,
+ * B7_REFINE_TRACE_WIDTH doubles each, in b7_refine_trace's layout: x after the iteration (d) | the path's value there | the path's
+ * gradient there (d) | eta before the step | the four rungs' path values (NaN where no ladder was run) | the rung taken (-1:
+ * stayed) | status bits | zeros.  The ladder ran on the negated values and gradients.  b7_ts_refine_trace: the records of start
+ * `start` of path `path` (nullable) and their number, iters + 1.  B7_ERR_STATE without a traced call. */
+int b7_ts_refine_trace_enable(b7_ctx *ctx, int on);
+int b7_ts_refine_trace(b7_ctx *ctx, int path, int start, double *records, int *n_records);
+/* The kept paths of the last b7_ts_nominate / b7_ts_paths / b7_ts_nominate_refine and their gradients at the rows of X1, by the
+ * refinement's kernel: val M1 x q, grad M1 x q x d (both nullable).  It disturbs nothing.  B7_ERR_STATE: no kept paths, or the grid,
+ * the data or the covariance kernel changed since they were drawn; a member of a group.  B7_ERR_UNSUPPORTED: the kept paths are
+ * b7_blr_ts_nominate's (the DNGO head), a communicator of more than one rank, more than one response column. */
+int b7_ts_path_grad_at(b7_ctx *ctx, const double *X1 /*M1 x d*/, int64_t M1, double *val /*M1 x q*/, double *grad /*M1 x q x d*/);
+
 /* THOMPSON SAMPLING FOR THE BAYESIAN-LINEAR HEAD (DNGO): q nominees per call.  No counterpart in the reference.  The head's posterior
  * over its z weights is a finite Gaussian, N(m_s, inv(A_s)) with A_s = alpha_s I + beta_s Z'Z = L_s L_s', so a sample path is exact:
  *   f_j(x) = mean_s + phi(x)' w_j,      w_j = m_s + L_s^-T eps_j,      eps_j ~ N(0, I_z),      s = j mod S

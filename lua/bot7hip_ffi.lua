@@ -100,6 +100,11 @@ int b7_ts_nominate(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_
 int b7_ts_last_paths(b7_ctx *ctx, double *paths_host );
 int b7_ts_last_draws(b7_ctx *ctx, int path, double *omega , double *phase , double *weight , double *eps );
 int b7_rff_compute(b7_ctx *ctx, const double *X , int64_t M1, int d, const double *omega , const double *phase , const double *W , int F, int q, double *out );
+int b7_ts_nominate_refine(b7_ctx *ctx, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, const b7_refine_opts *opts, double *path_min , int64_t *best_idx1 , double *x_out , double *val_out , int64_t *start_idx1_out , double *jitter_out , int *info_out );
+int b7_ts_refine_last(b7_ctx *ctx, int path, int *P, double *x , double *val , int64_t *start_idx1 , int *status );
+int b7_ts_refine_trace_enable(b7_ctx *ctx, int on);
+int b7_ts_refine_trace(b7_ctx *ctx, int path, int start, double *records, int *n_records);
+int b7_ts_path_grad_at(b7_ctx *ctx, const double *X1 , int64_t M1, double *val , double *grad );
 int b7_blr_ts_nominate(b7_ctx *ctx, const b7_mlp *net, const double *X0, const double *Y0, int N, int S, const double *alpha_prec, const double *beta, const double *mean , int q, uint64_t seed, double *path_min , int64_t *best_idx1 , double *nll_out , double *jitter_used );
 int b7_blr_ts_last_draws(b7_ctx *ctx, int path, double *eps , double *weight );
 int b7_blr_paths_compute(b7_ctx *ctx, const double *Z , int64_t M1, int z, const double *W , const double *mean0 , int q, double *out );

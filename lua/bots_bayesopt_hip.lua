@@ -271,6 +271,58 @@ function bot:nominate_refine(candidates)
   return x, tonumber(ri[0])
 end
 
+-- q Thompson nominees refined off the grid by descent on their own sample paths (b7_ts_nominate_refine; no original): switched on by
+-- config.score.refine = {starts, iters, eta0} under the thompson_sampling_hip score; config.bot.refine stays the per-point scores'.
+-- lo / hi (d-vectors; nil: config.grid.mins / maxes) are the box, a trust-region driver passes its trial's.  Returns a LongTensor of
+-- the q GRID NOMINEES' indices into `candidates` as it stands -- distinct by construction, whichever start won: the caller steals
+-- those rows -- and the refined points (q x d), which it evaluates and observes.  One rank, no group, the gp_hip model, no
+-- constraints or objectives: the rest is refused by name.
+function bot:nominate_ts_refine(q, candidates, lo, hi)
+  local candidates = candidates or self.candidates
+  q = q or self.config.bot.batch or 1
+  assert(D.world == 1 and not hip.group, 'nominate_ts_refine: one rank, no group (refinement of sample paths over a sharded grid is not built)')
+  assert(torch.type(self.score) == 'bot7.scores.thompson_sampling_hip', 'nominate_ts_refine: config.score.refine refines thompson_sampling_hip nominees')
+  assert(not self.config.bot.constraints and not self.config.bot.objectives,
+         'nominate_ts_refine: refinement under constraints or several objectives is not built')
+  local model, keep = self.model, {}
+  assert(torch.type(model) == 'bot7.models.gp_hip', 'nominate_ts_refine: needs the gp_hip model (the dngo head\'s paths are not refined)')
+  local ref = (self.score.config or {}).refine
+  if type(ref) ~= 'table' then ref = {} end
+  local Y_obs = self.responses
+  if Y_obs:dim() == 1 then Y_obs = Y_obs:view(-1, 1) end
+  local X_obs, S = self.observed, self.config.bot.nSamples
+  model:sample_hypers(X_obs, Y_obs)                                          -- :68
+  local hyps = ffi.new('b7_hyp[?]', S)
+  for s = 1, S do                                                            -- :73-75
+    local hyp = model:parse_hypers(model:sample_hypers(X_obs, Y_obs, nil, nil, true))
+    local ls  = hip.pin(hyp.lenscale_sq)
+    keep[#keep + 1] = ls
+    hyps[s-1].lenscale_sq, hyps[s-1].amp, hyps[s-1].noise, hyps[s-1].mean = hip.data(ls), hyp.amp, hyp.noise, hyp.mean
+  end
+  model:stage(X_obs, Y_obs, candidates)
+  hip.set_kernel(model.kernel_code)
+  local d = candidates:size(2)
+  local opts = ffi.new('b7_refine_opts[1]')
+  hip.check(hip.C.b7_refine_default_opts(opts))
+  opts[0].starts = ref.starts or opts[0].starts
+  opts[0].iters  = ref.iters or opts[0].iters
+  opts[0].eta0   = ref.eta0 or opts[0].eta0
+  local blo, bhi = hip.pin(lo or torch.Tensor(self.config.grid.mins)), hip.pin(hi or torch.Tensor(self.config.grid.maxes))
+  keep[#keep + 1], keep[#keep + 2] = blo, bhi
+  opts[0].lo, opts[0].hi = hip.data(blo), hip.data(bhi)
+  local seed = ffi.new('uint64_t', torch.random())
+  local v, i = ffi.new('double[?]', q), ffi.new('int64_t[?]', q)
+  local rv, ri = ffi.new('double[?]', q), ffi.new('int64_t[?]', q)
+  local x = torch.Tensor(q, d)
+  local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
+  hip.check(hip.C.b7_ts_nominate_refine(hip.ctx, S, hyps, q, (self.score.config or {}).nFeatures or 1024, seed, opts, v, i,
+                                        hip.data(x), rv, ri, jit, info))
+  local out = torch.LongTensor(q)
+  for k = 0, q - 1 do out[k + 1] = tonumber(i[k]) end
+  self.best_score = rv[0]
+  return out, x
+end
+
 -- S hyper tables of `model` over (X_obs, Y_obs) as a b7_hyp array, sampled as bots/bayesopt.lua:68,73-75 does
 local function sample_hyps(model, X_obs, Y_obs, S, keep)
   model:sample_hypers(X_obs, Y_obs)                                          -- :68
