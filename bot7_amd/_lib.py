@@ -41,6 +41,7 @@ SYMBOLS = [
     "b7_group_grid_remove_rows", "b7_group_gp_set_data", "b7_group_eval_nominate", "b7_group_nominate_commit",
     "b7_ei_compute", "b7_cb_compute", "b7_logei_compute", "b7_argmax",
     "b7_score_logpi", "b7_logpi_compute", "b7_feas_reset", "b7_feas_add", "b7_feas_add_acc", "b7_feas_get", "b7_feas_nominate", "b7_eval_nominate_feasible",
+    "b7_clf_nll_batch", "b7_clf_fit_hyp", "b7_clf_mode_get", "b7_clf_eval_logfeas", "b7_probit_compute",
     "b7_timer_start", "b7_timer_stop", "b7_timer_ms", "b7_profile_enable", "b7_profile_reset", "b7_profile_get", "b7_persist_fallbacks",
 ]
 
@@ -293,6 +294,11 @@ def load(which=None):
         "b7_feas_get": (i32, [vp, vp]),
         "b7_feas_nominate": (i32, [vp, C.POINTER(dbl), C.POINTER(i64)]),
         "b7_eval_nominate_feasible": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(ScoreSpec), C.POINTER(dbl), C.POINTER(i64), vp, vp]),
+        "b7_clf_nll_batch": (i32, [vp, i32, C.POINTER(Hyp), vp, vp, vp]),
+        "b7_clf_fit_hyp": (i32, [vp, C.POINTER(Hyp), C.POINTER(dbl), C.POINTER(i32), C.POINTER(i32)]),
+        "b7_clf_mode_get": (i32, [vp, vp, vp, vp]),
+        "b7_clf_eval_logfeas": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(dbl), C.POINTER(i64), vp, vp]),
+        "b7_probit_compute": (i32, [vp, vp, i64, vp, vp, vp]),
         "b7_timer_start": (i32, [vp, i32]),
         "b7_timer_stop": (i32, [vp, i32]),
         "b7_timer_ms": (i32, [vp, i32, C.POINTER(C.c_float)]),
@@ -536,7 +542,74 @@ class ThompsonRefine(object):
         return val, grad
 
 
-class Context(BlrThompson, ThompsonObjectives, ThompsonFeasible, ThompsonRefine):
+class LaplaceClassifier(object):
+    """The probit GP classifier by Laplace's method (b7_clf_*; csrc/laplace.hip), mixed into Context below: binary constraints, the
+    resident data's one response column holding labels 0 / 1 with 1 = violated.  A class of its own for BlrThompson's reason; these
+    are held to the same call twice giving the same bits by tests/test_gpu_laplace.py."""
+
+    CLF_NOT_CONVERGED = 1   # info bit 0: the stopping rule was not met within 32 Newton iterations
+
+    def _clf_hyps(self, hyps):
+        # without resident data the library's own refusal is the answer: the lengthscales are packed at the length they come in
+        d = getattr(self, "_data_d", None)
+        if d is None and len(hyps):
+            h = hyps[0]
+            d = _f64(h["lenscale_sq"] if isinstance(h, dict) else h[0]).size
+        return self._pack_hyps(hyps, d)
+
+    def clf_nll_batch(self, hyps, want_info=False):
+        """-log of Laplace's approximate evidence of the resident labels under each hyper vector of hyps (sequence of (lenscale_sq,
+        amp, noise, mean) or dicts; noise is ignored), B workgroups of one launch (b7_clf_nll_batch).  Returns nll[B] (, iterations[B],
+        info[B])."""
+        B = len(hyps)
+        arr, keep = self._clf_hyps(hyps)
+        nll, it, info = np.empty(max(B, 1), dtype=np.float64), np.zeros(max(B, 1), dtype=np.int32), np.zeros(max(B, 1), dtype=np.int32)
+        self._ck(self._L.b7_clf_nll_batch(self._h, B, arr, _ptr(nll), _ptr(it), _ptr(info)))
+        return (nll[:B], it[:B], info[:B]) if want_info else nll[:B]
+
+    def clf_fit_hyp(self, lenscale_sq, amp, noise, mean):
+        """One Laplace fit into the context's own fit slot (b7_clf_fit_hyp): gp_predict / gp_predict_at then return the LATENT mean and
+        variance.  Returns dict(nll, iters, info)."""
+        ls = _f64(lenscale_sq).ravel()
+        if ls.size != getattr(self, "_data_d", ls.size):
+            raise Bot7HipError(-1, "lenscale_sq must have d entries")
+        hyp = Hyp(ls.ctypes.data_as(C.POINTER(C.c_double)), float(amp), float(noise), float(mean))
+        nll, it, info = C.c_double(), C.c_int(), C.c_int()
+        self._ck(self._L.b7_clf_fit_hyp(self._h, C.byref(hyp), C.byref(nll), C.byref(it), C.byref(info)))
+        self.fit_token += 1
+        return {"nll": nll.value, "iters": it.value, "info": info.value}
+
+    def clf_mode_get(self):
+        """(f^, a, W) of the last clf_fit_hyp, N entries each (b7_clf_mode_get)."""
+        n = getattr(self, "_data_n", 0)
+        f, a, W = (np.empty(n, dtype=np.float64) for _ in range(3))
+        self._ck(self._L.b7_clf_mode_get(self._h, _ptr(f), _ptr(a), _ptr(W)))
+        return f, a, W
+
+    def clf_eval_logfeas(self, hyps, want_report=False):
+        """S Laplace fits, their latent posteriors over the resident grid (kept: posterior_get(s) serves them) and the marginal
+        log Pr[feasible | x] = log((1/S) sum_s Phi(-mu_s / sqrt(var_s + 1))) left in the accumulator, as eval_nominate(score="logpi",
+        fmin=0) leaves one for a regression constraint: feas_add_acc(this context) takes it (b7_clf_eval_logfeas).  Returns (value,
+        1-based index[, dict(iters, info)]) of the accumulator's arg-max."""
+        S = len(hyps)
+        arr, keep = self._clf_hyps(hyps)
+        it, info = np.zeros(max(S, 1), dtype=np.int32), np.zeros(max(S, 1), dtype=np.int32)
+        v, i = C.c_double(), C.c_int64()
+        self._ck(self._L.b7_clf_eval_logfeas(self._h, S, arr, C.byref(v), C.byref(i), _ptr(it), _ptr(info)))
+        self.fit_token += 1
+        if want_report:
+            return v.value, i.value, {"iters": it[:S], "info": info[:S]}
+        return v.value, i.value
+
+    def probit_compute(self, z):
+        """(log Phi(z), phi(z)/Phi(z), W(z)) of a host vector by the fit's own device functions (b7_probit_compute)."""
+        z = _f64(z).ravel()
+        out = [np.empty(z.size, dtype=np.float64) for _ in range(3)]
+        self._ck(self._L.b7_probit_compute(self._h, _ptr(z), z.size, *[_ptr(o) for o in out]))
+        return tuple(out)
+
+
+class Context(BlrThompson, ThompsonObjectives, ThompsonFeasible, ThompsonRefine, LaplaceClassifier):
     """One GPU's worth of state: the resident candidate grid, the current GP fit, the score accumulator."""
 
     def __init__(self, device_id=0, _borrowed=None, lib=None):

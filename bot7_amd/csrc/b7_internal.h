@@ -324,6 +324,14 @@ struct b7_ctx {
   DevBuf ehvi3_front;  // the cuts of the three objectives (3 (PMAX + 1) doubles), then the boxes as five table rows each (ints)
   DevBuf ehvi3_table;  // T [rows][C] of one chunk of C candidates, then the row-class flags [3][C] (ints)
   DevBuf ehvi3_user;   // b7_ehvi3_compute's staging, apart from the kept posterior
+  // ---- the probit classifier (laplace.hip): per fit of the last call nll | iterations | info | psi ([B][4] doubles), then the mode
+  // f | a | W ([3][Npad]) of the last b7_clf_fit_hyp; b7_probit_compute's staging, apart from them
+  DevBuf clf, clf_mode, clf_user;
+  uint64_t clf_lab_epoch = ~(uint64_t)0;  // the epoch at which the resident labels were last checked to be 0 / 1, their count then, and
+  int clf_lab_N = 0, clf_lab_bad = 0;     // the first offender (1-based; 0: none)
+  bool clf_mode_valid = false;  // b7_clf_fit_hyp has left a mode since the data, the kernel or the fit slot last changed
+  uint64_t clf_epoch = 0;       // the context's epoch when it did
+  int clf_N = 0;
   DevBuf feat;   // DNGO basis features of the resident grid: Mfeat x Npad (zero-padded columns)
   size_t feat_zeroed_bytes = 0;  // how much of `feat` was zeroed when it was laid out for feat_z columns
   int feat_z = -1;
@@ -501,6 +509,13 @@ int launch_gemv_rows_batch(b7_ctx *c, int S, const double *A, int lda, const dou
                            int64_t rows, double *y, int64_t sy);
 int launch_nll_small(b7_ctx *c, int B, const double *hyp_dev, const double *hyp_host, double *terms_dev, int *info_dev,
                      unsigned *done_dev);
+// laplace.hip: B Laplace fits of the probit classifier, one workgroup each, the whole Newton iteration inside the launch.  K: the
+// fits' covariance matrices K(X,X) without a diagonal term, Npad x Npad each at stride sK (the lower triangle is read; the kernel mirrors
+// it into the upper one); mean_dev: B constant means on the device, or null with the one fit's mean in mean0; out [B][4] (nll,
+// iterations, info bit 0 = not converged within the cap, psi); Linv / alpha (both null: the evidence only): L^-1 W^1/2 and a in the
+// batch-slot layout of FitSet; mode (nullable): f | a | W, [3][Npad] per fit
+int launch_laplace_small(b7_ctx *c, int B, double *K, int64_t sK, const double *mean_dev, double mean0, double *out, double *Linv,
+                         double *alpha, double *mode);
 // kpost_small.hip
 bool kpost_small_applies(const b7_ctx *c);
 int launch_kpost_small(b7_ctx *c, const FitSet &f, const double *xq, int64_t M, double *mu, double *var, int64_t sout);

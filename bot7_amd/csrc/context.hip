@@ -199,7 +199,7 @@ void b7_destroy(b7_ctx *c) {
                    &c->bLinv, &c->balpha, &c->bmu, &c->bvar, &c->ticket, &c->bel, &c->belvec, &c->ystar, &c->mes_ticket, &c->mes_user,
                    &c->ts_paths, &c->ts_draw, &c->ts_work, &c->ts_user, &c->ts_ref_ws, &c->ts_ref_trace, &c->ts_ref_user, &c->slice_trace, &c->slice_state, &c->refine_ws, &c->refine_trace, &c->refine_user,
                    &c->feas, &c->feas_stage, &c->kg, &c->kgvec, &c->kg_slopes, &c->kg_user,
-                   &c->ts_hvi, &c->ts_hvi_t, &c->ts_hvi_user, &c->ts_feas, &c->ts_feas_user, &c->post, &c->ehvi_front, &c->ehvi_user, &c->ehvi3_front, &c->ehvi3_table, &c->ehvi3_user};
+                   &c->ts_hvi, &c->ts_hvi_t, &c->ts_hvi_user, &c->ts_feas, &c->ts_feas_user, &c->post, &c->ehvi_front, &c->ehvi_user, &c->ehvi3_front, &c->ehvi3_table, &c->ehvi3_user, &c->clf, &c->clf_mode, &c->clf_user};
   for (auto &kv : c->pjobs_cache) b7_release(kv.second.buf);
   for (DevBuf *b : all) b7_release(*b);
   if (c->tev_init)

@@ -64,6 +64,15 @@ def gardner1(X):
     return np.stack([y, c], axis=1)
 
 
+def gardner1_hidden(X):
+    """gardner1 with the constraint HIDDEN behind an outcome (no counterpart in benchmarks/): rows [y, v] with v = 1 where gardner1's
+    constraint is violated (c > GARDNER1_THRESHOLD) and 0 where it holds, and y = NaN wherever v = 1 -- the run failed, there is no
+    objective value (config.bot.constraints = [{"threshold": 0.5, "binary": True, "model": {"type": "gp_classifier", ...}}])."""
+    R = gardner1(X)
+    bad = R[:, 1] > GARDNER1_THRESHOLD
+    return np.stack([np.where(bad, np.nan, R[:, 0]), bad.astype(np.float64)], axis=1)
+
+
 def two_spheres(X):
     """A TWO-OBJECTIVE toy (no counterpart in benchmarks/), any dims: rows [y1, y2] = (|x - a|^2, |x - b|^2) with a = 0.25 * 1 and
     b = 0.75 * 1, both minimised.  Its Pareto set is the segment between a and b (config.bot.objectives = {"ref": ..., "model": ...})."""
@@ -80,5 +89,5 @@ def three_spheres(X):
     return np.stack([((X - 0.25) ** 2).sum(1), ((X - 0.5) ** 2).sum(1), ((X - 0.75) ** 2).sum(1)], axis=1)
 
 
-registry = {"braninhoo": braninhoo, "hartmann6": hartmann6, "ackley": ackley, "rastrigin": rastrigin, "gardner1": gardner1,
+registry = {"braninhoo": braninhoo, "hartmann6": hartmann6, "ackley": ackley, "rastrigin": rastrigin, "gardner1": gardner1, "gardner1_hidden": gardner1_hidden,
             "two_spheres": two_spheres, "three_spheres": three_spheres}

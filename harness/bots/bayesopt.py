@@ -42,6 +42,13 @@ into its feasibility column (feas_reset, feas_add_acc) and nominates with the we
 response among the rows that satisfy every constraint -- or, while no row does, by feasibility alone (feas_nominate).  The stolen
 row leaves every context's resident grid.  What is not built is refused by name (constraint_refusal).
 
+A constraint with "binary": True (ours) is one observed only as an OUTCOME -- a run diverged, ran out of memory, returned NaN: its
+response column holds 0 (satisfied) or 1 (violated), its threshold is 0.5 (so feasible_rows / best_feasible_fmin read it as they are)
+and its model is a gp_classifier, a probit GP by Laplace's method (Gelbart et al. 2014, section 2.3), which leaves the same log
+accumulator through clf_eval_logfeas instead of eval_nominate(score="logpi").  The objective need not exist where such a constraint
+is violated: with a binary constraint present, observed rows whose objective is not finite are left out of the OBJECTIVE model's data
+(objective_rows); they stay in every constraint model's.  constrained_thompson_sampling refuses a binary constraint by name.
+
 config.score.type = 'constrained_thompson_sampling' with config.bot.constraints is CONSTRAINED THOMPSON SAMPLING (the selection rule of
 SCBO: Eriksson & Poloczek 2021), for any config.bot.batch from 1 to 16: per model-based trial the objective's model and every
 constraint's model sample their hypers, stage their column on their own context and keep config.bot.batch sample paths (ts_paths, a
@@ -167,6 +174,9 @@ def constrained_thompson_refusal(config, model_class="bot7.models.gp_regressor",
     if model_class == "bot7.models.dngo":
         return "%s with the dngo model: joint paths with the Bayesian-linear head are not built" % kind
     for k, con in enumerate(cons):
+        if con.get("binary"):
+            return "%s with config.bot.constraints[%d] binary: sample paths of a classifier's latent are not built (binary constraints " \
+                   "nominate through the feasibility weight)" % (kind, k)
         if (con.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
             return "%s with config.bot.constraints[%d] on the %s model: a constraint is modelled by a gp_regressor" % (kind, k, con["model"]["type"])
     if len(cons) > TS_FEAS_CMAX:
@@ -203,8 +213,25 @@ def constraint_refusal(config, model_class="bot7.models.gp_regressor", sharded=F
     if kind not in CONSTRAINED_SCORES:
         return "config.bot.constraints with %s: only %s are built" % (kind, ", ".join(CONSTRAINED_SCORES))
     for k, con in enumerate(config["bot"]["constraints"]):
-        if (con.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
+        why = binary_refusal(k, con)
+        if why:
+            return why
+        if not con.get("binary") and (con.get("model") or {}).get("type", "gp_regressor") != "gp_regressor":
             return "config.bot.constraints[%d] with the %s model: a constraint is modelled by a gp_regressor" % (k, con["model"]["type"])
+    return None
+
+
+def binary_refusal(k, con):
+    """Why constraint k's binary flag and model do not go together, by name, or None.  A binary constraint -- response 0 or 1, 1 =
+    violated -- is modelled by a gp_classifier, and a gp_classifier models nothing else."""
+    mtype = (con.get("model") or {}).get("type", "gp_classifier" if con.get("binary") else "gp_regressor")
+    if con.get("binary") and mtype != "gp_classifier":
+        return "config.bot.constraints[%d] is binary with the %s model: a binary constraint is modelled by a gp_classifier" % (k, mtype)
+    if not con.get("binary") and mtype == "gp_classifier":
+        return "config.bot.constraints[%d] with the gp_classifier model: a classifier models a binary constraint (set binary = True)" % k
+    if con.get("binary") and float(con.get("threshold", 0.5)) != 0.5:
+        return "config.bot.constraints[%d] is binary with threshold %g: the labels are 0 (satisfied) and 1 (violated), threshold 0.5" % (
+            k, float(con["threshold"]))
     return None
 
 
@@ -403,6 +430,16 @@ def feasible_rows(responses, thresholds):
     return ok
 
 
+def objective_rows(Y_obs, constraints):
+    """Which observed rows reach the OBJECTIVE's model: all of them, unless a binary constraint is present -- the objective then does
+    not exist where a run failed (NaN), and the rows whose objective is not finite are left out of its data.  They stay in every
+    constraint model's."""
+    Y = np.asarray(Y_obs, dtype=np.float64)
+    if not any(c.get("binary") for c in constraints):
+        return np.ones(Y.shape[0], dtype=bool)
+    return np.isfinite(Y).all(axis=1)
+
+
 def best_feasible_fmin(responses, thresholds):
     """fmin of the constrained nomination: the best objective value among the feasible rows, as a 1-vector -- or None when no row
     is feasible (the nomination then goes by feasibility alone)."""
@@ -447,9 +484,7 @@ class bayesopt(abstract):
         if not config["bot"]["constraints"]:            # (an empty list constrains nothing: the reference's loop)
             config["bot"]["constraints"] = None
         if config["bot"]["constraints"] is not None:
-            config["bot"]["constraints"] = [{"threshold": float(c["threshold"]),
-                                             "model": self._model_defaults(c.get("model"), config["bot"]["nSamples"])}
-                                            for c in config["bot"]["constraints"]]
+            config["bot"]["constraints"] = [self._constraint_defaults(c, config["bot"]["nSamples"]) for c in config["bot"]["constraints"]]
         config["bot"].setdefault("objectives", None)    # ours: None, or {"ref": [r1, r2] | None, "model": {...}} (nominate_objectives)
         if config["bot"]["objectives"] is not None and "models" in config["bot"]["objectives"]:
             # THREE objectives: {"ref": [r1, r2, r3] | None, "models": [{...}, {...}]}, the second and the third objective's models
@@ -471,6 +506,19 @@ class bayesopt(abstract):
             tr.setdefault("base", config["grid"]["type"])
             config["bot"]["trust_region"] = tr
         return config
+
+    @classmethod
+    def _constraint_defaults(cls, con, nSamples):
+        """{"threshold": t, "model": {...}}; a BINARY constraint (ours: "binary": True -- the response column holds 0 or 1, 1 =
+        violated, and the objective may be NaN there) keeps its flag and is modelled by a gp_classifier unless the config says otherwise
+        (binary_refusal then names it)."""
+        model = dict(con.get("model") or {})
+        if con.get("binary"):
+            model.setdefault("type", "gp_classifier")
+        out = {"threshold": float(con["threshold"]), "model": cls._model_defaults(model, nSamples)}
+        if con.get("binary"):
+            out["binary"] = True
+        return out
 
     @staticmethod
     def _model_defaults(model, nSamples):
@@ -702,7 +750,7 @@ class bayesopt(abstract):
             self.constraints = []
             for con in self.config["bot"]["constraints"]:
                 ctx = Context(self.model.ctx.device_id)
-                self.constraints.append({"threshold": con["threshold"], "ctx": ctx, "grid": None,
+                self.constraints.append({"threshold": con["threshold"], "ctx": ctx, "grid": None, "binary": bool(con.get("binary")),
                                          "model": Models.registry[con["model"]["type"]](con["model"], context=ctx)})
         return self.constraints
 
@@ -734,22 +782,36 @@ class bayesopt(abstract):
                 con["ctx"].grid_upload(host)
                 con["grid"] = DeviceGrid(host, con["ctx"], con["ctx"].grid_version)
             con["model"].stage(X_obs, Ck, con["grid"])
-            con["ctx"].eval_nominate(hyps, score="logpi", fmin=[con["threshold"]], tradeoff=0.0)   # log Pr[c_k <= t_k] in the accumulator
+            if con.get("binary"):                                 # the classifier's log Pr[feasible] in the accumulator
+                con["ctx"].clf_eval_logfeas(hyps)
+            else:
+                con["ctx"].eval_nominate(hyps, score="logpi", fmin=[con["threshold"]], tradeoff=0.0)   # log Pr[c_k <= t_k] in the accumulator
             con_hyps.append(hyps)
-        hyps = self._sample_hyps(model, X_obs, Y_obs)
-        model.stage(X_obs, Y_obs, cand)
+        rows = objective_rows(Y_obs, cons)                        # (all of them unless a binary constraint is present)
+        if not rows.all():
+            X_obs, Y_obs = np.ascontiguousarray(X_obs[rows]), np.ascontiguousarray(Y_obs[rows])
         ctx = model.ctx
+        if rows.any():
+            hyps = self._sample_hyps(model, X_obs, Y_obs)
+            model.stage(X_obs, Y_obs, cand)
+        else:                                                     # no run has returned an objective yet: feasibility alone, no objective model
+            hyps = None
+            if not model._is_resident(cand):
+                ctx.grid_upload(np.atleast_2d(host))
         ctx.feas_reset()
         for con in cons:
             ctx.feas_add_acc(con["ctx"])
         fmin = best_feasible_fmin(self.responses, thresholds)
-        if fmin is None:                                          # no feasible observation yet: Gelbart et al. 2014, section 3.2
+        if fmin is None or hyps is None:                          # no feasible observation yet: Gelbart et al. 2014, section 3.2
+            fmin = None
             val, idx = ctx.feas_nominate()
         else:
             spec = dict(self.score.device_spec(Y_obs), fmin=fmin)
             val, idx = ctx.eval_nominate_feasible(hyps, **spec)
         self.last_scores = None
         self.last_constrained = {"hyps": hyps, "constraint_hyps": con_hyps, "fmin": fmin, "value": val, "index": int(idx)}
+        if not rows.all():
+            self.last_constrained["objective_rows"] = rows
         return int(idx)
 
     # ---- constrained Thompson sampling (config.score.type = 'constrained_thompson_sampling' with config.bot.constraints) ------------
@@ -856,7 +918,9 @@ class bayesopt(abstract):
         self.observed, self.pending = T.steal(self.observed, self.pending, [k])  # :143-144
         if self.model is not None and self.nTrials == self.config["bot"]["nInitial"]:
             Y_obs, C_obs = split_columns(self.responses, C)
-            self.model.init(self.observed, Y_obs)                  # :147-149
+            rows = objective_rows(Y_obs, self.config["bot"]["constraints"])
+            if rows.any():                                         # (none yet: the model initialises itself at its first sample_hypers)
+                self.model.init(self.observed[rows], Y_obs[rows])  # :147-149
             for con, Ck in zip(self._constraints_setup(), C_obs):
                 con["model"].init(self.observed, Ck)
         return nominee, y

@@ -1153,6 +1153,47 @@ int b7_logpi_compute(b7_ctx *ctx, const double *mean, const double *var, const d
                      int64_t M, int c, double *out);
 int b7_argmax(b7_ctx *ctx, const double *scores, int64_t M, double *best_val, int64_t *best_idx1);
 
+/* ---- binary constraints: a probit GP classifier by Laplace's method ---------------------------
+ * No counterpart in the reference (Gelbart, Snoek & Adams 2014, section 2.3; Rasmussen & Williams 2006, algorithms 3.1 / 3.2).
+ * The resident data (b7_gp_set_data) are N <= 128 rows with ONE response column of labels, each exactly 0 or 1, 1 meaning the
+ * constraint is VIOLATED; Pr[label = 1 | h] = Phi(h) of a latent GP h with constant prior mean hyp.mean and the context's covariance
+ * kernel (b7_gp_set_kernel).  hyp.noise is ignored (the probit link has unit variance) and must still be finite.  A fit is the mode
+ * f^ of the latent's posterior by Newton's iteration, run WHOLE inside one kernel launch (csrc/laplace.hip states the rule: at most
+ * 32 iterations, stop at |a+ - a|_inf <= 2^-26 max(1, |a+|_inf), step halving on psi), then
+ *   Linv = L^-1 W^1/2,  alpha = a = grad log p(labels | f^),  nll = -log q(labels | hyp) (Laplace's approximate evidence)
+ * in the regressor's layout, so that every posterior entry point reads it unchanged.  There is no jitter schedule: B = I +
+ * W^1/2 K W^1/2 has every eigenvalue >= 1.  iters_out: Newton iterations taken; info_out: bit 0 set when the stopping rule was not met
+ * within 32 (results are delivered all the same).  The same call twice gives the same bits; a fit's bits depend neither on the
+ * batch, nor on its position in it, nor on the grid.
+ * Every entry point below refuses, the case named: labels other than exactly 0 or 1 (B7_ERR_INVALID); N > 128 or more than one
+ * response column (B7_ERR_UNSUPPORTED); a communicator of more than one rank (B7_ERR_UNSUPPORTED); a member of a group, no resident
+ * data (B7_ERR_STATE).  NULL arguments, lenscale_sq or amp <= 0 or any hyper not finite: B7_ERR_INVALID.  A refusal leaves the
+ * context as it was.
+ *   b7_clf_nll_batch     the hyper sampler's density: nll of the resident labels under B hyper vectors, B workgroups of one
+ *                        launch.  iters_out / info_out nullable.  The context's fit slot, predictions and accumulator are untouched.
+ *   b7_clf_fit_hyp       one fit into the context's own fit slot.  Afterwards b7_gp_predict / b7_gp_predict_at return the LATENT
+ *                        mean and variance (b7_gp_opts.var_with_noise adds nothing: the fit's noise is 0); nothing else is
+ *                        special-cased, and b7_gp_append / b7_gp_fantasize / b7_gp_download's L are not meaningful on such a fit.
+ *                        All outputs nullable.
+ *   b7_clf_mode_get      f^, a and W of the last b7_clf_fit_hyp, N entries each (all nullable).  B7_ERR_STATE without one, or after
+ *                        the data or the covariance kernel changed.
+ *   b7_clf_eval_logfeas  S fits side by side, the latent posterior of every sample over the resident grid by the route the
+ *                        regressor's nomination takes for that shape -- kept, as b7_eval_posterior keeps one: b7_posterior_get(s)
+ *                        serves it --, then log Phi((0 - mu_s) / sqrt(var_s + 1)) per sample, folded by log-sum-exp in sample order
+ *                        and divided by S: log Pr[feasible | x] marginalised over the samples.  This leaves exactly the log
+ *                        accumulator that b7_eval_nominate(B7_SCORE_LOGPI, fmin = 0) leaves for a regression constraint:
+ *                        b7_feas_add_acc(objective, ctx) takes it, b7_score_finish downloads it.  The + 1 is this entry point's own,
+ *                        whatever b7_gp_opts.var_with_noise says.  Returns the accumulator's arg-max.  B7_ERR_STATE without a grid;
+ *                        B7_ERR_INVALID when the grid's dims differ from the data's.  iters_out / info_out nullable.
+ *   b7_probit_compute    the likelihood's three scalar pieces on a host vector z of n entries: log Phi(z), phi(z)/Phi(z) and
+ *                        W(z) = -(log Phi)''(z), as the fit evaluates them.  It disturbs nothing. */
+int b7_clf_nll_batch(b7_ctx *ctx, int B, const b7_hyp *hyps, double *nll_out /*B*/, int *iters_out /*B*/, int *info_out /*B*/);
+int b7_clf_fit_hyp(b7_ctx *ctx, const b7_hyp *hyp, double *nll_out, int *iters_out, int *info_out);
+int b7_clf_mode_get(b7_ctx *ctx, double *f_out /*N*/, double *a_out /*N*/, double *W_out /*N*/);
+int b7_clf_eval_logfeas(b7_ctx *ctx, int S, const b7_hyp *hyps, double *best_val, int64_t *best_idx1, int *iters_out /*S*/,
+                        int *info_out /*S*/);
+int b7_probit_compute(b7_ctx *ctx, const double *z, int64_t n, double *logcdf_out /*n*/, double *ratio_out /*n*/, double *w_out /*n*/);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 
 /* HIP-event timers on the context's stream (the stream every kernel of this library is launched on). */

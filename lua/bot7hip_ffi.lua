@@ -163,6 +163,11 @@ int b7_cb_compute(b7_ctx *ctx, const double *mean, const double *var, double tra
 int b7_logei_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M, int c, double *out);
 int b7_logpi_compute(b7_ctx *ctx, const double *mean, const double *var, const double *fmin, double tradeoff, int64_t M, int c, double *out);
 int b7_argmax(b7_ctx *ctx, const double *scores, int64_t M, double *best_val, int64_t *best_idx1);
+int b7_clf_nll_batch(b7_ctx *ctx, int B, const b7_hyp *hyps, double *nll_out , int *iters_out , int *info_out );
+int b7_clf_fit_hyp(b7_ctx *ctx, const b7_hyp *hyp, double *nll_out, int *iters_out, int *info_out);
+int b7_clf_mode_get(b7_ctx *ctx, double *f_out , double *a_out , double *W_out );
+int b7_clf_eval_logfeas(b7_ctx *ctx, int S, const b7_hyp *hyps, double *best_val, int64_t *best_idx1, int *iters_out , int *info_out );
+int b7_probit_compute(b7_ctx *ctx, const double *z, int64_t n, double *logcdf_out , double *ratio_out , double *w_out );
 int b7_timer_start(b7_ctx *ctx, int slot);
 int b7_timer_stop(b7_ctx *ctx, int slot);
 int b7_timer_ms(b7_ctx *ctx, int slot, float *ms_out);

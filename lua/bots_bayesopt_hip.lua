@@ -376,6 +376,10 @@ end
 -- returned row from self.candidates (bots/abstract.lua:118: the contract follow_steal relies on); the next call deletes it from
 -- every constraint context's grid before anything is staged there.  One rank, no group, EI / LogEI / LogPI; at parity with
 -- harness/bots/bayesopt.py's nominate_constrained.
+-- A constraint with binary = true is observed only as an outcome (0 satisfied, 1 violated; threshold 0.5): its model is a
+-- gp_classifier_hip and b7_clf_eval_logfeas leaves the same log accumulator in place of b7_eval_nominate(LogPI).  With a binary
+-- constraint present the rows whose objective is not finite (the run failed: there is no value) are left out of the OBJECTIVE
+-- model's data; they stay in every constraint model's.
 function bot:nominate_constrained(candidates)
   local candidates = candidates or self.candidates
   if torch.type(self.score) == 'bot7.scores.constrained_thompson_sampling_hip' then
@@ -395,37 +399,63 @@ function bot:nominate_constrained(candidates)
     for k, cfg in ipairs(cons) do
       local ctxp = ffi.new('b7_ctx*[1]')
       assert(hip.C.b7_create(ctxp, hip.device) == 0, 'nominate_constrained: b7_create failed')   -- the objective's device
-      self.constraints[k] = {threshold = cfg.threshold, model = bot7.models.gp_hip(cfg.model), ctx = ffi.gc(ctxp[0], hip.C.b7_destroy),
+      local mtype = (cfg.model or {}).type or (cfg.binary and 'gp_classifier' or 'gp_regressor')
+      assert((cfg.binary and true or false) == (mtype == 'gp_classifier' or mtype == 'gp_classifier_hip'),
+             'config.bot.constraints[' .. k .. ']: a binary constraint is modelled by a gp_classifier, and a gp_classifier models nothing else')
+      assert(not cfg.binary or cfg.threshold == 0.5, 'config.bot.constraints[' .. k .. '] is binary: the labels are 0 and 1, threshold 0.5')
+      local class = cfg.binary and bot7.models.gp_classifier_hip or bot7.models.gp_hip
+      self.constraints[k] = {threshold = cfg.threshold, model = class(cfg.model), ctx = ffi.gc(ctxp[0], hip.C.b7_destroy),
+                             binary = cfg.binary and true or false,
                              kernel = hip.KERNEL_ARDSE}   -- a new context starts on ARD-SE: the constraint's own kernel cache
     end
   end
-  local feasible = torch.ByteTensor(R:size(1)):fill(1)
+  local feasible, binary = torch.ByteTensor(R:size(1)):fill(1), false
   for k, con in ipairs(self.constraints) do
     local C_obs = R:narrow(2, k + 1, 1):contiguous()
     feasible:cmul(C_obs:view(-1):le(con.threshold))
+    binary = binary or con.binary
     follow_steal(con, self.constrained_idx, candidates)
     on_context(con, function()
       if not con.inited then con.model:init(X_obs, C_obs); con.inited = true end
       local hyps = sample_hyps(con.model, X_obs, C_obs, S, keep)
       con.model:stage(X_obs, C_obs, candidates)
       hip.set_kernel(con.model.kernel_code)
-      local t = hip.pin(torch.Tensor{con.threshold})
-      keep[#keep + 1] = t
-      local spec = ffi.new('b7_score_spec', {hip.SCORE_LOGPI, 0.0, 0, 0.0, hip.data(t)})
       local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
-      hip.check(hip.C.b7_eval_nominate(hip.ctx, S, hyps, spec, 0, v, i, nil, nil))
+      if con.binary then                                                     -- the classifier's log Pr[feasible] in the accumulator
+        hip.check(hip.C.b7_clf_eval_logfeas(hip.ctx, S, hyps, v, i, nil, nil))
+      else
+        local t = hip.pin(torch.Tensor{con.threshold})
+        keep[#keep + 1] = t
+        local spec = ffi.new('b7_score_spec', {hip.SCORE_LOGPI, 0.0, 0, 0.0, hip.data(t)})
+        hip.check(hip.C.b7_eval_nominate(hip.ctx, S, hyps, spec, 0, v, i, nil, nil))
+      end
     end)
   end
-  local hyps = sample_hyps(model, X_obs, Y_obs, S, keep)
-  model:stage(X_obs, Y_obs, candidates)
+  -- the rows that reach the objective's model: all of them unless a binary constraint is present (a failed run has no objective)
+  local Y_all, have_objective = Y_obs, true
+  if binary then
+    local finite = Y_obs:view(-1):eq(Y_obs:view(-1)):cmul(torch.abs(Y_obs:view(-1)):lt(math.huge))
+    have_objective = finite:sum() > 0
+    if have_objective and finite:sum() < Y_obs:size(1) then
+      local rows = finite:nonzero():view(-1)
+      X_obs, Y_obs = X_obs:index(1, rows), Y_obs:index(1, rows)
+    end
+  end
+  local hyps
+  if have_objective then
+    hyps = sample_hyps(model, X_obs, Y_obs, S, keep)
+    model:stage(X_obs, Y_obs, candidates)
+  elseif not hip.is_resident(candidates) then
+    hip.upload_grid(candidates)                                              -- feasibility alone: no objective model yet
+  end
   hip.set_kernel(model.kernel_code)
   hip.check(hip.C.b7_feas_reset(hip.ctx))
   for _, con in ipairs(self.constraints) do hip.check(hip.C.b7_feas_add_acc(hip.ctx, con.ctx)) end
   local v, i = ffi.new('double[1]'), ffi.new('int64_t[1]')
-  if feasible:sum() == 0 then                                                -- Gelbart et al. 2014, section 3.2
+  if feasible:sum() == 0 or not have_objective then                          -- Gelbart et al. 2014, section 3.2
     hip.check(hip.C.b7_feas_nominate(hip.ctx, v, i))
   else
-    local Y_feas = Y_obs:index(1, feasible:nonzero():view(-1))
+    local Y_feas = Y_all:index(1, feasible:nonzero():view(-1))
     local spec = assert(score_spec(self.score, Y_feas, keep), 'nominate_constrained: needs a *_hip score')
     local jit, info = ffi.new('double[?]', S), ffi.new('int[?]', S)
     hip.check(hip.C.b7_eval_nominate_feasible(hip.ctx, S, hyps, spec, v, i, jit, info))
@@ -749,6 +779,9 @@ local function constrained_ts_refusal(self, q)
   end
   if torch.type(self.model) ~= 'bot7.models.gp_hip' then return kind .. ' needs the gp_hip model' end
   for k, cfg in ipairs(b.constraints) do
+    if cfg.binary then
+      return kind .. ' with config.bot.constraints[' .. k .. '] binary: sample paths of the latent of a classifier are not built (binary constraints nominate through the feasibility weight)'
+    end
     local mtype = cfg.model and cfg.model.type or 'gp_regressor'
     if mtype ~= 'gp_regressor' and mtype ~= 'gp_hip' then
       return kind .. ' with config.bot.constraints[' .. k .. '] on the ' .. mtype .. ' model: a constraint is modelled by a gp_regressor'
