@@ -22,7 +22,7 @@ SOURCES = ["context.hip", "grid_api.hip", "gp_api.hip", "nominate.hip", "blr_api
 # a bit-for-bit reference.  Only translation units that mention B7_DIAG are compiled a second time; the rest are shared.
 DIAG_ONLY_SOURCES = ["nll_small.hip"]
 DIAG_OUT = os.path.join(ROOT, "tools", "_build", "libbot7hip_diag.so")
-HEADERS = [os.path.join(CSRC, "b7_internal.h"), os.path.join(CSRC, "gemm_f64.h"), os.path.join(CSRC, "potrf_diag.h"), os.path.join(CSRC, "comm_rccl.h"), os.path.join(CSRC, "ksx_exp.h"), os.path.join(CSRC, "ksx_walk.h"), os.path.join(CSRC, "exp_table.h"), os.path.join(CSRC, "mes_math.h"), os.path.join(CSRC, "logei_math.h"), os.path.join(CSRC, "ehvi_math.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "gp_small_body.h"), os.path.join(CSRC, "post_ring_layout.h"), os.path.join(CSRC, "probit_math.h"),
+HEADERS = [os.path.join(CSRC, "b7_internal.h"), os.path.join(CSRC, "argbest.h"), os.path.join(CSRC, "gemm_f64.h"), os.path.join(CSRC, "potrf_diag.h"), os.path.join(CSRC, "comm_rccl.h"), os.path.join(CSRC, "ksx_exp.h"), os.path.join(CSRC, "ksx_walk.h"), os.path.join(CSRC, "exp_table.h"), os.path.join(CSRC, "mes_math.h"), os.path.join(CSRC, "logei_math.h"), os.path.join(CSRC, "ehvi_math.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "gp_small_body.h"), os.path.join(CSRC, "post_ring_layout.h"), os.path.join(CSRC, "probit_math.h"),
            os.path.join(ROOT, "include", "bot7hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-fast-math", "-Wall",

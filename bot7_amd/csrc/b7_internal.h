@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "argbest.h"
 #include "bot7hip.h"
 
 // Tile constants.  Every matrix dimension that a GEMM-class kernel sees is padded to these.
@@ -58,8 +59,6 @@ struct PinBuf {
 // What a fit reports to the host: the pivot report (first failing pivot, 1-based, 0 if none | hand-off time-out code) and the
 // likelihood terms (sum log L_ii, then r_k' alpha_k per response column).
 struct FitBlock { int info[4]; double terms[257]; };
-// An arg-max as the kernels write it: layout of score.hip's Best, whose name is part of its kernels' symbols and stays there.
-struct BestPair { double v; int64_t i; };
 // Direction numbers of the Sobol sequence (sobol.hip), uploaded into the scratch block.
 constexpr int SOBOL_DIMS = 40;  // table rows (the reference admits dims < 40, grids/sobol.lua:36)
 constexpr int SOBOL_BITS = 30;  // log_max, grids/sobol.lua:32
@@ -72,14 +71,15 @@ struct SobolTable {
 constexpr size_t B7_PINNED_BYTES = 16384;
 struct PinnedBlock {
   FitBlock fit;                       // a fit's report (gp_api.hip: fit_hyp_core); the Bayesian linear head's, its first 16 bytes
-  alignas(256) BestPair best;            // launch_finish's arg-max, written by the kernel through the mapped address
+  alignas(256) ArgBest best;             // launch_finish's arg-max (argbest.h), written by the kernel through the mapped address
   alignas(4096) double fmin[256];     // f_min of several response columns on their way to the device (stage_fmin)
   alignas(4096) double vec[B7_MAX_D + 3];  // a small vector on its way to the device: a fit's lengthscales (the one-launch fit reads
                                            // amp, noise and mean behind them), a grid map's per-column shift / scale
   alignas(4096) double tr[5 * B7_MAX_D];   // the trust-region map's center | lo | span | shift | hi on their way to the device
 };
 static_assert(offsetof(PinnedBlock, fit) == 0 && offsetof(PinnedBlock, best) == 2304 && offsetof(PinnedBlock, fmin) == 4096 &&
-                  offsetof(PinnedBlock, vec) == 8192 && offsetof(PinnedBlock, tr) == 12288 && sizeof(PinnedBlock) <= B7_PINNED_BYTES,
+                  offsetof(PinnedBlock, vec) == 8192 && offsetof(PinnedBlock, tr) == 12288 && sizeof(PinnedBlock) <= B7_PINNED_BYTES &&
+                  sizeof(ArgBest) == 16 && offsetof(ArgBest, i) == 8,
               "pinned block: kernels and copies address these slots");
 
 // c->scratch: 64 KiB of device memory, never regrown.
@@ -143,10 +143,33 @@ struct TsRefLast {
   std::vector<int> status;      // [q][16] B7_REFINE_* bits
 };
 
+// What the last path-drawing call left on a context: filled once, by ts_paths_core (rff.hip: b7_ts_nominate, b7_ts_paths) or by
+// b7_blr_ts_nominate (blr_ts.hip), read by everything that picks from, refines or downloads the kept paths.  A call that draws
+// paths starts by setting who = TS_NONE, so a failed call leaves none.  The DNGO head's paths are laid out like a GP's ([M][q]), its
+// ts_draw holds eps [q][z] | weight [q][z], F = z and N = d = 0.
+enum { TS_NONE = 0, TS_GP = 1, TS_BLR = 2 };  // TsPaths::who
+struct TsPaths {
+  int who = TS_NONE;
+  int64_t M = 0;
+  int q = 0, S = 0, F = 0, N = 0, d = 0;
+  int ns = 0;          // min(S, q): the hyper samples that own a path
+  uint64_t epoch = 0;  // the context's epoch when the paths were made
+  std::vector<double> hyp;  // a GP's ns hyper samples: lenscale_sq d | amp | noise | mean each
+  // the pieces of c->ts_work that outlive the call.  alpha (a GP's): sample s's columns at alpha + s alpha_stride ([Npad][yld], yld =
+  // 1 or the sample's columns rounded up to 64; column p is v_j of path j = s + S p).  pmin / taken [q], part [nblk]: the arg-mins'
+  const double *alpha = nullptr;
+  int64_t alpha_stride = 0;
+  double *pmin = nullptr;
+  long long *taken = nullptr;
+  ArgBest *part = nullptr;
+  int nblk = 0;
+};
 struct b7_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev_fit = nullptr;  // behind the fit report's copy: b7_gp_predict_hyp waits for it, not for the prediction
+  // streams_order (context.hip): the other contexts' streams of a call -> this one (slot m - 1 for the m-th), and back (the last slot)
+  hipEvent_t ev_order[1 + B7_TS_FEAS_CMAX] = {};
   std::string err;
   int cus = 0;
 
@@ -255,7 +278,6 @@ struct b7_ctx {
   DevBuf feas;
   DevBuf feas_stage;        // b7_feas_add's host vector on its way onto the column
   bool feas_valid = false;
-  hipEvent_t ev_feas[2] = {nullptr, nullptr};  // b7_feas_add_acc: the source's stream -> this one, and back (created on first use)
   DevBuf scratch; // a ScratchBlock (b7_scratch)
   DevBuf tmpgrid; // predict_at temporary grid
   DevBuf tmpmu, tmpvar;
@@ -270,15 +292,7 @@ struct b7_ctx {
   DevBuf ts_paths;  // [M][q]
   DevBuf ts_draw;   // omega [min(S, q)][F][d] | phase [F] | weight [q][F] | eps [q][N]
   DevBuf ts_work, ts_user;
-  bool ts_valid = false;  // a b7_ts_nominate has succeeded; the shapes of what it left:
-  int64_t ts_M = 0;
-  int ts_q = 0, ts_S = 0, ts_F = 0, ts_N = 0, ts_d = 0;
-  // ... or a b7_blr_ts_nominate (blr_ts.hip): the paths are laid out alike, ts_draw holds eps [q][z] | weight [q][z] and ts_F = z
-  bool ts_blr = false;
-  // ... or a b7_ts_paths, which stops short of the arg-mins.  ts_epoch: the context's epoch (below) when the paths were made; the
-  // multi-objective nominations (ts_hvi.hip) answer B7_ERR_STATE to paths of an earlier grid or data, b7_ts_last_paths still serves them
-  uint64_t ts_epoch = 0;
-  std::vector<double> ts_hyp;  // the min(S, q) hyper samples a GP's paths were drawn under: lenscale_sq d | amp | noise | mean each
+  TsPaths ts;  // what the last path-drawing call left (above)
   // ---- b7_ts_nominate_refine / b7_ts_path_grad_at (ts_refine.hip): the packed operands and the starts' state, the last call's
   // trace, b7_ts_path_grad_at's staging, and the last call's result on the host
   DevBuf ts_ref_ws, ts_ref_trace, ts_ref_user;
@@ -292,8 +306,6 @@ struct b7_ctx {
   // picks' values (ts_feas), and b7_ts_feas_compute's staging, apart from the kept paths
   DevBuf ts_feas, ts_feas_user;
   int ts_feas_onepass = 0;  // 0: path by path, q chained passes (default: the faster arm on real paths); 1: all q paths scored in one pass, exclusions resolved on the host
-  // the constraint contexts' streams -> this one (0 .. C - 1), and back (the last); created on first use
-  hipEvent_t ev_ts_feas[B7_TS_FEAS_CMAX + 1] = {};
   // ---- b7_eval_nominate_refine / b7_gp_grad_at (refine.hip): the workspace of 64 query columns, the last call's trace and result
   DevBuf refine_ws, refine_trace;
   DevBuf refine_user;       // b7_score_grad_compute's staging, apart from them
@@ -318,8 +330,6 @@ struct b7_ctx {
   int64_t post_M = 0;
   DevBuf ehvi_front; // a_1 .. a_P, r1 | r2, b_1 .. b_P: 2 (P + 1) doubles as the kernel reads them
   DevBuf ehvi_user;
-  // ehvi_nominate of n objectives: the other contexts' streams -> this one (0 .. n - 2), and back (n - 1); created on first use
-  hipEvent_t ev_ehvi[3] = {nullptr, nullptr, nullptr};
   // ---- b7_ehvi3_* (ehvi3.hip): three objectives over the same kept posteriors
   DevBuf ehvi3_front;  // the cuts of the three objectives (3 (PMAX + 1) doubles), then the boxes as five table rows each (ints)
   DevBuf ehvi3_table;  // T [rows][C] of one chunk of C candidates, then the row-class flags [3][C] (ints)
@@ -601,6 +611,16 @@ int acc_materialize(b7_ctx *c);
 void feas_forget(b7_ctx *c);  // the grid changed: there is no feasibility column until the next b7_feas_reset
 // the grid or the data changed: there is no kept posterior until the next b7_eval_posterior (ehvi.hip)
 static inline void post_forget(b7_ctx *c) { c->post_valid = false, ++c->epoch; }
+// The kept paths of a context, for every caller that wants them: none, the DNGO head's (whatever their age), a GP's of an earlier
+// grid, data or covariance kernel, or a GP's of this one.  Every site that changes M, N, dfit or the kernel goes through post_forget,
+// so the epoch alone decides; the shapes are compared as well, which costs nothing.  The callers word their own refusals.
+enum { TS_STATE_NONE = 0, TS_STATE_BLR, TS_STATE_STALE, TS_STATE_FRESH };
+static inline int ts_state(const b7_ctx *c) {
+  const TsPaths &t = c->ts;
+  if (t.who == TS_NONE) return TS_STATE_NONE;
+  if (t.who == TS_BLR) return TS_STATE_BLR;
+  return (t.epoch != c->epoch || t.M != c->M || t.N != c->N || t.d != c->dfit) ? TS_STATE_STALE : TS_STATE_FRESH;
+}
 int feas_write_zeros(b7_ctx *c);                      // L := 0.0 over the resident grid (allocates on demand)
 int launch_feas_add(b7_ctx *c, const double *src);    // L[j] += src[j], src: c->M doubles on the device
 int launch_feas_best(b7_ctx *c, double *best_val, int64_t *best_idx1);  // score:max(1) of L alone (waits)
@@ -717,10 +737,10 @@ struct Staged3 {
 };
 void stage3_host(const double *front, int P, const double *ref, Staged3 *st);
 int launch_ehvi3(b7_ctx *c, bool log, const double *const *mu, const double *const *var, const int *S, const Staged3 &st, int64_t M, double *out);
-// ehvi.hip: what ts_hvi.hip shares with the two-objective nomination: the front's check (messages named `who`) and the ordering of
-// the contexts' streams around the kernels of o[0]
+// ehvi.hip: what ts_hvi.hip shares with the two-objective nomination: the front's check (messages named `who`)
 int front_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref);
-int ehvi_order(b7_ctx *const *o, int n, bool before);
+// context.hip: the streams of a call's contexts o[0 .. n - 1] ordered around the work o[0]'s stream does on the others' buffers
+int streams_order(b7_ctx *const *o, int n, bool before);
 // mes.hip: c->ystar laid out for S samples of M rows at K levels; y* of nS samples (sample s at mu / var + s * stride) searched into
 // slots [slot0, slot0 + nS) of that layout, R + 1 launches; the device address of a slot's K values
 int mes_begin(b7_ctx *c, int S, int64_t M, int K);
@@ -769,7 +789,7 @@ struct BelPass {
 int launch_believer(b7_ctx *c, int S, const BelPass &p, bool column);
 // rff.hip: path j = 0 .. q - 1 in order, each its first minimum over the rows of paths (M x q) that no earlier path took, a NaN never
 // winning, into pmin[j] / taken[j] (0-based) on the device; part: 16 nblk bytes of workspace, nblk <= 1024 blocks per pass
-int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, void *part, int nblk);
+int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, ArgBest *part, int nblk);
 // what the last successful GP b7_ts_nominate / b7_ts_paths left on the device for the paths' refinement (ts_refine.hip): the draws
 // (omega [ns][F][d], phase [F], weight [q][F]), sample s's alpha columns at alpha + s alpha_stride ([Npad][yld], yld = 1 or the
 // sample's columns rounded up to 64; column p is v_j of path j = s + S p).  B7_ERR_STATE if
@@ -781,7 +801,7 @@ struct TsKept {
 };
 int ts_kept(const b7_ctx *c, TsKept *k);
 // ... and path j's alone, over the rows not in taken[0 .. j) (ts_hvi.hip's fallback pick)
-int launch_ts_argmin(b7_ctx *c, const double *paths, int64_t M, int q, int j, double *pmin, long long *taken, void *part, int nblk);
+int launch_ts_argmin(b7_ctx *c, const double *paths, int64_t M, int q, int j, double *pmin, long long *taken, ArgBest *part, int nblk);
 // blr_api.hip: what b7_blr_ts_nominate (blr_ts.hip) shares with the DNGO entry points
 int blr_upload_net(b7_ctx *c, const b7_mlp *net, int *z_out);
 int blr_feat_alloc(b7_ctx *c, int64_t M, int z);

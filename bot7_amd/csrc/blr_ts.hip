@@ -191,8 +191,9 @@ int b7_blr_ts_nominate(b7_ctx *c, const b7_mlp *net, const double *X0, const dou
   if (z > 256) return b7_fail(c, B7_ERR_UNSUPPORTED, "blr: basis width %d > 256", z);
   if (net->dims[0] != c->d) return b7_fail(c, B7_ERR_INVALID, "blr_ts_nominate: network input width %d != grid dims %d", net->dims[0], c->d);
   const int64_t M = c->M;
-  const int zpad = npad_of(c, z), nblk = (int)std::min<int64_t>(1024, (M + 255) / 256);
-  c->ts_valid = false;
+  const int zpad = npad_of(c, z), nblk = argbest_blocks(M);
+  TsPaths &kept = c->ts;
+  kept.who = TS_NONE;
 
   B7_TRY(b7_ensure(c, c->ts_paths, sizeof(double) * (size_t)M * q));
   B7_TRY(b7_ensure(c, c->ts_draw, sizeof(double) * 2 * (size_t)q * z));  // eps [q][z] | weight [q][z]
@@ -211,7 +212,7 @@ int b7_blr_ts_nominate(b7_ctx *c, const b7_mlp *net, const double *X0, const dou
     B7_TRY(launch_mlp_forward(c, (const double *)c->grid[c->grid_cur].p, M, c->d, (const double *)c->netbuf.p, net->dims, net->n_layers,
                               net->activation, (double *)c->feat.p, zpad));
     B7_TRY(launch_blr_paths(c, (const double *)c->feat.p, M, zpad, wfrag, mean0, q, paths));
-    B7_TRY(launch_ts_argmins(c, paths, M, q, pmin, taken, wk + off[4], nblk));
+    B7_TRY(launch_ts_argmins(c, paths, M, q, pmin, taken, reinterpret_cast<ArgBest *>(wk + off[4]), nblk));
     B7_HIP(c, hipMemcpyAsync(path_min, pmin, sizeof(double) * q, hipMemcpyDeviceToHost, c->stream));
     B7_HIP(c, hipMemcpyAsync(tk, taken, sizeof(long long) * q, hipMemcpyDeviceToHost, c->stream));
     B7_HIP(c, hipStreamSynchronize(c->stream));
@@ -248,17 +249,20 @@ int b7_blr_ts_nominate(b7_ctx *c, const b7_mlp *net, const double *X0, const dou
     B7_TRY(tail());
   }
   for (int j = 0; j < q; ++j) best_idx1[j] = tk[j] + 1;
-  c->ts_valid = true, c->ts_blr = true;
-  c->ts_M = M, c->ts_q = q, c->ts_S = S, c->ts_F = z, c->ts_N = 0, c->ts_d = 0;
+  kept.M = M, kept.q = q, kept.S = S, kept.F = z, kept.N = 0, kept.d = 0, kept.ns = S < q ? S : q;
+  kept.epoch = c->epoch;
+  kept.alpha = nullptr, kept.alpha_stride = 0;
+  kept.pmin = pmin, kept.taken = taken, kept.part = reinterpret_cast<ArgBest *>(wk + off[4]), kept.nblk = nblk;
+  kept.who = TS_BLR;
   return B7_OK;
 }
 
 int b7_blr_ts_last_draws(b7_ctx *c, int path, double *eps, double *weight) {
   if (!c) return B7_ERR_INVALID;
-  if (!c->ts_valid || !c->ts_blr) return b7_fail(c, B7_ERR_STATE, "blr_ts_last_draws: no successful b7_blr_ts_nominate on this context");
-  if (path < 0 || path >= c->ts_q) return b7_fail(c, B7_ERR_INVALID, "blr_ts_last_draws: path %d not in [0, %d)", path, c->ts_q);
+  if (ts_state(c) != TS_STATE_BLR) return b7_fail(c, B7_ERR_STATE, "blr_ts_last_draws: no successful b7_blr_ts_nominate on this context");
+  if (path < 0 || path >= c->ts.q) return b7_fail(c, B7_ERR_INVALID, "blr_ts_last_draws: path %d not in [0, %d)", path, c->ts.q);
   B7_HIP(c, hipSetDevice(c->device));
-  const int z = c->ts_F, q = c->ts_q;
+  const int z = c->ts.F, q = c->ts.q;
   const double *e = (const double *)c->ts_draw.p, *w = e + (size_t)q * z;
   if (eps) B7_HIP(c, hipMemcpyAsync(eps, e + (size_t)path * z, sizeof(double) * z, hipMemcpyDeviceToHost, c->stream));
   if (weight) B7_HIP(c, hipMemcpyAsync(weight, w + (size_t)path * z, sizeof(double) * z, hipMemcpyDeviceToHost, c->stream));

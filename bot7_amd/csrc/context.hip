@@ -104,6 +104,26 @@ PhaseScope::~PhaseScope() {
 
 int npad_of(const b7_ctx *c, int64_t n) { return (c->npad_small && n <= 64) ? 64 : (int)round_up(n, B7_NPAD); }
 
+// The streams of the contexts o[0 .. n - 1] of one call, n <= 1 + B7_TS_FEAS_CMAX, ordered by events both ways around the work that
+// o[0]'s stream does on the others' buffers.  before: o[0]'s stream waits for what every other stream has been given (event m - 1 for
+// o[m]: a nomination may return before its stream is formally idle); after: whatever the other contexts enqueue next waits for that
+// work (the last event).  A context that appears twice is waited on once.  The events are o[0]'s, made when first needed.
+int streams_order(b7_ctx *const *o, int n, bool before) {
+  b7_ctx *c = o[0];
+  bool recorded = false;
+  for (int m = 1; m < n; ++m) {
+    bool seen = false;
+    for (int i = 0; i < m; ++i) seen = seen || o[m] == o[i];
+    if (seen) continue;
+    hipEvent_t &e = c->ev_order[before ? m - 1 : B7_TS_FEAS_CMAX];
+    if (!e) B7_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (before || !recorded) B7_HIP(c, hipEventRecord(e, before ? o[m]->stream : c->stream));
+    recorded = true;
+    B7_HIP(c, hipStreamWaitEvent(before ? c->stream : o[m]->stream, e, 0));
+  }
+  return B7_OK;
+}
+
 static int timers_init(b7_ctx *c) {
   if (c->tev_init) return B7_OK;
   for (int i = 0; i < B7_MAX_TIMERS; ++i) {
@@ -215,11 +235,7 @@ void b7_destroy(b7_ctx *c) {
   for (hipEvent_t e : c->free_events) (void)hipEventDestroy(e);
   if (c->phase_e0) (void)hipEventDestroy(c->phase_e0);
   if (c->ev_fit) (void)hipEventDestroy(c->ev_fit);
-  for (hipEvent_t e : c->ev_feas)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ev_ehvi)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ev_ts_feas)
+  for (hipEvent_t e : c->ev_order)
     if (e) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(c->stream);
   delete c;

@@ -145,7 +145,7 @@ int front_defect(const double *front, int P, const double *ref, int *k_out) {
 
 }  // namespace
 
-// front_refuse and ehvi_order are ts_hvi.hip's too (b7_internal.h)
+// front_refuse is ts_hvi.hip's too (b7_internal.h)
 int front_refuse(b7_ctx *c, const char *who, const double *front, int P, const double *ref) {
   if (!ref) return b7_fail(c, B7_ERR_INVALID, "%s: ref is NULL", who);
   if (P < 0 || P > B7_EHVI_PMAX) return b7_fail(c, B7_ERR_INVALID, "%s: a front of %d points (0..%d are built)", who, P, B7_EHVI_PMAX);
@@ -232,34 +232,6 @@ int ehvi2_compute(b7_ctx *c, bool log, const char *who, const double *mu1, const
 
 }  // namespace
 
-// The streams of a nomination's contexts o[0 .. n - 1] are ordered by events both ways, as b7_feas_add_acc orders them.  before: the
-// first context's stream waits for what every other stream has been given (events 0 .. n - 2); after: whatever the other contexts
-// enqueue next waits for the kernels (event n - 1).  A context that appears twice is waited on once.
-int ehvi_order(b7_ctx *const *o, int n, bool before) {
-  b7_ctx *c = o[0];
-  bool wait[3] = {false, false, false}, any = false;
-  for (int m = 1; m < n; ++m) {
-    wait[m] = true;
-    for (int q = 0; q < m; ++q) wait[m] = wait[m] && o[m] != o[q];
-    any = any || wait[m];
-  }
-  if (!any) return B7_OK;
-  if (before) {
-    for (hipEvent_t &e : c->ev_ehvi)
-      if (!e) B7_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (int m = 1; m < n; ++m)
-      if (wait[m]) {
-        B7_HIP(c, hipEventRecord(c->ev_ehvi[m - 1], o[m]->stream));
-        B7_HIP(c, hipStreamWaitEvent(c->stream, c->ev_ehvi[m - 1], 0));
-      }
-  } else {
-    B7_HIP(c, hipEventRecord(c->ev_ehvi[n - 1], c->stream));
-    for (int m = 1; m < n; ++m)
-      if (wait[m]) B7_HIP(c, hipStreamWaitEvent(o[m]->stream, c->ev_ehvi[n - 1], 0));
-  }
-  return B7_OK;
-}
-
 int ehvi_nominate(b7_ctx *const *o, int n, bool log, const char *who, const double *front, int P, const double *ref, double *best_val,
                   int64_t *best_idx1) {
   static const char *const nth[3] = {"first", "second", "third"};
@@ -298,14 +270,14 @@ int ehvi_nominate(b7_ctx *const *o, int n, bool log, const char *who, const doub
   Staged3 st;
   if (n == 2) B7_TRY(front_stage(c, front, P, ref, &fh));
   else stage3_host(front, P, ref, &st);
-  B7_TRY(ehvi_order(o, n, true));
+  B7_TRY(streams_order(o, n, true));
   // the accumulator is declared written (linear: zeros; log space: a log accumulator); the kernel then writes every row of it
   if (log) acc_declare_log_written(c);
   else B7_TRY(acc_write_zeros(c));
   if (n == 3) B7_TRY(launch_ehvi3(c, log, mu, var, S, st, M, acc));
   else if (log) B7_TRY(launch_ehvi2<EhviLog>(c, mu[0], var[0], S[0], mu[1], var[1], S[1], P, M, acc));
   else B7_TRY(launch_ehvi2<EhviLin>(c, mu[0], var[0], S[0], mu[1], var[1], S[1], P, M, acc));
-  B7_TRY(ehvi_order(o, n, false));
+  B7_TRY(streams_order(o, n, false));
   // score:max(1) of the accumulator, the divisor 1 (log space: log 1 == 0 is subtracted); waits, so the staged front is consumed
   return launch_finish(c, acc, M, 1.0, best_val, best_idx1, log);
 }

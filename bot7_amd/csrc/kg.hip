@@ -324,55 +324,20 @@ int launch_kg(b7_ctx *c, int S, const KgPass &p, bool column) {
 }
 
 // ---- the small kernels around it -------------------------------------------------------------------------------------------
-struct KgBest { double v; long long i; };
 struct KgRows { long long row[KL]; };
 
-// a lower marginal mean wins, then the lower index; a NaN counts as +inf, so n <= M rows are always found
-__device__ __forceinline__ bool kg_lower(double v, long long i, double bv, long long bi) {
-  if (i < 0) return false;
-  if (bi < 0) return true;
-  const double x = (v != v) ? INFINITY : v, y = (bv != bv) ? INFINITY : bv;
-  return x < y || (x == y && i < bi);
-}
-__device__ __forceinline__ void kg_block_lowest(double &bv, long long &bi, KgBest *sm) {
-  const int t = threadIdx.x;
-  sm[t].v = bv, sm[t].i = bi;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o && kg_lower(sm[t + o].v, sm[t + o].i, sm[t].v, sm[t].i)) sm[t] = sm[t + o];
-    __syncthreads();
-  }
-  bv = sm[0].v, bi = sm[0].i;
-}
-// pick j of A: the lowest (1/S) sum_s mu_s over the rows not taken by picks 0 .. j-1
-__global__ void __launch_bounds__(256) kg_rows_part_kernel(const double *__restrict__ mu, int S, int64_t M, int j,
-                                                           const long long *__restrict__ taken, KgBest *__restrict__ part) {
-  __shared__ KgBest sm[256];
-  long long tk[KL];
-  for (int i = 0; i < j; ++i) tk[i] = taken[i];
-  double bv = 0.0;
-  long long bi = -1;
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < M; g += (int64_t)gridDim.x * 256) {
-    bool skip = false;
-    for (int i = 0; i < j; ++i) skip = skip || tk[i] == g;
-    if (skip) continue;
+// pick j of A: the lowest (1/S) sum_s mu_s over the rows not taken by picks 0 .. j-1; a lower marginal mean wins, then the lower
+// index; a NaN counts as +inf, so n <= M rows are always found (argbest.h: OrderMinNanInf over this loader)
+struct KgMeanLoad {
+  const double *mu;  // [S][M]
+  int S;
+  long long M;
+  __device__ __forceinline__ double operator()(long long g) const {
     double m = mu[g];
-    for (int s = 1; s < S; ++s) m += mu[(int64_t)s * M + g];
-    m = m / (double)S;
-    if (kg_lower(m, g, bv, bi)) bv = m, bi = g;
+    for (int s = 1; s < S; ++s) m += mu[(long long)s * M + g];
+    return m / (double)S;
   }
-  kg_block_lowest(bv, bi, sm);
-  if (threadIdx.x == 0) part[blockIdx.x].v = bv, part[blockIdx.x].i = bi;
-}
-__global__ void __launch_bounds__(256) kg_rows_final_kernel(const KgBest *__restrict__ part, int nblk, int j, long long *__restrict__ taken) {
-  __shared__ KgBest sm[256];
-  double bv = 0.0;
-  long long bi = -1;
-  for (int b = threadIdx.x; b < nblk; b += 256)
-    if (kg_lower(part[b].v, part[b].i, bv, bi)) bv = part[b].v, bi = part[b].i;
-  kg_block_lowest(bv, bi, sm);
-  if (threadIdx.x == 0) taken[j] = bi;
-}
+};
 // the caller's rows: they travel as a kernel argument (no staging copy)
 __global__ void kg_rows_set_kernel(KgRows r, int n, long long *__restrict__ rows) {
   if ((int)threadIdx.x < n) rows[threadIdx.x] = r.row[threadIdx.x];
@@ -429,13 +394,13 @@ struct KgState {
   double *mu, *var, *v;                      // [S][M] each
   double *kcol, *W, *par, *sa, *ha, *al;     // [KL][S][Npad] x 2, [S][2], [S][KL][dpad], [S][KL] x 2
   long long *rows;                           // [KL]
-  KgBest *part;                              // [nblk]
+  ArgBest *part;                             // [nblk]
   int nblk;
 };
 
 int kg_state(b7_ctx *c, int S, KgState *st) {
   const size_t SM = (size_t)S * c->M, col = (size_t)KL * S * c->Npad;
-  st->nblk = (int)std::min<int64_t>(1024, (c->M + 255) / 256);
+  st->nblk = argbest_blocks(c->M);
   B7_TRY(b7_ensure(c, c->kg, sizeof(double) * 3 * SM));
   B7_TRY(b7_ensure(c, c->kgvec, sizeof(double) * (2 * col + 2 * (size_t)S + (size_t)S * KL * (c->dpad + 2) + KL + 2 * (size_t)st->nblk)));
   B7_TRY(b7_pin_ensure(c, c->pin_kg, sizeof(double) * 2 * (size_t)S, false));
@@ -443,7 +408,7 @@ int kg_state(b7_ctx *c, int S, KgState *st) {
   st->kcol = (double *)c->kgvec.p, st->W = st->kcol + col, st->par = st->W + col, st->sa = st->par + 2 * (size_t)S;
   st->ha = st->sa + (size_t)S * KL * c->dpad, st->al = st->ha + (size_t)S * KL;
   st->rows = reinterpret_cast<long long *>(st->al + (size_t)S * KL);
-  st->part = reinterpret_cast<KgBest *>(st->rows + KL);
+  st->part = reinterpret_cast<ArgBest *>(st->rows + KL);
   return B7_OK;
 }
 
@@ -464,10 +429,8 @@ int kg_enqueue(b7_ctx *c, int S, const b7_hyp *hyps, const double *jit, int n, c
     if (rows0) {
       hipLaunchKernelGGL(kg_rows_set_kernel, dim3(1), dim3(64), 0, c->stream, *rows0, n, st.rows);
     } else {
-      for (int j = 0; j < n; ++j) {
-        hipLaunchKernelGGL(kg_rows_part_kernel, dim3(st.nblk), dim3(256), 0, c->stream, (const double *)st.mu, S, M, j, (const long long *)st.rows, st.part);
-        hipLaunchKernelGGL(kg_rows_final_kernel, dim3(1), dim3(256), 0, c->stream, (const KgBest *)st.part, st.nblk, j, st.rows);
-      }
+      for (int j = 0; j < n; ++j)
+        launch_argbest<OrderMinNanInf>(c->stream, KgMeanLoad{st.mu, S, (long long)M}, (long long)M, st.nblk, st.part, j, st.rows, (double *)nullptr);
     }
     hipLaunchKernelGGL(kg_points_kernel, dim3(S), dim3(256), 0, c->stream, grid, c->d, c->dpad, (const long long *)st.rows, n, keep.fits.w,
                        (const double *)st.mu, M, st.sa, st.ha, st.al);

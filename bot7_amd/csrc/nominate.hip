@@ -448,8 +448,8 @@ int b7_feas_add(b7_ctx *c, const double *logw, int64_t M) {
   return B7_OK;
 }
 
-// L += src's accumulator, device to device.  The two streams are ordered by events both ways: the add waits for what src's stream
-// has been given (b7_eval_nominate may return before its stream is formally idle), and whatever src enqueues next waits for the add.
+// L += src's accumulator, device to device.  The two streams are ordered by events both ways (streams_order): the add waits for what
+// src's stream has been given (b7_eval_nominate may return before its stream is formally idle), and whatever src enqueues next waits for the add.
 int b7_feas_add_acc(b7_ctx *c, b7_ctx *src) {
   if (!c) return B7_ERR_INVALID;
   if (!src) return b7_fail(c, B7_ERR_INVALID, "feas_add_acc: the source context is NULL");
@@ -462,15 +462,10 @@ int b7_feas_add_acc(b7_ctx *c, b7_ctx *src) {
   if (src->acc_fresh) return b7_fail(c, B7_ERR_STATE, "feas_add_acc: the source's log accumulator is declared but nothing has been added onto it");
   if (src->M != c->M)
     return b7_fail(c, B7_ERR_INVALID, "feas_add_acc: the source's grid has %lld rows, this one %lld", (long long)src->M, (long long)c->M);
-  if (src == c) return launch_feas_add(c, (const double *)c->acc.p);
-  for (hipEvent_t &e : c->ev_feas)
-    if (!e) B7_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  B7_HIP(c, hipEventRecord(c->ev_feas[0], src->stream));
-  B7_HIP(c, hipStreamWaitEvent(c->stream, c->ev_feas[0], 0));
+  b7_ctx *const o[2] = {c, src};  // (src == c orders nothing)
+  B7_TRY(streams_order(o, 2, true));
   B7_TRY(launch_feas_add(c, (const double *)src->acc.p));
-  B7_HIP(c, hipEventRecord(c->ev_feas[1], c->stream));
-  B7_HIP(c, hipStreamWaitEvent(src->stream, c->ev_feas[1], 0));
-  return B7_OK;
+  return streams_order(o, 2, false);
 }
 
 int b7_feas_get(b7_ctx *c, double *out) {

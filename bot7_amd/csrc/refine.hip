@@ -244,58 +244,7 @@ __global__ void __launch_bounds__(1024) refine_gather_kernel(const double *__res
 }
 
 // ---- the starts: TH's max over the accumulator, P times, the earlier winners left out ------------------------------------------
-struct RBest { double v; long long i; };
-__device__ __forceinline__ bool rbetter(const RBest &a, const RBest &b) {  // score.hip's ordering: the first NaN wins, ties to the lower row
-  if (b.i < 0) return a.i >= 0;
-  if (a.i < 0) return false;
-  const bool an = a.v != a.v, bn = b.v != b.v;
-  if (an || bn) return an && (!bn || a.i < b.i);
-  return (a.v > b.v) || (a.v == b.v && a.i < b.i);
-}
-__device__ __forceinline__ RBest rblock_best(RBest x, RBest *sh) {
-  for (int o = 32; o > 0; o >>= 1) {
-    RBest y{__shfl_xor(x.v, o), __shfl_xor(x.i, o)};
-    if (rbetter(y, x)) x = y;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = x;
-  __syncthreads();
-  if (wave == 0) {
-    RBest y = (lane < (int)(blockDim.x >> 6)) ? sh[lane] : RBest{0.0, -1};
-    for (int o = 32; o > 0; o >>= 1) {
-      RBest z{__shfl_xor(y.v, o), __shfl_xor(y.i, o)};
-      if (rbetter(z, y)) y = z;
-    }
-    if (lane == 0) sh[0] = y;
-  }
-  __syncthreads();
-  return sh[0];
-}
-// start p: per-block best over the rows that are none of idx[0 .. p)
-__global__ void __launch_bounds__(256) refine_top_part_kernel(const double *__restrict__ acc, long long M, const long long *__restrict__ idx,
-                                                              int p, RBest *__restrict__ part) {
-  __shared__ RBest sh[4];
-  long long ex[B7_REFINE_MAX_STARTS];
-  for (int e = 0; e < B7_REFINE_MAX_STARTS; ++e) ex[e] = (e < p) ? idx[e] : -1;
-  RBest b{0.0, -1};
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    bool out = false;
-    for (int e = 0; e < B7_REFINE_MAX_STARTS; ++e) out = out || ex[e] == j;
-    const RBest cnd{acc[j], j};
-    if (!out && rbetter(cnd, b)) b = cnd;
-  }
-  b = rblock_best(b, sh);
-  if (threadIdx.x == 0) part[blockIdx.x] = b;
-}
-__global__ void __launch_bounds__(256) refine_top_final_kernel(const RBest *__restrict__ part, int n, long long *__restrict__ idx, int p) {
-  __shared__ RBest sh[4];
-  RBest b{0.0, -1};
-  for (int j = threadIdx.x; j < n; j += blockDim.x)
-    if (rbetter(part[j], b)) b = part[j];
-  b = rblock_best(b, sh);
-  if (threadIdx.x == 0) idx[p] = b.i;
-}
+// (argbest.h: OrderMaxNanFirst over acc[row], start p leaving out the rows idx[0 .. p))
 
 // the state of a call before iteration 0: start p at its grid row, and the 64 query rows (every rung at the start itself)
 __global__ void __launch_bounds__(256) refine_init_kernel(RefState *__restrict__ st, const double *__restrict__ grid,
@@ -331,7 +280,7 @@ struct RefWork {
   double *vpart, *cpart;       // [S][nb][64], [S][nb][64][PW]
   double *mu, *var, *dmu, *dvar;  // [S][64], [S][64][d]
   RefState *st;
-  long long *part;             // the top-P partials
+  ArgBest *part;               // the top-P partials
 };
 
 int ref_work(b7_ctx *c, int S, int nparts, RefWork *wk) {
@@ -352,7 +301,7 @@ int ref_work(b7_ctx *c, int S, int nparts, RefWork *wk) {
   wk->xq[0] = b + o_xq0, wk->xq[1] = b + o_xq1, wk->par = b + o_par, wk->box = b + o_box;
   wk->kt = b + o_kt, wk->gt = b + o_gt, wk->V = b + o_V, wk->vpart = b + o_vp, wk->cpart = b + o_cp;
   wk->mu = b + o_mu, wk->var = b + o_var, wk->dmu = b + o_dmu, wk->dvar = b + o_dvar;
-  wk->st = reinterpret_cast<RefState *>(b + o_st), wk->part = reinterpret_cast<long long *>(b + o_part);
+  wk->st = reinterpret_cast<RefState *>(b + o_st), wk->part = reinterpret_cast<ArgBest *>(b + o_part);
   return B7_OK;
 }
 
@@ -463,10 +412,7 @@ int b7_eval_nominate_refine(b7_ctx *c, int S, const b7_hyp *hyps, const b7_score
   {
     PhaseScope ps(c, "refine:starts");
     for (int p = 1; p < P; ++p) {
-      hipLaunchKernelGGL(refine_top_part_kernel, dim3(nparts), dim3(256), 0, c->stream, acc, (long long)c->M, (const long long *)wk.st->idx,
-                         p, reinterpret_cast<RBest *>(wk.part));
-      hipLaunchKernelGGL(refine_top_final_kernel, dim3(1), dim3(256), 0, c->stream, reinterpret_cast<const RBest *>(wk.part), nparts,
-                         wk.st->idx, p);
+      launch_argbest<OrderMaxNanFirst>(c->stream, ArgLoadStrided{acc, 1}, (long long)c->M, nparts, wk.part, p, wk.st->idx, (double *)nullptr);
     }
     hipLaunchKernelGGL(refine_init_kernel, dim3(1), dim3(256), 0, c->stream, wk.st, grid, acc, d, P, opts->eta0, wk.xq[0]);
     B7_HIP(c, hipGetLastError());

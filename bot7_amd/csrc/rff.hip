@@ -218,55 +218,6 @@ __global__ void __launch_bounds__(256) ts_pseudo_kernel(const double *__restrict
   ycols[e] = (y[i] - phiw[e]) - ev;
 }
 
-// ---- the arg-mins ---------------------------------------------------------------------------------------------------------
-// Path j's first minimum over the rows no earlier path of the call took; a NaN does not win.
-struct TsBest { double v; long long i; };
-__device__ __forceinline__ bool ts_better(double av, long long ai, double bv, long long bi) {
-  if (ai < 0) return false;
-  if (bi < 0) return true;
-  const bool an = av != av, bn = bv != bv;
-  if (an != bn) return bn;
-  if (!an && av != bv) return av < bv;
-  return ai < bi;
-}
-__device__ __forceinline__ void ts_block_reduce(double &v, long long &i, TsBest *sm) {
-  const int t = threadIdx.x;
-  sm[t].v = v, sm[t].i = i;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s && ts_better(sm[t + s].v, sm[t + s].i, sm[t].v, sm[t].i)) sm[t] = sm[t + s];
-    __syncthreads();
-  }
-  v = sm[0].v, i = sm[0].i;
-}
-__global__ void __launch_bounds__(256) ts_argmin_part_kernel(const double *__restrict__ paths, int64_t M, int q, int j,
-                                                             const long long *__restrict__ taken, TsBest *__restrict__ part) {
-  __shared__ TsBest sm[256];
-  long long tk[B7_BATCH_MAX];
-  for (int i = 0; i < j; ++i) tk[i] = taken[i];
-  double bv = 0.0;
-  long long bi = -1;
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < M; g += (int64_t)gridDim.x * 256) {
-    bool skip = false;
-    for (int i = 0; i < j; ++i) skip = skip || tk[i] == g;
-    if (skip) continue;
-    const double v = paths[g * q + j];
-    if (ts_better(v, g, bv, bi)) bv = v, bi = g;
-  }
-  ts_block_reduce(bv, bi, sm);
-  if (threadIdx.x == 0) part[blockIdx.x].v = bv, part[blockIdx.x].i = bi;
-}
-__global__ void __launch_bounds__(256) ts_argmin_final_kernel(const TsBest *__restrict__ part, int nblk, int j, long long *__restrict__ taken,
-                                                              double *__restrict__ pmin) {
-  __shared__ TsBest sm[256];
-  double bv = 0.0;
-  long long bi = -1;
-  for (int b = threadIdx.x; b < nblk; b += 256)
-    if (ts_better(part[b].v, part[b].i, bv, bi)) bv = part[b].v, bi = part[b].i;
-  ts_block_reduce(bv, bi, sm);
-  if (threadIdx.x == 0) taken[j] = bi, pmin[j] = bv;
-}
-
 template <int DPAD>
 void rff_launch_class(b7_ctx *c, const double *X, int64_t M, int d, const double *omf, const double *phase, const double *wf, int F,
                       const double *base, int ldb, double *out, int ldo, int ocol0, int ostride, int qn) {
@@ -327,8 +278,8 @@ int ts_mean_over_grid(b7_ctx *c) {
 // c->ts_work: one hyper sample's operands, each piece on a 256-byte boundary (the multi-column mean reads alpha in 16-byte pairs):
 // omf F dpad | wf 16 F | phiw N qmax | ycols np qmax | alpha np yldmax | resid np qmax | inv_ls d | pmin q | taken q | part 2 nblk
 // Every hyper sample's alpha is kept (ns of them, sample s at alpha + s np yldmax): column p of sample s is v_j of path j = s + S p,
-// which the refinement of the paths (ts_refine.hip, through ts_kept) and b7dbg_ts_alpha read.
-constexpr int TS_ALPHA_PIECE = 4;
+// which the refinement of the paths (ts_refine.hip, through ts_kept) and b7dbg_ts_alpha read.  ts_paths_core carves the buffer with
+// this, once, and records where alpha, pmin, taken and part lie in c->ts: nobody else derives the layout.
 void ts_work_layout(int F, int dpad, int N, int np, int qmax, int yldmax, int d, int q, int nblk, int ns, size_t off[11]) {
   const size_t nalpha = (size_t)ns;
   const size_t pieces[10] = {(size_t)F * dpad, 16 * (size_t)F, (size_t)N * qmax, (size_t)np * qmax, nalpha * np * yldmax, (size_t)np * qmax,
@@ -352,15 +303,14 @@ struct YSwap {
 
 }  // namespace
 
-int launch_ts_argmin(b7_ctx *c, const double *paths, int64_t M, int q, int j, double *pmin, long long *taken, void *part, int nblk) {
-  hipLaunchKernelGGL(ts_argmin_part_kernel, dim3(nblk), dim3(256), 0, c->stream, paths, M, q, j, (const long long *)taken,
-                     static_cast<TsBest *>(part));
-  hipLaunchKernelGGL(ts_argmin_final_kernel, dim3(1), dim3(256), 0, c->stream, (const TsBest *)part, nblk, j, taken, pmin);
+// ---- the arg-mins: path j's first minimum over the rows no earlier path of the call took; a NaN does not win (argbest.h) ----
+int launch_ts_argmin(b7_ctx *c, const double *paths, int64_t M, int q, int j, double *pmin, long long *taken, ArgBest *part, int nblk) {
+  launch_argbest<OrderMinNanLast>(c->stream, ArgLoadStrided{paths + j, q}, (long long)M, nblk, part, j, taken, pmin);
   B7_HIP(c, hipGetLastError());
   return B7_OK;
 }
 
-int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, void *part, int nblk) {
+int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *pmin, long long *taken, ArgBest *part, int nblk) {
   PhaseScope ps(c, "ts_argmin");
   for (int j = 0; j < q; ++j) B7_TRY(launch_ts_argmin(c, paths, M, q, j, pmin, taken, part, nblk));
   return B7_OK;
@@ -368,34 +318,22 @@ int launch_ts_argmins(b7_ctx *c, const double *paths, int64_t M, int q, double *
 
 // What the last GP paths left for their refinement: the draws and every path's v_j (b7_internal.h: TsKept)
 int ts_kept(const b7_ctx *c, TsKept *k) {
-  const int q = c->ts_q, S = c->ts_S, F = c->ts_F, N = c->ts_N, d = c->ts_d, np = c->Npad, ns = S < q ? S : q;
-  const int qmax = (q + ns - 1) / ns, yldmax = qmax == 1 ? 1 : (int)round_up(qmax, 64);
-  const int nblk = (int)std::min<int64_t>(1024, (c->ts_M + 255) / 256);
-  size_t off[11];
-  ts_work_layout(F, rff_dpad(d), N, np, qmax, yldmax, d, q, nblk, ns, off);
-  if (!c->ts_work.p || c->ts_work.cap < sizeof(double) * off[10] || c->ts_hyp.size() != (size_t)ns * (d + 3)) return B7_ERR_STATE;
-  const TsDraws dr = ts_draws(c, ns, q, F, d, N);
+  const TsPaths &t = c->ts;
+  if (t.who != TS_GP) return B7_ERR_STATE;
+  const TsDraws dr = ts_draws(c, t.ns, t.q, t.F, t.d, t.N);
   k->omega = dr.omega, k->phase = dr.phase, k->weight = dr.weight;
-  k->alpha = (const double *)c->ts_work.p + off[TS_ALPHA_PIECE], k->alpha_stride = (int64_t)np * yldmax;
-  k->ns = ns;
+  k->alpha = t.alpha, k->alpha_stride = t.alpha_stride;
+  k->ns = t.ns;
   return B7_OK;
 }
 
 namespace {
 
-// What the paths core leaves for the arg-mins: the paths and the pieces of c->ts_work they use
-struct TsArgminWork {
-  double *paths, *pmin;
-  long long *taken;
-  TsBest *part;
-  int nblk;
-};
-
 // The path half of a Thompson nomination, b7_ts_nominate's and b7_ts_paths' (`who` in the messages): validation, draws, one fit per
-// hyper sample and the paths over the grid into c->ts_paths ([M][q]); the context remembers their shapes and its epoch.  null_out:
+// hyper sample and the paths over the grid into c->ts_paths ([M][q]); c->ts records what they are and where their pieces lie.  null_out:
 // an output of the entry's own is missing (answered in its place among the checks); what: the arguments the entry needs, for that message.
 int ts_paths_core(b7_ctx *c, const char *who, bool null_out, const char *what, int S, const b7_hyp *hyps, int q, int F, uint64_t seed,
-                  double *jitter_out, int *info_out, TsArgminWork *aw) {
+                  double *jitter_out, int *info_out) {
   if (c->group) return b7_fail(c, B7_ERR_STATE, "%s: this context belongs to a group (sharded Thompson sampling is not built)", who);
   if (q < 1 || q > B7_BATCH_MAX) return b7_fail(c, B7_ERR_INVALID, "%s: q = %d not in [1, %d]", who, q, B7_BATCH_MAX);
   if (F < 16 || F > B7_TS_MAX_FEATURES || F % 16)
@@ -415,17 +353,18 @@ int ts_paths_core(b7_ctx *c, const char *who, bool null_out, const char *what, i
   const int64_t M = c->M;
   if (jitter_out) std::fill(jitter_out, jitter_out + S, 0.0);
   if (info_out) std::fill(info_out, info_out + S, 0);
-  c->ts_valid = false, c->ts_blr = false;
-  c->ts_hyp.resize((size_t)ns * (d + 3));  // the hyper samples the paths are drawn under, for the paths' refinement
+  TsPaths &t = c->ts;
+  t.who = TS_NONE;
+  t.hyp.resize((size_t)ns * (d + 3));  // the hyper samples the paths are drawn under, for the paths' refinement
   for (int s = 0; s < ns; ++s) {
-    double *hs = &c->ts_hyp[(size_t)s * (d + 3)];
+    double *hs = &t.hyp[(size_t)s * (d + 3)];
     std::copy(hyps[s].lenscale_sq, hyps[s].lenscale_sq + d, hs);
     hs[d] = hyps[s].amp, hs[d + 1] = hyps[s].noise, hs[d + 2] = hyps[s].mean;
   }
 
   // device memory beyond the posterior's own: the paths (M x q), the draws, and the operands of one hyper sample
   const int qmax = (q + ns - 1) / ns, yldmax = qmax == 1 ? 1 : (int)round_up(qmax, 64);
-  const int nblk = (int)std::min<int64_t>(1024, (M + 255) / 256);
+  const int nblk = argbest_blocks(M);
   B7_TRY(b7_ensure(c, c->ts_paths, sizeof(double) * (size_t)M * q));
   B7_TRY(b7_ensure(c, c->ts_draw, sizeof(double) * ((size_t)ns * F * d + F + (size_t)q * F + (size_t)q * N)));
   size_t off[11];
@@ -434,9 +373,7 @@ int ts_paths_core(b7_ctx *c, const char *who, bool null_out, const char *what, i
   const TsDraws dr = ts_draws(c, ns, q, F, d, N);
   double *wk = (double *)c->ts_work.p;
   double *omf = wk + off[0], *wf = wk + off[1], *phiw = wk + off[2], *ycols = wk + off[3], *alpha = wk + off[4], *resid = wk + off[5];
-  double *inv_ls = wk + off[6], *pmin = wk + off[7];
-  long long *taken = reinterpret_cast<long long *>(wk + off[8]);
-  TsBest *part = reinterpret_cast<TsBest *>(wk + off[9]);
+  double *inv_ls = wk + off[6];
   double *paths = (double *)c->ts_paths.p;
   const double *grid = (const double *)c->grid[c->grid_cur].p;
 
@@ -484,12 +421,69 @@ int ts_paths_core(b7_ctx *c, const char *who, bool null_out, const char *what, i
       B7_TRY(launch_rff(c, grid, M, d, omf, dr.phase, wf, F, (const double *)c->mu.p, qs, paths, q, s, S, qs));
     }
   }
-  c->ts_valid = true;
-  c->ts_M = M, c->ts_q = q, c->ts_S = S, c->ts_F = F, c->ts_N = N, c->ts_d = d;
-  c->ts_epoch = c->epoch;
-  aw->paths = paths, aw->pmin = pmin, aw->taken = taken, aw->part = part, aw->nblk = nblk;
+  t.M = M, t.q = q, t.S = S, t.F = F, t.N = N, t.d = d, t.ns = ns;
+  t.epoch = c->epoch;
+  t.alpha = alpha, t.alpha_stride = (int64_t)np * yldmax;
+  t.pmin = wk + off[7], t.taken = reinterpret_cast<long long *>(wk + off[8]), t.part = reinterpret_cast<ArgBest *>(wk + off[9]), t.nblk = nblk;
+  t.who = TS_GP;
   return B7_OK;
 }
+
+#ifdef B7_DIAG
+// b7dbg_argbest_loop's kernel: n <= 16 successive picks by ONE workgroup that calls block_best in a loop, a barrier ahead of every
+// call, each pick leaving out the earlier ones
+template <class Order>
+__global__ void __launch_bounds__(256) dbg_argbest_loop_kernel(const double *__restrict__ v, long long M, int n, long long *__restrict__ taken,
+                                                               double *__restrict__ val) {
+  __shared__ ArgBest sh[4];
+  long long ex[ARGBEST_MAX_EXCL];
+  argbest_load_excl(nullptr, 0, ex);
+  for (int p = 0; p < n; ++p) {
+    ArgBest b{0.0, -1};
+    for (long long r = threadIdx.x; r < M; r += 256) {
+      const ArgBest cnd{v[r], r};
+      if (argbest_excluded(ex, r) || (Order::skips_nan && cnd.v != cnd.v)) continue;
+      if (Order()(cnd, b)) b = cnd;
+    }
+    __syncthreads();  // sh is free again
+    b = block_best<Order>(b, sh);
+#pragma unroll
+    for (int e = 0; e < ARGBEST_MAX_EXCL; ++e) ex[e] = (e == p) ? b.i : ex[e];  // (ex stays in registers)
+    if (threadIdx.x == 0) taken[p] = b.i, val[p] = b.v;
+  }
+}
+// both diagnostic entries: values M | taken 32 | val 32 | part 2 x 1024 on b7_rff_compute's staging buffer
+int dbg_argbest_run(b7_ctx *c, int order, const double *values, int64_t M, const long long *excl, int n, bool loop, double *val_out,
+                    long long *row_out) {
+  if (!c || !values || M < 1 || n < (loop ? 1 : 0) || n > ARGBEST_MAX_EXCL || (!loop && n > 0 && !excl) || !val_out || !row_out) return B7_ERR_INVALID;
+  B7_HIP(c, hipSetDevice(c->device));
+  const size_t m = (size_t)round_up(M, 32);
+  B7_TRY(b7_ensure(c, c->ts_user, sizeof(double) * (m + 64 + 2 * 1024)));
+  double *vd = (double *)c->ts_user.p, *val = vd + m + 32;
+  long long *taken = reinterpret_cast<long long *>(vd + m);
+  B7_HIP(c, hipMemcpyAsync(vd, values, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+  if (!loop && n > 0) B7_HIP(c, hipMemcpyAsync(taken, excl, sizeof(long long) * n, hipMemcpyHostToDevice, c->stream));
+  auto run = [&](auto ord) {
+    using Order = decltype(ord);
+    if (loop) hipLaunchKernelGGL(dbg_argbest_loop_kernel<Order>, dim3(1), dim3(256), 0, c->stream, (const double *)vd, (long long)M, n, taken, val);
+    else launch_argbest<Order>(c->stream, ArgLoadStrided{vd, 1}, (long long)M, argbest_blocks(M), reinterpret_cast<ArgBest *>(vd + m + 64), n, taken, val);
+  };
+  switch (order) {
+    case 0: run(OrderMaxNanFirst()); break;
+    case 1: run(OrderMinNanLast()); break;
+    case 2: run(OrderMaxNoNan()); break;
+    case 3: run(OrderMinNanInf()); break;
+    case 4: run(OrderMin()); break;
+    default: return B7_ERR_INVALID;
+  }
+  B7_HIP(c, hipGetLastError());
+  const int k0 = loop ? 0 : n, cnt = loop ? n : 1;  // one pass leaves pick n_excl; the loop leaves picks 0 .. n - 1
+  B7_HIP(c, hipMemcpyAsync(val_out, val + k0, sizeof(double) * cnt, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipMemcpyAsync(row_out, taken + k0, sizeof(long long) * cnt, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipStreamSynchronize(c->stream));
+  return B7_OK;
+}
+#endif
 
 }  // namespace
 
@@ -498,24 +492,23 @@ extern "C" {
 int b7_ts_nominate(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *path_min, int64_t *best_idx1,
                    double *jitter_out, int *info_out) {
   if (!c) return B7_ERR_INVALID;
-  TsArgminWork aw;
   B7_TRY(ts_paths_core(c, "ts_nominate", !path_min || !best_idx1, "hyps, path_min and best_idx1 are needed", S, hyps, q, F, seed, jitter_out,
-                       info_out, &aw));
-  c->ts_valid = false;  // until the arg-mins have come back
-  B7_TRY(launch_ts_argmins(c, aw.paths, c->ts_M, q, aw.pmin, aw.taken, aw.part, aw.nblk));
+                       info_out));
+  TsPaths &t = c->ts;
+  t.who = TS_NONE;  // until the arg-mins have come back
+  B7_TRY(launch_ts_argmins(c, (const double *)c->ts_paths.p, t.M, q, t.pmin, t.taken, t.part, t.nblk));
   long long tk[B7_BATCH_MAX];
-  B7_HIP(c, hipMemcpyAsync(path_min, aw.pmin, sizeof(double) * q, hipMemcpyDeviceToHost, c->stream));
-  B7_HIP(c, hipMemcpyAsync(tk, aw.taken, sizeof(long long) * q, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipMemcpyAsync(path_min, t.pmin, sizeof(double) * q, hipMemcpyDeviceToHost, c->stream));
+  B7_HIP(c, hipMemcpyAsync(tk, t.taken, sizeof(long long) * q, hipMemcpyDeviceToHost, c->stream));
   B7_HIP(c, hipStreamSynchronize(c->stream));
   for (int j = 0; j < q; ++j) best_idx1[j] = tk[j] + 1;
-  c->ts_valid = true;
+  t.who = TS_GP;
   return B7_OK;
 }
 
 int b7_ts_paths(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t seed, double *jitter_out, int *info_out) {
   if (!c) return B7_ERR_INVALID;
-  TsArgminWork aw;
-  B7_TRY(ts_paths_core(c, "ts_paths", false, "hyps is needed", S, hyps, q, F, seed, jitter_out, info_out, &aw));
+  B7_TRY(ts_paths_core(c, "ts_paths", false, "hyps is needed", S, hyps, q, F, seed, jitter_out, info_out));
   B7_HIP(c, hipStreamSynchronize(c->stream));  // the fits' reports (jitter_out, info_out) are complete and the paths stand
   return B7_OK;
 }
@@ -523,22 +516,24 @@ int b7_ts_paths(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, uint64_t see
 int b7_ts_last_paths(b7_ctx *c, double *paths_host) {
   if (!c) return B7_ERR_INVALID;
   if (!paths_host) return b7_fail(c, B7_ERR_INVALID, "ts_last_paths: NULL argument");
-  if (!c->ts_valid) return b7_fail(c, B7_ERR_STATE, "ts_last_paths: no successful b7_ts_nominate or b7_ts_paths on this context");
-  B7_HIP(c, hipSetDevice(c->device));
-  B7_HIP(c, hipMemcpyAsync(paths_host, c->ts_paths.p, sizeof(double) * (size_t)c->ts_M * c->ts_q, hipMemcpyDeviceToHost, c->stream));
+  if (ts_state(c) == TS_STATE_NONE) return b7_fail(c, B7_ERR_STATE, "ts_last_paths: no successful b7_ts_nominate or b7_ts_paths on this context");
+  B7_HIP(c, hipSetDevice(c->device));  // (stale paths are served too)
+  B7_HIP(c, hipMemcpyAsync(paths_host, c->ts_paths.p, sizeof(double) * (size_t)c->ts.M * c->ts.q, hipMemcpyDeviceToHost, c->stream));
   B7_HIP(c, hipStreamSynchronize(c->stream));
   return B7_OK;
 }
 
 int b7_ts_last_draws(b7_ctx *c, int path, double *omega, double *phase, double *weight, double *eps) {
   if (!c) return B7_ERR_INVALID;
-  if (!c->ts_valid) return b7_fail(c, B7_ERR_STATE, "ts_last_draws: no successful b7_ts_nominate or b7_ts_paths on this context");
-  if (c->ts_blr) return b7_fail(c, B7_ERR_STATE, "ts_last_draws: the last nomination was b7_blr_ts_nominate's (b7_blr_ts_last_draws reads its draws)");
-  if (path < 0 || path >= c->ts_q) return b7_fail(c, B7_ERR_INVALID, "ts_last_draws: path %d not in [0, %d)", path, c->ts_q);
+  const TsPaths &t = c->ts;
+  const int state = ts_state(c);
+  if (state == TS_STATE_NONE) return b7_fail(c, B7_ERR_STATE, "ts_last_draws: no successful b7_ts_nominate or b7_ts_paths on this context");
+  if (state == TS_STATE_BLR) return b7_fail(c, B7_ERR_STATE, "ts_last_draws: the last nomination was b7_blr_ts_nominate's (b7_blr_ts_last_draws reads its draws)");
+  if (path < 0 || path >= t.q) return b7_fail(c, B7_ERR_INVALID, "ts_last_draws: path %d not in [0, %d)", path, t.q);
   B7_HIP(c, hipSetDevice(c->device));
-  const int F = c->ts_F, d = c->ts_d, N = c->ts_N, ns = c->ts_S < c->ts_q ? c->ts_S : c->ts_q;
-  const TsDraws dr = ts_draws(c, ns, c->ts_q, F, d, N);
-  if (omega) B7_HIP(c, hipMemcpyAsync(omega, dr.omega + (size_t)(path % c->ts_S) * F * d, sizeof(double) * (size_t)F * d, hipMemcpyDeviceToHost, c->stream));
+  const int F = t.F, d = t.d, N = t.N;
+  const TsDraws dr = ts_draws(c, t.ns, t.q, F, d, N);
+  if (omega) B7_HIP(c, hipMemcpyAsync(omega, dr.omega + (size_t)(path % t.S) * F * d, sizeof(double) * (size_t)F * d, hipMemcpyDeviceToHost, c->stream));
   if (phase) B7_HIP(c, hipMemcpyAsync(phase, dr.phase, sizeof(double) * F, hipMemcpyDeviceToHost, c->stream));
   if (weight) B7_HIP(c, hipMemcpyAsync(weight, dr.weight + (size_t)path * F, sizeof(double) * F, hipMemcpyDeviceToHost, c->stream));
   if (eps) B7_HIP(c, hipMemcpyAsync(eps, dr.eps + (size_t)path * N, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
@@ -550,20 +545,25 @@ int b7_ts_last_draws(b7_ctx *c, int path, double *omega, double *phase, double *
 // diagnostic build only: the alpha columns (N x qs, row-major; qs = the paths j = s, s + S, .. < q) of hyper sample s's
 // pseudo-response fit in the last b7_ts_nominate; *qs_out (nullable) receives qs
 int b7dbg_ts_alpha(b7_ctx *c, int s, double *out_host, int *qs_out) {
-  if (!c || !out_host || !c->ts_valid || c->ts_N != c->N) return B7_ERR_INVALID;
-  const int q = c->ts_q, S = c->ts_S, F = c->ts_F, N = c->ts_N, d = c->ts_d, np = c->Npad, ns = S < q ? S : q;
-  if (s < 0 || s >= ns) return B7_ERR_INVALID;
-  const int qmax = (q + ns - 1) / ns, yldmax = qmax == 1 ? 1 : (int)round_up(qmax, 64);
-  const int nblk = (int)std::min<int64_t>(1024, (c->ts_M + 255) / 256);
-  const int qs = (q - s + S - 1) / S, yld = qs == 1 ? 1 : (int)round_up(qs, 64);
-  size_t off[11];
-  ts_work_layout(F, rff_dpad(d), N, np, qmax, yldmax, d, q, nblk, ns, off);
-  if (!c->ts_work.p || c->ts_work.cap < sizeof(double) * off[10]) return B7_ERR_INVALID;
-  const double *alpha = (const double *)c->ts_work.p + off[TS_ALPHA_PIECE] + (size_t)s * np * yldmax;
+  if (!c || !out_host || c->ts.who != TS_GP || c->ts.N != c->N) return B7_ERR_INVALID;
+  const TsPaths &t = c->ts;
+  if (s < 0 || s >= t.ns) return B7_ERR_INVALID;
+  const int qs = (t.q - s + t.S - 1) / t.S, yld = qs == 1 ? 1 : (int)round_up(qs, 64);
+  const double *alpha = t.alpha + (size_t)s * t.alpha_stride;
   B7_HIP(c, hipStreamSynchronize(c->stream));
-  B7_HIP(c, hipMemcpy2D(out_host, sizeof(double) * qs, alpha, sizeof(double) * yld, sizeof(double) * qs, N, hipMemcpyDeviceToHost));
+  B7_HIP(c, hipMemcpy2D(out_host, sizeof(double) * qs, alpha, sizeof(double) * yld, sizeof(double) * qs, t.N, hipMemcpyDeviceToHost));
   if (qs_out) *qs_out = qs;
   return B7_OK;
+}
+
+// diagnostic build only: argbest.h on the caller's values[M].  order: 0 OrderMaxNanFirst, 1 OrderMinNanLast, 2 OrderMaxNoNan,
+// 3 OrderMinNanInf, 4 OrderMin.  b7dbg_argbest: one pass of the shared part kernel and the final kernel with the rows excl[0 .. n_excl)
+// left out, n_excl <= 16: *row (-1: none) and *value.  b7dbg_argbest_loop: n <= 16 successive picks in one launch (above)
+int b7dbg_argbest(b7_ctx *c, int order, const double *values, int64_t M, const long long *excl, int n_excl, double *value, long long *row) {
+  return dbg_argbest_run(c, order, values, M, excl, n_excl, false, value, row);
+}
+int b7dbg_argbest_loop(b7_ctx *c, int order, const double *values, int64_t M, int n, double *values_out, long long *rows_out) {
+  return dbg_argbest_run(c, order, values, M, nullptr, n, true, values_out, rows_out);
 }
 #endif
 

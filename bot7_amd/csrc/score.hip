@@ -453,64 +453,31 @@ __global__ void __launch_bounds__(256) fill_kernel(double *__restrict__ p, int64
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) p[j] = v;
 }
 
-// (value, index) ordering of TH's max: the first NaN wins; otherwise the larger value; ties -> lower index.
-struct Best {
-  double v;
-  int64_t i;
-};
-static_assert(sizeof(Best) == sizeof(BestPair) && offsetof(Best, i) == offsetof(BestPair, i), "PinnedBlock::best holds a Best");
-__device__ __forceinline__ bool better(const Best &a, const Best &b) {  // is a strictly preferred to b
-  if (b.i < 0) return a.i >= 0;
-  if (a.i < 0) return false;
-  const bool an = a.v != a.v, bn = b.v != b.v;
-  if (an || bn) return an && (!bn || a.i < b.i);
-  return (a.v > b.v) || (a.v == b.v && a.i < b.i);
-}
-__device__ __forceinline__ Best wave_best(Best x) {
-  for (int o = 32; o > 0; o >>= 1) {
-    Best y;
-    y.v = __shfl_xor(x.v, o);
-    y.i = __shfl_xor(x.i, o);
-    if (better(y, x)) x = y;
-  }
-  return x;
-}
-__device__ __forceinline__ Best block_best(Best x, Best *sh) {
-  x = wave_best(x);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = x;
-  __syncthreads();
-  if (wave == 0) {
-    Best y = (lane < (int)(blockDim.x >> 6)) ? sh[lane] : Best{0.0, -1};
-    y = wave_best(y);
-    if (lane == 0) sh[0] = y;
-  }
-  __syncthreads();
-  return sh[0];
-}
+// (value, index) ordering of TH's max: the first NaN wins; otherwise the larger value; ties -> lower index (argbest.h).
+using Better = OrderMaxNanFirst;  // Better()(a, b): is a strictly preferred to b
 
 // acc[j] /= divisor (score:div; a log accumulator: acc[j] -= log(divisor)), then per-block best.
 __global__ void __launch_bounds__(256)
-    finish_kernel(double *__restrict__ acc, int64_t M, double divisor, Best *__restrict__ part, int logacc) {
-  __shared__ Best sh[4];
-  Best b{0.0, -1};
+    finish_kernel(double *__restrict__ acc, int64_t M, double divisor, ArgBest *__restrict__ part, int logacc) {
+  __shared__ ArgBest sh[4];
+  ArgBest b{0.0, -1};
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
     double v = logacc ? acc[j] + (-log(divisor)) : acc[j] / divisor;
     acc[j] = v;
-    Best cnd{v, j};
-    if (better(cnd, b)) b = cnd;
+    ArgBest cnd{v, j};
+    if (Better()(cnd, b)) b = cnd;
   }
-  b = block_best(b, sh);
+  b = block_best<Better>(b, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = b;
 }
 
-__global__ void __launch_bounds__(256) argmax_final_kernel(const Best *__restrict__ part, int n, Best *__restrict__ out) {
-  __shared__ Best sh[4];
-  Best b{0.0, -1};
+__global__ void __launch_bounds__(256) argmax_final_kernel(const ArgBest *__restrict__ part, int n, ArgBest *__restrict__ out) {
+  __shared__ ArgBest sh[4];
+  ArgBest b{0.0, -1};
   for (int j = threadIdx.x; j < n; j += blockDim.x)
-    if (better(part[j], b)) b = part[j];
-  b = block_best(b, sh);
+    if (Better()(part[j], b)) b = part[j];
+  b = block_best<Better>(b, sh);
   if (threadIdx.x == 0) out[0] = b;
 }
 
@@ -519,7 +486,7 @@ __global__ void __launch_bounds__(256) argmax_final_kernel(const Best *__restric
 // zeroed as well (comm.hip sums the tables of all ranks); a single-process group merges records on the host and needs
 // only this one.
 // this rank's record (and, with all_slots, zeros for every other rank's) from the local best b; every thread of the block calls
-__device__ __forceinline__ void write_record(Best b, unsigned long long *__restrict__ tab, int rank, int world, long long offset,
+__device__ __forceinline__ void write_record(ArgBest b, unsigned long long *__restrict__ tab, int rank, int world, long long offset,
                                              long long rows, const double *__restrict__ grid, int d, int all_slots,
                                              unsigned long long *__restrict__ host_rec, unsigned *__restrict__ host_done) {
   if (all_slots)
@@ -546,32 +513,32 @@ __device__ __forceinline__ void write_record(Best b, unsigned long long *__restr
   }
 }
 
-__global__ void __launch_bounds__(256) argmax_slot_kernel(const Best *__restrict__ part, int n, unsigned long long *__restrict__ tab,
+__global__ void __launch_bounds__(256) argmax_slot_kernel(const ArgBest *__restrict__ part, int n, unsigned long long *__restrict__ tab,
                                                           int rank, int world, long long offset, long long rows,
                                                           const double *__restrict__ grid, int d, int all_slots,
                                                           long long forced_local, unsigned long long *__restrict__ host_rec,
                                                           unsigned *__restrict__ host_done) {
-  __shared__ Best sh[4];
-  Best b{0.0, -1};
+  __shared__ ArgBest sh[4];
+  ArgBest b{0.0, -1};
   if (n > 0) {
     for (int j = threadIdx.x; j < n; j += blockDim.x)
-      if (better(part[j], b)) b = part[j];
-    b = block_best(b, sh);
+      if (Better()(part[j], b)) b = part[j];
+    b = block_best<Better>(b, sh);
   } else if (forced_local >= 0) {  // no scores: the record names a given row (b7_nominate_commit's broadcast)
-    b = Best{0.0, forced_local};
+    b = ArgBest{0.0, forced_local};
   }
   write_record(b, tab, rank, world, offset, rows, grid, d, all_slots, host_rec, host_done);
 }
 
 // The tail of the fused nomination kernel: per-block best, and the LAST block to arrive (a ticket from one atomic counter; every
 // block's partial is fenced before its ticket) reduces the partials and writes the record.
-// Every thread of the block calls; sh: 4 Best, last: one word, both in LDS.
-__device__ __forceinline__ void block_best_ticket_record(Best b, Best *sh, unsigned *last, Best *__restrict__ part,
+// Every thread of the block calls; sh: 4 ArgBest, last: one word, both in LDS.
+__device__ __forceinline__ void block_best_ticket_record(ArgBest b, ArgBest *sh, unsigned *last, ArgBest *__restrict__ part,
                                                          unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank,
                                                          int world, long long offset, long long M, const double *__restrict__ grid, int d,
                                                          int all_slots, unsigned long long *__restrict__ host_rec,
                                                          unsigned *__restrict__ host_done) {
-  b = block_best(b, sh);
+  b = block_best<Better>(b, sh);
   if (threadIdx.x == 0) {
     part[blockIdx.x] = b;
     __threadfence();  // the partial is visible device-wide before the ticket is taken
@@ -581,15 +548,15 @@ __device__ __forceinline__ void block_best_ticket_record(Best b, Best *sh, unsig
   __syncthreads();
   if (!*last) return;
   __threadfence();  // the other blocks' partials, published before their tickets
-  Best f{0.0, -1};
+  ArgBest f{0.0, -1};
   for (int j = threadIdx.x; j < (int)gridDim.x; j += blockDim.x) {
-    Best pj;  // agent-scope loads: the partials of other CUs, not a stale line of this CU's cache
+    ArgBest pj;  // agent-scope loads: the partials of other CUs, not a stale line of this CU's cache
     pj.v = __hip_atomic_load(&part[j].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     pj.i = __hip_atomic_load(&part[j].i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (better(pj, f)) f = pj;
+    if (Better()(pj, f)) f = pj;
   }
   __syncthreads();
-  f = block_best(f, sh);
+  f = block_best<Better>(f, sh);
   if (threadIdx.x == 0) *ticket = 0u;  // ready for the next launch (stream order: nobody else touches it meanwhile)
   write_record(f, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
 }
@@ -601,19 +568,19 @@ __device__ __forceinline__ void block_best_ticket_record(Best b, Best *sh, unsig
 // registers of the EI and CB ones.)
 template <int K>
 __global__ void __launch_bounds__(256)
-    score_finish_slot_kernel(ScoreParams p, int fresh, double *__restrict__ acc, long long M, double divisor, Best *__restrict__ part,
+    score_finish_slot_kernel(ScoreParams p, int fresh, double *__restrict__ acc, long long M, double divisor, ArgBest *__restrict__ part,
                              unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank, int world, long long offset,
                              const double *__restrict__ grid, int d, int all_slots, unsigned long long *__restrict__ host_rec,
                              unsigned *__restrict__ host_done) {
-  __shared__ Best sh[4];
+  __shared__ ArgBest sh[4];
   __shared__ unsigned last;
-  Best b{0.0, -1};
+  ArgBest b{0.0, -1};
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
     const double v = div<K>(fold_samples<K>(p, j, fresh ? empty<K>() : acc[j]), divisor);
     acc[j] = v;
-    Best cnd{v, j};
-    if (better(cnd, b)) b = cnd;
+    ArgBest cnd{v, j};
+    if (Better()(cnd, b)) b = cnd;
   }
   block_best_ticket_record(b, sh, &last, part, ticket, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
 }
@@ -622,21 +589,21 @@ __global__ void __launch_bounds__(256)
 // written like any other; only the candidate for the block reduction is withheld, so a NaN there does not win.
 template <int K>
 __global__ void __launch_bounds__(256)
-    score_finish_slot_excl_kernel(ScoreParams p, int fresh, double *__restrict__ acc, long long M, double divisor, Best *__restrict__ part,
+    score_finish_slot_excl_kernel(ScoreParams p, int fresh, double *__restrict__ acc, long long M, double divisor, ArgBest *__restrict__ part,
                                   unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank, int world,
                                   long long offset, const double *__restrict__ grid, int d, int all_slots,
                                   unsigned long long *__restrict__ host_rec, unsigned *__restrict__ host_done, ExclRows excl) {
-  __shared__ Best sh[4];
+  __shared__ ArgBest sh[4];
   __shared__ unsigned last;
-  Best b{0.0, -1};
+  ArgBest b{0.0, -1};
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
     const double v = div<K>(fold_samples<K>(p, j, fresh ? empty<K>() : acc[j]), divisor);
     acc[j] = v;
     bool out = false;
     for (int e = 0; e < excl.n; ++e) out = out || excl.row[e] == j;
-    Best cnd{v, j};
-    if (!out && better(cnd, b)) b = cnd;
+    ArgBest cnd{v, j};
+    if (!out && Better()(cnd, b)) b = cnd;
   }
   block_best_ticket_record(b, sh, &last, part, ticket, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
 }
@@ -645,21 +612,21 @@ __global__ void __launch_bounds__(256)
 // score:div becomes w(v, feas[j]) (see the header), and that is what the accumulator holds and the arg-max sees.
 template <int K>
 __global__ void __launch_bounds__(256)
-    score_finish_slot_feas_kernel(ScoreParams p, int fresh, double *__restrict__ acc, long long M, double divisor, Best *__restrict__ part,
+    score_finish_slot_feas_kernel(ScoreParams p, int fresh, double *__restrict__ acc, long long M, double divisor, ArgBest *__restrict__ part,
                                   unsigned *__restrict__ ticket, unsigned long long *__restrict__ tab, int rank, int world,
                                   long long offset, const double *__restrict__ grid, int d, int all_slots,
                                   unsigned long long *__restrict__ host_rec, unsigned *__restrict__ host_done,
                                   const double *__restrict__ feas) {
-  __shared__ Best sh[4];
+  __shared__ ArgBest sh[4];
   __shared__ unsigned last;
-  Best b{0.0, -1};
+  ArgBest b{0.0, -1};
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
     const double v = div<K>(fold_samples<K>(p, j, fresh ? empty<K>() : acc[j]), divisor);
     const double w = feas_weight<score_acc_kind(K) == B7_ACC_LOG>(v, feas[j]);
     acc[j] = w;
-    Best cnd{w, j};
-    if (better(cnd, b)) b = cnd;
+    ArgBest cnd{w, j};
+    if (Better()(cnd, b)) b = cnd;
   }
   block_best_ticket_record(b, sh, &last, part, ticket, tab, rank, world, offset, M, grid, d, all_slots, host_rec, host_done);
 }
@@ -667,18 +634,18 @@ __global__ void __launch_bounds__(256)
 // finish_kernel with the feasibility column: acc[j] <- w(acc[j] / divisor, feas[j]) (a log accumulator: - log(divisor)), then the
 // per-block best; argmax_slot_kernel follows, a launch boundary away.
 __global__ void __launch_bounds__(256) feas_finish_kernel(double *__restrict__ acc, const double *__restrict__ feas, int64_t M,
-                                                          double divisor, Best *__restrict__ part, int logacc) {
-  __shared__ Best sh[4];
-  Best b{0.0, -1};
+                                                          double divisor, ArgBest *__restrict__ part, int logacc) {
+  __shared__ ArgBest sh[4];
+  ArgBest b{0.0, -1};
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
     const double v = logacc ? acc[j] + (-log(divisor)) : acc[j] / divisor;
     const double w = logacc ? feas_weight<true>(v, feas[j]) : feas_weight<false>(v, feas[j]);
     acc[j] = w;
-    Best cnd{w, j};
-    if (better(cnd, b)) b = cnd;
+    ArgBest cnd{w, j};
+    if (Better()(cnd, b)) b = cnd;
   }
-  b = block_best(b, sh);
+  b = block_best<Better>(b, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = b;
 }
 
@@ -688,15 +655,15 @@ __global__ void __launch_bounds__(256) feas_add_kernel(double *__restrict__ L, c
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) L[j] = L[j] + src[j];
 }
-__global__ void __launch_bounds__(256) feas_best_kernel(const double *__restrict__ L, int64_t M, Best *__restrict__ part) {
-  __shared__ Best sh[4];
-  Best b{0.0, -1};
+__global__ void __launch_bounds__(256) feas_best_kernel(const double *__restrict__ L, int64_t M, ArgBest *__restrict__ part) {
+  __shared__ ArgBest sh[4];
+  ArgBest b{0.0, -1};
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < M; j += stride) {
-    Best cnd{L[j], j};
-    if (better(cnd, b)) b = cnd;
+    ArgBest cnd{L[j], j};
+    if (Better()(cnd, b)) b = cnd;
   }
-  b = block_best(b, sh);
+  b = block_best<Better>(b, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = b;
 }
 
@@ -851,12 +818,12 @@ int launch_feas_add(b7_ctx *c, const double *src) {
 int launch_feas_best(b7_ctx *c, double *best_val, int64_t *best_idx1) {
   PhaseScope ps(c, "argmax");
   const int nb = nblocks(c, c->M);
-  B7_TRY(b7_ensure(c, c->part, sizeof(Best) * (size_t)(nb + 1)));
-  Best *part = (Best *)c->part.p;
+  B7_TRY(b7_ensure(c, c->part, sizeof(ArgBest) * (size_t)(nb + 1)));
+  ArgBest *part = (ArgBest *)c->part.p;
   hipLaunchKernelGGL(feas_best_kernel, dim3(nb), dim3(256), 0, c->stream, (const double *)c->feas.p, (int64_t)c->M, part);
-  Best *res_dev = reinterpret_cast<Best *>(&c->pinned_dev->best);
-  const BestPair &h = c->pinned->best;
-  hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, c->stream, (const Best *)part, nb, res_dev);
+  ArgBest *res_dev = &c->pinned_dev->best;
+  const ArgBest &h = c->pinned->best;
+  hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, c->stream, (const ArgBest *)part, nb, res_dev);
   B7_HIP(c, hipGetLastError());
   B7_HIP(c, hipStreamSynchronize(c->stream));
   if (best_val) *best_val = h.v;
@@ -868,13 +835,13 @@ int launch_finish(b7_ctx *c, double *acc, int64_t M, double divisor, double *bes
   PhaseScope ps(c, "argmax");
   if (M <= 0) return b7_fail(c, B7_ERR_INVALID, "finish: empty score vector");
   const int nb = nblocks(c, M);
-  B7_TRY(b7_ensure(c, c->part, sizeof(Best) * (size_t)(nb + 1)));
-  Best *part = (Best *)c->part.p;
+  B7_TRY(b7_ensure(c, c->part, sizeof(ArgBest) * (size_t)(nb + 1)));
+  ArgBest *part = (ArgBest *)c->part.p;
   hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, M, divisor, part, logacc ? 1 : 0);
   // the final (value, index) goes straight into pinned, device-mapped host memory: no copy, just the synchronisation
-  Best *res_dev = reinterpret_cast<Best *>(&c->pinned_dev->best);
-  const BestPair &h = c->pinned->best;
-  hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, c->stream, (const Best *)part, nb, res_dev);
+  ArgBest *res_dev = &c->pinned_dev->best;
+  const ArgBest &h = c->pinned->best;
+  hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, c->stream, (const ArgBest *)part, nb, res_dev);
   B7_HIP(c, hipGetLastError());
   B7_HIP(c, hipStreamSynchronize(c->stream));
   if (best_val) *best_val = h.v;
@@ -891,13 +858,13 @@ int launch_finish_slot(b7_ctx *c, double *acc, int64_t M, double divisor, uint64
                        bool logacc, const double *feas) {
   PhaseScope ps(c, "argmax");
   const int nb = M > 0 ? nblocks(c, M) : 0;
-  B7_TRY(b7_ensure(c, c->part, sizeof(Best) * (size_t)(nb + 1)));
-  Best *part = (Best *)c->part.p;
+  B7_TRY(b7_ensure(c, c->part, sizeof(ArgBest) * (size_t)(nb + 1)));
+  ArgBest *part = (ArgBest *)c->part.p;
   if (nb > 0 && feas)
     hipLaunchKernelGGL(feas_finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, feas, M, divisor, part, logacc ? 1 : 0);
   else if (nb > 0)
     hipLaunchKernelGGL(finish_kernel, dim3(nb), dim3(256), 0, c->stream, acc, M, divisor, part, logacc ? 1 : 0);
-  hipLaunchKernelGGL(argmax_slot_kernel, dim3(1), dim3(256), 0, c->stream, (const Best *)part, nb,
+  hipLaunchKernelGGL(argmax_slot_kernel, dim3(1), dim3(256), 0, c->stream, (const ArgBest *)part, nb,
                      (unsigned long long *)tab_dev, rank, world, (long long)offset, (long long)M, grid, d, all_slots ? 1 : 0,
                      -1ll, (unsigned long long *)host_rec, host_done);
   B7_HIP(c, hipGetLastError());
@@ -917,8 +884,8 @@ int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64
   // blocks: 137 vs 132 us.  The kernel's 15 us are launch, ticket and the last block's pass, not the ten scores in a row)
   const int threads = 256;
   const int nb = nblocks(c, M);
-  B7_TRY(b7_ensure(c, c->part, sizeof(Best) * (size_t)(nb + 1)));
-  Best *part = (Best *)c->part.p;
+  B7_TRY(b7_ensure(c, c->part, sizeof(ArgBest) * (size_t)(nb + 1)));
+  ArgBest *part = (ArgBest *)c->part.p;
   if (!c->ticket.p) {  // the ticket counter: a word of its own (c->part is shared scratch), zero between launches
     B7_TRY(b7_ensure(c, c->ticket, 64));
     B7_HIP(c, hipMemsetAsync(c->ticket.p, 0, 64, c->stream));
@@ -953,7 +920,7 @@ int launch_score_finish_slot(b7_ctx *c, const ScoreParams &p, double *acc, int64
 // (0.0, idx1_global, 0, rows, the row); every other rank writes zeros.
 int launch_row_slot(b7_ctx *c, uint64_t *tab_dev, int rank, int world, int64_t idx1_global, int64_t local0, const double *grid,
                     int d) {
-  hipLaunchKernelGGL(argmax_slot_kernel, dim3(1), dim3(256), 0, c->stream, (const Best *)nullptr, 0,
+  hipLaunchKernelGGL(argmax_slot_kernel, dim3(1), dim3(256), 0, c->stream, (const ArgBest *)nullptr, 0,
                      (unsigned long long *)tab_dev, rank, world, (long long)(idx1_global - 1 - (local0 >= 0 ? local0 : 0)),
                      (long long)c->M, grid, d, 1, (long long)local0, (unsigned long long *)nullptr, (unsigned *)nullptr);
   B7_HIP(c, hipGetLastError());

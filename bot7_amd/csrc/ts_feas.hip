@@ -356,34 +356,6 @@ int tf_thresholds(b7_ctx *c, const char *who, const double *thr, int C) {
   return B7_OK;
 }
 
-// The streams of o[0 .. n - 1] ordered by events both ways, as ehvi_order orders two or three.  before: the first context's stream
-// waits for what every other stream has been given; after: whatever the other contexts enqueue next waits for the kernels (the last
-// event).  A context that appears twice is waited on once.
-int tf_order(b7_ctx *const *o, int n, bool before) {
-  b7_ctx *c = o[0];
-  bool wait[TF_YW], any = false;
-  for (int m = 0; m < n; ++m) {
-    wait[m] = m > 0;
-    for (int i = 0; i < m; ++i) wait[m] = wait[m] && o[m] != o[i];
-    any = any || wait[m];
-  }
-  if (!any) return B7_OK;
-  if (before) {
-    for (hipEvent_t &e : c->ev_ts_feas)
-      if (!e) B7_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (int m = 1; m < n; ++m)
-      if (wait[m]) {
-        B7_HIP(c, hipEventRecord(c->ev_ts_feas[m - 1], o[m]->stream));
-        B7_HIP(c, hipStreamWaitEvent(c->stream, c->ev_ts_feas[m - 1], 0));
-      }
-  } else {
-    B7_HIP(c, hipEventRecord(c->ev_ts_feas[B7_TS_FEAS_CMAX], c->stream));
-    for (int m = 1; m < n; ++m)
-      if (wait[m]) B7_HIP(c, hipStreamWaitEvent(o[m]->stream, c->ev_ts_feas[B7_TS_FEAS_CMAX], 0));
-  }
-  return B7_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -421,31 +393,32 @@ int b7_ts_feas_nominate(b7_ctx *c, b7_ctx *const *cons, const double *thresholds
       return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: the context of %s is on device %d, this one on device %d (paths across devices are not built)", who,
                      name(k, nm, sizeof nm), o[k]->device, c->device);
   for (int k = 0; k < n; ++k) {
-    if (!o[k]->ts_valid)
+    const int state = ts_state(o[k]);
+    if (state == TS_STATE_NONE)
       return b7_fail(c, B7_ERR_STATE, "%s: no kept paths of %s (call b7_ts_paths on its context)", who, name(k, nm, sizeof nm));
-    if (o[k]->ts_blr)
+    if (state == TS_STATE_BLR)
       return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: the kept paths of %s were left by b7_blr_ts_nominate (the DNGO head is not built here)", who,
                      name(k, nm, sizeof nm));
-    if (o[k]->ts_epoch != o[k]->epoch || o[k]->ts_M != o[k]->M)
+    if (state == TS_STATE_STALE)
       return b7_fail(c, B7_ERR_STATE, "%s: the kept paths of %s are stale: its grid, its data or its kernel changed since (call b7_ts_paths again)",
                      who, name(k, nm, sizeof nm));
   }
   for (int k = 1; k < n; ++k) {
-    if (o[k]->ts_M != c->ts_M)
+    if (o[k]->ts.M != c->ts.M)
       return b7_fail(c, B7_ERR_INVALID, "%s: the grid of %s has M = %lld rows, the objective's %lld", who, name(k, nm, sizeof nm),
-                     (long long)o[k]->ts_M, (long long)c->ts_M);
-    if (o[k]->ts_q != c->ts_q)
-      return b7_fail(c, B7_ERR_INVALID, "%s: %s keeps q = %d paths, the objective %d", who, name(k, nm, sizeof nm), o[k]->ts_q, c->ts_q);
+                     (long long)o[k]->ts.M, (long long)c->ts.M);
+    if (o[k]->ts.q != c->ts.q)
+      return b7_fail(c, B7_ERR_INVALID, "%s: %s keeps q = %d paths, the objective %d", who, name(k, nm, sizeof nm), o[k]->ts.q, c->ts.q);
   }
-  const int q = c->ts_q;
-  const int64_t M = c->ts_M;
+  const int q = c->ts.q;
+  const int64_t M = c->ts.M;
   if (q < 1 || q > B7_BATCH_MAX || M < q) return b7_fail(c, B7_ERR_INVALID, "%s: q = %d not in [1, %d] or above the grid's %lld rows", who, q, B7_BATCH_MAX, (long long)M);
   B7_HIP(c, hipSetDevice(c->device));
   const double *buf[TF_YW];
   for (int k = 0; k < n; ++k) buf[k] = (const double *)o[k]->ts_paths.p;
-  B7_TRY(tf_order(o, n, true));
+  B7_TRY(streams_order(o, n, true));
   const int rc = tf_pick(c, buf, thresholds, C, M, q, nullptr, key_out, class_out, best_idx1, y_out, reruns_out);
-  const int rc2 = tf_order(o, n, false);
+  const int rc2 = streams_order(o, n, false);
   return rc != B7_OK ? rc : rc2;
 }
 

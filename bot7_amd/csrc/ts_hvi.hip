@@ -15,7 +15,7 @@
 // (scalar loads), no LDS for the score.  Objective m's values are read as (base, row stride): column j of an [M][q] path buffer
 // (stride q), a contiguous column of a [q][M] copy (stride 1), or a column of b7_hvi_compute's M1 x m host array (stride m).  The
 // arg-max is fused: every workgroup leaves its best (value, row) over the rows not in taken[0 .. j), the largest value first and the
-// lowest row among equals; hvi_final_kernel folds the partials into taken[j] / val[j].  No score vector is stored during a
+// lowest row among equals; argbest.h's final kernel folds the partials into taken[j] / val[j].  No score vector is stored during a
 // nomination; b7_hvi_compute runs the same kernel with `out` set and no partials.  A value depends on its own row and the front alone.
 //
 // The pick loop is sequential, path j = 0 .. q - 1: the working front of path j is the canonical front (b7_pareto_front2 / 3) of the
@@ -40,12 +40,10 @@
 namespace {
 
 constexpr int HVI_THREADS = 256;
-constexpr int HVI_BLOCKS_MAX = 1024;
+constexpr int HVI_BLOCKS_MAX = 1024;  // argbest_blocks' cap: the partials' room in c->ts_hvi
 constexpr int HVI_BOXES_MAX = 3 * B7_EHVI3_PMAX + 1;
 constexpr int HVI_REC = 2 + 3 * B7_BATCH_MAX;  // a pick's record in doubles: value | row (long long) | y[m][q] at 2 + 16 m + p
 constexpr int TR_ROWS = 64;                    // rows per workgroup of the transposition
-
-struct HviBest { double v; long long i; };
 
 struct HviArgs {
   const double *y[3];        // objective m's values: row g at y[m][g * stride[m]]
@@ -56,7 +54,7 @@ struct HviArgs {
   const long long *taken;    // rows kept out of the arg-max: taken[0 .. j)
   int j;
   double *out;               // [M], or null: no score vector
-  HviBest *part;             // [gridDim.x], or null: no arg-max
+  ArgBest *part;             // [gridDim.x], or null: no arg-max
 };
 
 __device__ __forceinline__ bool hvi_finite(double v) { return fabs(v) < INFINITY; }  // false for NaN too
@@ -97,64 +95,32 @@ __device__ __forceinline__ double hvi_score(const HviArgs &g, long long row) {
   return sum;
 }
 
-// a: a candidate that is a row with a score that is not NaN; b: the best so far, bi < 0 for none
-__device__ __forceinline__ bool hvi_better(double av, long long ai, double bv, long long bi) {
-  if (ai < 0) return false;
-  if (bi < 0) return true;
-  if (av != bv) return av > bv;
-  return ai < bi;
-}
-
-__device__ __forceinline__ void hvi_block_reduce(double &v, long long &i, HviBest *sm) {
-  const int t = threadIdx.x;
-  sm[t].v = v, sm[t].i = i;
-  __syncthreads();
-  for (int s = HVI_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s && hvi_better(sm[t + s].v, sm[t + s].i, sm[t].v, sm[t].i)) sm[t] = sm[t + s];
-    __syncthreads();
-  }
-  v = sm[0].v, i = sm[0].i;
-}
-
+// The score fused with the arg-max (argbest.h: OrderMaxNoNan, which is a total order only without NaNs: a NaN score is skipped
+// here, ahead of the comparison, and so never wins)
 template <int NOBJ>
-__device__ __forceinline__ void hvi_body(const HviArgs &g, HviBest *sm) {
-  long long tk[B7_BATCH_MAX];
-  const int nt = g.part ? g.j : 0;
-  for (int i = 0; i < nt; ++i) tk[i] = g.taken[i];
-  double bv = 0.0;
-  long long bi = -1;
+__device__ __forceinline__ void hvi_body(const HviArgs &g, ArgBest *sh) {
+  long long ex[ARGBEST_MAX_EXCL];
+  argbest_load_excl(g.taken, g.part ? g.j : 0, ex);
+  ArgBest b{0.0, -1};
   for (long long r = (long long)blockIdx.x * HVI_THREADS + threadIdx.x; r < g.M; r += (long long)gridDim.x * HVI_THREADS) {
     const double v = hvi_score<NOBJ>(g, r);
     if (g.out) g.out[r] = v;
-    bool skip = v != v;  // a NaN never wins
-    for (int i = 0; i < nt; ++i) skip = skip || tk[i] == r;
-    if (!skip && hvi_better(v, r, bv, bi)) bv = v, bi = r;
+    const ArgBest cnd{v, r};
+    if (v == v && !argbest_excluded(ex, r) && OrderMaxNoNan()(cnd, b)) b = cnd;
   }
   if (!g.part) return;  // uniform over the launch
-  hvi_block_reduce(bv, bi, sm);
-  if (threadIdx.x == 0) g.part[blockIdx.x].v = bv, g.part[blockIdx.x].i = bi;
+  b = block_best<OrderMaxNoNan>(b, sh);
+  if (threadIdx.x == 0) g.part[blockIdx.x] = b;
 }
 
 __global__ void __launch_bounds__(HVI_THREADS) hvi2_kernel(HviArgs g) {
-  __shared__ HviBest sm[HVI_THREADS];
-  hvi_body<2>(g, sm);
+  __shared__ ArgBest sh[4];
+  hvi_body<2>(g, sh);
 }
 
 __global__ void __launch_bounds__(HVI_THREADS) hvi3_kernel(HviArgs g) {
-  __shared__ HviBest sm[HVI_THREADS];
-  hvi_body<3>(g, sm);
-}
-
-// the partials of one pass into taken[j] (-1: no row scored) and val[j]
-__global__ void __launch_bounds__(HVI_THREADS) hvi_final_kernel(const HviBest *__restrict__ part, int nblk, int j, long long *__restrict__ taken,
-                                                                double *__restrict__ val) {
-  __shared__ HviBest sm[HVI_THREADS];
-  double bv = 0.0;
-  long long bi = -1;
-  for (int b = threadIdx.x; b < nblk; b += HVI_THREADS)
-    if (hvi_better(part[b].v, part[b].i, bv, bi)) bv = part[b].v, bi = part[b].i;
-  hvi_block_reduce(bv, bi, sm);
-  if (threadIdx.x == 0) taken[j] = bi, val[j] = bv;
+  __shared__ ArgBest sh[4];
+  hvi_body<3>(g, sh);
 }
 
 // pick j's record: its value, its row and the row's q values under every objective's [M][q] paths
@@ -199,7 +165,7 @@ __global__ void __launch_bounds__(HVI_THREADS) ts_transpose_kernel(const double 
 struct HviWork {
   double *fr, *rec, *val, *pmin;
   long long *taken;
-  HviBest *part;
+  ArgBest *part;
 };
 constexpr size_t HVI_FR = 5 * (size_t)HVI_BOXES_MAX > 2 * (size_t)(B7_EHVI_PMAX + 1) ? 5 * (size_t)HVI_BOXES_MAX : 2 * (size_t)(B7_EHVI_PMAX + 1);
 int hvi_work(b7_ctx *c, HviWork *w) {
@@ -209,11 +175,9 @@ int hvi_work(b7_ctx *c, HviWork *w) {
   w->fr = p, w->rec = p + fr;
   w->taken = reinterpret_cast<long long *>(p + fr + rec);
   w->val = p + fr + rec + small, w->pmin = w->val + small;
-  w->part = reinterpret_cast<HviBest *>(w->pmin + small);
+  w->part = reinterpret_cast<ArgBest *>(w->pmin + small);
   return B7_OK;
 }
-
-int hvi_blocks(int64_t M) { return (int)std::min<int64_t>(HVI_BLOCKS_MAX, (M + HVI_THREADS - 1) / HVI_THREADS); }
 
 // the front as the kernels read it into `host` (which must outlive the copy: the callers wait) and onto the device; *n_out: P or B
 int hvi_stage(b7_ctx *c, int m, const double *front, int P, const double *ref, double *dev, std::vector<double> *host, int *n_out) {
@@ -259,37 +223,38 @@ int ts_hvi_nominate(b7_ctx *const *o, int m, const char *who, const double *fron
       return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: the %s objective's context is on device %d, this one on device %d (paths across devices are not built)",
                      who, nth[k], o[k]->device, c->device);
   for (int k = 0; k < m; ++k) {
-    if (!o[k]->ts_valid)
+    const int state = ts_state(o[k]);
+    if (state == TS_STATE_NONE)
       return b7_fail(c, B7_ERR_STATE, "%s: no kept paths of the %s objective (call b7_ts_paths on its context)", who, nth[k]);
-    if (o[k]->ts_blr)
+    if (state == TS_STATE_BLR)
       return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: the %s objective's kept paths were left by b7_blr_ts_nominate (the DNGO head is not built here)", who,
                      nth[k]);
-    if (o[k]->ts_epoch != o[k]->epoch || o[k]->ts_M != o[k]->M)
+    if (state == TS_STATE_STALE)
       return b7_fail(c, B7_ERR_STATE, "%s: the kept paths of the %s objective are stale: its grid or its data changed since (call b7_ts_paths again)",
                      who, nth[k]);
   }
   for (int k = 1; k < m; ++k) {
-    if (o[k]->ts_M != c->ts_M)
-      return b7_fail(c, B7_ERR_INVALID, "%s: the %s objective's grid has M = %lld rows, this one %lld", who, nth[k], (long long)o[k]->ts_M,
-                     (long long)c->ts_M);
-    if (o[k]->ts_q != c->ts_q)
-      return b7_fail(c, B7_ERR_INVALID, "%s: the %s objective keeps q = %d paths, this one %d", who, nth[k], o[k]->ts_q, c->ts_q);
+    if (o[k]->ts.M != c->ts.M)
+      return b7_fail(c, B7_ERR_INVALID, "%s: the %s objective's grid has M = %lld rows, this one %lld", who, nth[k], (long long)o[k]->ts.M,
+                     (long long)c->ts.M);
+    if (o[k]->ts.q != c->ts.q)
+      return b7_fail(c, B7_ERR_INVALID, "%s: the %s objective keeps q = %d paths, this one %d", who, nth[k], o[k]->ts.q, c->ts.q);
   }
   B7_TRY(m == 2 ? front_refuse(c, who, front, P, ref) : front3_refuse(c, who, front, P, ref));
-  const int q = c->ts_q, pmax = m == 2 ? B7_EHVI_PMAX : B7_EHVI3_PMAX;
+  const int q = c->ts.q, pmax = m == 2 ? B7_EHVI_PMAX : B7_EHVI3_PMAX;
   if (P + q - 1 > pmax)
     return b7_fail(c, B7_ERR_INVALID, "%s: P + q - 1 = %d exceeds %d front points (the working front can grow by a point per pick)", who, P + q - 1,
                    pmax);
   B7_HIP(c, hipSetDevice(c->device));
-  const int64_t M = c->ts_M;
-  const int nblk = hvi_blocks(M);
+  const int64_t M = c->ts.M;
+  const int nblk = argbest_blocks(M);
   HviWork w;
   B7_TRY(hvi_work(c, &w));
   const double *paths[3] = {nullptr, nullptr, nullptr};
   for (int k = 0; k < m; ++k) paths[k] = (const double *)o[k]->ts_paths.p;
   const bool transposed = c->ts_hvi_layout != 0 && q > 1;
   if (transposed) B7_TRY(b7_ensure(c, c->ts_hvi_t, sizeof(double) * (size_t)m * (size_t)q * (size_t)M));
-  B7_TRY(ehvi_order(o, m, true));
+  B7_TRY(streams_order(o, m, true));
   if (transposed) {
     PhaseScope ps(c, "ts_transpose");
     for (int k = 0; k < m; ++k)
@@ -323,7 +288,7 @@ int ts_hvi_nominate(b7_ctx *const *o, int m, const char *who, const double *fron
     }
     g.fr = w.fr, g.n = n, g.M = (long long)M, g.taken = w.taken, g.j = j, g.out = nullptr, g.part = w.part;
     if ((rc = launch_hvi(c, m, g, nblk)) != B7_OK) break;
-    hipLaunchKernelGGL(hvi_final_kernel, dim3(1), dim3(HVI_THREADS), 0, c->stream, (const HviBest *)w.part, nblk, j, w.taken, w.val);
+    hipLaunchKernelGGL(argbest_final_kernel<OrderMaxNoNan>, dim3(1), dim3(HVI_THREADS), 0, c->stream, (const ArgBest *)w.part, nblk, j, w.taken, w.val);
     HviGatherArgs ga;
     for (int k = 0; k < 3; ++k) ga.paths[k] = paths[k];
     ga.taken = w.taken, ga.val = w.val, ga.rec = w.rec + (size_t)j * HVI_REC, ga.j = j, ga.q = q, ga.m = m;
@@ -357,7 +322,7 @@ int ts_hvi_nominate(b7_ctx *const *o, int m, const char *who, const double *fron
       if (y_out) y_out[(size_t)j * m + k] = rec[2 + k * B7_BATCH_MAX + j];
     }
   }
-  const int rc2 = ehvi_order(o, m, false);
+  const int rc2 = streams_order(o, m, false);
   return rc != B7_OK ? rc : rc2;
 }
 
@@ -396,7 +361,7 @@ int b7_hvi_compute(b7_ctx *c, const double *Y, int64_t M1, int m, const double *
   B7_HIP(c, hipMemcpyAsync(Yd, Y, sizeof(double) * n * m, hipMemcpyHostToDevice, c->stream));
   for (int k = 0; k < 3; ++k) g.y[k] = k < m ? Yd + k : nullptr, g.stride[k] = m;
   g.fr = w.fr, g.M = (long long)M1, g.taken = nullptr, g.j = 0, g.out = od, g.part = nullptr;
-  B7_TRY(launch_hvi(c, m, g, hvi_blocks(M1)));
+  B7_TRY(launch_hvi(c, m, g, argbest_blocks(M1)));
   B7_HIP(c, hipMemcpyAsync(out, od, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
   B7_HIP(c, hipStreamSynchronize(c->stream));  // the caller's arrays and the staged front are consumed
   return B7_OK;

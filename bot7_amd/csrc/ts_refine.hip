@@ -396,71 +396,53 @@ __global__ void __launch_bounds__(256) ts_path_grad_kernel(TsOps o, const double
 // Path j's starts beyond its nominee: the n = starts - 1 rows of lowest f_j among the rows that are none of the q nominees,
 // ascending by (value, row); a NaN is never chosen.  One pass over the paths: every workgroup leaves its slice's n lowest per path
 // (the next one is the lowest above the previous: the order is total), one workgroup per path merges the lists the same way.
-struct TsPick { double v; long long i; };
-__device__ __forceinline__ bool ts_pick_less(double av, long long ai, double bv, long long bi) {  // a before b; i < 0: none
-  if (ai < 0) return false;
-  if (bi < 0) return true;
-  return av < bv || (av == bv && ai < bi);
-}
-__device__ __forceinline__ TsPick ts_pick_block_min(TsPick x, TsPick *sh) {
-  for (int off = 32; off > 0; off >>= 1) {
-    const double yv = __shfl_xor(x.v, off);
-    const long long yi = __shfl_xor(x.i, off);
-    if (ts_pick_less(yv, yi, x.v, x.i)) x.v = yv, x.i = yi;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();  // sh is free again
-  if (lane == 0) sh[wave] = x;
-  __syncthreads();
-  TsPick b = sh[0];
-  for (int w = 1; w < 4; ++w)
-    if (ts_pick_less(sh[w].v, sh[w].i, b.v, b.i)) b = sh[w];
-  return b;
-}
+// (argbest.h: OrderMin, which is total only without NaNs -- a NaN value is skipped ahead of every comparison --, and block_best,
+// which the loops below call again and again: a barrier ahead of every call frees its LDS slots)
 __global__ void __launch_bounds__(256) ts_starts_kernel(const double *__restrict__ paths, long long M, int q, int n,
-                                                        const long long *__restrict__ taken, TsPick *__restrict__ part) {
-  __shared__ TsPick sh[4];
+                                                        const long long *__restrict__ taken, ArgBest *__restrict__ part) {
+  __shared__ ArgBest sh[4];
   const int j = blockIdx.y;
-  long long tk[B7_BATCH_MAX];
-  for (int i = 0; i < B7_BATCH_MAX; ++i) tk[i] = i < q ? taken[i] : -1;
-  TsPick prev{0.0, -1};
+  long long tk[ARGBEST_MAX_EXCL];
+  argbest_load_excl(taken, q, tk);
+  ArgBest prev{0.0, -1};
   for (int p = 0; p < n; ++p) {
-    TsPick b{0.0, -1};
+    ArgBest b{0.0, -1};
     for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < M; g += (long long)gridDim.x * 256) {
-      const double v = paths[g * q + j];
-      bool skip = v != v;
-      for (int i = 0; i < B7_BATCH_MAX; ++i) skip = skip || tk[i] == g;
-      if (prev.i >= 0) skip = skip || !ts_pick_less(prev.v, prev.i, v, g);
-      if (!skip && ts_pick_less(v, g, b.v, b.i)) b.v = v, b.i = g;
+      const ArgBest cnd{paths[g * q + j], g};
+      bool skip = cnd.v != cnd.v || argbest_excluded(tk, g);
+      if (prev.i >= 0) skip = skip || !OrderMin()(prev, cnd);
+      if (!skip && OrderMin()(cnd, b)) b = cnd;
     }
-    b = ts_pick_block_min(b, sh);
+    __syncthreads();  // sh is free again
+    b = block_best<OrderMin>(b, sh);
     if (threadIdx.x == 0) part[((long long)j * gridDim.x + blockIdx.x) * n + p] = b;
     prev = b;
     if (b.i < 0) {  // the slice is exhausted
-      for (int r = p + 1 + threadIdx.x; r < n; r += 256) part[((long long)j * gridDim.x + blockIdx.x) * n + r] = TsPick{0.0, -1};
+      for (int r = p + 1 + threadIdx.x; r < n; r += 256) part[((long long)j * gridDim.x + blockIdx.x) * n + r] = ArgBest{0.0, -1};
       break;
     }
   }
 }
 // starts[j][0] = the nominee, starts[j][1 + p] = the p-th lowest of the partial lists (-1: none), starts[j][P ..] = -1
-__global__ void __launch_bounds__(256) ts_starts_final_kernel(const TsPick *__restrict__ part, int nblk, int n,
+__global__ void __launch_bounds__(256) ts_starts_final_kernel(const ArgBest *__restrict__ part, int nblk, int n,
                                                               const long long *__restrict__ taken, long long *__restrict__ starts) {
-  __shared__ TsPick sh[4];
+  __shared__ ArgBest sh[4];
   const int j = blockIdx.x;
-  const TsPick *mine = part + (long long)j * nblk * n;
+  const ArgBest *mine = part + (long long)j * nblk * n;
   if (threadIdx.x == 0) starts[j * TS_PMAX] = taken[j];
-  TsPick prev{0.0, -1};
+  ArgBest prev{0.0, -1};
   bool done = false;
   for (int p = 0; p < TS_PMAX - 1; ++p) {
-    TsPick b{0.0, -1};
+    ArgBest b{0.0, -1};
     if (p < n && !done) {
       for (int e = threadIdx.x; e < nblk * n; e += 256) {
-        const TsPick c = mine[e];
+        const ArgBest c = mine[e];
         if (c.i < 0) continue;
-        if (prev.i >= 0 && !ts_pick_less(prev.v, prev.i, c.v, c.i)) continue;
-        if (ts_pick_less(c.v, c.i, b.v, b.i)) b = c;
+        if (prev.i >= 0 && !OrderMin()(prev, c)) continue;
+        if (OrderMin()(c, b)) b = c;
       }
-      b = ts_pick_block_min(b, sh);
+      __syncthreads();  // sh is free again
+      b = block_best<OrderMin>(b, sh);
       prev = b;
       done = b.i < 0;
     }
@@ -475,7 +457,7 @@ struct TsRefWork {
   double *box;        // lo d | hi d
   long long *taken;   // [16]
   long long *starts;  // [q][16]
-  TsPick *part;       // [q][nblk][15]
+  ArgBest *part;       // [q][nblk][15]
   TsRefOut out;
   int nblk;
 };
@@ -490,19 +472,20 @@ int ts_ref_check(b7_ctx *c, const char *who) {
   return B7_OK;
 }
 int ts_ref_kept(b7_ctx *c, const char *who, TsKept *k) {
-  if (!c->ts_valid) return b7_fail(c, B7_ERR_STATE, "%s: no successful b7_ts_nominate or b7_ts_paths on this context", who);
-  if (c->ts_blr)
+  const int state = ts_state(c);
+  if (state == TS_STATE_NONE) return b7_fail(c, B7_ERR_STATE, "%s: no successful b7_ts_nominate or b7_ts_paths on this context", who);
+  if (state == TS_STATE_BLR)
     return b7_fail(c, B7_ERR_UNSUPPORTED, "%s: the kept paths are the Bayesian-linear (DNGO) head's (their gradient is the basis network's Jacobian: not built)", who);
-  if (c->ts_epoch != c->epoch || c->ts_M != c->M || c->ts_N != c->N || c->ts_d != c->dfit || ts_kept(c, k) != B7_OK)
+  if (state != TS_STATE_FRESH || ts_kept(c, k) != B7_OK)
     return b7_fail(c, B7_ERR_STATE, "%s: the kept paths are stale (the grid, the data or the covariance kernel changed since they were drawn)", who);
   return B7_OK;
 }
 
 // the operands of the kept paths into c->ts_ref_ws, in fragment order; the rest of the workspace carved behind them
 int ts_ref_pack(b7_ctx *c, const TsKept &k, TsRefWork *wk) {
-  const int q = c->ts_q, S = c->ts_S, F = c->ts_F, N = c->ts_N, d = c->ts_d, ns = k.ns;
+  const int q = c->ts.q, S = c->ts.S, F = c->ts.F, N = c->ts.N, d = c->ts.d, ns = k.ns;
   const int dpad = rff_dpad(d), NT = (dpad + 15) / 16, np16 = (int)round_up(N, 16);
-  const int nblk = (int)std::min<int64_t>(512, (c->ts_M + 255) / 256);
+  const int nblk = (int)std::min<int64_t>(512, (c->ts.M + 255) / 256);
   size_t off = 0;
   auto take = [&](size_t doubles) {
     const size_t o = off;
@@ -526,11 +509,11 @@ int ts_ref_pack(b7_ctx *c, const TsKept &k, TsRefWork *wk) {
   o.d = d, o.F = F, o.N = N, o.np16 = np16, o.S = S;
   wk->hyp = b + o_hyp, wk->box = b + o_box;
   wk->taken = reinterpret_cast<long long *>(b + o_taken), wk->starts = reinterpret_cast<long long *>(b + o_starts);
-  wk->part = reinterpret_cast<TsPick *>(b + o_part);
+  wk->part = reinterpret_cast<ArgBest *>(b + o_part);
   wk->out.x = b + o_x, wk->out.g = b + o_g, wk->out.v = b + o_v, wk->out.status = reinterpret_cast<int *>(b + o_st), wk->out.trace = nullptr;
   wk->nblk = nblk;
   PhaseScope ps(c, "ts_refine:pack");
-  B7_HIP(c, hipMemcpyAsync(wk->hyp, c->ts_hyp.data(), sizeof(double) * c->ts_hyp.size(), hipMemcpyHostToDevice, c->stream));
+  B7_HIP(c, hipMemcpyAsync(wk->hyp, c->ts.hyp.data(), sizeof(double) * c->ts.hyp.size(), hipMemcpyHostToDevice, c->stream));
   const int64_t per = (int64_t)(F + np16) * (dpad + 16 * NT) + np16 + dpad;
   hipLaunchKernelGGL(ts_pack_sample_kernel, dim3((unsigned)std::min<int64_t>(1024, (per + 255) / 256), ns), dim3(256), 0, c->stream, k.omega,
                      (const double *)c->xobs.p, (const double *)wk->hyp, F, d, dpad, N, np16, b + o_omf, b + o_omt, b + o_zf, b + o_zt, b + o_zss,
@@ -612,9 +595,9 @@ int b7_ts_nominate_refine(b7_ctx *c, int S, const b7_hyp *hyps, int q, int F, ui
   {
     PhaseScope ps(c, "ts_refine:starts");
     if (P > 1)
-      hipLaunchKernelGGL(ts_starts_kernel, dim3(wk.nblk, q), dim3(256), 0, c->stream, (const double *)c->ts_paths.p, (long long)c->ts_M, q, P - 1,
+      hipLaunchKernelGGL(ts_starts_kernel, dim3(wk.nblk, q), dim3(256), 0, c->stream, (const double *)c->ts_paths.p, (long long)c->ts.M, q, P - 1,
                          (const long long *)wk.taken, wk.part);
-    hipLaunchKernelGGL(ts_starts_final_kernel, dim3(q), dim3(256), 0, c->stream, (const TsPick *)wk.part, wk.nblk, P - 1,
+    hipLaunchKernelGGL(ts_starts_final_kernel, dim3(q), dim3(256), 0, c->stream, (const ArgBest *)wk.part, wk.nblk, P - 1,
                        (const long long *)wk.taken, wk.starts);
     B7_HIP(c, hipGetLastError());
   }
@@ -714,7 +697,7 @@ int b7_ts_path_grad_at(b7_ctx *c, const double *X1, int64_t M1, double *val, dou
   B7_TRY(ts_ref_kept(c, who, &kept));
   if (M1 == 0) return B7_OK;
   B7_HIP(c, hipSetDevice(c->device));
-  const int q = c->ts_q, d = c->ts_d;
+  const int q = c->ts.q, d = c->ts.d;
   TsRefWork wk;
   B7_TRY(ts_ref_pack(c, kept, &wk));
   const size_t nx = (size_t)M1 * d, nv = (size_t)M1 * q, ng = nv * d;
