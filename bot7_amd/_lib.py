@@ -42,6 +42,7 @@ SYMBOLS = [
     "b7_ei_compute", "b7_cb_compute", "b7_logei_compute", "b7_argmax",
     "b7_score_logpi", "b7_logpi_compute", "b7_feas_reset", "b7_feas_add", "b7_feas_add_acc", "b7_feas_get", "b7_feas_nominate", "b7_eval_nominate_feasible",
     "b7_clf_nll_batch", "b7_clf_fit_hyp", "b7_clf_mode_get", "b7_clf_eval_logfeas", "b7_probit_compute",
+    "b7_gp_fit_hyp_grad", "b7_gp_nll_grad", "b7_lbfgsb_default_opts", "b7_lbfgsb_minimize", "b7_gp_fit_map", "b7_gp_fit_map_trace_enable", "b7_gp_fit_map_trace",
     "b7_timer_start", "b7_timer_stop", "b7_timer_ms", "b7_profile_enable", "b7_profile_reset", "b7_profile_get", "b7_persist_fallbacks",
 ]
 
@@ -112,6 +113,58 @@ class Mlp(C.Structure):
 
 ACTIVATIONS = {None: 0, "Identity": 0, "Tanh": 1, "ReLU": 2, "Sigmoid": 3}
 _MLP_CACHE = {}
+
+
+class LbfgsbOpts(C.Structure):   # b7_lbfgsb_opts
+    _fields_ = [("max_iters", C.c_int), ("max_evals", C.c_int), ("gtol", C.c_double)]
+
+
+# b7_lbfgsb_minimize's status bits
+LBFGSB_CONVERGED, LBFGSB_MAX_ITERS, LBFGSB_MAX_EVALS, LBFGSB_LINESEARCH, LBFGSB_STOPPED, LBFGSB_BAD_START = 1, 2, 4, 8, 16, 32
+_OBJECTIVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+
+
+def _lbfgsb_opts(max_iters=None, max_evals=None, gtol=None):
+    """b7_lbfgsb_opts from keywords; None selects the library's default of that field."""
+    return LbfgsbOpts(-1 if max_iters is None else int(max_iters), 0 if max_evals is None else int(max_evals),
+                      0.0 if gtol is None else float(gtol))
+
+
+def lbfgsb_minimize(fun, x0, lo, hi, max_iters=None, max_evals=None, gtol=None):
+    """The library's projected L-BFGS with bounds on a Python callable (b7_lbfgsb_minimize; host only, no context): fun(x) returns
+    (f, g) with g of x's length; an exception inside fun stops the run and is raised again here.  Returns dict(x, f, g, iters, evals,
+    status)."""
+    x0, lo, hi = (np.ascontiguousarray(_f64(v).ravel()) for v in (x0, lo, hi))
+    n = x0.size
+    if lo.size != n or hi.size != n:
+        raise Bot7HipError(-1, "x0, lo and hi must have the same length")
+    err = []
+
+    def cb(_user, nn, xp, fp, gp):
+        try:
+            f, g = fun(np.array(xp[:nn], dtype=np.float64))
+            g = np.asarray(g, dtype=np.float64).ravel()
+            if g.size != nn:
+                raise ValueError("the gradient must have %d entries" % nn)
+            fp[0] = float(f)
+            for i in range(nn):
+                gp[i] = g[i]
+            return 0
+        except BaseException as e:   # never let an exception cross the C frames
+            err.append(e)
+            return 1
+
+    keep = _OBJECTIVE(cb)
+    opts = _lbfgsb_opts(max_iters, max_evals, gtol)
+    x, g = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+    f, it, ev, st = C.c_double(), C.c_int(), C.c_int(), C.c_int()
+    rc = load().b7_lbfgsb_minimize(C.cast(keep, C.c_void_p), None, n, _ptr(x0), _ptr(lo), _ptr(hi), C.byref(opts), _ptr(x), C.byref(f),
+                                   _ptr(g), C.byref(it), C.byref(ev), C.byref(st))
+    if err:
+        raise err[0]
+    if rc != B7_OK:
+        raise Bot7HipError(rc, "lbfgsb_minimize: n in 1..99, lo <= hi, x0 finite and inside the box")
+    return {"x": x, "f": f.value, "g": g, "iters": it.value, "evals": ev.value, "status": st.value}
 
 
 class GpOpts(C.Structure):
@@ -299,6 +352,14 @@ def load(which=None):
         "b7_clf_mode_get": (i32, [vp, vp, vp, vp]),
         "b7_clf_eval_logfeas": (i32, [vp, i32, C.POINTER(Hyp), C.POINTER(dbl), C.POINTER(i64), vp, vp]),
         "b7_probit_compute": (i32, [vp, vp, i64, vp, vp, vp]),
+        "b7_gp_fit_hyp_grad": (i32, [vp, C.POINTER(Hyp), C.POINTER(dbl), vp, C.POINTER(dbl), C.POINTER(i32)]),
+        "b7_gp_nll_grad": (i32, [vp, vp]),
+        "b7_lbfgsb_default_opts": (i32, [C.POINTER(LbfgsbOpts)]),
+        "b7_lbfgsb_minimize": (i32, [vp, vp, i32, vp, vp, vp, C.POINTER(LbfgsbOpts), vp, C.POINTER(dbl), vp, C.POINTER(i32), C.POINTER(i32),
+                                     C.POINTER(i32)]),
+        "b7_gp_fit_map": (i32, [vp, vp, vp, vp, C.POINTER(LbfgsbOpts), vp, C.POINTER(dbl), vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "b7_gp_fit_map_trace_enable": (i32, [vp, i32]),
+        "b7_gp_fit_map_trace": (i32, [vp, vp, C.POINTER(i32), C.POINTER(i32)]),
         "b7_timer_start": (i32, [vp, i32]),
         "b7_timer_stop": (i32, [vp, i32]),
         "b7_timer_ms": (i32, [vp, i32, C.POINTER(C.c_float)]),
@@ -609,7 +670,60 @@ class LaplaceClassifier(object):
         return tuple(out)
 
 
-class Context(BlrThompson, ThompsonObjectives, ThompsonFeasible, ThompsonRefine, LaplaceClassifier):
+class LikelihoodGradient(object):
+    """The likelihood's gradient and the bounded fit that descends on it (b7_gp_fit_hyp_grad, b7_gp_nll_grad, b7_gp_fit_map;
+    csrc/nll_grad.hip), mixed into Context below.  A class of its own for BlrThompson's reason; these are held to the same call twice
+    giving the same bits by tests/test_gpu_nllgrad.py.  theta = [log lenscale_sq (d), log amp, log noise, mean]."""
+
+    def gp_fit_hyp_grad(self, lenscale_sq, amp, noise, mean):
+        """gp_fit_hyp plus the gradient of its nll in theta's coordinates.  Returns dict(nll, grad[d + 3], jitter, info)."""
+        ls = _f64(lenscale_sq).ravel()
+        if ls.size != getattr(self, "_data_d", ls.size):
+            raise Bot7HipError(-1, "lenscale_sq must have d entries (call gp_set_data first)")
+        hyp = Hyp(ls.ctypes.data_as(C.POINTER(C.c_double)), float(amp), float(noise), float(mean))
+        grad = np.empty(ls.size + 3, dtype=np.float64)
+        nll, jit, info = C.c_double(), C.c_double(), C.c_int()
+        self._ck(self._L.b7_gp_fit_hyp_grad(self._h, C.byref(hyp), C.byref(nll), _ptr(grad), C.byref(jit), C.byref(info)))
+        self.fit_token += 1
+        return {"nll": nll.value, "grad": grad, "jitter": jit.value, "info": info.value}
+
+    def gp_nll_grad(self):
+        """The gradient of the fit the context holds (b7_gp_nll_grad): d + 3 components."""
+        grad = np.empty(getattr(self, "_data_d", B7_MAX_D_PY) + 3, dtype=np.float64)
+        self._ck(self._L.b7_gp_nll_grad(self._h, _ptr(grad)))
+        return grad
+
+    def gp_fit_map(self, theta0, lo, hi, max_iters=None, max_evals=None, gtol=None):
+        """Bounded maximum likelihood of the resident data from theta0 inside [lo, hi] (b7_gp_fit_map); the context's fit slot holds
+        the fit at the result.  Returns dict(theta, nll, grad, iters, evals, status)."""
+        t0, lo, hi = (np.ascontiguousarray(_f64(v).ravel()) for v in (theta0, lo, hi))
+        n = getattr(self, "_data_d", t0.size - 3) + 3
+        if t0.size != n or lo.size != n or hi.size != n:
+            raise Bot7HipError(-1, "theta0, lo and hi must have d + 3 entries (call gp_set_data first)")
+        opts = _lbfgsb_opts(max_iters, max_evals, gtol)
+        th, g = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+        nll, it, ev, st = C.c_double(), C.c_int(), C.c_int(), C.c_int()
+        self._ck(self._L.b7_gp_fit_map(self._h, _ptr(t0), _ptr(lo), _ptr(hi), C.byref(opts), _ptr(th), C.byref(nll), _ptr(g), C.byref(it),
+                                       C.byref(ev), C.byref(st)))
+        self.fit_token += 1
+        return {"theta": th, "nll": nll.value, "grad": g, "iters": it.value, "evals": ev.value, "status": st.value}
+
+    def gp_fit_map_trace_enable(self, on=True):
+        self._ck(self._L.b7_gp_fit_map_trace_enable(self._h, int(bool(on))))
+
+    def gp_fit_map_trace(self):
+        """The last traced gp_fit_map: one row per accepted iterate, row 0 the start: theta (d + 3) | nll | step."""
+        n, w = C.c_int(), C.c_int()
+        self._ck(self._L.b7_gp_fit_map_trace(self._h, None, C.byref(n), C.byref(w)))
+        buf = np.empty((n.value, w.value), dtype=np.float64)
+        self._ck(self._L.b7_gp_fit_map_trace(self._h, _ptr(buf), C.byref(n), C.byref(w)))
+        return buf
+
+
+B7_MAX_D_PY = 96
+
+
+class Context(BlrThompson, ThompsonObjectives, ThompsonFeasible, ThompsonRefine, LaplaceClassifier, LikelihoodGradient):
     """One GPU's worth of state: the resident candidate grid, the current GP fit, the score accumulator."""
 
     def __init__(self, device_id=0, _borrowed=None, lib=None):

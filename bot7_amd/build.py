@@ -17,12 +17,12 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "_build")
 OUT = os.path.join(HERE, "libbot7hip.so")
-SOURCES = ["context.hip", "grid_api.hip", "gp_api.hip", "nominate.hip", "blr_api.hip", "sobol.hip", "covar.hip", "potrf.hip", "potrf_persist.hip", "posterior.hip", "score.hip", "extras.hip", "comm.hip", "group.hip", "blr_small.hip", "gp_small.hip", "kpost_small.hip", "batch.hip", "mes.hip", "rff.hip", "slice.hip", "refine.hip", "kg.hip", "ehvi.hip", "trust_region.hip", "ehvi3.hip", "blr_ts.hip", "ts_hvi.hip", "ts_feas.hip", "ts_refine.hip", "laplace.hip"]
+SOURCES = ["context.hip", "grid_api.hip", "gp_api.hip", "nominate.hip", "blr_api.hip", "sobol.hip", "covar.hip", "potrf.hip", "potrf_persist.hip", "posterior.hip", "score.hip", "extras.hip", "comm.hip", "group.hip", "blr_small.hip", "gp_small.hip", "kpost_small.hip", "batch.hip", "mes.hip", "rff.hip", "slice.hip", "refine.hip", "kg.hip", "ehvi.hip", "trust_region.hip", "ehvi3.hip", "blr_ts.hip", "ts_hvi.hip", "ts_feas.hip", "ts_refine.hip", "laplace.hip", "nll_grad.hip", "lbfgsb.hip"]
 # The DIAGNOSTIC build (tools/_build/libbot7hip_diag.so, -DB7_DIAG): the shipped sources + round 3's likelihood kernel kept as
 # a bit-for-bit reference.  Only translation units that mention B7_DIAG are compiled a second time; the rest are shared.
 DIAG_ONLY_SOURCES = ["nll_small.hip"]
 DIAG_OUT = os.path.join(ROOT, "tools", "_build", "libbot7hip_diag.so")
-HEADERS = [os.path.join(CSRC, "b7_internal.h"), os.path.join(CSRC, "argbest.h"), os.path.join(CSRC, "gemm_f64.h"), os.path.join(CSRC, "potrf_diag.h"), os.path.join(CSRC, "comm_rccl.h"), os.path.join(CSRC, "ksx_exp.h"), os.path.join(CSRC, "ksx_walk.h"), os.path.join(CSRC, "exp_table.h"), os.path.join(CSRC, "mes_math.h"), os.path.join(CSRC, "logei_math.h"), os.path.join(CSRC, "ehvi_math.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "gp_small_body.h"), os.path.join(CSRC, "post_ring_layout.h"), os.path.join(CSRC, "probit_math.h"),
+HEADERS = [os.path.join(CSRC, "b7_internal.h"), os.path.join(CSRC, "argbest.h"), os.path.join(CSRC, "gemm_f64.h"), os.path.join(CSRC, "potrf_diag.h"), os.path.join(CSRC, "comm_rccl.h"), os.path.join(CSRC, "ksx_exp.h"), os.path.join(CSRC, "ksx_walk.h"), os.path.join(CSRC, "exp_table.h"), os.path.join(CSRC, "mes_math.h"), os.path.join(CSRC, "logei_math.h"), os.path.join(CSRC, "ehvi_math.h"), os.path.join(CSRC, "counter_rng.h"), os.path.join(CSRC, "gp_small_body.h"), os.path.join(CSRC, "post_ring_layout.h"), os.path.join(CSRC, "probit_math.h"), os.path.join(CSRC, "lbfgsb.h"),
            os.path.join(ROOT, "include", "bot7hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-fast-math", "-Wall",

@@ -350,6 +350,16 @@ struct b7_ctx {
   uint64_t feat_version = 0, grid_version = 0;
   uint64_t epoch = 0;  // counts the changes of the grid, the data or the covariance kernel (post_forget): what was kept under an earlier one is stale
   DevBuf netbuf; // MLP weights/biases of the basis network
+  // ---- likelihood gradients and the bounded fit (nll_grad.hip)
+  DevBuf gradpart;           // [tiles][d + 2] partial sums of the last gradient, then its d + 3 components
+  PinBuf pin_grad;           // those components on their way to the host (not mapped)
+  bool grad_hook = false;    // fit_hyp_core enqueues the gradient behind the fit's tail (set around the call by b7_gp_fit_hyp_grad)
+  bool gfit = false;         // the context's fit slot holds what fit_hyp_core left (b7_gp_nll_grad asks: fit_front and b7_gp_append
+  double gfit_jitter = 0.0;  // withdraw it; a change of the grid does not), with its jitter and the N it was made at
+  int gfit_N = 0;
+  bool map_trace_on = false; // b7_gp_fit_map_trace_enable
+  std::vector<double> map_trace;  // the last traced b7_gp_fit_map's records, map_trace_n of map_trace_w doubles
+  int map_trace_n = 0, map_trace_w = 0;
 
   // ---- the arg-max exchange (comm.hip): RCCL communicator of this rank, one per context = per GPU = per process
   void *comm = nullptr;  // ncclComm_t
@@ -672,6 +682,8 @@ int check_hyp(b7_ctx *c, const b7_hyp *hyp, int d);
 void launch_resid_batch(b7_ctx *c, int B, const double *mean_dev);  // c->bresid[b] = Y - mean[b] (padding rows zero), B fits
 int fit_front(b7_ctx *c, const b7_hyp *hyp, const double *ls_dev);  // residual, observation scaling and K(X,X) of one hyper sample
 int fit_hyp_core(b7_ctx *c, const b7_hyp *hyp, double *nll_out, double *jitter_used, int *info_out, bool then_predict);
+// nll_grad.hip: the gradient of the context's fit and its copy to pinned memory, enqueued (fit_hyp_core's hook, c->grad_hook)
+int nll_grad_enqueue(b7_ctx *c);
 int64_t predict_chunk(const b7_ctx *c, int64_t M);  // candidate rows per pass of predict_into: what c->ks has to hold
 int predict_into(b7_ctx *c, const FitSet &fit, const double *xq, int64_t M, double *mu, double *var);  // one fit, host scalars
 // mean (M x cols) / variance (M) to the caller (either may be null), then one synchronisation if either was asked for, or `wait`

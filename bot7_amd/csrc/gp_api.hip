@@ -159,6 +159,7 @@ int fit_front(b7_ctx *c, const b7_hyp *hyp, const double *ls_dev) {
   c->amp = hyp->amp;
   c->noise = hyp->noise;
   c->mean = hyp->mean;
+  c->gfit = false;
   const int64_t ntotal = (int64_t)c->Npad * ycols;
   hipLaunchKernelGGL(resid_kernel, dim3((unsigned)((ntotal + 255) / 256)), dim3(256), 0, c->stream,
                      (const double *)c->ybuf.p, (double *)c->resid.p, (int64_t)N * ycols, ntotal, hyp->mean);
@@ -194,6 +195,7 @@ int fit_hyp_core(b7_ctx *c, const b7_hyp *hyp, double *nll_out, double *jitter_u
     c->amp = hyp->amp;
     c->noise = hyp->noise;
     c->mean = hyp->mean;
+    c->gfit = false;
   } else {
     B7_HIP(c, hipMemcpyAsync(ls_dev, ls_stage, sizeof(double) * d, hipMemcpyHostToDevice, c->stream));
     B7_TRY(fit_front(c, hyp, ls_dev));
@@ -224,6 +226,7 @@ int fit_hyp_core(b7_ctx *c, const b7_hyp *hyp, double *nll_out, double *jitter_u
         if (nll_out) B7_TRY(launch_nll_terms(c, terms_dev));
       }
     }
+    if (tail_done && c->grad_hook) B7_TRY(nll_grad_enqueue(c));
     B7_HIP(c, hipMemcpyAsync(&blk, c->info.p, tail_done ? blk_bytes : 16, hipMemcpyDeviceToHost, c->stream));
     if (then_predict && tail_done) {
       B7_HIP(c, hipEventRecord(c->ev_fit, c->stream));
@@ -254,6 +257,7 @@ int fit_hyp_core(b7_ctx *c, const b7_hyp *hyp, double *nll_out, double *jitter_u
     B7_TRY(launch_trtri(c));
     B7_TRY(launch_alpha(c, nullptr, 0, note));
     if (nll_out) B7_TRY(launch_nll_terms(c, terms_dev));
+    if (c->grad_hook) B7_TRY(nll_grad_enqueue(c));
     B7_HIP(c, hipMemcpyAsync(&blk, c->info.p, blk_bytes, hipMemcpyDeviceToHost, c->stream));
     B7_HIP(c, hipStreamSynchronize(c->stream));
   }
@@ -267,6 +271,7 @@ int fit_hyp_core(b7_ctx *c, const b7_hyp *hyp, double *nll_out, double *jitter_u
   if (info_out) *info_out = info_first;
   persist_restore(c);
   c->fitted = true;
+  c->gfit = true, c->gfit_jitter = jitter, c->gfit_N = c->N;
   return B7_OK;
 }
 
@@ -658,6 +663,7 @@ int b7_gp_append(b7_ctx *c, const double *x_new, const double *y_new) {
   B7_HIP(c, hipSetDevice(c->device));
   const int N = c->N, np = c->Npad, d = c->dfit, yc = c->ycols;
   c->predicted = false;
+  c->gfit = false;  // an extended fit is not b7_gp_fit_hyp's: b7_gp_nll_grad asks for a new one
   post_forget(c);
   // the new observation joins the observation set (raw row, scaled row, half norm, residual row)
   B7_HIP(c, hipMemcpyAsync((double *)c->xobs.p + (size_t)N * d, x_new, sizeof(double) * d, hipMemcpyHostToDevice,

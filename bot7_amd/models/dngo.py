@@ -26,6 +26,9 @@ class dngo(abstract):
 
     def __init__(self, config=None, context=None):
         self.config = dict(config or {})
+        if "fit" in self.config:
+            raise NotImplementedError("dngo with config.fit = %r: gradients of the Bayesian linear head's evidence are not built (the fit "
+                                      "is gp_regressor's)" % (self.config["fit"],))
         self._ctx = context
         self.hyp = None
         net = self.config.get("network")

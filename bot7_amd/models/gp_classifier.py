@@ -24,6 +24,9 @@ class gp_classifier(gp_regressor):
     title = "bot7.models.gp_classifier"
 
     def __init__(self, config=None, context=None):
+        if "fit" in dict(config or {}):
+            raise NotImplementedError("gp_classifier with config.fit = %r: gradients of the Laplace evidence are not built (the fit is the "
+                                      "regressor's)" % (dict(config)["fit"],))
         super().__init__(config, context)
         if self.config.get("sampler", "slice") == "slice_device":
             raise NotImplementedError("gp_classifier with sampler 'slice_device': the classifier's chain on the device is not built "

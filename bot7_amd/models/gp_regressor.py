@@ -48,6 +48,17 @@ class gp_regressor(abstract):
         self._ctx = context
         self.hyp = None
         self.last_fit = None
+        if "fit" in self.config:
+            self._check_fit_mode()
+
+    def _check_fit_mode(self):
+        """config.fit = 'map' (absent: the point estimate is init's heuristic, as ever): sample_hypers returns the bounded maximum of
+        the marginal likelihood over _bounds' box, which is the MAP estimate under the sampler's flat box prior (b7_gp_fit_map)."""
+        if self.config["fit"] != "map":
+            raise NotImplementedError("config.fit = %r: only 'map' is built (leave it out for the heuristic point estimate)" % (self.config["fit"],))
+        if self.config.get("sample"):
+            raise NotImplementedError("config.fit = 'map' with config.sample = True: the fit replaces the sampler's point estimate, "
+                                      "it does not seed a chain (use one or the other)")
 
     @property
     def ctx(self):
@@ -189,6 +200,8 @@ class gp_regressor(abstract):
         Y = np.asarray(Y_obs, dtype=np.float64).reshape(X.shape[0], -1)
         if self.hyp is None:
             self.init(X, Y)
+        if "fit" in self.config:
+            return self._fit_map(X, Y)
         if self.config.get("sample") and self.config.get("sampler", "slice") == "slice_device":
             return self._sample_hypers_device(X, Y, state)
         if self.config.get("sample") and int(self.config.get("chains", 1)) > 1:
@@ -212,6 +225,54 @@ class gp_regressor(abstract):
                 theta = self._sampler.sample(f, theta.reshape(1, -1), dict(self._sopt, nSamples=1), None)[0]
             self.hyp = self._from_theta(theta)
             self._chain_state = (theta, self.hyp)
+        h = self.hyp
+        return np.concatenate([h["lenscale_sq"], [h["amp"], h["noise"], h["mean"]]])
+
+    # ---- the point estimate by bounded maximum likelihood: one b7_gp_fit_map per data set --------------------------------------
+    def _fit_map(self, X, Y):
+        """config.fit = 'map': the estimate of the current data inside _bounds, with config.fit_opt = {max_iters, gtol}.  One fit per
+        data set: the driver's repeated calls of a trial are served from it.  The fit starts from the previous estimate, or from
+        init's heuristic where that has the lower likelihood value on the new data (the first time they are the same point); the
+        optimiser never returns a point worse than its start, so a trial's estimate is never worse than the heuristic."""
+        import math
+        self._check_fit_mode()
+        if Y.shape[1] != 1:
+            raise NotImplementedError("config.fit = 'map' with %d response columns: the likelihood gradient of one column is built" % Y.shape[1])
+        ctx = self.ctx
+        info = getattr(ctx, "comm_info", None)
+        if getattr(ctx, "members", None) is not None or (info is not None and info()[1] > 1):
+            raise NotImplementedError("config.fit = 'map' on a sharded context (a group, or a communicator of several ranks): the "
+                                      "likelihood gradient over sharded data is not built")
+        key = self._data_key(X, Y)
+        done = getattr(self, "_map_done", None)
+        if done is None or done[0] != key or done[1] is not self.hyp:
+            d = X.shape[1]
+            noiseless = bool(self.config.get("noiseless"))
+            lo, hi = (np.array(v, dtype=np.float64) for v in self._bounds(X, Y))
+            heur = gp_regressor({"noiseless": noiseless}).init(X, Y)
+            if noiseless:
+                lo[d + 1] = hi[d + 1] = self._to_theta(heur)[d + 1]    # lo == hi: the component is fixed
+            starts = [np.clip(self._to_theta(h), lo, hi) for h in (self.hyp, heur)]
+            opt = dict(self.config.get("fit_opt") or {})
+            self._use_kernel()
+            if getattr(self, "_resident_key", None) != (key, ctx.fit_token):
+                ctx.gp_set_data(X, Y)
+            evals, t0 = 0, starts[0]
+            if not np.array_equal(starts[0], starts[1]):
+                priced = [ctx.gp_fit_map(t, lo, hi, max_iters=0) for t in starts]   # each start's own likelihood value on these data
+                evals = sum(p["evals"] for p in priced)
+                if not priced[0]["nll"] <= priced[1]["nll"]:
+                    t0 = starts[1]
+            r = ctx.gp_fit_map(t0, lo, hi, max_iters=opt.get("max_iters"), gtol=opt.get("gtol"))
+            evals += r["evals"]
+            self._resident_key = (key, ctx.fit_token)
+            t = r["theta"]
+            self.hyp = {"lenscale_sq": np.array([math.exp(v) for v in t[:d]]), "amp": math.exp(t[d]),
+                        "noise": 0.0 if noiseless else math.exp(t[d + 1]), "mean": float(t[d + 2])}
+            self.nEvals = getattr(self, "nEvals", 0) + evals
+            self.last_fit = {"nll": np.array([r["nll"]]), "iters": r["iters"], "evals": evals, "status": r["status"], "theta": t.copy(),
+                             "bounds": (lo, hi), "start": t0.copy(), "from_heuristic": t0 is starts[1]}
+            self._map_done = (key, self.hyp)
         h = self.hyp
         return np.concatenate([h["lenscale_sq"], [h["amp"], h["noise"], h["mean"]]])
 

@@ -45,6 +45,12 @@ def run(ctx, trials=None, on_trial=None, out=None, **over):
     for k in ("sampler", "chains"):   # optional: config.model.sampler ('slice_device': the chain on the device) and its chain count
         if k in cfg:
             mcfg[k] = cfg[k]
+    if "sample" in cfg:   # optional: config.model.sample (False: the point estimate alone, no hyper sampling)
+        mcfg["sample"] = bool(cfg["sample"])
+    if "fit" in cfg:   # optional: config.model.fit ('map': the point estimate by bounded maximum likelihood, no sampling) and its options
+        mcfg["fit"], mcfg["sample"] = cfg["fit"], False
+        if "fit_opt" in cfg:
+            mcfg["fit_opt"] = cfg["fit_opt"]
     if mcfg.get("sampler") == "slice_device":   # (the model is handed over ready-made: what the bot's configure step would set)
         mcfg["prefetch"] = int(cfg["nSamples"])
     model = bot7_amd.models.gp_regressor(mcfg, context=ctx)

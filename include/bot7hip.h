@@ -1194,6 +1194,74 @@ int b7_clf_eval_logfeas(b7_ctx *ctx, int S, const b7_hyp *hyps, double *best_val
                         int *info_out /*S*/);
 int b7_probit_compute(b7_ctx *ctx, const double *z, int64_t n, double *logcdf_out /*n*/, double *ratio_out /*n*/, double *w_out /*n*/);
 
+/* ---- likelihood gradients and the gradient-based point estimate of the GP regressor's hypers.  No counterpart in the reference,
+ * whose only way from data to hypers is the slice sampler.  Added without a change of B7_ABI_VERSION: the change is additive.
+ *
+ * The gradient is taken in the sampler's coordinates (b7_gp_slice_sample's theta):
+ *   theta = [log lenscale_sq_1 .. log lenscale_sq_d, log amp, log noise, mean]                      d + 3 components
+ * and it is the derivative of the value b7_gp_fit_hyp returns in nll_out (one response column).  With Q = inv(K) - alpha alpha',
+ * Kf = K - noise I, w = 1 / lenscale_sq and the radial factor g of the context's kernel (ARD-SE: g = k; Matern-5/2:
+ * g = (5/3) amp (1 + s) exp(-s)):
+ *   d/d log lenscale_sq_k = 1/4 sum_ij Q_ij g_ij (x_ik - x_jk)^2 w_k        d/d log amp = 1/2 sum_ij Q_ij Kf_ij
+ *   d/d log noise = 1/2 noise (tr inv(K) - alpha'alpha)  (exactly 0 at noise == 0)     d/d mean = -sum_i alpha_i
+ * A jitter the schedule added is a constant on the diagonal.  After the chol(I) fallback (jitter_used = -1) every component is NaN.
+ * The same call gives the same bits; they do not depend on how many workgroups run side by side.
+ *
+ *   b7_gp_fit_hyp_grad   b7_gp_fit_hyp, bit for bit in nll_out, jitter_used, info and the fit it leaves, plus grad_out[d + 3]; the
+ *                        gradient is enqueued behind the fit, and the host waits once (a failed plain attempt redoes it after the
+ *                        jitter schedule).  nll_out, jitter_used and info are nullable.
+ *   b7_gp_nll_grad       the gradient of the fit the context already holds.  B7_ERR_STATE without a GP fit of the resident data (also
+ *                        after b7_clf_fit_hyp, a Bayesian-linear fit, b7_gp_append or a nomination: their fits are not b7_gp_fit_hyp's).
+ *                        A change of the candidate grid leaves the fit, and this call, as they were.
+ * Both: B7_ERR_UNSUPPORTED, the case named, for more than one response column or a communicator of more than one rank;
+ * B7_ERR_STATE for a member of a group. */
+int b7_gp_fit_hyp_grad(b7_ctx *ctx, const b7_hyp *hyp, double *nll_out, double *grad_out /*d+3*/, double *jitter_used, int *info);
+int b7_gp_nll_grad(b7_ctx *ctx, double *grad_out /*d+3*/);
+
+/* A projected limited-memory BFGS with box bounds.  Host-only (no context, no GPU), shared by both host languages.
+ *   memory 8, two-loop recursion; a pair (s, y) is skipped where s'y <= 1e-10 |s| |y| (Armijo's test does not ask for positive
+ *   curvature), and a skipped pair empties the memory: the next direction is the projected steepest descent
+ *   iterates are projected onto [lo, hi]; a component at an active bound whose gradient points outward is held for that step, and
+ *   a component with lo == hi is fixed
+ *   Armijo backtracking, t = 1, 1/2, .. at most 20 halvings, c1 = 1e-4; a non-finite value or gradient is a failed trial point
+ *   it stops on a projected-gradient infinity norm <= gtol (default 1e-5 max(1, |f|)), on max_iters, on max_evals, or on a line
+ *   search that finds nothing
+ * Deterministic; it never returns a point worse than x0.  fn(user, n, x, &f, g) fills the value and the n gradient components and
+ * returns 0; a nonzero return stops the run (B7_LBFGSB_STOPPED) at the best point so far.  f_out, g_out, iters_out, evals_out and
+ * status_out are nullable; opts NULL selects every default.  B7_ERR_INVALID: NULL fn, x0, lo, hi or x_out, n outside 1..99, lo > hi,
+ * x0 outside the box or not finite. */
+typedef int (*b7_objective_fn)(void *user, int n, const double *x, double *f_out, double *g_out /*n*/);
+typedef struct {
+  int max_iters; /* [50]  iterations (accepted steps); < 0 selects the default, 0 evaluates x0 and returns it */
+  int max_evals; /* [0]   cap on the calls of fn; <= 0: none of its own */
+  double gtol;   /* [0]   absolute tolerance on the projected gradient; <= 0 selects 1e-5 max(1, |f|) */
+} b7_lbfgsb_opts;
+#define B7_LBFGSB_CONVERGED 1   /* projected gradient within the tolerance */
+#define B7_LBFGSB_MAX_ITERS 2   /* the iteration budget ran out */
+#define B7_LBFGSB_MAX_EVALS 4   /* the evaluation budget ran out */
+#define B7_LBFGSB_LINESEARCH 8  /* a line search found no acceptable point */
+#define B7_LBFGSB_STOPPED 16    /* fn asked to stop */
+#define B7_LBFGSB_BAD_START 32  /* f(x0) or its gradient is not finite: x0 is returned */
+int b7_lbfgsb_default_opts(b7_lbfgsb_opts *out);
+int b7_lbfgsb_minimize(b7_objective_fn fn, void *user, int n, const double *x0, const double *lo /*n*/, const double *hi /*n*/,
+                       const b7_lbfgsb_opts *opts, double *x_out /*n*/, double *f_out, double *g_out /*n*/, int *iters_out,
+                       int *evals_out, int *status_out);
+
+/* The point estimate of the hypers: b7_lbfgsb_minimize over the resident data (b7_gp_set_data) with b7_gp_fit_hyp_grad as fn, from
+ * theta0 inside [lo, hi] (d + 3 entries each, the coordinates above).  A component with lo == hi is fixed (a noiseless model fixes
+ * log noise).  A trial point whose factorisation fell back to chol(I), or whose exp() leaves the hypers' domain, is a failed trial
+ * point.  There is no prior term: with a box this is BOUNDED MAXIMUM LIKELIHOOD, which is the MAP estimate under the flat box prior
+ * of the sampler.  On return the context's fit slot holds the fit at theta_out (b7_gp_predict follows directly), nll_out and
+ * grad_out[d + 3] are that fit's, status_out holds B7_LBFGSB_* bits.  Outputs other than theta_out are nullable.  Refusals as
+ * b7_gp_fit_hyp_grad's; B7_ERR_INVALID as b7_lbfgsb_minimize's.
+ * b7_gp_fit_map_trace_enable(on): keep one record per accepted iterate of the calls that follow, record 0 the start:
+ * theta (d + 3) | nll | the step length that led there.  b7_gp_fit_map_trace: the last call's records (records nullable: the counts
+ * alone), *width = d + 5; B7_ERR_STATE when there is none. */
+int b7_gp_fit_map(b7_ctx *ctx, const double *theta0, const double *lo, const double *hi, const b7_lbfgsb_opts *opts,
+                  double *theta_out /*d+3*/, double *nll_out, double *grad_out /*d+3*/, int *iters_out, int *evals_out, int *status_out);
+int b7_gp_fit_map_trace_enable(b7_ctx *ctx, int on);
+int b7_gp_fit_map_trace(b7_ctx *ctx, double *records, int *n_records, int *width);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 
 /* HIP-event timers on the context's stream (the stream every kernel of this library is launched on). */

@@ -168,6 +168,15 @@ int b7_clf_fit_hyp(b7_ctx *ctx, const b7_hyp *hyp, double *nll_out, int *iters_o
 int b7_clf_mode_get(b7_ctx *ctx, double *f_out , double *a_out , double *W_out );
 int b7_clf_eval_logfeas(b7_ctx *ctx, int S, const b7_hyp *hyps, double *best_val, int64_t *best_idx1, int *iters_out , int *info_out );
 int b7_probit_compute(b7_ctx *ctx, const double *z, int64_t n, double *logcdf_out , double *ratio_out , double *w_out );
+int b7_gp_fit_hyp_grad(b7_ctx *ctx, const b7_hyp *hyp, double *nll_out, double *grad_out , double *jitter_used, int *info);
+int b7_gp_nll_grad(b7_ctx *ctx, double *grad_out );
+typedef int (*b7_objective_fn)(void *user, int n, const double *x, double *f_out, double *g_out );
+typedef struct { int max_iters; int max_evals; double gtol; } b7_lbfgsb_opts;
+int b7_lbfgsb_default_opts(b7_lbfgsb_opts *out);
+int b7_lbfgsb_minimize(b7_objective_fn fn, void *user, int n, const double *x0, const double *lo , const double *hi , const b7_lbfgsb_opts *opts, double *x_out , double *f_out, double *g_out , int *iters_out, int *evals_out, int *status_out);
+int b7_gp_fit_map(b7_ctx *ctx, const double *theta0, const double *lo, const double *hi, const b7_lbfgsb_opts *opts, double *theta_out , double *nll_out, double *grad_out , int *iters_out, int *evals_out, int *status_out);
+int b7_gp_fit_map_trace_enable(b7_ctx *ctx, int on);
+int b7_gp_fit_map_trace(b7_ctx *ctx, double *records, int *n_records, int *width);
 int b7_timer_start(b7_ctx *ctx, int slot);
 int b7_timer_stop(b7_ctx *ctx, int slot);
 int b7_timer_ms(b7_ctx *ctx, int slot, float *ms_out);
@@ -223,6 +232,12 @@ M.EHVI_SMAX = 32
 M.EHVI_SREG = 10
 M.EHVI3_PMAX = 256
 M.TS_FEAS_CMAX = 8
+M.LBFGSB_CONVERGED = 1
+M.LBFGSB_MAX_ITERS = 2
+M.LBFGSB_MAX_EVALS = 4
+M.LBFGSB_LINESEARCH = 8
+M.LBFGSB_STOPPED = 16
+M.LBFGSB_BAD_START = 32
 M.MAX_TIMERS = 16
 -- END generated constants
 

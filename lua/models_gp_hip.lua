@@ -307,8 +307,55 @@ function model:sample_hypers_device(X_obs, Y_obs, state)
   return torch.cat(h.lenscale_sq, torch.DoubleTensor{h.amp, h.noise, h.mean})
 end
 
+-- ---- config.fit = 'map': the point estimate by bounded maximum likelihood (b7_gp_fit_map) ----------------------------------
+-- Mirrors gp_regressor._fit_map of the Python harness: one fit per data set inside model:bounds, config.fit_opt = {max_iters,
+-- gtol}, started from the previous estimate, or from init's heuristic where that has the lower likelihood value on the new data;
+-- the optimiser never returns a point worse than its start.  With the flat box prior this is the MAP estimate.
+function model:fit_map(X_obs, Y_obs)
+  if self.config.fit ~= 'map' then error("bot7hip: config.fit = '" .. tostring(self.config.fit) .. "': only 'map' is built") end
+  if self.config.sample then error("bot7hip: config.fit = 'map' with config.sample = true: use one or the other") end
+  if Y_obs:dim() == 2 and Y_obs:size(2) > 1 then error("bot7hip: config.fit = 'map' with several response columns is not built") end
+  if hip.group then error("bot7hip: config.fit = 'map' on a sharded context (a group) is not built") end
+  self:stage_data(X_obs, Y_obs)
+  if self._map_data ~= self._data or self._map_hyp ~= self.hyp then
+    local d = X_obs:size(2)
+    local n = d + 3
+    local lo, hi = self:bounds(X_obs, Y_obs)
+    local prev = self.hyp
+    local heur = self:init(X_obs, Y_obs)                             -- init's heuristic on these data ...
+    self.hyp = prev                                                  -- ... with the estimate left alone
+    if self.config.noiseless then local tn = to_theta(heur)[d + 2]; lo[d + 2] = tn; hi[d + 2] = tn end   -- lo == hi: fixed
+    local fopt = self.config.fit_opt or {}
+    local opts = ffi.new('b7_lbfgsb_opts', {fopt.max_iters or -1, 0, fopt.gtol or 0.0})
+    local zero = ffi.new('b7_lbfgsb_opts', {0, 0, 0.0})              -- max_iters = 0: the start's own likelihood value, nothing else
+    local function run(t0, o)
+      local th, nll = torch.DoubleTensor(n), ffi.new('double[1]')
+      local it, ev, st = ffi.new('int[1]'), ffi.new('int[1]'), ffi.new('int[1]')
+      hip.check(hip.C.b7_gp_fit_map(hip.ctx, torch.data(t0), torch.data(lo), torch.data(hi), o, torch.data(th), nll, nil, it, ev, st))
+      return {theta = th, nll = nll[0], iters = it[0], evals = ev[0], status = st[0]}
+    end
+    local t_prev, t_heur = to_theta(prev):cmax(lo):cmin(hi), to_theta(heur):cmax(lo):cmin(hi)
+    local t0, evals = t_prev, 0
+    if not t_prev:equal(t_heur) then
+      local p_prev, p_heur = run(t_prev, zero), run(t_heur, zero)
+      evals = p_prev.evals + p_heur.evals
+      if not (p_prev.nll <= p_heur.nll) then t0 = t_heur end
+    end
+    local r = run(t0, opts)
+    evals = evals + r.evals
+    self.hyp = from_theta(r.theta)
+    if self.config.noiseless then self.hyp.noise = 0.0 end
+    self.nEvals = self.nEvals + evals
+    self.last_fit = {nll = r.nll, iters = r.iters, evals = evals, status = r.status}
+    self._map_data, self._map_hyp = self._data, self.hyp
+  end
+  local h = self.hyp
+  return torch.cat(h.lenscale_sq, torch.DoubleTensor{h.amp, h.noise, h.mean})
+end
+
 function model:sample_hypers(X_obs, Y_obs, _, _, state) -- bots/bayesopt.lua:68 (burn-in) and :74 (state = true)
   if not self.hyp then self:init(X_obs, Y_obs) end
+  if self.config.fit ~= nil then return self:fit_map(X_obs, Y_obs) end
   if self.config.sample and self.config.sampler == 'slice_device' then return self:sample_hypers_device(X_obs, Y_obs, state) end
   if self.config.sample and (self.config.chains or 1) > 1 then return self:sample_hypers_chains(X_obs, Y_obs, state) end
   if self.config.sample then
